@@ -18,6 +18,12 @@ evaluations (no collective) is reported beside it.  Both launch forms run the sa
 In the first form the parent never imports torch and never touches a GPU: it starts N fresh rank processes
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in their environment), relays rank 0's JSON line and exits non-zero
 if any rank does.  Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`).  `--full` adds
+everything else the line can carry: predict_f latency / throughput, LML + gradient, the small-N table, the instrumented
+roofline pass, the CPU stand-in, and at N > 1 the parity check against one GPU and the independent evaluations.
+`--dump-outputs DIR` writes what the timed path returned in its last step as DIR/<name>.npy (float64); the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -67,6 +73,23 @@ def plan_attempts(args):
         if a not in ATTEMPTS:
             raise SystemExit("bench.py: unknown attempt %r (known: %s)" % (a, ", ".join(ATTEMPTS)))
     return names
+
+
+DUMP_LIMIT_BYTES = 60 << 20          # (under 64 MB in all, .npy headers included)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy (float64) per array.  Past DUMP_LIMIT_BYTES in all, every array keeps the same
+    fixed, seeded sample of its rows (sorted), so that two runs of the same arguments still compare element for element."""
+    import numpy as np
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES and a.ndim >= 1:
+            keep = int(a.shape[0] * DUMP_LIMIT_BYTES // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _atomic_write(path, text):
@@ -308,7 +331,15 @@ def main():
                          "M inducing points over N data points, the data points sharded over the ranks (gpflowSlim/distributed_sparse.py)")
     ap.add_argument("--cfg5-m", type=int, default=4096)
     ap.add_argument("--cfg5-n", type=int, default=1000000)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beside the headline (predict_f latency / "
+                         "throughput, LML + gradient, small-N table, roofline pass, CPU stand-in; N > 1: parity with one GPU, "
+                         "independent evaluations; cfg5: the SVGP / SGPR bounds).  Off: time the steps and print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     alive.period = max(0.5, min(15.0, args.stall / 3.0))
 
     if args.gpus > 1 and not os.environ.get("GPS_BENCH_CHILD"):
@@ -516,8 +547,16 @@ def main():
     elapsed = max_over_ranks(elapsed)
     ms_per_step = 1e3 * elapsed / args.steps
     value = args.steps / elapsed                     # whole-job evaluations / s (N > 1: ONE evaluation per step)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"lml": [lml]})
+    head = {"metric": metric, "value": round(value, 4), "unit": "evals/s",
+            "n_gpus": dist.get_world_size() if world > 1 else 1, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
+            "scaling": scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": workload, "n": n, "d": d, "n_new": args.n_new, "parallelism": parallelism},
+            "lml_last_step": lml}
 
-    if world > 1:
+    if world > 1 and args.full:
         # parity of the block-column result with the fused single-GPU evaluation of the same hyper-parameters (rank 0's GPU)
         ref1 = model.compute_log_likelihood()
         extra["distributed"]["parity_rel_err_vs_one_gpu"] = abs(lml - ref1) / abs(ref1)
@@ -538,7 +577,7 @@ def main():
             extra["distributed"]["speedup_vs_fused_one_gpu_eval"] = round((1e3 * ti / args.independent_steps) / ms_per_step, 3)
 
     out = None
-    if rank == 0:
+    if rank == 0 and args.full:
         stages = h.last_stage_ms()
         if world > 1:
             set_step(args.steps, False); model.compute_log_likelihood(); stages = h.last_stage_ms()
@@ -772,11 +811,7 @@ def main():
                    "sample_seconds": round(tm["total_s"], 3), "kmat_inplace_seconds": round(kin, 3),
                    "sample_parity_rel_err": abs(got - ref_lml) / abs(ref_lml)}
 
-        out = {"metric": metric, "value": round(value, 4), "unit": "evals/s",
-               "n_gpus": dist.get_world_size() if world > 1 else 1, "steps": args.steps,
-               "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-               "scaling": scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-               "config": {"workload": workload, "n": n, "d": d, "n_new": args.n_new, "parallelism": parallelism},
+        out = dict(head, **{
                "predict_f_latency_ms": {"cold_refactor": round(cold_ms, 2), "warm_resident_factor": round(warm_ms, 2), "n_new": args.n_new,
                                         "statistic": "median of 5 calls", "cold_calls": cold, "warm_calls": warm},
                "predict_f_latency_table": table,
@@ -790,10 +825,14 @@ def main():
                "lml_plus_gradient_ms": round(grad_ms, 2),
                "small_n_latency": small,
                "stage_ms_one_gpu_eval": {k: round(v, 3) for k, v in stages.items()},
-               "lml_last_step": lml,
-               "roofline": roofline, "hbm_bound_kernels": hbm_bound, "cpu_baseline": cpu}
+               "roofline": roofline, "hbm_bound_kernels": hbm_bound, "cpu_baseline": cpu})
         out.update(extra)
         progress("cpu_baseline_done")
+        print(json.dumps(out), flush=True)
+    elif rank == 0:
+        # (roofline / cpu_baseline: keys every line carries, null = not measured; --full measures them)
+        out = dict(head, roofline=None, cpu_baseline=None)
+        out.update(extra)
         print(json.dumps(out), flush=True)
     if world > 1:
         with alive("last_barrier"):          # (ranks != 0 wait here while rank 0 runs its single-GPU tail and the CPU stand-in)
@@ -857,12 +896,21 @@ def run_cfg5(args, rank, world, torch, dist, gpf, np):
         return dt / steps, out
     t_cond, (fm, fv) = timed(lambda: conditional_distributed(X, Z, kern, f, comm=comm, white=True), args.steps, args.warmup)
     progress("conditional_done")
-    mod = gpf.models.SVGP(X, Y, kern, gpf.likelihoods.Gaussian(0.1), Z=Z, q_diag=True, whiten=True)
-    t_svgp, elbo = timed(lambda: svgp_bound_distributed(mod, comm), max(1, args.steps // 2), 1)
-    sg = gpf.models.SGPR(X, Y, kern, Z=Z, obs_var=0.1)
-    t_sgpr, sbound = timed(lambda: sparse_bound_distributed(sg, comm), max(1, args.steps // 2), 1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"fmean": fm, "fvar": fv})
+    mp = ((m + 127) // 128) * 128
+    bounds = {}
+    if args.full:
+        mod = gpf.models.SVGP(X, Y, kern, gpf.likelihoods.Gaussian(0.1), Z=Z, q_diag=True, whiten=True)
+        t_svgp, elbo = timed(lambda: svgp_bound_distributed(mod, comm), max(1, args.steps // 2), 1)
+        sg = gpf.models.SGPR(X, Y, kern, Z=Z, obs_var=0.1)
+        t_sgpr, sbound = timed(lambda: sparse_bound_distributed(sg, comm), max(1, args.steps // 2), 1)
+        bounds = {"svgp_bound": {"ms": round(1e3 * t_svgp, 3), "elbo": elbo, "q_diag": True,
+                                 "collective": "one gathered scalar per rank, added in rank order"},
+                  "sgpr_bound": {"ms": round(1e3 * t_sgpr, 3), "bound": sbound,
+                                 "collective": "one in-place device all-reduce of [A A^T | A err | diag | scalars] (%d doubles) inside gps_sgpr" % (
+                                     mp * mp + mp * 1 + mp + 4)}}
     if rank == 0:
-        mp = ((m + 127) // 128) * 128
         flops = float(mp) * mp * n + mp ** 3 / 3.0                       # trsm M^2 N + Kuu potrf
         print(json.dumps({
             "metric": "conditional() test points/sec, RBF, M=%d inducing points, N=%d points, fp64" % (m, n),
@@ -877,12 +925,7 @@ def run_cfg5(args, rank, world, torch, dist, gpf, np):
                          "peak": FP64_MFMA_PEAK_TFLOPS * world, "unit": "TFLOP/s",
                          "frac": round(flops / t_cond / 1e12 / (FP64_MFMA_PEAK_TFLOPS * world), 4), "traffic": None,
                          "note": "whole-step rate incl. the 8 M N-byte Kuf build, the mean / variance pass and the host gather"},
-            "cpu_baseline": None,
-            "svgp_bound": {"ms": round(1e3 * t_svgp, 3), "elbo": elbo, "q_diag": True,
-                           "collective": "one gathered scalar per rank, added in rank order"},
-            "sgpr_bound": {"ms": round(1e3 * t_sgpr, 3), "bound": sbound,
-                           "collective": "one in-place device all-reduce of [A A^T | A err | diag | scalars] (%d doubles) inside gps_sgpr" % (
-                               mp * mp + mp * 1 + mp + 4)},
+            "cpu_baseline": None, **bounds,
             "checksum": {"fmean_sum": float(fm.sum()), "fvar_min": float(fv.min())}}), flush=True)
     if world > 1:
         dist.barrier()

@@ -23,7 +23,7 @@ def _last_json(text):
 
 def test_bench_one_gpu_line():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--npoints", "4096",
-                        "--cpu-sample-n", "1024", "--num-new-throughput", "1024"], capture_output=True, text=True, timeout=300)
+                        "--cpu-sample-n", "1024", "--num-new-throughput", "1024", "--full"], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     out = _last_json(p.stdout)
     assert COMMON <= set(out), sorted(COMMON - set(out))
@@ -44,13 +44,30 @@ def test_bench_one_gpu_line():
         assert 0 < tab[k]["warm_ms"] <= tab[k]["warm_max_ms"] and tab[k]["first_call_after_new_factor_ms"] > 0 and 0 < tab[k]["trsm_frac_of_peak"] < 1
 
 
+def test_bench_plain_line_dumps_the_last_step(tmp_path):
+    """Without --full the run only times the steps: the headline fields, nothing measured beside them; --dump-outputs
+    writes the last timed step's result, which equals the line's lml_last_step."""
+    import numpy as np
+    dump = tmp_path / "out"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--npoints", "4096",
+                        "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    out = _last_json(p.stdout)
+    assert COMMON <= set(out), sorted(COMMON - set(out))
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and abs(out["value"] - 1e3 / out["ms_per_step"]) <= 1e-3 * out["value"]
+    assert out["roofline"] is None and out["cpu_baseline"] is None and "predict_f_latency_ms" not in out
+    assert sorted(os.listdir(dump)) == ["lml.npy"]
+    lml = np.load(dump / "lml.npy")
+    assert lml.dtype == np.float64 and lml.shape == (1,) and lml[0] == out["lml_last_step"]
+
+
 def test_bench_two_ranks_block_column_gloo():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
            "--backend", "gloo", "--force-device", "0", "--npoints", "4096", "--dist-nb", "256", "--num-new-throughput", "512",
-           "--dist-timeout", "200", "--no-dist-autotune", "--cpu-sample-n", "1024"]
+           "--dist-timeout", "200", "--no-dist-autotune", "--cpu-sample-n", "1024", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
     out = _last_json(p.stdout)
@@ -81,7 +98,7 @@ def test_bench_gpus_flag_starts_the_ranks_itself():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--backend", "gloo",
            "--force-device", "0", "--npoints", "4096", "--dist-nb", "256", "--num-new-throughput", "512", "--dist-timeout", "200",
-           "--no-dist-autotune", "--independent-steps", "1", "--no-cpu-baseline"]
+           "--no-dist-autotune", "--independent-steps", "1", "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=env)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -107,7 +124,7 @@ def test_bench_slow_rank0_tail_does_not_trip_the_stall_supervisor():
     env["GPS_BENCH_TEST_SLOW_TAIL"] = "15"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--backend", "gloo",
            "--force-device", "0", "--npoints", "4096", "--dist-nb", "256", "--num-new-throughput", "256", "--dist-timeout", "200",
-           "--no-dist-autotune", "--independent-steps", "0", "--cpu-sample-n", "512", "--small-n", "", "--stall", "6"]
+           "--no-dist-autotune", "--independent-steps", "0", "--cpu-sample-n", "512", "--small-n", "", "--stall", "6", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=env)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
     out = _last_json(p.stdout)
@@ -123,7 +140,7 @@ def test_bench_two_ranks_autotuned_panel_width():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--backend", "gloo", "--force-device", "0", "--npoints", "4096", "--dist-nb", "256", "--num-new-throughput", "512",
-           "--dist-timeout", "200", "--independent-steps", "0", "--no-roofline", "--no-cpu-baseline"]
+           "--dist-timeout", "200", "--independent-steps", "0", "--no-roofline", "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
     out = _last_json(p.stdout)
@@ -143,7 +160,7 @@ def test_bench_cfg5_side_line_two_ranks():
     outs = []
     for gpus in (1, 2):
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg5", "--gpus", str(gpus), "--steps", "2", "--warmup", "1",
-               "--backend", "gloo", "--force-device", "0", "--cfg5-m", "512", "--cfg5-n", "60000"]
+               "--backend", "gloo", "--force-device", "0", "--cfg5-m", "512", "--cfg5-n", "60000", "--full"]
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=env)
         assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
         outs.append(_last_json(p.stdout))
@@ -167,7 +184,7 @@ def test_bench_two_ranks_native_communicator_stand_in_transport():
     env["GPFLOWSLIM_RCCL_LIB"] = lib
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--comm", "rccl", "--steps", "2", "--warmup", "1", "--backend", "gloo",
            "--force-device", "0", "--npoints", "4096", "--dist-nb", "256", "--num-new-throughput", "512", "--dist-timeout", "200",
-           "--no-dist-autotune", "--independent-steps", "0", "--no-roofline", "--no-cpu-baseline"]
+           "--no-dist-autotune", "--independent-steps", "0", "--no-roofline", "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=env)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
     out = _last_json(p.stdout)
@@ -195,7 +212,7 @@ def _fake_rccl_env():
 
 SMALL = ["--steps", "2", "--warmup", "1", "--backend", "gloo", "--force-device", "0", "--npoints", "4096", "--dist-nb", "256",
          "--num-new-throughput", "512", "--dist-timeout", "200", "--no-dist-autotune", "--independent-steps", "0", "--no-roofline",
-         "--no-cpu-baseline", "--small-n", ""]
+         "--no-cpu-baseline", "--small-n", "", "--full"]
 
 
 @pytest.mark.parametrize("mode", ["error", "stall"])

@@ -24,7 +24,7 @@ if [ "$what" = all ] || [ "$what" = pmc ]; then
   unset GPS_LOOKAHEAD
 fi
 if [ "$what" = all ] || [ "$what" = stats ]; then
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -- python3 $R/bench.py --steps 5 --no-cpu-baseline > $OUT/prof_bench.log 2>&1 || exit 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -- python3 $R/bench.py --steps 5 --no-cpu-baseline --full > $OUT/prof_bench.log 2>&1 || exit 1
   echo "bench stats done"
   # the reference's own workload size (examples/gpr.py: N ~ 455): per-step latency table, kernel statistics
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_small -- python3 $R/tools/small_n.py 512 2048 > $OUT/prof_small.log 2>&1 || exit 1
@@ -54,7 +54,7 @@ if [ "$what" = all ] || [ "$what" = stats ]; then
   (cd $R && for f in 32 64 65; do python3 tools/tp_stamps.py 1048576 0 $f 2>&1 | grep -v amdgpu.ids; done) > $OUT/trsm512_stamps.txt || true
   (cd $R && python3 tools/kmat_ab.py 2>&1 | grep -v amdgpu.ids) > $OUT/kmat_ab.txt || true
   # the bench line without a profiler around it (kernel tracing costs ~3 %)
-  (cd $R && python3 bench.py > $OUT/bench_unprofiled.log 2> $OUT/bench_unprofiled.err) || exit 1
+  (cd $R && python3 bench.py --full > $OUT/bench_unprofiled.log 2> $OUT/bench_unprofiled.err) || exit 1
   echo "un-profiled bench done"
   for c in 2 4 5; do
     rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_cfg$c -- python3 $R/tools/configs.py $c > $OUT/prof_cfg$c.log 2>&1 || exit 1
