@@ -28,6 +28,8 @@ def main():
     ap.add_argument("--comm", default="torch", choices=["torch", "rccl"])
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for tests)")
     ap.add_argument("--force-device", type=int, default=-1, help="testing: put every rank on this GPU")
+    ap.add_argument("--fit", type=int, default=0, metavar="STEPS",
+                    help="then fit the hyper-parameters: STEPS Adam steps on the distributed LML gradient (optimize_distributed)")
     args = ap.parse_args()
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -71,6 +73,13 @@ def main():
         print("ranks %d  N %d  log marginal likelihood %.6f  (%.3f s)  predict_f %d points (%.3f s)  rmse vs noise-free truth %.4f  "
               "device bytes on rank 0: %.2f GB" % (world, args.n, lml, t1 - t0, args.n_test, t2 - t1, rmse,
                                                     gpf.get_handle().device_bytes() / 1e9), flush=True)
+    if args.fit > 0:
+        from gpflowSlim.distributed import optimize_distributed
+        show = (lambda it, f: print("step %d  objective %.6f" % (it, f), flush=True)) if rank == 0 else None
+        optimize_distributed(model, comm, nb=args.nb, max_iter=args.fit, method="adam", learning_rate=0.05, callback=show)
+        final = -gpr_lml_distributed(model, comm, nb=args.nb, lookahead=2)
+        if rank == 0:
+            print("fit: %d Adam steps over %d ranks  objective %.6f -> %.6f" % (args.fit, world, -lml, final), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -1,0 +1,243 @@
+// C ABI of libgpflowslim_hip.so (include/gpflowslim_hip.h): the LML gradient over the block-column distributed factor.
+//
+//   d LML / d theta = 1/2 sum_ij W_ij d K_ij / d theta ,  W = A A^T - r K_y^-1 ,  A = K_y^-1 (Y - m)      (gps_gpr_lml_grad)
+//
+// The single-GPU path holds K_y^-1 as a dense N x N buffer.  Here every rank forms only the block columns of K_y^-1 it owns
+// (c % P == rank, the columns of the partitioned factor it holds) and contracts only those; the ranks then add their slot
+// sums.  The owned columns come out of two more streams of the factor's panels, in the message format of gps_dist_solve_pack
+// (L[j nb:, j], its 128-block inverses) -- both kept TRANSPOSED, one row per owned column, so that each step is the row-major
+// NT product and triangular solve the rest of the library is built from (gemm_f64.hip, blocked.hpp):
+//
+//   forward  (j ascending):   Z^T = E_own^T L^-T      Z^T_j <- Z^T_j L_jj^-T ;  Z^T_{>j} -= Z^T_j L[>j, j]^T
+//                             (= gps_dist_solve_apply with the identity columns as right-hand sides; alpha_j^T is picked
+//                             up from the augmented rows as the panel passes)
+//   backward (j descending):  X^T L = Z^T             X^T_j <- (Z^T_j - X^T_{>j} L[>j, j]) L_jj^-1
+//                             on the transposed panel; the same step takes A^T = alpha^T L^-1 along (rows 0..127)
+//
+// Only the owned columns c <= j take part in step j: they are the first  k_j = #{owned c <= j}  local blocks, contiguous
+// rows of Z^T.  Entries of block column c above row c nb are never touched (zero in L^-1 E_c; not needed of K_y^-1 by
+// symmetry), so each stream costs ~ N^3 / (3P) flop per rank.  After the backward stream row lj of X^T holds column
+// global(lj) of K_y^-1 for rows >= its block start: the gradient kernels read it in their block-cyclic column mode
+// (GradCyclic, kinv_t = 1).
+//
+// Buffer dDistZ: [128 + ncl nb][np]; rows 0..127: alpha^T then A^T (r real rows), rows 128..: Z^T then X^T.
+// Buffer dDistPT: [nb][np], the transposed panel of the current backward step.
+#include "gps_ops.hpp"
+
+// identity blocks (c, c) of the owned columns: Z^T[128 + lc nb + q][c nb + q] = 1, c = lc P + rank
+__global__ __launch_bounds__(256) void dist_grad_eye_kernel(double* __restrict__ Z, i64 ldz, i64 ncols, i64 nb, int P, int rank) {
+  const i64 idx = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= ncols) return;
+  const i64 lc = idx / nb, q = idx % nb;
+  Z[(GPS_TILE + idx) * ldz + (lc * P + rank) * nb + q] = 1.0;
+}
+
+static inline i64 dg_owned_upto(gps_handle_t h, i64 j) {          // owned block columns c <= j
+  if (j < h->dist_rank) return 0;
+  const i64 k = (j - h->dist_rank) / h->dist_P + 1;
+  return k < h->dist_ncl ? k : h->dist_ncl;
+}
+
+#define DG_CHECK(h, j, buf)                                                                                        \
+  if (!h || !h->dist_grad_ready || !h->dist_have_part_factor || h->dist_nb <= 0 || j < 0 || j * h->dist_nb >= h->dist_np) \
+    return gps_fail(h, GPS_ERR_STATE, "gps_dist_grad_*: bad panel index or gps_dist_grad_begin not called");        \
+  if (buf < 0 || buf >= h->dist_ncomm || !h->dist_comm[buf])                                                       \
+    return gps_fail(h, GPS_ERR_STATE, "gps_dist_set_comm has not been called");                                     \
+  GPS_HIP(h, hipSetDevice(h->device));                                                                             \
+  h->refine_now = h->factor_refine;                                                                                \
+  const i64 np = h->dist_np, nb = h->dist_nb;                                                                      \
+  const i64 rows = np + GPS_TILE - j * nb, nbb = nb / GPS_TILE;                                                    \
+  const i64 below = np - (j + 1) * nb;                                                                             \
+  double* const msg = h->dist_comm[buf];                                                                           \
+  double* const Z = h->dDistZ.d();                                                                                 \
+  HipOps ops{h, msg + rows * nb, msg + rows * nb + nbb * GPS_TILE * GPS_TILE, (int*)h->dInfo.p};                     \
+  Blocked<HipOps> bl(ops);
+
+extern "C" int gps_dist_grad_begin(gps_handle_t h) {
+  if (!h) return GPS_ERR_ARG;
+  if (!h->dist_have_part_factor || !h->dist_part || h->dist_nb <= 0)
+    return gps_fail(h, GPS_ERR_STATE, "gps_dist_grad_begin: no partitioned factor (run the distributed factorisation first)");
+  GPS_HIP(h, hipSetDevice(h->device));
+  const i64 np = h->dist_np, nb = h->dist_nb, ncols = h->dist_ncl * nb;
+  GPS_HIP(h, h->dDistZ.ensure((size_t)(GPS_TILE + ncols) * np * 8));
+  GPS_HIP(h, h->dDistPT.ensure((size_t)nb * np * 8));
+  GPS_HIP(h, hipMemsetAsync(h->dDistZ.p, 0, (size_t)(GPS_TILE + ncols) * np * 8, h->stream));
+  if (ncols > 0) {
+    LaunchScope ls(h, KC_OTHER, 0.0, 8.0 * (double)ncols);
+    hipLaunchKernelGGL(dist_grad_eye_kernel, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, h->stream, h->dDistZ.d(), np, ncols,
+                       nb, h->dist_P, h->dist_rank);
+    GPS_HIP(h, hipGetLastError());
+  }
+  h->dist_grad_ready = true;
+  return GPS_OK;
+}
+
+// forward stream, panel j (any comm slot; the message of gps_dist_solve_pack)
+extern "C" int gps_dist_grad_fwd_apply(gps_handle_t h, int64_t j, int buf) {
+  DG_CHECK(h, j, buf)
+  // alpha_j^T: the augmented rows of the panel
+  if (h->dist_r > 0)
+    GPS_HIP(h, hipMemcpy2DAsync(Z + j * nb, (size_t)np * 8, msg + (rows - GPS_TILE) * nb, (size_t)nb * 8, (size_t)nb * 8,
+                                (size_t)h->dist_r, hipMemcpyDeviceToDevice, h->stream));
+  const i64 m = dg_owned_upto(h, j) * nb;
+  if (m == 0) return GPS_OK;
+  double* Bj = Z + GPS_TILE * np + j * nb;                       // [m, nb] block column j of Z^T, ld np
+  int rc = bl.trsm_rec(msg, nb, nb, 0, Bj, np, m);               // Z^T_j <- Z^T_j L_jj^-T
+  if (rc) return rc;
+  if (below > 0) rc = gps_launch_gemm_nt(h, 0, 0, m, below, nb, Bj, np, msg + nb * nb, nb, Bj + nb, np);   // Z^T_{>j} -= Z^T_j L[>j, j]^T
+  return rc;
+}
+
+// backward stream, panel j (j descending), in place over Z^T; rows 0..127 carry alpha^T -> A^T
+extern "C" int gps_dist_grad_bwd_apply(gps_handle_t h, int64_t j, int buf) {
+  DG_CHECK(h, j, buf)
+  const i64 m = GPS_TILE + dg_owned_upto(h, j) * nb;
+  double* PT = h->dDistPT.d();
+  // U = [L_jj ; L[>j, j]]^T  [nb, np - j nb]: L_jj^T (the upper factor trsm_rn_rec takes) then L[>j, j]^T (the B operand)
+  int rc = gps_launch_transpose(h, msg, nb, np - j * nb, nb, PT, np);
+  if (rc) return rc;
+  double* Xj = Z + j * nb;
+  if (below > 0) {
+    rc = gps_launch_gemm_nt(h, 0, 0, m, nb, below, Xj + nb, np, PT + nb, np, Xj, np);     // X^T_j -= X^T_{>j} L[>j, j]
+    if (rc) return rc;
+  }
+  return bl.trsm_rn_rec(PT, np, nb, 0, Xj, np, m);              // X^T_j <- X^T_j L_jj^-1
+}
+
+// this rank's raw slot sums (no lengthscale division: gps_dist_grad_fold adds the ranks' sums first) and K_y^-1 resid
+//   sums_out[0 .. n_slots)  the slots,  sums_out[n_slots]  d / d noise variance ;  kinv_resid_out [n, r] (may be NULL)
+extern "C" int gps_dist_grad_local(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double* sums_out, int cap,
+                                   int* n_slots_out, double* kinv_resid_out) {
+  if (!h || !prog || !sums_out) return gps_fail(h, GPS_ERR_ARG, "gps_dist_grad_local: bad argument");
+  // (the partitioned factor the streams ran on must still be there: gpr_set_data and every other factorisation drop it)
+  if (!h->dist_grad_ready || !h->dist_have_part_factor)
+    return gps_fail(h, GPS_ERR_STATE, "gps_dist_grad_local: gps_dist_grad_begin has not been called on the current partitioned factor");
+  GPS_HIP(h, hipSetDevice(h->device));
+  int ns = 0;
+  int rc = gps_grad_slots(h, prog, n_nodes, &ns);
+  if (rc) return rc;
+  if (n_slots_out) *n_slots_out = ns;
+  if (ns + 1 > cap) return gps_fail(h, GPS_ERR_ARG, "gps_dist_grad_local: sums_out too small (n_slots + 1)");
+  const i64 n = h->n, np = h->dist_np, nb = h->dist_nb, r = h->dist_r;
+  const double* At = h->dDistZ.d();                              // [r][np]
+  const double* Kt = h->dDistZ.d() + GPS_TILE * np;              // [ncl nb][np]
+  if (kinv_resid_out && r > 0) {
+    GPS_HIP(h, h->dTmp2.ensure((size_t)n * r * 8));
+    rc = gps_launch_transpose(h, At, np, r, n, h->dTmp2.d(), r);
+    if (rc) return rc;
+    GPS_HIP(h, hipMemcpyAsync(kinv_resid_out, h->dTmp2.p, (size_t)n * r * 8, hipMemcpyDeviceToHost, h->stream));
+    GPS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  GradCyclic cyc;
+  cyc.P = h->dist_P; cyc.rank = h->dist_rank; cyc.nb = nb; cyc.ncols = h->dist_ncl * nb; cyc.kinv_t = 1;
+  if (!gps_grad_is_simple(prog, n_nodes))
+    return gps_launch_grad_general_cyclic(h, prog, n_nodes, h->dX.d(), n, h->d_all, np, Kt, np, At, np, r, cyc, sums_out, sums_out + ns);
+  GradPost post;
+  GPS_HIP(h, h->dGradSums.ensure((size_t)GPS_GRAD_SUMS * 8));
+  rc = gps_grad_prepare(h, prog, n_nodes, h->dX.d(), n, h->d_all, np, &post);
+  if (rc) return rc;
+  rc = gps_grad_run(h, post, n, np, Kt, np, At, np, r, h->dGradSums.d(), &cyc);
+  if (rc) return rc;
+  double sums[GPS_GRAD_SUMS];
+  GPS_HIP(h, hipMemcpyAsync(sums, h->dGradSums.p, sizeof(sums), hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipStreamSynchronize(h->stream));
+  for (int s = 0; s < ns; ++s) sums_out[s] = sums[s];
+  sums_out[ns] = sums[GPS_GRAD_SUMS - 1];
+  return GPS_OK;
+}
+
+// P ranks' gps_dist_grad_local sums (rank p at rank_sums + p * stride) -> gradient slots and d / d noise variance: added in
+// rank order, then the lengthscale division of gps_grad_finish once.  Host only; the same input gives the same bits anywhere.
+extern "C" int gps_dist_grad_fold(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* rank_sums, int P,
+                                  int64_t stride, double* grad_slots, int n_slots_cap, int* n_slots_out, double* grad_noise) {
+  if (!h || !prog || !rank_sums || P <= 0 || !grad_slots || !grad_noise) return gps_fail(h, GPS_ERR_ARG, "gps_dist_grad_fold: bad argument");
+  int ns = 0;
+  int rc = gps_grad_slots(h, prog, n_nodes, &ns);
+  if (rc) return rc;
+  if (n_slots_out) *n_slots_out = ns;
+  if (ns > n_slots_cap || stride < ns + 1) return gps_fail(h, GPS_ERR_ARG, "gps_dist_grad_fold: grad_slots too small or stride < n_slots + 1");
+  std::vector<double> ls;
+  rc = gps_grad_ls_of_slot(h, prog, n_nodes, h->d_all, &ls);
+  if (rc) return rc;
+  if ((int)ls.size() != ns) return gps_fail(h, GPS_ERR_STATE, "gps_dist_grad_fold: slot layout mismatch");
+  for (int s = 0; s <= ns; ++s) {
+    double tot = 0.0;
+    for (int p = 0; p < P; ++p) tot += rank_sums[(i64)p * stride + s];
+    if (s == ns) *grad_noise = tot;
+    else grad_slots[s] = ls[s] > 0.0 ? tot / ls[s] : tot;
+  }
+  return GPS_OK;
+}
+
+// ---- the whole distributed gradient driven from here (native communicator; no host language per panel) --------------------
+// gpflowSlim/distributed.py::grad_stream_schedule, statement for statement: 2 n_panels steps k (forward: panel k; backward:
+// panel 2 n_panels - 1 - k), two comm slots alternating, the exchange of step k + 1 in flight while step k is applied (the
+// pack of step k + 1 is stream-ordered after apply(k - 1), the last reader of its slot).
+static int dg_streams(gps_handle_t h, int exchange_mode) {
+  const int P = h->comm_world, rank = h->comm_rank;
+  const i64 n_panels = h->dist_np / h->dist_nb;
+  void* bufs[2] = {h->dDistComm[0].p, h->dDistComm[1].p};
+  int rc = gps_dist_set_comm_bufs(h, bufs, 2);
+  if (rc) return rc;
+  rc = gps_dist_grad_begin(h);
+  if (rc) return rc;
+  auto panel = [&](i64 k) -> i64 { return k < n_panels ? k : 2 * n_panels - 1 - k; };
+  auto send = [&](i64 k) -> int {
+    const i64 j = panel(k);
+    const int buf = (int)(k % 2);
+    if (rank == (int)(j % P)) { int rcc = gps_dist_solve_pack(h, j, buf); if (rcc) return rcc; }
+    int64_t n = 0;
+    int rcc = gps_dist_msg_doubles(h, j, &n);
+    if (rcc) return rcc;
+    return gps_comm_exchange(h, bufs[buf], ((n + P - 1) / P) * P, (int)(j % P), exchange_mode, (int)(k % 8));
+  };
+  rc = send(0);
+  for (i64 k = 0; k < 2 * n_panels && !rc; ++k) {
+    rc = gps_comm_wait(h, (int)(k % 8));
+    if (!rc && k + 1 < 2 * n_panels) rc = send(k + 1);
+    if (!rc) rc = k < n_panels ? gps_dist_grad_fwd_apply(h, panel(k), (int)(k % 2)) : gps_dist_grad_bwd_apply(h, panel(k), (int)(k % 2));
+  }
+  if (rc) { (void)hipStreamSynchronize(h->stream); if (h->comm_stream) (void)hipStreamSynchronize(h->comm_stream); }
+  return rc;
+}
+
+extern "C" int gps_dist_lml_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double noise_var, const double* resid,
+                                 int64_t r, int64_t nb, int lookahead, int exchange_mode, double* lml, double* grad_slots,
+                                 int n_slots_cap, int* n_slots_out, double* grad_noise, double* kinv_resid, int* info) {
+  if (!h || !prog || !lml || !grad_slots || !grad_noise || r <= 0) return gps_fail(h, GPS_ERR_ARG, "gps_dist_lml_grad: bad argument");
+  if (!h->comm) return gps_fail(h, GPS_ERR_STATE, "gps_dist_lml_grad: the handle has no communicator (gps_comm_init)");
+  if (!h->dist_partitioned) return gps_fail(h, GPS_ERR_STATE, "gps_dist_lml_grad: needs partitioned storage (option dist_partitioned = 1)");
+  int ns = 0;
+  int rc = gps_grad_slots(h, prog, n_nodes, &ns);
+  if (rc) return rc;
+  if (n_slots_out) *n_slots_out = ns;
+  if (ns > n_slots_cap) return gps_fail(h, GPS_ERR_ARG, "gps_dist_lml_grad: grad_slots too small");
+  int linfo = 0;
+  rc = gps_dist_lml(h, prog, n_nodes, noise_var, resid, r, nb, lookahead, exchange_mode, lml, &linfo);
+  if (info) *info = linfo;
+  if (rc || linfo) return rc;            // not positive definite (on every rank alike): outputs undefined
+  rc = dg_streams(h, exchange_mode);
+  if (rc) return rc;
+  const int P = h->comm_world, rank = h->comm_rank;
+  const i64 n = h->n, w = ns + 1;
+  std::vector<double> loc((size_t)w), kr((size_t)n * r);
+  rc = gps_dist_grad_local(h, prog, n_nodes, loc.data(), (int)w, nullptr, kr.data());
+  if (rc) return rc;
+  // gather: every rank writes its sums into row `rank` of a zeroed [P][w] block (rank 0 also K_y^-1 resid behind it); one
+  // all-reduce adds x + 0 + ... = x exactly, so every rank folds the same bits in the same order
+  const i64 tot = (i64)P * w + n * r;
+  GPS_HIP(h, h->dDistPT.ensure((size_t)tot * 8));
+  double* g = h->dDistPT.d();
+  GPS_HIP(h, hipMemsetAsync(g, 0, (size_t)tot * 8, h->stream));
+  GPS_HIP(h, hipMemcpyAsync(g + (i64)rank * w, loc.data(), (size_t)w * 8, hipMemcpyHostToDevice, h->stream));
+  if (rank == 0) GPS_HIP(h, hipMemcpyAsync(g + (i64)P * w, kr.data(), (size_t)n * r * 8, hipMemcpyHostToDevice, h->stream));
+  rc = gps_comm_allreduce(h, g, tot);
+  if (rc) return rc;
+  std::vector<double> all((size_t)tot);
+  GPS_HIP(h, hipMemcpyAsync(all.data(), g, (size_t)tot * 8, hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipStreamSynchronize(h->stream));
+  rc = gps_dist_grad_fold(h, prog, n_nodes, all.data(), P, w, grad_slots, n_slots_cap, nullptr, grad_noise);
+  if (rc) return rc;
+  if (kinv_resid) memcpy(kinv_resid, all.data() + (i64)P * w, (size_t)n * r * 8);
+  return GPS_OK;
+}

@@ -227,6 +227,11 @@ struct gps_handle_s {
   std::vector<hipEvent_t> dist_events; size_t dist_event_next = 0;
   DevBuf dDistScal;                 // [n_panels][4] per-panel sum log L_ii, sum alpha^2, info
   DevBuf dDistComm[3];              // comm buffers of gps_dist_lml (the all-native driver; other callers bring their own)
+  // distributed gradient (dist_grad.hip): [128 + ncl * nb][np] rows 0..127 = alpha^T then A^T = (K_y^-1 resid)^T (r real rows),
+  // then one row per owned column of (L^-1 E_own)^T, in place (L^-T L^-1 E_own)^T = the owned columns of K_y^-1
+  DevBuf dDistZ;
+  DevBuf dDistPT;                   // [nb][np] the transposed panel of the backward stream
+  bool dist_grad_ready = false;     // gps_dist_grad_begin ran on the current partitioned factor
 
   DevBuf dA;        // [r][npad]  K_y^-1 (Y - m)                         (gradient path)
   DevBuf dY;        // [npad, npad]  L^-T                                 (gradient path)
@@ -436,9 +441,16 @@ int gps_launch_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, co
 #define GPS_HRES_BYTES (192 * 1024)
 struct GradPost { int n_slots = 0, nfeat = 0; std::vector<double> ls_of_slot; std::vector<char> blob; };   // blob: the device program (grad.hip)
 int gps_grad_prepare(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n, i64 d_all, i64 npad, GradPost* post);
+// Block-cyclic column mode of the gradient contraction (the distributed gradient, dist_grad.hip): the kernel walks the `ncols`
+// LOCAL columns lj of this rank; global column = ((lj / nb) * P + rank) * nb + lj % nb.  kinv_t: K_y^-1 is read transposed
+// (Kinv[lj * ldk + i], one row per local column).  P = 1, rank = 0, ncols = npad, kinv_t = 0 is the plain mode.
+struct GradCyclic { int P = 1, rank = 0; i64 nb = 0, ncols = 0; int kinv_t = 0; };
 int gps_grad_run(gps_handle_t h, const GradPost& post, i64 n, i64 npad, const double* dKinv, i64 ldk, const double* dA, i64 lda, i64 r,
-                 double* d_sums);
+                 double* d_sums, const GradCyclic* cyc = nullptr);
 bool gps_grad_is_simple(const gps_kern_node_t* prog, int n_nodes);
+// the lengthscale that divides each slot's raw sum (0: none): the slot layout of whichever kernel takes the program
+int gps_grad_ls_of_slot(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, std::vector<double>* ls);
+int gps_grad_general_ls_of_slot(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, std::vector<double>* ls);
 int gps_grad_enqueue(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n,
                      i64 d_all, i64 npad, const double* dKinv, i64 ldk, const double* dA, i64 lda, i64 r,
                      double* d_sums, GradPost* post);
@@ -448,6 +460,10 @@ int gps_grad_general_slots(gps_handle_t h, const gps_kern_node_t* prog, int n_no
 int gps_launch_grad_general(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n,
                             i64 d_all, i64 npad, const double* dKinv, i64 ldk, const double* dA, i64 lda, i64 r,
                             double* grad_slots_host, double* grad_noise_host);
+// raw per-slot sums (no lengthscale division: the caller adds several ranks' sums first) in block-cyclic column mode
+int gps_launch_grad_general_cyclic(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n,
+                                   i64 d_all, i64 npad, const double* dKinv, i64 ldk, const double* dA, i64 lda, i64 r,
+                                   const GradCyclic& cyc, double* raw_slots_host, double* raw_noise_host);
 int gps_launch_kmat_input_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dXr, i64 nr,
                               const double* dXc, i64 nc, i64 d_all, const double* Wd, i64 ldw, double factor,
                               double* grad_X_host);

@@ -78,7 +78,7 @@ extern "C" int gps_dist_begin(gps_handle_t h, const gps_kern_node_t* prog, int n
   const i64 n = h->n;
   const i64 np = ((n + nb - 1) / nb) * nb;
   const i64 nblk = np / nb;
-  h->have_factor = false; h->factor_gen++; h->dist_have_part_factor = false;
+  h->have_factor = false; h->factor_gen++; h->dist_have_part_factor = false; h->dist_grad_ready = false;
   h->npad = np; h->dist_np = np; h->dist_nb = nb; h->dist_P = nparts; h->dist_rank = part; h->dist_r = r;
   h->dist_part = h->dist_partitioned != 0;
   h->dist_ncl = part < nblk ? (nblk - 1 - part) / nparts + 1 : 0;            // owned block columns
@@ -551,7 +551,7 @@ extern "C" int gps_device_bytes(gps_handle_t h, int64_t* bytes) {
                     &h->dKinv, &h->dNkn, &h->dS1, &h->dS2, &h->dS3, &h->dS4, &h->dGemvWs, &h->dGemvCnt, &h->dGemmWs, &h->dGemmCnt,
                     &h->dDistScal, &h->dGradSums, &h->dSmallOut, &h->dFeatG, &h->dG1, &h->dG2, &h->dG3, &h->dG4, &h->dWave, &h->dInfo, &h->dScal, &h->dWaveCtl, &h->dLaFlags,
                     &h->dBlkCond, &h->dStage, &h->dWbig, &h->dWtbig, &h->dBigT, &h->dB2, &h->dSmallSync,
-                    &h->dDistComm[0], &h->dDistComm[1], &h->dDistComm[2]};
+                    &h->dDistComm[0], &h->dDistComm[1], &h->dDistComm[2], &h->dDistZ, &h->dDistPT};
   int64_t tot = 0;
   for (DevBuf* b : bufs) tot += (int64_t)b->cap;
   *bytes = tot;

@@ -38,7 +38,14 @@ struct GArgs {
   i64 n, npad;
   double* partial;                      // [gridDim.x][G_MAXSLOT + 1]  (last = noise)
   int tiles_r, tiles_c;
+  // block-cyclic column mode (GradCyclic, gps_common.hpp): cyc_nb == 0 is the plain mode (local column = global column)
+  int cyc_P, cyc_rank; i64 cyc_nb; int kinv_t;
 };
+
+// global column of local column lj (the tile's GT_C columns never straddle a block: GT_C divides nb)
+__device__ __forceinline__ i64 grad_global_col(i64 lj, int P, int rank, i64 nb) {
+  return nb > 0 ? ((lj / nb) * P + rank) * nb + lj % nb : lj;
+}
 
 __device__ __forceinline__ double wave_sum64(double v) {
 #pragma unroll
@@ -119,18 +126,19 @@ __global__ __launch_bounds__(256) void grad_kernel(GArgs a, GProg P) {
   const i64 ntiles = (i64)a.tiles_r * a.tiles_c;
   for (i64 t = blockIdx.x; t < ntiles; t += gridDim.x) {
     const int ti = (int)(t / a.tiles_c), tj = (int)(t % a.tiles_c);
-    const i64 gi0 = (i64)ti * GT_R, gj0 = (i64)tj * GT_C;
+    const i64 lj0 = (i64)tj * GT_C;
+    const i64 gi0 = (i64)ti * GT_R, gj0 = grad_global_col(lj0, a.cyc_P, a.cyc_rank, a.cyc_nb);
     if (gj0 > gi0 + GT_R - 1) continue;                     // strictly above the diagonal
     // ---- weights c_e * W_e for the thread's 8 elements
     double w[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const i64 i = gi0 + ty * 4 + (e >> 1), j = gj0 + tx * 2 + (e & 1);
+      const i64 i = gi0 + ty * 4 + (e >> 1), j = gj0 + tx * 2 + (e & 1), lj = lj0 + tx * 2 + (e & 1);
       double val = 0.0;
       if (i < a.n && j <= i) {
         double s = 0.0;
         for (int q = 0; q < a.r; ++q) s += a.A[(i64)q * a.lda + i] * a.A[(i64)q * a.lda + j];
-        val = s - (double)a.r * a.Kinv[i * a.ldk + j];
+        val = s - (double)a.r * (a.kinv_t ? a.Kinv[lj * a.ldk + i] : a.Kinv[i * a.ldk + lj]);
         if (i == j) val *= 0.5;
       }
       w[e] = val;
@@ -397,11 +405,12 @@ bool gps_grad_is_simple(const gps_kern_node_t* prog, int n_nodes) { return !grad
 // The gradient in two halves for callers that want the features early (gps_gpr_lml_grad at small N launches gps_grad_prepare in
 // front of the factorisation, where it is off the chain): prepare = program analysis + feature launch (into dFeatG), run = the
 // tile sums and their reduction into d_sums[GPS_GRAD_SUMS] (slot s at [s], noise at [G_MAXSLOT]).  No synchronisation in either.
-int gps_grad_prepare(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n, i64 d_all, i64 npad, GradPost* post) {
+// program analysis only (host): the device program, the feature table and the slot layout (post->ls_of_slot)
+static int grad_analyse(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, GradPost* post, std::vector<GPrepFeat>& feats) {
   static_assert(GPS_GRAD_SUMS == G_MAXSLOT + 1, "GPS_GRAD_SUMS");
   post->blob.resize(sizeof(GProg));
   GProg& P = *reinterpret_cast<GProg*>(post->blob.data());
-  std::vector<GPrepFeat> feats;
+  feats.clear();
   std::vector<double>& ls_of_slot = post->ls_of_slot;          // lengthscale that divides a per-dim slot
   ls_of_slot.clear();
   P.n_nodes = n_nodes; P.n_prims = 0; P.n_slots = 0;
@@ -443,7 +452,15 @@ int gps_grad_prepare(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, c
   }
   if (depth != 1) return gps_fail(h, GPS_ERR_ARG, "gradient: program must leave exactly one value");
   if (P.n_slots > G_MAXSLOT) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: too many parameters");
+  post->n_slots = P.n_slots;
+  return GPS_OK;
+}
 
+int gps_grad_prepare(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n, i64 d_all, i64 npad, GradPost* post) {
+  std::vector<GPrepFeat> feats;
+  int rc = grad_analyse(h, prog, n_nodes, d_all, post, feats);
+  if (rc) return rc;
+  const GProg& P = *reinterpret_cast<const GProg*>(post->blob.data());
   const int nfeat = (int)feats.size();
   if (nfeat > 0) {
     GPS_HIP(h, h->dFeatG.ensure((size_t)nfeat * npad * 8));
@@ -466,20 +483,43 @@ int gps_grad_prepare(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, c
   return GPS_OK;
 }
 
+// the lengthscale that divides each slot's raw sum (0: none), from the same analysis the kernels run on
+int gps_grad_ls_of_slot(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, std::vector<double>* ls) {
+  if (grad_needs_general(prog, n_nodes)) return gps_grad_general_ls_of_slot(h, prog, n_nodes, d_all, ls);
+  GradPost post;
+  std::vector<GPrepFeat> feats;
+  int rc = grad_analyse(h, prog, n_nodes, d_all, &post, feats);
+  if (rc) return rc;
+  *ls = post.ls_of_slot;
+  return GPS_OK;
+}
+
 int gps_grad_run(gps_handle_t h, const GradPost& post, i64 n, i64 npad, const double* dKinv, i64 ldk, const double* dA, i64 lda, i64 r,
-                 double* d_sums) {
+                 double* d_sums, const GradCyclic* cyc) {
   const GProg& P = *reinterpret_cast<const GProg*>(post.blob.data());
   const int nfeat = post.nfeat;
   GArgs a;
   a.Ft = h->dFeatG.d(); a.ldf = npad; a.Kinv = dKinv; a.ldk = ldk; a.A = dA; a.lda = lda; a.r = (int)r;
   a.n = n; a.npad = npad; a.tiles_r = (int)(npad / GT_R); a.tiles_c = (int)(npad / GT_C);
+  a.cyc_P = 1; a.cyc_rank = 0; a.cyc_nb = 0; a.kinv_t = 0;
+  if (cyc) {
+    if (cyc->nb <= 0 || cyc->nb % GT_C || cyc->ncols % cyc->nb || cyc->P < 1 || cyc->rank < 0 || cyc->rank >= cyc->P)
+      return gps_fail(h, GPS_ERR_ARG, "gradient: bad block-cyclic column mode");
+    a.cyc_P = cyc->P; a.cyc_rank = cyc->rank; a.cyc_nb = cyc->nb; a.kinv_t = cyc->kinv_t;
+    a.tiles_c = (int)(cyc->ncols / GT_C);
+    if (a.tiles_c == 0) {                                   // a rank without columns: its sums are zero
+      GPS_HIP(h, hipMemsetAsync(d_sums, 0, (size_t)GPS_GRAD_SUMS * 8, h->stream));
+      return GPS_OK;
+    }
+  }
   const i64 ntiles = (i64)a.tiles_r * a.tiles_c;
   const int nblocks = (int)(ntiles < GRAD_BLOCKS ? ntiles : GRAD_BLOCKS);
   const size_t pbytes = (size_t)nblocks * (G_MAXSLOT + 1) * 8;
   GPS_HIP(h, h->dTmp2.ensure(pbytes));
   a.partial = h->dTmp2.d();
   {
-    LaunchScope ls(h, KC_REDUCE, 0.5 * (double)npad * npad * (60.0 + 4.0 * nfeat), 4.0 * (double)npad * npad);
+    const double cols = (double)a.tiles_c * GT_C;
+    LaunchScope ls(h, KC_REDUCE, 0.5 * (double)npad * cols * (60.0 + 4.0 * nfeat), 4.0 * (double)npad * cols);
     hipLaunchKernelGGL(grad_kernel, dim3(nblocks), dim3(256), 0, h->stream, a, P);
     GPS_HIP(h, hipGetLastError());
   }

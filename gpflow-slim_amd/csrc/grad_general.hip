@@ -49,6 +49,8 @@ struct GGArgs {
   // same_points: rows and columns index the same point set (K(Z, Z)): White contributes on i == j
   int rect, tiles_c, same_points;
   const double* Wd; i64 ldw; i64 nr, nc;
+  // block-cyclic column mode of the likelihood gradient (GradCyclic, gps_common.hpp); cyc_nb == 0: plain
+  int cyc_P, cyc_rank; i64 cyc_nb; int kinv_t;
 };
 
 __device__ __forceinline__ double gg_wave_sum(double v) {
@@ -304,26 +306,28 @@ __global__ __launch_bounds__(256) void gg_kernel(GGArgs a, GGProg P) {
   const i64 ntiles = (i64)a.tiles * a.tiles_c;
   for (i64 t = blockIdx.x; t < ntiles; t += gridDim.x) {
     const int ti = (int)(t / a.tiles_c), tj = (int)(t % a.tiles_c);
-    if (!a.rect && tj > ti) continue;
-    const i64 gi0 = (i64)ti * GG_T, gj0 = (i64)tj * GG_T;
+    // (local column tile -> global column: the 32 columns of a tile never straddle a block, GG_T divides nb)
+    const i64 lj0 = (i64)tj * GG_T;
+    const i64 gi0 = (i64)ti * GG_T, gj0 = a.cyc_nb > 0 ? ((lj0 / a.cyc_nb) * a.cyc_P + a.cyc_rank) * a.cyc_nb + lj0 % a.cyc_nb : lj0;
+    if (!a.rect && gj0 > gi0) continue;
     // ---- weights c_e W_e
     double w[GG_E];
     double dsum = 0.0;
 #pragma unroll
     for (int e = 0; e < GG_E; ++e) {
-      const i64 i = gi0 + ty * 2 + (e >> 1), j = gj0 + tx * 2 + (e & 1);
+      const i64 i = gi0 + ty * 2 + (e >> 1), j = gj0 + tx * 2 + (e & 1), lj = lj0 + tx * 2 + (e & 1);
       double val = 0.0;
       if (a.rect) {
         if (i < a.nr && j < a.nc) val = a.Wd[i * a.ldw + j];
       } else if (i < a.n && j <= i) {
         double s = 0.0;
         for (int q = 0; q < a.r; ++q) s += a.A[(i64)q * a.lda + i] * a.A[(i64)q * a.lda + j];
-        val = s - (double)a.r * a.Kinv[i * a.ldk + j];
+        val = s - (double)a.r * (a.kinv_t ? a.Kinv[lj * a.ldk + i] : a.Kinv[i * a.ldk + lj]);
         if (i == j) { val *= 0.5; dsum += val; }
       }
       w[e] = val;
     }
-    if (!a.rect && ti == tj) {                             // noise: d K_y / d sigma^2 = I
+    if (!a.rect && gi0 == gj0) {                           // noise: d K_y / d sigma^2 = I
       dsum = gg_wave_sum(dsum);
       if (lane == 0) acc_s[wave][GG_MAXSLOT] += dsum;
     }
@@ -637,6 +641,14 @@ static int gg_build(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i6
   return GPS_OK;
 }
 
+int gps_grad_general_ls_of_slot(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, std::vector<double>* ls) {
+  GGBuilt B;
+  int rc = gg_build(h, prog, n_nodes, d_all, B);
+  if (rc) return rc;
+  *ls = B.ls_of_slot;
+  return GPS_OK;
+}
+
 // features of `n` points (padded to npad) into `feat`
 static int gg_features(gps_handle_t h, const GGBuilt& B, const double* dX, i64 n, i64 d_all, i64 npad, DevBuf& feat) {
   const int nfeat = (int)B.feats.size();
@@ -653,7 +665,7 @@ static int gg_features(gps_handle_t h, const GGBuilt& B, const double* dX, i64 n
 
 // launch + fold the fixed-order partials; slots: set (accumulate == 0) or added to
 static int gg_run(gps_handle_t h, const GGBuilt& B, GGArgs& a, double flops, double bytes, int accumulate,
-                  double* grad_slots_host, double* grad_noise_host) {
+                  double* grad_slots_host, double* grad_noise_host, bool raw = false) {
   const GGProg& P = B.P;
   const size_t wbytes = B.W.size() * 8;
   GPS_HIP(h, h->dNkn.ensure(wbytes + 64));
@@ -676,7 +688,7 @@ static int gg_run(gps_handle_t h, const GGBuilt& B, GGArgs& a, double flops, dou
     for (int b = 0; b < GG_BLOCKS; ++b) tot += part[(size_t)b * (GG_MAXSLOT + 1) + s];
     if (s == GG_MAXSLOT) { if (grad_noise_host) *grad_noise_host = tot; }
     else {
-      if (B.ls_of_slot[s] > 0.0) tot /= B.ls_of_slot[s];       // -2 delta^2 / l_d : delta is already x/l
+      if (!raw && B.ls_of_slot[s] > 0.0) tot /= B.ls_of_slot[s];       // -2 delta^2 / l_d : delta is already x/l
       if (accumulate) grad_slots_host[s] += tot; else grad_slots_host[s] = tot;
     }
   }
@@ -697,6 +709,30 @@ int gps_launch_grad_general(gps_handle_t h, const gps_kern_node_t* prog, int n_n
   a.n = n; a.npad = npad; a.tiles = (int)(npad / GG_T); a.tiles_c = a.tiles; a.rect = 0; a.same_points = 1;
   return gg_run(h, B, a, 0.5 * (double)npad * npad * (60.0 + 4.0 * B.feats.size() + 40.0 * B.P.n_layers), 4.0 * (double)npad * npad,
                 0, grad_slots_host, grad_noise_host);
+}
+
+int gps_launch_grad_general_cyclic(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n,
+                                   i64 d_all, i64 npad, const double* dKinv, i64 ldk, const double* dA, i64 lda, i64 r,
+                                   const GradCyclic& cyc, double* raw_slots_host, double* raw_noise_host) {
+  if (cyc.nb <= 0 || cyc.nb % GG_T || cyc.ncols % cyc.nb || cyc.P < 1 || cyc.rank < 0 || cyc.rank >= cyc.P)
+    return gps_fail(h, GPS_ERR_ARG, "gradient: bad block-cyclic column mode");
+  GGBuilt B;
+  int rc = gg_build(h, prog, n_nodes, d_all, B);
+  if (rc) return rc;
+  if (cyc.ncols == 0) {                                    // a rank without columns: its sums are zero
+    for (int s = 0; s < B.P.n_slots; ++s) raw_slots_host[s] = 0.0;
+    *raw_noise_host = 0.0;
+    return GPS_OK;
+  }
+  rc = gg_features(h, B, dX, n, d_all, npad, h->dFeat);
+  if (rc) return rc;
+  GGArgs a;
+  memset(&a, 0, sizeof(a));
+  a.Ft = h->dFeat.d(); a.ldf = npad; a.Ftc = a.Ft; a.ldfc = npad; a.Kinv = dKinv; a.ldk = ldk; a.A = dA; a.lda = lda; a.r = (int)r;
+  a.n = n; a.npad = npad; a.tiles = (int)(npad / GG_T); a.tiles_c = (int)(cyc.ncols / GG_T); a.rect = 0; a.same_points = 1;
+  a.cyc_P = cyc.P; a.cyc_rank = cyc.rank; a.cyc_nb = cyc.nb; a.kinv_t = cyc.kinv_t;
+  return gg_run(h, B, a, 0.5 * (double)npad * cyc.ncols * (60.0 + 4.0 * B.feats.size() + 40.0 * B.P.n_layers), 4.0 * (double)npad * cyc.ncols,
+                0, raw_slots_host, raw_noise_host, true);
 }
 
 // Vector-Jacobian product of the kernel-matrix build:  slots (+)= sum_{i < nr, j < nc} Wd[i][j] d k(xr_i, xc_j) / d theta

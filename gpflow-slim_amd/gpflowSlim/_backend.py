@@ -108,6 +108,15 @@ _SIGNATURES = {
     "gps_device_bytes": [ctypes.c_void_p, ctypes.POINTER(_i64)],
     "gps_dist_solve_begin": [ctypes.c_void_p, ctypes.POINTER(KernNode), ctypes.c_int, _c_double_p, _i64],
     "gps_dist_solve_pack": [ctypes.c_void_p, _i64, ctypes.c_int],
+    "gps_dist_grad_begin": [ctypes.c_void_p],
+    "gps_dist_grad_fwd_apply": [ctypes.c_void_p, _i64, ctypes.c_int],
+    "gps_dist_grad_bwd_apply": [ctypes.c_void_p, _i64, ctypes.c_int],
+    "gps_dist_grad_local": [ctypes.c_void_p, ctypes.POINTER(KernNode), ctypes.c_int, _c_double_p, ctypes.c_int, _c_int_p, _c_double_p],
+    "gps_dist_grad_fold": [ctypes.c_void_p, ctypes.POINTER(KernNode), ctypes.c_int, _c_double_p, ctypes.c_int, _i64, _c_double_p,
+                           ctypes.c_int, _c_int_p, _c_double_p],
+    "gps_dist_lml_grad": [ctypes.c_void_p, ctypes.POINTER(KernNode), ctypes.c_int, ctypes.c_double, _c_double_p, _i64, _i64,
+                          ctypes.c_int, ctypes.c_int, _c_double_p, _c_double_p, ctypes.c_int, _c_int_p, _c_double_p, _c_double_p,
+                          _c_int_p],
     "gps_dist_solve_apply": [ctypes.c_void_p, _i64, ctypes.c_int],
     "gps_dist_solve_finish": [ctypes.c_void_p, ctypes.POINTER(KernNode), ctypes.c_int, _c_double_p, _c_double_p],
     "gps_dist_lml": [ctypes.c_void_p, ctypes.POINTER(KernNode), ctypes.c_int, ctypes.c_double, _c_double_p, _i64, _i64, ctypes.c_int,
@@ -421,6 +430,55 @@ class Handle(object):
 
     def dist_solve_apply(self, j, buf):
         self._check(self._lib.gps_dist_solve_apply(self._h, int(j), int(buf)), "gps_dist_solve_apply")
+
+    def dist_grad_begin(self):
+        self._check(self._lib.gps_dist_grad_begin(self._h), "gps_dist_grad_begin")
+
+    def dist_grad_fwd_apply(self, j, buf):
+        self._check(self._lib.gps_dist_grad_fwd_apply(self._h, int(j), int(buf)), "gps_dist_grad_fwd_apply")
+
+    def dist_grad_bwd_apply(self, j, buf):
+        self._check(self._lib.gps_dist_grad_bwd_apply(self._h, int(j), int(buf)), "gps_dist_grad_bwd_apply")
+
+    def dist_grad_local(self, prog, n, r):
+        """gps_dist_grad_local: (raw sums [n_slots + 1] -- the noise-variance sum last --, K_y^-1 resid [n, r])."""
+        cap = 641
+        sums = np.zeros(cap)
+        ns = ctypes.c_int(0)
+        kinv_resid = np.empty((n, r))
+        self._check(self._lib.gps_dist_grad_local(self._h, prog, len(prog), _ptr(sums), cap, ctypes.byref(ns), _ptr(kinv_resid)),
+                    "gps_dist_grad_local")
+        return sums[:ns.value + 1].copy(), kinv_resid
+
+    def dist_grad_fold(self, prog, rank_sums):
+        """gps_dist_grad_fold over rank_sums [P, n_slots + 1]: (grad_slots, grad_noise)."""
+        rank_sums = _f64(rank_sums)
+        slots = np.zeros(640)
+        ns = ctypes.c_int(0)
+        gnoise = ctypes.c_double(0)
+        self._check(self._lib.gps_dist_grad_fold(self._h, prog, len(prog), _ptr(rank_sums), rank_sums.shape[0], rank_sums.shape[1],
+                                                 _ptr(slots), 640, ctypes.byref(ns), ctypes.byref(gnoise)), "gps_dist_grad_fold")
+        return slots[:ns.value].copy(), gnoise.value
+
+    def dist_lml_grad(self, prog, noise_var, resid, nb, lookahead, exchange_mode):
+        """gps_dist_lml_grad: (lml, grad_slots, grad_noise, K_y^-1 resid), the whole distributed LML + gradient inside the
+        library (native communicator required)."""
+        resid = _f64(resid)
+        n, r = resid.shape
+        lml = ctypes.c_double(0)
+        info = ctypes.c_int(0)
+        ns = ctypes.c_int(0)
+        slots = np.zeros(640)
+        gnoise = ctypes.c_double(0)
+        kinv_resid = np.empty((n, r))
+        self.resident_token_factor = None
+        self._check(self._lib.gps_dist_lml_grad(self._h, prog, len(prog), float(noise_var), _ptr(resid), r, int(nb), int(lookahead),
+                                                int(exchange_mode), ctypes.byref(lml), _ptr(slots), 640, ctypes.byref(ns),
+                                                ctypes.byref(gnoise), _ptr(kinv_resid), ctypes.byref(info)), "gps_dist_lml_grad")
+        if info.value > 0:
+            raise NotPositiveDefiniteError(
+                "Cholesky decomposition was not successful: leading minor of order %d is not positive definite" % info.value)
+        return lml.value, slots[:ns.value].copy(), gnoise.value, kinv_resid
 
     def dist_solve_finish(self, prog, n_new, r):
         mean = np.empty((n_new, max(r, 1)))

@@ -106,6 +106,45 @@ def block_column_schedule(ops, comm, n_panels, lookahead=2):
         ops.wait(CHAIN, tok)
 
 
+def grad_stream_schedule(ops, comm, n_panels):
+    """The two streams of the distributed LML gradient, over a factor that stays partitioned.
+
+    Step k = 0 .. 2 n_panels - 1 handles panel j = k (forward stream, Z^T <- Z^T L^-T on this rank's identity columns) and then
+    j = 2 n_panels - 1 - k (backward stream, X^T L = Z^T: the owned block columns of K_y^-1, and A = K_y^-1 resid on every rank).
+    The owner of panel j packs it again (the message of the factorisation), the panel is exchanged, every rank applies it.
+    One lane; two comm slots alternate (slot k % 2): the exchange of step k + 1 is in flight while step k is applied, and its
+    pack / receive is ordered after apply(k - 1), the last reader of that slot.
+
+    `ops`: begin(), pack(j, buf), message(j, buf) -> buffer object for comm, fwd_apply(j, buf), bwd_apply(j, buf), local() ->
+    this rank's result, and the context manager comm_lane().  `comm`: rank, world, exchange(buffer, src) -> object with wait().
+    Returns ops.local()."""
+    P, rank = comm.world, comm.rank
+    steps = 2 * n_panels
+
+    def panel(k):
+        return k if k < n_panels else steps - 1 - k
+
+    def send(k):
+        j, buf = panel(k), k % 2
+        if rank == j % P:
+            ops.pack(j, buf)
+        with ops.comm_lane():
+            return comm.exchange(ops.message(j, buf), j % P)
+
+    ops.begin()
+    pending = send(0)
+    for k in range(steps):
+        with ops.comm_lane():
+            pending.wait()
+        if k + 1 < steps:
+            pending = send(k + 1)
+        if k < n_panels:
+            ops.fwd_apply(panel(k), k % 2)
+        else:
+            ops.bwd_apply(panel(k), k % 2)
+    return ops.local()
+
+
 # ---- GPU side -------------------------------------------------------------------------------------
 _SIDE_GROUPS = {}
 
@@ -492,6 +531,19 @@ def _default_comm():
         return SingleComm()
 
 
+def _count_native_exchanges(comm, h, n_panels, mode, passes):
+    """Add to comm's counters what the library put on the wire for `passes` exchanges of every panel message (what
+    RcclComm.exchange would have counted): the native drivers exchange inside the library."""
+    comm.exchanges += passes * n_panels
+    if comm.world == 1:
+        return
+    for j in range(n_panels):
+        cnt = -(-h.dist_msg_doubles(j) // comm.world) * comm.world
+        root = (j % comm.world) == comm.rank
+        comm.bytes_sent += passes * ((8 * (cnt // comm.world) * (comm.world - 1) * (2 if root else 1)) if mode == 1
+                                     else (8 * cnt * (comm.world - 1) if root else 0))
+
+
 def gpr_lml_distributed(model, comm=None, nb=512, lookahead=2, partitioned=True):
     """Log-marginal likelihood of a gpflowSlim.models.GPR with the covariance factorised across the
     ranks of `comm` (default: the default torch.distributed group, or a single rank).  Every rank must
@@ -510,13 +562,7 @@ def gpr_lml_distributed(model, comm=None, nb=512, lookahead=2, partitioned=True)
         h.set_option("dist_partitioned", 1 if partitioned else 0)
         mode = 1 if comm.mode == "scatter_allgather" else 0
         lml = h.dist_lml(prog, float(np.squeeze(model.likelihood.variance)), model._resid(), nb, 2 if lookahead is True else int(lookahead), mode)
-        n_panels = -(-model.X.shape[0] // nb)
-        comm.exchanges += n_panels
-        for j in range(n_panels):              # the payload the library put on the wire (what RcclComm.exchange would have counted)
-            cnt = -(-h.dist_msg_doubles(j) // comm.world) * comm.world
-            root = (j % comm.world) == comm.rank
-            if comm.world > 1:
-                comm.bytes_sent += (8 * (cnt // comm.world) * (comm.world - 1) * (2 if root else 1)) if mode == 1 else (8 * cnt * (comm.world - 1) if root else 0)
+        _count_native_exchanges(comm, h, -(-model.X.shape[0] // nb), mode, 1)
         if partitioned:
             h.dist_state = {"key": model._state_key(), "native": True, "world": comm.world}
         else:
@@ -619,3 +665,110 @@ def predict_streamed(h, prog, Xmine, comm, n_panels, bufs, nparts, R):
         torch.cuda.current_stream().wait_stream(lane)
         h.set_stream(0, False)
     return mu, var
+
+
+class HipGradOps(object):
+    """grad_stream_schedule's pieces on one GPU through the C ABI (gps_dist_solve_pack / gps_dist_grad_*), on one torch
+    stream installed as the handle's stream (device-memory / stream plumbing only).  `bufs`: the comm buffers the partitioned
+    factorisation left in h.dist_state.  Use as a context manager: leaving it always gives the handle its own stream back."""
+
+    def __init__(self, handle, prog, n, r, bufs, nparts):
+        import torch
+        self.h, self.torch, self.prog, self.n, self.r = handle, torch, prog, n, r
+        self.bufs, self.nparts = bufs, max(int(nparts), 1)
+        self.lane = torch.cuda.Stream()
+        self.lane.wait_stream(torch.cuda.current_stream())
+        handle.set_stream(self.lane.cuda_stream, True)
+        self._installed = True
+        try:
+            handle.dist_set_comm_bufs([b.data_ptr() for b in bufs])
+        except Exception:
+            self.close()
+            raise
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def close(self):
+        if self._installed:
+            self._installed = False
+            self.torch.cuda.current_stream().wait_stream(self.lane)
+            self.h.set_stream(0, False)
+
+    def comm_lane(self):
+        return self.torch.cuda.stream(self.lane)
+
+    def begin(self):
+        self.h.dist_grad_begin()
+
+    def pack(self, j, buf):
+        self.h.dist_solve_pack(j, buf)
+
+    def message(self, j, buf):
+        n = self.h.dist_msg_doubles(j)
+        return self.bufs[buf][: -(-n // self.nparts) * self.nparts]
+
+    def fwd_apply(self, j, buf):
+        self.h.dist_grad_fwd_apply(j, buf)
+
+    def bwd_apply(self, j, buf):
+        self.h.dist_grad_bwd_apply(j, buf)
+
+    def local(self):
+        return self.h.dist_grad_local(self.prog, self.n, self.r)
+
+
+def gpr_lml_grad_distributed(model, comm=None, nb=512, lookahead=2):
+    """LML and its gradient of a gpflowSlim.models.GPR over the ranks of `comm` -- what
+    GPR.compute_log_likelihood_and_gradients returns, (lml, [(Parameter, d LML / d unconstrained parameter), ...]), with the
+    covariance factorised across the ranks (partitioned storage: 8 N^2 / P bytes per rank for the factor, as many again for
+    this rank's block columns of K_y^-1).  Every rank must call this with the same model state; every
+    rank returns the same bits, or every rank raises NotPositiveDefiniteError.  Afterwards the partitioned factor stays
+    claimed in the handle's dist_state: predict_f_distributed follows without a second factorisation.
+
+    With an RcclComm that has native_schedule, the whole call runs inside the library (gps_dist_lml_grad); otherwise
+    gpr_lml_distributed, grad_stream_schedule over HipGradOps, a gather of the ranks' raw slot sums and gps_dist_grad_fold."""
+    comm = comm or _default_comm()
+    h = model._handle()
+    d_all = model.X.shape[1]
+    prog = model.kern._program(d_all)
+    layout = model.kern._grad_layout(d_all)
+    noise = float(np.squeeze(model.likelihood.variance))
+    if isinstance(comm, RcclComm) and comm.native_schedule and comm.h is h:
+        model._factor_key = None
+        h.set_option("dist_partitioned", 1)
+        mode = 1 if comm.mode == "scatter_allgather" else 0
+        lml, slots, gnoise, kinv_resid = h.dist_lml_grad(prog, noise, model._resid(), nb, 2 if lookahead is True else int(lookahead), mode)
+        # the factorisation's exchanges, the two gradient streams' and the all-reduce that gathers the [P][n_slots + 1] sums
+        # and K_y^-1 resid
+        _count_native_exchanges(comm, h, -(-model.X.shape[0] // nb), mode, 3)
+        if comm.world > 1:
+            comm.bytes_sent += 8 * (comm.world * (len(slots) + 1) + kinv_resid.size)
+        h.dist_state = {"key": model._state_key(), "native": True, "world": comm.world}
+        return lml, model._gradients_from_slots(layout, slots, gnoise, kinv_resid)
+    lml = gpr_lml_distributed(model, comm, nb=nb, lookahead=lookahead, partitioned=True)
+    st = h.dist_state
+    n, r = model.Y.shape
+    with HipGradOps(h, prog, n, r, st["bufs"], st["nparts"]) as ops:
+        sums, kinv_resid = grad_stream_schedule(ops, comm, st["n_panels"])
+    w = sums.shape[0]
+    # every rank's raw sums (and K_y^-1 resid, of which rank 0's is taken) on every rank, folded in rank order: the same bits
+    both = comm.all_gather_rows(np.concatenate([sums, kinv_resid.ravel()])[None, :], [1] * comm.world)
+    slots, gnoise = h.dist_grad_fold(prog, both[:, :w])
+    return lml, model._gradients_from_slots(layout, slots, gnoise, both[0, w:].reshape(n, r))
+
+
+def optimize_distributed(model, comm=None, nb=512, lookahead=2, **optimize_kwargs):
+    """Model.optimize (models/model.py:172-196 of the reference; L-BFGS-B or Adam) with the LML and its gradient taken from
+    gpr_lml_grad_distributed at every step.  Every rank must call it with the same model and arguments; the gradients are
+    bit-identical on every rank, so every rank takes the same steps.  Returns what Model.optimize returns."""
+    comm = comm or _default_comm()
+    model.compute_log_likelihood_and_gradients = lambda: gpr_lml_grad_distributed(model, comm, nb=nb, lookahead=lookahead)
+    try:
+        return model.optimize(**optimize_kwargs)
+    finally:
+        del model.compute_log_likelihood_and_gradients

@@ -91,6 +91,13 @@ class GPR(GPModel):
         self._factor_key = None
         lml, slots, gnoise, kinv_resid = h.gpr_lml_grad(prog, float(np.squeeze(self.likelihood.variance)), resid)
         self._factor_key = self._state_key()
+        return lml, self._gradients_from_slots(layout, slots, gnoise, kinv_resid)
+
+    def _gradients_from_slots(self, layout, slots, gnoise, kinv_resid):
+        """Map the kernel's gradient slots, d LML / d(noise variance) and K_y^-1 (Y - m) onto
+        [(Parameter, d LML / d(unconstrained parameter)), ...] in `self.parameters` order: the slot layout of
+        the kernel program, the mean-function chain rule through K_y^-1 (Y - m) and the transforms.  Shared
+        by compute_log_likelihood_and_gradients and gpflowSlim.distributed.gpr_lml_grad_distributed."""
         if len(layout) != len(slots):
             raise RuntimeError("gradient slot layout mismatch: %d vs %d" % (len(layout), len(slots)))
         grads = {id(p): np.zeros_like(np.atleast_1d(p.vf_val), dtype=settings.float_type) for p in self.parameters}
@@ -119,7 +126,7 @@ class GPR(GPModel):
         for p in self.parameters:
             g = grads[id(p)].reshape(np.atleast_1d(p.vf_val).shape) * np.atleast_1d(p.transform.forward_grad(p.vf_val))
             out.append((p, g.reshape(p.vf_val.shape)))
-        return lml, out
+        return out
 
     def _build_predict(self, Xnew, full_cov=False):
         """models/gpr.py:119-131"""

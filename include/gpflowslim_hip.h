@@ -401,6 +401,34 @@ int gps_dist_solve_finish(gps_handle_t h, const gps_kern_node_t* prog, int n_nod
  * shard of the test points (n_new may be 0), mean [n_new, r] without the mean function, var [n_new].               */
 int gps_dist_predict(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Xnew, int64_t n_new,
                      int exchange_mode, double* mean_out, double* var_out);
+/* LML gradient over the partitioned factor (examples/gpr.py:53-61 and models/model.py:172-196 of the reference take the
+ * LML and its gradient at every optimiser step; here over P ranks).  Per-step pieces for host-driven schedules, after a
+ * partitioned factorisation that succeeded:
+ *   gps_dist_grad_begin                 Z^T = identity rows of this rank's block columns (c % P == rank)
+ *   forward  j = 0 .. n_panels-1:       owner gps_dist_solve_pack(j, buf), exchange, all gps_dist_grad_fwd_apply(j, buf)
+ *                                       (Z^T <- Z^T L^-T, only the owned columns c <= j; alpha_j from the augmented rows)
+ *   backward j = n_panels-1 .. 0:       the same exchange, all gps_dist_grad_bwd_apply(j, buf)
+ *                                       (X^T L = Z^T: the owned block columns of K_y^-1, rows >= the column; and A = K_y^-1 resid)
+ *   gps_dist_grad_local                 this rank's RAW slot sums (no lengthscale division) in sums_out[0 .. n_slots), the
+ *                                       noise-variance sum in sums_out[n_slots] (cap >= n_slots + 1), K_y^-1 resid [n, r]
+ *                                       (kinv_resid_out may be NULL)
+ *   gps_dist_grad_fold                  host only: the P ranks' sums (rank p at rank_sums + p * stride) added in rank order,
+ *                                       then the lengthscale division of gps_gpr_lml_grad -- the same bits on every rank
+ * Sum of the ranks' results = the outputs of gps_gpr_lml_grad.                                                      */
+int gps_dist_grad_begin(gps_handle_t h);
+int gps_dist_grad_fwd_apply(gps_handle_t h, int64_t j, int buf);
+int gps_dist_grad_bwd_apply(gps_handle_t h, int64_t j, int buf);
+int gps_dist_grad_local(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double* sums_out, int cap,
+                        int* n_slots_out, double* kinv_resid_out);
+int gps_dist_grad_fold(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* rank_sums, int P,
+                       int64_t stride, double* grad_slots, int n_slots_cap, int* n_slots_out, double* grad_noise);
+/* ... and the whole LML + gradient from inside the library (native communicator, option dist_partitioned = 1; reference
+ * examples/gpr.py:53-61): gps_dist_lml, both streams, the local contraction, one all-reduce of the zero-padded [P][n_slots + 1]
+ * sums (x + 0 = x: a gather) and the fold.  Outputs as gps_gpr_lml_grad, bit-identical on every rank; the partitioned factor
+ * stays for gps_dist_predict.                                                                                     */
+int gps_dist_lml_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double noise_var, const double* resid,
+                      int64_t r, int64_t nb, int lookahead, int exchange_mode, double* lml, double* grad_slots,
+                      int n_slots_cap, int* n_slots_out, double* grad_noise, double* kinv_resid, int* info);
 /* device bytes held by the handle's own buffers (tests of the 8 N^2 / P + O(N nb) bound) */
 int gps_device_bytes(gps_handle_t h, int64_t* bytes);
 int gps_dist_set_bulk_stream(gps_handle_t h, void* hip_stream);

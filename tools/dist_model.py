@@ -2,7 +2,8 @@
 ranks computes per panel at N = argv[1] (default 32768; partitioned storage: rank 0 holds 8 N^2 / P bytes, so N = 131072 fits
 for every P) -- the panel factorisation (chain) and its share of the trailing update (bulk) --
 with the exchange left out (other ranks' panels are garbage: kernel times do not depend on the data).  The exchange is
-modelled: scatter + all-gather moves 2 S / P bytes per rank and phase over P - 1 links; assumed per-link rate below."""
+modelled: scatter + all-gather moves 2 S / P bytes per rank and phase over P - 1 links; assumed per-link rate below.  Then the
+same for the two panel streams of the distributed LML gradient (grad_cases)."""
 import json, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -59,10 +60,41 @@ for nb in ((512, 1024) if N <= 32768 else (1024,)):
                 "bulk_ms_per_rank": round(bulk, 1), "model_ms_no_overlap": round(total1, 1), "model_ms_two_lanes": round(total2, 1)}
         out["cases"].append(case)
         print(json.dumps(case), flush=True)
+# The two panel streams of the distributed LML gradient (csrc/dist_grad.hip), per rank 0 of P: step j of the forward stream is
+# the NT product [k_j nb, N - (j+1) nb, K = nb], of the backward stream [128 + k_j nb, nb, K = N - (j+1) nb] (k_j = owned block
+# columns <= j), both timed as such on this GPU (gps_diag_gemm_timeline: the production launcher on device data, so the few
+# output tiles of the backward product at large P are in the figure); the panel exchange of the next step is in flight while a
+# step is applied: a step costs max(product, exchange).  The 128-column solves of each step (~ N nb^2 / P flop) are left out.
+grad_cases = []
+for nb in ((512,) if N <= 32768 else (1024,)):
+    npan = N // nb
+    stride = max(1, npan // 16)
+    for P in (1, 2, 4, 8):
+        fwd = bwd = ex_tot = 0.0
+        for j in range(0, npan, stride):
+            k_j = min(j // P + 1, len(range(0, npan, P)))
+            below = N - (j + 1) * nb
+            rows = N + 128 - j * nb
+            S = 8.0 * (rows * nb + 2 * (nb // 128) * 128 * 128 + 4)
+            ex = 0.0 if P == 1 else (2.0 * S / P / (LINK_GBS * 1e9) * 1e3 + 2 * COLL_LAT_US * 1e-3)
+            tf = h.diag_gemm_timeline(0, 0, k_j * nb, below, nb, reps=2)[0] if below > 0 else 0.0
+            tb = h.diag_gemm_timeline(0, 0, 128 + k_j * nb, nb, below, reps=2)[0] if below > 0 else 0.0
+            w = min(stride, npan - j)
+            fwd += w * max(tf, ex); bwd += w * max(tb, ex); ex_tot += 2 * w * ex
+        fac = [c for c in out["cases"] if c["nb"] == nb and c["P"] == P][0]["model_ms_two_lanes"]
+        case = {"what": "MODEL OUTPUT (exchange at an ASSUMED link rate; not a multi-GPU measurement)", "nb": nb, "P": P,
+                "grad_forward_stream_ms": round(fwd, 1), "grad_backward_stream_ms": round(bwd, 1), "of_which_exchange_ms": round(ex_tot, 1),
+                "factorisation_ms": fac, "lml_and_grad_ms": round(fac + fwd + bwd, 1)}
+        grad_cases.append(case)
+        print(json.dumps(case), flush=True)
+out["grad_cases"] = grad_cases
 # the fused single-GPU evaluation of the same problem, for the "vs one GPU" column
 if N <= 131072:
     m = gpf.models.GPR(X, Y, kern, obs_var=0.1)
     m.compute_log_likelihood()
     out["fused_one_gpu_ms"] = round(timed(m.compute_log_likelihood, 2), 1)
     print(json.dumps({"fused_one_gpu_ms": out["fused_one_gpu_ms"]}), flush=True)
+    m.compute_log_likelihood_and_gradients()
+    out["fused_one_gpu_lml_and_grad_ms"] = round(timed(m.compute_log_likelihood_and_gradients, 2), 1)
+    print(json.dumps({"fused_one_gpu_lml_and_grad_ms": out["fused_one_gpu_lml_and_grad_ms"]}), flush=True)
 json.dump(out, open(os.path.join(ROOT, "gpurun_out", "dist_model_n%d.json" % N), "w"), indent=1)
