@@ -1,7 +1,7 @@
 """Counterpart of the reference's examples/svgp.py on the MI355X path, with the part of it this library covers: the
 reference script trains an SVGP (whiten=False, Z initialised from the training inputs, Adam on `objective`,
 examples/svgp.py:144-161) with a MultiClass likelihood on MNIST; the likelihood here is Gaussian (regression on synthetic
-data -- non-Gaussian likelihoods are outside the scope of this library), everything else follows the script: the same model
+data; examples/svgp_classify.py is the classification counterpart), everything else follows the script: the same model
 construction, the same optimiser on `objective` over every parameter including the inducing inputs, predictions at
 intervals.  An SGPR on the same data shows the collapsed bound the SVGP bound approaches.
 

@@ -238,6 +238,7 @@ struct gps_handle_s {
   DevBuf dKinv;     // [npad, npad]  K_y^-1, lower triangle               (gradient path)
   DevBuf dS1, dS2, dS3, dS4;   // SGPR work space (gps_sgpr)
   DevBuf dG1, dG2, dG3, dG4;   // SVGP gradient work space (gps_svgp_elbo_grad)
+  DevBuf dLikIn, dLikOut, dLikPart, dLikH;   // likelihoods (lik.hip): moments / Y / mean ; dmu, dvar ; per-workgroup partials ; H^T [k][nspad]
   DevBuf dTmp;      // generic scratch (host-matrix entry points)
   DevBuf dTmp2;
   DevBuf dTmp3;
@@ -422,6 +423,17 @@ int gps_launch_scale_cols(gps_handle_t h, const double* src, i64 lds_, i64 rows,
 int gps_launch_scale_add_eye(gps_handle_t h, double* B, i64 ldb, i64 n, i64 n_real, double scale);
 int gps_launch_var_finish(gps_handle_t h, double* var, const double* kdiag_or_null,
                           double kdiag_const, const double* sumsq, i64 n);
+// lik.hip : variational expectations of the non-Gaussian likelihoods and the pieces of their backward pass
+struct LikHost { double raw[8 + 2 * GPS_LIK_MAX_GH]; };      // the descriptor as the kernels take it (opaque outside lik.hip)
+int gps_lik_prepare(gps_handle_t h, const gps_lik_t* lik, i64 k, LikHost* out);
+int gps_lik_launch(gps_handle_t h, const LikHost* L, const double* fmu, const double* mean, const double* fvar, i64 v_si, i64 v_sq,
+                   const double* Y, i64 n, i64 k, int want_grad, double oscale, double* dmu, double* dvar, i64 o_si, i64 o_sq,
+                   double* ve_sum, double* dparam_sum, double* dvar_sum);
+int gps_launch_lik_var_plane(gps_handle_t h, const double* base, const double* extra, i64 n, double* out);
+int gps_launch_lik_rowsq(gps_handle_t h, const double* A, i64 lda, i64 rows, i64 cols, const double* Ht, i64 ldh, i64 k, double* out);
+int gps_launch_lik_abar(gps_handle_t h, const double* Bt, i64 ld, i64 rows, i64 cols, const double* Et, const double* Ht, i64 lde,
+                        const double* qmu, const double* cq, i64 k, double* Abar);
+int gps_launch_lik_rows_axpy(gps_handle_t h, double* Abar, const double* P, i64 ld, i64 rows, i64 cols, const double* Hq);
 // kmat.hip
 int gps_launch_kmat(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes,
                     const double* dX, i64 n, const double* dX2 /*nullptr: symmetric*/, i64 m,

@@ -22,6 +22,16 @@ struct SvgpAcc {
   double noise_var;
   double sq_sum = 0.0;     // sum_{i,q} (yres - fmean)^2 + fvar
   double kl = 0.0;
+  // any other likelihood (gps_svgp_elbo_lik; lik.hip): yres holds the targets Y [n, ky] themselves, `mean` (optional, host
+  // [n, k]) is added to fmean on the device, and the per-point terms come from ONE launch over the finished moments
+  // (fvar of latent q kept as plane q + 1 of dVar).  want_grad: E^T = scale dmu -> dA, H^T = scale dvar -> dLikH, both [k][nsp]
+  const LikHost* lik = nullptr;
+  const double* mean = nullptr;
+  i64 ky = 0;
+  int want_grad = 0;
+  double scale = 1.0;
+  double ve = 0.0, dparam = 0.0;   // sum of the variational expectations and of their derivative in param[0] (unscaled)
+  double hsum = 0.0;               // sum_iq H[i][q] = d ELBO / d Kdiag summed over the points
 };
 
 // tr(Sigma_p^-1 Sigma_q) pieces of the KL for p = N(0, L L^T)                      kullback_leiblers.py:83-94
@@ -139,8 +149,16 @@ static int conditional_tail(gps_handle_t h, CondIn& c, const double* f, const do
     if (full_cov || !q_sqrt) return gps_fail(h, GPS_ERR_ARG, "svgp: needs q_sqrt and marginal variances");
     GPS_HIP(h, h->dS1.ensure((size_t)n_new * k * 8 + 64 * 8));
     dYres = h->dS1.d();
+    if (sv->lik) {
+      GPS_HIP(h, hipMemcpyAsync(dYres, sv->yres, (size_t)n_new * sv->ky * 8, hipMemcpyHostToDevice, h->stream));
+      if (sv->mean) {
+        GPS_HIP(h, h->dLikIn.ensure((size_t)n_new * k * 8));
+        GPS_HIP(h, hipMemcpyAsync(h->dLikIn.p, sv->mean, (size_t)n_new * k * 8, hipMemcpyHostToDevice, h->stream));
+      }
+    } else {
     GPS_HIP(h, hipMemcpyAsync(dYres, sv->yres, (size_t)n_new * k * 8, hipMemcpyHostToDevice, h->stream));
     GPS_HIP(h, hipMemsetAsync(dYres + (size_t)n_new * k, 0, 64 * 8, h->stream));
+    }
   } else if (!full_cov) {
     base.resize(n_new);
     GPS_HIP(h, hipMemcpyAsync(base.data(), h->dVar.p, (size_t)n_new * 8, hipMemcpyDeviceToHost, h->stream));
@@ -210,7 +228,8 @@ static int conditional_tail(gps_handle_t h, CondIn& c, const double* f, const do
                           : gps_launch_rowdot(h, dLTA, mp, n_new, mp, nullptr, mp, 0, nullptr, dss);
       if (rc) return rc;
       // sum_i (yres - fmean)^2 + fvar for this latent, fvar = base + extra           likelihoods.py:186-188
-      rc = gps_launch_varexp(h, dmean, dYres, k, (int)q, h->dVar.d(), dss, n_new, dYres + (size_t)n_new * k);
+      if (sv->lik) rc = gps_launch_lik_var_plane(h, h->dVar.d(), dss, n_new, h->dVar.d() + (size_t)(q + 1) * n_new);
+      else rc = gps_launch_varexp(h, dmean, dYres, k, (int)q, h->dVar.d(), dss, n_new, dYres + (size_t)n_new * k);
       if (rc) return rc;
       if (!white && q_sqrt_ndim == 3) {
         // tr(Kuu^-1 S_q) from the L_q^T that is already on the device (dLTA no longer needs it)
@@ -239,12 +258,26 @@ static int conditional_tail(gps_handle_t h, CondIn& c, const double* f, const do
       for (size_t e = 0; e < per; ++e) o[e] = base[e] + extra[e];
     }
   }
+  if (sv && sv->lik) {
+    // the per-point terms of the bound (and, for the gradient, its cotangents in fmean / fvar) from the finished moments
+    double* Et = nullptr; double* Ht = nullptr;
+    if (sv->want_grad) {
+      GPS_HIP(h, h->dA.ensure((size_t)k * nsp * 8));
+      GPS_HIP(h, h->dLikH.ensure((size_t)k * nsp * 8));
+      Et = h->dA.d(); Ht = h->dLikH.d();
+      GPS_HIP(h, hipMemsetAsync(Et, 0, (size_t)k * nsp * 8, h->stream));
+      GPS_HIP(h, hipMemsetAsync(Ht, 0, (size_t)k * nsp * 8, h->stream));
+    }
+    rc = gps_lik_launch(h, sv->lik, dmean, sv->mean ? h->dLikIn.d() : nullptr, h->dVar.d() + n_new, 1, n_new, dYres, n_new, k,
+                        sv->want_grad, sv->scale, Et, Ht, 1, nsp, &sv->ve, &sv->dparam, &sv->hsum);
+    if (rc) return rc;
+  }
   if (sv) {
     double part[64];
-    GPS_HIP(h, hipMemcpyAsync(part, dYres + (size_t)n_new * k, sizeof(part), hipMemcpyDeviceToHost, h->stream));
+    if (!sv->lik) GPS_HIP(h, hipMemcpyAsync(part, dYres + (size_t)n_new * k, sizeof(part), hipMemcpyDeviceToHost, h->stream));
     rc = read_info(h, d_info, info);
     if (rc) return rc;
-    for (int b = 0; b < 64; ++b) sv->sq_sum += part[b];
+    if (!sv->lik) for (int b = 0; b < 64; ++b) sv->sq_sum += part[b];
     // KL[q || p]                                                           kullback_leiblers.py:68-105
     double slog = 0.0, mahal = 0.0, logdet_q = 0.0, trace = 0.0;
     for (int b = 0; b < 64; ++b) { slog += kl_hp[2 * b]; mahal += kl_hp[2 * b + 1]; }
@@ -495,6 +528,132 @@ static int svgp_whiten(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes,
   return GPS_OK;
 }
 
+// Second half of the backward pass, shared by the Gaussian and the general likelihoods: from Abar^T [nsp, mp] (d ELBO / d A,
+// transposed), the whitened gradients in grad_q_mu / grad_q_sqrt and kdiag_bar = sum_iq d ELBO / d fvar[i][q] to the kernel
+// parameters (and Z); for the unwhitened parametrisation also the pull-back of grad_q_mu / grad_q_sqrt (see above svgp_whiten).
+struct SvgpTail {
+  const gps_kern_node_t* prog; int n_nodes; i64 m, d_all, n, k; int ns;
+  bool unwhite; int ndim_in;
+  const double* q_mu; const double* q_sqrt;          // the (whitened) variational parameters the gradient was taken at
+  double* grad_q_mu; double* grad_q_sqrt; double* grad_q_sqrt_out;
+  double* Abar; double* Am; double kdiag_bar;
+  double* grad_slots; double* grad_Z;
+};
+static int svgp_grad_tail(gps_handle_t h, Blocked<HipOps>& bl, const SvgpTail& t) {
+  const gps_kern_node_t* prog = t.prog; const int n_nodes = t.n_nodes, ns = t.ns, ndim_in = t.ndim_in;
+  const i64 m = t.m, d_all = t.d_all, n = t.n, k = t.k, mp = gps_pad(t.m), nsp = gps_pad(t.n);
+  const bool unwhite = t.unwhite;
+  const double* q_mu = t.q_mu; const double* q_sqrt = t.q_sqrt;
+  double* grad_q_mu = t.grad_q_mu; double* grad_q_sqrt = t.grad_q_sqrt; double* grad_q_sqrt_out = t.grad_q_sqrt_out;
+  double* Abar = t.Abar; double* Am = t.Am; double* grad_slots = t.grad_slots; double* grad_Z = t.grad_Z;
+  const double kdiag_bar = t.kdiag_bar;
+  double* Lm = h->dK.d();
+  int rc;
+  // Kuf_bar^T = Abar^T Lm^-1  (X Lm = Abar^T through U = Lm^T), then Kuf_bar [mp, nsp]
+  GPS_HIP(h, h->dTmp.ensure((size_t)mp * mp * 8));
+  double* U = h->dTmp.d();
+  rc = gps_launch_transpose(h, Lm, mp, mp, mp, U, mp);
+  if (rc) return rc;
+  rc = gps_launch_tri_map(h, U, mp, mp, 3);            // (above the diagonal blocks the factor's buffer was never written)
+  if (rc) return rc;
+  rc = bl.trsm_rn_rec(U, mp, mp, 0, Abar, mp, nsp);
+  if (rc) return rc;
+  GPS_HIP(h, h->dS1.ensure((size_t)mp * nsp * 8));
+  double* KufBar = h->dS1.d();
+  rc = gps_launch_transpose(h, Abar, mp, nsp, mp, KufBar, nsp);
+  if (rc) return rc;
+  // Lm_bar = -tril(Kuf_bar A^T)
+  GPS_HIP(h, h->dS3.ensure((size_t)mp * mp * 8));
+  double* LmBar = h->dS3.d();
+  rc = gps_launch_gemm_nt(h, 1, 1, mp, mp, nsp, KufBar, nsp, Am, nsp, LmBar, mp);
+  if (rc) return rc;
+  if (unwhite) {
+    // pull-back of (g_w, G_w) through m_w = Lm^-1 q_mu, L_w = Lm^-1 L_q; their dependence on Lm joins Lm_bar (still
+    // un-negated here: Lm_bar = -tril(Kuf_bar A^T + g(q_mu) m_w^T + sum_q (Lm^-T G_w,q) L_w,q^T))
+    std::vector<double> buf((size_t)GPS_TILE * mp, 0.0);
+    for (i64 j = 0; j < m; ++j) for (i64 q = 0; q < k; ++q) buf[(size_t)q * mp + j] = grad_q_mu[j * k + q];
+    GPS_HIP(h, h->dG3.ensure(buf.size() * 8));
+    GPS_HIP(h, hipMemcpyAsync(h->dG3.p, buf.data(), buf.size() * 8, hipMemcpyHostToDevice, h->stream));
+    rc = bl.trsm_rn_rec(U, mp, mp, 0, h->dG3.d(), mp, GPS_TILE);                       // rows: g_w^T Lm^-1 = (Lm^-T g_w)^T
+    if (rc) return rc;
+    GPS_HIP(h, hipMemcpyAsync(buf.data(), h->dG3.p, buf.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    GPS_HIP(h, hipStreamSynchronize(h->stream));
+    std::vector<double> ga((size_t)mp * GPS_TILE, 0.0), mb((size_t)mp * GPS_TILE, 0.0);
+    for (i64 j = 0; j < m; ++j)
+      for (i64 q = 0; q < k; ++q) {
+        const double g = buf[(size_t)q * mp + j];
+        grad_q_mu[j * k + q] = g;
+        ga[(size_t)j * GPS_TILE + q] = g;
+        mb[(size_t)j * GPS_TILE + q] = q_mu[j * k + q];
+      }
+    GPS_HIP(h, h->dG1.ensure((size_t)mp * mp * 8));
+    GPS_HIP(h, h->dG2.ensure((size_t)mp * mp * 8));
+    GPS_HIP(h, h->dTmp2.ensure((size_t)mp * mp * 8));
+    GPS_HIP(h, hipMemcpyAsync(h->dG1.p, ga.data(), ga.size() * 8, hipMemcpyHostToDevice, h->stream));
+    GPS_HIP(h, hipMemcpyAsync(h->dG2.p, mb.data(), mb.size() * 8, hipMemcpyHostToDevice, h->stream));
+    rc = gps_launch_gemm_nt(h, 2, 1, mp, mp, GPS_TILE, h->dG1.d(), GPS_TILE, h->dG2.d(), GPS_TILE, LmBar, mp);   // += g(q_mu) m_w^T
+    if (rc) return rc;
+    GPS_HIP(h, hipStreamSynchronize(h->stream));
+    std::vector<double> T((size_t)mp * mp);
+    for (i64 q = 0; q < k; ++q) {
+      const double* Gw = grad_q_sqrt + (size_t)q * m * m;              // whitened gradient, lower triangular [m][m]
+      const double* Lwq = q_sqrt + (size_t)q * m * m;
+      std::fill(T.begin(), T.end(), 0.0);
+      for (i64 a = 0; a < m; ++a) for (i64 b = 0; b <= a; ++b) T[(size_t)b * mp + a] = Gw[a * m + b];      // G_w^T
+      GPS_HIP(h, hipMemcpyAsync(h->dTmp2.p, T.data(), T.size() * 8, hipMemcpyHostToDevice, h->stream));
+      rc = bl.trsm_rn_rec(U, mp, mp, 0, h->dTmp2.d(), mp, mp);                          // (Lm^-T G_w)^T
+      if (rc) return rc;
+      rc = gps_launch_transpose(h, h->dTmp2.d(), mp, mp, mp, h->dG1.d(), mp);          // Lm^-T G_w
+      if (rc) return rc;
+      GPS_HIP(h, hipMemcpyAsync(T.data(), h->dG1.p, T.size() * 8, hipMemcpyDeviceToHost, h->stream));
+      GPS_HIP(h, hipStreamSynchronize(h->stream));
+      if (ndim_in == 2) {
+        for (i64 a = 0; a < m; ++a) grad_q_sqrt_out[a * k + q] = T[(size_t)a * mp + a];
+      } else {
+        double* gq = grad_q_sqrt_out + (size_t)q * m * m;
+        for (i64 a = 0; a < m; ++a) for (i64 b = 0; b < m; ++b) gq[a * m + b] = (b <= a) ? T[(size_t)a * mp + b] : 0.0;
+      }
+      std::fill(T.begin(), T.end(), 0.0);
+      for (i64 a = 0; a < m; ++a) for (i64 b = 0; b <= a; ++b) T[(size_t)a * mp + b] = Lwq[a * m + b];
+      GPS_HIP(h, hipMemcpyAsync(h->dG2.p, T.data(), T.size() * 8, hipMemcpyHostToDevice, h->stream));
+      rc = gps_launch_gemm_nt(h, 2, 1, mp, mp, mp, h->dG1.d(), mp, h->dG2.d(), mp, LmBar, mp);               // += (Lm^-T G_w) L_w^T
+      if (rc) return rc;
+      GPS_HIP(h, hipStreamSynchronize(h->stream));
+    }
+  }
+  rc = gps_launch_tri_map(h, LmBar, mp, mp, 1);
+  if (rc) return rc;
+  // Cholesky adjoint: Kuu_bar = Lm^-T (Phi(P) + Phi(P)^T) Lm^-1 / 2, P = Lm^T Lm_bar   (chol_adjoint2 leaves twice that)
+  GPS_HIP(h, h->dG1.ensure((size_t)mp * mp * 8));
+  GPS_HIP(h, h->dG2.ensure((size_t)mp * mp * 8));
+  double* LmBarT = h->dG1.d();
+  rc = chol_adjoint2(h, bl, U, LmBar, LmBarT, h->dG2.d(), mp);
+  if (rc) return rc;
+  // contractions with the kernel derivatives
+  for (int sI = 0; sI < ns; ++sI) grad_slots[sI] = 0.0;
+  rc = gps_launch_kmat_vjp(h, prog, n_nodes, h->dX.d(), m, h->dXnew.d(), n, d_all, KufBar, nsp, 0, grad_slots);
+  if (rc) return rc;
+  {
+    std::vector<double> uu((size_t)ns, 0.0);
+    rc = gps_launch_kmat_vjp(h, prog, n_nodes, h->dX.d(), m, nullptr, 0, d_all, LmBarT, mp, 0, uu.data());
+    if (rc) return rc;
+    for (int sI = 0; sI < ns; ++sI) grad_slots[sI] += 0.5 * uu[sI];
+  }
+  rc = gps_kdiag_vjp(h, prog, n_nodes, d_all, kdiag_bar, grad_slots);
+  if (rc) return rc;
+  if (grad_Z) {
+    // inducing inputs: Z enters through Kuf = k(Z, X) (cotangent Kuf_bar) and Kuu = k(Z, Z) (cotangent Kuu_bar / 2 on the full
+    // symmetric matrix: both arguments move, which doubles the first-argument gradient); Kdiag and the jitter do not depend on Z
+    for (i64 i = 0; i < m * d_all; ++i) grad_Z[i] = 0.0;
+    rc = gps_launch_kmat_input_vjp(h, prog, n_nodes, h->dX.d(), m, h->dXnew.d(), n, d_all, KufBar, nsp, 1.0, grad_Z);
+    if (rc) return rc;
+    rc = gps_launch_kmat_input_vjp(h, prog, n_nodes, h->dX.d(), m, nullptr, 0, d_all, LmBarT, mp, 1.0, grad_Z);
+    if (rc) return rc;
+  }
+  GPS_HIP(h, hipStreamSynchronize(h->stream));
+  return GPS_OK;
+}
+
 static int svgp_elbo_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
                                   int64_t d_all, double jitter, const double* X, int64_t n, const double* yres,
                                   const double* q_mu, int64_t k, const double* q_sqrt, int q_sqrt_ndim, int white,
@@ -552,7 +711,6 @@ static int svgp_elbo_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int 
   const size_t blk_bytes = (size_t)(mp / GPS_TILE) * GPS_TILE * GPS_TILE * 8;
   HipOps ops{h, h->dLinv.d(), h->dLinv.d() + blk_bytes / 8, (int*)h->dInfo.p};
   Blocked<HipOps> bl(ops);
-  double* Lm = h->dK.d();
   double* Bt = h->dB.d();
   // sum ((y - mu)^2 + var) back out of the variational expectations (likelihoods.py:186-188)
   const double c0 = -0.5 * log(2.0 * M_PI) - 0.5 * log(s2);
@@ -647,109 +805,220 @@ static int svgp_elbo_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int 
     rc = gps_launch_gemm_nt(h, 0, 0, nsp, mp, mp, Bt, mp, Ssum, mp, Abar, mp);                           // Abar^T -= A^T S
     if (rc) return rc;
   }
-  // Kuf_bar^T = Abar^T Lm^-1  (X Lm = Abar^T through U = Lm^T), then Kuf_bar [mp, nsp]
-  GPS_HIP(h, h->dTmp.ensure((size_t)mp * mp * 8));
-  double* U = h->dTmp.d();
-  rc = gps_launch_transpose(h, Lm, mp, mp, mp, U, mp);
+  SvgpTail tl{prog, n_nodes, m, d_all, n, k, ns, unwhite, ndim_in, q_mu, q_sqrt, grad_q_mu, grad_q_sqrt, grad_q_sqrt_out, Abar, Am,
+              -w * (double)k * (double)n / (2.0 * s2), grad_slots, grad_Z};
+  return svgp_grad_tail(h, bl, tl);
+}
+
+// ---- SVGP bound and gradient with a non-Gaussian likelihood (models/svgp.py:108-125; lik.hip for the per-point terms) ----
+// Forward: gps_svgp_elbo's, with the per-point reduction replaced by one likelihood launch over the finished moments.
+static int svgp_lik_forward(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, i64 m, i64 d_all,
+                            double jitter, const double* X, i64 n, const double* q_mu, i64 k, const double* q_sqrt,
+                            int q_sqrt_ndim, int white, SvgpAcc& sv, int* info) {
+  GPS_HIP(h, hipSetDevice(h->device));
+  h->have_factor = false; h->factor_gen++; h->dist_have_part_factor = false; h->n = 0;
+  h->refine_now = (h->leaf_refine != 0);
+  if (info) *info = 0;
+  CondIn c;
+  c.m = m; c.mp = gps_pad(m); c.n_new = n; c.nsp = gps_pad(n); c.k = k;
+  const size_t blk_bytes = (size_t)(c.mp / GPS_TILE) * GPS_TILE * GPS_TILE * 8;
+  GPS_HIP(h, h->dX.ensure((size_t)m * d_all * 8));
+  GPS_HIP(h, hipMemcpyAsync(h->dX.p, Z, (size_t)m * d_all * 8, hipMemcpyHostToDevice, h->stream));
+  GPS_HIP(h, h->dXnew.ensure((size_t)n * d_all * 8));
+  GPS_HIP(h, hipMemcpyAsync(h->dXnew.p, X, (size_t)n * d_all * 8, hipMemcpyHostToDevice, h->stream));
+  GPS_HIP(h, h->dK.ensure((size_t)c.mp * c.mp * 8));
+  GPS_HIP(h, h->dLinv.ensure(2 * blk_bytes));
+  GPS_HIP(h, h->dB.ensure((size_t)c.nsp * c.mp * 8));
+  c.Kmm = h->dK.d(); c.Bt = h->dB.d(); c.linv = h->dLinv.d(); c.linvT = h->dLinv.d() + blk_bytes / 8;
+  int rc = gps_launch_kmat(h, prog, n_nodes, h->dX.d(), m, nullptr, m, d_all, jitter, c.Kmm, c.mp, c.mp, c.mp, 1, 1);
   if (rc) return rc;
-  rc = gps_launch_tri_map(h, U, mp, mp, 3);            // (above the diagonal blocks the factor's buffer was never written)
+  rc = gps_launch_kmat(h, prog, n_nodes, h->dXnew.d(), n, h->dX.d(), m, d_all, 0.0, c.Bt, c.mp, c.nsp, c.mp, 0, 0);
   if (rc) return rc;
-  rc = bl.trsm_rn_rec(U, mp, mp, 0, Abar, mp, nsp);
+  c.dKnnDiag = nullptr; c.dKnnFull = nullptr; c.knn_const = 0.0;
+  rc = gps_launch_kdiag(h, prog, n_nodes, &c.knn_const);
   if (rc) return rc;
-  GPS_HIP(h, h->dS1.ensure((size_t)mp * nsp * 8));
-  double* KufBar = h->dS1.d();
-  rc = gps_launch_transpose(h, Abar, mp, nsp, mp, KufBar, nsp);
+  return conditional_tail(h, c, q_mu, q_sqrt, q_sqrt_ndim, white, 0, nullptr, nullptr, info, &sv);
+}
+
+extern "C" int gps_svgp_elbo_lik(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
+                                 int64_t d_all, double jitter, const double* X, int64_t n, const double* Y, const double* mean,
+                                 const double* q_mu, int64_t k, const double* q_sqrt, int q_sqrt_ndim, int white,
+                                 const gps_lik_t* lik, double scale, double* elbo, double* kl_out, double* var_exp_sum, int* info) {
+  return with_la_retry(h, [&]() -> int {
+  if (!h || !Z || !X || !Y || !q_mu || !q_sqrt || !lik || !elbo || m <= 0 || n <= 0 || k <= 0 || d_all <= 0)
+    return gps_fail(h, GPS_ERR_ARG, "gps_svgp_elbo_lik: bad argument");
+  if (q_sqrt_ndim != 2 && q_sqrt_ndim != 3) return gps_fail(h, GPS_ERR_ARG, "gps_svgp_elbo_lik: q_sqrt_ndim must be 2 or 3");
+  if (k > GPS_TILE) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gps_svgp_elbo_lik: at most 128 latent functions");
+  LikHost LH;
+  int rc = gps_lik_prepare(h, lik, k, &LH);
   if (rc) return rc;
-  // Lm_bar = -tril(Kuf_bar A^T)
-  GPS_HIP(h, h->dS3.ensure((size_t)mp * mp * 8));
-  double* LmBar = h->dS3.d();
-  rc = gps_launch_gemm_nt(h, 1, 1, mp, mp, nsp, KufBar, nsp, Am, nsp, LmBar, mp);
+  SvgpAcc sv; sv.yres = Y; sv.noise_var = 0.0; sv.lik = &LH; sv.mean = mean; sv.scale = scale;
+  sv.ky = (lik->kind == GPS_LIK_MULTICLASS) ? 1 : k;
+  int linfo = 0;
+  rc = svgp_lik_forward(h, prog, n_nodes, Z, m, d_all, jitter, X, n, q_mu, k, q_sqrt, q_sqrt_ndim, white, sv, &linfo);
+  if (info) *info = linfo;
+  if (rc || linfo) return rc;
+  if (var_exp_sum) *var_exp_sum = sv.ve;
+  if (kl_out) *kl_out = sv.kl;
+  *elbo = sv.ve * scale - h->svgp_kl_weight * sv.kl;
+  return GPS_OK;
+  });
+}
+
+// Backward pass for per-point cotangents.  With the forward pass of gps_svgp_elbo (whitened form; white == 0 goes through
+// svgp_whiten and the pull-back of svgp_grad_tail like the Gaussian) and, per point i and latent q,
+//   E[i][q] = scale d var_exp_i / d fmean[i][q] ,  H[i][q] = scale d var_exp_i / d fvar[i][q]           (lik.hip)
+//   g(q_mu) = A E - klw q_mu ;  grad_mean = E ;  Kdiag_bar = sum_iq H[i][q]
+//   Abar^T  = E q_mu^T + 2 sum_q diag(H_q) A^T (L_q L_q^T - I)        (the -I part and a diagonal q_sqrt: one row / column scaling;
+//                                                                      a full q_sqrt: one [n, m] x [m, m] product PER LATENT)
+//   g(L_q)  = tril(2 (A diag(H_q) A^T) L_q) + klw (-L_q + diag(1 / L_q,ii))   (one long product per latent; diagonal q_sqrt: its
+//                                                                      diagonal only, sum_i A[j][i]^2 H[i][q], one pass over A)
+// The Gaussian's H = -scale / (2 s2) is constant, which is what lets gps_svgp_elbo_grad fold all latents into one product; with
+// that H these formulas are the ones above svgp_whiten (tests/test_gpu_lik.py checks the identity through GPS_LIK_GAUSSIAN).
+static int svgp_elbo_lik_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
+                                   int64_t d_all, double jitter, const double* X, int64_t n, const double* Y, const double* mean,
+                                   const double* q_mu, int64_t k, const double* q_sqrt, int q_sqrt_ndim, int white,
+                                   const gps_lik_t* lik, double scale, double* elbo, double* grad_slots, int n_slots_cap,
+                                   int* n_slots_out, double* grad_lik, double* grad_q_mu, double* grad_q_sqrt,
+                                   double* grad_mean, double* grad_Z, int* info) {
+  if (!h || !elbo || !grad_slots || !grad_q_mu || !grad_q_sqrt || !lik)
+    return gps_fail(h, GPS_ERR_ARG, "gps_svgp_elbo_lik_grad: bad argument");
+  if (h->allreduce) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gps_svgp_elbo_lik_grad: not available with the data sharded over ranks");
+  if (k > GPS_TILE) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gps_svgp_elbo_lik_grad: at most 128 latent functions");
+  if (!Z || !X || !Y || !q_mu || !q_sqrt || m <= 0 || n <= 0 || k <= 0 || d_all <= 0 || (q_sqrt_ndim != 2 && q_sqrt_ndim != 3))
+    return gps_fail(h, GPS_ERR_ARG, "gps_svgp_elbo_lik_grad: bad argument");
+  LikHost LH;
+  int rc = gps_lik_prepare(h, lik, k, &LH);
   if (rc) return rc;
+  int ns = 0;
+  rc = gps_grad_general_slots(h, prog, n_nodes, &ns);
+  if (rc) return rc;
+  if (n_slots_out) *n_slots_out = ns;
+  if (ns > n_slots_cap) return gps_fail(h, GPS_ERR_ARG, "gps_svgp_elbo_lik_grad: grad_slots too small");
+  int linfo = 0;
+  const bool unwhite = !white;
+  const int ndim_in = q_sqrt_ndim;
+  double* const grad_q_sqrt_out = grad_q_sqrt;
+  std::vector<double> mw_h, Lw_h, gw_tmp;
   if (unwhite) {
-    // pull-back of (g_w, G_w) through m_w = Lm^-1 q_mu, L_w = Lm^-1 L_q; their dependence on Lm joins Lm_bar (still
-    // un-negated here: Lm_bar = -tril(Kuf_bar A^T + g(q_mu) m_w^T + sum_q (Lm^-T G_w,q) L_w,q^T))
-    std::vector<double> buf((size_t)GPS_TILE * mp, 0.0);
-    for (i64 j = 0; j < m; ++j) for (i64 q = 0; q < k; ++q) buf[(size_t)q * mp + j] = grad_q_mu[j * k + q];
-    GPS_HIP(h, h->dG3.ensure(buf.size() * 8));
-    GPS_HIP(h, hipMemcpyAsync(h->dG3.p, buf.data(), buf.size() * 8, hipMemcpyHostToDevice, h->stream));
-    rc = bl.trsm_rn_rec(U, mp, mp, 0, h->dG3.d(), mp, GPS_TILE);                       // rows: g_w^T Lm^-1 = (Lm^-T g_w)^T
-    if (rc) return rc;
-    GPS_HIP(h, hipMemcpyAsync(buf.data(), h->dG3.p, buf.size() * 8, hipMemcpyDeviceToHost, h->stream));
-    GPS_HIP(h, hipStreamSynchronize(h->stream));
-    std::vector<double> ga((size_t)mp * GPS_TILE, 0.0), mb((size_t)mp * GPS_TILE, 0.0);
-    for (i64 j = 0; j < m; ++j)
-      for (i64 q = 0; q < k; ++q) {
-        const double g = buf[(size_t)q * mp + j];
-        grad_q_mu[j * k + q] = g;
-        ga[(size_t)j * GPS_TILE + q] = g;
-        mb[(size_t)j * GPS_TILE + q] = q_mu[j * k + q];
-      }
-    GPS_HIP(h, h->dG1.ensure((size_t)mp * mp * 8));
-    GPS_HIP(h, h->dG2.ensure((size_t)mp * mp * 8));
-    GPS_HIP(h, h->dTmp2.ensure((size_t)mp * mp * 8));
-    GPS_HIP(h, hipMemcpyAsync(h->dG1.p, ga.data(), ga.size() * 8, hipMemcpyHostToDevice, h->stream));
-    GPS_HIP(h, hipMemcpyAsync(h->dG2.p, mb.data(), mb.size() * 8, hipMemcpyHostToDevice, h->stream));
-    rc = gps_launch_gemm_nt(h, 2, 1, mp, mp, GPS_TILE, h->dG1.d(), GPS_TILE, h->dG2.d(), GPS_TILE, LmBar, mp);   // += g(q_mu) m_w^T
-    if (rc) return rc;
-    GPS_HIP(h, hipStreamSynchronize(h->stream));
-    std::vector<double> T((size_t)mp * mp);
-    for (i64 q = 0; q < k; ++q) {
-      const double* Gw = grad_q_sqrt + (size_t)q * m * m;              // whitened gradient, lower triangular [m][m]
-      const double* Lwq = q_sqrt + (size_t)q * m * m;
-      std::fill(T.begin(), T.end(), 0.0);
-      for (i64 a = 0; a < m; ++a) for (i64 b = 0; b <= a; ++b) T[(size_t)b * mp + a] = Gw[a * m + b];      // G_w^T
-      GPS_HIP(h, hipMemcpyAsync(h->dTmp2.p, T.data(), T.size() * 8, hipMemcpyHostToDevice, h->stream));
-      rc = bl.trsm_rn_rec(U, mp, mp, 0, h->dTmp2.d(), mp, mp);                          // (Lm^-T G_w)^T
-      if (rc) return rc;
-      rc = gps_launch_transpose(h, h->dTmp2.d(), mp, mp, mp, h->dG1.d(), mp);          // Lm^-T G_w
-      if (rc) return rc;
-      GPS_HIP(h, hipMemcpyAsync(T.data(), h->dG1.p, T.size() * 8, hipMemcpyDeviceToHost, h->stream));
-      GPS_HIP(h, hipStreamSynchronize(h->stream));
-      if (ndim_in == 2) {
-        for (i64 a = 0; a < m; ++a) grad_q_sqrt_out[a * k + q] = T[(size_t)a * mp + a];
-      } else {
-        double* gq = grad_q_sqrt_out + (size_t)q * m * m;
-        for (i64 a = 0; a < m; ++a) for (i64 b = 0; b < m; ++b) gq[a * m + b] = (b <= a) ? T[(size_t)a * mp + b] : 0.0;
-      }
-      std::fill(T.begin(), T.end(), 0.0);
-      for (i64 a = 0; a < m; ++a) for (i64 b = 0; b <= a; ++b) T[(size_t)a * mp + b] = Lwq[a * m + b];
-      GPS_HIP(h, hipMemcpyAsync(h->dG2.p, T.data(), T.size() * 8, hipMemcpyHostToDevice, h->stream));
-      rc = gps_launch_gemm_nt(h, 2, 1, mp, mp, mp, h->dG1.d(), mp, h->dG2.d(), mp, LmBar, mp);               // += (Lm^-T G_w) L_w^T
-      if (rc) return rc;
-      GPS_HIP(h, hipStreamSynchronize(h->stream));
-    }
+    rc = svgp_whiten(h, prog, n_nodes, Z, m, d_all, jitter, q_mu, k, q_sqrt, q_sqrt_ndim, mw_h, Lw_h, &linfo);
+    if (info) *info = linfo;
+    if (rc || linfo) return rc;
+    q_mu = mw_h.data(); q_sqrt = Lw_h.data(); q_sqrt_ndim = 3;
+    if (ndim_in == 2) { gw_tmp.assign((size_t)k * m * m, 0.0); grad_q_sqrt = gw_tmp.data(); }
   }
-  rc = gps_launch_tri_map(h, LmBar, mp, mp, 1);
-  if (rc) return rc;
-  // Cholesky adjoint: Kuu_bar = Lm^-T (Phi(P) + Phi(P)^T) Lm^-1 / 2, P = Lm^T Lm_bar   (chol_adjoint2 leaves twice that)
-  GPS_HIP(h, h->dG1.ensure((size_t)mp * mp * 8));
-  GPS_HIP(h, h->dG2.ensure((size_t)mp * mp * 8));
-  double* LmBarT = h->dG1.d();
-  rc = chol_adjoint2(h, bl, U, LmBar, LmBarT, h->dG2.d(), mp);
-  if (rc) return rc;
-  // contractions with the kernel derivatives
-  for (int sI = 0; sI < ns; ++sI) grad_slots[sI] = 0.0;
-  rc = gps_launch_kmat_vjp(h, prog, n_nodes, h->dX.d(), m, h->dXnew.d(), n, d_all, KufBar, nsp, 0, grad_slots);
-  if (rc) return rc;
-  {
-    std::vector<double> uu((size_t)ns, 0.0);
-    rc = gps_launch_kmat_vjp(h, prog, n_nodes, h->dX.d(), m, nullptr, 0, d_all, LmBarT, mp, 0, uu.data());
+  SvgpAcc sv; sv.yres = Y; sv.noise_var = 0.0; sv.lik = &LH; sv.mean = mean; sv.scale = scale; sv.want_grad = 1;
+  sv.ky = (lik->kind == GPS_LIK_MULTICLASS) ? 1 : k;
+  rc = svgp_lik_forward(h, prog, n_nodes, Z, m, d_all, jitter, X, n, q_mu, k, q_sqrt, q_sqrt_ndim, 1, sv, &linfo);
+  if (info) *info = linfo;
+  if (rc || linfo) return rc;
+  const double klw = h->svgp_kl_weight;
+  *elbo = sv.ve * scale - klw * sv.kl;
+  if (grad_lik) *grad_lik = scale * sv.dparam;
+  // on the device now: dK = Lm, dLinv (+T), dB = A^T [nsp, mp], dX = Z, dXnew = X, dA = E^T, dLikH = H^T (both [k][nsp], zero padded)
+  const i64 mp = gps_pad(m), nsp = gps_pad(n);
+  const size_t blk_bytes = (size_t)(mp / GPS_TILE) * GPS_TILE * GPS_TILE * 8;
+  HipOps ops{h, h->dLinv.d(), h->dLinv.d() + blk_bytes / 8, (int*)h->dInfo.p};
+  Blocked<HipOps> bl(ops);
+  double* Bt = h->dB.d();
+  double* Et = h->dA.d();
+  double* Ht = h->dLikH.d();
+  if (grad_mean) {                                       // d ELBO / d mean_function(X) = E   [n, k]
+    GPS_HIP(h, h->dTmp2.ensure((size_t)n * k * 8));
+    rc = gps_launch_transpose(h, Et, nsp, k, n, h->dTmp2.d(), k);
     if (rc) return rc;
-    for (int sI = 0; sI < ns; ++sI) grad_slots[sI] += 0.5 * uu[sI];
+    GPS_HIP(h, hipMemcpyAsync(grad_mean, h->dTmp2.p, (size_t)n * k * 8, hipMemcpyDeviceToHost, h->stream));
   }
-  rc = gps_kdiag_vjp(h, prog, n_nodes, d_all, -w * (double)k * (double)n / (2.0 * s2), grad_slots);
+  GPS_HIP(h, h->dS2.ensure((size_t)mp * nsp * 8));
+  double* Am = h->dS2.d();
+  rc = gps_launch_transpose(h, Bt, mp, nsp, mp, Am, nsp);
   if (rc) return rc;
-  if (grad_Z) {
-    // inducing inputs: Z enters through Kuf = k(Z, X) (cotangent Kuf_bar) and Kuu = k(Z, Z) (cotangent Kuu_bar / 2 on the full
-    // symmetric matrix: both arguments move, which doubles the first-argument gradient); Kdiag and the jitter do not depend on Z
-    for (i64 i = 0; i < m * d_all; ++i) grad_Z[i] = 0.0;
-    rc = gps_launch_kmat_input_vjp(h, prog, n_nodes, h->dX.d(), m, h->dXnew.d(), n, d_all, KufBar, nsp, 1.0, grad_Z);
+  GPS_HIP(h, h->dG4.ensure((size_t)(2 * mp * k + mp) * 8));
+  double* dAE = h->dG4.d();
+  double* dDiag = dAE + (size_t)mp * k;
+  double* dRS = dDiag + mp;
+  rc = gps_launch_rowdot(h, Am, nsp, m, nsp, Et, nsp, k, dAE, dDiag);
+  if (rc) return rc;
+  std::vector<double> hAE((size_t)m * k), hRS;
+  GPS_HIP(h, hipMemcpyAsync(hAE.data(), dAE, hAE.size() * 8, hipMemcpyDeviceToHost, h->stream));
+  if (q_sqrt_ndim == 2) {
+    rc = gps_launch_lik_rowsq(h, Am, nsp, m, nsp, Ht, nsp, k, dRS);
     if (rc) return rc;
-    rc = gps_launch_kmat_input_vjp(h, prog, n_nodes, h->dX.d(), m, nullptr, 0, d_all, LmBarT, mp, 1.0, grad_Z);
-    if (rc) return rc;
+    hRS.resize((size_t)m * k);
+    GPS_HIP(h, hipMemcpyAsync(hRS.data(), dRS, hRS.size() * 8, hipMemcpyDeviceToHost, h->stream));
   }
   GPS_HIP(h, hipStreamSynchronize(h->stream));
-  return GPS_OK;
+  for (i64 i = 0; i < m * k; ++i) grad_q_mu[i] = hAE[i] - klw * q_mu[i];
+
+  // Abar^T [nsp, mp]: the part that needs no product
+  std::vector<double> up((size_t)2 * mp * k, 0.0);          // q_mu [mp][k] | c [mp][k]
+  for (i64 j = 0; j < m; ++j)
+    for (i64 q = 0; q < k; ++q) {
+      up[j * k + q] = q_mu[j * k + q];
+      up[(size_t)mp * k + j * k + q] = (q_sqrt_ndim == 2) ? q_sqrt[j * k + q] * q_sqrt[j * k + q] - 1.0 : -1.0;
+    }
+  GPS_HIP(h, h->dG3.ensure(up.size() * 8));
+  GPS_HIP(h, hipMemcpyAsync(h->dG3.p, up.data(), up.size() * 8, hipMemcpyHostToDevice, h->stream));
+  GPS_HIP(h, hipStreamSynchronize(h->stream));
+  GPS_HIP(h, h->dY.ensure((size_t)nsp * mp * 8));
+  double* Abar = h->dY.d();
+  rc = gps_launch_lik_abar(h, Bt, mp, nsp, mp, Et, Ht, nsp, h->dG3.d(), h->dG3.d() + (size_t)mp * k, k, Abar);
+  if (rc) return rc;
+
+  if (q_sqrt_ndim == 2) {
+    for (i64 j = 0; j < m; ++j)
+      for (i64 q = 0; q < k; ++q) {
+        const double s = q_sqrt[j * k + q];
+        grad_q_sqrt[j * k + q] = 2.0 * hRS[j * k + q] * s + klw * (-s + 1.0 / s);
+      }
+  } else {
+    GPS_HIP(h, h->dS3.ensure((size_t)mp * mp * 8));
+    GPS_HIP(h, h->dTmp.ensure((size_t)mp * mp * 8));
+    GPS_HIP(h, h->dTmp2.ensure((size_t)mp * mp * 8));
+    GPS_HIP(h, h->dG1.ensure((size_t)mp * mp * 8));
+    GPS_HIP(h, h->dG2.ensure((size_t)mp * mp * 8));
+    GPS_HIP(h, h->dTmp3.ensure((size_t)mp * nsp * 8));
+    double* W = h->dS3.d();
+    double* Sq = h->dG2.d();
+    double* big = h->dTmp3.d();                                       // [mp, nsp], then [nsp, mp]
+    std::vector<double> G((size_t)mp * mp);
+    for (i64 q = 0; q < k; ++q) {
+      const double* Lq = q_sqrt + (size_t)q * m * m;                  // C-ABI layout [k][m][m]
+      const double* Hq = Ht + (size_t)q * nsp;
+      rc = upload_tril(h, Lq, m, h->dTmp2.d(), mp, 1.0, 1);           // L_q^T
+      if (!rc) rc = gps_launch_tril_pad(h, h->dStage.d(), m, h->dTmp.d(), mp, 1.0, 0);      // L_q
+      if (rc) return rc;
+      rc = gps_launch_gemm_nt(h, 1, 0, mp, mp, mp, h->dTmp.d(), mp, h->dTmp.d(), mp, Sq, mp);              // S_q = L_q L_q^T
+      if (rc) return rc;
+      rc = gps_launch_scale_cols(h, Am, nsp, mp, nsp, Hq, big, nsp);                                        // A diag(H_q)
+      if (rc) return rc;
+      rc = gps_launch_gemm_nt(h, 1, 0, mp, mp, nsp, big, nsp, Am, nsp, W, mp);                             // A diag(H_q) A^T
+      if (rc) return rc;
+      rc = gps_launch_gemm_nt(h, 1, 0, mp, mp, mp, W, mp, h->dTmp2.d(), mp, h->dG1.d(), mp);               // (A diag(H_q) A^T) L_q
+      if (rc) return rc;
+      GPS_HIP(h, hipMemcpyAsync(G.data(), h->dG1.p, (size_t)mp * mp * 8, hipMemcpyDeviceToHost, h->stream));
+      rc = gps_launch_gemm_nt(h, 1, 0, nsp, mp, mp, Bt, mp, Sq, mp, big, mp);                              // A^T S_q
+      if (rc) return rc;
+      rc = gps_launch_lik_rows_axpy(h, Abar, big, mp, nsp, mp, Hq);                                        // Abar^T += 2 diag(H_q) A^T S_q
+      if (rc) return rc;
+      GPS_HIP(h, hipStreamSynchronize(h->stream));
+      double* gq = grad_q_sqrt + (size_t)q * m * m;
+      for (i64 a = 0; a < m; ++a)
+        for (i64 b = 0; b < m; ++b)
+          gq[a * m + b] = (b > a) ? 0.0 : (2.0 * G[(size_t)a * mp + b] + klw * (-Lq[a * m + b] + (a == b ? 1.0 / Lq[a * m + a] : 0.0)));
+    }
+  }
+  SvgpTail tl{prog, n_nodes, m, d_all, n, k, ns, unwhite, ndim_in, q_mu, q_sqrt, grad_q_mu, grad_q_sqrt, grad_q_sqrt_out, Abar, Am,
+              sv.hsum, grad_slots, grad_Z};
+  return svgp_grad_tail(h, bl, tl);
+}
+extern "C" int gps_svgp_elbo_lik_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
+                                      int64_t d_all, double jitter, const double* X, int64_t n, const double* Y, const double* mean,
+                                      const double* q_mu, int64_t k, const double* q_sqrt, int q_sqrt_ndim, int white,
+                                      const gps_lik_t* lik, double scale, double* elbo, double* grad_slots, int n_slots_cap,
+                                      int* n_slots_out, double* grad_lik, double* grad_q_mu, double* grad_q_sqrt,
+                                      double* grad_mean, double* grad_Z, int* info) {
+  return with_la_retry(h, [&]() -> int { return svgp_elbo_lik_grad_body(h, prog, n_nodes, Z, m, d_all, jitter, X, n, Y, mean, q_mu, k, q_sqrt, q_sqrt_ndim, white, lik, scale, elbo, grad_slots, n_slots_cap, n_slots_out, grad_lik, grad_q_mu, grad_q_sqrt, grad_mean, grad_Z, info); });
 }
 
 // ---- vector-Jacobian product of kernels.K: grad_slots = sum_ij W[i][j] d k(X_i, X2_j) / d theta ---------------------------

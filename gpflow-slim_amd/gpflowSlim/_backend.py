@@ -35,6 +35,37 @@ class KernNode(ctypes.Structure):
                 ("lengthscales", ctypes.c_double * GPS_MAX_DIMS)]
 
 
+class LikDesc(ctypes.Structure):
+    """gps_lik_t"""
+    _fields_ = [("kind", ctypes.c_int),
+                ("n_gh", ctypes.c_int),
+                ("param", ctypes.c_double * 4),
+                ("gh_x", ctypes.POINTER(ctypes.c_double)),
+                ("gh_w", ctypes.POINTER(ctypes.c_double))]
+
+
+LIK_MAX_GH = 64
+LIK_MULTICLASS = 5
+
+
+def make_lik(kind, params=(), n_gh=20):
+    """A gps_lik_t (and the arrays it points into, which the caller keeps alive): kind of include/gpflowslim_hip.h, up to four
+    scalar parameters, and the Gauss-Hermite rule computed here exactly as the reference does (numpy's hermgauss)."""
+    params = [float(v) for v in params]
+    if len(params) > 4:
+        raise ValueError("a likelihood has at most four scalar parameters")
+    if not 1 <= int(n_gh) <= LIK_MAX_GH:
+        raise ValueError("the device likelihoods take 1..%d Gauss-Hermite points, got %d" % (LIK_MAX_GH, n_gh))
+    gx, gw = np.polynomial.hermite.hermgauss(int(n_gh))
+    gx, gw = np.ascontiguousarray(gx, dtype=np.float64), np.ascontiguousarray(gw, dtype=np.float64)
+    d = LikDesc()
+    d.kind, d.n_gh = int(kind), int(n_gh)
+    for i in range(4):
+        d.param[i] = params[i] if i < len(params) else 0.0
+    d.gh_x, d.gh_w = gx.ctypes.data_as(_c_double_p), gw.ctypes.data_as(_c_double_p)
+    return d, (gx, gw)
+
+
 def lib_path():
     env = os.environ.get("GPFLOWSLIM_HIP_LIB")
     if env:
@@ -73,6 +104,15 @@ _SIGNATURES = {
                            _c_double_p, _i64, _c_double_p, _c_double_p, _i64, _c_double_p, ctypes.c_int, ctypes.c_int,
                            ctypes.c_double, ctypes.c_double, _c_double_p, _c_double_p, ctypes.c_int, _c_int_p, _c_double_p,
                            _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_int_p],
+    "gps_lik_varexp": [ctypes.c_void_p, ctypes.POINTER(LikDesc), _c_double_p, _c_double_p, _c_double_p, _i64, _i64, _c_double_p,
+                       _c_double_p, _c_double_p, _c_double_p],
+    "gps_svgp_elbo_lik": [ctypes.c_void_p, ctypes.POINTER(KernNode), ctypes.c_int, _c_double_p, _i64, _i64, ctypes.c_double,
+                          _c_double_p, _i64, _c_double_p, _c_double_p, _c_double_p, _i64, _c_double_p, ctypes.c_int, ctypes.c_int,
+                          ctypes.POINTER(LikDesc), ctypes.c_double, _c_double_p, _c_double_p, _c_double_p, _c_int_p],
+    "gps_svgp_elbo_lik_grad": [ctypes.c_void_p, ctypes.POINTER(KernNode), ctypes.c_int, _c_double_p, _i64, _i64, ctypes.c_double,
+                               _c_double_p, _i64, _c_double_p, _c_double_p, _c_double_p, _i64, _c_double_p, ctypes.c_int,
+                               ctypes.c_int, ctypes.POINTER(LikDesc), ctypes.c_double, _c_double_p, _c_double_p, ctypes.c_int,
+                               _c_int_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_int_p],
     "gps_kmat_vjp": [ctypes.c_void_p, ctypes.POINTER(KernNode), ctypes.c_int, _c_double_p, _i64, _c_double_p, _i64, _i64,
                      _c_double_p, _c_double_p, ctypes.c_int, _c_int_p],
     "gps_kmat_input_vjp": [ctypes.c_void_p, ctypes.POINTER(KernNode), ctypes.c_int, _c_double_p, _i64, _c_double_p, _i64, _i64,
@@ -919,6 +959,92 @@ class Handle(object):
         if want_grad_Z:
             return elbo.value, slots[:nslots.value].copy(), gnoise.value, g_qmu, g_q, g_mean, g_Z
         return elbo.value, slots[:nslots.value].copy(), gnoise.value, g_qmu, g_q, g_mean
+
+    def lik_varexp(self, lik, Fmu, Fvar, Y, want_grad=False):
+        """Sum over points and latents of the variational expectations of a device likelihood (``lik`` from make_lik) for
+        q(f) = N(Fmu, Fvar), both [N, K]; Y [N, K] ([N] or [N, 1] class labels for MultiClass).  want_grad: also
+        (dmu [N, K], dvar [N, K], d sum / d parameter 0)."""
+        desc, keep = lik
+        Fmu, Fvar, Y = _f64(Fmu), _f64(Fvar), _f64(Y)
+        _need(Fmu.ndim == 2 and Fvar.shape == Fmu.shape, "Fmu and Fvar must both be [N, K]")
+        n, k = Fmu.shape
+        _need(n > 0 and k > 0, "empty moments")
+        _need(Y.size == (n if desc.kind == LIK_MULTICLASS else n * k), "Y must be [N, K] (one label per point for MultiClass)")
+        ve, dpar = ctypes.c_double(0), ctypes.c_double(0)
+        dmu = np.zeros((n, k)) if want_grad else None
+        dvar = np.zeros((n, k)) if want_grad else None
+        self._check(self._lib.gps_lik_varexp(self._h, ctypes.byref(desc), _ptr(Fmu), _ptr(Fvar), _ptr(Y), n, k, ctypes.byref(ve),
+                                             _ptr(dmu) if want_grad else None, _ptr(dvar) if want_grad else None,
+                                             ctypes.byref(dpar) if want_grad else None), "gps_lik_varexp")
+        del keep
+        if want_grad:
+            return ve.value, dmu, dvar, dpar.value
+        return ve.value
+
+    def _svgp_lik_args(self, lik, Z, X, Y, mean, q_mu, q_sqrt):
+        desc, _ = lik
+        Z, X, Y, q_mu = _f64(Z), _f64(X), _f64(Y), _f64(q_mu)
+        _need(Z.ndim == 2 and X.ndim == 2 and Z.shape[1] == X.shape[1], "Z [M, D] and X [N, D] must share D")
+        m, d = Z.shape
+        n = X.shape[0]
+        _need(q_mu.ndim == 2 and q_mu.shape[0] == m, "q_mu must be [M, K]")
+        k = q_mu.shape[1]
+        _need(m > 0 and n > 0 and k > 0, "empty SVGP problem")
+        if desc.kind == LIK_MULTICLASS:
+            _need(Y.size == n, "MultiClass takes one class label per point")
+            _need(np.all(Y == np.floor(Y)) and Y.min() >= 0 and Y.max() < k, "class labels must be integers in [0, K)")
+        else:
+            _need(Y.shape == (n, k), "Y must be [N, K] with K = number of latent functions")
+        if mean is not None:
+            mean = _f64(np.broadcast_to(mean, (n, k)))
+        q, qnd = self._prep_q_sqrt(q_sqrt)
+        _need(q is not None, "SVGP needs q_sqrt")
+        self._check_q_sqrt(q, qnd, m, k)
+        return desc, Z, X, Y, mean, q_mu, q, qnd, m, d, n, k
+
+    def svgp_elbo_lik(self, prog, Z, X, Y, q_mu, q_sqrt, jitter, lik, mean=None, white=True, scale=1.0):
+        """(elbo, kl, sum of variational expectations) of models/svgp.py:108-125 for a device likelihood (make_lik); mean:
+        mean_function(X) [N, K] or None."""
+        desc, Z, X, Y, mean, q_mu, q, qnd, m, d, n, k = self._svgp_lik_args(lik, Z, X, Y, mean, q_mu, q_sqrt)
+        elbo, kl, ve = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0)
+        info = ctypes.c_int(0)
+        self.resident_token = None
+        self.factor_key = None
+        self._check(self._lib.gps_svgp_elbo_lik(self._h, prog, len(prog), _ptr(Z), m, d, float(jitter), _ptr(X), n, _ptr(Y),
+                                                _ptr(mean) if mean is not None else None, _ptr(q_mu), k, _ptr(q), qnd,
+                                                1 if white else 0, ctypes.byref(desc), float(scale), ctypes.byref(elbo),
+                                                ctypes.byref(kl), ctypes.byref(ve), ctypes.byref(info)), "gps_svgp_elbo_lik")
+        if info.value > 0:
+            raise NotPositiveDefiniteError("Kuu + jitter*I is not positive definite (leading minor of order %d)" % info.value)
+        return elbo.value, kl.value, ve.value
+
+    def svgp_elbo_lik_grad(self, prog, Z, X, Y, q_mu, q_sqrt, jitter, lik, mean=None, white=True, scale=1.0, want_grad_Z=False):
+        """svgp_elbo_grad for a device likelihood: (elbo, grad_slots, d/d likelihood parameter 0, grad_q_mu, grad_q_sqrt,
+        d/d mean(X) [N, K][, grad_Z])."""
+        desc, Z, X, Y, mean, q_mu, q, qnd, m, d, n, k = self._svgp_lik_args(lik, Z, X, Y, mean, q_mu, q_sqrt)
+        elbo, glik = ctypes.c_double(0), ctypes.c_double(0)
+        info, nslots = ctypes.c_int(0), ctypes.c_int(0)
+        cap = 700
+        slots = np.zeros(cap)
+        g_qmu = np.zeros((m, k))
+        g_q = np.zeros_like(q)
+        g_mean = np.zeros((n, k))
+        g_Z = np.zeros((m, d))
+        self.resident_token = None
+        self.factor_key = None
+        self._check(self._lib.gps_svgp_elbo_lik_grad(self._h, prog, len(prog), _ptr(Z), m, d, float(jitter), _ptr(X), n, _ptr(Y),
+                                                     _ptr(mean) if mean is not None else None, _ptr(q_mu), k, _ptr(q), qnd,
+                                                     1 if white else 0, ctypes.byref(desc), float(scale), ctypes.byref(elbo),
+                                                     _ptr(slots), cap, ctypes.byref(nslots), ctypes.byref(glik), _ptr(g_qmu),
+                                                     _ptr(g_q), _ptr(g_mean), _ptr(g_Z) if want_grad_Z else None,
+                                                     ctypes.byref(info)), "gps_svgp_elbo_lik_grad")
+        if info.value > 0:
+            raise NotPositiveDefiniteError("Kuu + jitter*I is not positive definite (leading minor of order %d)" % info.value)
+        if qnd == 3:
+            g_q = np.ascontiguousarray(np.transpose(g_q, (1, 2, 0)))           # [k, m, m] -> [m, m, k]
+        if want_grad_Z:
+            return elbo.value, slots[:nslots.value].copy(), glik.value, g_qmu, g_q, g_mean, g_Z
+        return elbo.value, slots[:nslots.value].copy(), glik.value, g_qmu, g_q, g_mean
 
     def kmat_input_vjp(self, prog, X, W, X2=None):
         """d/dX sum_ij W[i, j] k(X_i, X2_j)  [N, D]: reverse mode through kern.K(X, X2) with respect to the points X

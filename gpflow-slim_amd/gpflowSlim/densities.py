@@ -1,10 +1,12 @@
-"""Log-densities on the exact-GP path.
+"""Log-densities.
 
-Mirrors gpflowSlim/densities.py: gaussian :24-25, multivariate_normal :73-95.  The triangular
+Mirrors gpflowSlim/densities.py: gaussian :24-25, bernoulli / poisson / exponential / student_t :33-70 (what the
+likelihoods' logp are made of; numpy on the host), multivariate_normal :73-95.  The triangular
 solve of multivariate_normal runs on the GPU (csrc: recursive trsm); the scalar reductions of
 an [N, R] host array stay on the host.
 """
 import numpy as np
+from scipy.special import gammaln
 
 from . import _backend as be
 
@@ -12,6 +14,29 @@ from . import _backend as be
 def gaussian(x, mu, var):
     """densities.py:24-25"""
     return -0.5 * (np.log(2 * np.pi) + np.log(var) + np.square(mu - x) / var)
+
+
+def bernoulli(p, y):
+    """densities.py:33-34"""
+    return np.log(np.where(np.equal(y, 1), p, 1 - p))
+
+
+def poisson(lamb, y):
+    """densities.py:37-38"""
+    return y * np.log(lamb) - lamb - gammaln(y + 1.)
+
+
+def exponential(lamb, y):
+    """densities.py:41-42"""
+    return - y / lamb - np.log(lamb)
+
+
+def student_t(x, mean, scale, deg_free):
+    """densities.py:50-60"""
+    const = gammaln((deg_free + 1.) * 0.5) - gammaln(deg_free * 0.5) \
+        - 0.5 * (np.log(np.square(scale)) + np.log(deg_free) + np.log(np.pi))
+    return const - 0.5 * (deg_free + 1.) * \
+        np.log(1. + (1. / deg_free) * (np.square((x - mean) / scale)))
 
 
 def multivariate_normal(x, mu, L):

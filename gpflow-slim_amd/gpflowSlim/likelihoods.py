@@ -1,18 +1,34 @@
-"""Gaussian likelihood (the only one on the exact-GP path).
+"""Likelihoods.
 
-Mirrors gpflowSlim/likelihoods.py:158-188.
+Mirrors gpflowSlim/likelihoods.py: the generic Gauss-Hermite routines of ``Likelihood`` (:45-152), Gaussian (:158-188),
+Poisson (:191-224), Exponential (:226-243), StudentT (:246-266), probit / Bernoulli (:269-298), RobustMax / MultiClass
+(:379-487).  Everything here is host numpy: it serves prediction (``predict_y`` / ``predict_density`` at modest N*) and is
+the slow path of the SVGP bound for user-defined likelihoods and links.  The built-in classes additionally describe
+themselves to the backend (``_device_spec``): for them the per-point term of the SVGP bound, its derivatives and the whole
+backward pass run on the device (csrc/lik.hip, gps_svgp_elbo_lik / gps_svgp_elbo_lik_grad).
 """
 import numpy as np
+from scipy.special import erf, gammaln
 
 from . import densities
 from . import transforms
 from ._settings import settings
 from .params import Parameter
 
+# kinds of include/gpflowslim_hip.h
+LIK_GAUSSIAN, LIK_BERNOULLI, LIK_POISSON, LIK_EXPONENTIAL, LIK_STUDENT_T, LIK_MULTICLASS = range(6)
+
+
+def hermgauss(n):
+    """quadrature.py: numpy's rule, as the reference takes it"""
+    x, w = np.polynomial.hermite.hermgauss(n)
+    return x.astype(settings.float_type), w.astype(settings.float_type)
+
 
 class Likelihood(object):
     def __init__(self, name='likelihood'):
         self._name = name
+        self.num_gauss_hermite_points = 20
         self._parameters = []
 
     @property
@@ -22,6 +38,56 @@ class Likelihood(object):
     @property
     def parameters(self):
         return self._parameters
+
+    def conditional_mean(self, F):
+        raise NotImplementedError
+
+    def conditional_variance(self, F):
+        raise NotImplementedError
+
+    def logp(self, F, Y):
+        raise NotImplementedError
+
+    def _device_spec(self):
+        """(kind, [up to four scalar parameters], trainable Parameter behind parameter 0 or None) when the device kernels
+        implement this likelihood, else None (host path)."""
+        return None
+
+    def predict_mean_and_var(self, Fmu, Fvar):
+        """likelihoods.py:45-86"""
+        gh_x, gh_w = hermgauss(self.num_gauss_hermite_points)
+        gh_w = gh_w / np.sqrt(np.pi)
+        gh_w = gh_w.reshape(-1, 1)
+        shape = np.shape(Fmu)
+        Fmu, Fvar = [np.reshape(e, (-1, 1)) for e in (Fmu, Fvar)]
+        X = gh_x[None, :] * np.sqrt(2.0 * Fvar) + Fmu
+        E_y = np.reshape(np.matmul(self.conditional_mean(X), gh_w), shape)
+        integrand = self.conditional_variance(X) + np.square(self.conditional_mean(X))
+        V_y = np.reshape(np.matmul(integrand, gh_w), shape) - np.square(E_y)
+        return E_y, V_y
+
+    def predict_density(self, Fmu, Fvar, Y):
+        """likelihoods.py:88-119"""
+        gh_x, gh_w = hermgauss(self.num_gauss_hermite_points)
+        gh_w = gh_w.reshape(-1, 1) / np.sqrt(np.pi)
+        shape = np.shape(Fmu)
+        Fmu, Fvar, Y = [np.reshape(e, (-1, 1)) for e in (Fmu, Fvar, Y)]
+        X = gh_x[None, :] * np.sqrt(2.0 * Fvar) + Fmu
+        Y = np.tile(Y, [1, self.num_gauss_hermite_points])
+        logp = self.logp(X, Y)
+        return np.reshape(np.log(np.matmul(np.exp(logp), gh_w)), shape)
+
+    def variational_expectations(self, Fmu, Fvar, Y):
+        """likelihoods.py:121-152"""
+        gh_x, gh_w = hermgauss(self.num_gauss_hermite_points)
+        gh_x = gh_x.reshape(1, -1)
+        gh_w = gh_w.reshape(-1, 1) / np.sqrt(np.pi)
+        shape = np.shape(Fmu)
+        Fmu, Fvar, Y = [np.reshape(e, (-1, 1)) for e in (Fmu, Fvar, Y)]
+        X = gh_x * np.sqrt(2.0 * Fvar) + Fmu
+        Y = np.tile(Y, [1, self.num_gauss_hermite_points])
+        logp = self.logp(X, Y)
+        return np.reshape(np.matmul(logp, gh_w), shape)
 
 
 class Gaussian(Likelihood):
@@ -56,3 +122,198 @@ class Gaussian(Likelihood):
         """likelihoods.py:186-188"""
         return -0.5 * np.log(2 * np.pi) - 0.5 * np.log(self.variance) \
                - 0.5 * (np.square(Y - Fmu) + Fvar) / self.variance
+
+
+class Poisson(Likelihood):
+    """likelihoods.py:191-224: p(y | f) = Poisson(y | invlink(f) * binsize)"""
+
+    def __init__(self, invlink=np.exp, binsize=1.):
+        Likelihood.__init__(self)
+        self.invlink = invlink
+        self.binsize = np.double(binsize)
+
+    def logp(self, F, Y):
+        return densities.poisson(self.invlink(F) * self.binsize, Y)
+
+    def conditional_variance(self, F):
+        return self.invlink(F) * self.binsize
+
+    def conditional_mean(self, F):
+        return self.invlink(F) * self.binsize
+
+    def variational_expectations(self, Fmu, Fvar, Y):
+        if self.invlink is np.exp:
+            return Y * Fmu - np.exp(Fmu + Fvar / 2) * self.binsize \
+                   - gammaln(Y + 1) + Y * np.log(self.binsize)
+        return super(Poisson, self).variational_expectations(Fmu, Fvar, Y)
+
+    def _device_spec(self):
+        return (LIK_POISSON, [float(self.binsize)], None) if self.invlink is np.exp else None
+
+
+class Exponential(Likelihood):
+    """likelihoods.py:226-243"""
+
+    def __init__(self, invlink=np.exp):
+        super().__init__()
+        self.invlink = invlink
+
+    def logp(self, F, Y):
+        return densities.exponential(self.invlink(F), Y)
+
+    def conditional_mean(self, F):
+        return self.invlink(F)
+
+    def conditional_variance(self, F):
+        return np.square(self.invlink(F))
+
+    def variational_expectations(self, Fmu, Fvar, Y):
+        if self.invlink is np.exp:
+            return - np.exp(-Fmu + Fvar / 2) * Y - Fmu
+        return super().variational_expectations(Fmu, Fvar, Y)
+
+    def _device_spec(self):
+        return (LIK_EXPONENTIAL, [], None) if self.invlink is np.exp else None
+
+
+class StudentT(Likelihood):
+    """likelihoods.py:246-266"""
+
+    def __init__(self, deg_free=3.0):
+        Likelihood.__init__(self)
+        self.deg_free = deg_free
+        self._scale = Parameter(1.0, transform=transforms.positive, dtype=settings.float_type, name='scale')
+        self._parameters = self._parameters + [self._scale]
+
+    @property
+    def scale(self):
+        return self._scale.value
+
+    def logp(self, F, Y):
+        return densities.student_t(Y, F, self.scale, self.deg_free)
+
+    def conditional_mean(self, F):
+        return np.array(F, copy=True)
+
+    def conditional_variance(self, F):
+        return F * 0.0 + (self.deg_free / (self.deg_free - 2.0))
+
+    def _device_spec(self):
+        return (LIK_STUDENT_T, [float(np.squeeze(self.scale)), float(self.deg_free)], self._scale)
+
+
+def probit(x):
+    """likelihoods.py:269-270"""
+    return 0.5 * (1.0 + erf(x / np.sqrt(2.0))) * (1 - 2e-3) + 1e-3
+
+
+class Bernoulli(Likelihood):
+    """likelihoods.py:273-298"""
+
+    def __init__(self, invlink=probit):
+        Likelihood.__init__(self)
+        self.invlink = invlink
+
+    def logp(self, F, Y):
+        return densities.bernoulli(self.invlink(F), Y)
+
+    def predict_mean_and_var(self, Fmu, Fvar):
+        if self.invlink is probit:
+            p = probit(Fmu / np.sqrt(1 + Fvar))
+            return p, p - np.square(p)
+        return Likelihood.predict_mean_and_var(self, Fmu, Fvar)
+
+    def predict_density(self, Fmu, Fvar, Y):
+        p = self.predict_mean_and_var(Fmu, Fvar)[0]
+        return densities.bernoulli(p, Y)
+
+    def conditional_mean(self, F):
+        return self.invlink(F)
+
+    def conditional_variance(self, F):
+        p = self.invlink(F)
+        return p - np.square(p)
+
+    def _device_spec(self):
+        return (LIK_BERNOULLI, [], None) if self.invlink is probit else None
+
+
+class RobustMax(object):
+    """likelihoods.py:379-425: y_i = 1 - eps for i = argmax(f), eps / (k - 1) otherwise."""
+
+    def __init__(self, num_classes, epsilon=1e-3):
+        self.epsilon = epsilon
+        self.num_classes = num_classes
+        self._eps_K1 = self.epsilon / (self.num_classes - 1.)
+
+    def __call__(self, F):
+        i = np.argmax(F, 1)
+        out = np.full((np.shape(F)[0], self.num_classes), self._eps_K1, dtype=settings.float_type)
+        out[np.arange(out.shape[0]), i] = 1. - self.epsilon
+        return out
+
+    def prob_is_largest(self, Y, mu, var, gh_x, gh_w):
+        """likelihoods.py:404-425"""
+        Y = np.asarray(Y).astype(np.int64).reshape(-1)
+        oh_on = np.zeros((Y.shape[0], self.num_classes), dtype=settings.float_type)
+        oh_on[np.arange(Y.shape[0]), Y] = 1.
+        mu_selected = np.sum(oh_on * mu, 1)
+        var_selected = np.sum(oh_on * var, 1)
+        X = np.reshape(mu_selected, (-1, 1)) + gh_x * np.reshape(
+            np.sqrt(np.clip(2. * var_selected, 1e-10, np.inf)), (-1, 1))
+        dist = (np.expand_dims(X, 1) - np.expand_dims(mu, 2)) / np.expand_dims(
+            np.sqrt(np.clip(var, 1e-10, np.inf)), 2)
+        cdfs = 0.5 * (1.0 + erf(dist / np.sqrt(2.0)))
+        cdfs = cdfs * (1 - 2e-4) + 1e-4
+        oh_off = 1. - oh_on
+        cdfs = cdfs * np.expand_dims(oh_off, 2) + np.expand_dims(oh_on, 2)
+        return np.matmul(np.prod(cdfs, axis=1), np.reshape(gh_w / np.sqrt(np.pi), (-1, 1)))
+
+
+class MultiClass(Likelihood):
+    """likelihoods.py:428-487; the only inverse link is a RobustMax."""
+
+    def __init__(self, num_classes, invlink=None):
+        Likelihood.__init__(self)
+        self.num_classes = num_classes
+        if invlink is None:
+            invlink = RobustMax(self.num_classes)
+        elif not isinstance(invlink, RobustMax):
+            raise NotImplementedError
+        self.invlink = invlink
+
+    def logp(self, F, Y):
+        hits = np.equal(np.expand_dims(np.argmax(F, 1), 1), np.asarray(Y).astype(np.int64))
+        yes = np.ones(np.shape(Y), dtype=settings.float_type) - self.invlink.epsilon
+        no = np.zeros(np.shape(Y), dtype=settings.float_type) + self.invlink._eps_K1
+        return np.log(np.where(hits, yes, no))
+
+    def variational_expectations(self, Fmu, Fvar, Y):
+        gh_x, gh_w = hermgauss(self.num_gauss_hermite_points)
+        p = self.invlink.prob_is_largest(Y, Fmu, Fvar, gh_x, gh_w)
+        return p * np.log(1 - self.invlink.epsilon) + (1. - p) * np.log(self.invlink._eps_K1)
+
+    def predict_mean_and_var(self, Fmu, Fvar):
+        n = np.shape(Fmu)[0]
+        ps = [self._predict_non_logged_density(Fmu, Fvar, np.full((n, 1), i, dtype=np.int64))
+              for i in range(self.num_classes)]
+        ps = np.transpose(np.stack([np.reshape(p, (-1,)) for p in ps]))
+        return ps, ps - np.square(ps)
+
+    def predict_density(self, Fmu, Fvar, Y):
+        return np.log(self._predict_non_logged_density(Fmu, Fvar, Y))
+
+    def _predict_non_logged_density(self, Fmu, Fvar, Y):
+        gh_x, gh_w = hermgauss(self.num_gauss_hermite_points)
+        p = self.invlink.prob_is_largest(Y, Fmu, Fvar, gh_x, gh_w)
+        return p * (1 - self.invlink.epsilon) + (1. - p) * (self.invlink._eps_K1)
+
+    def conditional_mean(self, F):
+        return self.invlink(F)
+
+    def conditional_variance(self, F):
+        p = self.conditional_mean(F)
+        return p - np.square(p)
+
+    def _device_spec(self):
+        return (LIK_MULTICLASS, [float(self.invlink.epsilon)], None)

@@ -3,8 +3,11 @@
 Mirrors gpflowSlim/models/svgp.py:30-130: ELBO = sum of variational expectations (rescaled for
 mini-batches) - KL[q(u) || p(u)].  With the Gaussian likelihood the whole bound is one device call
 (gps_svgp_elbo: Kuu potrf + Kuf trsm of BASELINE config 5, the q_sqrt products, the reduction of the
-expectations and the KL on the same factor); any other likelihood object with a
-``variational_expectations`` goes through conditional() + gauss_kl() like the reference.
+expectations and the KL on the same factor); the built-in non-Gaussian likelihoods
+(Bernoulli, Poisson, Exponential, StudentT, MultiClass with their default links) take the same route with the per-point
+term and its derivatives evaluated by the likelihood kernels (gps_svgp_elbo_lik / gps_svgp_elbo_lik_grad: one Kuu
+factorisation, no [N, K] array crosses to the host); any other likelihood object with a ``variational_expectations`` goes
+through conditional() + gauss_kl() like the reference (bound only: there is no autodiff to differentiate it).
 """
 import numpy as np
 
@@ -62,9 +65,32 @@ class SVGP(GPModel):
             K = self.feature.Kuu(self.kern, jitter=settings.numerics.jitter_level)
         return kullback_leiblers.gauss_kl(self.q_mu, self.q_sqrt, K)
 
+    def _device_lik(self):
+        """(descriptor for the backend, Parameter behind its trainable scalar or None) for a built-in non-Gaussian likelihood
+        with its built-in link; None for everything else."""
+        spec = getattr(self.likelihood, "_device_spec", lambda: None)()
+        if spec is None or type(self.likelihood) is likelihoods.Gaussian:
+            return None
+        kind, params, trainable = spec
+        if self.likelihood.num_gauss_hermite_points > be.LIK_MAX_GH:
+            return None
+        return be.make_lik(kind, params, self.likelihood.num_gauss_hermite_points), trainable
+
+    def _mean_on(self, X):
+        mean = np.asarray(self.mean_function(X), dtype=settings.float_type)
+        if not np.any(mean):
+            return None
+        return np.ascontiguousarray(np.broadcast_to(mean, (X.shape[0], self.num_latent)))
+
     def _bound_on(self, X, Y, scale, handle=None):
-        """The Gaussian-likelihood bound on the data points (X, Y) with the given mini-batch scale: one device call.
+        """The bound on the data points (X, Y) with the given mini-batch scale: one device call.
         (The whole data set for _build_likelihood; one rank's shard for gpflowSlim.distributed_sparse.)"""
+        dl = self._device_lik()
+        if dl is not None:
+            elbo, _, _ = (handle or be.get_handle()).svgp_elbo_lik(
+                self.kern._program(X.shape[1]), self.feature.Z, X, Y, self.q_mu, self.q_sqrt,
+                settings.numerics.jitter_level, dl[0], mean=self._mean_on(X), white=self.whiten, scale=scale)
+            return elbo
         yres = np.ascontiguousarray(np.broadcast_to(Y - self.mean_function(X), Y.shape))
         elbo, _, _ = (handle or be.get_handle()).svgp_elbo(
             self.kern._program(X.shape[1]), self.feature.Z, X, yres, self.q_mu, self.q_sqrt,
@@ -74,7 +100,7 @@ class SVGP(GPModel):
     def _build_likelihood(self):
         """models/svgp.py:108-125"""
         scale = float(self.num_data) / float(self.X.shape[0])
-        if type(self.likelihood) is likelihoods.Gaussian:
+        if type(self.likelihood) is likelihoods.Gaussian or self._device_lik() is not None:
             return self._bound_on(self.X, self.Y, scale)
         KL = self.build_prior_KL()
         fmean, fvar = self._build_predict(self.X, full_cov=False)
@@ -91,17 +117,27 @@ class SVGP(GPModel):
     def _bound_and_gradients_on(self, X, Y, scale, handle=None):
         """compute_log_likelihood_and_gradients on the data points (X, Y) with the given scale (see _bound_on); every
         output is linear in the per-point terms, which is what lets ranks add their shards' results up."""
-        if type(self.likelihood) is not likelihoods.Gaussian:
-            raise NotImplementedError("analytic gradients of the SVGP bound need the Gaussian likelihood")
+        gaussian = type(self.likelihood) is likelihoods.Gaussian
+        dl = None if gaussian else self._device_lik()
+        if not gaussian and dl is None:
+            raise NotImplementedError("analytic gradients of the SVGP bound need the Gaussian likelihood or one of the built-in "
+                                      "likelihoods (Bernoulli, Poisson, Exponential, StudentT, MultiClass) with its default link")
         d_all = X.shape[1]
         prog = self.kern._program(d_all)
         layout = self.kern._grad_layout(d_all)
-        yres = np.ascontiguousarray(np.broadcast_to(Y - self.mean_function(X), Y.shape))
         zparam = getattr(self.feature, "_Z", None)
         want_z = zparam is not None and any(p is zparam for p in self.parameters)
-        res = (handle or be.get_handle()).svgp_elbo_grad(
-            prog, self.feature.Z, X, yres, self.q_mu, self.q_sqrt, settings.numerics.jitter_level,
-            float(np.squeeze(self.likelihood.variance)), white=self.whiten, scale=scale, want_grad_Z=want_z)
+        if gaussian:
+            yres = np.ascontiguousarray(np.broadcast_to(Y - self.mean_function(X), Y.shape))
+            res = (handle or be.get_handle()).svgp_elbo_grad(
+                prog, self.feature.Z, X, yres, self.q_mu, self.q_sqrt, settings.numerics.jitter_level,
+                float(np.squeeze(self.likelihood.variance)), white=self.whiten, scale=scale, want_grad_Z=want_z)
+            lik_param = self.likelihood._variance
+        else:
+            res = (handle or be.get_handle()).svgp_elbo_lik_grad(
+                prog, self.feature.Z, X, Y, self.q_mu, self.q_sqrt, settings.numerics.jitter_level, dl[0],
+                mean=self._mean_on(X), white=self.whiten, scale=scale, want_grad_Z=want_z)
+            lik_param = dl[1]
         elbo, slots, gnoise, g_qmu, g_qsqrt, g_mean = res[:6]
         g_Z = res[6] if want_z else None
         if len(layout) != len(slots):
@@ -114,7 +150,8 @@ class SVGP(GPModel):
                 grads[id(param)] += g
             else:
                 grads[id(param)].reshape(-1)[idx] += g
-        grads[id(self.likelihood._variance)] += gnoise
+        if lik_param is not None:
+            grads[id(lik_param)] += gnoise
         from ..mean_functions import Constant as _MConst, Linear as _MLin
         mf = self.mean_function
 

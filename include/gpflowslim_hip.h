@@ -214,6 +214,62 @@ int gps_svgp_elbo_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes,
                        double* elbo, double* grad_slots, int n_slots_cap, int* n_slots_out, double* grad_noise,
                        double* grad_q_mu, double* grad_q_sqrt, double* grad_mean, double* grad_Z, int* info);
 
+/* ---- non-Gaussian likelihoods (likelihoods.py:191-487): the variational expectations  int log p(y | f) q(f) df  of a point
+ * with q(f) = N(mu, var), their derivatives in mu and var, and the SVGP bound / gradient built on them.
+ *   kind                  param[]                            per-point term
+ *   GPS_LIK_GAUSSIAN      [0] variance                       likelihoods.py:186-188 (closed form; kept for checking the general
+ *                                                            backward pass against the Gaussian entry points above)
+ *   GPS_LIK_BERNOULLI     -                                  Gauss-Hermite of densities.bernoulli(probit(f), y)   (:269-298; the probit
+ *                                                            carries the (1 - 2e-3) + 1e-3 squash of :270)
+ *   GPS_LIK_POISSON       [0] binsize                        y mu - exp(mu + var/2) binsize - lgamma(y + 1) + y log binsize   (:220-224)
+ *   GPS_LIK_EXPONENTIAL   -                                  -exp(-mu + var/2) y - mu                                           (:240-243)
+ *   GPS_LIK_STUDENT_T     [0] scale, [1] deg_free            Gauss-Hermite of densities.student_t(y, f, scale, deg_free)      (:246-266)
+ *   GPS_LIK_MULTICLASS    [0] RobustMax epsilon              p log(1 - eps) + (1 - p) log(eps / (K - 1)), p = prob_is_largest  (:379-454),
+ *                                                            K = the number of latent functions; Y holds ONE class label per point
+ * The Gauss-Hermite rule is the caller's: gh_x, gh_w = numpy.polynomial.hermite.hermgauss(n_gh) as the reference calls it
+ * (:140; unnormalised weights, the library divides by sqrt(pi) as :142 does), 1 <= n_gh <= GPS_LIK_MAX_GH; ignored by the
+ * closed forms.  The inverse links are the reference's defaults (probit, exp); any other link stays with the caller.      */
+enum { GPS_LIK_GAUSSIAN = 0, GPS_LIK_BERNOULLI = 1, GPS_LIK_POISSON = 2, GPS_LIK_EXPONENTIAL = 3, GPS_LIK_STUDENT_T = 4,
+       GPS_LIK_MULTICLASS = 5 };
+#define GPS_LIK_MAX_GH 64
+typedef struct {
+  int kind;
+  int n_gh;
+  double param[4];
+  const double* gh_x;   /* host [n_gh] */
+  const double* gh_w;   /* host [n_gh] */
+} gps_lik_t;
+
+/* The likelihood kernels on their own (the building block of models assembled by the caller): fmu, fvar host [n, k]; Y host
+ * [n, k] ([n] labels for GPS_LIK_MULTICLASS).  *var_exp_sum = sum over points and latents of the variational expectations
+ * (Likelihood.variational_expectations, :121-152; per-workgroup partial sums added up in a fixed order: bit-reproducible).
+ * Optional (both or neither): dmu_out, dvar_out host [n, k] = d var_exp_i / d fmu[i][q], d fvar[i][q] (for MultiClass every
+ * latent of the point).  Optional dparam_out: d sum / d param[0] (the Student-t scale, the Gaussian variance; 0 otherwise). */
+int gps_lik_varexp(gps_handle_t h, const gps_lik_t* lik, const double* fmu, const double* fvar, const double* Y,
+                   int64_t n, int64_t k, double* var_exp_sum, double* dmu_out, double* dvar_out, double* dparam_out);
+
+/* The SVGP bound (models/svgp.py:108-125) with one of the likelihoods above: arguments of the Gaussian bound above with the
+ * descriptor in place of noise_var, the targets Y host [n, k] ([n] labels for MultiClass) and an optional mean host [n, k] =
+ * mean_function(X) (added to the conditional mean on the device; NULL: zero) in place of yres.  One factorisation of Kuu;
+ * the moments [n, k] stay on the device.                                                                              */
+int gps_svgp_elbo_lik(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes,
+                      const double* Z, int64_t m, int64_t d_all, double jitter,
+                      const double* X, int64_t n, const double* Y, const double* mean,
+                      const double* q_mu, int64_t k, const double* q_sqrt, int q_sqrt_ndim,
+                      int white, const gps_lik_t* lik, double scale,
+                      double* elbo, double* kl, double* var_exp_sum, int* info);
+/* ... and its gradient: outputs of the Gaussian gradient above, grad_lik = d/d param[0] in place of grad_noise.  Backward
+ * pass for per-point cotangents E = scale dmu, H = scale dvar (the Gaussian's H is a constant, which lets it share one
+ * [n, m] x [m, m] product between the latents; here a full q_sqrt costs one such product and one A diag(H_q) A^T per latent).
+ * Not available while the data are sharded over ranks through gps_set_allreduce (GPS_ERR_UNSUPPORTED).             */
+int gps_svgp_elbo_lik_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes,
+                           const double* Z, int64_t m, int64_t d_all, double jitter,
+                           const double* X, int64_t n, const double* Y, const double* mean,
+                           const double* q_mu, int64_t k, const double* q_sqrt, int q_sqrt_ndim,
+                           int white, const gps_lik_t* lik, double scale,
+                           double* elbo, double* grad_slots, int n_slots_cap, int* n_slots_out, double* grad_lik,
+                           double* grad_q_mu, double* grad_q_sqrt, double* grad_mean, double* grad_Z, int* info);
+
 /* Vector-Jacobian product of the kernel-matrix build -- reverse-mode autodiff through kern.K(X, X2) (kernels.py:408-439,
  * 1071-1084; neural_kernel_network.py:41-47):  grad_slots[s] = sum_ij W[i][j] d k(X_i, X2_j) / d theta_s  for a
  * caller-supplied cotangent W host [n, m] (X2 == NULL: K(X, X), W [n, n] used as given).  Slot layout of
