@@ -144,6 +144,9 @@ def test_single_comm_rbf_matches_oracle(handle):
     gl = np.ravel([got[id(p)] for p in kp if np.size(p.vf_val) == d][0])
     assert abs(gv - gk[0]) <= 2e-6 * max(1.0, abs(gk[0]))
     assert np.all(np.abs(gl - gk[1:]) <= 2e-6 * np.maximum(1.0, np.abs(gk[1:])))
+    import _grad_ref as gr                                         # analytic dK (tests/_grad_ref.py): the suite's own 1e-8
+    ana = gr.lml_grad_ref(spec_fn, theta, X, Y, orc.constrained(0.1))
+    assert np.abs(np.concatenate([[gv], gl]) - ana.g).max() <= 1e-8 * max(1.0, np.abs(ana.g).max()), (gv, gl, ana.g)
 
 
 @pytest.mark.parametrize("world,n,nb,kname,r", [(2, 1024, 128, "rbf_ard", 1), (3, 1400, 256, "m52_plus_periodic", 2),

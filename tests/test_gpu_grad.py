@@ -96,6 +96,9 @@ def test_lml_gradient_matches_oracle(handle, kind, n, d, r):
     assert got.shape == g_ref.shape
     scale = max(1.0, np.abs(g_ref).max())
     assert np.abs(got - g_ref).max() <= 2e-6 * scale, (got, g_ref)      # oracle dK is a central difference
+    import _grad_ref as gr                                               # analytic dK: the suite's own 1e-8
+    ana = gr.lml_grad_ref(fn, theta, X, Y, noise)
+    assert np.abs(got - ana.g).max() <= 1e-8 * max(1.0, np.abs(ana.g).max()), (got, ana.g)
     gn = [g for p, g in grads if p is m.likelihood._variance][0]
     gn_c = float(gn / m.likelihood._variance.transform.forward_grad(m.likelihood._variance.vf_val))
     assert abs(gn_c - gnoise_ref) <= 1e-8 * max(1.0, abs(gnoise_ref))      # exact formula on both sides

@@ -428,6 +428,14 @@ def test_trsv_wavefront_equals_recursive_substitution(handle, n, r):
     assert np.abs(res[1][3] - kinv).max() <= 1e-9 * np.abs(kinv).max()                 # backward wavefront
     assert np.abs(res[1][3] - res[0][3]).max() <= 1e-12 * np.abs(kinv).max()
     assert np.abs(res[1][1] - res[0][1]).max() <= 1e-10 * max(1.0, np.abs(res[0][1]).max())
+    # ... and the slots of both against the analytic reference (tests/_grad_ref.py), not only against each other
+    import _grad_ref as gr
+    ana = gr.lml_grad_ref(lambda t: dict(spec, variance=t[0], lengthscales=t[1]), np.array([spec["variance"], spec["lengthscales"]]), X, Y, 0.2)
+    for wave in (1, 0):
+        slots = np.ravel(res[wave][1])
+        got = np.array([slots[0], slots[1:1 + d].sum()])              # (isotropic: one entry per active dim, summed)
+        assert np.abs(got - ana.g).max() <= 1e-8 * max(1.0, np.abs(ana.g).max()), (wave, got, ana.g)
+        assert abs(res[wave][2] - ana.g_noise) <= 1e-8 * max(1.0, abs(ana.g_noise))
     assert handle.profile_get("trsv_wave_fallbacks")["launches"] == 0
 
 
