@@ -76,18 +76,17 @@ extern "C" int gps_trsm_lower(gps_handle_t h, const double* L, int64_t n, double
   GPS_HIP(h, hipSetDevice(h->device));
   h->refine_now = (h->leaf_refine != 0);
   const i64 np = gps_pad(n), mp = gps_pad(nrhs);
-  const size_t blk_bytes = (size_t)(np / GPS_TILE) * GPS_TILE * GPS_TILE * 8;
   // dTmp: L padded (and, for trans, U = L^T) ; dTmp2: staging ; dTmp3: inverses ; dB: B^T padded
   GPS_HIP(h, h->dTmp2.ensure((size_t)(n * n > n * nrhs ? n * n : n * nrhs) * 8));
   GPS_HIP(h, h->dTmp.ensure((size_t)np * np * 8 * (trans ? 2 : 1)));
-  GPS_HIP(h, h->dTmp3.ensure(2 * blk_bytes));
+  GPS_HIP(h, h->dTmp3.ensure(linv_bytes(np)));
   GPS_HIP(h, h->dB.ensure((size_t)mp * np * 8));
   double* dL = h->dTmp.d();
   GPS_HIP(h, hipMemcpyAsync(h->dTmp2.p, L, (size_t)n * n * 8, hipMemcpyHostToDevice, h->stream));
   int rc = gps_launch_pad_copy(h, h->dTmp2.d(), n, n, n, dL, np, np, np, 1, 0.0);
   if (rc) return rc;
   int* d_info = (int*)h->dInfo.p;
-  HipOps ops{h, h->dTmp3.d(), h->dTmp3.d() + blk_bytes / 8, d_info};
+  HipOps ops = factor_ops(h, h->dTmp3.d(), np, d_info);
   ops.factor = 0;
   for (i64 b = 0; b < np / GPS_TILE; ++b) {
     rc = ops.potrf_base(dL + b * GPS_TILE * np + b * GPS_TILE, np, b, b * GPS_TILE);
@@ -126,7 +125,7 @@ extern "C" int gps_gpr_set_data(gps_handle_t h, const double* X, int64_t n, int6
   GPS_HIP(h, hipMemcpyAsync(h->dX.p, X, (size_t)n * d_all * 8, hipMemcpyHostToDevice, h->stream));
   // (K itself is allocated by whoever factors it: gpr_factor the whole [N, N], a rank of the block-column path only its
   // own block columns -- 8 N^2 / P bytes)
-  GPS_HIP(h, h->dLinv.ensure(2 * (size_t)(h->npad / GPS_TILE) * GPS_TILE * GPS_TILE * 8));
+  GPS_HIP(h, h->dLinv.ensure(linv_bytes(h->npad)));
   GPS_HIP(h, hipStreamSynchronize(h->stream));
   return GPS_OK;
 }
@@ -276,7 +275,7 @@ static int gpr_factor(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, 
   h->gpr_linvT_stale = false;
   rc = gps_launch_fill_info(h, d_info, INT_MAX);
   if (rc) return rc;
-  HipOps ops{h, h->dLinv.d(), h->dLinv.d() + (np / GPS_TILE) * GPS_TILE * GPS_TILE, d_info};
+  HipOps ops = factor_ops(h, h->dLinv.d(), np, d_info);
   {
     // the factorisation itself only needs the block inverses; their transposes (for the vector solves) are produced
     // by batched launches off the critical path rather than by 128 KB of extra stores in every potrf_base.
@@ -454,8 +453,7 @@ extern "C" int gps_gpr_lml_grad(gps_handle_t h, const gps_kern_node_t* prog, int
     if (!small_inv) {
       rc = gpr_ensure_linvT(h);
       if (rc) return rc;
-      double* linv = h->dLinv.d();
-      HipOps ops{h, linv, linv + (np / GPS_TILE) * GPS_TILE * GPS_TILE, (int*)h->dInfo.p};
+      HipOps ops = factor_ops(h, h->dLinv.d(), np, (int*)h->dInfo.p);
       Blocked<HipOps> bl(ops);
       // A = K_y^-1 resid = L^-T (L^-1 resid)
       GPS_HIP(h, hipMemcpyAsync(h->dA.p, h->dAlpha.p, (size_t)r * np * 8, hipMemcpyDeviceToDevice, h->stream));
@@ -523,8 +521,7 @@ static int gpr_wide_inverse(gps_handle_t h) {
   GPS_HIP(h, h->dBigT.ensure((size_t)(nf / 2) * (WB / 2) * 8));
   int rc = gpr_ensure_linvT(h);
   if (rc) return rc;
-  const i64 nblk = np / GPS_TILE;
-  HipOps ops{h, h->dLinv.d(), h->dLinv.d() + nblk * GPS_TILE * GPS_TILE, (int*)h->dInfo.p};
+  HipOps ops = factor_ops(h, h->dLinv.d(), np, (int*)h->dInfo.p);
   Blocked<HipOps> bl(ops);
   rc = bl.wide_inverse(h->dK.d(), np, nf, WB, ops.linv, ops.linvT, h->dWbig.d(), h->dWtbig.d(), h->dBigT.d());
   if (rc) return rc;
@@ -572,7 +569,7 @@ extern "C" int gps_gpr_predict(gps_handle_t h, const gps_kern_node_t* prog, int 
   rc = gps_launch_kmat(h, prog, n_nodes, h->dXnew.d(), n_new, h->dX.d(), n, d, 0.0, h->dB.d(), np, nsp, np, 0, 0);
   if (rc) return rc;
   // A^T = Kx^T L^-T                                              models/gpr.py:122
-  HipOps ops{h, h->dLinv.d(), h->dLinv.d() + (np / GPS_TILE) * GPS_TILE * GPS_TILE, (int*)h->dInfo.p};
+  HipOps ops = factor_ops(h, h->dLinv.d(), np, (int*)h->dInfo.p);
   Blocked<HipOps> bl(ops);
   const double* dAt = h->dB.d();                  // where A^T ends up
   const i64 nf = (np / GPS_WB) * GPS_WB;

@@ -1,6 +1,7 @@
 // Host orchestration shared by the entry-point families of libgpflowslim_hip.so (gps_handle.hip, gps_gpr.hip, gps_cond.hip,
-// gps_dist.hip, gps_sparse.hip): the HIP "Ops" policy of blocked.hpp and the helpers around a factorisation.  Every arithmetic
-// step is a HIP kernel from the sibling .hip files.
+// gps_svgp.hip, gps_dist.hip, gps_sparse.hip): the HIP "Ops" policy of blocked.hpp and the helpers around a factorisation.
+// Every arithmetic step is a HIP kernel from the sibling .hip files.  (What the inducing-point entries of gps_cond.hip,
+// gps_svgp.hip and gps_sparse.hip share beyond that is in gps_inducing.hpp.)
 #pragma once
 #include "gps_common.hpp"
 #include "blocked.hpp"
@@ -230,6 +231,13 @@ struct HipOps {
     return GPS_OK;
   }
 };
+
+// A factor of npad padded rows keeps the inverses of its npad / 128 diagonal blocks and, back to back behind them, their
+// transposes in one buffer of linv_bytes(npad); factor_ops is the policy over that buffer.
+static inline size_t linv_bytes(i64 npad) { return 2 * (size_t)(npad / GPS_TILE) * GPS_TILE * GPS_TILE * 8; }
+static inline HipOps factor_ops(gps_handle_t h, double* linv_buf, i64 npad, int* d_info) {
+  return HipOps{h, linv_buf, linv_buf + (npad / GPS_TILE) * GPS_TILE * GPS_TILE, d_info};
+}
 
 // L a = y / L^T a = y for r right-hand sides (rows of y): one wavefront launch (trsv_wave.hip) -- with one refinement step
 // per diagonal block inside the wavefront where the leaves are to be refined (jittered / low-noise factors; round 4: the

@@ -1,5 +1,5 @@
 // C ABI of libgpflowslim_hip.so (include/gpflowslim_hip.h): SGPR / GPRFITC bounds, predictions and gradients (models/sgpr.py).
-#include "gps_ops.hpp"
+#include "gps_inducing.hpp"
 
 // ---- SGPR (Titsias 2009): bound and prediction ---------------------------------------------------------
 // models/sgpr.py:121-153 (_build_likelihood) and :155-189 (_build_predict).  Everything O(M^2 N) runs on the
@@ -14,39 +14,34 @@ static int sparse_gpr_impl(gps_handle_t h, int fitc, const gps_kern_node_t* prog
   if (!h || !Z || !X || !resid || m <= 0 || n <= 0 || d_all <= 0 || r <= 0 || !(noise_var > 0.0))
     return gps_fail(h, GPS_ERR_ARG, "gps_sgpr: bad argument");
   if (n_new > 0 && (!Xnew || !mean_out || !var_out)) return gps_fail(h, GPS_ERR_ARG, "gps_sgpr: prediction outputs missing");
-  GPS_HIP(h, hipSetDevice(h->device));
-  if (info) *info = 0;
-  h->have_factor = false; h->factor_gen++; h->dist_have_part_factor = false; h->n = 0;                       // GPR resident buffers are reused below
-  h->refine_now = (h->leaf_refine != 0);
+  int rc = begin_inducing_call(h, info);                         // (GPR resident buffers are reused below)
+  if (rc) return rc;
   const i64 mp = gps_pad(m), np = gps_pad(n);
-  const size_t blk_bytes = (size_t)(mp / GPS_TILE) * GPS_TILE * GPS_TILE * 8;
   const double sigma2 = noise_var;
   // buffers: dX <- Z ; dXnew <- X (then Xnew) ; dK <- Kuu/L ; dLinv (2 sets for L) ; dS1 <- At [np, mp] ;
   //          dS2 <- A [mp, np] ; dS3 <- B / LB [mp, mp] ; dS4 <- inverses of LB (2 sets)
-  GPS_HIP(h, h->dX.ensure((size_t)m * d_all * 8));
-  GPS_HIP(h, hipMemcpyAsync(h->dX.p, Z, (size_t)m * d_all * 8, hipMemcpyHostToDevice, h->stream));
-  GPS_HIP(h, h->dXnew.ensure((size_t)(n > n_new ? n : n_new) * d_all * 8));
-  GPS_HIP(h, hipMemcpyAsync(h->dXnew.p, X, (size_t)n * d_all * 8, hipMemcpyHostToDevice, h->stream));
+  rc = inducing_upload(h, Z, m, X, n, n > n_new ? n : n_new, d_all);
+  if (rc) return rc;
   GPS_HIP(h, h->dK.ensure((size_t)mp * mp * 8));
-  GPS_HIP(h, h->dLinv.ensure(2 * blk_bytes));
+  GPS_HIP(h, h->dLinv.ensure(linv_bytes(mp)));
   GPS_HIP(h, h->dS1.ensure((size_t)np * mp * 8));
   GPS_HIP(h, h->dS2.ensure((size_t)mp * np * 8));
   GPS_HIP(h, h->dS3.ensure((size_t)mp * mp * 8));
-  GPS_HIP(h, h->dS4.ensure(2 * blk_bytes));
+  GPS_HIP(h, h->dS4.ensure(linv_bytes(mp)));
   int* d_info = (int*)h->dInfo.p;
-  int rc = gps_launch_fill_info(h, d_info, INT_MAX);
+  rc = gps_launch_fill_info(h, d_info, INT_MAX);
   if (rc) return rc;
   // Kuu + jitter I -> L                                                 (features.py:74-77, sgpr.py:133-135)
-  rc = gps_launch_kmat(h, prog, n_nodes, h->dX.d(), m, nullptr, m, d_all, jitter, h->dK.d(), mp, mp, mp, 1, 1);
+  rc = inducing_kuu(h, prog, n_nodes, m, d_all, jitter);
   if (rc) return rc;
-  HipOps opsL{h, h->dLinv.d(), h->dLinv.d() + blk_bytes / 8, d_info};
+  HipOps opsL = factor_ops(h, h->dLinv.d(), mp, d_info);
   Blocked<HipOps> blL(opsL);
   rc = blL.potrf_rec(h->dK.d(), mp, mp, 0, 0);
   if (rc) return rc;
   rc = classify_blocks(h, opsL, h->dK.d(), mp, mp);
   if (rc) return rc;
   // At = K(X, Z) L^-T  = (L^-1 Kuf)^T   [np, mp]                         (sgpr.py:139, without the 1/sigma)
-  rc = gps_launch_kmat(h, prog, n_nodes, h->dXnew.d(), n, h->dX.d(), m, d_all, 0.0, h->dS1.d(), mp, np, mp, 0, 0);
+  rc = inducing_kuf(h, prog, n_nodes, n, m, d_all, h->dS1.d());
   if (rc) return rc;
   rc = blL.trsm_rec(h->dK.d(), mp, mp, 0, h->dS1.d(), mp, np);
   if (rc) return rc;
@@ -133,7 +128,7 @@ static int sparse_gpr_impl(gps_handle_t h, int fitc, const gps_kern_node_t* prog
   // B = A A^T * weight + I ; LB = chol(B)                                     (sgpr.py:141-142, 244-245)
   rc = gps_launch_scale_add_eye(h, h->dS3.d(), mp, mp, m, wgt);
   if (rc) return rc;
-  HipOps opsB{h, h->dS4.d(), h->dS4.d() + blk_bytes / 8, d_info};
+  HipOps opsB = factor_ops(h, h->dS4.d(), mp, d_info);
   Blocked<HipOps> blB(opsB);
   rc = blB.potrf_rec(h->dS3.d(), mp, mp, 0, 0);
   if (rc) return rc;
@@ -184,7 +179,7 @@ static int sparse_gpr_impl(gps_handle_t h, int fitc, const gps_kern_node_t* prog
   GPS_HIP(h, h->dB.ensure((size_t)nsp * mp * 8 * 2));
   double* T1 = h->dB.d();                                         // tmp1^T [nsp, mp]
   double* T2 = T1 + (size_t)nsp * mp;                             // tmp2^T
-  rc = gps_launch_kmat(h, prog, n_nodes, h->dXnew.d(), n_new, h->dX.d(), m, d_all, 0.0, T1, mp, nsp, mp, 0, 0);
+  rc = inducing_kuf(h, prog, n_nodes, n_new, m, d_all, T1);
   if (rc) return rc;
   rc = blL.trsm_rec(h->dK.d(), mp, mp, 0, T1, mp, nsp);
   if (rc) return rc;
@@ -242,55 +237,42 @@ extern "C" int gps_fitc(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes
   });
 }
 
-// common tail of the SGPR / FITC gradients: from A_bar^T [np, mp] (cotangent of A = L^-1 Kuf, transposed) to the kernel
-// parameters and the inducing inputs.  On the device: dK = L (blL: its block inverses), A [mp, np], dX = Z, dXnew = X.
-//   Kuf_bar = L^-T A_bar ; L_bar = -tril(Kuf_bar A^T) ; Kuu_bar = adjoint(L, L_bar) ; kernel-matrix VJPs ; Kdiag's share kbar
-static int sparse_grad_tail(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 m, i64 n, i64 d_all,
-                            Blocked<HipOps>& blL, double* AbarT, const double* A, double* U, double kdiag_bar, int ns,
-                            double* grad_slots, double* grad_Z) {
-  const i64 mp = gps_pad(m), np = gps_pad(n);
-  double* L = h->dK.d();
-  int rc;
-  // Kuf_bar^T = A_bar^T L^-1 ; Kuf_bar [mp, np]
-  rc = gps_launch_transpose(h, L, mp, mp, mp, U, mp);
+// Shared by both gradients, from the host rows hv = vbar^T, hu = u^T ([r][mp]) and LB = dS3 (blB: its block inverses):
+// LB_bar = -tril(vbar u^T + R diag(1 / LB_ii)) -> dG1 ; LB^T -> dTmp ; 2 B_bar = 2 adjoint(LB, LB_bar) -> dG2 (dTmp2, dTmp3: scratch).
+// lbar_dot_lb (SGPR; or nullptr): <LB_bar, LB> over the lower triangle.
+static int sparse_lb_bar(gps_handle_t h, Blocked<HipOps>& blB, const std::vector<double>& hv, const std::vector<double>& hu,
+                         i64 m, i64 r, double* lbar_dot_lb) {
+  const i64 mp = gps_pad(m);
+  const double* LB = h->dS3.d();
+  GPS_HIP(h, h->dG1.ensure((size_t)mp * mp * 8));
+  GPS_HIP(h, h->dG2.ensure((size_t)mp * mp * 8));
+  GPS_HIP(h, h->dTmp.ensure((size_t)mp * mp * 8));
+  GPS_HIP(h, h->dTmp2.ensure((size_t)mp * mp * 8));
+  GPS_HIP(h, h->dTmp3.ensure((size_t)2 * mp * GPS_TILE * 8));
+  std::vector<double> va((size_t)mp * GPS_TILE, 0.0), ub((size_t)mp * GPS_TILE, 0.0);
+  for (i64 j = 0; j < m; ++j) for (i64 q = 0; q < r; ++q) { va[(size_t)j * GPS_TILE + q] = hv[(size_t)q * mp + j]; ub[(size_t)j * GPS_TILE + q] = hu[(size_t)q * mp + j]; }
+  double* dVa = h->dTmp3.d(); double* dUb = dVa + (size_t)mp * GPS_TILE;
+  GPS_HIP(h, hipMemcpyAsync(dVa, va.data(), va.size() * 8, hipMemcpyHostToDevice, h->stream));
+  GPS_HIP(h, hipMemcpyAsync(dUb, ub.data(), ub.size() * 8, hipMemcpyHostToDevice, h->stream));
+  double* LBbar = h->dG1.d();
+  int rc = gps_launch_gemm_nt(h, 1, 1, mp, mp, GPS_TILE, dVa, GPS_TILE, dUb, GPS_TILE, LBbar, mp);
+  if (rc) return rc;
+  rc = gps_launch_diag_recip_add(h, LBbar, mp, LB, mp, m, (double)r);
+  if (rc) return rc;
+  rc = gps_launch_tri_map(h, LBbar, mp, mp, 1);
+  if (rc) return rc;
+  if (lbar_dot_lb) {
+    double dots[2];
+    rc = gps_tri_dot(h, LBbar, mp, LB, mp, m, dots);
+    if (rc) return rc;
+    *lbar_dot_lb = dots[0];
+  }
+  double* U = h->dTmp.d();
+  rc = gps_launch_transpose(h, LB, mp, mp, mp, U, mp);
   if (rc) return rc;
   rc = gps_launch_tri_map(h, U, mp, mp, 3);
   if (rc) return rc;
-  rc = blL.trsm_rn_rec(U, mp, mp, 0, AbarT, mp, np);
-  if (rc) return rc;
-  GPS_HIP(h, h->dB.ensure((size_t)mp * np * 8));
-  double* KufBar = h->dB.d();
-  rc = gps_launch_transpose(h, AbarT, mp, np, mp, KufBar, np);
-  if (rc) return rc;
-  // L_bar = -tril(Kuf_bar A^T) ; Kuu_bar
-  double* Lbar = h->dG1.d();
-  rc = gps_launch_gemm_nt(h, 1, 1, mp, mp, np, KufBar, np, A, np, Lbar, mp);
-  if (rc) return rc;
-  rc = gps_launch_tri_map(h, Lbar, mp, mp, 1);
-  if (rc) return rc;
-  double* K2 = h->dG2.d();                                        // 2 Kuu_bar
-  rc = chol_adjoint2(h, blL, U, Lbar, K2, h->dTmp2.d(), mp);
-  if (rc) return rc;
-  for (int sI = 0; sI < ns; ++sI) grad_slots[sI] = 0.0;
-  rc = gps_launch_kmat_vjp(h, prog, n_nodes, h->dX.d(), m, h->dXnew.d(), n, d_all, KufBar, np, 0, grad_slots);
-  if (rc) return rc;
-  {
-    std::vector<double> uu((size_t)ns, 0.0);
-    rc = gps_launch_kmat_vjp(h, prog, n_nodes, h->dX.d(), m, nullptr, 0, d_all, K2, mp, 0, uu.data());
-    if (rc) return rc;
-    for (int sI = 0; sI < ns; ++sI) grad_slots[sI] += 0.5 * uu[sI];
-  }
-  rc = gps_kdiag_vjp(h, prog, n_nodes, d_all, kdiag_bar, grad_slots);
-  if (rc) return rc;
-  if (grad_Z) {
-    for (i64 i = 0; i < m * d_all; ++i) grad_Z[i] = 0.0;
-    rc = gps_launch_kmat_input_vjp(h, prog, n_nodes, h->dX.d(), m, h->dXnew.d(), n, d_all, KufBar, np, 1.0, grad_Z);
-    if (rc) return rc;
-    rc = gps_launch_kmat_input_vjp(h, prog, n_nodes, h->dX.d(), m, nullptr, 0, d_all, K2, mp, 1.0, grad_Z);
-    if (rc) return rc;
-  }
-  GPS_HIP(h, hipStreamSynchronize(h->stream));
-  return GPS_OK;
+  return chol_adjoint2(h, blB, U, LBbar, h->dG2.d(), h->dTmp2.d(), mp);
 }
 
 // ---- gradient of the SGPR bound ----------------------------------------------------------------------------------
@@ -304,17 +286,6 @@ static int sparse_grad_tail(gps_handle_t h, const gps_kern_node_t* prog, int n_n
 //   d/d s = -|u|^2 / s^3 - <B_bar, G> / s^2 - R tr(G) / (2 s^2) - N R / (2 s) + |err|^2 / (2 s^2) + R N Kdiag / (2 s^2),
 //           <B_bar, G> = s (<LB_bar, LB> / 2 - tr B_bar)     (B = LB LB^T scales like LB^2; no second copy of G is kept)
 //   d/d mean(X) = err / s - A^T vbar ; d/d Z through k(Z, X) and k(Z, Z) (gps_launch_kmat_input_vjp).
-static int sgpr_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
-                             const double* X, int64_t n, int64_t d_all, double jitter, double noise_var,
-                             const double* resid, int64_t r, double* bound, double* grad_slots, int n_slots_cap,
-                             int* n_slots_out, double* grad_noise, double* grad_mean, double* grad_Z, int* info);
-// (wrapped like every factorising entry point: a missed look-ahead hand-over re-runs the body once, with_la_retry)
-extern "C" int gps_sgpr_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
-                             const double* X, int64_t n, int64_t d_all, double jitter, double noise_var,
-                             const double* resid, int64_t r, double* bound, double* grad_slots, int n_slots_cap,
-                             int* n_slots_out, double* grad_noise, double* grad_mean, double* grad_Z, int* info) {
-  return with_la_retry(h, [&]() -> int { return sgpr_grad_body(h, prog, n_nodes, Z, m, X, n, d_all, jitter, noise_var, resid, r, bound, grad_slots, n_slots_cap, n_slots_out, grad_noise, grad_mean, grad_Z, info); });
-}
 static int sgpr_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
                              const double* X, int64_t n, int64_t d_all, double jitter, double noise_var,
                              const double* resid, int64_t r, double* bound, double* grad_slots, int n_slots_cap,
@@ -335,9 +306,8 @@ static int sgpr_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_nod
   // dAlpha = err^T [r][np], then u^T [r][mp] ; dX = Z ; dXnew = X
   const i64 mp = gps_pad(m), np = gps_pad(n);
   const double s = noise_var, R = (double)r, N = (double)n;
-  const size_t blk_bytes = (size_t)(mp / GPS_TILE) * GPS_TILE * GPS_TILE * 8;
-  HipOps opsL{h, h->dLinv.d(), h->dLinv.d() + blk_bytes / 8, (int*)h->dInfo.p};
-  HipOps opsB{h, h->dS4.d(), h->dS4.d() + blk_bytes / 8, (int*)h->dInfo.p};
+  HipOps opsL = factor_ops(h, h->dLinv.d(), mp, (int*)h->dInfo.p);
+  HipOps opsB = factor_ops(h, h->dS4.d(), mp, (int*)h->dInfo.p);
   Blocked<HipOps> blL(opsL), blB(opsB);
   double* At = h->dS1.d(); double* A = h->dS2.d(); double* LB = h->dS3.d();
   double* dErrT = h->dAlpha.d(); double* dUT = dErrT + (size_t)r * np;
@@ -355,37 +325,10 @@ static int sgpr_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_nod
   if (rc) return rc;
   GPS_HIP(h, hipMemcpyAsync(hv.data(), dVT, hv.size() * 8, hipMemcpyDeviceToHost, h->stream));
   GPS_HIP(h, hipStreamSynchronize(h->stream));
-  // LB_bar = -tril(vbar u^T + R diag(1 / LB_ii))
-  GPS_HIP(h, h->dG1.ensure((size_t)mp * mp * 8));
-  GPS_HIP(h, h->dG2.ensure((size_t)mp * mp * 8));
-  GPS_HIP(h, h->dTmp.ensure((size_t)mp * mp * 8));
-  GPS_HIP(h, h->dTmp2.ensure((size_t)mp * mp * 8));
-  GPS_HIP(h, h->dTmp3.ensure((size_t)2 * mp * GPS_TILE * 8));
-  std::vector<double> va((size_t)mp * GPS_TILE, 0.0), ub((size_t)mp * GPS_TILE, 0.0);
-  for (i64 j = 0; j < m; ++j) for (i64 q = 0; q < r; ++q) { va[(size_t)j * GPS_TILE + q] = hv[(size_t)q * mp + j]; ub[(size_t)j * GPS_TILE + q] = hu[(size_t)q * mp + j]; }
-  double* dVa = h->dTmp3.d(); double* dUb = dVa + (size_t)mp * GPS_TILE;
-  GPS_HIP(h, hipMemcpyAsync(dVa, va.data(), va.size() * 8, hipMemcpyHostToDevice, h->stream));
-  GPS_HIP(h, hipMemcpyAsync(dUb, ub.data(), ub.size() * 8, hipMemcpyHostToDevice, h->stream));
-  double* LBbar = h->dG1.d();
-  rc = gps_launch_gemm_nt(h, 1, 1, mp, mp, GPS_TILE, dVa, GPS_TILE, dUb, GPS_TILE, LBbar, mp);
-  if (rc) return rc;
-  rc = gps_launch_diag_recip_add(h, LBbar, mp, LB, mp, m, R);
-  if (rc) return rc;
-  rc = gps_launch_tri_map(h, LBbar, mp, mp, 1);
-  if (rc) return rc;
-  double dots[2];
-  rc = gps_tri_dot(h, LBbar, mp, LB, mp, m, dots);                 // <LB_bar, LB> over the lower triangle
-  if (rc) return rc;
-  const double lbar_dot_lb = dots[0];
-  // B_bar: U_B = LB^T, adjoint
-  double* U = h->dTmp.d();
-  rc = gps_launch_transpose(h, LB, mp, mp, mp, U, mp);
-  if (rc) return rc;
-  rc = gps_launch_tri_map(h, U, mp, mp, 3);
+  double lbar_dot_lb = 0.0, dots[2];
+  rc = sparse_lb_bar(h, blB, hv, hu, m, r, &lbar_dot_lb);
   if (rc) return rc;
   double* B2 = h->dG2.d();                                        // 2 B_bar
-  rc = chol_adjoint2(h, blB, U, LBbar, B2, h->dTmp2.d(), mp);
-  if (rc) return rc;
   rc = gps_tri_dot(h, B2, mp, B2, mp, m, dots);
   if (rc) return rc;
   const double trBbar = 0.5 * dots[1];
@@ -422,7 +365,15 @@ static int sgpr_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_nod
     for (i64 i = 0; i < n * r; ++i) grad_mean[i] = resid[i] / s - av[i];
   }
   GPS_HIP(h, hipStreamSynchronize(h->stream));                    // (host vectors above are read by the copies)
-  return sparse_grad_tail(h, prog, n_nodes, m, n, d_all, blL, AbarT, A, U, -0.5 * R * N / s, ns, grad_slots, grad_Z);
+  const InducingGrad g{prog, n_nodes, m, n, d_all, ns, -0.5 * R * N / s, grad_slots, grad_Z};
+  return inducing_backward(h, blL, g, AbarT, A, h->dTmp, h->dB, h->dG1, h->dG2, h->dTmp2, no_more_lbar);
+}
+// (wrapped like every factorising entry point: a missed look-ahead hand-over re-runs the body once, with_la_retry)
+extern "C" int gps_sgpr_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
+                             const double* X, int64_t n, int64_t d_all, double jitter, double noise_var,
+                             const double* resid, int64_t r, double* bound, double* grad_slots, int n_slots_cap,
+                             int* n_slots_out, double* grad_noise, double* grad_mean, double* grad_Z, int* info) {
+  return with_la_retry(h, [&]() -> int { return sgpr_grad_body(h, prog, n_nodes, Z, m, X, n, d_all, jitter, noise_var, resid, r, bound, grad_slots, n_slots_cap, n_slots_out, grad_noise, grad_mean, grad_Z, info); });
 }
 
 // ---- gradient of the FITC log-likelihood (models/sgpr.py:229-290 under TF autodiff) ---------------------------------------
@@ -433,17 +384,6 @@ static int sgpr_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_nod
 //   Ah_bar = 2 B_bar Ah + vbar beta^T ; beta_bar = Ah^T vbar - beta
 //   wbar_i = <Ah_bar[:, i], A[:, i]> + <beta_bar_i, err_i> ; nubar_i = -wbar_i nu_i^-3/2 / 2 - R / (2 nu_i)
 //   sbar = sum nubar ; Kdiag_bar = sum nubar ; A_bar[:, i] = w_i Ah_bar[:, i] - 2 nubar_i A[:, i] ; then the common tail.
-static int fitc_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
-                             const double* X, int64_t n, int64_t d_all, double jitter, double noise_var,
-                             const double* resid, int64_t r, double* bound, double* grad_slots, int n_slots_cap,
-                             int* n_slots_out, double* grad_noise, double* grad_mean, double* grad_Z, int* info);
-// (wrapped like every factorising entry point: a missed look-ahead hand-over re-runs the body once, with_la_retry)
-extern "C" int gps_fitc_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
-                             const double* X, int64_t n, int64_t d_all, double jitter, double noise_var,
-                             const double* resid, int64_t r, double* bound, double* grad_slots, int n_slots_cap,
-                             int* n_slots_out, double* grad_noise, double* grad_mean, double* grad_Z, int* info) {
-  return with_la_retry(h, [&]() -> int { return fitc_grad_body(h, prog, n_nodes, Z, m, X, n, d_all, jitter, noise_var, resid, r, bound, grad_slots, n_slots_cap, n_slots_out, grad_noise, grad_mean, grad_Z, info); });
-}
 static int fitc_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
                              const double* X, int64_t n, int64_t d_all, double jitter, double noise_var,
                              const double* resid, int64_t r, double* bound, double* grad_slots, int n_slots_cap,
@@ -464,9 +404,8 @@ static int fitc_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_nod
   // dAlpha = beta^T [r][np], then u^T [r][mp] ; dTmp3 = w [np]
   const i64 mp = gps_pad(m), np = gps_pad(n);
   const double R = (double)r;
-  const size_t blk_bytes = (size_t)(mp / GPS_TILE) * GPS_TILE * GPS_TILE * 8;
-  HipOps opsL{h, h->dLinv.d(), h->dLinv.d() + blk_bytes / 8, (int*)h->dInfo.p};
-  HipOps opsB{h, h->dS4.d(), h->dS4.d() + blk_bytes / 8, (int*)h->dInfo.p};
+  HipOps opsL = factor_ops(h, h->dLinv.d(), mp, (int*)h->dInfo.p);
+  HipOps opsB = factor_ops(h, h->dS4.d(), mp, (int*)h->dInfo.p);
   Blocked<HipOps> blL(opsL), blB(opsB);
   double* Aht = h->dS1.d(); double* Ah = h->dS2.d(); double* LB = h->dS3.d();
   double* dBetaT = h->dAlpha.d(); double* dUT = dBetaT + (size_t)r * np;
@@ -486,32 +425,9 @@ static int fitc_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_nod
   if (rc) return rc;
   GPS_HIP(h, hipMemcpyAsync(hv.data(), dVT, hv.size() * 8, hipMemcpyDeviceToHost, h->stream));
   GPS_HIP(h, hipStreamSynchronize(h->stream));
-  // LB_bar, B_bar
-  GPS_HIP(h, h->dG1.ensure((size_t)mp * mp * 8));
-  GPS_HIP(h, h->dG2.ensure((size_t)mp * mp * 8));
-  GPS_HIP(h, h->dTmp.ensure((size_t)mp * mp * 8));
-  GPS_HIP(h, h->dTmp2.ensure((size_t)mp * mp * 8));
-  GPS_HIP(h, h->dTmp3.ensure((size_t)2 * mp * GPS_TILE * 8));
-  std::vector<double> va((size_t)mp * GPS_TILE, 0.0), ub((size_t)mp * GPS_TILE, 0.0);
-  for (i64 j = 0; j < m; ++j) for (i64 q = 0; q < r; ++q) { va[(size_t)j * GPS_TILE + q] = hv[(size_t)q * mp + j]; ub[(size_t)j * GPS_TILE + q] = hu[(size_t)q * mp + j]; }
-  double* dVa = h->dTmp3.d(); double* dUb = dVa + (size_t)mp * GPS_TILE;
-  GPS_HIP(h, hipMemcpyAsync(dVa, va.data(), va.size() * 8, hipMemcpyHostToDevice, h->stream));
-  GPS_HIP(h, hipMemcpyAsync(dUb, ub.data(), ub.size() * 8, hipMemcpyHostToDevice, h->stream));
-  double* LBbar = h->dG1.d();
-  rc = gps_launch_gemm_nt(h, 1, 1, mp, mp, GPS_TILE, dVa, GPS_TILE, dUb, GPS_TILE, LBbar, mp);
-  if (rc) return rc;
-  rc = gps_launch_diag_recip_add(h, LBbar, mp, LB, mp, m, R);
-  if (rc) return rc;
-  rc = gps_launch_tri_map(h, LBbar, mp, mp, 1);
-  if (rc) return rc;
-  double* U = h->dTmp.d();
-  rc = gps_launch_transpose(h, LB, mp, mp, mp, U, mp);
-  if (rc) return rc;
-  rc = gps_launch_tri_map(h, U, mp, mp, 3);
+  rc = sparse_lb_bar(h, blB, hv, hu, m, r, nullptr);
   if (rc) return rc;
   double* B2 = h->dG2.d();                                        // 2 B_bar
-  rc = chol_adjoint2(h, blB, U, LBbar, B2, h->dTmp2.d(), mp);
-  if (rc) return rc;
   // Ah_bar^T [np, mp] = beta vbar^T + Ah^T (2 B_bar)
   GPS_HIP(h, h->dY.ensure((size_t)np * mp * 8));
   double* AbarT = h->dY.d();
@@ -560,7 +476,15 @@ static int fitc_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_nod
   rc = gps_launch_scale_cols(h, Ah, np, mp, n, dW, Ah, np);
   if (rc) return rc;
   GPS_HIP(h, hipStreamSynchronize(h->stream));                    // (host vectors above are read by the copies)
-  return sparse_grad_tail(h, prog, n_nodes, m, n, d_all, blL, AbarT, Ah, U, nubar_sum, ns, grad_slots, grad_Z);
+  const InducingGrad g{prog, n_nodes, m, n, d_all, ns, nubar_sum, grad_slots, grad_Z};
+  return inducing_backward(h, blL, g, AbarT, Ah, h->dTmp, h->dB, h->dG1, h->dG2, h->dTmp2, no_more_lbar);
+}
+// (wrapped like every factorising entry point: a missed look-ahead hand-over re-runs the body once, with_la_retry)
+extern "C" int gps_fitc_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
+                             const double* X, int64_t n, int64_t d_all, double jitter, double noise_var,
+                             const double* resid, int64_t r, double* bound, double* grad_slots, int n_slots_cap,
+                             int* n_slots_out, double* grad_noise, double* grad_mean, double* grad_Z, int* info) {
+  return with_la_retry(h, [&]() -> int { return fitc_grad_body(h, prog, n_nodes, Z, m, X, n, d_all, jitter, noise_var, resid, r, bound, grad_slots, n_slots_cap, n_slots_out, grad_noise, grad_mean, grad_Z, info); });
 }
 
 extern "C" int gps_set_allreduce(gps_handle_t h, gps_allreduce_fn fn, void* ctx, void* dev_buf, int64_t capacity_doubles) {

@@ -1,6 +1,6 @@
 // Variational expectations of the non-Gaussian likelihoods (likelihoods.py:121-152 and the special cases :191-487) with
 // their derivatives in the moments of q(f): the per-point term of the SVGP bound and the two per-point cotangents its
-// backward pass starts from (gps_cond.hip: gps_svgp_elbo_lik / gps_svgp_elbo_lik_grad), and gps_lik_varexp on its own.
+// backward pass starts from (gps_svgp.hip: gps_svgp_elbo_lik / gps_svgp_elbo_lik_grad), and gps_lik_varexp on its own.
 //   quadrature kinds   var_exp = sum_h w_h l(f_h),  f_h = mu + sqrt(2 var) x_h,  w_h = hermgauss weight / sqrt(pi)   (:140-152)
 //                      dmu = sum_h w_h l'(f_h) ;  dvar = sum_h w_h l'(f_h) x_h / sqrt(2 var)     (autodiff through :147)
 //   closed forms       Poisson / Exponential with the exp link                                       (:220-224, :240-243)
