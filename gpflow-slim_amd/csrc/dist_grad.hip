@@ -130,20 +130,7 @@ extern "C" int gps_dist_grad_local(gps_handle_t h, const gps_kern_node_t* prog, 
   }
   GradCyclic cyc;
   cyc.P = h->dist_P; cyc.rank = h->dist_rank; cyc.nb = nb; cyc.ncols = h->dist_ncl * nb; cyc.kinv_t = 1;
-  if (!gps_grad_is_simple(prog, n_nodes))
-    return gps_launch_grad_general_cyclic(h, prog, n_nodes, h->dX.d(), n, h->d_all, np, Kt, np, At, np, r, cyc, sums_out, sums_out + ns);
-  GradPost post;
-  GPS_HIP(h, h->dGradSums.ensure((size_t)GPS_GRAD_SUMS * 8));
-  rc = gps_grad_prepare(h, prog, n_nodes, h->dX.d(), n, h->d_all, np, &post);
-  if (rc) return rc;
-  rc = gps_grad_run(h, post, n, np, Kt, np, At, np, r, h->dGradSums.d(), &cyc);
-  if (rc) return rc;
-  double sums[GPS_GRAD_SUMS];
-  GPS_HIP(h, hipMemcpyAsync(sums, h->dGradSums.p, sizeof(sums), hipMemcpyDeviceToHost, h->stream));
-  GPS_HIP(h, hipStreamSynchronize(h->stream));
-  for (int s = 0; s < ns; ++s) sums_out[s] = sums[s];
-  sums_out[ns] = sums[GPS_GRAD_SUMS - 1];
-  return GPS_OK;
+  return gps_launch_grad(h, prog, n_nodes, h->dX.d(), n, h->d_all, np, Kt, np, At, np, r, &cyc, sums_out, sums_out + ns);
 }
 
 // P ranks' gps_dist_grad_local sums (rank p at rank_sums + p * stride) -> gradient slots and d / d noise variance: added in

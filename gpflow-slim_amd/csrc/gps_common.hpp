@@ -443,39 +443,33 @@ int gps_launch_kmat_block(gps_handle_t h, const gps_kern_node_t* prog, int n_nod
                           i64 n, i64 d_all, i64 npad, double diag_add, double* dKb, i64 ldk, i64 r0,
                           i64 nrows, i64 c0, i64 ncols, int prep);
 int gps_launch_kdiag(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double* kdiag_const);
-// grad.hip
+// grad.hip, grad_general.hip (what the two share among themselves: grad_common.hpp)
+// slot count and, per slot, the lengthscale that divides its raw sum (0: none) -- of any program, whichever kernel takes it
 int gps_grad_slots(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, int* n_slots);
-int gps_launch_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n,
-                    i64 d_all, i64 npad, const double* dKinv, i64 ldk, const double* dA, i64 lda, i64 r,
-                    double* grad_slots_host, double* grad_noise_host);
-// the same in two halves, for callers that read several results back with ONE synchronisation (gps_gpr_lml_grad, small N)
-#define GPS_GRAD_SUMS 161
-#define GPS_HRES_BYTES (192 * 1024)
-struct GradPost { int n_slots = 0, nfeat = 0; std::vector<double> ls_of_slot; std::vector<char> blob; };   // blob: the device program (grad.hip)
-int gps_grad_prepare(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n, i64 d_all, i64 npad, GradPost* post);
+int gps_grad_ls_of_slot(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, std::vector<double>* ls);
 // Block-cyclic column mode of the gradient contraction (the distributed gradient, dist_grad.hip): the kernel walks the `ncols`
 // LOCAL columns lj of this rank; global column = ((lj / nb) * P + rank) * nb + lj % nb.  kinv_t: K_y^-1 is read transposed
 // (Kinv[lj * ldk + i], one row per local column).  P = 1, rank = 0, ncols = npad, kinv_t = 0 is the plain mode.
 struct GradCyclic { int P = 1, rank = 0; i64 nb = 0, ncols = 0; int kinv_t = 0; };
-int gps_grad_run(gps_handle_t h, const GradPost& post, i64 n, i64 npad, const double* dKinv, i64 ldk, const double* dA, i64 lda, i64 r,
-                 double* d_sums, const GradCyclic* cyc = nullptr);
+// the gradient of any program, read back: slots and d / d noise variance on the host.  With cyc the slots are this rank's RAW
+// sums (no lengthscale division: gps_dist_grad_fold adds the ranks' sums first)
+int gps_launch_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n,
+                    i64 d_all, i64 npad, const double* dKinv, i64 ldk, const double* dA, i64 lda, i64 r,
+                    const GradCyclic* cyc, double* grad_slots_host, double* grad_noise_host);
+// grad_general.hip: the same for the programs grad.hip's kernel does not take (gps_launch_grad decides; not called otherwise)
+int gps_launch_grad_general(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n, i64 d_all, i64 npad,
+                            const double* dKinv, i64 ldk, const double* dA, i64 lda, i64 r, const GradCyclic* cyc,
+                            double* grad_slots_host, double* grad_noise_host);
+// the same in two halves for the programs grad.hip's own kernel takes (gps_grad_is_simple), for callers that read several
+// results back with ONE synchronisation (gps_gpr_lml_grad, small N): enqueue leaves the sums in d_sums[GPS_GRAD_SUMS]
+#define GPS_GRAD_SUMS 161
+#define GPS_HRES_BYTES (192 * 1024)
+struct GradPost { int n_slots = 0, nfeat = 0; std::vector<double> ls_of_slot; std::vector<char> blob; };   // blob: the device program (grad.hip)
 bool gps_grad_is_simple(const gps_kern_node_t* prog, int n_nodes);
-// the lengthscale that divides each slot's raw sum (0: none): the slot layout of whichever kernel takes the program
-int gps_grad_ls_of_slot(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, std::vector<double>* ls);
-int gps_grad_general_ls_of_slot(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, std::vector<double>* ls);
 int gps_grad_enqueue(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n,
                      i64 d_all, i64 npad, const double* dKinv, i64 ldk, const double* dA, i64 lda, i64 r,
-                     double* d_sums, GradPost* post);
-void gps_grad_finish(const GradPost& post, const double* sums, double* grad_slots_host, double* grad_noise_host);
-// grad_general.hip : programs grad.hip does not take (more than 4 primitives, neural-kernel-network layers)
-int gps_grad_general_slots(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, int* n_slots);
-int gps_launch_grad_general(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n,
-                            i64 d_all, i64 npad, const double* dKinv, i64 ldk, const double* dA, i64 lda, i64 r,
-                            double* grad_slots_host, double* grad_noise_host);
-// raw per-slot sums (no lengthscale division: the caller adds several ranks' sums first) in block-cyclic column mode
-int gps_launch_grad_general_cyclic(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n,
-                                   i64 d_all, i64 npad, const double* dKinv, i64 ldk, const double* dA, i64 lda, i64 r,
-                                   const GradCyclic& cyc, double* raw_slots_host, double* raw_noise_host);
+                     double* d_sums, GradPost* post, const GradCyclic* cyc = nullptr);
+void gps_grad_finish(const GradPost& post, const double* sums, double* grad_slots_host, double* grad_noise_host, bool raw = false);
 int gps_launch_kmat_input_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dXr, i64 nr,
                               const double* dXc, i64 nc, i64 d_all, const double* Wd, i64 ldw, double factor,
                               double* grad_X_host);

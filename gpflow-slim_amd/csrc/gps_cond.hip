@@ -148,7 +148,7 @@ extern "C" int gps_kmat_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_n
   GPS_HIP(h, hipSetDevice(h->device));
   if (!X2) m = n;
   int ns = 0;
-  int rc = gps_grad_general_slots(h, prog, n_nodes, &ns);
+  int rc = gps_grad_slots(h, prog, n_nodes, &ns);
   if (rc) return rc;
   if (n_slots_out) *n_slots_out = ns;
   if (ns > n_slots_cap) return gps_fail(h, GPS_ERR_ARG, "gps_kmat_vjp: grad_slots too small");

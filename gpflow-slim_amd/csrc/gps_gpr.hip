@@ -365,7 +365,7 @@ static int gpr_small_grad_tail(gps_handle_t h, const gps_kern_node_t* prog, int 
   rc = gps_launch_small_inverse(h, h->dK.d(), np, h->dLinv.d(), h->dAlpha.d(), r, h->dY.d(), h->dKinv.d(), h->dA.d(), d_res + 4,
                                 kinv_resid ? d_kr : nullptr, n);
   if (rc) return rc;                   // (the factorisation took this shape: so does the inverse)
-  // (launching the gradient kernel's features in front of the factorisation instead -- gps_grad_prepare -- was measured: no gain)
+  // (launching the gradient kernel's features in front of the factorisation instead -- the first half of gps_grad_enqueue -- was measured: no gain)
   GradPost post;
   rc = gps_grad_enqueue(h, prog, n_nodes, h->dX.d(), n, h->d_all, np, h->dKinv.d(), np, h->dA.d(), np, r, d_res + 5, &post);
   if (rc) return rc;
@@ -465,8 +465,8 @@ extern "C" int gps_gpr_lml_grad(gps_handle_t h, const gps_kern_node_t* prog, int
       rc = bl.lauum_rec(h->dY.d(), np, np, h->dKinv.d(), np);
       if (rc) return rc;
     }
-    rc = gps_launch_grad(h, prog, n_nodes, h->dX.d(), n, h->d_all, np, h->dKinv.d(), np, h->dA.d(), np, r, grad_slots,
-                         grad_noise);
+    rc = gps_launch_grad(h, prog, n_nodes, h->dX.d(), n, h->d_all, np, h->dKinv.d(), np, h->dA.d(), np, r, nullptr,
+                         grad_slots, grad_noise);
     if (rc) return rc;
     if (kinv_resid) {
       GPS_HIP(h, h->dTmp2.ensure((size_t)n * r * 8));

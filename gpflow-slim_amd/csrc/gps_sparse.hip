@@ -294,7 +294,7 @@ static int sgpr_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_nod
   if (!h || !bound || !grad_slots || !grad_noise) return gps_fail(h, GPS_ERR_ARG, "gps_sgpr_grad: bad argument");
   if (r > GPS_TILE) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gps_sgpr_grad: at most 128 outputs");
   int ns = 0;
-  int rc = gps_grad_general_slots(h, prog, n_nodes, &ns);
+  int rc = gps_grad_slots(h, prog, n_nodes, &ns);
   if (rc) return rc;
   if (n_slots_out) *n_slots_out = ns;
   if (ns > n_slots_cap) return gps_fail(h, GPS_ERR_ARG, "gps_sgpr_grad: grad_slots too small");
@@ -392,7 +392,7 @@ static int fitc_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_nod
   if (!h || !bound || !grad_slots || !grad_noise) return gps_fail(h, GPS_ERR_ARG, "gps_fitc_grad: bad argument");
   if (r > GPS_TILE) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gps_fitc_grad: at most 128 outputs");
   int ns = 0;
-  int rc = gps_grad_general_slots(h, prog, n_nodes, &ns);
+  int rc = gps_grad_slots(h, prog, n_nodes, &ns);
   if (rc) return rc;
   if (n_slots_out) *n_slots_out = ns;
   if (ns > n_slots_cap) return gps_fail(h, GPS_ERR_ARG, "gps_fitc_grad: grad_slots too small");

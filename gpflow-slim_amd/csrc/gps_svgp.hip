@@ -271,7 +271,7 @@ struct SvgpGradHead {
 static int svgp_grad_head(gps_handle_t h, const char* entry, const gps_kern_node_t* prog, int n_nodes, const double* Z, i64 m,
                           i64 d_all, double jitter, const double* q_mu, i64 k, const double* q_sqrt, int q_sqrt_ndim, int white,
                           int n_slots_cap, int* n_slots_out, double* grad_q_sqrt, int* info, int* linfo, SvgpGradHead& hd) {
-  int rc = gps_grad_general_slots(h, prog, n_nodes, &hd.ns);
+  int rc = gps_grad_slots(h, prog, n_nodes, &hd.ns);
   if (rc) return rc;
   if (n_slots_out) *n_slots_out = hd.ns;
   if (hd.ns > n_slots_cap) return gps_fail(h, GPS_ERR_ARG, std::string(entry) + ": grad_slots too small");

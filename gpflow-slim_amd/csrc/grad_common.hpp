@@ -1,0 +1,221 @@
+// What the gradient kernels share (grad.hip: 64x32 tiles, at most four primitives, sums reduced on the device; grad_general.hip:
+// 32x32 tiles, up to eight primitives, network layers, the rectangular VJP mode): the feature table and its prep kernel, the
+// per-entry formulas of the primitive kernels, the forward-mode tangent of a Sum / Product program, and the host analysis of
+// the primitive part of a kernel program (slot layout included).  The formulas are the reference's (kernels.py:436-439,
+// 573-610, 806-819; Stationary.euclid_dist's sqrt(r2 + 1e-12), :424-426).  Every expression keeps the grouping it had when
+// each kernel carried its own copy: the compiler contracts multiply-adds by expression shape.
+// Both gradient files include this header, so each gets its own copy of the static host functions and its own code object of
+// the two grad_prep_kernel<> instantiations (same name, same code: the runtime keeps one registration of the shared host stub).
+#pragma once
+#include "gps_common.hpp"
+#include <cmath>
+
+#define GRAD_MAX_NODES 32
+#define GRAD_MAXF 64       // feature rows of one primitive: periodic = 3 per dim (<= 21 dims)
+
+struct GradFeat { int dim; int kind; double param; };   // 0: x/param ; 1: cos(2pi x/param) ; 2: sin ; 3: 2pi x/param
+struct GradNode { int op; int prim; int f0; int nf; int slot0; int ndims; double variance; double ls0; double period; };
+
+// ---- feature prep: Ft[f][i] = feature f of point i (zero in the padding) ------------------------------------------------------
+#define GRAD_PREP_SMALL_F 24
+struct GradTabPtr { const GradFeat* __restrict__ f; };
+struct GradTabVal { GradFeat f[GRAD_PREP_SMALL_F]; };    // (a small table travels in the kernel arguments: no copy command in front of the launch)
+template <class Tab>
+__global__ __launch_bounds__(256) void grad_prep_kernel(const double* __restrict__ X, i64 n, i64 d_all, i64 npad, Tab tab, int nfeat,
+                                                        double* __restrict__ Ft, i64 ldf) {
+  const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= npad) return;
+  for (int f = 0; f < nfeat; ++f) {
+    double v = 0.0;
+    if (i < n) {
+      const GradFeat pf = tab.f[f];
+      const double xv = X[i * d_all + pf.dim];
+      if (pf.kind == 0) v = xv / pf.param;
+      else {
+        const double ang = 2.0 * M_PI * xv / pf.param;
+        v = (pf.kind == 1) ? cos(ang) : (pf.kind == 2 ? sin(ang) : ang);
+      }
+    }
+    Ft[(i64)f * ldf + i] = v;
+  }
+}
+
+// features of `n` points (padded to npad) into Ft [nfeat][npad].  in_args: a small table goes by value; otherwise (and always
+// for callers whose kernels read the table later) it is uploaded to dProg and stays there.
+static int grad_launch_prep(gps_handle_t h, const std::vector<GradFeat>& feats, const double* dX, i64 n, i64 d_all, i64 npad, double* Ft,
+                            bool in_args) {
+  const int nfeat = (int)feats.size();
+  const dim3 grid((unsigned)((npad + 255) / 256));
+  in_args = in_args && nfeat <= GRAD_PREP_SMALL_F;
+  if (!in_args) {
+    GPS_HIP(h, h->dProg.ensure((size_t)nfeat * sizeof(GradFeat) + 64));
+    GPS_HIP(h, h->ring.upload(h->dProg.p, feats.data(), (size_t)nfeat * sizeof(GradFeat), h->stream));
+  }
+  LaunchScope ls(h, KC_KMAT, 0.0, 8.0 * (double)npad * nfeat);
+  if (in_args) {
+    GradTabVal tab;
+    memset(&tab, 0, sizeof(tab));
+    for (int f = 0; f < nfeat; ++f) tab.f[f] = feats[f];
+    hipLaunchKernelGGL(grad_prep_kernel<GradTabVal>, grid, dim3(256), 0, h->stream, dX, n, d_all, npad, tab, nfeat, Ft, npad);
+  } else {
+    hipLaunchKernelGGL(grad_prep_kernel<GradTabPtr>, grid, dim3(256), 0, h->stream, dX, n, d_all, npad,
+                       GradTabPtr{(const GradFeat*)h->dProg.p}, nfeat, Ft, npad);
+  }
+  GPS_HIP(h, hipGetLastError());
+  return GPS_OK;
+}
+
+// ---- device helpers -----------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double grad_wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// global column of local column lj in block-cyclic column mode (GradCyclic; nb == 0: local = global).  A tile's columns never
+// straddle a block: the tile width divides nb.
+__device__ __forceinline__ i64 grad_global_col(i64 lj, int P, int rank, i64 nb) {
+  return nb > 0 ? ((lj / nb) * P + rank) * nb + lj % nb : lj;
+}
+
+// c_ij W_ij = (A A^T - r K_y^-1)_ij below the diagonal, half of it on the diagonal, 0 above it and in the padding; lj: the
+// local column of global column j (Args: GArgs / GGArgs)
+template <class Args>
+__device__ __forceinline__ double grad_lml_weight(const Args& a, i64 i, i64 j, i64 lj) {
+  double val = 0.0;
+  if (i < a.n && j <= i) {
+    double s = 0.0;
+    for (int q = 0; q < a.r; ++q) s += a.A[(i64)q * a.lda + i] * a.A[(i64)q * a.lda + j];
+    val = s - (double)a.r * (a.kinv_t ? a.Kinv[lj * a.ldk + i] : a.Kinv[i * a.ldk + lj]);
+    if (i == j) val *= 0.5;
+  }
+  return val;
+}
+
+#define GRAD_SQRT3 1.7320508075688772
+#define GRAD_SQRT5 2.23606797749979
+
+// stationary primitive from the squared scaled distance q2
+__device__ __forceinline__ double grad_stationary_value(int op, double variance, double q2) {
+  if (op == GPS_K_RBF) return variance * exp(-q2 / 2.0);
+  const double sq3 = GRAD_SQRT3, sq5 = GRAD_SQRT5;
+  const double rad = sqrt(q2 + 1e-12);
+  if (op == GPS_K_MATERN12) return variance * exp(-rad);
+  if (op == GPS_K_EXPONENTIAL) return variance * exp(-0.5 * rad);
+  if (op == GPS_K_MATERN32) return variance * (1.0 + sq3 * rad) * exp(-sq3 * rad);
+  return variance * (1.0 + sq5 * rad + 5.0 / 3.0 * (rad * rad)) * exp(-sq5 * rad);
+}
+
+// Periodic primitive from dot = sum_d (cos_id cos_jd + sin_id sin_jd); *S = sum_d sin^2(pi D_d / p); l2 = lengthscale^2
+__device__ __forceinline__ double grad_periodic_value(double variance, int ndims, double dot, double l2, double* S) {
+  *S = 0.5 * ((double)ndims - dot);
+  return variance * exp(-0.5 * *S / l2);
+}
+
+// d k / d (q2) of a stationary primitive with value k at squared scaled distance q2
+__device__ __forceinline__ double grad_dk_dq2(int op, double variance, double k, double q2) {
+  if (op == GPS_K_RBF) return -0.5 * k;
+  const double sq3 = GRAD_SQRT3, sq5 = GRAD_SQRT5;
+  const double rad = sqrt(q2 + 1e-12);
+  if (op == GPS_K_MATERN12) return -k / (2.0 * rad);
+  if (op == GPS_K_EXPONENTIAL) return -k / (4.0 * rad);
+  if (op == GPS_K_MATERN32) return -1.5 * variance * exp(-sq3 * rad);
+  return -(5.0 / 6.0) * variance * (1.0 + sq5 * rad) * exp(-sq5 * rad);
+}
+
+// plain (Sum / Product) program over the primitive values pv: d out / d prim_p by forward mode
+template <int MAXP, class Prog>
+__device__ __forceinline__ double grad_prog_tangent(const Prog& P, const double (&pv)[MAXP], int p) {
+  double sv[GPS_MAX_STACK], st[GPS_MAX_STACK];
+#pragma unroll
+  for (int s = 0; s < GPS_MAX_STACK; ++s) { sv[s] = 0.0; st[s] = 0.0; }
+  for (int nd = 0; nd < P.n_nodes; ++nd) {
+    const int op = P.nodes[nd].op;
+    if (op == GPS_K_ADD || op == GPS_K_MUL) {
+      const double a = sv[1], ta = st[1], b = sv[0], tb = st[0];
+      sv[0] = (op == GPS_K_ADD) ? a + b : a * b;
+      st[0] = (op == GPS_K_ADD) ? ta + tb : ta * b + a * tb;
+#pragma unroll
+      for (int s = 1; s < GPS_MAX_STACK - 1; ++s) { sv[s] = sv[s + 1]; st[s] = st[s + 1]; }
+    } else {
+      const int q = P.nodes[nd].prim;
+      double val = pv[0];
+#pragma unroll
+      for (int u = 1; u < MAXP; ++u) val = (q == u) ? pv[u] : val;
+#pragma unroll
+      for (int s = GPS_MAX_STACK - 1; s > 0; --s) { sv[s] = sv[s - 1]; st[s] = st[s - 1]; }
+      sv[0] = val; st[0] = (q == p) ? 1.0 : 0.0;
+    }
+  }
+  return st[0];
+}
+
+// ---- host: the primitive part of a kernel program ------------------------------------------------------------------------------
+static inline bool grad_is_prim(int op) {
+  return op == GPS_K_RBF || op == GPS_K_MATERN12 || op == GPS_K_MATERN32 || op == GPS_K_MATERN52 || op == GPS_K_PERIODIC ||
+         op == GPS_K_WHITE || op == GPS_K_CONSTANT || op == GPS_K_EXPONENTIAL;
+}
+
+// what the analysis hands back beside the device nodes: the feature table, the lengthscale that divides each per-dim slot's
+// raw sum (0: none), and the counts
+struct GradPrims {
+  int n_prims = 0, n_slots = 0;
+  std::vector<GradFeat> feats;
+  std::vector<double> ls_of_slot;
+};
+
+// nodes [0, n_nodes) of `prog` -- primitives and, unless the program feeds a network (nkn), Sum / Product -- into `nodes`:
+// stack discipline, parameter ranges, feature rows and slots ([variance] then one slot per active dim, Periodic:
+// [lengthscale, period], White / Constant: nothing more), at most max_prims primitives (too_many: the kernel's own message)
+static int grad_analyse_prims(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, int max_prims, const char* too_many,
+                              bool nkn, GradNode* nodes, GradPrims& R) {
+  if (n_nodes <= 0 || n_nodes > GRAD_MAX_NODES) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: program too long");
+  std::vector<GradFeat>& feats = R.feats;
+  std::vector<double>& ls_of_slot = R.ls_of_slot;
+  int depth = 0;
+  for (int i = 0; i < n_nodes; ++i) {
+    const gps_kern_node_t& nd = prog[i];
+    GradNode& g = nodes[i];
+    g = GradNode{};
+    g.op = nd.op; g.prim = -1; g.variance = nd.variance; g.period = nd.period;
+    if (nd.op == GPS_K_ADD || nd.op == GPS_K_MUL) {
+      if (nkn) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: NKN primitives must be primitive kernels");
+      if (depth < 2) return gps_fail(h, GPS_ERR_ARG, "gradient: stack underflow");
+      depth -= 1; continue;
+    }
+    if (!grad_is_prim(nd.op)) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: unknown op");
+    if (R.n_prims >= max_prims) return gps_fail(h, GPS_ERR_UNSUPPORTED, too_many);
+    g.prim = R.n_prims++;
+    g.slot0 = R.n_slots;
+    depth += 1;
+    if (!nkn && depth > GPS_MAX_STACK) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: expression too deep");
+    if (!(nd.variance > 0.0)) return gps_fail(h, GPS_ERR_ARG, "gradient: variance must be positive");
+    ls_of_slot.push_back(0.0);
+    if (nd.op == GPS_K_WHITE || nd.op == GPS_K_CONSTANT) { R.n_slots += 1; continue; }
+    if (nd.n_dims <= 0 || nd.n_dims > GPS_MAX_DIMS) return gps_fail(h, GPS_ERR_ARG, "gradient: n_dims out of range");
+    for (int d = 0; d < nd.n_dims; ++d)
+      if (nd.active_dims[d] < 0 || nd.active_dims[d] >= d_all) return gps_fail(h, GPS_ERR_ARG, "gradient: active dim outside X");
+    g.ndims = nd.n_dims;
+    g.f0 = (int)feats.size();
+    if (nd.op == GPS_K_PERIODIC) {
+      for (int d = 0; d < nd.n_dims; ++d) { feats.push_back({nd.active_dims[d], 1, nd.period}); feats.push_back({nd.active_dims[d], 2, nd.period}); }
+      for (int d = 0; d < nd.n_dims; ++d) feats.push_back({nd.active_dims[d], 3, nd.period});
+      g.nf = 3 * nd.n_dims; g.ls0 = nd.lengthscales[0];
+      R.n_slots += 3; ls_of_slot.push_back(0.0); ls_of_slot.push_back(0.0);
+    } else {
+      for (int d = 0; d < nd.n_dims; ++d) { feats.push_back({nd.active_dims[d], 0, nd.lengthscales[d]}); ls_of_slot.push_back(nd.lengthscales[d]); }
+      g.nf = nd.n_dims;
+      R.n_slots += 1 + nd.n_dims;
+    }
+    if (g.nf > GRAD_MAXF) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: too many active dims");
+  }
+  if (!nkn && depth != 1) return gps_fail(h, GPS_ERR_ARG, "gradient: program must leave exactly one value");
+  return GPS_OK;
+}
+
+// block-cyclic column mode: whole blocks of whole tiles (tile_w: the kernel's tile width), a rank inside the grid
+static int grad_check_cyclic(gps_handle_t h, const GradCyclic& c, int tile_w) {
+  if (c.nb <= 0 || c.nb % tile_w || c.ncols % c.nb || c.P < 1 || c.rank < 0 || c.rank >= c.P)
+    return gps_fail(h, GPS_ERR_ARG, "gradient: bad block-cyclic column mode");
+  return GPS_OK;
+}

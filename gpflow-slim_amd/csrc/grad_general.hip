@@ -15,8 +15,7 @@
 // Slot layout (host and device agree on it): primitives first, as in grad.hip ([variance], then one slot per active
 // dim, or [lengthscale, period] for Periodic); then, for every Linear layer in network order and every output o:
 // [W[o][0 .. in-1], bias[o]].
-#include "gps_common.hpp"
-#include <cmath>
+#include "grad_common.hpp"
 
 #define GG_T 32            // tile edge
 #define GG_E 4             // elements per thread (2 x 2)
@@ -24,15 +23,11 @@
 #define GG_MAXL 8          // network layers
 #define GG_W 16            // layer width
 #define GG_MAXSLOT 640
-#define GG_MAX_NODES 32
-#define GG_MAXF 64         // feature rows of one primitive
 
-struct GGFeat { int dim; int kind; double param; };   // 0: x/param ; 1: cos(2pi x/param) ; 2: sin ; 3: 2pi x/param
-struct GGNode { int op; int prim; int f0; int nf; int slot0; int ndims; double variance; double ls0; double period; };
 struct GGLayer { int type; int in_dim; int out_dim; int step; int slot0; };       // 0 linear, 1 product, 2 exp
 struct GGProg {
   int n_nodes, n_prims, n_slots, nkn, n_layers;
-  GGNode nodes[GG_MAX_NODES];
+  GradNode nodes[GRAD_MAX_NODES];
   GGLayer layers[GG_MAXL];
 };
 struct GGArgs {
@@ -53,32 +48,6 @@ struct GGArgs {
   int cyc_P, cyc_rank; i64 cyc_nb; int kinv_t;
 };
 
-__device__ __forceinline__ double gg_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-__global__ __launch_bounds__(256) void gg_prep_kernel(const double* __restrict__ X, i64 n, i64 d_all, i64 npad,
-                                                      const GGFeat* __restrict__ feats, int nfeat,
-                                                      double* __restrict__ Ft, i64 ldf) {
-  const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npad) return;
-  for (int f = 0; f < nfeat; ++f) {
-    double v = 0.0;
-    if (i < n) {
-      const GGFeat pf = feats[f];
-      const double xv = X[i * d_all + pf.dim];
-      if (pf.kind == 0) v = xv / pf.param;
-      else {
-        const double ang = 2.0 * M_PI * xv / pf.param;
-        v = (pf.kind == 1) ? cos(ang) : (pf.kind == 2 ? sin(ang) : ang);
-      }
-    }
-    Ft[(i64)f * ldf + i] = v;
-  }
-}
-
 // stage the feature rows [f0, f0 + nf) of the tile's rows / columns
 __device__ __forceinline__ void gg_stage(const GGArgs& a, int f0, int nf, i64 gi0, i64 gj0, double* Fr_s, double* Fc_s, int tid) {
   __syncthreads();
@@ -91,7 +60,7 @@ __device__ __forceinline__ void gg_stage(const GGArgs& a, int f0, int nf, i64 gi
 }
 
 // value and (squared distance | periodic sum) of one primitive at the thread's four entries
-__device__ __forceinline__ void gg_prim(const GGNode& node, const double* Fr_s, const double* Fc_s, int ty, int tx, i64 gi0,
+__device__ __forceinline__ void gg_prim(const GradNode& node, const double* Fr_s, const double* Fc_s, int ty, int tx, i64 gi0,
                                         i64 gj0, bool same_points, double (&val)[GG_E], double (&rr)[GG_E]) {
   if (node.op == GPS_K_CONSTANT) {
 #pragma unroll
@@ -117,11 +86,7 @@ __device__ __forceinline__ void gg_prim(const GGNode& node, const double* Fr_s, 
     }
     const double l2 = node.ls0 * node.ls0;
 #pragma unroll
-    for (int e = 0; e < GG_E; ++e) {
-      const double S = 0.5 * ((double)node.ndims - acc[e]);       // sum_d sin^2(pi D_d / p)
-      rr[e] = S;
-      val[e] = node.variance * exp(-0.5 * S / l2);
-    }
+    for (int e = 0; e < GG_E; ++e) val[e] = grad_periodic_value(node.variance, node.ndims, acc[e], l2, &rr[e]);
     return;
   }
   for (int f = 0; f < node.ndims; ++f) {
@@ -131,48 +96,8 @@ __device__ __forceinline__ void gg_prim(const GGNode& node, const double* Fr_s, 
     d = r0 - c0; acc[0] = fma(d, d, acc[0]); d = r0 - c1; acc[1] = fma(d, d, acc[1]);
     d = r1 - c0; acc[2] = fma(d, d, acc[2]); d = r1 - c1; acc[3] = fma(d, d, acc[3]);
   }
-  const double sq3 = 1.7320508075688772, sq5 = 2.23606797749979;
 #pragma unroll
-  for (int e = 0; e < GG_E; ++e) {
-    const double q2 = acc[e];
-    rr[e] = q2;
-    double v_;
-    if (node.op == GPS_K_RBF) v_ = node.variance * exp(-q2 / 2.0);
-    else {
-      const double rad = sqrt(q2 + 1e-12);
-      if (node.op == GPS_K_MATERN12) v_ = node.variance * exp(-rad);
-      else if (node.op == GPS_K_EXPONENTIAL) v_ = node.variance * exp(-0.5 * rad);
-      else if (node.op == GPS_K_MATERN32) v_ = node.variance * (1.0 + sq3 * rad) * exp(-sq3 * rad);
-      else v_ = node.variance * (1.0 + sq5 * rad + 5.0 / 3.0 * (rad * rad)) * exp(-sq5 * rad);
-    }
-    val[e] = v_;
-  }
-}
-
-// plain (Sum / Product) program: d out / d prim_p by forward mode
-__device__ __forceinline__ double gg_prog_tangent(const GGProg& P, const double (&pv)[GG_MAXP], int p) {
-  double sv[GPS_MAX_STACK], st[GPS_MAX_STACK];
-#pragma unroll
-  for (int s = 0; s < GPS_MAX_STACK; ++s) { sv[s] = 0.0; st[s] = 0.0; }
-  for (int nd = 0; nd < P.n_nodes; ++nd) {
-    const int op = P.nodes[nd].op;
-    if (op == GPS_K_ADD || op == GPS_K_MUL) {
-      const double a = sv[1], ta = st[1], b = sv[0], tb = st[0];
-      sv[0] = (op == GPS_K_ADD) ? a + b : a * b;
-      st[0] = (op == GPS_K_ADD) ? ta + tb : ta * b + a * tb;
-#pragma unroll
-      for (int s = 1; s < GPS_MAX_STACK - 1; ++s) { sv[s] = sv[s + 1]; st[s] = st[s + 1]; }
-    } else {
-      const int q = P.nodes[nd].prim;
-      double val = pv[0];
-#pragma unroll
-      for (int u = 1; u < GG_MAXP; ++u) val = (q == u) ? pv[u] : val;
-#pragma unroll
-      for (int s = GPS_MAX_STACK - 1; s > 0; --s) { sv[s] = sv[s - 1]; st[s] = st[s - 1]; }
-      sv[0] = val; st[0] = (q == p) ? 1.0 : 0.0;
-    }
-  }
-  return st[0];
+  for (int e = 0; e < GG_E; ++e) { rr[e] = acc[e]; val[e] = grad_stationary_value(node.op, node.variance, acc[e]); }
 }
 
 // ---- pass 1: values of all primitives at the thread's four entries of tile (gi0, gj0)
@@ -183,7 +108,7 @@ __device__ __forceinline__ void gg_values(const GGArgs& a, const GGProg& P, i64 
 #pragma unroll
     for (int e = 0; e < GG_E; ++e) pv[p][e] = 0.0;
   for (int nd = 0; nd < P.n_nodes; ++nd) {
-    const GGNode node = P.nodes[nd];
+    const GradNode node = P.nodes[nd];
     if (node.prim < 0) continue;
     if (node.nf > 0) gg_stage(a, node.f0, (node.op == GPS_K_PERIODIC) ? 2 * node.ndims : node.ndims, gi0, gj0, Fr_s, Fc_s, tid);
     double val[GG_E], rr[GG_E];
@@ -209,7 +134,7 @@ __device__ __forceinline__ void gg_adjoints(const GGProg& P, const double* W_s, 
 #pragma unroll
         for (int u = 0; u < GG_MAXP; ++u) pve[u] = pv[u][e];
 #pragma unroll
-        for (int p = 0; p < GG_MAXP; ++p) fp[p][e] = (p < P.n_prims) ? w[e] * gg_prog_tangent(P, pve, p) : 0.0;
+        for (int p = 0; p < GG_MAXP; ++p) fp[p][e] = (p < P.n_prims) ? w[e] * grad_prog_tangent(P, pve, p) : 0.0;
       }
     } else {
 #pragma unroll 1
@@ -260,13 +185,13 @@ __device__ __forceinline__ void gg_adjoints(const GGProg& P, const double* W_s, 
               const double ao = adj[o];
               for (int j = 0; j < ly.in_dim; ++j) {
                 if (ACCW) {
-                  double g = gg_wave_sum(ao * act[L][j]);             // d / d W[o][j]
+                  double g = grad_wave_sum(ao * act[L][j]);             // d / d W[o][j]
                   if (lane == 0) acc_s[wave][ly.slot0 + o * (ly.in_dim + 1) + j] += g;
                 }
                 nxt[j] = fma(Wl[o * (GG_W + 1) + j], ao, nxt[j]);
               }
               if (ACCW) {
-                double gb = gg_wave_sum(ao);                          // d / d bias[o]
+                double gb = grad_wave_sum(ao);                          // d / d bias[o]
                 if (lane == 0) acc_s[wave][ly.slot0 + o * (ly.in_dim + 1) + ly.in_dim] += gb;
               }
             }
@@ -291,8 +216,8 @@ __device__ __forceinline__ void gg_adjoints(const GGProg& P, const double* W_s, 
 }
 
 __global__ __launch_bounds__(256) void gg_kernel(GGArgs a, GGProg P) {
-  __shared__ double Fr_s[GG_MAXF * GG_T];
-  __shared__ double Fc_s[GG_MAXF * GG_T];
+  __shared__ double Fr_s[GRAD_MAXF * GG_T];
+  __shared__ double Fc_s[GRAD_MAXF * GG_T];
   __shared__ double acc_s[4][GG_MAXSLOT + 1];
   __shared__ double W_s[GG_MAXL * GG_W * (GG_W + 1)];
 
@@ -306,9 +231,8 @@ __global__ __launch_bounds__(256) void gg_kernel(GGArgs a, GGProg P) {
   const i64 ntiles = (i64)a.tiles * a.tiles_c;
   for (i64 t = blockIdx.x; t < ntiles; t += gridDim.x) {
     const int ti = (int)(t / a.tiles_c), tj = (int)(t % a.tiles_c);
-    // (local column tile -> global column: the 32 columns of a tile never straddle a block, GG_T divides nb)
     const i64 lj0 = (i64)tj * GG_T;
-    const i64 gi0 = (i64)ti * GG_T, gj0 = a.cyc_nb > 0 ? ((lj0 / a.cyc_nb) * a.cyc_P + a.cyc_rank) * a.cyc_nb + lj0 % a.cyc_nb : lj0;
+    const i64 gi0 = (i64)ti * GG_T, gj0 = grad_global_col(lj0, a.cyc_P, a.cyc_rank, a.cyc_nb);
     if (!a.rect && gj0 > gi0) continue;
     // ---- weights c_e W_e
     double w[GG_E];
@@ -319,16 +243,14 @@ __global__ __launch_bounds__(256) void gg_kernel(GGArgs a, GGProg P) {
       double val = 0.0;
       if (a.rect) {
         if (i < a.nr && j < a.nc) val = a.Wd[i * a.ldw + j];
-      } else if (i < a.n && j <= i) {
-        double s = 0.0;
-        for (int q = 0; q < a.r; ++q) s += a.A[(i64)q * a.lda + i] * a.A[(i64)q * a.lda + j];
-        val = s - (double)a.r * (a.kinv_t ? a.Kinv[lj * a.ldk + i] : a.Kinv[i * a.ldk + lj]);
-        if (i == j) { val *= 0.5; dsum += val; }
+      } else {
+        val = grad_lml_weight(a, i, j, lj);
+        if (i == j) dsum += val;
       }
       w[e] = val;
     }
     if (!a.rect && gi0 == gj0) {                           // noise: d K_y / d sigma^2 = I
-      dsum = gg_wave_sum(dsum);
+      dsum = grad_wave_sum(dsum);
       if (lane == 0) acc_s[wave][GG_MAXSLOT] += dsum;
     }
     // ---- pass 1: primitive values ; pass 2: adjoints  fp[p][e] = c W d k / d prim_p (network weights on the way)
@@ -337,7 +259,7 @@ __global__ __launch_bounds__(256) void gg_kernel(GGArgs a, GGProg P) {
     gg_adjoints<true>(P, W_s, w, pv, fp, acc_s, lane, wave);
     // ---- pass 3: the primitives' own parameters
     for (int nd = 0; nd < P.n_nodes; ++nd) {
-      const GGNode node = P.nodes[nd];
+      const GradNode node = P.nodes[nd];
       if (node.prim < 0) continue;
       double f4[GG_E], k4[GG_E];
 #pragma unroll
@@ -352,7 +274,7 @@ __global__ __launch_bounds__(256) void gg_kernel(GGArgs a, GGProg P) {
         double s = 0.0;
 #pragma unroll
         for (int e = 0; e < GG_E; ++e) s += f4[e] * k4[e];
-        s = gg_wave_sum(s) / node.variance;
+        s = grad_wave_sum(s) / node.variance;
         if (lane == 0) acc_s[wave][node.slot0] += s;
       }
       if (node.op == GPS_K_WHITE || node.op == GPS_K_CONSTANT) continue;
@@ -364,7 +286,7 @@ __global__ __launch_bounds__(256) void gg_kernel(GGArgs a, GGProg P) {
         double s = 0.0;                                    // d k / d l = k S / l^3
 #pragma unroll
         for (int e = 0; e < GG_E; ++e) s += f4[e] * k4[e] * S4[e];
-        s = gg_wave_sum(s) / (l2 * l);
+        s = grad_wave_sum(s) / (l2 * l);
         if (lane == 0) acc_s[wave][node.slot0 + 1] += s;
         // d k / d p = k / (2 l^2) sum_d sin(a_i - a_j) (a_i - a_j) / (2 p),  a = 2 pi x / p
         double sp = 0.0;
@@ -378,7 +300,7 @@ __global__ __launch_bounds__(256) void gg_kernel(GGArgs a, GGProg P) {
             sp += f4[e] * k4[e] * (si * cj_ - ci * sj) * da;
           }
         }
-        sp = gg_wave_sum(sp) / (2.0 * l2) / (2.0 * node.period);
+        sp = grad_wave_sum(sp) / (2.0 * l2) / (2.0 * node.period);
         if (lane == 0) acc_s[wave][node.slot0 + 2] += sp;
         continue;
       }
@@ -386,26 +308,13 @@ __global__ __launch_bounds__(256) void gg_kernel(GGArgs a, GGProg P) {
       gg_stage(a, node.f0, node.ndims, gi0, gj0, Fr_s, Fc_s, tid);
       double val[GG_E], q4[GG_E], Q[GG_E];
       gg_prim(node, Fr_s, Fc_s, ty, tx, gi0, gj0, same_points, val, q4);
-      const double sq3 = 1.7320508075688772, sq5 = 2.23606797749979;
 #pragma unroll
-      for (int e = 0; e < GG_E; ++e) {
-        const double k = k4[e];
-        double dk;
-        if (node.op == GPS_K_RBF) dk = -0.5 * k;
-        else {
-          const double rad = sqrt(q4[e] + 1e-12);
-          if (node.op == GPS_K_MATERN12) dk = -k / (2.0 * rad);
-          else if (node.op == GPS_K_EXPONENTIAL) dk = -k / (4.0 * rad);
-          else if (node.op == GPS_K_MATERN32) dk = -1.5 * node.variance * exp(-sq3 * rad);
-          else dk = -(5.0 / 6.0) * node.variance * (1.0 + sq5 * rad) * exp(-sq5 * rad);
-        }
-        Q[e] = f4[e] * dk;
-      }
+      for (int e = 0; e < GG_E; ++e) Q[e] = f4[e] * grad_dk_dq2(node.op, node.variance, k4[e], q4[e]);
       for (int d = 0; d < node.ndims; ++d) {
         const double r0 = Fr_s[d * GG_T + ty * 2], r1 = Fr_s[d * GG_T + ty * 2 + 1];
         const double c0 = Fc_s[d * GG_T + tx * 2], c1 = Fc_s[d * GG_T + tx * 2 + 1];
         double s = Q[0] * (r0 - c0) * (r0 - c0) + Q[1] * (r0 - c1) * (r0 - c1) + Q[2] * (r1 - c0) * (r1 - c0) + Q[3] * (r1 - c1) * (r1 - c1);
-        s = gg_wave_sum(s);
+        s = grad_wave_sum(s);
         if (lane == 0) acc_s[wave][node.slot0 + 1 + d] += -2.0 * s;     // the host divides by l_d
       }
     }
@@ -424,11 +333,11 @@ __global__ __launch_bounds__(256) void gg_kernel(GGArgs a, GGProg P) {
 //   Periodic    S = sum_d sin^2((a_id - a_jd) / 2), a = 2 pi x / p :  d k / d x_id = -k / (2 l^2) (1/2) sin(a_id - a_jd) 2 pi / p
 // Workgroup (ti, slice) owns 32 rows and a slice of the column tiles; row sums over the 16 threads of a patch row by
 // shuffles, over the tiles in LDS; the slices' partial sums [slices][rows][d_all] are added in order on the host.
-struct GIArgs { const GGFeat* feats; double* part; int d_all; int slices; i64 rows_pad; };
+struct GIArgs { const GradFeat* feats; double* part; int d_all; int slices; i64 rows_pad; };
 
 __global__ __launch_bounds__(256) void gg_input_kernel(GGArgs a, GGProg P, GIArgs gi) {
-  __shared__ double Fr_s[GG_MAXF * GG_T];
-  __shared__ double Fc_s[GG_MAXF * GG_T];
+  __shared__ double Fr_s[GRAD_MAXF * GG_T];
+  __shared__ double Fc_s[GRAD_MAXF * GG_T];
   __shared__ double W_s[GG_MAXL * GG_W * (GG_W + 1)];
   __shared__ double rowacc[GG_T][GPS_MAX_DIMS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -453,7 +362,7 @@ __global__ __launch_bounds__(256) void gg_input_kernel(GGArgs a, GGProg P, GIArg
     gg_values(a, P, gi0, gj0, same_points, Fr_s, Fc_s, tid, ty, tx, pv);
     gg_adjoints<false>(P, W_s, w, pv, fp, nullptr, lane, wave);
     for (int nd = 0; nd < P.n_nodes; ++nd) {
-      const GGNode node = P.nodes[nd];
+      const GradNode node = P.nodes[nd];
       if (node.prim < 0 || node.op == GPS_K_WHITE || node.op == GPS_K_CONSTANT) continue;
       double f4[GG_E], k4[GG_E];
 #pragma unroll
@@ -489,21 +398,8 @@ __global__ __launch_bounds__(256) void gg_input_kernel(GGArgs a, GGProg P, GIArg
       gg_stage(a, node.f0, node.ndims, gi0, gj0, Fr_s, Fc_s, tid);
       double val[GG_E], q4[GG_E];
       gg_prim(node, Fr_s, Fc_s, ty, tx, gi0, gj0, same_points, val, q4);
-      const double sq3 = 1.7320508075688772, sq5 = 2.23606797749979;
 #pragma unroll
-      for (int e = 0; e < GG_E; ++e) {
-        const double k = k4[e];
-        double dk;
-        if (node.op == GPS_K_RBF) dk = -0.5 * k;
-        else {
-          const double rad = sqrt(q4[e] + 1e-12);
-          if (node.op == GPS_K_MATERN12) dk = -k / (2.0 * rad);
-          else if (node.op == GPS_K_EXPONENTIAL) dk = -k / (4.0 * rad);
-          else if (node.op == GPS_K_MATERN32) dk = -1.5 * node.variance * exp(-sq3 * rad);
-          else dk = -(5.0 / 6.0) * node.variance * (1.0 + sq5 * rad) * exp(-sq5 * rad);
-        }
-        Q[e] = 2.0 * f4[e] * dk;
-      }
+      for (int e = 0; e < GG_E; ++e) Q[e] = 2.0 * f4[e] * grad_dk_dq2(node.op, node.variance, k4[e], q4[e]);
       for (int d = 0; d < node.ndims; ++d) {
         const double r0 = Fr_s[d * GG_T + ty * 2], r1 = Fr_s[d * GG_T + ty * 2 + 1];
         const double c0 = Fc_s[d * GG_T + tx * 2], c1 = Fc_s[d * GG_T + tx * 2 + 1];
@@ -512,7 +408,7 @@ __global__ __launch_bounds__(256) void gg_input_kernel(GGArgs a, GGProg P, GIArg
 #pragma unroll
         for (int off = 1; off < 16; off <<= 1) { s0 += __shfl_xor(s0, off, 64); s1 += __shfl_xor(s1, off, 64); }
         if (tx == 0) {
-          const GGFeat ft = gi.feats[node.f0 + d];
+          const GradFeat ft = gi.feats[node.f0 + d];
           rowacc[ty * 2][ft.dim] += s0 / ft.param; rowacc[ty * 2 + 1][ft.dim] += s1 / ft.param;
         }
       }
@@ -528,12 +424,8 @@ __global__ __launch_bounds__(256) void gg_input_kernel(GGArgs a, GGProg P, GIArg
 // ---- host side ------------------------------------------------------------------------------------
 #define GG_BLOCKS 2048
 
-static bool gg_is_prim(int op) {
-  return op == GPS_K_RBF || op == GPS_K_MATERN12 || op == GPS_K_MATERN32 || op == GPS_K_MATERN52 || op == GPS_K_PERIODIC ||
-         op == GPS_K_WHITE || op == GPS_K_CONSTANT || op == GPS_K_EXPONENTIAL;
-}
-
-int gps_grad_general_slots(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, int* n_slots) {
+// Slot count of any program, whichever kernel takes it (the layout: see the top of this file and of grad.hip)
+int gps_grad_slots(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, int* n_slots) {
   int s = 0;
   for (int i = 0; i < n_nodes; ++i) {
     const int op = prog[i].op;
@@ -541,7 +433,7 @@ int gps_grad_general_slots(gps_handle_t h, const gps_kern_node_t* prog, int n_no
     if (op == GPS_K_WHITE || op == GPS_K_CONSTANT) s += 1;
     else if (op == GPS_K_PERIODIC) s += 3;
     else if (op == GPS_K_NKN_LINROW) s += prog[i].n_dims + 1;
-    else if (gg_is_prim(op)) s += 1 + prog[i].n_dims;
+    else if (grad_is_prim(op)) s += 1 + prog[i].n_dims;
     else return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: unknown op");
   }
   *n_slots = s;
@@ -551,60 +443,23 @@ int gps_grad_general_slots(gps_handle_t h, const gps_kern_node_t* prog, int n_no
 // compiled form of a kernel program for gg_kernel
 struct GGBuilt {
   GGProg P;
-  std::vector<GGFeat> feats;
-  std::vector<double> ls_of_slot;
+  GradPrims prims;           // feature table, lengthscale of every slot (the network's slots: 0)
   std::vector<double> W;
 };
 
 static int gg_build(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, GGBuilt& B) {
   GGProg& P = B.P;
-  std::vector<GGFeat>& feats = B.feats;
-  std::vector<double>& ls_of_slot = B.ls_of_slot;
   std::vector<double>& W = B.W;
   W.assign((size_t)GG_MAXL * GG_W * (GG_W + 1), 0.0);
   memset(&P, 0, sizeof(P));
   int n_prim_nodes = 0;
   for (int i = 0; i < n_nodes; ++i) if (prog[i].op < GPS_K_NKN_LINROW) n_prim_nodes = i + 1;
   P.nkn = (n_prim_nodes < n_nodes) ? 1 : 0;
-  if (n_prim_nodes <= 0 || n_prim_nodes > GG_MAX_NODES) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: program too long");
-  P.n_nodes = n_prim_nodes;
-  int depth = 0;
-  for (int i = 0; i < n_prim_nodes; ++i) {
-    const gps_kern_node_t& nd = prog[i];
-    GGNode& g = P.nodes[i];
-    g.op = nd.op; g.prim = -1; g.variance = nd.variance; g.period = nd.period;
-    if (nd.op == GPS_K_ADD || nd.op == GPS_K_MUL) {
-      if (P.nkn) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: NKN primitives must be primitive kernels");
-      if (depth < 2) return gps_fail(h, GPS_ERR_ARG, "gradient: stack underflow");
-      depth -= 1; continue;
-    }
-    if (!gg_is_prim(nd.op)) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: unknown op");
-    if (P.n_prims >= GG_MAXP) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: kernel programs with more than 8 primitive nodes are not supported");
-    g.prim = P.n_prims++;
-    g.slot0 = P.n_slots;
-    depth += 1;
-    if (!P.nkn && depth > GPS_MAX_STACK) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: expression too deep");
-    if (!(nd.variance > 0.0)) return gps_fail(h, GPS_ERR_ARG, "gradient: variance must be positive");
-    ls_of_slot.push_back(0.0);
-    if (nd.op == GPS_K_WHITE || nd.op == GPS_K_CONSTANT) { P.n_slots += 1; continue; }
-    if (nd.n_dims <= 0 || nd.n_dims > GPS_MAX_DIMS) return gps_fail(h, GPS_ERR_ARG, "gradient: n_dims out of range");
-    for (int d = 0; d < nd.n_dims; ++d)
-      if (nd.active_dims[d] < 0 || nd.active_dims[d] >= d_all) return gps_fail(h, GPS_ERR_ARG, "gradient: active dim outside X");
-    g.ndims = nd.n_dims;
-    g.f0 = (int)feats.size();
-    if (nd.op == GPS_K_PERIODIC) {
-      for (int d = 0; d < nd.n_dims; ++d) { feats.push_back({nd.active_dims[d], 1, nd.period}); feats.push_back({nd.active_dims[d], 2, nd.period}); }
-      for (int d = 0; d < nd.n_dims; ++d) feats.push_back({nd.active_dims[d], 3, nd.period});
-      g.nf = 3 * nd.n_dims; g.ls0 = nd.lengthscales[0];
-      P.n_slots += 3; ls_of_slot.push_back(0.0); ls_of_slot.push_back(0.0);
-    } else {
-      for (int d = 0; d < nd.n_dims; ++d) { feats.push_back({nd.active_dims[d], 0, nd.lengthscales[d]}); ls_of_slot.push_back(nd.lengthscales[d]); }
-      g.nf = nd.n_dims;
-      P.n_slots += 1 + nd.n_dims;
-    }
-    if (g.nf > GG_MAXF) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: too many active dims");
-  }
-  if (!P.nkn && depth != 1) return gps_fail(h, GPS_ERR_ARG, "gradient: program must leave exactly one value");
+  int rc = grad_analyse_prims(h, prog, n_prim_nodes, d_all, GG_MAXP, "gradient: kernel programs with more than 8 primitive nodes are not supported",
+                              P.nkn != 0, P.nodes, B.prims);
+  if (rc) return rc;
+  P.n_nodes = n_prim_nodes; P.n_prims = B.prims.n_prims;
+  int& n_slots = B.prims.n_slots;
   // ---- network layers (kernel-program encoding of gpflowSlim/neural_kernel_network: see kmat.hip compile_prog)
   if (P.nkn) {
     int width = P.n_prims, i = n_prim_nodes;
@@ -615,13 +470,12 @@ static int gg_build(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i6
         const int layer_id = prog[i].active_dims[0];
         double* Wl = W.data() + (size_t)P.n_layers * GG_W * (GG_W + 1);
         int o = 0;
-        ly.type = 0; ly.in_dim = width; ly.slot0 = P.n_slots;
+        ly.type = 0; ly.in_dim = width; ly.slot0 = n_slots;
         while (i < n_nodes && prog[i].op == GPS_K_NKN_LINROW && prog[i].active_dims[0] == layer_id) {
           if (prog[i].n_dims != width || o >= GG_W || width > GG_W) return gps_fail(h, GPS_ERR_ARG, "gradient: Linear layer width mismatch (max 16)");
           for (int j = 0; j < width; ++j) Wl[o * (GG_W + 1) + j] = prog[i].lengthscales[j];
           Wl[o * (GG_W + 1) + GG_W] = prog[i].variance;
-          for (int j = 0; j <= width; ++j) ls_of_slot.push_back(0.0);
-          P.n_slots += width + 1;
+          n_slots += width + 1;
           ++o; ++i;
         }
         ly.out_dim = o; width = o;
@@ -637,40 +491,45 @@ static int gg_build(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i6
     }
     if (width != 1) return gps_fail(h, GPS_ERR_ARG, "gradient: the network must end with one output");
   }
-  if (P.n_slots > GG_MAXSLOT) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: too many parameters");
+  if (n_slots > GG_MAXSLOT) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: too many parameters");
+  P.n_slots = n_slots;
+  B.prims.ls_of_slot.resize((size_t)n_slots, 0.0);
   return GPS_OK;
 }
 
-int gps_grad_general_ls_of_slot(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, std::vector<double>* ls) {
+// the lengthscale that divides each slot's raw sum (0: none), from the same analysis the kernels run on
+int gps_grad_ls_of_slot(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, std::vector<double>* ls) {
   GGBuilt B;
   int rc = gg_build(h, prog, n_nodes, d_all, B);
   if (rc) return rc;
-  *ls = B.ls_of_slot;
+  *ls = B.prims.ls_of_slot;
   return GPS_OK;
 }
 
-// features of `n` points (padded to npad) into `feat`
+// features of `n` points (padded to npad) into `feat`; the table is uploaded (gg_input_kernel reads it from dProg)
 static int gg_features(gps_handle_t h, const GGBuilt& B, const double* dX, i64 n, i64 d_all, i64 npad, DevBuf& feat) {
-  const int nfeat = (int)B.feats.size();
-  GPS_HIP(h, feat.ensure((size_t)(nfeat > 0 ? nfeat : 1) * npad * 8));
+  const size_t nfeat = B.prims.feats.size();
+  GPS_HIP(h, feat.ensure((nfeat > 0 ? nfeat : 1) * npad * 8));
   if (nfeat == 0) return GPS_OK;
-  GPS_HIP(h, h->dProg.ensure((size_t)nfeat * sizeof(GGFeat) + 64));
-  GPS_HIP(h, h->ring.upload(h->dProg.p, B.feats.data(), (size_t)nfeat * sizeof(GGFeat), h->stream));
-  LaunchScope ls(h, KC_KMAT, 0.0, 8.0 * (double)npad * nfeat);
-  hipLaunchKernelGGL(gg_prep_kernel, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, h->stream, dX, n, d_all, npad,
-                     (const GGFeat*)h->dProg.p, nfeat, feat.d(), npad);
-  GPS_HIP(h, hipGetLastError());
-  return GPS_OK;
+  return grad_launch_prep(h, B.prims.feats, dX, n, d_all, npad, feat.d(), false);
 }
 
-// launch + fold the fixed-order partials; slots: set (accumulate == 0) or added to
-static int gg_run(gps_handle_t h, const GGBuilt& B, GGArgs& a, double flops, double bytes, int accumulate,
-                  double* grad_slots_host, double* grad_noise_host, bool raw = false) {
-  const GGProg& P = B.P;
+static int gg_upload_net(gps_handle_t h, const GGBuilt& B, GGArgs& a) {
   const size_t wbytes = B.W.size() * 8;
   GPS_HIP(h, h->dNkn.ensure(wbytes + 64));
   GPS_HIP(h, h->ring.upload(h->dNkn.p, B.W.data(), wbytes, h->stream));
   a.Wnet = (const double*)h->dNkn.p;
+  return GPS_OK;
+}
+
+static double gg_work(const GGBuilt& B, double rows, double cols, double per_feat) {
+  return rows * cols * (60.0 + per_feat * B.prims.feats.size() + 40.0 * B.P.n_layers);
+}
+
+// launch + fold the fixed-order partials; slots: set (accumulate == 0) or added to; raw: no lengthscale division
+static int gg_run(gps_handle_t h, const GGBuilt& B, GGArgs& a, double flops, double bytes, int accumulate,
+                  double* grad_slots_host, double* grad_noise_host, bool raw) {
+  const GGProg& P = B.P;
   const size_t pbytes = (size_t)GG_BLOCKS * (GG_MAXSLOT + 1) * 8;
   GPS_HIP(h, h->dTmp2.ensure(pbytes));
   a.partial = h->dTmp2.d();
@@ -688,40 +547,25 @@ static int gg_run(gps_handle_t h, const GGBuilt& B, GGArgs& a, double flops, dou
     for (int b = 0; b < GG_BLOCKS; ++b) tot += part[(size_t)b * (GG_MAXSLOT + 1) + s];
     if (s == GG_MAXSLOT) { if (grad_noise_host) *grad_noise_host = tot; }
     else {
-      if (!raw && B.ls_of_slot[s] > 0.0) tot /= B.ls_of_slot[s];       // -2 delta^2 / l_d : delta is already x/l
+      if (!raw && B.prims.ls_of_slot[s] > 0.0) tot /= B.prims.ls_of_slot[s];       // -2 delta^2 / l_d : delta is already x/l
       if (accumulate) grad_slots_host[s] += tot; else grad_slots_host[s] = tot;
     }
   }
   return GPS_OK;
 }
 
-int gps_launch_grad_general(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n, i64 d_all,
-                            i64 npad, const double* dKinv, i64 ldk, const double* dA, i64 lda, i64 r,
+int gps_launch_grad_general(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n, i64 d_all, i64 npad,
+                            const double* dKinv, i64 ldk, const double* dA, i64 lda, i64 r, const GradCyclic* cyc,
                             double* grad_slots_host, double* grad_noise_host) {
+  int rc = cyc ? grad_check_cyclic(h, *cyc, GG_T) : GPS_OK;
+  if (rc) return rc;
   GGBuilt B;
-  int rc = gg_build(h, prog, n_nodes, d_all, B);
+  rc = gg_build(h, prog, n_nodes, d_all, B);
   if (rc) return rc;
-  rc = gg_features(h, B, dX, n, d_all, npad, h->dFeat);
-  if (rc) return rc;
-  GGArgs a;
-  memset(&a, 0, sizeof(a));
-  a.Ft = h->dFeat.d(); a.ldf = npad; a.Ftc = a.Ft; a.ldfc = npad; a.Kinv = dKinv; a.ldk = ldk; a.A = dA; a.lda = lda; a.r = (int)r;
-  a.n = n; a.npad = npad; a.tiles = (int)(npad / GG_T); a.tiles_c = a.tiles; a.rect = 0; a.same_points = 1;
-  return gg_run(h, B, a, 0.5 * (double)npad * npad * (60.0 + 4.0 * B.feats.size() + 40.0 * B.P.n_layers), 4.0 * (double)npad * npad,
-                0, grad_slots_host, grad_noise_host);
-}
-
-int gps_launch_grad_general_cyclic(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n,
-                                   i64 d_all, i64 npad, const double* dKinv, i64 ldk, const double* dA, i64 lda, i64 r,
-                                   const GradCyclic& cyc, double* raw_slots_host, double* raw_noise_host) {
-  if (cyc.nb <= 0 || cyc.nb % GG_T || cyc.ncols % cyc.nb || cyc.P < 1 || cyc.rank < 0 || cyc.rank >= cyc.P)
-    return gps_fail(h, GPS_ERR_ARG, "gradient: bad block-cyclic column mode");
-  GGBuilt B;
-  int rc = gg_build(h, prog, n_nodes, d_all, B);
-  if (rc) return rc;
-  if (cyc.ncols == 0) {                                    // a rank without columns: its sums are zero
-    for (int s = 0; s < B.P.n_slots; ++s) raw_slots_host[s] = 0.0;
-    *raw_noise_host = 0.0;
+  const i64 ncols = cyc ? cyc->ncols : npad;
+  if (ncols == 0) {                                        // a rank without columns: its sums are zero
+    for (int s = 0; s < B.P.n_slots; ++s) grad_slots_host[s] = 0.0;
+    if (grad_noise_host) *grad_noise_host = 0.0;
     return GPS_OK;
   }
   rc = gg_features(h, B, dX, n, d_all, npad, h->dFeat);
@@ -729,10 +573,32 @@ int gps_launch_grad_general_cyclic(gps_handle_t h, const gps_kern_node_t* prog, 
   GGArgs a;
   memset(&a, 0, sizeof(a));
   a.Ft = h->dFeat.d(); a.ldf = npad; a.Ftc = a.Ft; a.ldfc = npad; a.Kinv = dKinv; a.ldk = ldk; a.A = dA; a.lda = lda; a.r = (int)r;
-  a.n = n; a.npad = npad; a.tiles = (int)(npad / GG_T); a.tiles_c = (int)(cyc.ncols / GG_T); a.rect = 0; a.same_points = 1;
-  a.cyc_P = cyc.P; a.cyc_rank = cyc.rank; a.cyc_nb = cyc.nb; a.kinv_t = cyc.kinv_t;
-  return gg_run(h, B, a, 0.5 * (double)npad * cyc.ncols * (60.0 + 4.0 * B.feats.size() + 40.0 * B.P.n_layers), 4.0 * (double)npad * cyc.ncols,
-                0, raw_slots_host, raw_noise_host, true);
+  a.n = n; a.npad = npad; a.tiles = (int)(npad / GG_T); a.tiles_c = (int)(ncols / GG_T); a.rect = 0; a.same_points = 1;
+  if (cyc) { a.cyc_P = cyc->P; a.cyc_rank = cyc->rank; a.cyc_nb = cyc->nb; a.kinv_t = cyc->kinv_t; }
+  rc = gg_upload_net(h, B, a);
+  if (rc) return rc;
+  return gg_run(h, B, a, 0.5 * gg_work(B, (double)npad, (double)ncols, 4.0), 4.0 * (double)npad * ncols, 0, grad_slots_host,
+                grad_noise_host, cyc != nullptr);
+}
+
+// What the two VJP entries below share: the program, the features of the row points (dFeat) and of the column points
+// (dFeat2; dXc == nullptr: K(Xr, Xr), one feature set, White on i == j), the rectangular arguments and the network weights
+static int gg_rect_setup(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dXr, i64 nr, const double* dXc, i64 nc,
+                         i64 d_all, const double* Wd, i64 ldw, GGBuilt& B, GGArgs& a) {
+  int rc = gg_build(h, prog, n_nodes, d_all, B);
+  if (rc) return rc;
+  const bool same = (dXc == nullptr);
+  if (same) nc = nr;
+  const i64 nrp = gps_pad(nr), ncp = gps_pad(nc);
+  rc = gg_features(h, B, dXr, nr, d_all, nrp, h->dFeat);
+  if (rc) return rc;
+  if (!same) { rc = gg_features(h, B, dXc, nc, d_all, ncp, h->dFeat2); if (rc) return rc; }
+  memset(&a, 0, sizeof(a));
+  a.Ft = h->dFeat.d(); a.ldf = nrp;
+  a.Ftc = same ? h->dFeat.d() : h->dFeat2.d(); a.ldfc = same ? nrp : ncp;
+  a.n = nr; a.npad = nrp; a.tiles = (int)(nrp / GG_T); a.tiles_c = (int)(ncp / GG_T);
+  a.rect = 1; a.same_points = same ? 1 : 0; a.Wd = Wd; a.ldw = ldw; a.nr = nr; a.nc = nc;
+  return gg_upload_net(h, B, a);
 }
 
 // Vector-Jacobian product of the kernel-matrix build:  slots (+)= sum_{i < nr, j < nc} Wd[i][j] d k(xr_i, xc_j) / d theta
@@ -741,22 +607,11 @@ int gps_launch_grad_general_cyclic(gps_handle_t h, const gps_kern_node_t* prog, 
 int gps_launch_kmat_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dXr, i64 nr, const double* dXc,
                         i64 nc, i64 d_all, const double* Wd, i64 ldw, int accumulate, double* grad_slots_host) {
   GGBuilt B;
-  int rc = gg_build(h, prog, n_nodes, d_all, B);
-  if (rc) return rc;
-  const bool same = (dXc == nullptr);
-  if (same) { dXc = dXr; nc = nr; }
-  const i64 nrp = gps_pad(nr), ncp = gps_pad(nc);
-  rc = gg_features(h, B, dXr, nr, d_all, nrp, h->dFeat);
-  if (rc) return rc;
-  if (!same) { rc = gg_features(h, B, dXc, nc, d_all, ncp, h->dFeat2); if (rc) return rc; }
   GGArgs a;
-  memset(&a, 0, sizeof(a));
-  a.Ft = h->dFeat.d(); a.ldf = nrp;
-  a.Ftc = same ? h->dFeat.d() : h->dFeat2.d(); a.ldfc = same ? nrp : ncp;
-  a.n = nr; a.npad = nrp; a.tiles = (int)(nrp / GG_T); a.tiles_c = (int)(ncp / GG_T);
-  a.rect = 1; a.same_points = same ? 1 : 0; a.Wd = Wd; a.ldw = ldw; a.nr = nr; a.nc = nc;
-  return gg_run(h, B, a, (double)nrp * ncp * (60.0 + 4.0 * B.feats.size() + 40.0 * B.P.n_layers), 8.0 * (double)nrp * ncp,
-                accumulate, grad_slots_host, nullptr);
+  int rc = gg_rect_setup(h, prog, n_nodes, dXr, nr, dXc, nc, d_all, Wd, ldw, B, a);
+  if (rc) return rc;
+  const double rows = (double)a.npad, cols = (double)a.tiles_c * GG_T;
+  return gg_run(h, B, a, gg_work(B, rows, cols, 4.0), 8.0 * rows * cols, accumulate, grad_slots_host, nullptr, false);
 }
 
 // d (sum_i kbar_i Kdiag_i) / d theta for the constant Kdiag of these programs (every primitive's Kdiag is its variance,
@@ -771,7 +626,7 @@ int gps_kdiag_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 
     double sv[GPS_MAX_STACK + 1], st[GPS_MAX_STACK + 1]; int sp = 0;
     int slot = -1;
     for (int nd = 0; nd < B.P.n_nodes; ++nd) {
-      const GGNode& g = B.P.nodes[nd];
+      const GradNode& g = B.P.nodes[nd];
       if (g.op == GPS_K_ADD || g.op == GPS_K_MUL) {
         const double b = sv[--sp], tb = st[sp], a = sv[--sp], ta = st[sp];
         sv[sp] = (g.op == GPS_K_ADD) ? a + b : a * b;
@@ -795,33 +650,20 @@ int gps_launch_kmat_input_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n
                               double* grad_X_host) {
   if (d_all > GPS_MAX_DIMS) return gps_fail(h, GPS_ERR_UNSUPPORTED, "input gradient: more input dimensions than GPS_MAX_DIMS");
   GGBuilt B;
-  int rc = gg_build(h, prog, n_nodes, d_all, B);
-  if (rc) return rc;
-  const bool same = (dXc == nullptr);
-  if (same) { dXc = dXr; nc = nr; }
-  const i64 nrp = gps_pad(nr), ncp = gps_pad(nc);
-  if (!same) { rc = gg_features(h, B, dXc, nc, d_all, ncp, h->dFeat2); if (rc) return rc; }
-  rc = gg_features(h, B, dXr, nr, d_all, nrp, h->dFeat);            // (last: leaves the feature table in dProg)
-  if (rc) return rc;
   GGArgs a;
-  memset(&a, 0, sizeof(a));
-  a.Ft = h->dFeat.d(); a.ldf = nrp;
-  a.Ftc = same ? h->dFeat.d() : h->dFeat2.d(); a.ldfc = same ? nrp : ncp;
-  a.n = nr; a.npad = nrp; a.tiles = (int)(nrp / GG_T); a.tiles_c = (int)(ncp / GG_T);
-  a.rect = 1; a.same_points = same ? 1 : 0; a.Wd = Wd; a.ldw = ldw; a.nr = nr; a.nc = nc;
-  const size_t wbytes = B.W.size() * 8;
-  GPS_HIP(h, h->dNkn.ensure(wbytes + 64));
-  GPS_HIP(h, h->ring.upload(h->dNkn.p, B.W.data(), wbytes, h->stream));
-  a.Wnet = (const double*)h->dNkn.p;
+  int rc = gg_rect_setup(h, prog, n_nodes, dXr, nr, dXc, nc, d_all, Wd, ldw, B, a);
+  if (rc) return rc;
+  const i64 nrp = a.npad;
   GIArgs gi;
-  gi.feats = (const GGFeat*)h->dProg.p; gi.d_all = (int)d_all; gi.rows_pad = nrp;
+  gi.feats = (const GradFeat*)h->dProg.p; gi.d_all = (int)d_all; gi.rows_pad = nrp;      // (gg_features left the table there)
   int slices = 2048 / a.tiles; if (slices > a.tiles_c) slices = a.tiles_c; if (slices < 1) slices = 1; if (slices > 64) slices = 64;
   gi.slices = slices;
   const size_t pbytes = (size_t)slices * nrp * d_all * 8;
   GPS_HIP(h, h->dTmp2.ensure(pbytes));
   gi.part = h->dTmp2.d();
   {
-    LaunchScope ls(h, KC_REDUCE, (double)nrp * ncp * (60.0 + 6.0 * B.feats.size() + 40.0 * B.P.n_layers), 8.0 * (double)nrp * ncp);
+    const double rows = (double)nrp, cols = (double)a.tiles_c * GG_T;
+    LaunchScope ls(h, KC_REDUCE, gg_work(B, rows, cols, 6.0), 8.0 * rows * cols);
     hipLaunchKernelGGL(gg_input_kernel, dim3((unsigned)a.tiles, (unsigned)slices), dim3(256), 0, h->stream, a, B.P, gi);
     GPS_HIP(h, hipGetLastError());
   }
