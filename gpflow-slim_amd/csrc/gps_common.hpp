@@ -204,6 +204,7 @@ struct gps_handle_s {
   int predict_inv_blocks = 1;   // option "predict_inverse_blocks"
   DevBuf dMean;     // [n_new, r]
   DevBuf dVar;      // [n_new] or [nspad, nspad]
+  DevBuf dKdiag;    // [n] per-point Kdiag of a program with Linear / Polynomial (gps_launch_kdiag_vec)
   // ---- block-column distributed factorisation (gps_dist_*) ----
   int dist_P = 0, dist_rank = 0;
   i64 dist_nb = 0, dist_np = 0, dist_r = 0;
@@ -443,6 +444,12 @@ int gps_launch_kmat_block(gps_handle_t h, const gps_kern_node_t* prog, int n_nod
                           i64 n, i64 d_all, i64 npad, double diag_add, double* dKb, i64 ldk, i64 r0,
                           i64 nrows, i64 c0, i64 ncols, int prep);
 int gps_launch_kdiag(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double* kdiag_const);
+// Kdiag of a program that contains Linear / Polynomial depends on the point: gps_launch_kdiag refuses those, and
+// gps_launch_kdiag_vec writes Kdiag(X)[i] for the n resident points dX [n, d_all] to d_out [n] (any program; uses dFeat).
+// sum_out (optional): sum_i Kdiag_i on the host -- that one synchronises.
+bool gps_kdiag_is_const(const gps_kern_node_t* prog, int n_nodes);
+int gps_launch_kdiag_vec(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n, i64 d_all, double* d_out,
+                         double* sum_out);
 // grad.hip, grad_general.hip (what the two share among themselves: grad_common.hpp)
 // slot count and, per slot, the lengthscale that divides its raw sum (0: none) -- of any program, whichever kernel takes it
 int gps_grad_slots(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, int* n_slots);

@@ -81,7 +81,12 @@ extern "C" int gps_conditional(gps_handle_t h, const gps_kern_node_t* prog, int 
   rc = inducing_setup(h, prog, n_nodes, Z, m, Xnew, n_new, d_all, jitter, k, c);
   if (rc) return rc;
   if (!full_cov) {
-    rc = gps_launch_kdiag(h, prog, n_nodes, &c.knn_const);
+    if (gps_kdiag_is_const(prog, n_nodes)) rc = gps_launch_kdiag(h, prog, n_nodes, &c.knn_const);
+    else {                                               // Linear / Polynomial: Kdiag(Xnew) per point
+      GPS_HIP(h, h->dKdiag.ensure((size_t)n_new * 8));
+      rc = gps_launch_kdiag_vec(h, prog, n_nodes, h->dXnew.d(), n_new, d_all, h->dKdiag.d(), nullptr);
+      c.dKnnDiag = h->dKdiag.d();
+    }
     if (rc) return rc;
   } else {
     GPS_HIP(h, h->dTmp.ensure((size_t)c.nsp * c.nsp * 8 + (size_t)c.mp * c.mp * 8));

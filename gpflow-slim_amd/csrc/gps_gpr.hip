@@ -155,8 +155,16 @@ static int gpr_factor(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, 
   h->have_factor = false; h->factor_gen++; h->dist_have_part_factor = false;
   {
     // leaves refined or not: from the bound cond(K + noise I) <= (N Kdiag + noise) / noise (gps_gpr_needs_refine)
+    // (Linear / Polynomial: Kdiag depends on the point; sum_i Kdiag_i is the same trace bound on lambda_max as N Kdiag)
     double kd = 0.0;
-    int rck = gps_launch_kdiag(h, prog, n_nodes, &kd);
+    int rck;
+    if (gps_kdiag_is_const(prog, n_nodes)) rck = gps_launch_kdiag(h, prog, n_nodes, &kd);
+    else {
+      GPS_HIP(h, h->dKdiag.ensure((size_t)h->n * 8));
+      double tr = 0.0;
+      rck = gps_launch_kdiag_vec(h, prog, n_nodes, h->dX.d(), h->n, h->d_all, h->dKdiag.d(), &tr);
+      kd = tr / (double)h->n;
+    }
     if (rck) return rck;
     h->refine_now = gps_gpr_needs_refine(h, noise_var, kd, h->n);
     h->factor_refine = h->refine_now;
@@ -601,12 +609,19 @@ extern "C" int gps_gpr_predict(gps_handle_t h, const gps_kern_node_t* prog, int 
   double* dss = dmean + n_new * (r > 0 ? r : 1);
   rc = gps_launch_rowdot(h, dAt, np, n_new, np, h->dAlpha.d(), np, r, dmean, dss);
   if (rc) return rc;
-  double kd = 0.0;
-  rc = gps_launch_kdiag(h, prog, n_nodes, &kd);
-  if (rc) return rc;
   if (!full_cov) {
+    // Kdiag: one number, or (Linear / Polynomial, kernels.py:507-510, 553-554) one per test point
+    double kd = 0.0;
+    const double* dkd = nullptr;
+    if (gps_kdiag_is_const(prog, n_nodes)) rc = gps_launch_kdiag(h, prog, n_nodes, &kd);
+    else {
+      GPS_HIP(h, h->dKdiag.ensure((size_t)n_new * 8));
+      rc = gps_launch_kdiag_vec(h, prog, n_nodes, h->dXnew.d(), n_new, d, h->dKdiag.d(), nullptr);
+      dkd = h->dKdiag.d();
+    }
+    if (rc) return rc;
     GPS_HIP(h, h->dVar.ensure((size_t)n_new * 8));
-    rc = gps_launch_var_finish(h, h->dVar.d(), nullptr, kd, dss, n_new);
+    rc = gps_launch_var_finish(h, h->dVar.d(), dkd, kd, dss, n_new);
     if (rc) return rc;
     GPS_HIP(h, hipMemcpyAsync(var_out, h->dVar.p, (size_t)n_new * 8, hipMemcpyDeviceToHost, h->stream));
   } else {

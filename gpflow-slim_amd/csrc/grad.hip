@@ -11,7 +11,8 @@
 // Slot layout (host and device agree on it): for every primitive node of the kernel program, in
 // program order: [variance] then, stationary kernels: one slot per active dim (d k / d lengthscale_d;
 // an isotropic kernel's gradient is the sum of its slots), Periodic: [lengthscale, period],
-// White / Constant: nothing more.  The noise variance has its own output.
+// White / Constant: nothing more, RatQuad: the stationary slots and then [alpha]; Linear: one slot per active dim
+// (d k / d v_d; no variance slot), Polynomial: the same and then [offset].  The noise variance has its own output.
 #include "grad_common.hpp"
 
 #define GT_R 64            // tile rows
@@ -34,6 +35,9 @@ struct GArgs {
   int cyc_P, cyc_rank; i64 cyc_nb; int kinv_t;
 };
 
+// EXT: the instance that also knows RatQuad, Linear and Polynomial.  Programs without them run the other one, whose code --
+// registers, no scratch -- is what it was before those primitives existed (with them in one kernel the compiler spilled).
+template <bool EXT>
 __global__ __launch_bounds__(256) void grad_kernel(GArgs a, GProg P) {
   __shared__ double Fr_s[GRAD_MAXF * GT_R];
   __shared__ double Fc_s[GRAD_MAXF * GT_C];
@@ -104,7 +108,7 @@ __global__ __launch_bounds__(256) void grad_kernel(GArgs a, GProg P) {
         double acc8[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc8[e] = 0.0;
-        if (node.op == GPS_K_PERIODIC) {
+        if (node.op == GPS_K_PERIODIC || (EXT && grad_is_dot(node.op))) {
           for (int f = 0; f < nfd; ++f) {
             double fr[4], fc[2];
 #pragma unroll
@@ -114,9 +118,14 @@ __global__ __launch_bounds__(256) void grad_kernel(GArgs a, GProg P) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc8[e] = fma(fr[e >> 1], fc[e & 1], acc8[e]);
           }
-          const double l2 = node.ls0 * node.ls0;
+          if (node.op == GPS_K_PERIODIC) {
+            const double l2 = node.ls0 * node.ls0;
 #pragma unroll
-          for (int e = 0; e < 8; ++e) val[e] = grad_periodic_value(node.variance, node.ndims, acc8[e], l2, &rr[e]);
+            for (int e = 0; e < 8; ++e) val[e] = grad_periodic_value(node.variance, node.ndims, acc8[e], l2, &rr[e]);
+          } else {                           // Linear / Polynomial: rr keeps lin
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { rr[e] = acc8[e]; val[e] = grad_dot_value(node.op, acc8[e], node.variance, node.period); }
+          }
         } else {
           for (int f = 0; f < nfd; ++f) {
             double fr[4], fc[2];
@@ -128,7 +137,7 @@ __global__ __launch_bounds__(256) void grad_kernel(GArgs a, GProg P) {
             for (int e = 0; e < 8; ++e) { const double dlt = fr[e >> 1] - fc[e & 1]; acc8[e] = fma(dlt, dlt, acc8[e]); }
           }
 #pragma unroll
-          for (int e = 0; e < 8; ++e) { rr[e] = acc8[e]; val[e] = grad_stationary_value(node.op, node.variance, acc8[e]); }
+          for (int e = 0; e < 8; ++e) { rr[e] = acc8[e]; val[e] = grad_stationary_value<EXT>(node.op, node.variance, acc8[e], node.period); }
         }
       }
 #pragma unroll
@@ -153,6 +162,42 @@ __global__ __launch_bounds__(256) void grad_kernel(GArgs a, GProg P) {
 #pragma unroll
         for (int u = 0; u < G_MAXP; ++u) pve[u] = pv[u][e];
         f8[e] = w[e] * grad_prog_tangent(P, pve, p);
+      }
+      if (EXT && grad_is_dot(node.op)) {
+        // Linear / Polynomial: Q_e = c W adj * dk/d(lin) ; d k / d v_d = Q F_d F'_d / v_d ; d k / d offset = Q
+        double Q[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) Q[e] = f8[e] * grad_dot_dlin(node.op, r2[p][e], node.variance, node.period);
+        if (node.op == GPS_K_POLYNOMIAL) {
+          double s = 0.0;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) s += Q[e];
+          s = grad_wave_sum(s);
+          if (lane == 0) acc_s[wave][node.slot0 + node.ndims] += s;
+        }
+        __syncthreads();
+        for (int idx = tid; idx < node.ndims * GT_R; idx += 256) {
+          const int f = idx >> 6, pp = idx & 63;
+          Fr_s[f * GT_R + pp] = a.Ft[(i64)(node.f0 + f) * a.ldf + gi0 + pp];
+        }
+        for (int idx = tid; idx < node.ndims * GT_C; idx += 256) {
+          const int f = idx >> 5, pp = idx & 31;
+          Fc_s[f * GT_C + pp] = a.Ft[(i64)(node.f0 + f) * a.ldf + gj0 + pp];
+        }
+        __syncthreads();
+        for (int d = 0; d < node.ndims; ++d) {
+          double fr[4], fc[2];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) fr[q] = Fr_s[d * GT_R + ty * 4 + q];
+#pragma unroll
+          for (int q = 0; q < 2; ++q) fc[q] = Fc_s[d * GT_C + tx * 2 + q];
+          double s = 0.0;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) s += Q[e] * (fr[e >> 1] * fc[e & 1]);
+          s = grad_wave_sum(s);
+          if (lane == 0) acc_s[wave][node.slot0 + d] += s;          // the host divides by v_d
+        }
+        continue;
       }
       // variance: d prim / d v = prim / v
       {
@@ -202,7 +247,14 @@ __global__ __launch_bounds__(256) void grad_kernel(GArgs a, GProg P) {
       // stationary: Q_e = c W adj * dk/d(r2) ; d k / d l_d = Q * (-2 delta_d^2 / l_d)
       double Q[8];
 #pragma unroll
-      for (int e = 0; e < 8; ++e) Q[e] = f8[e] * grad_dk_dq2(node.op, node.variance, pv[p][e], r2[p][e]);
+      for (int e = 0; e < 8; ++e) Q[e] = f8[e] * grad_dk_dq2<EXT>(node.op, node.variance, pv[p][e], r2[p][e], node.period);
+      if (EXT && node.op == GPS_K_RATQUAD) {
+        double s = 0.0;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s += f8[e] * grad_ratquad_dalpha(pv[p][e], r2[p][e], node.period);
+        s = grad_wave_sum(s);
+        if (lane == 0) acc_s[wave][node.slot0 + 1 + node.ndims] += s;
+      }
       __syncthreads();
       for (int idx = tid; idx < node.ndims * GT_R; idx += 256) {
         const int f = idx >> 6, pp = idx & 63;
@@ -311,7 +363,11 @@ static int grad_run(gps_handle_t h, const GradPost& post, i64 n, i64 npad, const
   {
     const double cols = (double)a.tiles_c * GT_C;
     LaunchScope ls(h, KC_REDUCE, 0.5 * (double)npad * cols * (60.0 + 4.0 * nfeat), 4.0 * (double)npad * cols);
-    hipLaunchKernelGGL(grad_kernel, dim3(nblocks), dim3(256), 0, h->stream, a, P);
+    bool ext = false;
+    for (int i = 0; i < P.n_nodes; ++i)
+      if (P.nodes[i].op == GPS_K_RATQUAD || P.nodes[i].op == GPS_K_LINEAR || P.nodes[i].op == GPS_K_POLYNOMIAL) ext = true;
+    if (ext) hipLaunchKernelGGL(grad_kernel<true>, dim3(nblocks), dim3(256), 0, h->stream, a, P);
+    else hipLaunchKernelGGL(grad_kernel<false>, dim3(nblocks), dim3(256), 0, h->stream, a, P);
     GPS_HIP(h, hipGetLastError());
   }
   {

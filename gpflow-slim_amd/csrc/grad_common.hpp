@@ -2,7 +2,7 @@
 // 32x32 tiles, up to eight primitives, network layers, the rectangular VJP mode): the feature table and its prep kernel, the
 // per-entry formulas of the primitive kernels, the forward-mode tangent of a Sum / Product program, and the host analysis of
 // the primitive part of a kernel program (slot layout included).  The formulas are the reference's (kernels.py:436-439,
-// 573-610, 806-819; Stationary.euclid_dist's sqrt(r2 + 1e-12), :424-426).  Every expression keeps the grouping it had when
+// 467-471, 499-505, 550-551, 573-610, 806-819; Stationary.euclid_dist's sqrt(r2 + 1e-12), :424-426).  Every expression keeps the grouping it had when
 // each kernel carried its own copy: the compiler contracts multiply-adds by expression shape.
 // Both gradient files include this header, so each gets its own copy of the static host functions and its own code object of
 // the two grad_prep_kernel<> instantiations (same name, same code: the runtime keeps one registration of the shared host stub).
@@ -13,7 +13,8 @@
 #define GRAD_MAX_NODES 32
 #define GRAD_MAXF 64       // feature rows of one primitive: periodic = 3 per dim (<= 21 dims)
 
-struct GradFeat { int dim; int kind; double param; };   // 0: x/param ; 1: cos(2pi x/param) ; 2: sin ; 3: 2pi x/param
+struct GradFeat { int dim; int kind; double param; };   // 0: x/param ; 1: cos(2pi x/param) ; 2: sin ; 3: 2pi x/param ; 4: x*param
+// variance: Polynomial: the offset (Linear: 1) ; period: RatQuad: alpha, Polynomial: degree
 struct GradNode { int op; int prim; int f0; int nf; int slot0; int ndims; double variance; double ls0; double period; };
 
 // ---- feature prep: Ft[f][i] = feature f of point i (zero in the padding) ------------------------------------------------------
@@ -31,6 +32,7 @@ __global__ __launch_bounds__(256) void grad_prep_kernel(const double* __restrict
       const GradFeat pf = tab.f[f];
       const double xv = X[i * d_all + pf.dim];
       if (pf.kind == 0) v = xv / pf.param;
+      else if (pf.kind == 4) v = xv * pf.param;
       else {
         const double ang = 2.0 * M_PI * xv / pf.param;
         v = (pf.kind == 1) ? cos(ang) : (pf.kind == 2 ? sin(ang) : ang);
@@ -95,9 +97,12 @@ __device__ __forceinline__ double grad_lml_weight(const Args& a, i64 i, i64 j, i
 #define GRAD_SQRT3 1.7320508075688772
 #define GRAD_SQRT5 2.23606797749979
 
-// stationary primitive from the squared scaled distance q2
-__device__ __forceinline__ double grad_stationary_value(int op, double variance, double q2) {
+// stationary primitive from the squared scaled distance q2 (alpha: RatQuad's).  EXT == false: a kernel instance that is never
+// handed RatQuad (grad.hip keeps one such instance, with the code it had before that primitive existed)
+template <bool EXT = true>
+__device__ __forceinline__ double grad_stationary_value(int op, double variance, double q2, double alpha) {
   if (op == GPS_K_RBF) return variance * exp(-q2 / 2.0);
+  if (EXT && op == GPS_K_RATQUAD) return variance * exp(-alpha * log1p(0.5 * q2 * (1.0 / alpha)));    // (1 + q2 / (2 alpha))^-alpha
   const double sq3 = GRAD_SQRT3, sq5 = GRAD_SQRT5;
   const double rad = sqrt(q2 + 1e-12);
   if (op == GPS_K_MATERN12) return variance * exp(-rad);
@@ -113,14 +118,37 @@ __device__ __forceinline__ double grad_periodic_value(double variance, int ndims
 }
 
 // d k / d (q2) of a stationary primitive with value k at squared scaled distance q2
-__device__ __forceinline__ double grad_dk_dq2(int op, double variance, double k, double q2) {
+template <bool EXT = true>
+__device__ __forceinline__ double grad_dk_dq2(int op, double variance, double k, double q2, double alpha) {
   if (op == GPS_K_RBF) return -0.5 * k;
+  if (EXT && op == GPS_K_RATQUAD) return -0.5 * k / (1.0 + 0.5 * q2 / alpha);
   const double sq3 = GRAD_SQRT3, sq5 = GRAD_SQRT5;
   const double rad = sqrt(q2 + 1e-12);
   if (op == GPS_K_MATERN12) return -k / (2.0 * rad);
   if (op == GPS_K_EXPONENTIAL) return -k / (4.0 * rad);
   if (op == GPS_K_MATERN32) return -1.5 * variance * exp(-sq3 * rad);
   return -(5.0 / 6.0) * variance * (1.0 + sq5 * rad) * exp(-sq5 * rad);
+}
+
+// d k / d alpha of RatQuad with value k:  k (t / (1 + t) - log1p(t)),  t = q2 / (2 alpha)
+__device__ __forceinline__ double grad_ratquad_dalpha(double k, double q2, double alpha) {
+  const double t = 0.5 * q2 / alpha;
+  return k * (t / (1.0 + t) - log1p(t));
+}
+
+// Linear / Polynomial from lin = sum_d v_d x_d x'_d (the dot product of the features x_d sqrt(v_d)): the value, and d k / d lin
+// -- which is also d k / d offset; d k / d v_d = (d k / d lin) x_d x'_d = (d k / d lin) F_d F'_d / v_d (the host divides)
+__device__ __forceinline__ bool grad_is_dot(int op) { return op == GPS_K_LINEAR || op == GPS_K_POLYNOMIAL; }
+__device__ __forceinline__ double grad_powi(double b, int e) {          // b^e, e >= 0
+  double p = 1.0;
+  for (int q = 0; q < e; ++q) p *= b;
+  return p;
+}
+__device__ __forceinline__ double grad_dot_value(int op, double lin, double offset, double degree) {
+  return op == GPS_K_LINEAR ? lin : grad_powi(lin + offset, (int)degree);
+}
+__device__ __forceinline__ double grad_dot_dlin(int op, double lin, double offset, double degree) {
+  return op == GPS_K_LINEAR ? 1.0 : degree * grad_powi(lin + offset, (int)degree - 1);
 }
 
 // plain (Sum / Product) program over the primitive values pv: d out / d prim_p by forward mode
@@ -153,11 +181,12 @@ __device__ __forceinline__ double grad_prog_tangent(const Prog& P, const double 
 // ---- host: the primitive part of a kernel program ------------------------------------------------------------------------------
 static inline bool grad_is_prim(int op) {
   return op == GPS_K_RBF || op == GPS_K_MATERN12 || op == GPS_K_MATERN32 || op == GPS_K_MATERN52 || op == GPS_K_PERIODIC ||
-         op == GPS_K_WHITE || op == GPS_K_CONSTANT || op == GPS_K_EXPONENTIAL;
+         op == GPS_K_WHITE || op == GPS_K_CONSTANT || op == GPS_K_EXPONENTIAL || op == GPS_K_RATQUAD || op == GPS_K_LINEAR ||
+         op == GPS_K_POLYNOMIAL;
 }
 
-// what the analysis hands back beside the device nodes: the feature table, the lengthscale that divides each per-dim slot's
-// raw sum (0: none), and the counts
+// what the analysis hands back beside the device nodes: the feature table, the lengthscale (Linear / Polynomial: the
+// variance v_d) that divides each per-dim slot's raw sum (0: none), and the counts
 struct GradPrims {
   int n_prims = 0, n_slots = 0;
   std::vector<GradFeat> feats;
@@ -166,7 +195,8 @@ struct GradPrims {
 
 // nodes [0, n_nodes) of `prog` -- primitives and, unless the program feeds a network (nkn), Sum / Product -- into `nodes`:
 // stack discipline, parameter ranges, feature rows and slots ([variance] then one slot per active dim, Periodic:
-// [lengthscale, period], White / Constant: nothing more), at most max_prims primitives (too_many: the kernel's own message)
+// [lengthscale, period], White / Constant: nothing more, RatQuad: [alpha] after the dims; Linear: one slot per active dim and
+// no variance slot, Polynomial: the same and then [offset]), at most max_prims primitives (too_many: the kernel's own message)
 static int grad_analyse_prims(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, int max_prims, const char* too_many,
                               bool nkn, GradNode* nodes, GradPrims& R) {
   if (n_nodes <= 0 || n_nodes > GRAD_MAX_NODES) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: program too long");
@@ -190,7 +220,8 @@ static int grad_analyse_prims(gps_handle_t h, const gps_kern_node_t* prog, int n
     depth += 1;
     if (!nkn && depth > GPS_MAX_STACK) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: expression too deep");
     if (!(nd.variance > 0.0)) return gps_fail(h, GPS_ERR_ARG, "gradient: variance must be positive");
-    ls_of_slot.push_back(0.0);
+    const bool dot = nd.op == GPS_K_LINEAR || nd.op == GPS_K_POLYNOMIAL;
+    if (!dot) ls_of_slot.push_back(0.0);
     if (nd.op == GPS_K_WHITE || nd.op == GPS_K_CONSTANT) { R.n_slots += 1; continue; }
     if (nd.n_dims <= 0 || nd.n_dims > GPS_MAX_DIMS) return gps_fail(h, GPS_ERR_ARG, "gradient: n_dims out of range");
     for (int d = 0; d < nd.n_dims; ++d)
@@ -202,10 +233,25 @@ static int grad_analyse_prims(gps_handle_t h, const gps_kern_node_t* prog, int n
       for (int d = 0; d < nd.n_dims; ++d) feats.push_back({nd.active_dims[d], 3, nd.period});
       g.nf = 3 * nd.n_dims; g.ls0 = nd.lengthscales[0];
       R.n_slots += 3; ls_of_slot.push_back(0.0); ls_of_slot.push_back(0.0);
+    } else if (dot) {
+      if (nd.op == GPS_K_LINEAR && nd.variance != 1.0) return gps_fail(h, GPS_ERR_ARG, "gradient: the variance field of Linear must be 1");
+      if (nd.op == GPS_K_POLYNOMIAL && (!(nd.period >= 1.0) || nd.period != floor(nd.period) || nd.period > 64.0))
+        return gps_fail(h, GPS_ERR_ARG, "gradient: Polynomial degree must be an integer in 1 .. 64");
+      for (int d = 0; d < nd.n_dims; ++d) {
+        if (!(nd.lengthscales[d] > 0.0)) return gps_fail(h, GPS_ERR_ARG, "gradient: Linear / Polynomial variance must be positive");
+        feats.push_back({nd.active_dims[d], 4, sqrt(nd.lengthscales[d])}); ls_of_slot.push_back(nd.lengthscales[d]);
+      }
+      g.nf = nd.n_dims;
+      R.n_slots += nd.n_dims;
+      if (nd.op == GPS_K_POLYNOMIAL) { R.n_slots += 1; ls_of_slot.push_back(0.0); }
     } else {
       for (int d = 0; d < nd.n_dims; ++d) { feats.push_back({nd.active_dims[d], 0, nd.lengthscales[d]}); ls_of_slot.push_back(nd.lengthscales[d]); }
       g.nf = nd.n_dims;
       R.n_slots += 1 + nd.n_dims;
+      if (nd.op == GPS_K_RATQUAD) {
+        if (!(nd.period > 0.0)) return gps_fail(h, GPS_ERR_ARG, "gradient: RatQuad alpha must be positive");
+        R.n_slots += 1; ls_of_slot.push_back(0.0);
+      }
     }
     if (g.nf > GRAD_MAXF) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: too many active dims");
   }

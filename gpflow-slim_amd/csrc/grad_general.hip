@@ -13,7 +13,7 @@
 // added on the host (bit-reproducible, no floating-point atomics).
 //
 // Slot layout (host and device agree on it): primitives first, as in grad.hip ([variance], then one slot per active
-// dim, or [lengthscale, period] for Periodic); then, for every Linear layer in network order and every output o:
+// dim, or [lengthscale, period] for Periodic; RatQuad, Linear, Polynomial: see grad.hip); then, for every Linear layer in network order and every output o:
 // [W[o][0 .. in-1], bias[o]].
 #include "grad_common.hpp"
 
@@ -78,15 +78,21 @@ __device__ __forceinline__ void gg_prim(const GradNode& node, const double* Fr_s
   double acc[GG_E];
 #pragma unroll
   for (int e = 0; e < GG_E; ++e) acc[e] = 0.0;
-  if (node.op == GPS_K_PERIODIC) {
-    for (int f = 0; f < 2 * node.ndims; ++f) {
+  if (node.op == GPS_K_PERIODIC || grad_is_dot(node.op)) {
+    const int nfd = (node.op == GPS_K_PERIODIC) ? 2 * node.ndims : node.ndims;
+    for (int f = 0; f < nfd; ++f) {
       const double r0 = Fr_s[f * GG_T + ty * 2], r1 = Fr_s[f * GG_T + ty * 2 + 1];
       const double c0 = Fc_s[f * GG_T + tx * 2], c1 = Fc_s[f * GG_T + tx * 2 + 1];
       acc[0] = fma(r0, c0, acc[0]); acc[1] = fma(r0, c1, acc[1]); acc[2] = fma(r1, c0, acc[2]); acc[3] = fma(r1, c1, acc[3]);
     }
-    const double l2 = node.ls0 * node.ls0;
+    if (node.op == GPS_K_PERIODIC) {
+      const double l2 = node.ls0 * node.ls0;
 #pragma unroll
-    for (int e = 0; e < GG_E; ++e) val[e] = grad_periodic_value(node.variance, node.ndims, acc[e], l2, &rr[e]);
+      for (int e = 0; e < GG_E; ++e) val[e] = grad_periodic_value(node.variance, node.ndims, acc[e], l2, &rr[e]);
+    } else {                                 // Linear / Polynomial: rr keeps lin
+#pragma unroll
+      for (int e = 0; e < GG_E; ++e) { rr[e] = acc[e]; val[e] = grad_dot_value(node.op, acc[e], node.variance, node.period); }
+    }
     return;
   }
   for (int f = 0; f < node.ndims; ++f) {
@@ -97,7 +103,7 @@ __device__ __forceinline__ void gg_prim(const GradNode& node, const double* Fr_s
     d = r1 - c0; acc[2] = fma(d, d, acc[2]); d = r1 - c1; acc[3] = fma(d, d, acc[3]);
   }
 #pragma unroll
-  for (int e = 0; e < GG_E; ++e) { rr[e] = acc[e]; val[e] = grad_stationary_value(node.op, node.variance, acc[e]); }
+  for (int e = 0; e < GG_E; ++e) { rr[e] = acc[e]; val[e] = grad_stationary_value(node.op, node.variance, acc[e], node.period); }
 }
 
 // ---- pass 1: values of all primitives at the thread's four entries of tile (gi0, gj0)
@@ -270,6 +276,26 @@ __global__ __launch_bounds__(256) void gg_kernel(GGArgs a, GGProg P) {
 #pragma unroll
           for (int e = 0; e < GG_E; ++e) { f4[e] = fp[p][e]; k4[e] = pv[p][e]; }
         }
+      if (grad_is_dot(node.op)) {
+        // Linear / Polynomial: Q_e = f dk/d(lin) ; d k / d v_d = Q F_d F'_d / v_d ; d k / d offset = Q
+        gg_stage(a, node.f0, node.ndims, gi0, gj0, Fr_s, Fc_s, tid);
+        double val[GG_E], lin[GG_E], Q[GG_E];
+        gg_prim(node, Fr_s, Fc_s, ty, tx, gi0, gj0, same_points, val, lin);
+#pragma unroll
+        for (int e = 0; e < GG_E; ++e) Q[e] = f4[e] * grad_dot_dlin(node.op, lin[e], node.variance, node.period);
+        if (node.op == GPS_K_POLYNOMIAL) {
+          double s = grad_wave_sum((Q[0] + Q[1]) + (Q[2] + Q[3]));
+          if (lane == 0) acc_s[wave][node.slot0 + node.ndims] += s;
+        }
+        for (int d = 0; d < node.ndims; ++d) {
+          const double r0 = Fr_s[d * GG_T + ty * 2], r1 = Fr_s[d * GG_T + ty * 2 + 1];
+          const double c0 = Fc_s[d * GG_T + tx * 2], c1 = Fc_s[d * GG_T + tx * 2 + 1];
+          double s = Q[0] * (r0 * c0) + Q[1] * (r0 * c1) + Q[2] * (r1 * c0) + Q[3] * (r1 * c1);
+          s = grad_wave_sum(s);
+          if (lane == 0) acc_s[wave][node.slot0 + d] += s;               // the host divides by v_d
+        }
+        continue;
+      }
       {                                                    // variance: d prim / d v = prim / v
         double s = 0.0;
 #pragma unroll
@@ -309,7 +335,14 @@ __global__ __launch_bounds__(256) void gg_kernel(GGArgs a, GGProg P) {
       double val[GG_E], q4[GG_E], Q[GG_E];
       gg_prim(node, Fr_s, Fc_s, ty, tx, gi0, gj0, same_points, val, q4);
 #pragma unroll
-      for (int e = 0; e < GG_E; ++e) Q[e] = f4[e] * grad_dk_dq2(node.op, node.variance, k4[e], q4[e]);
+      for (int e = 0; e < GG_E; ++e) Q[e] = f4[e] * grad_dk_dq2(node.op, node.variance, k4[e], q4[e], node.period);
+      if (node.op == GPS_K_RATQUAD) {
+        double s = 0.0;
+#pragma unroll
+        for (int e = 0; e < GG_E; ++e) s += f4[e] * grad_ratquad_dalpha(k4[e], q4[e], node.period);
+        s = grad_wave_sum(s);
+        if (lane == 0) acc_s[wave][node.slot0 + 1 + node.ndims] += s;
+      }
       for (int d = 0; d < node.ndims; ++d) {
         const double r0 = Fr_s[d * GG_T + ty * 2], r1 = Fr_s[d * GG_T + ty * 2 + 1];
         const double c0 = Fc_s[d * GG_T + tx * 2], c1 = Fc_s[d * GG_T + tx * 2 + 1];
@@ -398,8 +431,25 @@ __global__ __launch_bounds__(256) void gg_input_kernel(GGArgs a, GGProg P, GIArg
       gg_stage(a, node.f0, node.ndims, gi0, gj0, Fr_s, Fc_s, tid);
       double val[GG_E], q4[GG_E];
       gg_prim(node, Fr_s, Fc_s, ty, tx, gi0, gj0, same_points, val, q4);
+      if (grad_is_dot(node.op)) {
+        // Linear / Polynomial: lin = sum_d F_id F_jd, F = x sqrt(v) :  d k / d x_id = (d k / d lin) F_jd sqrt(v_d)
 #pragma unroll
-      for (int e = 0; e < GG_E; ++e) Q[e] = 2.0 * f4[e] * grad_dk_dq2(node.op, node.variance, k4[e], q4[e]);
+        for (int e = 0; e < GG_E; ++e) Q[e] = f4[e] * grad_dot_dlin(node.op, q4[e], node.variance, node.period);
+        for (int d = 0; d < node.ndims; ++d) {
+          const double c0 = Fc_s[d * GG_T + tx * 2], c1 = Fc_s[d * GG_T + tx * 2 + 1];
+          double s0 = Q[0] * c0 + Q[1] * c1;
+          double s1 = Q[2] * c0 + Q[3] * c1;
+#pragma unroll
+          for (int off = 1; off < 16; off <<= 1) { s0 += __shfl_xor(s0, off, 64); s1 += __shfl_xor(s1, off, 64); }
+          if (tx == 0) {
+            const GradFeat ft = gi.feats[node.f0 + d];
+            rowacc[ty * 2][ft.dim] += s0 * ft.param; rowacc[ty * 2 + 1][ft.dim] += s1 * ft.param;
+          }
+        }
+        continue;
+      }
+#pragma unroll
+      for (int e = 0; e < GG_E; ++e) Q[e] = 2.0 * f4[e] * grad_dk_dq2(node.op, node.variance, k4[e], q4[e], node.period);
       for (int d = 0; d < node.ndims; ++d) {
         const double r0 = Fr_s[d * GG_T + ty * 2], r1 = Fr_s[d * GG_T + ty * 2 + 1];
         const double c0 = Fc_s[d * GG_T + tx * 2], c1 = Fc_s[d * GG_T + tx * 2 + 1];
@@ -432,6 +482,9 @@ int gps_grad_slots(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, int
     if (op == GPS_K_ADD || op == GPS_K_MUL || op == GPS_K_NKN_PRODUCT || op == GPS_K_NKN_ACT) continue;
     if (op == GPS_K_WHITE || op == GPS_K_CONSTANT) s += 1;
     else if (op == GPS_K_PERIODIC) s += 3;
+    else if (op == GPS_K_RATQUAD) s += 2 + prog[i].n_dims;
+    else if (op == GPS_K_LINEAR) s += prog[i].n_dims;
+    else if (op == GPS_K_POLYNOMIAL) s += prog[i].n_dims + 1;
     else if (op == GPS_K_NKN_LINROW) s += prog[i].n_dims + 1;
     else if (grad_is_prim(op)) s += 1 + prog[i].n_dims;
     else return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: unknown op");
@@ -616,8 +669,11 @@ int gps_launch_kmat_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes
 
 // d (sum_i kbar_i Kdiag_i) / d theta for the constant Kdiag of these programs (every primitive's Kdiag is its variance,
 // kernels.py:428-429, 803-804, 327-328; Sum / Product fold them, :1075-1076, 1083-1084): kbar = sum_i kbar_i; only the
-// variance slots receive anything.  Forward mode over the fold, one primitive at a time.
+// variance slots receive anything (RatQuad's first slot is its variance).  Forward mode over the fold, one primitive at a time.
+// Linear / Polynomial: Kdiag depends on the point (and on v_d, offset) -- not taken here.
 int gps_kdiag_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, double kbar, double* grad_slots_host) {
+  if (!gps_kdiag_is_const(prog, n_nodes))
+    return gps_fail(h, GPS_ERR_UNSUPPORTED, "Kdiag gradient: Kdiag is not constant for a kernel program with Linear / Polynomial");
   GGBuilt B;
   int rc = gg_build(h, prog, n_nodes, d_all, B);
   if (rc) return rc;

@@ -5,6 +5,9 @@
 //   Stationary.square_dist   kernels.py:408-421   (x/l ; -2 a.b + |a|^2 + |b|^2 ; clip >= 0)
 //   Stationary.euclid_dist   kernels.py:424-426   (sqrt(r2 + 1e-12))
 //   RBF / Matern12/32/52 / Exponential .K         kernels.py:436-439, 560-610
+//   RatQuad.K                kernels.py:467-471   (same distance; (1 + r2 / (2 alpha))^-alpha = exp(-alpha log1p(r2 / (2 alpha))))
+//   Linear.K / Polynomial.K  kernels.py:499-505, 550-551 (features x_d sqrt(v_d): the dot product IS the kernel, and
+//                                                  K(X, X) is symmetric to the bit; no norm row)
 //   Periodic.K               kernels.py:806-819   (via u = (cos, sin) features: the docstring's
 //                                                  own mapping, kernels.py:776 -- avoids the
 //                                                  reference's [N,M,D] temporary and D*N*M sin())
@@ -25,13 +28,13 @@
 #define KLS 64         // LDS slab stride (doubles) per feature row
 #define KMAXF 64       // features per primitive (32 dims x {cos, sin})
 
-struct PrepFeat { int dim; int kind; double param; };   // kind 0: x/param ; 1: cos(2 pi x/param) ; 2: sin(...)
+struct PrepFeat { int dim; int kind; double param; };   // kind 0: x/param ; 1: cos(2 pi x/param) ; 2: sin(...) ; 3: x*param
 struct PrepNorm { int f0; int nf; };
 
 struct KNodeDev {
   int op; int f0; int nf; int norm_row;   // norm_row: row index in Ft holding |a|^2 (or -1)
-  double variance; double c0;             // c0: periodic lengthscale
-  double c1;                              // periodic: -1 / (4 c0^2)
+  double variance; double c0;             // c0: periodic lengthscale ; RatQuad: alpha ; Polynomial: degree (variance: its offset)
+  double c1;                              // periodic: -1 / (4 c0^2) ; RatQuad: 1 / alpha
 };
 struct KProgDev {
   int n_nodes;
@@ -72,6 +75,7 @@ __device__ __forceinline__ void kmat_prep_body(const double* __restrict__ X, i64
     const double xv = x[pf.dim];
     double v;
     if (pf.kind == 0) v = xv / pf.param;
+    else if (pf.kind == 3) v = xv * pf.param;
     else {
       const double ang = 2.0 * M_PI * xv / pf.param;
       v = (pf.kind == 1) ? cos(ang) : sin(ang);
@@ -208,6 +212,19 @@ __device__ __forceinline__ double gps_exp_nonpos(double x) {        // (kernels 
   const ExpTab t = gps_exp_load();
   return gps_exp_nonpos(x, t);
 }
+// RatQuad (kernels.py:470-471): variance (1 + 0.5 r2 (1 / alpha))^(-alpha), the power as exp(-alpha log1p(.)): the argument of
+// the exponential is <= 0 like every other one here, and its rounding error alpha log1p(.) u stays far below that of pow() only
+// where the value itself has underflowed.  inv_alpha = 1 / alpha from the host.
+__device__ __forceinline__ double gps_ratquad(double variance, double alpha, double inv_alpha, double r2) {
+  return variance * gps_exp_nonpos(-alpha * log1p(0.5 * r2 * inv_alpha));
+}
+// Polynomial (kernels.py:550-551): (lin + offset)^degree for the integer degrees compile_prog lets through (1 .. 64)
+__device__ __forceinline__ double gps_polynomial(double lin, double offset, double degree) {
+  const double b = lin + offset;
+  double p = b;
+  for (int q = 1; q < (int)degree; ++q) p *= b;
+  return p;
+}
 
 // ---- tile pass --------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void kmat_tile_kernel(KmatArgs a, KProgDev P) {
@@ -278,7 +295,13 @@ __global__ __launch_bounds__(256) void kmat_tile_kernel(KmatArgs a, KProgDev P) 
 #pragma unroll
         for (int e = 0; e < 16; ++e) dot[e] = fma(fr[e >> 2], fc[e & 3], dot[e]);
       }
-      if (node.op == GPS_K_PERIODIC) {
+      if (node.op == GPS_K_LINEAR) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) v[e] = dot[e];
+      } else if (node.op == GPS_K_POLYNOMIAL) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) v[e] = gps_polynomial(dot[e], node.variance, node.c0);
+      } else if (node.op == GPS_K_PERIODIC) {
         const double half_d = 0.5 * (double)(node.nf / 2);
         const double l2 = node.c0 * node.c0;
 #pragma unroll
@@ -299,6 +322,8 @@ __global__ __launch_bounds__(256) void kmat_tile_kernel(KmatArgs a, KProgDev P) 
             val = node.variance * gps_exp_nonpos(-r2 / 2.0);
           } else if (node.op == GPS_K_SQDIST) {
             val = node.variance * r2;                                    // kernels.py:408-421 as a callable
+          } else if (node.op == GPS_K_RATQUAD) {
+            val = gps_ratquad(node.variance, node.c0, node.c1, r2);
           } else {
             const double r = gps_sqrt_pos(r2 + 1e-12);
             if (node.op == GPS_K_MATERN12) val = node.variance * gps_exp_nonpos(-r);
@@ -414,6 +439,8 @@ __global__ __launch_bounds__(256, 4) void kmat_single_kernel(KmatArgs a, KNodeDe
       double val;
       if (OP == GPS_K_RBF) {
         val = node.variance * gps_exp_nonpos(-r2 / 2.0);
+      } else if (OP == GPS_K_RATQUAD) {
+        val = gps_ratquad(node.variance, node.c0, node.c1, r2);
       } else {
         const double r = gps_sqrt_pos(r2 + 1e-12);
         if (OP == GPS_K_MATERN12) val = node.variance * gps_exp_nonpos(-r);
@@ -761,8 +788,12 @@ static int launch_mfma(gps_handle_t h, KmatArgs a, const KProgDev& P, i64 prow, 
 // p0 (p_i op_i)* with op in {ADD, MUL}
 static bool is_left_deep_chain(const KProgDev& P) {
   if (P.n_nodes < 3 || (P.n_nodes & 1) == 0) return false;
-  // (the distance ops are evaluated by the interpreter only: they are helpers, not kernels of a model)
-  auto prim = [](int op) { return op != GPS_K_ADD && op != GPS_K_MUL && op != GPS_K_SQDIST && op != GPS_K_EUCLID && op < GPS_K_NKN_LINROW; };
+  // (the distance ops are evaluated by the interpreter only: they are helpers, not kernels of a model; so are RatQuad, Linear
+  // and Polynomial: the two chain kernels do not know their formulas, and a chain with one of them goes to kmat_tile_kernel)
+  auto prim = [](int op) {
+    return op != GPS_K_ADD && op != GPS_K_MUL && op != GPS_K_SQDIST && op != GPS_K_EUCLID && op != GPS_K_RATQUAD && op != GPS_K_LINEAR &&
+           op != GPS_K_POLYNOMIAL && op < GPS_K_NKN_LINROW;
+  };
   if (!prim(P.nodes[0].op)) return false;
   for (int i = 1; i < P.n_nodes; i += 2) {
     if (!prim(P.nodes[i].op)) return false;
@@ -790,10 +821,13 @@ __device__ __forceinline__ double prim_value(const KNodeDev& node, double dot, d
     const double rs = (0.5 * (double)(node.nf / 2) - 0.5 * dot) / l2;
     return node.variance * gps_exp_nonpos(-0.5 * rs);
   }
+  if (node.op == GPS_K_LINEAR) return dot;
+  if (node.op == GPS_K_POLYNOMIAL) return gps_polynomial(dot, node.variance, node.c0);
   const double sq3 = 1.7320508075688772, sq5 = 2.23606797749979;
   double r2 = -2.0 * dot + (ni + nj);
   r2 = gps_clamp0(r2);
   if (node.op == GPS_K_RBF) return node.variance * gps_exp_nonpos(-r2 / 2.0);
+  if (node.op == GPS_K_RATQUAD) return gps_ratquad(node.variance, node.c0, node.c1, r2);
   const double r = gps_sqrt_pos(r2 + 1e-12);
   if (node.op == GPS_K_MATERN12) return node.variance * gps_exp_nonpos(-r);
   if (node.op == GPS_K_EXPONENTIAL) return node.variance * gps_exp_nonpos(-0.5 * r);
@@ -927,7 +961,8 @@ static int compile_prog(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes
         depth += 1;
         break;
       case GPS_K_RBF: case GPS_K_MATERN12: case GPS_K_MATERN32: case GPS_K_MATERN52:
-      case GPS_K_EXPONENTIAL: case GPS_K_PERIODIC: case GPS_K_SQDIST: case GPS_K_EUCLID: {
+      case GPS_K_EXPONENTIAL: case GPS_K_PERIODIC: case GPS_K_SQDIST: case GPS_K_EUCLID: case GPS_K_RATQUAD:
+      case GPS_K_LINEAR: case GPS_K_POLYNOMIAL: {
         if (nd.n_dims <= 0 || nd.n_dims > GPS_MAX_DIMS)
           return gps_fail(h, GPS_ERR_ARG, "kernel program: n_dims out of range");
         kd.f0 = (int)out.feats.size();
@@ -945,7 +980,27 @@ static int compile_prog(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes
           kd.nf = 2 * nd.n_dims;
           kd.c0 = nd.lengthscales[0];
           kd.c1 = -1.0 / (4.0 * kd.c0 * kd.c0);
+        } else if (nd.op == GPS_K_LINEAR || nd.op == GPS_K_POLYNOMIAL) {
+          if (nd.op == GPS_K_LINEAR && nd.variance != 1.0)
+            return gps_fail(h, GPS_ERR_ARG, "kernel program: Linear carries its variances per dim, the variance field must be 1");
+          if (nd.op == GPS_K_POLYNOMIAL) {
+            if (!(nd.variance > 0.0)) return gps_fail(h, GPS_ERR_ARG, "kernel program: Polynomial offset must be positive");
+            if (!(nd.period >= 1.0)) return gps_fail(h, GPS_ERR_ARG, "kernel program: Polynomial degree must be at least 1");
+            if (nd.period != floor(nd.period) || nd.period > 64.0)
+              return gps_fail(h, GPS_ERR_UNSUPPORTED, "kernel program: Polynomial degree must be an integer up to 64");
+            kd.c0 = nd.period;
+          }
+          for (int d = 0; d < nd.n_dims; ++d) {
+            if (!(nd.lengthscales[d] > 0.0))
+              return gps_fail(h, GPS_ERR_ARG, "kernel program: Linear / Polynomial variance must be positive");
+            out.feats.push_back({nd.active_dims[d], 3, sqrt(nd.lengthscales[d])});
+          }
+          kd.nf = nd.n_dims;
         } else {
+          if (nd.op == GPS_K_RATQUAD) {
+            if (!(nd.period > 0.0)) return gps_fail(h, GPS_ERR_ARG, "kernel program: RatQuad alpha must be positive");
+            kd.c0 = nd.period; kd.c1 = 1.0 / nd.period;
+          }
           for (int d = 0; d < nd.n_dims; ++d) {
             if (!(nd.lengthscales[d] > 0.0))
               return gps_fail(h, GPS_ERR_ARG, "kernel program: lengthscale must be positive");
@@ -1046,7 +1101,8 @@ static int launch_tiles(gps_handle_t h, const KCompiled& kc, KmatArgs& a, i64 pr
       case GPS_K_MATERN32: return launch_single<GPS_K_MATERN32>(h, a, nd, prow, pcol, tiles);
       case GPS_K_MATERN52: return launch_single<GPS_K_MATERN52>(h, a, nd, prow, pcol, tiles);
       case GPS_K_EXPONENTIAL: return launch_single<GPS_K_EXPONENTIAL>(h, a, nd, prow, pcol, tiles);
-      default: break;
+      case GPS_K_RATQUAD: return launch_single<GPS_K_RATQUAD>(h, a, nd, prow, pcol, tiles);
+      default: break;                              // (the distance ops: the interpreter below)
     }
   }
   int maxnf = 1;
@@ -1070,9 +1126,18 @@ static int launch_tiles(gps_handle_t h, const KCompiled& kc, KmatArgs& a, i64 pr
   return GPS_OK;
 }
 
+// Kdiag is one number for every point unless the program holds Linear or Polynomial (kernels.py:507-510, 553-554)
+bool gps_kdiag_is_const(const gps_kern_node_t* prog, int n_nodes) {
+  for (int i = 0; i < n_nodes; ++i)
+    if (prog[i].op == GPS_K_LINEAR || prog[i].op == GPS_K_POLYNOMIAL) return false;
+  return true;
+}
+
 int gps_launch_kdiag(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double* kdiag_const) {
-  // Kdiag of every primitive is its variance (kernels.py:428-429, 803-804, 327-328);
+  // Kdiag of every primitive but Linear / Polynomial is its variance (kernels.py:428-429, 803-804, 327-328);
   // Sum.Kdiag / Product.Kdiag fold them (kernels.py:1075-1076, 1083-1084).
+  if (!gps_kdiag_is_const(prog, n_nodes))
+    return gps_fail(h, GPS_ERR_UNSUPPORTED, "Kdiag is not constant for a kernel program with Linear / Polynomial: this path takes constant-Kdiag kernels only");
   bool nkn = false;
   for (int i = 0; i < n_nodes; ++i) if (prog[i].op >= GPS_K_NKN_LINROW) nkn = true;
   if (nkn) {
@@ -1139,6 +1204,113 @@ static int run_prep(gps_handle_t h, const KCompiled& kc, const double* dX, i64 n
                      dX, n, d_all, npad, (const PrepFeat*)tables.p,
                      nfeat, (const PrepNorm*)((char*)tables.p + fb), nnorm, feat.d(), npad);
   GPS_HIP(h, hipGetLastError());
+  return GPS_OK;
+}
+
+// ---- per-point Kdiag ----------------------------------------------------------------------------------------------------------
+// Kdiag(X)[i] of any program: one thread per point runs the program over the primitives' diagonals -- the variance
+// (kernels.py:428-429, 803-804, 327-328), sum_d v_d x_d^2 for Linear (:507-510: the squared norm of the point's feature
+// rows), its (. + offset)^degree for Polynomial (:553-554) -- through the Sum / Product folds (:1075-1076, 1083-1084) or the
+// network layers (NeuralKernelNetwork.Kdiag, neural_kernel_network.py:35-39).  Wg: the layers' weights [n_layers][16][17].
+__global__ __launch_bounds__(256) void kdiag_vec_kernel(const double* __restrict__ Ft, i64 ldf, i64 n, KProgDev P, NknNet net, int nkn,
+                                                        const double* __restrict__ Wg, double* __restrict__ out) {
+  const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  auto prim_diag = [&](const KNodeDev& node) -> double {
+    if (node.op != GPS_K_LINEAR && node.op != GPS_K_POLYNOMIAL) return node.variance;
+    double s = 0.0;
+    for (int f = 0; f < node.nf; ++f) { const double v = Ft[(i64)(node.f0 + f) * ldf + i]; s = fma(v, v, s); }
+    return node.op == GPS_K_LINEAR ? s : gps_polynomial(s, node.variance, node.c0);
+  };
+  if (!nkn) {
+    double st[GPS_MAX_STACK];
+#pragma unroll
+    for (int s = 0; s < GPS_MAX_STACK; ++s) st[s] = 0.0;
+    for (int nd = 0; nd < P.n_nodes; ++nd) {
+      const int op = P.nodes[nd].op;
+      if (op == GPS_K_ADD || op == GPS_K_MUL) {
+        st[0] = (op == GPS_K_ADD) ? (st[1] + st[0]) : (st[1] * st[0]);
+#pragma unroll
+        for (int s = 1; s < GPS_MAX_STACK - 1; ++s) st[s] = st[s + 1];
+      } else {
+        const double v = prim_diag(P.nodes[nd]);
+#pragma unroll
+        for (int s = GPS_MAX_STACK - 1; s > 0; --s) st[s] = st[s - 1];
+        st[0] = v;
+      }
+    }
+    out[i] = st[0];
+    return;
+  }
+  double vin[NKN_W], vout[NKN_W];
+#pragma unroll
+  for (int q = 0; q < NKN_W; ++q) vin[q] = 0.0;
+#pragma unroll
+  for (int p = 0; p < NKN_MAXP; ++p)
+    if (p < net.n_prims) vin[p] = prim_diag(P.nodes[p]);
+  for (int L = 0; L < net.n_layers; ++L) {
+    const NknLayer ly = net.layers[L];
+    const double* Wl = Wg + L * NKN_W * (NKN_W + 1);
+#pragma unroll
+    for (int o = 0; o < NKN_W; ++o) vout[o] = 0.0;
+    if (ly.type == 0) {
+#pragma unroll
+      for (int o = 0; o < NKN_W; ++o) {
+        double acc = Wl[o * (NKN_W + 1) + NKN_W];
+#pragma unroll
+        for (int j = 0; j < NKN_W; ++j) acc = fma(Wl[o * (NKN_W + 1) + j], vin[j], acc);
+        vout[o] = acc;
+      }
+    } else if (ly.type == 1) {
+      if (ly.step == 2) {
+#pragma unroll
+        for (int o = 0; o < NKN_W / 2; ++o) vout[o] = vin[2 * o] * vin[2 * o + 1];
+      } else if (ly.step == 3) {
+#pragma unroll
+        for (int o = 0; o < NKN_W / 3; ++o) vout[o] = vin[3 * o] * vin[3 * o + 1] * vin[3 * o + 2];
+      } else {
+#pragma unroll
+        for (int o = 0; o < NKN_W / 4; ++o) vout[o] = (vin[4 * o] * vin[4 * o + 1]) * (vin[4 * o + 2] * vin[4 * o + 3]);
+      }
+    } else {
+#pragma unroll
+      for (int o = 0; o < NKN_W; ++o) vout[o] = exp(vin[o]);
+    }
+#pragma unroll
+    for (int q = 0; q < NKN_W; ++q) vin[q] = vout[q];
+  }
+  out[i] = vin[0];
+}
+
+int gps_launch_kdiag_vec(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n, i64 d_all, double* d_out,
+                         double* sum_out) {
+  KCompiled kc;
+  int rc = compile_prog(h, prog, n_nodes, d_all, kc);
+  if (rc) return rc;
+  const i64 npad = (n + KT - 1) / KT * KT;
+  i64 ldf = npad;
+  rc = run_prep(h, kc, dX, n, d_all, npad, h->dFeat, h->dProg, &ldf);
+  if (rc) return rc;
+  if (kc.has_nkn) {
+    const size_t wbytes = kc.W.size() * 8;
+    GPS_HIP(h, h->dNkn.ensure(wbytes + 64));
+    GPS_HIP(h, h->ring.upload(h->dNkn.p, kc.W.data(), wbytes, h->stream));
+  } else {
+    memset(&kc.net, 0, sizeof(kc.net));
+  }
+  {
+    LaunchScope ls(h, KC_KMAT, (double)n * (2.0 * kc.feats.size() + 10.0), 8.0 * (double)n * (kc.feats.size() + 1.0));
+    hipLaunchKernelGGL(kdiag_vec_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const double*)h->dFeat.p, ldf, n,
+                       kc.prog, kc.net, kc.has_nkn ? 1 : 0, (const double*)h->dNkn.p, d_out);
+    GPS_HIP(h, hipGetLastError());
+  }
+  if (!sum_out) return GPS_OK;
+  std::vector<double> kd((size_t)n);
+  GPS_HIP(h, hipMemcpyAsync(kd.data(), d_out, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipStreamSynchronize(h->stream));
+  double s = 0.0;
+  for (i64 i = 0; i < n; ++i) s += kd[(size_t)i];
+  *sum_out = s;
   return GPS_OK;
 }
 

@@ -17,6 +17,7 @@ GPS_MAX_STACK = 4
 # enum gps_kern_op
 K_RBF, K_MATERN12, K_MATERN32, K_MATERN52, K_PERIODIC, K_WHITE, K_CONSTANT, K_EXPONENTIAL = 1, 2, 3, 4, 5, 6, 7, 8
 K_SQDIST, K_EUCLID = 9, 10
+K_RATQUAD, K_LINEAR, K_POLYNOMIAL = 11, 12, 13      # (below K_ADD: network programs find their primitives with op < K_ADD)
 K_ADD, K_MUL = 16, 17
 K_NKN_LINROW, K_NKN_PRODUCT, K_NKN_ACT = 32, 33, 34
 
@@ -312,10 +313,17 @@ def make_program(nodes):
     return arr
 
 
-def primitive_node(op, variance, dims=(), lengthscales=(), period=0.0):
+def primitive_node(op, variance, dims=(), lengthscales=(), period=0.0, alpha=None, degree=None):
+    """One primitive of a kernel program.  The fields are shared (include/gpflowslim_hip.h): RatQuad keeps its ``alpha`` and
+    Polynomial its ``degree`` where Periodic keeps the period; Linear / Polynomial pass their per-dim variances as
+    ``lengthscales``, Polynomial its offset as ``variance`` and Linear 1.0."""
     nd = KernNode()
     nd.op = op
     nd.variance = float(variance)
+    if alpha is not None:
+        period = alpha
+    if degree is not None:
+        period = degree
     nd.period = float(period)
     k = len(dims)
     if k > GPS_MAX_DIMS:

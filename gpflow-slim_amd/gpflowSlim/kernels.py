@@ -2,8 +2,8 @@
 
 API mirror of gpflowSlim/kernels.py for the kernels on the hot path: Kernel (active-dims
 slicing :217-253, ``+`` / ``*`` :277-281), Static/White/Constant/Bias :308-357, Stationary
-:360-429, RBF :432-439, Exponential :557-565, Matern12/32/52 :569-610, Periodic :769-819,
-Combination/Sum/Product :1000-1084.
+:360-429, RBF :432-439, RatQuad :447-471, Linear :474-515, Polynomial :518-554, Exponential :557-565,
+Matern12/32/52 :569-610, Periodic :769-819, Combination/Sum/Product :1000-1084.
 
 Differences from the reference, on purpose: values are eager numpy fp64 arrays (there is no
 TensorFlow graph); ``K`` compiles the kernel *tree* into one reverse-Polish program and
@@ -223,6 +223,114 @@ class Stationary(Kernel):
 class RBF(Stationary):
     """kernels.py:432-439"""
     _op = be.K_RBF
+
+
+class RatQuad(Stationary):
+    """kernels.py:447-471: variance * (1 + r2 / (2 alpha))^(-alpha)"""
+    _op = be.K_RATQUAD
+
+    def __init__(self, input_dim, alpha=1., variance=1.0, lengthscales=None,
+                 active_dims=None, ARD=False, min_ls=1e-6, name='kernel'):
+        super().__init__(input_dim=input_dim, variance=variance, lengthscales=lengthscales, active_dims=active_dims,
+                         ARD=ARD, min_ls=min_ls, name=name)
+        self._alpha = Parameter(alpha, transform=transforms.positive, name='alpha')
+        self._parameters = self._parameters + [self._alpha]
+
+    @property
+    def alpha(self):
+        return self._alpha.value
+
+    def _nodes(self, presliced, d_all):
+        node, = super()._nodes(presliced, d_all)
+        node.period = float(np.squeeze(self.alpha))         # (the field Periodic keeps its period in)
+        return [node]
+
+    def _grad_layout(self, d_all):
+        return super()._grad_layout(d_all) + [(self._alpha, None)]
+
+    def dimwise(self, dim):
+        k = super().dimwise(dim)
+        k._alpha.assign(self.alpha)
+        return k
+
+
+class Linear(Kernel):
+    """kernels.py:474-515: sum_d v_d x_d x'_d.  Kdiag depends on the point, so the device paths that assume a constant
+    Kdiag (SVGP, SGPR, FITC, the distributed ones) refuse this kernel; GPR and conditional take it."""
+    _op = be.K_LINEAR
+
+    def __init__(self, input_dim, variance=1.0, active_dims=None, ARD=False, name='kernel'):
+        super().__init__(input_dim, active_dims, name=name)
+        self.ARD = ARD
+        variance = np.ones(self.input_dim, dtype=settings.float_type) * variance if ARD else variance
+        self._variance = Parameter(variance, transform=transforms.positive, name='variance')
+        self._parameters = self._parameters + [self._variance]
+
+    @property
+    def variance(self):
+        return self._variance.value
+
+    def _dim_variances(self, presliced, d_all):
+        dims = self._dims(presliced, d_all)
+        v = np.atleast_1d(self.variance)
+        if v.size not in (1, len(dims)):
+            raise ValueError("variances do not match the active dims")
+        return dims, v
+
+    def _nodes(self, presliced, d_all):
+        dims, v = self._dim_variances(presliced, d_all)
+        return [be.primitive_node(be.K_LINEAR, 1.0, dims, v)]
+
+    def _lin_diag(self, X, presliced):
+        X = np.asarray(X, dtype=settings.float_type)
+        dims, v = self._dim_variances(presliced, X.shape[1])
+        return np.sum(np.square(X[:, dims]) * v, 1)
+
+    def Kdiag(self, X, presliced=False):
+        """kernels.py:507-510"""
+        return self._lin_diag(X, presliced)
+
+    def _grad_layout(self, d_all):
+        nd = len(self._dims(False, d_all))
+        ard = np.atleast_1d(self.variance).size > 1
+        return [(self._variance, d if ard else None) for d in range(nd)]
+
+    def dimwise(self, dim):
+        """kernels.py:512-515"""
+        v = np.atleast_1d(self.variance)
+        return Linear(input_dim=1, variance=float(v[dim]) if self.ARD else float(v[0]) ** (1.0 / self.input_dim),
+                      name='Linear_dimwise_%d' % dim)
+
+
+class Polynomial(Linear):
+    """kernels.py:518-554: (Linear + offset)^degree; the degree is fixed (not a Parameter) and, on the device, an integer in
+    1 .. 64.  Unlike the reference, which appends ``_variance`` to ``parameters`` a second time (kernels.py:544) and so
+    would count its gradient twice, every Parameter is listed once."""
+    _op = be.K_POLYNOMIAL
+
+    def __init__(self, input_dim, degree=3.0, variance=1.0, offset=1.0, active_dims=None, ARD=False, name='kernel'):
+        super().__init__(input_dim, variance, active_dims, ARD, name=name)
+        self.degree = degree
+        self._offset = Parameter(offset, transform=transforms.positive, name='offset')
+        self._parameters = self._parameters + [self._offset]
+
+    @property
+    def offset(self):
+        return self._offset.value
+
+    def _nodes(self, presliced, d_all):
+        dims, v = self._dim_variances(presliced, d_all)
+        return [be.primitive_node(be.K_POLYNOMIAL, np.squeeze(self.offset), dims, v, degree=self.degree)]
+
+    def Kdiag(self, X, presliced=False):
+        """kernels.py:553-554"""
+        return (self._lin_diag(X, presliced) + self.offset) ** self.degree
+
+    def _grad_layout(self, d_all):
+        return super()._grad_layout(d_all) + [(self._offset, None)]
+
+    def dimwise(self, dim):
+        raise NotImplementedError("Polynomial has no one-dimensional factors")
 
 
 class Exponential(Stationary):

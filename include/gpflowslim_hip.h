@@ -56,6 +56,18 @@ enum gps_kern_op {
   GPS_K_SQDIST   = 9,  /* Stationary.square_dist  kernels.py:408-421: variance * max(0, |a|^2 + |b|^2 - 2 a.b), a = x / l (the
                           callable form of the distance every stationary primitive is built on; not differentiable here) */
   GPS_K_EUCLID   = 10, /* Stationary.euclid_dist  kernels.py:424-426: variance * sqrt(square_dist + 1e-12)               */
+  /* The next three keep the layout of gps_kern_node_t and re-use its fields with these meanings:
+   *   op          variance        lengthscales[d]                        period
+   *   RATQUAD     variance        lengthscales                           alpha (> 0)
+   *   LINEAR      must be 1.0     per-dim variance v_d (ARD, or the      unused
+   *                               scalar repeated), > 0
+   *   POLYNOMIAL  offset (> 0)    per-dim variance v_d, > 0              degree: an integer in [1, 64], fixed (not trained)
+   * Kdiag of LINEAR / POLYNOMIAL depends on the point (sum_d v_d x_d^2, (. + offset)^degree): the entry points that need
+   * Kdiag and take these two are gps_gpr_predict, gps_gpr_lml, gps_gpr_lml_grad and gps_conditional; the sparse and distributed
+   * paths return GPS_ERR_UNSUPPORTED ("Kdiag is not constant") for them.                                                  */
+  GPS_K_RATQUAD  = 11, /* RatQuad.K    kernels.py:467-471: variance * (1 + 0.5 r2 / alpha)^(-alpha), r2 as in SQDIST    */
+  GPS_K_LINEAR   = 12, /* Linear.K     kernels.py:499-505: sum_d v_d x_d x'_d                                          */
+  GPS_K_POLYNOMIAL = 13, /* Polynomial.K kernels.py:550-551: (Linear + offset)^degree                                   */
   GPS_K_ADD      = 16, /* Sum.K     reduce(tf.add, ...)      :1073          */
   GPS_K_MUL      = 17, /* Product.K reduce(tf.multiply, ...) :1081          */
   /* Neural Kernel Network (neural_kernel_network/neural_kernel_network.py:41-47): a program that
@@ -71,9 +83,9 @@ typedef struct gps_kern_node {
   int32_t op;                           /* enum gps_kern_op                  */
   int32_t n_dims;                       /* active dims of a primitive        */
   int32_t active_dims[GPS_MAX_DIMS];    /* column indices into X (Kernel._slice, kernels.py:217-253) */
-  double  variance;                     /* constrained value                 */
-  double  period;                       /* Periodic only                     */
-  double  lengthscales[GPS_MAX_DIMS];   /* per active dim (ARD) or repeated  */
+  double  variance;                     /* constrained value (Polynomial: the offset; Linear: 1.0)           */
+  double  period;                       /* Periodic: period; RatQuad: alpha; Polynomial: degree              */
+  double  lengthscales[GPS_MAX_DIMS];   /* per active dim (ARD) or repeated; Linear / Polynomial: variances  */
 } gps_kern_node_t;
 
 typedef struct gps_handle_s* gps_handle_t;
@@ -132,7 +144,9 @@ int gps_gpr_lml(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes,
  * models/model.py:172-187 L-BFGS):   d LML/d theta = 1/2 tr((A A^T - r K_y^-1) dK_y/dtheta),
  * A = K_y^-1 resid.  grad_slots: for every primitive node of the program in order, [d/d variance] then
  * stationary kernels one entry per active dim (d/d lengthscale_d; an isotropic kernel sums them),
- * Periodic [d/d lengthscale, d/d period], White / Constant nothing more -- all w.r.t. the CONSTRAINED
+ * Periodic [d/d lengthscale, d/d period], White / Constant nothing more; RatQuad [d/d variance, d/d lengthscale_d per
+ * active dim, d/d alpha]; Linear [d/d v_d per active dim] (no variance slot; an isotropic kernel sums them);
+ * Polynomial [d/d v_d per active dim, d/d offset] -- all w.r.t. the CONSTRAINED
  * values; the caller applies the transform's chain rule.  grad_noise = d/d noise_var.
  * kinv_resid (optional) host [n, r] = A = d LML / d resid (chain rule for mean-function parameters).
  * Neural-Kernel-Network programs (GPS_K_NKN_*: neural_kernel_network_wrapper.py:90-173, whose Linear weights and biases the
