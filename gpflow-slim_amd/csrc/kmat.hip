@@ -60,9 +60,10 @@ struct KmatArgs {
 struct PrepTabPtr { const PrepFeat* f; const PrepNorm* n; };
 struct PrepTabVal { PrepFeat f[PREP_SMALL_F]; PrepNorm n[PREP_SMALL_N]; };
 
+// (one kernel over both table forms, as grad_prep_kernel<Tab> of grad_common.hpp)
 template <class Tab>
-__device__ __forceinline__ void kmat_prep_body(const double* __restrict__ X, i64 n, i64 d_all, i64 npts_pad, const Tab& tab, int nfeat,
-                                               int nnorm, double* __restrict__ Ft, i64 ldf) {
+__global__ __launch_bounds__(256) void kmat_prep_kernel(const double* __restrict__ X, i64 n, i64 d_all, i64 npts_pad, Tab tab, int nfeat,
+                                                        int nnorm, double* __restrict__ Ft, i64 ldf) {
   const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= npts_pad) return;
   if (i >= n) {
@@ -91,20 +92,6 @@ __device__ __forceinline__ void kmat_prep_body(const double* __restrict__ X, i64
     }
     Ft[(i64)(nfeat + q) * ldf + i] = s;
   }
-}
-__global__ __launch_bounds__(256) void kmat_prep_kernel(const double* __restrict__ X, i64 n,
-                                                        i64 d_all, i64 npts_pad,
-                                                        const PrepFeat* __restrict__ feats,
-                                                        int nfeat,
-                                                        const PrepNorm* __restrict__ norms,
-                                                        int nnorm, double* __restrict__ Ft,
-                                                        i64 ldf) {
-  const PrepTabPtr tab{feats, norms};
-  kmat_prep_body(X, n, d_all, npts_pad, tab, nfeat, nnorm, Ft, ldf);
-}
-__global__ __launch_bounds__(256) void kmat_prep_args_kernel(const double* __restrict__ X, i64 n, i64 d_all, i64 npts_pad, PrepTabVal tab,
-                                                             int nfeat, int nnorm, double* __restrict__ Ft, i64 ldf) {
-  kmat_prep_body(X, n, d_all, npts_pad, tab, nfeat, nnorm, Ft, ldf);
 }
 
 // ---- exp(x) for x <= 0 (every kernel-matrix formula of kernels.py:436-439, 560-610, 813-819 has a non-positive argument up
@@ -138,19 +125,8 @@ __device__ __forceinline__ ExpTab gps_exp_load() {
   for (int i = 0; i < 16; ++i) t.c[i] = gps_exp_tab[i];
   return t;
 }
-__device__ __forceinline__ double gps_exp_nonpos(double x, const ExpTab& t) {        // exp(x) for x <= 0, <= 1 ulp-class error
-#ifndef GPS_EXP_LDEXP
-  // k = round(x log2 e) by adding 1.5 * 2^52: the sum's low mantissa bits ARE the integer k (two's complement), and 2^k is
-  // applied by adding k to the exponent field of the polynomial's value -- no v_rndne_f64 / v_cvt_i32_f64 / v_ldexp_f64 (each
-  // a multi-cycle fp64 instruction; the kernel-matrix kernels are VALU-issue-bound).  Arguments below -708 (results below
-  // 2.2e-308, where exp() would go through the denormals) give 0.
-  const double magic = 6755399441055744.0;
-  const double kd = fma(fmax(x, -1100.0), t.c[13], magic);
-  const int ki = __double2loint(kd);
-  const double k = kd - magic;
-#else
-  const double k = rint(x * t.c[13]);
-#endif
+// The core both exponentials share: x = k ln2 + r and the polynomial's value p = exp(r)
+__device__ __forceinline__ double gps_exp_poly(double x, double k, const ExpTab& t) {
   double r = fma(-k, t.c[14], x);
   r = fma(-k, t.c[15], r);
   // Taylor to degree 13 on |r| <= ln2 / 2 (remainder 4e-18), Horner
@@ -159,16 +135,45 @@ __device__ __forceinline__ double gps_exp_nonpos(double x, const ExpTab& t) {   
   for (int i = 1; i <= 10; ++i) p = fma(p, r, t.c[i]);
   p = fma(p, r, 0.5);
   p = fma(p, r, 1.0);
-  p = fma(p, r, 1.0);
+  return fma(p, r, 1.0);
+}
+// k = round(x log2 e) by adding 1.5 * 2^52: the sum's low mantissa bits ARE the integer k (two's complement), and 2^k is
+// applied by adding k to the exponent field of the polynomial's value -- no v_rndne_f64 / v_cvt_i32_f64 / v_ldexp_f64 (each
+// a multi-cycle fp64 instruction; the kernel-matrix kernels are VALU-issue-bound).  Returns 2^ki exp(r), good for
+// ki >= -1021 (p in [0.70, 1.42]: the exponent field cannot wrap); what becomes of smaller ki (arguments below -708: results
+// below 2.2e-308, where exp() would go through the denormals) and of a NaN argument (clamped to -1100 here) is the callers' tail.
+__device__ __forceinline__ double gps_exp_scaled(double x, const ExpTab& t, int& ki) {
+  const double magic = 6755399441055744.0;
+  const double kd = fma(fmax(x, -1100.0), t.c[13], magic);
+  ki = __double2loint(kd);
+  const double p = gps_exp_poly(x, kd - magic, t);
+  return __hiloint2double(__double2hiint(p) + (ki << 20), __double2loint(p));
+}
+__device__ __forceinline__ double gps_exp_nonpos(double x, const ExpTab& t) {        // exp(x) for x <= 0, <= 1 ulp-class error
 #ifndef GPS_EXP_LDEXP
-  const int hi = __double2hiint(p) + (ki << 20);         // p in [0.70, 1.42]: the exponent field cannot wrap for k >= -1021
-  const double v = __hiloint2double(hi, __double2loint(p));
-  // (a NaN argument -- NaN in X or in a hyper-parameter -- is clamped to -1100 above: hand it through, as tf.exp and the
-  // small-N path's exp() do, instead of returning 0 and a finite kernel matrix)
+  int ki;
+  const double v = gps_exp_scaled(x, t, ki);
+  // (a NaN argument -- NaN in X or in a hyper-parameter: hand it through, as tf.exp and the small-N path's exp() do, instead
+  // of returning 0 and a finite kernel matrix)
   return ki < -1021 ? (x == x ? 0.0 : x) : v;
 #else
-  return ldexp(p, (int)k);                          // k >= -1075: gradual underflow to 0 like exp()
+  const double k = rint(x * t.c[13]);
+  return ldexp(gps_exp_poly(x, k, t), (int)k);      // k >= -1075: gradual underflow to 0 like exp()
 #endif
+}
+// The same for the epilogue of kmat_mfma_kernel, where every VALU instruction counts (round 5).  A NaN argument is handed
+// through by a compare and a select on the result (round 6: the round-5 form, one FMA x * 0 + result, also turned an
+// argument of -infinity -- a squared distance that overflowed -- into NaN where tf.exp and the other kernel-matrix kernels
+// give 0: tests/test_gpu_parity.py::test_overflowed_distances_give_zero_not_nan).
+__device__ __forceinline__ double gps_exp_nonpos_lean(double x, const ExpTab& t) {
+  int ki;
+  const double v = gps_exp_scaled(x, t, ki);
+  const double z = ki < -1021 ? 0.0 : v;
+  return x != x ? x : z;
+}
+__device__ __forceinline__ double gps_exp_nonpos(double x) {        // (kernels that call it a few times only)
+  const ExpTab t = gps_exp_load();
+  return gps_exp_nonpos(x, t);
 }
 // sqrt(x) for x in [1e-12, huge): v_rsq_f64 and one coupled Newton step + a final correction (the library sqrt adds range
 // scaling and special cases around the same core)
@@ -186,32 +191,6 @@ __device__ __forceinline__ double gps_sqrt_pos(double x) {
   return sqrt(x);
 #endif
 }
-// The same for the epilogue of kmat_mfma_kernel, where every VALU instruction counts (round 5).  A NaN argument is handed
-// through by a compare and a select on the result (round 6: the round-5 form, one FMA x * 0 + result, also turned an
-// argument of -infinity -- a squared distance that overflowed -- into NaN where tf.exp and the other kernel-matrix kernels
-// give 0: tests/test_gpu_parity.py::test_overflowed_distances_give_zero_not_nan).
-__device__ __forceinline__ double gps_exp_nonpos_lean(double x, const ExpTab& t) {
-  const double magic = 6755399441055744.0;
-  const double kd = fma(fmax(x, -1100.0), t.c[13], magic);
-  const int ki = __double2loint(kd);
-  const double k = kd - magic;
-  double r = fma(-k, t.c[14], x);
-  r = fma(-k, t.c[15], r);
-  double p = t.c[0];
-#pragma unroll
-  for (int i = 1; i <= 10; ++i) p = fma(p, r, t.c[i]);
-  p = fma(p, r, 0.5);
-  p = fma(p, r, 1.0);
-  p = fma(p, r, 1.0);
-  const int hi = __double2hiint(p) + (ki << 20);
-  const double v = __hiloint2double(hi, __double2loint(p));
-  const double z = ki < -1021 ? 0.0 : v;
-  return x != x ? x : z;
-}
-__device__ __forceinline__ double gps_exp_nonpos(double x) {        // (kernels that call it a few times only)
-  const ExpTab t = gps_exp_load();
-  return gps_exp_nonpos(x, t);
-}
 // RatQuad (kernels.py:470-471): variance (1 + 0.5 r2 (1 / alpha))^(-alpha), the power as exp(-alpha log1p(.)): the argument of
 // the exponential is <= 0 like every other one here, and its rounding error alpha log1p(.) u stays far below that of pow() only
 // where the value itself has underflowed.  inv_alpha = 1 / alpha from the host.
@@ -226,19 +205,142 @@ __device__ __forceinline__ double gps_polynomial(double lin, double offset, doub
   return p;
 }
 
-// ---- tile pass --------------------------------------------------------------------------------
+// ---- the pieces the tile kernels share ---------------------------------------------------------------------------------------
+// Expression grouping in the formulas is part of the result: the compiler contracts multiply-adds by expression shape, so
+// -r2 / 2.0 stays -r2 / 2.0 and (ni + nj) keeps its parentheses (grad_common.hpp says the same of the gradient's formulas).
+
+// A lower-triangle build skips the tiles above the diagonal, 128-granular: diagonal blocks stay full
+__device__ __forceinline__ bool kmat_upper_tile(const KmatArgs& a, int ti, int tj) {
+  return a.lower_only && ((a.col_off >> 6) + tj) >> 1 > ((a.row_off >> 6) + ti) >> 1;
+}
+
+// Dynamic LDS of the four slab-staging kernels: the norms of the tile's 64 rows and 64 columns, then the row and column
+// feature slabs of one primitive at a time, `rows` feature rows of `stride` doubles (KLS; KLM on the matrix pipe)
+struct KSlabs { double *nr, *nc, *Fr, *Fc; };
+__device__ __forceinline__ KSlabs kmat_slabs(char* smem, int rows, int stride) {
+  KSlabs s;
+  s.nr = reinterpret_cast<double*>(smem); s.nc = s.nr + KT; s.Fr = s.nc + KT; s.Fc = s.Fr + rows * stride;
+  return s;
+}
+static size_t kmat_slab_bytes(int rows, int stride) { return (size_t)(2 * KT + 2 * rows * stride) * sizeof(double); }
+
+// Stage one primitive's slabs and norm rows; the barriers are the callers'.  ZFILL: the rows up to the next multiple of 4,
+// which the matrix pipe multiplies too, are zeros.
+template <int STRIDE, bool ZFILL>
+__device__ __forceinline__ void kmat_stage(const KmatArgs& a, const KNodeDev& node, const KSlabs& s, i64 gi0, i64 gj0, int tid) {
+  const int rows = ZFILL ? ((node.nf + 3) & ~3) : node.nf;
+  for (int idx = tid; idx < rows * KT; idx += 256) {
+    const int f = idx >> 6, p = idx & 63;
+    const bool real = !ZFILL || f < node.nf;
+    s.Fr[f * STRIDE + p] = real ? a.Fr[(i64)(node.f0 + f) * a.ldfr + gi0 + p] : 0.0;
+    s.Fc[f * STRIDE + p] = real ? a.Fc[(i64)(node.f0 + f) * a.ldfc + gj0 + p] : 0.0;
+  }
+  if (node.norm_row >= 0 && tid < KT) {
+    s.nr[tid] = a.Fr[(i64)node.norm_row * a.ldfr + gi0 + tid];
+    s.nc[tid] = a.Fc[(i64)node.norm_row * a.ldfc + gj0 + tid];
+  }
+}
+
+// The 4 x 4 patch of dot products of a thread of the VALU kernels: rows r0 .. r0 + 3, columns c_lo, c_lo + 1, c_hi, c_hi + 1
+__device__ __forceinline__ void kmat_dots(const KSlabs& s, int nf, int r0, int c_lo, int c_hi, double (&dot)[16]) {
+#pragma unroll
+  for (int e = 0; e < 16; ++e) dot[e] = 0.0;
+  for (int f = 0; f < nf; ++f) {
+    const double2 r01 = *reinterpret_cast<const double2*>(s.Fr + f * KLS + r0), r23 = *reinterpret_cast<const double2*>(s.Fr + f * KLS + r0 + 2);
+    const double2 c01 = *reinterpret_cast<const double2*>(s.Fc + f * KLS + c_lo), c23 = *reinterpret_cast<const double2*>(s.Fc + f * KLS + c_hi);
+    const double fr[4] = {r01.x, r01.y, r23.x, r23.y}, fc[4] = {c01.x, c01.y, c23.x, c23.y};
+#pragma unroll
+    for (int e = 0; e < 16; ++e) dot[e] = fma(fr[e >> 2], fc[e & 3], dot[e]);
+  }
+}
+
+// The value of a primitive with features from its dot product and the two squared norms, for the four VALU users.
+// OP >= 0: that op at compile time (kmat_single_kernel); OP < 0: `op` at run time.  EXT: RatQuad, Linear, Polynomial and the
+// distance ops too -- the interpreter, the network kernel and kmat_single_kernel<RATQUAD>; kmat_chain_kernel is routed none of
+// them (is_left_deep_chain) and does not pay registers for their formulas.
+template <int OP, bool EXT>
+__device__ __forceinline__ double kmat_prim_value(const KNodeDev& node, int op, double dot, double ni, double nj) {
+  const int o = (OP >= 0) ? OP : op;
+  if (o == GPS_K_PERIODIC) {
+    // sum_d sin^2(pi (x - x')/p) / l^2 = (D - sum_d cos(a_d - b_d)) / (2 l^2): kernels.py:813-819 in cos / sin feature form
+    const double half_d = 0.5 * (double)(node.nf / 2);
+    const double l2 = node.c0 * node.c0;
+    const double rs = (half_d - 0.5 * dot) / l2;
+    return node.variance * gps_exp_nonpos(-0.5 * rs);
+  }
+  if (EXT && o == GPS_K_LINEAR) return dot;
+  if (EXT && o == GPS_K_POLYNOMIAL) return gps_polynomial(dot, node.variance, node.c0);
+  const double sq3 = 1.7320508075688772, sq5 = 2.23606797749979;
+  double r2 = -2.0 * dot + (ni + nj);                                          // kernels.py:409-421
+  r2 = gps_clamp0(r2);
+  if (o == GPS_K_RBF) return node.variance * gps_exp_nonpos(-r2 / 2.0);
+  if (EXT && o == GPS_K_SQDIST) return node.variance * r2;                     // kernels.py:408-421 as a callable
+  if (EXT && o == GPS_K_RATQUAD) return gps_ratquad(node.variance, node.c0, node.c1, r2);
+  const double r = gps_sqrt_pos(r2 + 1e-12);
+  if (o == GPS_K_MATERN12) return node.variance * gps_exp_nonpos(-r);
+  if (EXT && o == GPS_K_EUCLID) return node.variance * r;                      // kernels.py:424-426
+  if (o == GPS_K_EXPONENTIAL) return node.variance * gps_exp_nonpos(-0.5 * r);
+  if (o == GPS_K_MATERN32) return node.variance * (1.0 + sq3 * r) * gps_exp_nonpos(-sq3 * r);
+  return node.variance * (1.0 + sq5 * r + 5.0 / 3.0 * (r * r)) * gps_exp_nonpos(-sq5 * r);
+}
+
+// One node of a program on the 4 x 4 patch (rows 4 ty .., columns 4 tx ..) of the interpreter and the chain kernel: Constant
+// and White without features, every other primitive through its staged slabs
+template <bool EXT>
+__device__ __forceinline__ void kmat_patch_value(const KmatArgs& a, const KNodeDev& node, const KSlabs& s, i64 gi0, i64 gj0, int tid,
+                                                 double (&v)[16]) {
+  const int tx = tid & 15, ty = tid >> 4;
+  if (node.op == GPS_K_CONSTANT) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) v[e] = node.variance;
+  } else if (node.op == GPS_K_WHITE) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const i64 gi = a.row_off + gi0 + ty * 4 + (e >> 2), gj = a.col_off + gj0 + tx * 4 + (e & 3);
+      v[e] = (a.sym && gi == gj) ? node.variance : 0.0;
+    }
+  } else {
+    __syncthreads();
+    kmat_stage<KLS, false>(a, node, s, gi0, gj0, tid);
+    __syncthreads();
+    kmat_dots(s, node.nf, ty * 4, tx * 4, tx * 4 + 2, v);
+    const bool has_norm = node.norm_row >= 0;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const double ni = has_norm ? s.nr[ty * 4 + (e >> 2)] : 0.0, nj = has_norm ? s.nc[tx * 4 + (e & 3)] : 0.0;
+      v[e] = kmat_prim_value<-1, EXT>(node, node.op, v[e], ni, nj);
+    }
+  }
+}
+
+// From the computed value to the stored one: padding (zeros, or the identity), diag_add on the diagonal of a symmetric build
+__device__ __forceinline__ double kmat_finish(const KmatArgs& a, double val, i64 gi, i64 gj) {
+  if (gi >= a.n || gj >= a.m) return (a.identity_pad && gi == gj) ? 1.0 : 0.0;
+  return (a.sym && gi == gj) ? val + a.diag_add : val;
+}
+
+// ... and the store of that 4 x 4 patch
+__device__ __forceinline__ void kmat_store_patch(const KmatArgs& a, const double (&v)[16], i64 gi0, i64 gj0, int tid) {
+  const int tx = tid & 15, ty = tid >> 4;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const i64 li = gi0 + ty * 4 + q;
+    double o[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) o[c] = kmat_finish(a, v[q * 4 + c], a.row_off + li, a.col_off + gj0 + tx * 4 + c);
+    double* dst = a.K + li * a.ldk + gj0 + tx * 4;
+    *reinterpret_cast<double2*>(dst) = make_double2(o[0], o[1]);
+    *reinterpret_cast<double2*>(dst + 2) = make_double2(o[2], o[3]);
+  }
+}
+
+// ---- tile pass: the interpreter ------------------------------------------------------------------
 __global__ __launch_bounds__(256) void kmat_tile_kernel(KmatArgs a, KProgDev P) {
   const int ti = blockIdx.y, tj = blockIdx.x;
-  if (a.lower_only && ((a.col_off >> 6) + tj) >> 1 > ((a.row_off >> 6) + ti) >> 1) return;   // 128-granular: diagonal blocks stay full
-
+  if (kmat_upper_tile(a, ti, tj)) return;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  double* nr_s = reinterpret_cast<double*>(smem_raw);      // [KT]
-  double* nc_s = nr_s + KT;                                // [KT]
-  double* Fr_s = nc_s + KT;                                // [a.maxnf][KLS]
-  double* Fc_s = Fr_s + a.maxnf * KLS;                     // [a.maxnf][KLS]
-
+  const KSlabs lds = kmat_slabs(smem_raw, a.maxnf, KLS);
   const int tid = threadIdx.x;
-  const int tx = tid & 15, ty = tid >> 4;
   const i64 gi0 = (i64)ti * KT, gj0 = (i64)tj * KT;
 
   double st[GPS_MAX_STACK][16];
@@ -258,84 +360,8 @@ __global__ __launch_bounds__(256) void kmat_tile_kernel(KmatArgs a, KProgDev P) 
       }
       continue;
     }
-    // ---- primitive: value v[16] ----
     double v[16];
-    if (node.op == GPS_K_CONSTANT) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) v[e] = node.variance;
-    } else if (node.op == GPS_K_WHITE) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const i64 gi = a.row_off + gi0 + ty * 4 + (e >> 2), gj = a.col_off + gj0 + tx * 4 + (e & 3);
-        v[e] = (a.sym && gi == gj) ? node.variance : 0.0;
-      }
-    } else {
-      // stage this primitive's feature slabs
-      __syncthreads();
-      for (int idx = tid; idx < node.nf * KT; idx += 256) {
-        const int f = idx >> 6, p = idx & 63;
-        Fr_s[f * KLS + p] = a.Fr[(i64)(node.f0 + f) * a.ldfr + gi0 + p];
-        Fc_s[f * KLS + p] = a.Fc[(i64)(node.f0 + f) * a.ldfc + gj0 + p];
-      }
-      if (node.norm_row >= 0 && tid < KT) {
-        nr_s[tid] = a.Fr[(i64)node.norm_row * a.ldfr + gi0 + tid];
-        nc_s[tid] = a.Fc[(i64)node.norm_row * a.ldfc + gj0 + tid];
-      }
-      __syncthreads();
-      double dot[16];
-#pragma unroll
-      for (int e = 0; e < 16; ++e) dot[e] = 0.0;
-      for (int f = 0; f < node.nf; ++f) {
-        double fr[4], fc[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          fr[q] = Fr_s[f * KLS + ty * 4 + q];
-          fc[q] = Fc_s[f * KLS + tx * 4 + q];
-        }
-#pragma unroll
-        for (int e = 0; e < 16; ++e) dot[e] = fma(fr[e >> 2], fc[e & 3], dot[e]);
-      }
-      if (node.op == GPS_K_LINEAR) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) v[e] = dot[e];
-      } else if (node.op == GPS_K_POLYNOMIAL) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) v[e] = gps_polynomial(dot[e], node.variance, node.c0);
-      } else if (node.op == GPS_K_PERIODIC) {
-        const double half_d = 0.5 * (double)(node.nf / 2);
-        const double l2 = node.c0 * node.c0;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          // sum_d sin^2(pi (x - x')/p) / l^2 = (D - sum_d cos(a_d - b_d)) / (2 l^2)
-          const double rs = (half_d - 0.5 * dot[e]) / l2;
-          v[e] = node.variance * gps_exp_nonpos(-0.5 * rs);
-        }
-      } else {
-        const double sq3 = 1.7320508075688772, sq5 = 2.23606797749979;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const double ni = nr_s[ty * 4 + (e >> 2)], nj = nc_s[tx * 4 + (e & 3)];
-          double r2 = -2.0 * dot[e] + (ni + nj);
-          r2 = gps_clamp0(r2);
-          double val;
-          if (node.op == GPS_K_RBF) {
-            val = node.variance * gps_exp_nonpos(-r2 / 2.0);
-          } else if (node.op == GPS_K_SQDIST) {
-            val = node.variance * r2;                                    // kernels.py:408-421 as a callable
-          } else if (node.op == GPS_K_RATQUAD) {
-            val = gps_ratquad(node.variance, node.c0, node.c1, r2);
-          } else {
-            const double r = gps_sqrt_pos(r2 + 1e-12);
-            if (node.op == GPS_K_MATERN12) val = node.variance * gps_exp_nonpos(-r);
-            else if (node.op == GPS_K_EUCLID) val = node.variance * r;    // kernels.py:424-426
-            else if (node.op == GPS_K_EXPONENTIAL) val = node.variance * gps_exp_nonpos(-0.5 * r);
-            else if (node.op == GPS_K_MATERN32) val = node.variance * (1.0 + sq3 * r) * gps_exp_nonpos(-sq3 * r);
-            else val = node.variance * (1.0 + sq5 * r + 5.0 / 3.0 * (r * r)) * gps_exp_nonpos(-sq5 * r);
-          }
-          v[e] = val;
-        }
-      }
-    }
+    kmat_patch_value<true>(a, node, lds, gi0, gj0, tid, v);
     // push
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
@@ -344,25 +370,7 @@ __global__ __launch_bounds__(256) void kmat_tile_kernel(KmatArgs a, KProgDev P) 
       st[0][e] = v[e];
     }
   }
-
-  // ---- write the 4x4 patch ----
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const i64 li = gi0 + ty * 4 + q;
-    const i64 gi = a.row_off + li;
-    double o[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const i64 gj = a.col_off + gj0 + tx * 4 + c;
-      double val = st[0][q * 4 + c];
-      if (gi >= a.n || gj >= a.m) val = (a.identity_pad && gi == gj) ? 1.0 : 0.0;
-      else if (a.sym && gi == gj) val += a.diag_add;
-      o[c] = val;
-    }
-    double* dst = a.K + li * a.ldk + gj0 + tx * 4;
-    *reinterpret_cast<double2*>(dst) = make_double2(o[0], o[1]);
-    *reinterpret_cast<double2*>(dst + 2) = make_double2(o[2], o[3]);
-  }
+  kmat_store_patch(a, st[0], gi0, gj0, tid);
 }
 
 
@@ -388,92 +396,37 @@ __global__ __launch_bounds__(256, 4) void kmat_single_kernel(KmatArgs a, KNodeDe
     ti = (int)(2 * bi + (sub >> 1)); tj = (int)(2 * bj + (sub & 1));
   } else {
     ti = blockIdx.y; tj = blockIdx.x;
-    if (a.lower_only && ((a.col_off >> 6) + tj) >> 1 > ((a.row_off >> 6) + ti) >> 1) return;   // 128-granular: diagonal blocks stay full
+    if (kmat_upper_tile(a, ti, tj)) return;
   }
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  double* nr_s = reinterpret_cast<double*>(smem_raw);      // [KT]
-  double* nc_s = nr_s + KT;                                // [KT]
-  double* Fr_s = nc_s + KT;                                // [nf][KLS]
-  double* Fc_s = Fr_s + node.nf * KLS;                     // [nf][KLS]
+  const KSlabs lds = kmat_slabs(smem_raw, node.nf, KLS);
   const int tid = threadIdx.x;
   const int tx = tid & 15, ty = tid >> 4;
   const i64 gi0 = (i64)ti * KT, gj0 = (i64)tj * KT;
-  for (int idx = tid; idx < node.nf * KT; idx += 256) {
-    const int f = idx >> 6, p = idx & 63;
-    Fr_s[f * KLS + p] = a.Fr[(i64)(node.f0 + f) * a.ldfr + gi0 + p];
-    Fc_s[f * KLS + p] = a.Fc[(i64)(node.f0 + f) * a.ldfc + gj0 + p];
-  }
-  if (tid < KT) {
-    nr_s[tid] = a.Fr[(i64)node.norm_row * a.ldfr + gi0 + tid];
-    nc_s[tid] = a.Fc[(i64)node.norm_row * a.ldfc + gj0 + tid];
-  }
+  kmat_stage<KLS, false>(a, node, lds, gi0, gj0, tid);
   __syncthreads();
   // the thread's 4 x 4 patch: rows 4 ty .. 4 ty + 3, columns {2 tx, 2 tx + 1, 32 + 2 tx, 33 + 2 tx} -- the sixteen lanes of a
   // row then store 256 contiguous bytes per instruction (whole 128-byte lines; columns 4 tx .. 4 tx + 3 made every store
   // instruction write every other 16 bytes of a row: round 6)
   const int c_lo = 2 * tx, c_hi = 32 + 2 * tx;
   double dot[16];
-#pragma unroll
-  for (int e = 0; e < 16; ++e) dot[e] = 0.0;
-  for (int f = 0; f < node.nf; ++f) {
-    const double2 r01 = *reinterpret_cast<const double2*>(Fr_s + f * KLS + ty * 4), r23 = *reinterpret_cast<const double2*>(Fr_s + f * KLS + ty * 4 + 2);
-    const double2 c01 = *reinterpret_cast<const double2*>(Fc_s + f * KLS + c_lo), c23 = *reinterpret_cast<const double2*>(Fc_s + f * KLS + c_hi);
-    const double fr[4] = {r01.x, r01.y, r23.x, r23.y}, fc[4] = {c01.x, c01.y, c23.x, c23.y};
-#pragma unroll
-    for (int e = 0; e < 16; ++e) dot[e] = fma(fr[e >> 2], fc[e & 3], dot[e]);
-  }
-  const double2 n01 = *reinterpret_cast<const double2*>(nc_s + c_lo), n23 = *reinterpret_cast<const double2*>(nc_s + c_hi);
+  kmat_dots(lds, node.nf, ty * 4, c_lo, c_hi, dot);
+  const double2 n01 = *reinterpret_cast<const double2*>(lds.nc + c_lo), n23 = *reinterpret_cast<const double2*>(lds.nc + c_hi);
   const double ncol[4] = {n01.x, n01.y, n23.x, n23.y};
-  const double sq3 = 1.7320508075688772, sq5 = 2.23606797749979;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const i64 li = gi0 + ty * 4 + q;
-    const i64 gi = a.row_off + li;
-    const double ni = nr_s[ty * 4 + q];
+    const double ni = lds.nr[ty * 4 + q];
     double o[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const i64 gj = a.col_off + gj0 + (c < 2 ? c_lo + c : c_hi + c - 2);
-      double r2 = -2.0 * dot[q * 4 + c] + (ni + ncol[c]);        // kernels.py:409-421, same op order as the interpreter
-      r2 = gps_clamp0(r2);
-      double val;
-      if (OP == GPS_K_RBF) {
-        val = node.variance * gps_exp_nonpos(-r2 / 2.0);
-      } else if (OP == GPS_K_RATQUAD) {
-        val = gps_ratquad(node.variance, node.c0, node.c1, r2);
-      } else {
-        const double r = gps_sqrt_pos(r2 + 1e-12);
-        if (OP == GPS_K_MATERN12) val = node.variance * gps_exp_nonpos(-r);
-        else if (OP == GPS_K_EXPONENTIAL) val = node.variance * gps_exp_nonpos(-0.5 * r);
-        else if (OP == GPS_K_MATERN32) val = node.variance * (1.0 + sq3 * r) * gps_exp_nonpos(-sq3 * r);
-        else val = node.variance * (1.0 + sq5 * r + 5.0 / 3.0 * (r * r)) * gps_exp_nonpos(-sq5 * r);
-      }
-      if (gi >= a.n || gj >= a.m) val = (a.identity_pad && gi == gj) ? 1.0 : 0.0;
-      else if (a.sym && gi == gj) val += a.diag_add;
-      o[c] = val;
+      o[c] = kmat_finish(a, kmat_prim_value<OP, true>(node, OP, dot[q * 4 + c], ni, ncol[c]), a.row_off + li, gj);
     }
     double* dst = a.K + li * a.ldk + gj0;
     *reinterpret_cast<double2*>(dst + c_lo) = make_double2(o[0], o[1]);
     *reinterpret_cast<double2*>(dst + c_hi) = make_double2(o[2], o[3]);
   }
-}
-
-template <int OP>
-static int launch_single(gps_handle_t h, const KmatArgs& a, const KNodeDev& node, i64 prow, i64 pcol, double tiles) {
-  const size_t lds = (size_t)(2 * KT + 2 * node.nf * KLS) * sizeof(double);
-  int rcl = gps_dyn_lds(h, reinterpret_cast<const void*>(&kmat_single_kernel<OP>), (int)((2 * KT + 2 * KMAXF * KLS) * sizeof(double)));
-  if (rcl) return rcl;
-  LaunchScope ls(h, KC_KMAT, tiles * KT * KT * (2.0 * node.nf + 30.0), tiles * KT * KT * 8.0);
-  KmatArgs at = a;
-  at.tri_grid = (a.lower_only && a.row_off == 0 && a.col_off == 0 && prow == pcol && prow % 128 == 0 && prow / 128 < 40000) ? 1 : 0;
-  if (at.tri_grid) {
-    const i64 nb = prow / 128;
-    hipLaunchKernelGGL(kmat_single_kernel<OP>, dim3((unsigned)(2 * nb * (nb + 1))), dim3(256), lds, h->stream, at, node);
-  } else {
-    hipLaunchKernelGGL(kmat_single_kernel<OP>, dim3((unsigned)(pcol / KT), (unsigned)(prow / KT)), dim3(256), lds, h->stream, at, node);
-  }
-  GPS_HIP(h, hipGetLastError());
-  return GPS_OK;
 }
 
 // ---- left-deep chains: p0 (p_i op_i)*  -- Sum / Product of a few primitives (BASELINE config 4: Matern-5/2 + Periodic) --
@@ -485,14 +438,10 @@ static int launch_single(gps_handle_t h, const KmatArgs& a, const KNodeDev& node
 // order (older op newer) as kmat_tile_kernel.
 __global__ __launch_bounds__(256, 2) void kmat_chain_kernel(KmatArgs a, KProgDev P) {      // (2: no scratch; with 3 the kernel spilled 20 VGPRs -- it is the fall-back behind kmat_mfma_kernel)
   const int ti = blockIdx.y, tj = blockIdx.x;
-  if (a.lower_only && ((a.col_off >> 6) + tj) >> 1 > ((a.row_off >> 6) + ti) >> 1) return;
+  if (kmat_upper_tile(a, ti, tj)) return;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  double* nr_s = reinterpret_cast<double*>(smem_raw);      // [KT]
-  double* nc_s = nr_s + KT;                                // [KT]
-  double* Fr_s = nc_s + KT;                                // [a.maxnf][KLS]
-  double* Fc_s = Fr_s + a.maxnf * KLS;                     // [a.maxnf][KLS]
+  const KSlabs lds = kmat_slabs(smem_raw, a.maxnf, KLS);
   const int tid = threadIdx.x;
-  const int tx = tid & 15, ty = tid >> 4;
   const i64 gi0 = (i64)ti * KT, gj0 = (i64)tj * KT;
   double acc[16];
 #pragma unroll
@@ -501,87 +450,12 @@ __global__ __launch_bounds__(256, 2) void kmat_chain_kernel(KmatArgs a, KProgDev
     const KNodeDev node = P.nodes[nd];
     const int op = (nd == 0) ? -1 : P.nodes[nd + 1].op;
     double v[16];
-    if (node.op == GPS_K_CONSTANT) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) v[e] = node.variance;
-    } else if (node.op == GPS_K_WHITE) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const i64 gi = a.row_off + gi0 + ty * 4 + (e >> 2), gj = a.col_off + gj0 + tx * 4 + (e & 3);
-        v[e] = (a.sym && gi == gj) ? node.variance : 0.0;
-      }
-    } else {
-      __syncthreads();
-      for (int idx = tid; idx < node.nf * KT; idx += 256) {
-        const int f = idx >> 6, p = idx & 63;
-        Fr_s[f * KLS + p] = a.Fr[(i64)(node.f0 + f) * a.ldfr + gi0 + p];
-        Fc_s[f * KLS + p] = a.Fc[(i64)(node.f0 + f) * a.ldfc + gj0 + p];
-      }
-      if (node.norm_row >= 0 && tid < KT) {
-        nr_s[tid] = a.Fr[(i64)node.norm_row * a.ldfr + gi0 + tid];
-        nc_s[tid] = a.Fc[(i64)node.norm_row * a.ldfc + gj0 + tid];
-      }
-      __syncthreads();
-#pragma unroll
-      for (int e = 0; e < 16; ++e) v[e] = 0.0;               // the dot products
-      for (int f = 0; f < node.nf; ++f) {
-        const double2 r01 = *reinterpret_cast<const double2*>(Fr_s + f * KLS + ty * 4), r23 = *reinterpret_cast<const double2*>(Fr_s + f * KLS + ty * 4 + 2);
-        const double2 c01 = *reinterpret_cast<const double2*>(Fc_s + f * KLS + tx * 4), c23 = *reinterpret_cast<const double2*>(Fc_s + f * KLS + tx * 4 + 2);
-        const double fr[4] = {r01.x, r01.y, r23.x, r23.y}, fc[4] = {c01.x, c01.y, c23.x, c23.y};
-#pragma unroll
-        for (int e = 0; e < 16; ++e) v[e] = fma(fr[e >> 2], fc[e & 3], v[e]);
-      }
-      if (node.op == GPS_K_PERIODIC) {
-        const double half_d = 0.5 * (double)(node.nf / 2);
-        const double l2 = node.c0 * node.c0;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const double rs = (half_d - 0.5 * v[e]) / l2;        // kernels.py:605-610 in cos / sin feature form
-          v[e] = node.variance * gps_exp_nonpos(-0.5 * rs);
-        }
-      } else {
-        const double sq3 = 1.7320508075688772, sq5 = 2.23606797749979;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const double ni = nr_s[ty * 4 + (e >> 2)], nj = nc_s[tx * 4 + (e & 3)];
-          double r2 = -2.0 * v[e] + (ni + nj);
-          r2 = gps_clamp0(r2);
-          double val;
-          if (node.op == GPS_K_RBF) {
-            val = node.variance * gps_exp_nonpos(-r2 / 2.0);
-          } else {
-            const double r = gps_sqrt_pos(r2 + 1e-12);
-            if (node.op == GPS_K_MATERN12) val = node.variance * gps_exp_nonpos(-r);
-            else if (node.op == GPS_K_EXPONENTIAL) val = node.variance * gps_exp_nonpos(-0.5 * r);
-            else if (node.op == GPS_K_MATERN32) val = node.variance * (1.0 + sq3 * r) * gps_exp_nonpos(-sq3 * r);
-            else val = node.variance * (1.0 + sq5 * r + 5.0 / 3.0 * (r * r)) * gps_exp_nonpos(-sq5 * r);
-          }
-          v[e] = val;
-        }
-      }
-    }
+    kmat_patch_value<false>(a, node, lds, gi0, gj0, tid, v);
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = (op < 0) ? v[e] : ((op == GPS_K_ADD) ? (acc[e] + v[e]) : (acc[e] * v[e]));
   }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const i64 li = gi0 + ty * 4 + q;
-    const i64 gi = a.row_off + li;
-    double o[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const i64 gj = a.col_off + gj0 + tx * 4 + c;
-      double val = acc[q * 4 + c];
-      if (gi >= a.n || gj >= a.m) val = (a.identity_pad && gi == gj) ? 1.0 : 0.0;
-      else if (a.sym && gi == gj) val += a.diag_add;
-      o[c] = val;
-    }
-    double* dst = a.K + li * a.ldk + gj0 + tx * 4;
-    *reinterpret_cast<double2*>(dst) = make_double2(o[0], o[1]);
-    *reinterpret_cast<double2*>(dst + 2) = make_double2(o[2], o[3]);
-  }
+  kmat_store_patch(a, acc, gi0, gj0, tid);
 }
-
 
 // ---- the dot products on the matrix pipe ------------------------------------------------------------------------------
 // kernels.py:408-421 is r2 = |a|^2 + |b|^2 - 2 a.b with a.b a [64 x F] x [F x 64] product per tile -- a dense contraction, and
@@ -597,6 +471,8 @@ __global__ __launch_bounds__(256, 2) void kmat_chain_kernel(KmatArgs a, KProgDev
 #define KLM 80
 typedef double v4d_k __attribute__((ext_vector_type(4)));
 
+// The primitive's value for the matrix-pipe kernel.  Separate from kmat_prim_value on purpose: the value comes as two factors
+// (below), through the lean exponential, and Periodic through the host-folded node.c1 instead of a division -- other roundings.
 // (no diagonal test per entry: the accumulators of the diagonal entries of a diagonal tile are patched before the epilogue
 // to the dot product that makes r2 -- or the Periodic argument -- exactly 0; see the kernel)
 // The value as TWO factors, pre (variance x polynomial) and e (the exponential): the fold into the running result is then an
@@ -636,12 +512,9 @@ __device__ __forceinline__ void kmat_prim_from_dot(const KNodeDev& node, int op,
 template <int OP>
 __global__ __launch_bounds__(256, 3) void kmat_mfma_kernel(KmatArgs a, KProgDev P) {
   const int ti = blockIdx.y, tj = blockIdx.x;
-  if (a.lower_only && ((a.col_off >> 6) + tj) >> 1 > ((a.row_off >> 6) + ti) >> 1) return;
+  if (kmat_upper_tile(a, ti, tj)) return;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  double* nr_s = reinterpret_cast<double*>(smem_raw);      // [KT]
-  double* nc_s = nr_s + KT;                                // [KT]
-  double* Fr_s = nc_s + KT;                                // [maxnf4][KLM]
-  double* Fc_s = Fr_s + a.maxnf * KLM;                     // [maxnf4][KLM]   (a.maxnf: already a multiple of 4 here)
+  const KSlabs lds = kmat_slabs(smem_raw, a.maxnf, KLM);   // (a.maxnf: already a multiple of 4 here)
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int l15 = lane & 15, kq = lane >> 4;
   const int pi = 4 * (l15 & 3) + (l15 >> 2);
@@ -673,22 +546,13 @@ __global__ __launch_bounds__(256, 3) void kmat_mfma_kernel(KmatArgs a, KProgDev 
     } else {
       const int nf4 = (node.nf + 3) & ~3;
       if (nd > 0) __syncthreads();
-      for (int idx = tid; idx < nf4 * KT; idx += 256) {
-        const int f = idx >> 6, p = idx & 63;
-        const bool real = f < node.nf;
-        Fr_s[f * KLM + p] = real ? a.Fr[(i64)(node.f0 + f) * a.ldfr + gi0 + p] : 0.0;
-        Fc_s[f * KLM + p] = real ? a.Fc[(i64)(node.f0 + f) * a.ldfc + gj0 + p] : 0.0;
-      }
-      if (node.norm_row >= 0 && tid < KT) {
-        nr_s[tid] = a.Fr[(i64)node.norm_row * a.ldfr + gi0 + tid];
-        nc_s[tid] = a.Fc[(i64)node.norm_row * a.ldfc + gj0 + tid];
-      }
+      kmat_stage<KLM, true>(a, node, lds, gi0, gj0, tid);
       __syncthreads();
       v4d_k acc[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[j] = (v4d_k){0.0, 0.0, 0.0, 0.0};
-      const double* rp = Fr_s + kq * KLM + row;            // B operand: the wave's 16 rows
-      const double* cp = Fc_s + kq * KLM + pi;             // A operand: 16 columns of block j, permuted
+      const double* rp = lds.Fr + kq * KLM + row;            // B operand: the wave's 16 rows
+      const double* cp = lds.Fc + kq * KLM + pi;             // A operand: 16 columns of block j, permuted
       for (int k0 = 0; k0 < nf4; k0 += 4) {
         const double bv = rp[k0 * KLM];
         const double a0 = cp[k0 * KLM], a1 = cp[k0 * KLM + 16], a2 = cp[k0 * KLM + 32], a3 = cp[k0 * KLM + 48];
@@ -698,7 +562,7 @@ __global__ __launch_bounds__(256, 3) void kmat_mfma_kernel(KmatArgs a, KProgDev 
         acc[3] = __builtin_amdgcn_mfma_f64_16x16x4f64(a3, bv, acc[3], 0, 0, 0);
       }
       const bool has_norm = node.norm_row >= 0;
-      const double ni = has_norm ? nr_s[row] : 0.0;
+      const double ni = has_norm ? lds.nr[row] : 0.0;
       if (diag_tile) {
         // the exact diagonal (x_i == x_j: r2 = 0, Periodic argument 0 -- NaN / infinite coordinates stay NaN).  Stationary:
         // dot = (n_i + n_i) / 2 makes -2 dot + (n_i + n_j) exactly 0; Periodic: dot = D.  Here, once per node of a diagonal
@@ -716,8 +580,8 @@ __global__ __launch_bounds__(256, 3) void kmat_mfma_kernel(KmatArgs a, KProgDev 
       _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                           \
         double ns[4] = {0.0, 0.0, 0.0, 0.0};                                                                    \
         if (has_norm) {                                                                                         \
-          const double2 n01 = *reinterpret_cast<const double2*>(nc_s + 16 * j + 4 * kq);                        \
-          const double2 n23 = *reinterpret_cast<const double2*>(nc_s + 16 * j + 4 * kq + 2);                    \
+          const double2 n01 = *reinterpret_cast<const double2*>(lds.nc + 16 * j + 4 * kq);                        \
+          const double2 n23 = *reinterpret_cast<const double2*>(lds.nc + 16 * j + 4 * kq + 2);                    \
           ns[0] = ni + n01.x; ns[1] = ni + n01.y; ns[2] = ni + n23.x; ns[3] = ni + n23.y;                       \
         }                                                                                                       \
         _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                         \
@@ -759,30 +623,10 @@ __global__ __launch_bounds__(256, 3) void kmat_mfma_kernel(KmatArgs a, KProgDev 
   for (int j = 0; j < 4; ++j) {
     double o[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const i64 gj = a.col_off + gj0 + 16 * j + 4 * kq + r;
-      double val = run[j * 4 + r];
-      if (gi >= a.n || gj >= a.m) val = (a.identity_pad && gi == gj) ? 1.0 : 0.0;
-      else if (a.sym && gi == gj) val += a.diag_add;
-      o[r] = val;
-    }
+    for (int r = 0; r < 4; ++r) o[r] = kmat_finish(a, run[j * 4 + r], gi, a.col_off + gj0 + 16 * j + 4 * kq + r);
     *reinterpret_cast<double2*>(dst + 16 * j) = make_double2(o[0], o[1]);
     *reinterpret_cast<double2*>(dst + 16 * j + 2) = make_double2(o[2], o[3]);
   }
-}
-
-template <int OP>
-static int launch_mfma(gps_handle_t h, KmatArgs a, const KProgDev& P, i64 prow, i64 pcol, double tiles, int nfeat_total) {
-  int maxnf = 4;
-  for (int i = 0; i < P.n_nodes; ++i) if (((P.nodes[i].nf + 3) & ~3) > maxnf) maxnf = (P.nodes[i].nf + 3) & ~3;
-  a.maxnf = maxnf;
-  const size_t lds = (size_t)(2 * KT + 2 * maxnf * KLM) * sizeof(double);
-  int rcl = gps_dyn_lds(h, reinterpret_cast<const void*>(&kmat_mfma_kernel<OP>), (int)((2 * KT + 2 * KMAXF * KLM) * sizeof(double)));
-  if (rcl) return rcl;
-  LaunchScope ls(h, KC_KMAT, tiles * KT * KT * (2.0 * nfeat_total + 30.0 * ((P.n_nodes + 1) / 2)), tiles * KT * KT * 8.0);
-  hipLaunchKernelGGL(kmat_mfma_kernel<OP>, dim3((unsigned)(pcol / KT), (unsigned)(prow / KT)), dim3(256), lds, h->stream, a, P);
-  GPS_HIP(h, hipGetLastError());
-  return GPS_OK;
 }
 
 // p0 (p_i op_i)* with op in {ADD, MUL}
@@ -815,30 +659,47 @@ static bool is_left_deep_chain(const KProgDev& P) {
 struct NknLayer { int type; int in_dim; int out_dim; int step; int act; int w_off; };   // type 0 linear, 1 product, 2 act
 struct NknNet { int n_layers; int n_prims; int ftot; int nnorm; NknLayer layers[NKN_MAXL]; };
 
-__device__ __forceinline__ double prim_value(const KNodeDev& node, double dot, double ni, double nj) {
-  if (node.op == GPS_K_PERIODIC) {
-    const double l2 = node.c0 * node.c0;
-    const double rs = (0.5 * (double)(node.nf / 2) - 0.5 * dot) / l2;
-    return node.variance * gps_exp_nonpos(-0.5 * rs);
+// The layers over one entry's primitive values vin[] (neural_kernel_network_wrapper.py:90-173); W: [n_layers][NKN_W][NKN_W + 1],
+// the last column the bias, in LDS (nkn_tile_kernel) or global memory (kdiag_vec_kernel).  The network's output is vin[0].
+__device__ __forceinline__ void nkn_forward(const NknNet& net, const double* W, double (&vin)[NKN_W]) {
+  double vout[NKN_W];
+  for (int L = 0; L < net.n_layers; ++L) {
+    const NknLayer ly = net.layers[L];
+    if (ly.type == 0) {
+      const double* Wl = W + L * NKN_W * (NKN_W + 1);
+#pragma unroll
+      for (int o = 0; o < NKN_W; ++o) {
+        double acc = Wl[o * (NKN_W + 1) + NKN_W];
+#pragma unroll
+        for (int j = 0; j < NKN_W; ++j) acc = fma(Wl[o * (NKN_W + 1) + j], vin[j], acc);
+        vout[o] = acc;
+      }
+    } else if (ly.type == 1) {
+#pragma unroll
+      for (int o = 0; o < NKN_W; ++o) vout[o] = 0.0;
+      if (ly.step == 2) {
+#pragma unroll
+        for (int o = 0; o < NKN_W / 2; ++o) vout[o] = vin[2 * o] * vin[2 * o + 1];
+      } else if (ly.step == 3) {
+#pragma unroll
+        for (int o = 0; o < NKN_W / 3; ++o) vout[o] = vin[3 * o] * vin[3 * o + 1] * vin[3 * o + 2];
+      } else {
+#pragma unroll
+        for (int o = 0; o < NKN_W / 4; ++o) vout[o] = (vin[4 * o] * vin[4 * o + 1]) * (vin[4 * o + 2] * vin[4 * o + 3]);
+      }
+    } else {
+#pragma unroll
+      for (int o = 0; o < NKN_W; ++o) vout[o] = exp(vin[o]);
+    }
+#pragma unroll
+    for (int q = 0; q < NKN_W; ++q) vin[q] = vout[q];
   }
-  if (node.op == GPS_K_LINEAR) return dot;
-  if (node.op == GPS_K_POLYNOMIAL) return gps_polynomial(dot, node.variance, node.c0);
-  const double sq3 = 1.7320508075688772, sq5 = 2.23606797749979;
-  double r2 = -2.0 * dot + (ni + nj);
-  r2 = gps_clamp0(r2);
-  if (node.op == GPS_K_RBF) return node.variance * gps_exp_nonpos(-r2 / 2.0);
-  if (node.op == GPS_K_RATQUAD) return gps_ratquad(node.variance, node.c0, node.c1, r2);
-  const double r = gps_sqrt_pos(r2 + 1e-12);
-  if (node.op == GPS_K_MATERN12) return node.variance * gps_exp_nonpos(-r);
-  if (node.op == GPS_K_EXPONENTIAL) return node.variance * gps_exp_nonpos(-0.5 * r);
-  if (node.op == GPS_K_MATERN32) return node.variance * (1.0 + sq3 * r) * gps_exp_nonpos(-sq3 * r);
-  return node.variance * (1.0 + sq5 * r + 5.0 / 3.0 * (r * r)) * gps_exp_nonpos(-sq5 * r);
 }
 
 __global__ __launch_bounds__(256) void nkn_tile_kernel(KmatArgs a, KProgDev P, NknNet net,
                                                        const double* __restrict__ Wg) {
   const int ti = blockIdx.y, tj = blockIdx.x;
-  if (a.lower_only && ((a.col_off >> 6) + tj) >> 1 > ((a.row_off >> 6) + ti) >> 1) return;
+  if (kmat_upper_tile(a, ti, tj)) return;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const int rows_f = net.ftot + net.nnorm;                 // feature rows incl. the norm rows
   double* Fr_s = reinterpret_cast<double*>(smem_raw);      // [rows_f][64]
@@ -858,7 +719,7 @@ __global__ __launch_bounds__(256) void nkn_tile_kernel(KmatArgs a, KProgDev P, N
   for (int e = 0; e < 16; ++e) {
     const int li = ty * 4 + (e >> 2), lj = tx * 4 + (e & 3);
     const i64 gi = a.row_off + gi0 + li, gj = a.col_off + gj0 + lj;
-    double vin[NKN_W], vout[NKN_W];
+    double vin[NKN_W];
 #pragma unroll
     for (int q = 0; q < NKN_W; ++q) vin[q] = 0.0;
     // primitives (program order = input order of the first layer)
@@ -874,46 +735,13 @@ __global__ __launch_bounds__(256) void nkn_tile_kernel(KmatArgs a, KProgDev P, N
           for (int f = 0; f < node.nf; ++f) dot = fma(Fr_s[(node.f0 + f) * KT + li], Fc_s[(node.f0 + f) * KT + lj], dot);
           double ni = 0.0, nj = 0.0;
           if (node.norm_row >= 0) { ni = Fr_s[node.norm_row * KT + li]; nj = Fc_s[node.norm_row * KT + lj]; }
-          val = prim_value(node, dot, ni, nj);
+          val = kmat_prim_value<-1, true>(node, node.op, dot, ni, nj);
         }
         vin[p] = val;
       }
     }
-    for (int L = 0; L < net.n_layers; ++L) {
-      const NknLayer ly = net.layers[L];
-      if (ly.type == 0) {
-        const double* Wl = W_s + L * NKN_W * (NKN_W + 1);
-#pragma unroll
-        for (int o = 0; o < NKN_W; ++o) {
-          double acc = Wl[o * (NKN_W + 1) + NKN_W];
-#pragma unroll
-          for (int j = 0; j < NKN_W; ++j) acc = fma(Wl[o * (NKN_W + 1) + j], vin[j], acc);
-          vout[o] = acc;
-        }
-      } else if (ly.type == 1) {
-#pragma unroll
-        for (int o = 0; o < NKN_W; ++o) vout[o] = 0.0;
-        if (ly.step == 2) {
-#pragma unroll
-          for (int o = 0; o < NKN_W / 2; ++o) vout[o] = vin[2 * o] * vin[2 * o + 1];
-        } else if (ly.step == 3) {
-#pragma unroll
-          for (int o = 0; o < NKN_W / 3; ++o) vout[o] = vin[3 * o] * vin[3 * o + 1] * vin[3 * o + 2];
-        } else {
-#pragma unroll
-          for (int o = 0; o < NKN_W / 4; ++o) vout[o] = (vin[4 * o] * vin[4 * o + 1]) * (vin[4 * o + 2] * vin[4 * o + 3]);
-        }
-      } else {
-#pragma unroll
-        for (int o = 0; o < NKN_W; ++o) vout[o] = exp(vin[o]);
-      }
-#pragma unroll
-      for (int q = 0; q < NKN_W; ++q) vin[q] = vout[q];
-    }
-    double val = vin[0];
-    if (gi >= a.n || gj >= a.m) val = (a.identity_pad && gi == gj) ? 1.0 : 0.0;
-    else if (a.sym && gi == gj) val += a.diag_add;
-    a.K[(gi0 + li) * a.ldk + gj0 + lj] = val;
+    nkn_forward(net, W_s, vin);
+    a.K[(gi0 + li) * a.ldk + gj0 + lj] = kmat_finish(a, vin[0], gi, gj);
   }
 }
 
@@ -1060,70 +888,101 @@ static int compile_prog(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes
   return GPS_OK;
 }
 
+// ---- launches -----------------------------------------------------------------------------------
+static dim3 kmat_grid(i64 prow, i64 pcol) { return dim3((unsigned)(pcol / KT), (unsigned)(prow / KT)); }
+
+// What the four kernels over (KmatArgs, program) share: dynamic LDS for `rows` feature rows of `stride` doubles (opted in once
+// for the largest primitive), the accounting and the launch
+template <class Prog>
+static int launch_program(gps_handle_t h, void (*kern)(KmatArgs, Prog), dim3 grid, const KmatArgs& a, const Prog& prog, int rows, int stride,
+                          double flops_per_entry, double tiles) {
+  int rc = gps_dyn_lds(h, reinterpret_cast<const void*>(kern), (int)kmat_slab_bytes(KMAXF, stride));
+  if (rc) return rc;
+  LaunchScope ls(h, KC_KMAT, tiles * KT * KT * flops_per_entry, tiles * KT * KT * 8.0);
+  hipLaunchKernelGGL(kern, grid, dim3(256), kmat_slab_bytes(rows, stride), h->stream, a, prog);
+  GPS_HIP(h, hipGetLastError());
+  return GPS_OK;
+}
+
+template <int OP>
+static int launch_single(gps_handle_t h, const KmatArgs& a, const KNodeDev& node, i64 prow, i64 pcol, double tiles) {
+  KmatArgs at = a;
+  at.tri_grid = (a.lower_only && a.row_off == 0 && a.col_off == 0 && prow == pcol && prow % 128 == 0 && prow / 128 < 40000) ? 1 : 0;
+  const i64 nb = prow / 128;
+  return launch_program(h, &kmat_single_kernel<OP>, at.tri_grid ? dim3((unsigned)(2 * nb * (nb + 1))) : kmat_grid(prow, pcol), at, node,
+                        node.nf, KLS, 2.0 * node.nf + 30.0, tiles);
+}
+
+template <int OP>
+static int launch_mfma(gps_handle_t h, KmatArgs a, const KProgDev& P, i64 prow, i64 pcol, double tiles, int nfeat_total) {
+  int maxnf = 4;
+  for (int i = 0; i < P.n_nodes; ++i) if (((P.nodes[i].nf + 3) & ~3) > maxnf) maxnf = (P.nodes[i].nf + 3) & ~3;
+  a.maxnf = maxnf;
+  return launch_program(h, &kmat_mfma_kernel<OP>, kmat_grid(prow, pcol), a, P, maxnf, KLM, 2.0 * nfeat_total + 30.0 * ((P.n_nodes + 1) / 2), tiles);
+}
+
+// The op of a one-primitive stationary program as a compile-time constant: *rc = f(std::integral_constant<int, op>()).  False,
+// and f not called, for every other op (the distance ops: the interpreter).  RATQUAD: RatQuad too, which of the two users
+// kmat_single_kernel alone knows.
+template <bool RATQUAD, class F>
+static bool with_stationary_op(int op, int* rc, F&& f) {
+  switch (op) {
+    case GPS_K_RBF: *rc = f(std::integral_constant<int, GPS_K_RBF>()); return true;
+    case GPS_K_MATERN12: *rc = f(std::integral_constant<int, GPS_K_MATERN12>()); return true;
+    case GPS_K_MATERN32: *rc = f(std::integral_constant<int, GPS_K_MATERN32>()); return true;
+    case GPS_K_MATERN52: *rc = f(std::integral_constant<int, GPS_K_MATERN52>()); return true;
+    case GPS_K_EXPONENTIAL: *rc = f(std::integral_constant<int, GPS_K_EXPONENTIAL>()); return true;
+    case GPS_K_RATQUAD:
+      if constexpr (RATQUAD) { *rc = f(std::integral_constant<int, GPS_K_RATQUAD>()); return true; }
+      return false;
+    default: return false;
+  }
+}
+
+// the layers' weights of a network program, through the pinned ring into h->dNkn
+static int upload_nkn_weights(gps_handle_t h, const KCompiled& kc) {
+  const size_t wbytes = kc.W.size() * 8;
+  GPS_HIP(h, h->dNkn.ensure(wbytes + 64));
+  GPS_HIP(h, h->ring.upload(h->dNkn.p, kc.W.data(), wbytes, h->stream));
+  return GPS_OK;
+}
+
 // launch the tile pass (plain program or NKN) for prepared features
 static int launch_tiles(gps_handle_t h, const KCompiled& kc, KmatArgs& a, i64 prow, i64 pcol, int n_nodes,
                         double tiles) {
   const int nfeat_total = (int)kc.feats.size();
+  int rc = GPS_OK;
   if (kc.has_nkn) {
-    const size_t wbytes = kc.W.size() * 8;
-    GPS_HIP(h, h->dNkn.ensure(wbytes + 64));
-    GPS_HIP(h, h->ring.upload(h->dNkn.p, kc.W.data(), wbytes, h->stream));
+    rc = upload_nkn_weights(h, kc);
+    if (rc) return rc;
     const int rows_f = kc.net.ftot + kc.net.nnorm;
     const size_t lds = ((size_t)2 * rows_f * KT + (size_t)kc.net.n_layers * NKN_W * (NKN_W + 1)) * 8;
     int rcl = gps_dyn_lds(h, reinterpret_cast<const void*>(&nkn_tile_kernel), 160 * 1024);
     if (rcl) return rcl;
     if (lds > 160 * 1024) return gps_fail(h, GPS_ERR_UNSUPPORTED, "NKN program: feature slabs exceed LDS");
     LaunchScope ls(h, KC_KMAT, tiles * KT * KT * (2.0 * nfeat_total + 600.0 * kc.net.n_layers), tiles * KT * KT * 8.0);
-    hipLaunchKernelGGL(nkn_tile_kernel, dim3((unsigned)(pcol / KT), (unsigned)(prow / KT)), dim3(256), lds, h->stream,
-                       a, kc.prog, kc.net, (const double*)h->dNkn.p);
+    hipLaunchKernelGGL(nkn_tile_kernel, kmat_grid(prow, pcol), dim3(256), lds, h->stream, a, kc.prog, kc.net, (const double*)h->dNkn.p);
     GPS_HIP(h, hipGetLastError());
     return GPS_OK;
   }
+  const KNodeDev& nd0 = kc.prog.nodes[0];
   // One stationary primitive: the VALU kernel is store-bound already (RBF, N = 32768: 0.99 ms = 4.3 TB/s either way; the
   // matrix-pipe version measured 0-4 % slower), so the matrix-pipe kernel is used for it only on request ("kmat_mfma" = 2).
-  if (kc.prog.n_nodes == 1 && kc.prog.nodes[0].norm_row >= 0 && h->kmat_fast && h->kmat_mfma >= 2) {
-    switch (kc.prog.nodes[0].op) {
-      case GPS_K_RBF: return launch_mfma<GPS_K_RBF>(h, a, kc.prog, prow, pcol, tiles, nfeat_total);
-      case GPS_K_MATERN12: return launch_mfma<GPS_K_MATERN12>(h, a, kc.prog, prow, pcol, tiles, nfeat_total);
-      case GPS_K_MATERN32: return launch_mfma<GPS_K_MATERN32>(h, a, kc.prog, prow, pcol, tiles, nfeat_total);
-      case GPS_K_MATERN52: return launch_mfma<GPS_K_MATERN52>(h, a, kc.prog, prow, pcol, tiles, nfeat_total);
-      case GPS_K_EXPONENTIAL: return launch_mfma<GPS_K_EXPONENTIAL>(h, a, kc.prog, prow, pcol, tiles, nfeat_total);
-      default: break;
-    }
-  }
+  if (kc.prog.n_nodes == 1 && nd0.norm_row >= 0 && h->kmat_fast && h->kmat_mfma >= 2 &&
+      with_stationary_op<false>(nd0.op, &rc, [&](auto op) { return launch_mfma<decltype(op)::value>(h, a, kc.prog, prow, pcol, tiles, nfeat_total); }))
+    return rc;
   if (h->kmat_fast && h->kmat_mfma && is_left_deep_chain(kc.prog))                     // Sum / Product of primitives, same
     return launch_mfma<-1>(h, a, kc.prog, prow, pcol, tiles, nfeat_total);
-  if (kc.prog.n_nodes == 1 && kc.prog.nodes[0].norm_row >= 0 && h->kmat_fast) {      // one stationary primitive
-    const KNodeDev& nd = kc.prog.nodes[0];
-    switch (nd.op) {
-      case GPS_K_RBF: return launch_single<GPS_K_RBF>(h, a, nd, prow, pcol, tiles);
-      case GPS_K_MATERN12: return launch_single<GPS_K_MATERN12>(h, a, nd, prow, pcol, tiles);
-      case GPS_K_MATERN32: return launch_single<GPS_K_MATERN32>(h, a, nd, prow, pcol, tiles);
-      case GPS_K_MATERN52: return launch_single<GPS_K_MATERN52>(h, a, nd, prow, pcol, tiles);
-      case GPS_K_EXPONENTIAL: return launch_single<GPS_K_EXPONENTIAL>(h, a, nd, prow, pcol, tiles);
-      case GPS_K_RATQUAD: return launch_single<GPS_K_RATQUAD>(h, a, nd, prow, pcol, tiles);
-      default: break;                              // (the distance ops: the interpreter below)
-    }
-  }
+  if (kc.prog.n_nodes == 1 && nd0.norm_row >= 0 && h->kmat_fast &&                   // one stationary primitive
+      with_stationary_op<true>(nd0.op, &rc, [&](auto op) { return launch_single<decltype(op)::value>(h, a, nd0, prow, pcol, tiles); }))
+    return rc;
   int maxnf = 1;
   for (int i = 0; i < kc.prog.n_nodes; ++i) if (kc.prog.nodes[i].nf > maxnf) maxnf = kc.prog.nodes[i].nf;
   a.maxnf = maxnf;
-  const size_t lds = (size_t)(2 * KT + 2 * maxnf * KLS) * sizeof(double);
-  if (h->kmat_fast && is_left_deep_chain(kc.prog)) {                                   // Sum / Product of primitives
-    int rcc = gps_dyn_lds(h, reinterpret_cast<const void*>(&kmat_chain_kernel), (int)((2 * KT + 2 * KMAXF * KLS) * sizeof(double)));
-    if (rcc) return rcc;
-    LaunchScope ls(h, KC_KMAT, tiles * KT * KT * (2.0 * nfeat_total + 30.0 * ((kc.prog.n_nodes + 1) / 2)), tiles * KT * KT * 8.0);
-    hipLaunchKernelGGL(kmat_chain_kernel, dim3((unsigned)(pcol / KT), (unsigned)(prow / KT)), dim3(256), lds, h->stream, a, kc.prog);
-    GPS_HIP(h, hipGetLastError());
-    return GPS_OK;
-  }
-  int rcl = gps_dyn_lds(h, reinterpret_cast<const void*>(&kmat_tile_kernel), (int)((2 * KT + 2 * KMAXF * KLS) * sizeof(double)));
-  if (rcl) return rcl;
-  LaunchScope ls(h, KC_KMAT, tiles * KT * KT * (2.0 * nfeat_total + 30.0), tiles * KT * KT * 8.0);
-  hipLaunchKernelGGL(kmat_tile_kernel, dim3((unsigned)(pcol / KT), (unsigned)(prow / KT)), dim3(256), lds,
-                     h->stream, a, kc.prog);
-  GPS_HIP(h, hipGetLastError());
-  return GPS_OK;
+  if (h->kmat_fast && is_left_deep_chain(kc.prog))                                     // Sum / Product of primitives
+    return launch_program(h, &kmat_chain_kernel, kmat_grid(prow, pcol), a, kc.prog, maxnf, KLS,
+                          2.0 * nfeat_total + 30.0 * ((kc.prog.n_nodes + 1) / 2), tiles);
+  return launch_program(h, &kmat_tile_kernel, kmat_grid(prow, pcol), a, kc.prog, maxnf, KLS, 2.0 * nfeat_total + 30.0, tiles);
 }
 
 // Kdiag is one number for every point unless the program holds Linear or Polynomial (kernels.py:507-510, 553-554)
@@ -1145,6 +1004,7 @@ int gps_launch_kdiag(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, d
     KCompiled kc;
     int rc = compile_prog(h, prog, n_nodes, 1 << 20, kc);
     if (rc) return rc;
+    // (not nkn_forward: this Product layer multiplies left to right, the device's step-4 one as (a b) (c d) -- other roundings)
     double vin[NKN_W] = {0}, vout[NKN_W];
     for (int p = 0; p < kc.net.n_prims; ++p) vin[p] = prog[p].variance;
     for (int L = 0; L < kc.net.n_layers; ++L) {
@@ -1189,7 +1049,7 @@ static int run_prep(gps_handle_t h, const KCompiled& kc, const double* dX, i64 n
     for (int f = 0; f < nfeat; ++f) tab.f[f] = kc.feats[f];
     for (int q = 0; q < nnorm; ++q) tab.n[q] = kc.norms[q];
     LaunchScope ls(h, KC_KMAT, 0.0, 8.0 * (double)npad * (double)(rows + d_all));
-    hipLaunchKernelGGL(kmat_prep_args_kernel, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, h->stream, dX, n, d_all, npad, tab,
+    hipLaunchKernelGGL(kmat_prep_kernel<PrepTabVal>, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, h->stream, dX, n, d_all, npad, tab,
                        nfeat, nnorm, feat.d(), npad);
     GPS_HIP(h, hipGetLastError());
     return GPS_OK;
@@ -1200,9 +1060,9 @@ static int run_prep(gps_handle_t h, const KCompiled& kc, const double* dX, i64 n
   if (fb) GPS_HIP(h, h->ring.upload(tables.p, kc.feats.data(), fb, h->stream));
   if (nb) GPS_HIP(h, h->ring.upload((char*)tables.p + fb, kc.norms.data(), nb, h->stream));
   LaunchScope ls(h, KC_KMAT, 0.0, 8.0 * (double)npad * (double)(rows + d_all));
-  hipLaunchKernelGGL(kmat_prep_kernel, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, h->stream,
-                     dX, n, d_all, npad, (const PrepFeat*)tables.p,
-                     nfeat, (const PrepNorm*)((char*)tables.p + fb), nnorm, feat.d(), npad);
+  const PrepTabPtr tab{(const PrepFeat*)tables.p, (const PrepNorm*)((char*)tables.p + fb)};
+  hipLaunchKernelGGL(kmat_prep_kernel<PrepTabPtr>, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, h->stream, dX, n, d_all, npad, tab,
+                     nfeat, nnorm, feat.d(), npad);
   GPS_HIP(h, hipGetLastError());
   return GPS_OK;
 }
@@ -1242,43 +1102,13 @@ __global__ __launch_bounds__(256) void kdiag_vec_kernel(const double* __restrict
     out[i] = st[0];
     return;
   }
-  double vin[NKN_W], vout[NKN_W];
+  double vin[NKN_W];
 #pragma unroll
   for (int q = 0; q < NKN_W; ++q) vin[q] = 0.0;
 #pragma unroll
   for (int p = 0; p < NKN_MAXP; ++p)
     if (p < net.n_prims) vin[p] = prim_diag(P.nodes[p]);
-  for (int L = 0; L < net.n_layers; ++L) {
-    const NknLayer ly = net.layers[L];
-    const double* Wl = Wg + L * NKN_W * (NKN_W + 1);
-#pragma unroll
-    for (int o = 0; o < NKN_W; ++o) vout[o] = 0.0;
-    if (ly.type == 0) {
-#pragma unroll
-      for (int o = 0; o < NKN_W; ++o) {
-        double acc = Wl[o * (NKN_W + 1) + NKN_W];
-#pragma unroll
-        for (int j = 0; j < NKN_W; ++j) acc = fma(Wl[o * (NKN_W + 1) + j], vin[j], acc);
-        vout[o] = acc;
-      }
-    } else if (ly.type == 1) {
-      if (ly.step == 2) {
-#pragma unroll
-        for (int o = 0; o < NKN_W / 2; ++o) vout[o] = vin[2 * o] * vin[2 * o + 1];
-      } else if (ly.step == 3) {
-#pragma unroll
-        for (int o = 0; o < NKN_W / 3; ++o) vout[o] = vin[3 * o] * vin[3 * o + 1] * vin[3 * o + 2];
-      } else {
-#pragma unroll
-        for (int o = 0; o < NKN_W / 4; ++o) vout[o] = (vin[4 * o] * vin[4 * o + 1]) * (vin[4 * o + 2] * vin[4 * o + 3]);
-      }
-    } else {
-#pragma unroll
-      for (int o = 0; o < NKN_W; ++o) vout[o] = exp(vin[o]);
-    }
-#pragma unroll
-    for (int q = 0; q < NKN_W; ++q) vin[q] = vout[q];
-  }
+  nkn_forward(net, Wg, vin);
   out[i] = vin[0];
 }
 
@@ -1292,9 +1122,8 @@ int gps_launch_kdiag_vec(gps_handle_t h, const gps_kern_node_t* prog, int n_node
   rc = run_prep(h, kc, dX, n, d_all, npad, h->dFeat, h->dProg, &ldf);
   if (rc) return rc;
   if (kc.has_nkn) {
-    const size_t wbytes = kc.W.size() * 8;
-    GPS_HIP(h, h->dNkn.ensure(wbytes + 64));
-    GPS_HIP(h, h->ring.upload(h->dNkn.p, kc.W.data(), wbytes, h->stream));
+    rc = upload_nkn_weights(h, kc);
+    if (rc) return rc;
   } else {
     memset(&kc.net, 0, sizeof(kc.net));
   }
