@@ -483,6 +483,23 @@ int gps_launch_kmat_input_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n
 int gps_kdiag_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, double kbar, double* grad_slots_host);
 int gps_launch_kmat_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dXr, i64 nr, const double* dXc,
                         i64 nc, i64 d_all, const double* Wd, i64 ldw, int accumulate, double* grad_slots_host);
+// psi.hip : expectations of the RBF kernel under q(x_n) = N(mu_n, diag S_n) and their VJPs (all pointers on the device)
+// par = [variance, l_0 .. l_{q-1}] ; A1 / A2 [n, q], C1 / C2 [n]: filled by gps_launch_psi_prep
+struct PsiIn {
+  const double* Z; const double* Xmu; const double* Xvar; const double* par;
+  double* A1; double* C1; double* A2; double* C2;
+  i64 n, m; int q;
+};
+void gps_psi2_chunking(i64 n, i64 m, int* tile, int* ntile, i64* chunk, int* nchunks);
+int gps_launch_psi_prep(gps_handle_t h, const PsiIn& in);
+int gps_launch_psi2(gps_handle_t h, const PsiIn& in, double* out, i64 ldo);
+int gps_launch_psi2n(gps_handle_t h, const PsiIn& in, double* out);
+int gps_launch_psi1(gps_handle_t h, const PsiIn& in, double* out);
+int gps_launch_psi1_py(gps_handle_t h, const PsiIn& in, const double* Y, i64 r, double* p, i64 ldp);
+int gps_launch_psi_pk(gps_handle_t h, const PsiIn& in, const double* X, i64 ldx, double scale, double* PK, i64 ldpk);
+int gps_launch_psi2_vjp(gps_handle_t h, const PsiIn& in, const double* PK, i64 ldpk, double* out_n, double* out_z, i64 ldz);
+int gps_launch_psi1_vjp(gps_handle_t h, const PsiIn& in, const double* Y, const double* Yt, i64 ldy, const double* Wt, i64 ldw, i64 r,
+                        double* out_n, double* out_z, i64 ldz);
 // diag.hip
 int gps_run_mfma_diag(gps_handle_t h, int waves_per_simd, double* tflops, int* layout_ok);
 int gps_run_gemm_timeline(gps_handle_t h, int op, int lower, i64 m, i64 n, i64 k, int reps, long long* stamps_out,

@@ -1,0 +1,391 @@
+// C ABI of libgpflowslim_hip.so (include/gpflowslim_hip.h): the Bayesian GPLVM (models/gplvm.py:126-204) -- the SGPR collapsed
+// bound with sum Kdiag, Kuf and Kuf Kuf^T replaced by the kernel expectations psi0, Psi1, Psi2 under q(x_n) = N(mu_n, diag S_n)
+// (psi.hip) -- its prediction and its gradient, and the expectations on their own (ekernels.py).
+#include "gps_inducing.hpp"
+
+// One RBF over the latent dimensions 0 .. q-1, in order: everything else (active_dims subsets, Linear / Sum / Product and their
+// cross terms, full covariances) is outside what psi.hip evaluates.
+static int gplvm_check_prog(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes, i64 q) {
+  if (!prog || n_nodes != 1 || prog[0].op != GPS_K_RBF)
+    return gps_fail(h, GPS_ERR_UNSUPPORTED, std::string(who) + ": the kernel expectations are implemented for a single RBF kernel only");
+  if (q > GPS_MAX_DIMS || prog[0].n_dims != (int)q)
+    return gps_fail(h, GPS_ERR_UNSUPPORTED, std::string(who) + ": the RBF kernel must act on all latent dimensions (no active_dims subset)");
+  for (int i = 0; i < (int)q; ++i)
+    if (prog[0].active_dims[i] != i)
+      return gps_fail(h, GPS_ERR_UNSUPPORTED, std::string(who) + ": the RBF kernel must act on the latent dimensions 0 .. q-1 in order");
+  return GPS_OK;
+}
+
+// Z -> dX ; into dA: [Xmu | Xvar | A1 | A2] [n, q] each, [C1 | C2] [n], par [1 + 32], Y [n, r] (optional) ; then the per-point terms
+static int gplvm_upload(gps_handle_t h, const gps_kern_node_t* prog, const double* Z, i64 m, const double* Xmu, const double* Xvar,
+                        i64 n, i64 q, const double* Y, i64 r, PsiIn* in, double** dY) {
+  GPS_HIP(h, h->dX.ensure((size_t)m * q * 8));
+  GPS_HIP(h, hipMemcpyAsync(h->dX.p, Z, (size_t)m * q * 8, hipMemcpyHostToDevice, h->stream));
+  const size_t nq = (size_t)n * q;
+  GPS_HIP(h, h->dA.ensure((4 * nq + 2 * (size_t)n + 40 + (size_t)n * r) * 8));
+  double* base = h->dA.d();
+  double* dMu = base; double* dVar = dMu + nq; double* dA1 = dVar + nq; double* dA2 = dA1 + nq;
+  double* dC1 = dA2 + nq; double* dC2 = dC1 + n; double* dPar = dC2 + n; double* dYraw = dPar + 40;
+  GPS_HIP(h, hipMemcpyAsync(dMu, Xmu, nq * 8, hipMemcpyHostToDevice, h->stream));
+  GPS_HIP(h, hipMemcpyAsync(dVar, Xvar, nq * 8, hipMemcpyHostToDevice, h->stream));
+  double par[1 + GPS_MAX_DIMS] = {};
+  par[0] = prog[0].variance;
+  for (i64 i = 0; i < q; ++i) par[1 + i] = prog[0].lengthscales[i];
+  GPS_HIP(h, h->ring.upload(dPar, par, sizeof(par), h->stream));
+  if (Y) GPS_HIP(h, hipMemcpyAsync(dYraw, Y, (size_t)n * r * 8, hipMemcpyHostToDevice, h->stream));
+  if (dY) *dY = dYraw;
+  *in = PsiIn{h->dX.d(), dMu, dVar, dPar, dA1, dC1, dA2, dC2, n, m, (int)q};
+  return gps_launch_psi_prep(h, *in);
+}
+
+static int gplvm_check_inputs(gps_handle_t h, const char* who, const double* Xvar, i64 n, i64 q, bool allow_zero) {
+  for (i64 i = 0; i < n * q; ++i)
+    if (!(Xvar[i] > 0.0) && !(allow_zero && Xvar[i] == 0.0))
+      return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": the variances of q(x) must be positive");
+  return GPS_OK;
+}
+
+extern "C" int gps_psi_stats(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
+                             const double* Xmu, const double* Xvar, int64_t n, int64_t q, double* psi1_out, double* psi2_out,
+                             double* psi2n_out) {
+  if (!h || !Z || !Xmu || !Xvar || m <= 0 || n <= 0 || q <= 0) return gps_fail(h, GPS_ERR_ARG, "gps_psi_stats: bad argument");
+  int rc = gplvm_check_prog(h, "gps_psi_stats", prog, n_nodes, q);
+  if (rc) return rc;
+  rc = gplvm_check_inputs(h, "gps_psi_stats", Xvar, n, q, true);
+  if (rc) return rc;
+  rc = begin_inducing_call(h, nullptr);                          // (dX is overwritten: a resident GPR factor is gone)
+  if (rc) return rc;
+  PsiIn in;
+  rc = gplvm_upload(h, prog, Z, m, Xmu, Xvar, n, q, nullptr, 0, &in, nullptr);
+  if (rc) return rc;
+  if (psi1_out) {
+    GPS_HIP(h, h->dLikOut.ensure((size_t)n * m * 8));
+    rc = gps_launch_psi1(h, in, h->dLikOut.d());
+    if (rc) return rc;
+    GPS_HIP(h, hipMemcpyAsync(psi1_out, h->dLikOut.p, (size_t)n * m * 8, hipMemcpyDeviceToHost, h->stream));
+    GPS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  if (psi2_out) {
+    GPS_HIP(h, h->dLikOut.ensure((size_t)m * m * 8));
+    rc = gps_launch_psi2(h, in, h->dLikOut.d(), m);
+    if (rc) return rc;
+    GPS_HIP(h, hipMemcpyAsync(psi2_out, h->dLikOut.p, (size_t)m * m * 8, hipMemcpyDeviceToHost, h->stream));
+    GPS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  if (psi2n_out) {
+    GPS_HIP(h, h->dLikOut.ensure((size_t)n * m * m * 8));
+    rc = gps_launch_psi2n(h, in, h->dLikOut.d());
+    if (rc) return rc;
+    GPS_HIP(h, hipMemcpyAsync(psi2n_out, h->dLikOut.p, (size_t)n * m * m * 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  GPS_HIP(h, hipStreamSynchronize(h->stream));
+  return GPS_OK;
+}
+
+// ---- the bound ------------------------------------------------------------------------------------------------------------------
+// With s the noise variance, R outputs, j the jitter:
+//   L = chol(Kuu + j I) ; p = Psi1^T Y ; G = L^-1 Psi2 L^-T ; B = I + G / s ; LB = chol(B) ; v = L^-1 p ; u = LB^-1 v ; c = u / s
+//   F = -N R / 2 log(2 pi s) - R sum log diag LB - |Y|^2 / (2 s) + |c|^2 / 2 - R psi0 / (2 s) + R tr(G) / (2 s),  psi0 = N variance
+// (gplvm.py:131-165 without the KL term, which is elementwise over [N, Q] and stays with the caller.)
+// Left on the device for the gradient: dK / dLinv = L ; dS3 / dS4 = LB ; dS2 = G (symmetric) ; dS1 = Psi2 [mp, mp] ; dX = Z ;
+// dA = the inputs (gplvm_upload) ; dAlpha = [Y^T [r][np] | v^T [r][mp] | u^T [r][mp]].
+struct GplvmFwd { PsiIn in; double* dY; double yy, trG, u2, slogLB; };
+
+static int gplvm_forward(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, i64 m, const double* Xmu,
+                         const double* Xvar, i64 n, i64 q, double jitter, double noise_var, const double* Y, i64 r,
+                         double* bound_out, int* info, GplvmFwd* f) {
+  int rc = begin_inducing_call(h, info);
+  if (rc) return rc;
+  const i64 mp = gps_pad(m), np = gps_pad(n);
+  const double s = noise_var, R = (double)r, N = (double)n;
+  rc = gplvm_upload(h, prog, Z, m, Xmu, Xvar, n, q, Y, r, &f->in, &f->dY);
+  if (rc) return rc;
+  GPS_HIP(h, h->dK.ensure((size_t)mp * mp * 8));
+  GPS_HIP(h, h->dLinv.ensure(linv_bytes(mp)));
+  GPS_HIP(h, h->dS1.ensure((size_t)mp * mp * 8));
+  GPS_HIP(h, h->dS2.ensure((size_t)mp * mp * 8));
+  GPS_HIP(h, h->dS3.ensure((size_t)mp * mp * 8));
+  GPS_HIP(h, h->dS4.ensure(linv_bytes(mp)));
+  int* d_info = (int*)h->dInfo.p;
+  rc = gps_launch_fill_info(h, d_info, INT_MAX);
+  if (rc) return rc;
+  rc = inducing_kuu(h, prog, n_nodes, m, q, jitter);
+  if (rc) return rc;
+  HipOps opsL = factor_ops(h, h->dLinv.d(), mp, d_info);
+  Blocked<HipOps> blL(opsL);
+  rc = blL.potrf_rec(h->dK.d(), mp, mp, 0, 0);
+  if (rc) return rc;
+  rc = classify_blocks(h, opsL, h->dK.d(), mp, mp);
+  if (rc) return rc;
+  // Psi2 -> dS1 ; G = L^-1 Psi2 L^-T -> dS2 through dS3: (Psi2 L^-T)^T L^-T
+  double* Psi2 = h->dS1.d(); double* G = h->dS2.d(); double* LB = h->dS3.d();
+  rc = gps_launch_psi2(h, f->in, Psi2, mp);
+  if (rc) return rc;
+  GPS_HIP(h, hipMemcpyAsync(LB, Psi2, (size_t)mp * mp * 8, hipMemcpyDeviceToDevice, h->stream));
+  rc = blL.trsm_rec(h->dK.d(), mp, mp, 0, LB, mp, mp);
+  if (rc) return rc;
+  rc = gps_launch_transpose(h, LB, mp, mp, mp, G, mp);
+  if (rc) return rc;
+  rc = blL.trsm_rec(h->dK.d(), mp, mp, 0, G, mp, mp);
+  if (rc) return rc;
+  rc = gps_launch_tri_map(h, G, mp, mp, 0);                        // exactly symmetric: the lower triangle mirrored
+  if (rc) return rc;
+  double dots[2];
+  rc = gps_tri_dot(h, G, mp, G, mp, m, dots);
+  if (rc) return rc;
+  f->trG = dots[1];
+  // B = G / s + I ; LB = chol(B)
+  GPS_HIP(h, hipMemcpyAsync(LB, G, (size_t)mp * mp * 8, hipMemcpyDeviceToDevice, h->stream));
+  rc = gps_launch_scale_add_eye(h, LB, mp, mp, m, 1.0 / s);
+  if (rc) return rc;
+  HipOps opsB = factor_ops(h, h->dS4.d(), mp, d_info);
+  Blocked<HipOps> blB(opsB);
+  rc = blB.potrf_rec(LB, mp, mp, 0, 0);
+  if (rc) return rc;
+  // Y^T ; p = Psi1^T Y as rows ; v = L^-1 p ; u = LB^-1 v
+  GPS_HIP(h, h->dAlpha.ensure(((size_t)r * np + 4 * (size_t)r * mp) * 8));
+  double* dYt = h->dAlpha.d(); double* dV = dYt + (size_t)r * np; double* dU = dV + (size_t)r * mp;
+  GPS_HIP(h, hipMemsetAsync(dYt, 0, (size_t)r * np * 8, h->stream));
+  rc = gps_launch_transpose(h, f->dY, r, n, r, dYt, np);
+  if (rc) return rc;
+  rc = gps_launch_psi1_py(h, f->in, f->dY, r, dV, mp);
+  if (rc) return rc;
+  rc = blL.trsv_rec(h->dK.d(), mp, mp, 0, dV, mp, r);
+  if (rc) return rc;
+  GPS_HIP(h, hipMemcpyAsync(dU, dV, (size_t)r * mp * 8, hipMemcpyDeviceToDevice, h->stream));
+  rc = blB.trsv_rec(LB, mp, mp, 0, dU, mp, r);
+  if (rc) return rc;
+  double* part = h->dScal.d();
+  rc = gps_launch_lml_reduce(h, LB, mp, m, dU, mp, r, part);
+  if (rc) return rc;
+  double hp[2 * 64];
+  GPS_HIP(h, hipMemcpyAsync(hp, part, sizeof(hp), hipMemcpyDeviceToHost, h->stream));
+  int linfo = 0;
+  rc = read_info(h, d_info, &linfo);
+  if (rc) return rc;
+  if (info) *info = linfo;
+  if (linfo) return GPS_OK;
+  f->slogLB = 0.0; f->u2 = 0.0; f->yy = 0.0;
+  for (int b = 0; b < 64; ++b) { f->slogLB += hp[2 * b]; f->u2 += hp[2 * b + 1]; }
+  for (i64 i = 0; i < n * r; ++i) f->yy += Y[i] * Y[i];
+  if (bound_out) {
+    const double psi0 = N * prog[0].variance;
+    *bound_out = -0.5 * N * R * log(2.0 * M_PI * s) - R * f->slogLB - 0.5 * f->yy / s + 0.5 * f->u2 / (s * s) - 0.5 * R * psi0 / s +
+                 0.5 * R * f->trG / s;
+  }
+  return GPS_OK;
+}
+
+static int gplvm_args(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes, const double* Z, i64 m,
+                      const double* Xmu, const double* Xvar, i64 n, i64 q, double noise_var, const double* Y, i64 r) {
+  if (!h || !Z || !Xmu || !Xvar || !Y || m <= 0 || n <= 0 || q <= 0 || r <= 0 || !(noise_var > 0.0))
+    return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": bad argument");
+  if (h->allreduce) return gps_fail(h, GPS_ERR_UNSUPPORTED, std::string(who) + ": not available with the data sharded over ranks");
+  if (r > GPS_TILE) return gps_fail(h, GPS_ERR_UNSUPPORTED, std::string(who) + ": at most 128 outputs");
+  int rc = gplvm_check_prog(h, who, prog, n_nodes, q);
+  if (rc) return rc;
+  return gplvm_check_inputs(h, who, Xvar, n, q, true);
+}
+
+extern "C" int gps_bgplvm(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m, const double* Xmu,
+                          const double* Xvar, int64_t n, int64_t q, double jitter, double noise_var, const double* Y, int64_t r,
+                          const double* Xnew, int64_t n_new, int full_cov, double* bound, double* mean_out, double* var_out,
+                          int* info) {
+  int rc = gplvm_args(h, "gps_bgplvm", prog, n_nodes, Z, m, Xmu, Xvar, n, q, noise_var, Y, r);
+  if (rc) return rc;
+  if (n_new > 0 && (!Xnew || !mean_out || !var_out)) return gps_fail(h, GPS_ERR_ARG, "gps_bgplvm: prediction outputs missing");
+  return with_la_retry(h, [&]() -> int {
+    GplvmFwd f;
+    int linfo = 0;
+    int rc2 = gplvm_forward(h, prog, n_nodes, Z, m, Xmu, Xvar, n, q, jitter, noise_var, Y, r, bound, &linfo, &f);
+    if (info) *info = linfo;
+    if (rc2 || linfo || n_new <= 0) return rc2;
+    const i64 mp = gps_pad(m), np = gps_pad(n);
+    HipOps opsL = factor_ops(h, h->dLinv.d(), mp, (int*)h->dInfo.p);
+    HipOps opsB = factor_ops(h, h->dS4.d(), mp, (int*)h->dInfo.p);
+    Blocked<HipOps> blL(opsL), blB(opsB);
+    double kdiag = 0.0;
+    rc2 = gps_launch_kdiag(h, prog, n_nodes, &kdiag);
+    if (rc2) return rc2;
+    GPS_HIP(h, h->dXnew.ensure((size_t)n_new * q * 8));
+    GPS_HIP(h, h->dMean.ensure((size_t)(n_new * r + 2 * n_new) * 8));
+    const double* dU = h->dAlpha.d() + (size_t)r * np + (size_t)r * mp;      // u = c s
+    return sparse_predict_tail(h, prog, n_nodes, blL, blB, m, q, dU, r, h->dMean.d(), 1.0 / noise_var, kdiag, Xnew, n_new, full_cov,
+                               mean_out, var_out);
+  });
+}
+
+// ---- gradient of the bound ----------------------------------------------------------------------------------------------------
+// Reverse mode over what gplvm_forward leaves on the device:
+//   ubar = u / s^2 ; vbar = LB^-T ubar ; LB_bar, B_bar as in sparse_lb_bar ; G_bar = B_bar / s + R / (2 s) I
+//   Psi2_bar = L^-T G_bar L^-1 (symmetric) ; W = L^-T vbar [M, R], Psi1_bar = Y W^T (rank R, formed inside the Psi1 VJP)
+//   L_bar = -tril(L^-T (2 G_bar G + vbar v^T)) ; Kuu_bar = adjoint(L, L_bar) -> kernel-matrix VJPs for theta and Z
+//   d / d variance also gets -R N / (2 s) from psi0 ; d / d s as in the SGPR gradient with psi0 in place of N Kdiag:
+//   d / d s = -|u|^2 / s^3 - <B_bar, G> / s^2 - R tr(G) / (2 s^2) - N R / (2 s) + |Y|^2 / (2 s^2) + R psi0 / (2 s^2)
+// and the two VJPs of psi.hip deliver variance, lengthscales, Z, mu and S through <Psi1_bar, dPsi1> + <Psi2_bar, dPsi2>.
+static int bgplvm_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, i64 m, const double* Xmu,
+                            const double* Xvar, i64 n, i64 q, double jitter, double noise_var, const double* Y, i64 r,
+                            double* bound, double* grad_slots, int n_slots_cap, int* n_slots_out, double* grad_noise, double* grad_Z,
+                            double* grad_Xmu, double* grad_Xvar, int* info) {
+  int ns = 0;
+  int rc = gps_grad_slots(h, prog, n_nodes, &ns);
+  if (rc) return rc;
+  if (n_slots_out) *n_slots_out = ns;
+  if (ns > n_slots_cap) return gps_fail(h, GPS_ERR_ARG, "gps_bgplvm_grad: grad_slots too small");
+  if (ns != 1 + (int)q) return gps_fail(h, GPS_ERR_STATE, "gps_bgplvm_grad: unexpected slot layout of the RBF kernel");
+  GplvmFwd f;
+  int linfo = 0;
+  rc = gplvm_forward(h, prog, n_nodes, Z, m, Xmu, Xvar, n, q, jitter, noise_var, Y, r, bound, &linfo, &f);
+  if (info) *info = linfo;
+  if (rc || linfo) return rc;
+  const i64 mp = gps_pad(m), np = gps_pad(n);
+  const double s = noise_var, R = (double)r, N = (double)n, var = prog[0].variance;
+  HipOps opsL = factor_ops(h, h->dLinv.d(), mp, (int*)h->dInfo.p);
+  HipOps opsB = factor_ops(h, h->dS4.d(), mp, (int*)h->dInfo.p);
+  Blocked<HipOps> blL(opsL), blB(opsB);
+  double* L = h->dK.d(); double* Psi2 = h->dS1.d(); double* G = h->dS2.d(); double* LB = h->dS3.d();
+  double* dYt = h->dAlpha.d(); double* dV = dYt + (size_t)r * np; double* dU = dV + (size_t)r * mp;
+  double* dVbar = dU + (size_t)r * mp; double* dW = dVbar + (size_t)r * mp;
+  std::vector<double> hu((size_t)r * mp), hv((size_t)r * mp), hvv((size_t)r * mp);
+  GPS_HIP(h, hipMemcpyAsync(hu.data(), dU, hu.size() * 8, hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipMemcpyAsync(hvv.data(), dV, hvv.size() * 8, hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipStreamSynchronize(h->stream));
+  for (size_t i = 0; i < hu.size(); ++i) hv[i] = hu[i] / (s * s);
+  GPS_HIP(h, hipMemcpyAsync(dVbar, hv.data(), hv.size() * 8, hipMemcpyHostToDevice, h->stream));
+  rc = blB.trsv_t_rec(LB, mp, mp, 0, dVbar, mp, r);
+  if (rc) return rc;
+  GPS_HIP(h, hipMemcpyAsync(hv.data(), dVbar, hv.size() * 8, hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipStreamSynchronize(h->stream));
+  double lbar_dot_lb = 0.0, dots[2];
+  rc = sparse_lb_bar(h, blB, hv, hu, m, r, &lbar_dot_lb);       // dG1 = LB_bar, dG2 = 2 B_bar (dTmp, dTmp2, dTmp3: scratch)
+  if (rc) return rc;
+  double* B2 = h->dG2.d();
+  rc = gps_tri_dot(h, B2, mp, B2, mp, m, dots);
+  if (rc) return rc;
+  const double trBbar = 0.5 * dots[1];
+  const double Bbar_dot_G = s * (0.5 * lbar_dot_lb - trBbar);
+  const double psi0 = N * var;
+  *grad_noise = -f.u2 / (s * s * s) - Bbar_dot_G / (s * s) - 0.5 * R * f.trG / (s * s) - 0.5 * N * R / s + 0.5 * f.yy / (s * s) +
+                0.5 * R * psi0 / (s * s);
+  // 2 G_bar = (2 B_bar) / s + (R / s) I
+  rc = gps_launch_axpby_eye(h, B2, mp, mp, m, 1.0 / s, R / s);
+  if (rc) return rc;
+  // U = L^T ; 2 Psi2_bar = L^-T (2 G_bar) L^-1 -> dTmp2 through dG1
+  GPS_HIP(h, h->dTmp.ensure((size_t)mp * mp * 8));
+  GPS_HIP(h, h->dTmp2.ensure((size_t)mp * mp * 8));
+  double* U = h->dTmp.d(); double* T1 = h->dG1.d(); double* P2 = h->dTmp2.d();
+  rc = gps_launch_transpose(h, L, mp, mp, mp, U, mp);
+  if (rc) return rc;
+  rc = gps_launch_tri_map(h, U, mp, mp, 3);
+  if (rc) return rc;
+  GPS_HIP(h, hipMemcpyAsync(T1, B2, (size_t)mp * mp * 8, hipMemcpyDeviceToDevice, h->stream));
+  rc = blL.trsm_rn_rec(U, mp, mp, 0, T1, mp, mp);                // 2 G_bar L^-1
+  if (rc) return rc;
+  rc = gps_launch_transpose(h, T1, mp, mp, mp, P2, mp);           // L^-T 2 G_bar
+  if (rc) return rc;
+  rc = blL.trsm_rn_rec(U, mp, mp, 0, P2, mp, mp);
+  if (rc) return rc;
+  // PK = Psi2_bar o (variance^2 exp(-|z_m - z_m'|^2 / 4 l^2)) -> dG4 ; W = L^-T vbar
+  GPS_HIP(h, h->dG4.ensure((size_t)mp * mp * 8));
+  double* PK = h->dG4.d();
+  rc = gps_launch_psi_pk(h, f.in, P2, mp, 0.5, PK, mp);
+  if (rc) return rc;
+  GPS_HIP(h, hipMemcpyAsync(dW, dVbar, (size_t)r * mp * 8, hipMemcpyDeviceToDevice, h->stream));
+  rc = blL.trsv_t_rec(L, mp, mp, 0, dW, mp, r);
+  if (rc) return rc;
+  // the two VJPs of the expectations: per-point sums [2 q + 1][n] and per-row sums [q][mp] of each
+  const size_t per_n = (size_t)(2 * q + 1) * n, per_z = (size_t)q * mp;
+  GPS_HIP(h, h->dLikOut.ensure((2 * per_n + 2 * per_z) * 8));
+  double* d2n = h->dLikOut.d(); double* d1n = d2n + per_n; double* d2z = d1n + per_n; double* d1z = d2z + per_z;
+  rc = gps_launch_psi2_vjp(h, f.in, PK, mp, d2n, d2z, mp);
+  if (rc) return rc;
+  rc = gps_launch_psi1_vjp(h, f.in, f.dY, dYt, np, dW, mp, r, d1n, d1z, mp);
+  if (rc) return rc;
+  std::vector<double> h2n(per_n), h1n(per_n), h2z(per_z), h1z(per_z), hP((size_t)mp * mp), hPsi2((size_t)mp * mp);
+  GPS_HIP(h, hipMemcpyAsync(h2n.data(), d2n, per_n * 8, hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipMemcpyAsync(h1n.data(), d1n, per_n * 8, hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipMemcpyAsync(h2z.data(), d2z, per_z * 8, hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipMemcpyAsync(h1z.data(), d1z, per_z * 8, hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipMemcpyAsync(hP.data(), P2, hP.size() * 8, hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipMemcpyAsync(hPsi2.data(), Psi2, hPsi2.size() * 8, hipMemcpyDeviceToHost, h->stream));
+  // L_bar = -tril(L^-T (2 G_bar G + vbar v^T)) -> dG1 ; Kuu_bar = adjoint(L, L_bar)
+  GPS_HIP(h, h->dTmp3.ensure((size_t)2 * mp * GPS_TILE * 8));
+  GPS_HIP(h, h->dB.ensure((size_t)mp * mp * 8));
+  std::vector<double> va((size_t)mp * GPS_TILE, 0.0), vb((size_t)mp * GPS_TILE, 0.0);
+  for (i64 j = 0; j < m; ++j)
+    for (i64 k = 0; k < r; ++k) { va[(size_t)j * GPS_TILE + k] = hv[(size_t)k * mp + j]; vb[(size_t)j * GPS_TILE + k] = hvv[(size_t)k * mp + j]; }
+  double* dVa = h->dTmp3.d(); double* dVb = dVa + (size_t)mp * GPS_TILE;
+  GPS_HIP(h, hipMemcpyAsync(dVa, va.data(), va.size() * 8, hipMemcpyHostToDevice, h->stream));
+  GPS_HIP(h, hipMemcpyAsync(dVb, vb.data(), vb.size() * 8, hipMemcpyHostToDevice, h->stream));
+  double* Mt = h->dB.d(); double* Lbar = h->dG1.d();
+  rc = gps_launch_gemm_nt(h, 1, 0, mp, mp, mp, G, mp, B2, mp, Mt, mp);               // (2 G_bar G)^T = G (2 G_bar): both symmetric
+  if (rc) return rc;
+  rc = gps_launch_gemm_nt(h, 2, 0, mp, mp, GPS_TILE, dVb, GPS_TILE, dVa, GPS_TILE, Mt, mp);   // + (vbar v^T)^T
+  if (rc) return rc;
+  rc = blL.trsm_rn_rec(U, mp, mp, 0, Mt, mp, mp);                                  // M^T L^-1 = (L^-T M)^T
+  if (rc) return rc;
+  rc = gps_launch_transpose(h, Mt, mp, mp, mp, Lbar, mp);
+  if (rc) return rc;
+  rc = gps_launch_tri_map(h, Lbar, mp, mp, 1);
+  if (rc) return rc;
+  double* Kbar2 = h->dG2.d();                                                       // (2 G_bar is not needed any more)
+  rc = chol_adjoint2(h, blL, U, Lbar, Kbar2, h->dTmp2.d(), mp);
+  if (rc) return rc;
+  GPS_HIP(h, hipStreamSynchronize(h->stream));                                    // (the read-backs above; P2 = dTmp2 was copied before the adjoint reused it)
+  for (int sI = 0; sI < ns; ++sI) grad_slots[sI] = 0.0;
+  {
+    std::vector<double> uu((size_t)ns, 0.0);
+    rc = gps_launch_kmat_vjp(h, prog, n_nodes, h->dX.d(), m, nullptr, 0, q, Kbar2, mp, 0, uu.data());
+    if (rc) return rc;
+    for (int sI = 0; sI < ns; ++sI) grad_slots[sI] += 0.5 * uu[sI];
+  }
+  std::vector<double> gz((size_t)m * q, 0.0);
+  rc = gps_launch_kmat_input_vjp(h, prog, n_nodes, h->dX.d(), m, nullptr, 0, q, Kbar2, mp, 1.0, gz.data());
+  if (rc) return rc;
+  GPS_HIP(h, hipStreamSynchronize(h->stream));
+  // ---- assembly of the expectation VJPs on the host: O(N Q + M^2 Q)
+  std::vector<double> ls((size_t)q);
+  for (i64 k = 0; k < q; ++k) ls[k] = prog[0].lengthscales[k];
+  double sum_w = 0.0, sum_t = 0.0;                                // <Psi2_bar, Psi2>, <Psi1_bar, Psi1>
+  std::vector<double> gl((size_t)q, 0.0);
+  for (i64 i = 0; i < n; ++i) { sum_w += h2n[i]; sum_t += h1n[i]; }
+  for (i64 i = 0; i < n; ++i)
+    for (i64 k = 0; k < q; ++k) {
+      const double S = Xvar[i * q + k], l = ls[k];
+      const double a2 = 1.0 / (l * l + 2.0 * S), a1 = 1.0 / (l * l + S);
+      const double s2 = h2n[i], SA2 = h2n[(size_t)(1 + k) * n + i], SB2 = h2n[(size_t)(1 + q + k) * n + i];
+      const double t1 = h1n[i], SA1 = h1n[(size_t)(1 + k) * n + i], SB1 = h1n[(size_t)(1 + q + k) * n + i];
+      const double sbar2 = -a2 * s2 + 2.0 * a2 * a2 * SB2, sbar1 = -0.5 * a1 * t1 + 0.5 * a1 * a1 * SB1;
+      if (grad_Xmu) grad_Xmu[i * q + k] = -2.0 * a2 * SA2 - a1 * SA1;
+      if (grad_Xvar) grad_Xvar[i * q + k] = sbar2 + sbar1;
+      gl[k] += l * sbar2 + s2 / l + 2.0 * l * sbar1 + t1 / l;
+    }
+  for (i64 a = 0; a < m; ++a)
+    for (i64 k = 0; k < q; ++k) gz[a * q + k] += h2z[(size_t)k * mp + a] + h1z[(size_t)k * mp + a];
+  for (i64 a = 0; a < m; ++a)
+    for (i64 b = 0; b < m; ++b) {
+      const double w2 = 0.25 * (hP[(size_t)a * mp + b] + hP[(size_t)b * mp + a]) * hPsi2[(size_t)a * mp + b];      // (P o Psi2)[a][b]
+      for (i64 k = 0; k < q; ++k) {
+        const double dz = Z[a * q + k] - Z[b * q + k], l = ls[k];
+        gz[a * q + k] -= w2 * dz / (l * l);
+        gl[k] += w2 * dz * dz / (2.0 * l * l * l);
+      }
+    }
+  grad_slots[0] += (2.0 * sum_w + sum_t) / var - 0.5 * R * N / s;
+  for (i64 k = 0; k < q; ++k) grad_slots[1 + k] += gl[k];
+  if (grad_Z) for (i64 i = 0; i < m * q; ++i) grad_Z[i] = gz[i];
+  return GPS_OK;
+}
+
+extern "C" int gps_bgplvm_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
+                               const double* Xmu, const double* Xvar, int64_t n, int64_t q, double jitter, double noise_var,
+                               const double* Y, int64_t r, double* bound, double* grad_slots, int n_slots_cap, int* n_slots_out,
+                               double* grad_noise, double* grad_Z, double* grad_Xmu, double* grad_Xvar, int* info) {
+  int rc = gplvm_args(h, "gps_bgplvm_grad", prog, n_nodes, Z, m, Xmu, Xvar, n, q, noise_var, Y, r);
+  if (rc) return rc;
+  if (!bound || !grad_slots || !grad_noise) return gps_fail(h, GPS_ERR_ARG, "gps_bgplvm_grad: bad argument");
+  return with_la_retry(h, [&]() -> int {
+    return bgplvm_grad_body(h, prog, n_nodes, Z, m, Xmu, Xvar, n, q, jitter, noise_var, Y, r, bound, grad_slots, n_slots_cap,
+                            n_slots_out, grad_noise, grad_Z, grad_Xmu, grad_Xvar, info);
+  });
+}

@@ -173,48 +173,7 @@ static int sparse_gpr_impl(gps_handle_t h, int fitc, const gps_kern_node_t* prog
     *bound_out = bound;
   }
   if (n_new <= 0) return GPS_OK;
-  // ---- prediction                                                      (sgpr.py:155-189)
-  const i64 nsp = gps_pad(n_new);
-  GPS_HIP(h, hipMemcpyAsync(h->dXnew.p, Xnew, (size_t)n_new * d_all * 8, hipMemcpyHostToDevice, h->stream));
-  GPS_HIP(h, h->dB.ensure((size_t)nsp * mp * 8 * 2));
-  double* T1 = h->dB.d();                                         // tmp1^T [nsp, mp]
-  double* T2 = T1 + (size_t)nsp * mp;                             // tmp2^T
-  rc = inducing_kuf(h, prog, n_nodes, n_new, m, d_all, T1);
-  if (rc) return rc;
-  rc = blL.trsm_rec(h->dK.d(), mp, mp, 0, T1, mp, nsp);
-  if (rc) return rc;
-  GPS_HIP(h, hipMemcpyAsync(T2, T1, (size_t)nsp * mp * 8, hipMemcpyDeviceToDevice, h->stream));
-  rc = blB.trsm_rec(h->dS3.d(), mp, mp, 0, T2, mp, nsp);
-  if (rc) return rc;
-  double* dmean = dDiag + mp;                                     // [n_new][r]
-  double* dss2 = dmean + (size_t)n_new * r;
-  double* dss1 = dss2 + n_new;
-  rc = gps_launch_rowdot(h, T2, mp, n_new, mp, dC, mp, r, dmean, dss2);     // tmp2^T (c sigma^2)
-  if (rc) return rc;
-  rc = gps_launch_rowdot(h, T1, mp, n_new, mp, nullptr, mp, 0, nullptr, dss1);
-  if (rc) return rc;
-  std::vector<double> hm((size_t)n_new * r), h2(n_new), h1(n_new);
-  GPS_HIP(h, hipMemcpyAsync(hm.data(), dmean, hm.size() * 8, hipMemcpyDeviceToHost, h->stream));
-  GPS_HIP(h, hipMemcpyAsync(h2.data(), dss2, (size_t)n_new * 8, hipMemcpyDeviceToHost, h->stream));
-  GPS_HIP(h, hipMemcpyAsync(h1.data(), dss1, (size_t)n_new * 8, hipMemcpyDeviceToHost, h->stream));
-  if (full_cov) {
-    GPS_HIP(h, h->dVar.ensure((size_t)nsp * nsp * 8));
-    rc = gps_launch_kmat(h, prog, n_nodes, h->dXnew.d(), n_new, nullptr, n_new, d_all, 0.0, h->dVar.d(), nsp, nsp, nsp, 0, 0);
-    if (rc) return rc;
-    rc = gps_launch_gemm_nt(h, 2, 0, nsp, nsp, mp, T2, mp, T2, mp, h->dVar.d(), nsp);
-    if (rc) return rc;
-    rc = gps_launch_gemm_nt(h, 0, 0, nsp, nsp, mp, T1, mp, T1, mp, h->dVar.d(), nsp);
-    if (rc) return rc;
-    GPS_HIP(h, h->dTmp2.ensure((size_t)n_new * n_new * 8));
-    rc = gps_launch_extract(h, h->dVar.d(), nsp, n_new, n_new, h->dTmp2.d(), n_new, 0);
-    if (rc) return rc;
-    GPS_HIP(h, hipMemcpyAsync(var_out, h->dTmp2.p, (size_t)n_new * n_new * 8, hipMemcpyDeviceToHost, h->stream));
-  }
-  GPS_HIP(h, hipStreamSynchronize(h->stream));
-  for (size_t i = 0; i < hm.size(); ++i) mean_out[i] = hm[i] * wgt;          // SGPR: c = (c sigma^2)/sigma^2
-  if (!full_cov)
-    for (i64 i = 0; i < n_new; ++i) var_out[i] = kdiag + h2[i] - h1[i];
-  return GPS_OK;
+  return sparse_predict_tail(h, prog, n_nodes, blL, blB, m, d_all, dC, r, dDiag + mp, wgt, kdiag, Xnew, n_new, full_cov, mean_out, var_out);
 }
 
 extern "C" int gps_sgpr(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
@@ -235,44 +194,6 @@ extern "C" int gps_fitc(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes
   return sparse_gpr_impl(h, 1, prog, n_nodes, Z, m, X, n, d_all, jitter, noise_var, resid, r, Xnew, n_new, full_cov,
                          bound_out, mean_out, var_out, info);
   });
-}
-
-// Shared by both gradients, from the host rows hv = vbar^T, hu = u^T ([r][mp]) and LB = dS3 (blB: its block inverses):
-// LB_bar = -tril(vbar u^T + R diag(1 / LB_ii)) -> dG1 ; LB^T -> dTmp ; 2 B_bar = 2 adjoint(LB, LB_bar) -> dG2 (dTmp2, dTmp3: scratch).
-// lbar_dot_lb (SGPR; or nullptr): <LB_bar, LB> over the lower triangle.
-static int sparse_lb_bar(gps_handle_t h, Blocked<HipOps>& blB, const std::vector<double>& hv, const std::vector<double>& hu,
-                         i64 m, i64 r, double* lbar_dot_lb) {
-  const i64 mp = gps_pad(m);
-  const double* LB = h->dS3.d();
-  GPS_HIP(h, h->dG1.ensure((size_t)mp * mp * 8));
-  GPS_HIP(h, h->dG2.ensure((size_t)mp * mp * 8));
-  GPS_HIP(h, h->dTmp.ensure((size_t)mp * mp * 8));
-  GPS_HIP(h, h->dTmp2.ensure((size_t)mp * mp * 8));
-  GPS_HIP(h, h->dTmp3.ensure((size_t)2 * mp * GPS_TILE * 8));
-  std::vector<double> va((size_t)mp * GPS_TILE, 0.0), ub((size_t)mp * GPS_TILE, 0.0);
-  for (i64 j = 0; j < m; ++j) for (i64 q = 0; q < r; ++q) { va[(size_t)j * GPS_TILE + q] = hv[(size_t)q * mp + j]; ub[(size_t)j * GPS_TILE + q] = hu[(size_t)q * mp + j]; }
-  double* dVa = h->dTmp3.d(); double* dUb = dVa + (size_t)mp * GPS_TILE;
-  GPS_HIP(h, hipMemcpyAsync(dVa, va.data(), va.size() * 8, hipMemcpyHostToDevice, h->stream));
-  GPS_HIP(h, hipMemcpyAsync(dUb, ub.data(), ub.size() * 8, hipMemcpyHostToDevice, h->stream));
-  double* LBbar = h->dG1.d();
-  int rc = gps_launch_gemm_nt(h, 1, 1, mp, mp, GPS_TILE, dVa, GPS_TILE, dUb, GPS_TILE, LBbar, mp);
-  if (rc) return rc;
-  rc = gps_launch_diag_recip_add(h, LBbar, mp, LB, mp, m, (double)r);
-  if (rc) return rc;
-  rc = gps_launch_tri_map(h, LBbar, mp, mp, 1);
-  if (rc) return rc;
-  if (lbar_dot_lb) {
-    double dots[2];
-    rc = gps_tri_dot(h, LBbar, mp, LB, mp, m, dots);
-    if (rc) return rc;
-    *lbar_dot_lb = dots[0];
-  }
-  double* U = h->dTmp.d();
-  rc = gps_launch_transpose(h, LB, mp, mp, mp, U, mp);
-  if (rc) return rc;
-  rc = gps_launch_tri_map(h, U, mp, mp, 3);
-  if (rc) return rc;
-  return chol_adjoint2(h, blB, U, LBbar, h->dG2.d(), h->dTmp2.d(), mp);
 }
 
 // ---- gradient of the SGPR bound ----------------------------------------------------------------------------------

@@ -8,6 +8,7 @@ from ._settings import settings
 from . import transforms
 from . import params
 from . import kernels
+from . import ekernels
 from . import mean_functions
 from . import densities
 from . import likelihoods

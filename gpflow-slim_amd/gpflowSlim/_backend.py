@@ -132,6 +132,14 @@ _SIGNATURES = {
     "gps_fitc": [ctypes.c_void_p, ctypes.POINTER(KernNode), ctypes.c_int, _c_double_p, _i64, _c_double_p, _i64, _i64,
                  ctypes.c_double, ctypes.c_double, _c_double_p, _i64, _c_double_p, _i64, ctypes.c_int, _c_double_p,
                  _c_double_p, _c_double_p, _c_int_p],
+    "gps_psi_stats": [ctypes.c_void_p, ctypes.POINTER(KernNode), ctypes.c_int, _c_double_p, _i64, _c_double_p, _c_double_p, _i64,
+                      _i64, _c_double_p, _c_double_p, _c_double_p],
+    "gps_bgplvm": [ctypes.c_void_p, ctypes.POINTER(KernNode), ctypes.c_int, _c_double_p, _i64, _c_double_p, _c_double_p, _i64, _i64,
+                   ctypes.c_double, ctypes.c_double, _c_double_p, _i64, _c_double_p, _i64, ctypes.c_int, _c_double_p, _c_double_p,
+                   _c_double_p, _c_int_p],
+    "gps_bgplvm_grad": [ctypes.c_void_p, ctypes.POINTER(KernNode), ctypes.c_int, _c_double_p, _i64, _c_double_p, _c_double_p, _i64,
+                        _i64, ctypes.c_double, ctypes.c_double, _c_double_p, _i64, _c_double_p, _c_double_p, ctypes.c_int, _c_int_p,
+                        _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_int_p],
     "gps_sparse_last_terms": [ctypes.c_void_p, _c_double_p],
     "gps_profile_enable": [ctypes.c_void_p, ctypes.c_int],
     "gps_profile_reset": [ctypes.c_void_p],
@@ -344,6 +352,17 @@ def op_node(op):
     nd = KernNode()
     nd.op = op
     return nd
+
+
+def psi2_chunking(n, m):
+    """(tile edge, lower-triangle tiles, points per chunk, chunks) of the Psi2 kernel for n points and m inducing points
+    (csrc/psi.hip: gps_psi2_chunking)."""
+    tm = 64 if m > 48 else 32
+    t = -(-m // tm)
+    nt = t * (t + 1) // 2
+    nc = min(max(-(-2048 // nt), 1), -(-n // 64))
+    chunk = 64 * -(-n // (64 * nc))
+    return tm, nt, chunk, -(-n // chunk)
 
 
 class Handle(object):
@@ -814,6 +833,82 @@ class Handle(object):
         if info.value > 0:
             raise NotPositiveDefiniteError("Cholesky decomposition was not successful (order %d)" % info.value)
         return bound.value, slots[:nslots.value].copy(), gnoise.value, g_mean, (g_Z if want_grad_Z else None)
+
+    # ---- Bayesian GPLVM and the kernel expectations behind it (csrc/psi.hip, csrc/gps_gplvm.hip)
+    @staticmethod
+    def _psi_args(Z, Xmu, Xvar):
+        Z, Xmu, Xvar = _f64(Z), _f64(Xmu), _f64(Xvar)
+        _need(Z.ndim == 2 and Xmu.ndim == 2 and Z.shape[1] == Xmu.shape[1] and Z.shape[0] > 0 and Xmu.shape[0] > 0,
+              "the kernel expectations need Z [M, Q] and Xmu [N, Q]")
+        if Xvar.ndim == 3:
+            raise NotImplementedError("full [N, Q, Q] covariances of q(x) are not implemented: pass the diagonals as [N, Q]")
+        _need(Xvar.shape == Xmu.shape, "Xvar must be [N, Q] like Xmu")
+        return Z, Xmu, Xvar
+
+    def psi_stats(self, prog, Z, Xmu, Xvar, want_psi1=False, want_psi2=False, want_psi2n=False):
+        """gps_psi_stats: (Psi1 [N, M], Psi2 [M, M], psi2n [N, M, M]) of one RBF kernel under q(x_n) = N(Xmu_n, diag Xvar_n);
+        None for what was not asked for."""
+        Z, Xmu, Xvar = self._psi_args(Z, Xmu, Xvar)
+        (m, q), n = Z.shape, Xmu.shape[0]
+        p1 = np.empty((n, m)) if want_psi1 else None
+        p2 = np.empty((m, m)) if want_psi2 else None
+        p2n = np.empty((n, m, m)) if want_psi2n else None
+        self.resident_token = None
+        self.factor_key = None
+        self._check(self._lib.gps_psi_stats(self._h, prog, len(prog), _ptr(Z), m, _ptr(Xmu), _ptr(Xvar), n, q,
+                                            None if p1 is None else _ptr(p1), None if p2 is None else _ptr(p2),
+                                            None if p2n is None else _ptr(p2n)), "gps_psi_stats")
+        return p1, p2, p2n
+
+    def bgplvm(self, prog, Z, Xmu, Xvar, Y, jitter, noise_var, Xnew=None, full_cov=False, want_bound=True):
+        """gps_bgplvm: (bound without the KL term, mean [N*, R], var [N*] or [N*, N*])."""
+        Z, Xmu, Xvar = self._psi_args(Z, Xmu, Xvar)
+        Y = _f64(Y)
+        (m, q), n = Z.shape, Xmu.shape[0]
+        _need(Y.ndim == 2 and Y.shape[0] == n, "Y must be [N, R]")
+        r = Y.shape[1]
+        bound, info = ctypes.c_double(0), ctypes.c_int(0)
+        if Xnew is not None:
+            Xnew = _f64(Xnew)
+            _need(Xnew.ndim == 2 and Xnew.shape[1] == q, "Xnew must be [N*, %d]" % q)
+            n_new = Xnew.shape[0]
+            if n_new == 0:
+                return 0.0, np.empty((0, r)), np.empty((0, 0) if full_cov else (0,))
+            mean = np.empty((n_new, r))
+            var = np.empty((n_new, n_new) if full_cov else (n_new,))
+            xp, mp_, vp = _ptr(Xnew), _ptr(mean), _ptr(var)
+        else:
+            n_new, mean, var, xp, mp_, vp = 0, None, None, None, None, None
+        self.resident_token = None
+        self.factor_key = None
+        self._check(self._lib.gps_bgplvm(self._h, prog, len(prog), _ptr(Z), m, _ptr(Xmu), _ptr(Xvar), n, q, float(jitter),
+                                         float(noise_var), _ptr(Y), r, xp, n_new, 1 if full_cov else 0,
+                                         ctypes.byref(bound) if want_bound else None, mp_, vp, ctypes.byref(info)), "gps_bgplvm")
+        if info.value > 0:
+            raise NotPositiveDefiniteError("Cholesky decomposition was not successful (order %d)" % info.value)
+        return bound.value, mean, var
+
+    def bgplvm_grad(self, prog, Z, Xmu, Xvar, Y, jitter, noise_var):
+        """gps_bgplvm_grad: (bound without the KL term, grad_slots, grad_noise, grad_Z [M, Q], grad_Xmu [N, Q], grad_Xvar [N, Q]),
+        gradients with respect to the constrained values."""
+        Z, Xmu, Xvar = self._psi_args(Z, Xmu, Xvar)
+        Y = _f64(Y)
+        (m, q), n = Z.shape, Xmu.shape[0]
+        _need(Y.ndim == 2 and Y.shape[0] == n, "Y must be [N, R]")
+        bound, gnoise = ctypes.c_double(0), ctypes.c_double(0)
+        info, nslots = ctypes.c_int(0), ctypes.c_int(0)
+        cap = 64
+        slots = np.zeros(cap)
+        g_Z, g_mu, g_var = np.zeros((m, q)), np.zeros((n, q)), np.zeros((n, q))
+        self.resident_token = None
+        self.factor_key = None
+        self._check(self._lib.gps_bgplvm_grad(self._h, prog, len(prog), _ptr(Z), m, _ptr(Xmu), _ptr(Xvar), n, q, float(jitter),
+                                              float(noise_var), _ptr(Y), Y.shape[1], ctypes.byref(bound), _ptr(slots), cap,
+                                              ctypes.byref(nslots), ctypes.byref(gnoise), _ptr(g_Z), _ptr(g_mu), _ptr(g_var),
+                                              ctypes.byref(info)), "gps_bgplvm_grad")
+        if info.value > 0:
+            raise NotPositiveDefiniteError("Cholesky decomposition was not successful (order %d)" % info.value)
+        return bound.value, slots[:nslots.value].copy(), gnoise.value, g_Z, g_mu, g_var
 
     # ---- native collectives (csrc/comm_rccl.hip; driven by gpflowSlim.distributed.RcclComm)
     def comm_init(self, rank, world, unique_id):

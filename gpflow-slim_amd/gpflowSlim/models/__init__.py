@@ -2,3 +2,4 @@ from .model import Model, GPModel
 from .gpr import GPR
 from .svgp import SVGP
 from .sgpr import SGPR, GPRFITC
+from .gplvm import BayesianGPLVM, PCA_reduce

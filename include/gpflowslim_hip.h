@@ -333,6 +333,34 @@ int gps_fitc_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes,
                   double* bound, double* grad_slots, int n_slots_cap, int* n_slots_out, double* grad_noise,
                   double* grad_mean, double* grad_Z, int* info);
 
+/* ---- Bayesian GPLVM (models/gplvm.py:54-204) and the kernel expectations behind it (ekernels.py:13-149) ----------------
+ * The SGPR collapsed bound with sum Kdiag, Kuf and Kuf Kuf^T replaced by psi0, Psi1, Psi2 = the expectations of the kernel
+ * under q(x_n) = N(Xmu_n, diag Xvar_n).  Scope: prog is ONE GPS_K_RBF node (ARD or isotropic) over the latent dimensions
+ * 0 .. q-1 in order, and the covariances of q are diagonal, Xvar host [n, q]; anything else (active_dims subsets, Linear / Sum /
+ * Product kernels and their cross terms, full [n, q, q] covariances) returns GPS_ERR_UNSUPPORTED.  Not available while the data
+ * are sharded over ranks (gps_set_allreduce).  Z host [m, q], Xmu host [n, q], Y host [n, r].
+ *
+ * gps_psi_stats: any of psi1_out host [n, m] (eKxz), psi2_out host [m, m] (sum_n eKzxKxz, O(m^2) device memory whatever n) and
+ * psi2n_out host [n, m, m] (eKzxKxz point by point: small sizes) may be NULL.  psi0 = n * variance needs no device.
+ * Psi2 is exactly symmetric, and every result is bitwise identical from run to run (no floating-point atomics).       */
+int gps_psi_stats(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
+                  const double* Xmu, const double* Xvar, int64_t n, int64_t q,
+                  double* psi1_out, double* psi2_out, double* psi2n_out);
+/* bound (optional) receives the bound WITHOUT the KL[q(x) || p(x)] term (gplvm.py:150-156: elementwise over [n, q], the
+ * caller's).  If n_new > 0: prediction at Xnew host [n_new, q] as gps_sgpr (gplvm.py:169-204).  info > 0: a factorisation
+ * met a non-positive pivot.                                                                                             */
+int gps_bgplvm(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
+               const double* Xmu, const double* Xvar, int64_t n, int64_t q, double jitter, double noise_var,
+               const double* Y, int64_t r, const double* Xnew, int64_t n_new, int full_cov,
+               double* bound, double* mean_out, double* var_out, int* info);
+/* The same bound and its gradient with respect to the constrained values: grad_slots (slot layout of gps_gpr_lml_grad: variance,
+ * then q lengthscale slots even for an isotropic kernel), grad_noise, grad_Z host [m, q], grad_Xmu and grad_Xvar host [n, q]
+ * (the last three optional).  Reverse mode at the matrix level; Psi2's vector-Jacobian product recomputes psi2n in two passes. */
+int gps_bgplvm_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
+                    const double* Xmu, const double* Xvar, int64_t n, int64_t q, double jitter, double noise_var,
+                    const double* Y, int64_t r, double* bound, double* grad_slots, int n_slots_cap, int* n_slots_out,
+                    double* grad_noise, double* grad_Z, double* grad_Xmu, double* grad_Xvar, int* info);
+
 /* GP regression with the FITC approximation: models.GPRFITC._build_likelihood / _build_predict
  * (models/sgpr.py:229-318: Luu = chol(Kuu), V = Luu^-1 Kuf, nu = Kdiag - colsumsq(V) + sigma^2,
  * L = chol(I + (V/nu) V^T), gamma = L^-1 V (err/nu)).  Same arguments, layouts and outputs as gps_sgpr;
