@@ -20,9 +20,20 @@ typedef int64_t i64;
 static inline i64 gps_pad(i64 n) { return ((n + GPS_TILE - 1) / GPS_TILE) * GPS_TILE; }
 
 // ---- growable device buffer -------------------------------------------------
+// Every DevBuf belongs to a handle and enters that handle's registry (DevBufList) when it is constructed: there is no other way
+// to make one, so release_buffers and gps_device_bytes, which walk the registry, cannot miss a buffer.
+//   WORK        given back by gps_release_buffers and by gps_destroy
+//   PERSISTENT  given back by gps_destroy only: allocated (and, the counters, cleared) once per handle
+struct DevBuf;
+typedef std::vector<DevBuf*> DevBufList;
 struct DevBuf {
+  enum Class { WORK, PERSISTENT };
   void*  p = nullptr;
   size_t cap = 0;
+  const Class cls;
+  DevBuf(DevBufList& owner, Class c = WORK) : cls(c) { owner.push_back(this); }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
   hipError_t ensure(size_t bytes) {
     // test aid: GPS_POISON_ALLOC=1 fills every NEW buffer with NaN bit patterns, =2 also every buffer that is
     // requested again (only valid for call sequences that do not rely on a resident factor): a kernel that reads
@@ -90,6 +101,7 @@ struct KClassStat {
 struct PendingEvt { int klass; hipEvent_t a, b; i64 t[4]; };
 
 struct gps_handle_s {
+  DevBufList bufs;                    // every DevBuf member below, in declaration order (first: they register here as they are constructed)
   int device = 0;
   hipStream_t stream = nullptr;
   hipStream_t own_stream = nullptr;   // the handle's own stream while an external one is installed
@@ -99,7 +111,7 @@ struct gps_handle_s {
 
   // GEMM tile selection (gemm_f64.hip): use the next smaller tile while the grid would have
   // fewer workgroups than this; gemm_force_tb != 0 pins the tile edge (diagnostics)
-  int gemm_min_tiles = 512;    // (constant)
+  static constexpr int gemm_min_tiles = 512;
   int gemm_force_tb = 0;
   int gemm_pair = 1;           // (diagnostics, GPS_GEMM_PAIR) products with a triangular operand: mirror tiles in pairs
   // look-ahead of the sweep (potrf_rl_groups): the remainder update of a pair of panels runs on side_stream (one CU per
@@ -117,14 +129,9 @@ struct gps_handle_s {
   // one call in ten); N = 8192: 5.90 -> 5.77 ms, N = 16384: 29.2 -> 28.8 ms, N = 32768 unchanged.
 #define GPS_LA_MASK_WORD0 0x00000000u
   hipEvent_t ev_la = nullptr;
-  DevBuf dLaFlags;                             // [0] fork ticket (chain -> side), [1] join ticket (side -> chain), [2] spin time-outs
+  DevBuf dLaFlags{bufs, DevBuf::PERSISTENT};   // [0] fork ticket (chain -> side), [1] join ticket (side -> chain), [2] spin time-outs
   unsigned long long la_ticket = 0, fol_ticket = 0;
   int la_fault_inject = 0;                     // diagnostics: see HipOps::chain_join
-  // padded points up to which the factorisation is one cooperative launch (as many workgroups as pairs up to 896, everything
-  // drawn from a queue above; against launch by launch: N = 1024 / 1536 / 2048: -17 / -14 / -11 % per likelihood, 3072: -2 %,
-  // 4096: +35 % -- the 16-row-slab products are no match for the GEMM kernel once the bulk outweighs the chain)
-  static constexpr i64 small_n_max = 2048;
-  int small_fault_inject = 0;                  // diagnostics: the k-th cooperative small-N launch from now starts aborted
   int wave_fault_inject = 0;                   // diagnostics: the k-th wavefront substitution from now reports "gave up"
   bool la_timed_out = false;                   // set by read_info when a hand-over wait gave up: the entry point re-runs without look-ahead
   long long la_retries = 0;                    // evaluations re-run that way (gps_profile_get "lookahead_retries")
@@ -180,31 +187,31 @@ struct gps_handle_s {
   void* allreduce_ctx = nullptr;
   double* red_buf = nullptr;                   // caller-owned device buffer the collective library knows
   i64 red_cap = 0;
-  DevBuf dStage;    // a user matrix as uploaded (q_sqrt [m, m]) before a device kernel masks / transposes / pads it
-  DevBuf dX;        // [n, d_all]
-  DevBuf dK;        // [npad, npad]  K then L (lower, row-major)
-  DevBuf dLinv;     // [npad/128][128*128] inverses of the diagonal blocks
-  DevBuf dAlpha;    // [r][npad]  residual then alpha = L^-1 resid
-  DevBuf dFeat;     // feature workspace of the kernel-matrix build (rows)
-  DevBuf dFeat2;    // feature workspace (cols / Xnew)
-  DevBuf dProg;     // device copy of the kernel program
-  DevBuf dNkn;      // neural-kernel-network layer weights
-  DevBuf dWave;     // trsv wavefront: exchange buffer [2][npad]
-  DevBuf dWaveCtl;  // [0] ticket, [1] give-ups (persistent)
-  DevBuf dScal;     // small scalar outputs: [0]=sum log diag, [1]=sum alpha^2, ...
-  DevBuf dInfo;     // int info word
-  DevBuf dXnew;     // [n_new, d_all]
-  DevBuf dB;        // [nspad, npad]   K(Xnew, X) then A^T
+  DevBuf dStage{bufs};    // a user matrix as uploaded (q_sqrt [m, m]) before a device kernel masks / transposes / pads it
+  DevBuf dX{bufs};        // [n, d_all]
+  DevBuf dK{bufs};        // [npad, npad]  K then L (lower, row-major)
+  DevBuf dLinv{bufs};     // [npad/128][128*128] inverses of the diagonal blocks
+  DevBuf dAlpha{bufs};    // [r][npad]  residual then alpha = L^-1 resid
+  DevBuf dFeat{bufs};     // feature workspace of the kernel-matrix build (rows)
+  DevBuf dFeat2{bufs};    // feature workspace (cols / Xnew)
+  DevBuf dProg{bufs};     // device copy of the kernel program
+  DevBuf dNkn{bufs};      // neural-kernel-network layer weights
+  DevBuf dWave{bufs};     // trsv wavefront: exchange buffer [2][npad]
+  DevBuf dWaveCtl{bufs, DevBuf::PERSISTENT};  // [0] ticket, [1] give-ups (persistent)
+  DevBuf dScal{bufs, DevBuf::PERSISTENT};     // small scalar outputs: [0]=sum log diag, [1]=sum alpha^2, ...
+  DevBuf dInfo{bufs, DevBuf::PERSISTENT};     // int info word
+  DevBuf dXnew{bufs};     // [n_new, d_all]
+  DevBuf dB{bufs};        // [nspad, npad]   K(Xnew, X) then A^T
   // predict_f on few test points (round 6): wide inverse blocks of the resident factor, built once per factor.  dWbig / dWtbig:
   // [nf, GPS_WB] = the inverses of the GPS_WB-column diagonal blocks of L (lower) / their transposes, stacked; nf = whole blocks
   // of npad.  dBigT: scratch of the level-by-level build.  dB2: the solution (the wide leaves are out-of-place products).
-  DevBuf dWbig, dWtbig, dBigT, dB2;
+  DevBuf dWbig{bufs}, dWtbig{bufs}, dBigT{bufs}, dB2{bufs};
   unsigned long long factor_gen = 0, big_inv_gen = ~0ull;   // the factor the wide blocks belong to (factor_gen: bumped whenever dK / dLinv change)
   i64 big_inv_nf = 0;
   int predict_inv_blocks = 1;   // option "predict_inverse_blocks"
-  DevBuf dMean;     // [n_new, r]
-  DevBuf dVar;      // [n_new] or [nspad, nspad]
-  DevBuf dKdiag;    // [n] per-point Kdiag of a program with Linear / Polynomial (gps_launch_kdiag_vec)
+  DevBuf dMean{bufs};     // [n_new, r]
+  DevBuf dVar{bufs};      // [n_new] or [nspad, nspad]
+  DevBuf dKdiag{bufs};    // [n] per-point Kdiag of a program with Linear / Polynomial (gps_launch_kdiag_vec)
   // ---- block-column distributed factorisation (gps_dist_*) ----
   int dist_P = 0, dist_rank = 0;
   i64 dist_nb = 0, dist_np = 0, dist_r = 0;
@@ -226,43 +233,55 @@ struct gps_handle_s {
   // gps_dist_lml's own two lanes (high / low priority) and its event pool: created once per handle, not per evaluation
   hipStream_t dist_chain = nullptr, dist_bulk_own = nullptr;
   std::vector<hipEvent_t> dist_events; size_t dist_event_next = 0;
-  DevBuf dDistScal;                 // [n_panels][4] per-panel sum log L_ii, sum alpha^2, info
-  DevBuf dDistComm[3];              // comm buffers of gps_dist_lml (the all-native driver; other callers bring their own)
+  DevBuf dDistScal{bufs};                 // [n_panels][4] per-panel sum log L_ii, sum alpha^2, info
+  DevBuf dDistComm[3]{{bufs}, {bufs}, {bufs}};   // comm buffers of gps_dist_lml (the all-native driver; other callers bring their own)
   // distributed gradient (dist_grad.hip): [128 + ncl * nb][np] rows 0..127 = alpha^T then A^T = (K_y^-1 resid)^T (r real rows),
   // then one row per owned column of (L^-1 E_own)^T, in place (L^-T L^-1 E_own)^T = the owned columns of K_y^-1
-  DevBuf dDistZ;
-  DevBuf dDistPT;                   // [nb][np] the transposed panel of the backward stream
+  DevBuf dDistZ{bufs};
+  DevBuf dDistPT{bufs};                   // [nb][np] the transposed panel of the backward stream
   bool dist_grad_ready = false;     // gps_dist_grad_begin ran on the current partitioned factor
 
-  DevBuf dA;        // [r][npad]  K_y^-1 (Y - m)                         (gradient path)
-  DevBuf dY;        // [npad, npad]  L^-T                                 (gradient path)
-  DevBuf dKinv;     // [npad, npad]  K_y^-1, lower triangle               (gradient path)
-  DevBuf dS1, dS2, dS3, dS4;   // SGPR work space (gps_sgpr)
-  DevBuf dG1, dG2, dG3, dG4;   // SVGP gradient work space (gps_svgp_elbo_grad)
-  DevBuf dLikIn, dLikOut, dLikPart, dLikH;   // likelihoods (lik.hip): moments / Y / mean ; dmu, dvar ; per-workgroup partials ; H^T [k][nspad]
-  DevBuf dTmp;      // generic scratch (host-matrix entry points)
-  DevBuf dTmp2;
-  DevBuf dTmp3;
+  DevBuf dA{bufs};        // [r][npad]  K_y^-1 (Y - m)                         (gradient path)
+  DevBuf dY{bufs};        // [npad, npad]  L^-T                                 (gradient path)
+  DevBuf dKinv{bufs};     // [npad, npad]  K_y^-1, lower triangle               (gradient path)
+  DevBuf dS1{bufs}, dS2{bufs}, dS3{bufs}, dS4{bufs};   // SGPR work space (gps_sgpr)
+  DevBuf dG1{bufs}, dG2{bufs}, dG3{bufs}, dG4{bufs};   // SVGP gradient work space (gps_svgp_elbo_grad)
+  DevBuf dLikIn{bufs}, dLikOut{bufs}, dLikPart{bufs}, dLikH{bufs};   // likelihoods (lik.hip): moments / Y / mean ; dmu, dvar ; per-workgroup partials ; H^T [k][nspad]
+  DevBuf dTmp{bufs};      // generic scratch (host-matrix entry points)
+  DevBuf dTmp2{bufs};
+  DevBuf dTmp3{bufs};
   static constexpr long long resid_ring_max = 1 << 16;   // residuals up to this many bytes are uploaded through a pinned slot (larger ones: the slots would each be re-allocated on first use, 0.3 ms a piece)
   int trsm_panel = 1;         // 512-column triangular solves as one launch (trsm_panel.hip); 0: down to 128 columns launch by launch
   int trsm_tall_ratio = 16;   // a solve of m rows against n columns goes panel by panel, left-looking, when m >= ratio * n (0: never; blocked.hpp::tall_panels)
   int trsm_panel_rows = 0;    // form of that launch: 32 (rows per workgroup, two workgroups per CU), 64 (persistent), 65 (64 rows, not persistent), 0 = by the number of rows
-  DevBuf dSmallOut;           // everything a small-N likelihood + gradient hands back, contiguous (one copy)
-  DevBuf dFeatG;              // features of the gradient kernel (its own buffer: they may be prepared before the kernel matrix is built)
-  DevBuf dGradSums;           // reduced sums of the gradient kernel (grad.hip)
+  DevBuf dSmallOut{bufs};           // everything a small-N likelihood + gradient hands back, contiguous (one copy)
+  DevBuf dFeatG{bufs};              // features of the gradient kernel (its own buffer: they may be prepared before the kernel matrix is built)
+  DevBuf dGradSums{bufs};           // reduced sums of the gradient kernel (grad.hip)
   void* hRes = nullptr;       // pinned host landing area of small read-backs (GPS_HRES_BYTES)
-  bool small_defer = false, small_pending = false;   // gps_gpr_lml_grad: the small launch's results are read back later, with the gradient's
-  DevBuf dBlkCond;            // kappa_1 of the diagonal blocks (classify_blocks)
-  DevBuf dSmallSync;          // counters of the one-launch factorisation of small problems (small_n.hip), zero between calls
-  int small_n = 1;            // option "small_n": GPR problems of up to 512 padded rows (and 16 outputs) are factored by one cooperative launch
-  long long small_fallbacks = 0;   // such launches that gave up (a bounded wait ran out): the evaluation was redone launch by launch
-  int small_consec = 0;            // give-ups in a row; the fourth sends the next 256 evaluations (small_cooldown) launch by launch
-  int small_cooldown = 0;          // (back-off: a device that something else keeps busy must not cost a bounded wait per step)
-  bool small_valid = false; double small_slog = 0.0, small_ssq = 0.0;   // reductions the last small launch produced
-  bool ev3_is_ev2 = false;
-  bool gpr_linvT_stale = false;    // the resident GPR factor's transposed block inverses have not been produced yet (gpr_ensure_linvT)
-  DevBuf dGemmWs, dGemmCnt;   // slice partials + arrival counters of the GEMM tail split
-  DevBuf dGemvWs, dGemvCnt;   // slice partials + arrival counters of the split transposed gemv (blas1.hip)
+  DevBuf dBlkCond{bufs};            // kappa_1 of the diagonal blocks (classify_blocks)
+  DevBuf dSmallSync{bufs, DevBuf::PERSISTENT};   // counters of the two cooperative launches of the small path (small_n.hip): allocated and cleared once, left zero by every launch
+  // ---- the one-launch path of small GPR problems (small_n.hip; host side: gps_gpr.hip) ----
+  // A GPR problem of at most small_n_max padded points and 16 outputs, with leaves that need no refinement, is factored by ONE
+  // cooperative launch, and K_y^-1 for its gradient by one more.  (As many workgroups as pairs up to 896 points, everything drawn
+  // from a queue above; against launch by launch: N = 1024 / 1536 / 2048: -17 / -14 / -11 % per likelihood, 3072: -2 %, 4096:
+  // +35 % -- the 16-row-slab products are no match for the GEMM kernel once the bulk outweighs the chain.)
+  static constexpr i64 small_n_max = 2048;
+  struct SmallPath {
+    int on = 1;                  // option "small_n" (0: every problem launch by launch)
+    int fault_inject = 0;        // option "small_fault_inject": the k-th cooperative launch from now starts with its abort word set
+    // give-ups: a bounded wait inside a launch ran out and the evaluation was redone launch by launch (gps_gpr.hip: small_gave_up)
+    long long fallbacks = 0;     // ... counted (gps_profile_get "small_n_fallbacks")
+    int consec = 0;              // ... in a row; a launch that comes back whole clears it
+    int cooldown = 0;            // evaluations still to go launch by launch: 256 after the fourth give-up in a row ("small_n_cooldown")
+    // the evaluation under way
+    bool defer = false;          // gps_gpr_lml_grad asks the factorisation to leave its results on the device (dSmallOut) ...
+    bool pending = false;        // ... and it did: they come back with the gradient's, in one copy
+    bool valid = false;          // the launch reduced sum log L_ii and sum alpha^2 itself and they are on the host:
+    double slog = 0.0, ssq = 0.0;
+    bool linvT_stale = false;    // the resident factor's transposed block inverses have not been produced yet (gpr_ensure_linvT)
+  } small;
+  DevBuf dGemmWs{bufs}, dGemmCnt{bufs};   // slice partials + arrival counters of the GEMM tail split
+  DevBuf dGemvWs{bufs}, dGemvCnt{bufs};   // slice partials + arrival counters of the split transposed gemv (blas1.hip)
 };
 
 static inline int gps_fail(gps_handle_t h, int code, const std::string& msg) {
@@ -448,6 +467,7 @@ int gps_launch_kdiag(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, d
 // gps_launch_kdiag_vec writes Kdiag(X)[i] for the n resident points dX [n, d_all] to d_out [n] (any program; uses dFeat).
 // sum_out (optional): sum_i Kdiag_i on the host -- that one synchronises.
 bool gps_kdiag_is_const(const gps_kern_node_t* prog, int n_nodes);
+#define GPS_KDIAG_NOT_CONST_MSG "Kdiag is not constant for a kernel program with Linear / Polynomial: this path takes constant-Kdiag kernels only"
 int gps_launch_kdiag_vec(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n, i64 d_all, double* d_out,
                          double* sum_out);
 // grad.hip, grad_general.hip (what the two share among themselves: grad_common.hpp)

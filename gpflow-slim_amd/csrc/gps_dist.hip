@@ -488,20 +488,11 @@ extern "C" int gps_dist_solve_finish(gps_handle_t h, const gps_kern_node_t* prog
   if (!h || !var_out || h->dist_solve_n <= 0 || !h->dist_have_part_factor) return gps_fail(h, GPS_ERR_STATE, "gps_dist_solve_finish: nothing to finish");
   if (h->dist_r > 0 && !mean_out) return gps_fail(h, GPS_ERR_ARG, "gps_dist_solve_finish: mean_out missing");
   GPS_HIP(h, hipSetDevice(h->device));
-  const i64 np = h->dist_np, r = h->dist_r, n_new = h->dist_solve_n;
-  GPS_HIP(h, h->dMean.ensure((size_t)(n_new * (r > 0 ? r : 1) + n_new) * 8));
-  double* dmean = h->dMean.d();
-  double* dss = dmean + n_new * (r > 0 ? r : 1);
-  int rc = gps_launch_rowdot(h, h->dB.d(), np, n_new, np, h->dAlpha.d(), np, r, dmean, dss);
+  // (a per-point Kdiag -- Linear / Polynomial -- is not for this path: refused in the words of gps_launch_kdiag, as before)
+  if (!gps_kdiag_is_const(prog, n_nodes)) return gps_fail(h, GPS_ERR_UNSUPPORTED, GPS_KDIAG_NOT_CONST_MSG);
+  const i64 n_new = h->dist_solve_n;
+  int rc = predict_finish(h, prog, n_nodes, h->dB.d(), h->dist_np, gps_pad(n_new), n_new, h->dist_r, /*full_cov*/ 0, mean_out, var_out);
   if (rc) return rc;
-  double kd = 0.0;
-  rc = gps_launch_kdiag(h, prog, n_nodes, &kd);
-  if (rc) return rc;
-  GPS_HIP(h, h->dVar.ensure((size_t)n_new * 8));
-  rc = gps_launch_var_finish(h, h->dVar.d(), nullptr, kd, dss, n_new);
-  if (rc) return rc;
-  GPS_HIP(h, hipMemcpyAsync(var_out, h->dVar.p, (size_t)n_new * 8, hipMemcpyDeviceToHost, h->stream));
-  if (r > 0) GPS_HIP(h, hipMemcpyAsync(mean_out, dmean, (size_t)n_new * r * 8, hipMemcpyDeviceToHost, h->stream));
   GPS_HIP(h, hipStreamSynchronize(h->stream));
   h->dist_solve_n = 0;
   return GPS_OK;
@@ -542,20 +533,13 @@ extern "C" int gps_dist_predict(gps_handle_t h, const gps_kern_node_t* prog, int
   return GPS_OK;
 }
 
-// device memory the handle holds right now: every growable buffer, the comm buffers of the all-native driver (gps_dist_lml /
-// gps_dist_predict allocate them on the handle) included; comm buffers a caller brings (gps_dist_set_comm_bufs) are its own
+// device memory the handle holds right now: every buffer of its registry (gps_common.hpp: DevBuf), the comm buffers of the
+// all-native driver (gps_dist_lml / gps_dist_predict allocate them on the handle) included; comm buffers a caller brings
+// (gps_dist_set_comm_bufs) are its own
 extern "C" int gps_device_bytes(gps_handle_t h, int64_t* bytes) {
   if (!h || !bytes) return GPS_ERR_ARG;
-  DevBuf* bufs[] = {&h->dX, &h->dK, &h->dLinv, &h->dAlpha, &h->dFeat, &h->dFeat2, &h->dProg,
-                    &h->dXnew, &h->dB, &h->dMean, &h->dVar, &h->dTmp, &h->dTmp2, &h->dTmp3, &h->dA, &h->dY,
-                    &h->dKinv, &h->dNkn, &h->dS1, &h->dS2, &h->dS3, &h->dS4, &h->dGemvWs, &h->dGemvCnt, &h->dGemmWs, &h->dGemmCnt,
-                    &h->dDistScal, &h->dGradSums, &h->dSmallOut, &h->dFeatG, &h->dG1, &h->dG2, &h->dG3, &h->dG4, &h->dWave, &h->dInfo, &h->dScal, &h->dWaveCtl, &h->dLaFlags,
-                    &h->dBlkCond, &h->dStage, &h->dWbig, &h->dWtbig, &h->dBigT, &h->dB2, &h->dSmallSync,
-                    &h->dDistComm[0], &h->dDistComm[1], &h->dDistComm[2], &h->dDistZ, &h->dDistPT};
   int64_t tot = 0;
-  for (DevBuf* b : bufs) tot += (int64_t)b->cap;
+  for (const DevBuf* b : h->bufs) tot += (int64_t)b->cap;
   *bytes = tot;
   return GPS_OK;
 }
-
-

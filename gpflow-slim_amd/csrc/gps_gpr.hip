@@ -137,79 +137,63 @@ static int ensure_hres(gps_handle_t h) {
   return GPS_OK;
 }
 
+// what a cooperative launch that came back whole hands over: res = {sum log L_ii, sum alpha^2, info, ...} on the host
+static void small_accept(gps_handle_t h, const double* res, int* info) {
+  const int v = (int)res[2];
+  if (info) *info = (v == INT_MAX) ? 0 : v;
+  h->small.valid = true; h->small.slog = res[0]; h->small.ssq = res[1];
+  h->have_factor = (info == nullptr) || (*info == 0);
+  h->small.consec = 0;
+}
+
 // the transposed block inverses of the resident GPR factor, if the factorisation left them out (the one-launch small path)
 static int gpr_ensure_linvT(gps_handle_t h) {
-  if (!h->gpr_linvT_stale) return GPS_OK;
+  if (!h->small.linvT_stale) return GPS_OK;
   const i64 nb = h->npad / GPS_TILE;
   int rc = gps_launch_transpose_blocks(h, h->dLinv.d(), h->dLinv.d() + nb * GPS_TILE * GPS_TILE, nb);
-  if (rc == GPS_OK) h->gpr_linvT_stale = false;
+  if (rc == GPS_OK) h->small.linvT_stale = false;
   return rc;
 }
 
-// K + noise I -> L, alpha.  Records ev[0..3].
-static int gpr_factor(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double noise_var,
-                      const double* resid, i64 r, int* info) {
-  if (h->n <= 0) return gps_fail(h, GPS_ERR_STATE, "gps_gpr_set_data has not been called");
-  if (r < 0 || (r > 0 && !resid)) return gps_fail(h, GPS_ERR_ARG, "resid missing");
-  const i64 n = h->n, np = h->npad;
-  h->have_factor = false; h->factor_gen++; h->dist_have_part_factor = false;
-  {
-    // leaves refined or not: from the bound cond(K + noise I) <= (N Kdiag + noise) / noise (gps_gpr_needs_refine)
-    // (Linear / Polynomial: Kdiag depends on the point; sum_i Kdiag_i is the same trace bound on lambda_max as N Kdiag)
-    double kd = 0.0;
-    int rck;
-    if (gps_kdiag_is_const(prog, n_nodes)) rck = gps_launch_kdiag(h, prog, n_nodes, &kd);
-    else {
-      GPS_HIP(h, h->dKdiag.ensure((size_t)h->n * 8));
-      double tr = 0.0;
-      rck = gps_launch_kdiag_vec(h, prog, n_nodes, h->dX.d(), h->n, h->d_all, h->dKdiag.d(), &tr);
-      kd = tr / (double)h->n;
-    }
-    if (rck) return rck;
-    h->refine_now = gps_gpr_needs_refine(h, noise_var, kd, h->n);
-    h->factor_refine = h->refine_now;
+// ---- the factorisation K + noise I -> L, alpha, in pieces ------------------------------------------------------
+// What a factorisation is going to do, decided (gpr_plan) before anything of it is enqueued.
+struct FactorPlan {
+  bool aug = false;      // (Y - m)^T rides through the factorisation as 128 more rows under K
+  bool small = false;    // one cooperative launch (small_n.hip) instead of launch by launch
+  SmallKgen kg;          // ... which builds K itself (kg.on): no kernel-matrix launches at all
+};
+static int gpr_plan(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double noise_var, i64 r, FactorPlan* p) {
+  const i64 np = h->npad;
+  // leaves refined or not: from the bound cond(K + noise I) <= (N Kdiag + noise) / noise (gps_gpr_needs_refine)
+  // (Linear / Polynomial: Kdiag depends on the point; sum_i Kdiag_i is the same trace bound on lambda_max as N Kdiag)
+  double kd = 0.0;
+  int rc;
+  if (gps_kdiag_is_const(prog, n_nodes)) rc = gps_launch_kdiag(h, prog, n_nodes, &kd);
+  else {
+    GPS_HIP(h, h->dKdiag.ensure((size_t)h->n * 8));
+    double tr = 0.0;
+    rc = gps_launch_kdiag_vec(h, prog, n_nodes, h->dX.d(), h->n, h->d_all, h->dKdiag.d(), &tr);
+    kd = tr / (double)h->n;
   }
-  GPS_HIP(h, hipEventRecord(h->ev[0], h->stream));
+  if (rc) return rc;
+  h->refine_now = gps_gpr_needs_refine(h, noise_var, kd, h->n);
+  h->factor_refine = h->refine_now;
   // Augmented rows (blocked.hpp::potrf_rec; option "gpr_aug_rows"): (Y - m)^T stored as 128 more rows under K rides
   // through the factorisation, which leaves alpha^T = (L^-1 (Y - m))^T there (densities.py:82) -- no forward-substitution
-  // pass (~4 N / 128 launch-latency-bound kernels).  Same-process A/B on MI355X: N = 2048 / 4096 / 8192 / 12288:
-  // -9 / -10 / -4.4 / -3.8 %; from N = 16384 on it loses (+0.9 %, N = 32768 +1.6 %): the extra tile row breaks the
-  // power-of-two tile counts of the big launches, whose whole rounds of 512 workgroup slots matter more than the 3 ms
-  // of trsv.  Against the one-launch wavefront substitution (trsv_wave.hip: 0.28 ms at N = 8192, 1.2 ms at 32768, where the
-  // recursive one took 0.62 / 3.2 ms) the augmented rows still win up to N = 4096 (-3 %), lose from 8192 on (+1.5 %) and
-  // tie at 12288.  Hence automatic (-1): on below 6200 points.  (The block-column multi-GPU path always uses it.)
-  // (The recursive substitution issued block by block behind the factorisation on a stream of its own was measured far worse
-  // still -- round 2, docs/LAB_NOTES.md -- and is gone.)
-  const bool aug = r > 0 && r <= GPS_TILE && (h->gpr_aug_rows > 0 || (h->gpr_aug_rows < 0 && np < 6200));
-  GPS_HIP(h, h->dK.ensure((size_t)(np + GPS_TILE) * np * 8));
-  double* const dAug = h->dK.d() + np * np;
+  // pass.  Automatic (-1): on below 6200 points, where it beats the one-launch wavefront substitution; above, the extra tile
+  // row costs the big GEMM launches more (the A/B numbers: docs/LAB_NOTES.md, "Augmented rows").
+  p->aug = r > 0 && r <= GPS_TILE && (h->gpr_aug_rows > 0 || (h->gpr_aug_rows < 0 && np < 6200));
   // Small problems (the reference's own size: examples/gpr.py, N ~ 455): the whole factorisation, alpha and the two
   // reductions of the likelihood as ONE cooperative launch (small_n.hip) -- three launches per evaluation with the two of the
   // kernel-matrix build, no memset, no transposition, one 32-byte read-back.  Not for refined leaves (ill-conditioned K).
-  h->small_valid = false;
   // (up to small_n_max padded points; above seven blocks the launch draws all its work from a queue)
-  bool small = h->small_n > 0 && aug && np <= h->small_n_max && np <= 4096 && r <= 16 && !h->refine_now &&
-               h->prop.multiProcessorCount >= 160;
-  if (small && h->small_cooldown > 0) { --h->small_cooldown; small = false; }      // (back-off after give-ups in a row: small_gave_up)
-  // residual, transposed to [r][np] and zero padded
-  if (r > 0) {
-    GPS_HIP(h, h->dAlpha.ensure((size_t)r * np * 8));
-    GPS_HIP(h, h->dTmp2.ensure((size_t)n * r * 8));
-    // (through a pinned slot when small: a copy from pageable memory blocks the host for its staging)
-    if ((size_t)n * r * 8 <= (size_t)h->resid_ring_max) GPS_HIP(h, h->ring.upload(h->dTmp2.p, resid, (size_t)n * r * 8, h->stream));
-    else GPS_HIP(h, hipMemcpyAsync(h->dTmp2.p, resid, (size_t)n * r * 8, hipMemcpyHostToDevice, h->stream));
-    if (!small) {
-      double* dst = aug ? dAug : h->dAlpha.d();
-      GPS_HIP(h, hipMemsetAsync(dst, 0, (size_t)(aug ? GPS_TILE : r) * np * 8, h->stream));
-      int rc0 = gps_launch_transpose(h, h->dTmp2.d(), r, n, r, dst, np);
-      if (rc0) return rc0;
-    }
-  }
-  // (small path, one stationary primitive: the cooperative launch generates K itself -- no kernel-matrix launches at all)
-  SmallKgen kg;
+  p->small = h->small.on > 0 && p->aug && np <= h->small_n_max && r <= 16 && !h->refine_now && h->prop.multiProcessorCount >= 160;
+  if (p->small && h->small.cooldown > 0) { --h->small.cooldown; p->small = false; }      // (back-off after give-ups in a row: small_gave_up)
+  // one stationary primitive: the cooperative launch generates K itself
   const int op0 = n_nodes == 1 ? prog[0].op : -1;
-  if (small && h->small_n >= 1 && (op0 == GPS_K_RBF || op0 == GPS_K_MATERN12 || op0 == GPS_K_MATERN32 || op0 == GPS_K_MATERN52 ||
-      op0 == GPS_K_EXPONENTIAL) && prog[0].n_dims >= 1 && prog[0].n_dims <= 16 && prog[0].variance > 0.0) {
+  SmallKgen& kg = p->kg;
+  if (p->small && (op0 == GPS_K_RBF || op0 == GPS_K_MATERN12 || op0 == GPS_K_MATERN32 || op0 == GPS_K_MATERN52 || op0 == GPS_K_EXPONENTIAL) &&
+      prog[0].n_dims >= 1 && prog[0].n_dims <= 16 && prog[0].variance > 0.0) {
     kg.on = 1; kg.op = op0; kg.X = h->dX.d(); kg.d_all = (int)h->d_all; kg.nd = prog[0].n_dims; kg.variance = prog[0].variance; kg.noise = noise_var;
     for (int d = 0; d < 16; ++d) { kg.dims[d] = 0; kg.inv_ls[d] = 0.0; }
     for (int d = 0; d < kg.nd; ++d) {
@@ -217,71 +201,38 @@ static int gpr_factor(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, 
       if (kg.dims[d] < 0 || kg.dims[d] >= kg.d_all || !(prog[0].lengthscales[d] > 0.0)) kg.on = 0;       // (left to the ordinary build and its error text)
     }
   }
-  int rc = GPS_OK;
-  if (!kg.on) {
-    rc = gps_launch_kmat(h, prog, n_nodes, h->dX.d(), n, nullptr, n, h->d_all, noise_var, h->dK.d(), np,
-                         np, np, /*lower_only*/ 1, /*identity_pad*/ 1);
-    if (rc) return rc;
-  }
-  GPS_HIP(h, hipEventRecord(h->ev[1], h->stream));
+  return GPS_OK;
+}
+
+// the residual [n][r] from the host into dTmp2 ...
+static int gpr_upload_resid(gps_handle_t h, const double* resid, i64 r) {
+  const size_t bytes = (size_t)h->n * r * 8;
+  GPS_HIP(h, h->dAlpha.ensure((size_t)r * h->npad * 8));
+  GPS_HIP(h, h->dTmp2.ensure(bytes));
+  // (through a pinned slot when small: a copy from pageable memory blocks the host for its staging)
+  if (bytes <= (size_t)h->resid_ring_max) GPS_HIP(h, h->ring.upload(h->dTmp2.p, resid, bytes, h->stream));
+  else GPS_HIP(h, hipMemcpyAsync(h->dTmp2.p, resid, bytes, hipMemcpyHostToDevice, h->stream));
+  return GPS_OK;
+}
+
+// ... and from there, as [r][np] and zero padded, to where the launch-by-launch piece reads it: the augmented rows of dK, or dAlpha
+static int gpr_place_resid(gps_handle_t h, i64 r, bool aug) {
+  const i64 n = h->n, np = h->npad;
+  double* dst = aug ? h->dK.d() + np * np : h->dAlpha.d();
+  GPS_HIP(h, hipMemsetAsync(dst, 0, (size_t)(aug ? GPS_TILE : r) * np * 8, h->stream));
+  return gps_launch_transpose(h, h->dTmp2.d(), r, n, r, dst, np);
+}
+static int gpr_build_K(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double noise_var) {
+  return gps_launch_kmat(h, prog, n_nodes, h->dX.d(), h->n, nullptr, h->n, h->d_all, noise_var, h->dK.d(), h->npad,
+                         h->npad, h->npad, /*lower_only*/ 1, /*identity_pad*/ 1);
+}
+
+// Launch by launch: K (and the augmented rows) in dK -> L, the block inverses, alpha.  Records ev[2]; synchronises (read_info).
+static int gpr_factor_blocked(gps_handle_t h, bool aug, i64 r, int* info) {
+  const i64 np = h->npad;
   int* d_info = (int*)h->dInfo.p;
-  if (small) {
-    double* d_res = h->dScal.d() + 256;
-    if (h->small_defer) {                 // (gps_gpr_lml_grad: with everything else it reads back, in one buffer)
-      GPS_HIP(h, h->dSmallOut.ensure((size_t)(5 + GPS_GRAD_SUMS + n * r) * 8));
-      d_res = h->dSmallOut.d();
-    }
-    double* linv = h->dLinv.d();
-    // (the transposed block inverses are not on the path of the likelihood: whoever needs them afterwards -- the gradient,
-    // a prediction from this factor -- has them produced by one batched launch then: gpr_ensure_linvT)
-    if (h->plain_linv == linv) h->plain_linv = nullptr;        // (these block inverses are produced anew, not through HipOps::potrf_base)
-    rc = gps_launch_small_factor(h, h->dK.d(), np, linv, nullptr, h->dTmp2.d(), n, r, d_info, d_res, h->dAlpha.d(), np, r, &kg);
-    h->gpr_linvT_stale = true;
-    if (rc == GPS_OK) {
-      GPS_HIP(h, hipEventRecord(h->ev[2], h->stream));
-      h->r = r;
-      if (h->small_defer) { h->small_pending = true; return GPS_OK; }      // (gps_gpr_lml_grad reads the results back itself, later)
-      int rch = ensure_hres(h);
-      if (rch) return rch;
-      double* res = (double*)h->hRes;
-      res[3] = 1.0;
-      GPS_HIP(h, hipMemcpyAsync(res, d_res, 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      GPS_HIP(h, hipStreamSynchronize(h->stream));
-      if (res[3] == 0.0) {
-        const int v = (int)res[2];
-        if (info) *info = (v == INT_MAX) ? 0 : v;
-        h->r = r;
-        h->small_valid = true; h->small_slog = res[0]; h->small_ssq = res[1];
-        h->have_factor = (info == nullptr) || (*info == 0);
-        h->small_consec = 0;
-        return GPS_OK;
-      }
-      // a bounded wait of the launch ran out (never seen; e.g. several such launches of one process interleaved on the GPU
-      // so that none was fully resident): counters back to zero, this evaluation again launch by launch
-      small_gave_up(h);
-      rc = gps_small_factor_reset(h);
-      if (rc) return rc;
-      const int saved = h->small_n;
-      h->small_n = 0;
-      rc = gpr_factor(h, prog, n_nodes, noise_var, resid, r, info);
-      h->small_n = saved;
-      return rc;
-    }
-    if (rc != GPS_ERR_UNSUPPORTED) return rc;
-    // (not a shape for that path after all: K, if the launch was to generate it, and the residual still have to go where the
-    // launch-by-launch path expects them)
-    if (kg.on) {
-      rc = gps_launch_kmat(h, prog, n_nodes, h->dX.d(), n, nullptr, n, h->d_all, noise_var, h->dK.d(), np, np, np, 1, 1);
-      if (rc) return rc;
-    }
-    if (r > 0) {
-      GPS_HIP(h, hipMemsetAsync(dAug, 0, (size_t)GPS_TILE * np * 8, h->stream));
-      rc = gps_launch_transpose(h, h->dTmp2.d(), r, n, r, dAug, np);
-      if (rc) return rc;
-    }
-  }
-  h->gpr_linvT_stale = false;
-  rc = gps_launch_fill_info(h, d_info, INT_MAX);
+  h->small.linvT_stale = false;
+  int rc = gps_launch_fill_info(h, d_info, INT_MAX);
   if (rc) return rc;
   HipOps ops = factor_ops(h, h->dLinv.d(), np, d_info);
   {
@@ -296,10 +247,9 @@ static int gpr_factor(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, 
     if (rc) return rc;
     if (h->refine_now) { rc = classify_blocks(h, ops, h->dK.d(), np, np); if (rc) return rc; }      // (low noise: the predictions' solves)
   }
-  Blocked<HipOps> bl(ops);
   GPS_HIP(h, hipEventRecord(h->ev[2], h->stream));
   if (aug) {
-    GPS_HIP(h, hipMemcpyAsync(h->dAlpha.p, dAug, (size_t)r * np * 8, hipMemcpyDeviceToDevice, h->stream));
+    GPS_HIP(h, hipMemcpyAsync(h->dAlpha.p, h->dK.d() + np * np, (size_t)r * np * 8, hipMemcpyDeviceToDevice, h->stream));
   } else if (r > 0) {
     rc = trsv_forward(h, ops, h->dK.d(), np, np, h->dAlpha.d(), np, r);
     if (rc) return rc;
@@ -309,6 +259,87 @@ static int gpr_factor(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, 
   if (rc) return rc;
   h->have_factor = (info == nullptr) || (*info == 0);
   return GPS_OK;
+}
+
+// The one cooperative launch: the residual in dTmp2, K in dK unless the launch builds it (p.kg.on).  Records ev[2]; reads its
+// results back and synchronises -- or, with small.defer, leaves them in dSmallOut for gps_gpr_lml_grad (small.pending).
+// GPS_ERR_UNSUPPORTED: not a shape for the launch after all, nothing was enqueued.  *gave_up: a bounded wait of the launch ran
+// out (never seen; e.g. several such launches of one process interleaved on the GPU so that none was fully resident).
+static int gpr_factor_small(gps_handle_t h, const FactorPlan& p, i64 r, int* info, bool* gave_up) {
+  const i64 n = h->n, np = h->npad;
+  double* d_res = h->dScal.d() + 256;
+  if (h->small.defer) {
+    GPS_HIP(h, h->dSmallOut.ensure((size_t)(5 + GPS_GRAD_SUMS + n * r) * 8));
+    d_res = h->dSmallOut.d();
+  }
+  double* linv = h->dLinv.d();
+  // (the transposed block inverses are not on the path of the likelihood: whoever needs them afterwards -- the gradient,
+  // a prediction from this factor -- has them produced by one batched launch then: gpr_ensure_linvT)
+  if (h->plain_linv == linv) h->plain_linv = nullptr;        // (these block inverses are produced anew, not through HipOps::potrf_base)
+  int rc = gps_launch_small_factor(h, h->dK.d(), np, linv, nullptr, h->dTmp2.d(), n, r, (int*)h->dInfo.p, d_res, h->dAlpha.d(), np, r, &p.kg);
+  h->small.linvT_stale = true;
+  if (rc) return rc;
+  GPS_HIP(h, hipEventRecord(h->ev[2], h->stream));
+  h->r = r;
+  if (h->small.defer) { h->small.pending = true; return GPS_OK; }
+  rc = ensure_hres(h);
+  if (rc) return rc;
+  double* res = (double*)h->hRes;
+  res[3] = 1.0;
+  GPS_HIP(h, hipMemcpyAsync(res, d_res, 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipStreamSynchronize(h->stream));
+  if (res[3] != 0.0) { *gave_up = true; return GPS_OK; }
+  small_accept(h, res, info);
+  return GPS_OK;
+}
+
+// A cooperative launch gave up during the factorisation (small_gave_up: gps_ops.hpp): the residual once more (the gradient's
+// partial sums may have gone over dTmp2 since) into the augmented rows, which the small path always has, K again (the launch
+// has overwritten part of it), and the launch-by-launch piece.  Records ev[0..2] anew.
+static int gpr_small_refactor(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double noise_var, const double* resid, i64 r,
+                              int* info) {
+  int rc = small_gave_up(h);
+  if (rc) return rc;
+  GPS_HIP(h, hipEventRecord(h->ev[0], h->stream));
+  rc = gpr_upload_resid(h, resid, r);
+  if (!rc) rc = gpr_place_resid(h, r, /*aug*/ true);
+  if (!rc) rc = gpr_build_K(h, prog, n_nodes, noise_var);
+  if (rc) return rc;
+  GPS_HIP(h, hipEventRecord(h->ev[1], h->stream));
+  return gpr_factor_blocked(h, /*aug*/ true, r, info);
+}
+
+// K + noise I -> L, alpha.  Records ev[0..2].
+static int gpr_factor(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double noise_var,
+                      const double* resid, i64 r, int* info) {
+  if (h->n <= 0) return gps_fail(h, GPS_ERR_STATE, "gps_gpr_set_data has not been called");
+  if (r < 0 || (r > 0 && !resid)) return gps_fail(h, GPS_ERR_ARG, "resid missing");
+  const i64 np = h->npad;
+  h->have_factor = false; h->factor_gen++; h->dist_have_part_factor = false;
+  h->small.valid = false;
+  FactorPlan p;
+  int rc = gpr_plan(h, prog, n_nodes, noise_var, r, &p);
+  if (rc) return rc;
+  GPS_HIP(h, hipEventRecord(h->ev[0], h->stream));
+  GPS_HIP(h, h->dK.ensure((size_t)(np + GPS_TILE) * np * 8));
+  if (r > 0) {
+    rc = gpr_upload_resid(h, resid, r);
+    if (!rc && !p.small) rc = gpr_place_resid(h, r, p.aug);        // (the small launch transposes it itself)
+    if (rc) return rc;
+  }
+  if (!p.kg.on) { rc = gpr_build_K(h, prog, n_nodes, noise_var); if (rc) return rc; }
+  GPS_HIP(h, hipEventRecord(h->ev[1], h->stream));
+  if (p.small) {
+    bool gave_up = false;
+    rc = gpr_factor_small(h, p, r, info, &gave_up);
+    if (gave_up) return gpr_small_refactor(h, prog, n_nodes, noise_var, resid, r, info);
+    if (rc != GPS_ERR_UNSUPPORTED) return rc;
+    // K, if the launch was to generate it, and the residual still have to go where the launch-by-launch piece expects them
+    if (p.kg.on) { rc = gpr_build_K(h, prog, n_nodes, noise_var); if (rc) return rc; }
+    rc = gpr_place_resid(h, r, /*aug*/ true);
+    if (rc) return rc;
+  }
+  return gpr_factor_blocked(h, p.aug, r, info);
 }
 
 extern "C" int gps_gpr_lml(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double noise_var,
@@ -329,12 +360,12 @@ static int gpr_lml_finish(gps_handle_t h, i64 r, double* lml) {
   int rc;
   const i64 n = h->n, np = h->npad;
   double slog = 0.0, ssq = 0.0;
-  if (h->small_valid) {
-    // (the one-launch factorisation of a small problem has reduced both sums itself and they are on the host already)
-    slog = h->small_slog; ssq = h->small_ssq;
-    h->ev3_is_ev2 = true;
+  // (the one-launch factorisation of a small problem has reduced both sums itself and they are on the host already: no
+  // reduction stage, ev[3] is not recorded)
+  const bool reduced = h->small.valid;
+  if (reduced) {
+    slog = h->small.slog; ssq = h->small.ssq;
   } else {
-    h->ev3_is_ev2 = false;
     double* part = h->dScal.d();
     rc = gps_launch_lml_reduce(h, h->dK.d(), np, n, h->dAlpha.d(), np, r, part);
     if (rc) return rc;
@@ -348,14 +379,60 @@ static int gpr_lml_finish(gps_handle_t h, i64 r, double* lml) {
   *lml = -0.5 * (double)n * (double)r * log(2.0 * M_PI) - (double)r * slog - 0.5 * ssq;
   stage_time(h, 0, 1, &h->stage_ms[0]);
   stage_time(h, 1, 2, &h->stage_ms[1]);
-  if (h->ev3_is_ev2) h->stage_ms[2] = 0.0; else stage_time(h, 2, 3, &h->stage_ms[2]);
+  if (reduced) h->stage_ms[2] = 0.0; else stage_time(h, 2, 3, &h->stage_ms[2]);
   h->stage_ms[3] = 0.0;
-  stage_time(h, 0, h->ev3_is_ev2 ? 2 : 3, &h->stage_ms[4]);
+  stage_time(h, 0, reduced ? 2 : 3, &h->stage_ms[4]);
   return GPS_OK;
 }
 
-// What follows the (not yet read back) one-launch factorisation of a small problem in gps_gpr_lml_grad.  *done = false: a
-// bounded wait gave up, nothing of the outputs is valid.
+// ---- the gradient: K_y^-1 (lower triangle) into dKinv and A = K_y^-1 resid into dA, from the resident factor ----------
+static int gpr_kinv_buffers(gps_handle_t h, i64 r) {
+  const i64 np = h->npad;
+  GPS_HIP(h, h->dA.ensure((size_t)r * np * 8));
+  GPS_HIP(h, h->dY.ensure((size_t)np * np * 8));
+  GPS_HIP(h, h->dKinv.ensure((size_t)np * np * 8));
+  return GPS_OK;
+}
+// After the one-launch factorisation of a small problem: one more cooperative launch (small_n.hip) instead of ~25.  d_abort
+// (device) is non-zero afterwards if a bounded wait of it ran out; d_AT (optional): A once more as [n][r].
+static int gpr_kinv_small(gps_handle_t h, i64 r, double* d_abort, double* d_AT) {
+  int rc = gpr_kinv_buffers(h, r);
+  if (rc) return rc;
+  return gps_launch_small_inverse(h, h->dK.d(), h->npad, h->dLinv.d(), h->dAlpha.d(), r, h->dY.d(), h->dKinv.d(), h->dA.d(), d_abort, d_AT, h->n);
+}
+// Launch by launch: the backward substitution and the two recursions.
+static int gpr_kinv_blocked(gps_handle_t h, i64 r) {
+  const i64 np = h->npad;
+  int rc = gpr_kinv_buffers(h, r);
+  if (!rc) rc = gpr_ensure_linvT(h);
+  if (rc) return rc;
+  HipOps ops = factor_ops(h, h->dLinv.d(), np, (int*)h->dInfo.p);
+  Blocked<HipOps> bl(ops);
+  // A = K_y^-1 resid = L^-T (L^-1 resid)
+  GPS_HIP(h, hipMemcpyAsync(h->dA.p, h->dAlpha.p, (size_t)r * np * 8, hipMemcpyDeviceToDevice, h->stream));
+  rc = trsv_backward(h, ops, h->dK.d(), np, np, h->dA.d(), np, r);
+  if (rc) return rc;
+  // K_y^-1 = L^-T L^-1
+  rc = bl.inv_t_rec(h->dK.d(), np, np, 0, h->dY.d(), np);
+  if (rc) return rc;
+  return bl.lauum_rec(h->dY.d(), np, np, h->dKinv.d(), np);
+}
+// the gradient from dKinv and dA, read back (synchronises), and K_y^-1 resid as [n][r] on its way to the host
+static int gpr_grad_readback(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 r, double* grad_slots, double* grad_noise,
+                             double* kinv_resid) {
+  const i64 n = h->n, np = h->npad;
+  int rc = gps_launch_grad(h, prog, n_nodes, h->dX.d(), n, h->d_all, np, h->dKinv.d(), np, h->dA.d(), np, r, nullptr, grad_slots, grad_noise);
+  if (rc || !kinv_resid) return rc;
+  GPS_HIP(h, h->dTmp2.ensure((size_t)n * r * 8));
+  rc = gps_launch_transpose(h, h->dA.d(), np, r, n, h->dTmp2.d(), r);
+  if (rc) return rc;
+  GPS_HIP(h, hipMemcpyAsync(kinv_resid, h->dTmp2.p, (size_t)n * r * 8, hipMemcpyDeviceToHost, h->stream));
+  return GPS_OK;
+}
+
+// What follows the (not yet read back) one-launch factorisation of a small problem in gps_gpr_lml_grad: the inverse and the
+// gradient sums enqueued behind it, and everything the host needs back in one pinned copy behind ONE synchronisation.
+// *done = false: a bounded wait of one of the two cooperative launches gave up, nothing of the outputs is valid.
 static int gpr_small_grad_tail(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 r, double* lml, double* grad_slots,
                                double* grad_noise, double* kinv_resid, int* info, bool* done) {
   const i64 n = h->n, np = h->npad;
@@ -363,43 +440,34 @@ static int gpr_small_grad_tail(gps_handle_t h, const gps_kern_node_t* prog, int 
   int rc = ensure_hres(h);
   if (rc) return rc;
   GPS_HIP(h, hipEventRecord(h->ev[5], h->stream));
-  GPS_HIP(h, h->dA.ensure((size_t)r * np * 8));
-  GPS_HIP(h, h->dY.ensure((size_t)np * np * 8));
-  GPS_HIP(h, h->dKinv.ensure((size_t)np * np * 8));
   // dSmallOut: [0..3] the factorisation's results (already on their way), [4] the inverse launch's abort word, [5 ..] the
   // gradient sums, then K^-1 resid as [n][r] -- one copy brings all of it back
   double* d_res = h->dSmallOut.d();
-  double* d_kr = d_res + 5 + GPS_GRAD_SUMS;
-  rc = gps_launch_small_inverse(h, h->dK.d(), np, h->dLinv.d(), h->dAlpha.d(), r, h->dY.d(), h->dKinv.d(), h->dA.d(), d_res + 4,
-                                kinv_resid ? d_kr : nullptr, n);
+  rc = gpr_kinv_small(h, r, d_res + 4, kinv_resid ? d_res + 5 + GPS_GRAD_SUMS : nullptr);
   if (rc) return rc;                   // (the factorisation took this shape: so does the inverse)
   // (launching the gradient kernel's features in front of the factorisation instead -- the first half of gps_grad_enqueue -- was measured: no gain)
   GradPost post;
   rc = gps_grad_enqueue(h, prog, n_nodes, h->dX.d(), n, h->d_all, np, h->dKinv.d(), np, h->dA.d(), np, r, d_res + 5, &post);
   if (rc) return rc;
   double* res = (double*)h->hRes;
-  double* kr = res + 5 + GPS_GRAD_SUMS;
   res[3] = 1.0; res[4] = 1.0;
   GPS_HIP(h, hipMemcpyAsync(res, d_res, (size_t)(5 + GPS_GRAD_SUMS + (kinv_resid ? n * r : 0)) * 8, hipMemcpyDeviceToHost, h->stream));
   GPS_HIP(h, hipEventRecord(h->ev[6], h->stream));
   GPS_HIP(h, hipStreamSynchronize(h->stream));
   if (res[3] != 0.0 || res[4] != 0.0) return GPS_OK;
   *done = true;
-  h->small_consec = 0;
-  const int v = (int)res[2];
-  *info = (v == INT_MAX) ? 0 : v;
-  h->have_factor = (*info == 0);
-  h->small_valid = true; h->small_slog = res[0]; h->small_ssq = res[1];
+  small_accept(h, res, info);
   if (*info) return GPS_OK;            // not positive definite: outputs undefined
   rc = gpr_lml_finish(h, r, lml);
   if (rc) return rc;
   stage_time(h, 5, 6, &h->stage_ms[3]);
   gps_grad_finish(post, res + 5, grad_slots, grad_noise);
-  if (kinv_resid) memcpy(kinv_resid, kr, (size_t)n * r * 8);
+  if (kinv_resid) memcpy(kinv_resid, res + 5 + GPS_GRAD_SUMS, (size_t)n * r * 8);
   return GPS_OK;
 }
 
 // LML and its gradient: d/d(kernel parameter slots), d/d(noise variance), d/d(resid) = -K_y^-1 resid ... see header
+//   factor  ->  K_y^-1 and A (one cooperative launch, or launch by launch)  ->  gradient  ->  read-back
 extern "C" int gps_gpr_lml_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double noise_var,
                                 const double* resid, int64_t r, double* lml, double* grad_slots,
                                 int n_slots_cap, int* n_slots_out, double* grad_noise, double* kinv_resid,
@@ -418,87 +486,50 @@ extern "C" int gps_gpr_lml_grad(gps_handle_t h, const gps_kern_node_t* prog, int
   int linfo = 0;
   // Small problems (the reference's own size: examples/gpr.py): factorisation, inverse and gradient sums are enqueued
   // back to back -- six launches -- and everything the host needs comes back in one pinned copy behind ONE synchronisation.
-  h->small_defer = h->small_n > 0 && r <= 16 && h->npad <= 2048 && h->npad <= h->small_n_max && gps_grad_is_simple(prog, n_nodes) && (!kinv_resid || (size_t)(5 + GPS_GRAD_SUMS + h->n * r) * 8 <= GPS_HRES_BYTES);
-  h->small_pending = false;
+  h->small.defer = h->small.on > 0 && r <= 16 && h->npad <= h->small_n_max && gps_grad_is_simple(prog, n_nodes) &&
+                   (!kinv_resid || (size_t)(5 + GPS_GRAD_SUMS + h->n * r) * 8 <= GPS_HRES_BYTES);
+  h->small.pending = false;
   rc = gpr_factor(h, prog, n_nodes, noise_var, resid, r, &linfo);
-  h->small_defer = false;
+  h->small.defer = false;
   if (rc) return rc;
-  if (h->small_pending) {
-    h->small_pending = false;
+  if (h->small.pending) {
+    h->small.pending = false;
     bool done = false;
     rc = gpr_small_grad_tail(h, prog, n_nodes, r, lml, grad_slots, grad_noise, kinv_resid, &linfo, &done);
     if (rc) return rc;
     if (done) { if (info) *info = linfo; return GPS_OK; }
-    // a bounded wait of one of the two cooperative launches ran out (never seen): this evaluation again, launch by launch
-    small_gave_up(h);
-    rc = gps_small_factor_reset(h);
-    if (rc) return rc;
-    const int saved = h->small_n;
-    h->small_n = 0;
-    rc = gpr_factor(h, prog, n_nodes, noise_var, resid, r, &linfo);
-    h->small_n = saved;
+    rc = gpr_small_refactor(h, prog, n_nodes, noise_var, resid, r, &linfo);
     if (rc) return rc;
   }
   if (info) *info = linfo;
   if (linfo) return GPS_OK;
   rc = gpr_lml_finish(h, r, lml);
   if (rc) return rc;
-  const i64 n = h->n, np = h->npad;
   GPS_HIP(h, hipEventRecord(h->ev[5], h->stream));
-  GPS_HIP(h, h->dA.ensure((size_t)r * np * 8));
-  GPS_HIP(h, h->dY.ensure((size_t)np * np * 8));
-  GPS_HIP(h, h->dKinv.ensure((size_t)np * np * 8));
-  // K_y^-1 (lower triangle) and A = K_y^-1 resid.  After the one-launch factorisation of a small problem: one more
-  // cooperative launch (small_n.hip) instead of ~25 (the two recursions and the backward substitution below)
-  bool small_inv = h->small_valid && h->small_n > 0;
-  double* d_res1 = h->dScal.d() + 260;
-  if (small_inv) {
-    rc = gps_launch_small_inverse(h, h->dK.d(), np, h->dLinv.d(), h->dAlpha.d(), r, h->dY.d(), h->dKinv.d(), h->dA.d(), d_res1);
-    if (rc == GPS_ERR_UNSUPPORTED) small_inv = false;
-    else if (rc) return rc;
+  if (h->small.valid && h->small.on > 0) {
+    double* d_abort = h->dScal.d() + 260;
+    rc = gpr_kinv_small(h, r, d_abort, nullptr);
+    if (rc == GPS_OK) {
+      rc = gpr_grad_readback(h, prog, n_nodes, r, grad_slots, grad_noise, kinv_resid);
+      if (rc) return rc;
+      // (the launch-by-launch path touches neither the info word nor a hand-over: the only thing to read back is whether a
+      // bounded wait of the cooperative launch ran out -- never seen -- and then the same again launch by launch, below)
+      double ab = 1.0;
+      GPS_HIP(h, hipMemcpyAsync(&ab, d_abort, 8, hipMemcpyDeviceToHost, h->stream));
+      GPS_HIP(h, hipStreamSynchronize(h->stream));
+      if (ab == 0.0) {
+        GPS_HIP(h, hipEventRecord(h->ev[6], h->stream));
+        GPS_HIP(h, hipEventSynchronize(h->ev[6]));
+        stage_time(h, 5, 6, &h->stage_ms[3]);
+        return GPS_OK;
+      }
+      rc = small_gave_up(h);           // (the redo is the fall-through into gpr_kinv_blocked and the gradient, below)
+      if (rc) return rc;
+    } else if (rc != GPS_ERR_UNSUPPORTED) return rc;
   }
-  for (int pass = 0; pass < 2; ++pass) {
-    if (!small_inv) {
-      rc = gpr_ensure_linvT(h);
-      if (rc) return rc;
-      HipOps ops = factor_ops(h, h->dLinv.d(), np, (int*)h->dInfo.p);
-      Blocked<HipOps> bl(ops);
-      // A = K_y^-1 resid = L^-T (L^-1 resid)
-      GPS_HIP(h, hipMemcpyAsync(h->dA.p, h->dAlpha.p, (size_t)r * np * 8, hipMemcpyDeviceToDevice, h->stream));
-      rc = trsv_backward(h, ops, h->dK.d(), np, np, h->dA.d(), np, r);
-      if (rc) return rc;
-      // K_y^-1 = L^-T L^-1
-      rc = bl.inv_t_rec(h->dK.d(), np, np, 0, h->dY.d(), np);
-      if (rc) return rc;
-      rc = bl.lauum_rec(h->dY.d(), np, np, h->dKinv.d(), np);
-      if (rc) return rc;
-    }
-    rc = gps_launch_grad(h, prog, n_nodes, h->dX.d(), n, h->d_all, np, h->dKinv.d(), np, h->dA.d(), np, r, nullptr,
-                         grad_slots, grad_noise);
-    if (rc) return rc;
-    if (kinv_resid) {
-      GPS_HIP(h, h->dTmp2.ensure((size_t)n * r * 8));
-      rc = gps_launch_transpose(h, h->dA.d(), np, r, n, h->dTmp2.d(), r);
-      if (rc) return rc;
-      GPS_HIP(h, hipMemcpyAsync(kinv_resid, h->dTmp2.p, (size_t)n * r * 8, hipMemcpyDeviceToHost, h->stream));
-    }
-    if (!small_inv) break;
-    // (the launch-by-launch path touches neither the info word nor a hand-over: the only thing to read back is whether a
-    // bounded wait of the cooperative launch ran out -- never seen -- and then the same again launch by launch)
-    double ab = 1.0;
-    GPS_HIP(h, hipMemcpyAsync(&ab, d_res1, 8, hipMemcpyDeviceToHost, h->stream));
-    GPS_HIP(h, hipStreamSynchronize(h->stream));
-    if (ab == 0.0) {
-      GPS_HIP(h, hipEventRecord(h->ev[6], h->stream));
-      GPS_HIP(h, hipEventSynchronize(h->ev[6]));
-      stage_time(h, 5, 6, &h->stage_ms[3]);
-      return GPS_OK;
-    }
-    small_gave_up(h);
-    rc = gps_small_factor_reset(h);
-    if (rc) return rc;
-    small_inv = false;
-  }
+  rc = gpr_kinv_blocked(h, r);
+  if (!rc) rc = gpr_grad_readback(h, prog, n_nodes, r, grad_slots, grad_noise, kinv_resid);
+  if (rc) return rc;
   GPS_HIP(h, hipEventRecord(h->ev[6], h->stream));
   // synchronises, and surfaces a backward wavefront substitution that gave up (its result would poison dA and every
   // gradient slot) as GPS_ERR_STATE for the retry above instead of leaving the counter for the next entry point
@@ -603,42 +634,8 @@ extern "C" int gps_gpr_predict(gps_handle_t h, const gps_kern_node_t* prog, int 
     rc = bl.trsm_rec(h->dK.d(), np, np, 0, h->dB.d(), np, nsp);
     if (rc) return rc;
   }
-  // fmean = A^T V ; sumsq = colsum(A*A)                          models/gpr.py:124,130
-  GPS_HIP(h, h->dMean.ensure((size_t)(n_new * (r > 0 ? r : 1) + n_new) * 8));
-  double* dmean = h->dMean.d();
-  double* dss = dmean + n_new * (r > 0 ? r : 1);
-  rc = gps_launch_rowdot(h, dAt, np, n_new, np, h->dAlpha.d(), np, r, dmean, dss);
+  rc = predict_finish(h, prog, n_nodes, dAt, np, nsp, n_new, r, full_cov, mean_out, var_out);
   if (rc) return rc;
-  if (!full_cov) {
-    // Kdiag: one number, or (Linear / Polynomial, kernels.py:507-510, 553-554) one per test point
-    double kd = 0.0;
-    const double* dkd = nullptr;
-    if (gps_kdiag_is_const(prog, n_nodes)) rc = gps_launch_kdiag(h, prog, n_nodes, &kd);
-    else {
-      GPS_HIP(h, h->dKdiag.ensure((size_t)n_new * 8));
-      rc = gps_launch_kdiag_vec(h, prog, n_nodes, h->dXnew.d(), n_new, d, h->dKdiag.d(), nullptr);
-      dkd = h->dKdiag.d();
-    }
-    if (rc) return rc;
-    GPS_HIP(h, h->dVar.ensure((size_t)n_new * 8));
-    rc = gps_launch_var_finish(h, h->dVar.d(), dkd, kd, dss, n_new);
-    if (rc) return rc;
-    GPS_HIP(h, hipMemcpyAsync(var_out, h->dVar.p, (size_t)n_new * 8, hipMemcpyDeviceToHost, h->stream));
-  } else {
-    // K(Xnew) - A^T A                                             models/gpr.py:126
-    GPS_HIP(h, h->dVar.ensure((size_t)nsp * nsp * 8));
-    rc = gps_launch_kmat(h, prog, n_nodes, h->dXnew.d(), n_new, nullptr, n_new, d, 0.0, h->dVar.d(), nsp, nsp,
-                         nsp, 0, 0);
-    if (rc) return rc;
-    rc = gps_launch_gemm_nt(h, 0, 0, nsp, nsp, np, dAt, np, dAt, np, h->dVar.d(), nsp);
-    if (rc) return rc;
-    GPS_HIP(h, h->dTmp2.ensure((size_t)n_new * n_new * 8));
-    rc = gps_launch_extract(h, h->dVar.d(), nsp, n_new, n_new, h->dTmp2.d(), n_new, 0);
-    if (rc) return rc;
-    GPS_HIP(h, hipMemcpyAsync(var_out, h->dTmp2.p, (size_t)n_new * n_new * 8, hipMemcpyDeviceToHost, h->stream));
-  }
-  if (r > 0)
-    GPS_HIP(h, hipMemcpyAsync(mean_out, dmean, (size_t)n_new * r * 8, hipMemcpyDeviceToHost, h->stream));
   GPS_HIP(h, hipEventRecord(h->ev[4], h->stream));
   GPS_HIP(h, hipStreamSynchronize(h->stream));
   stage_time(h, 0, 1, &h->stage_ms[0]);

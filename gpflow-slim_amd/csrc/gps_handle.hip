@@ -25,15 +25,9 @@ extern "C" int gps_create(int device_id, gps_handle_t* out) {
   return GPS_OK;
 }
 
-// every growable device buffer of the handle (the small fixed ones -- info word, look-ahead flags, pinned ring -- stay)
-static void release_work_buffers(gps_handle_t h, bool all) {
-  DevBuf* bufs[] = {&h->dX, &h->dK, &h->dLinv, &h->dAlpha, &h->dFeat, &h->dFeat2, &h->dProg,
-                    &h->dXnew, &h->dB, &h->dMean, &h->dVar, &h->dKdiag, &h->dTmp, &h->dTmp2, &h->dTmp3, &h->dA, &h->dY,
-                    &h->dKinv, &h->dNkn, &h->dS1, &h->dS2, &h->dS3, &h->dS4, &h->dGemvWs, &h->dGemvCnt, &h->dGemmWs, &h->dGemmCnt, &h->dBlkCond, &h->dStage, &h->dWbig, &h->dWtbig, &h->dBigT, &h->dB2,
-                    &h->dDistScal, &h->dGradSums, &h->dSmallOut, &h->dFeatG, &h->dG1, &h->dG2, &h->dG3, &h->dG4, &h->dLikIn, &h->dLikOut, &h->dLikPart, &h->dLikH, &h->dWave, &h->dDistComm[0], &h->dDistComm[1], &h->dDistComm[2]};
-  for (DevBuf* b : bufs) b->release();
-  if (all) h->dSmallSync.release();
-  if (all) { h->dInfo.release(); h->dScal.release(); h->dWaveCtl.release(); }      // (allocated by gps_create; every reduction writes there)
+// the handle's device buffers back to the allocator, by class (gps_common.hpp: DevBuf): the registry is the only list there is
+static void release_buffers(gps_handle_t h, bool persistent_too) {
+  for (DevBuf* b : h->bufs) if (persistent_too || b->cls == DevBuf::WORK) b->release();
 }
 
 // Hand the handle's device memory back to the allocator (K / L of a large problem is N^2 x 8 bytes and stays allocated
@@ -46,8 +40,8 @@ extern "C" int gps_release_buffers(gps_handle_t h) {
   if (h->side_stream) GPS_HIP(h, hipStreamSynchronize(h->side_stream));
   if (h->def_stream) GPS_HIP(h, hipStreamSynchronize(h->def_stream));
   gps_profile_collect(h);
-  release_work_buffers(h, false);
-  h->have_factor = false; h->factor_gen++; h->dist_have_part_factor = false; h->n = 0; h->npad = 0; h->r = 0;
+  release_buffers(h, false);
+  h->have_factor = false; h->factor_gen++; h->dist_have_part_factor = false; h->dist_grad_ready = false; h->n = 0; h->npad = 0; h->r = 0;
   h->dist_np = 0; h->dist_nb = 0;          // (a distributed factorisation must start over with gps_dist_begin)
   return GPS_OK;
 }
@@ -60,7 +54,6 @@ extern "C" int gps_destroy(gps_handle_t h) {
   gps_profile_collect(h);
   for (auto e : h->evt_pool) (void)hipEventDestroy(e);
   for (int i = 0; i < 8; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-  release_work_buffers(h, true);
   (void)hipStreamDestroy(h->ext_stream ? h->own_stream : h->stream);
   if (h->side_stream) { (void)hipStreamSynchronize(h->side_stream); (void)hipStreamDestroy(h->side_stream); }
   if (h->def_stream) { (void)hipStreamSynchronize(h->def_stream); (void)hipStreamDestroy(h->def_stream); }
@@ -69,7 +62,7 @@ extern "C" int gps_destroy(gps_handle_t h) {
   for (auto e : h->dist_events) (void)hipEventDestroy(e);
   if (h->ev_def_fork) (void)hipEventDestroy(h->ev_def_fork);
   if (h->ev_def_join) (void)hipEventDestroy(h->ev_def_join);
-  h->dLaFlags.release();
+  release_buffers(h, true);          // (behind the side streams: their hand-over kernels read dLaFlags)
   h->ring.release();
   if (h->hRes) (void)hipHostFree(h->hRes);
   if (h->ev_la) (void)hipEventDestroy(h->ev_la);
@@ -107,34 +100,22 @@ extern "C" int gps_profile_reset(gps_handle_t h) {
 extern "C" int gps_profile_get(gps_handle_t h, const char* klass, int64_t* launches, double* ms,
                                double* flops, double* bytes) {
   if (!h || !klass) return GPS_ERR_ARG;
-  if (strcmp(klass, "lookahead_retries") == 0) {      // evaluations re-run without look-ahead after a missed hand-over
-    if (launches) *launches = h->la_retries;
-    if (ms) *ms = 0.0; if (flops) *flops = 0.0; if (bytes) *bytes = 0.0;
-    return GPS_OK;
-  }
-  if (strcmp(klass, "factor_refined") == 0) {         // 1: the resident GPR factor was built (and is solved) with refined leaves
-    if (launches) *launches = h->factor_refine ? 1 : 0;
-    if (ms) *ms = 0.0; if (flops) *flops = 0.0; if (bytes) *bytes = 0.0;
-    return GPS_OK;
-  }
-  if (strcmp(klass, "small_n_fallbacks") == 0) {      // one-launch factorisations of small problems that gave up and were redone launch by launch
-    if (launches) *launches = (int64_t)h->small_fallbacks;
-    if (ms) *ms = 0.0; if (flops) *flops = 0.0; if (bytes) *bytes = 0.0;
-    return GPS_OK;
-  }
-  if (strcmp(klass, "leaves_plain") == 0 || strcmp(klass, "leaves_refined") == 0) {     // leaf launches in refine mode, by kind
-    if (launches) *launches = (int64_t)(klass[7] == 'p' ? h->leaves_plain : h->leaves_refined);
-    if (ms) *ms = 0.0; if (flops) *flops = 0.0; if (bytes) *bytes = 0.0;
-    return GPS_OK;
-  }
-  if (strcmp(klass, "small_n_cooldown") == 0) {       // evaluations the small-N back-off (small_gave_up) still sends launch by launch
-    if (launches) *launches = (int64_t)h->small_cooldown;
-    if (ms) *ms = 0.0; if (flops) *flops = 0.0; if (bytes) *bytes = 0.0;
-    return GPS_OK;
-  }
-  if (strcmp(klass, "trsv_wave_fallbacks") == 0) {    // wavefront substitutions that gave up (handle fell back to the recursive one)
-    if (launches) *launches = (int64_t)h->wave_fallbacks;
-    if (ms) *ms = 0.0; if (flops) *flops = 0.0; if (bytes) *bytes = 0.0;
+  // counters of the handle: the value comes back in *launches, nothing is synchronised
+  const struct { const char* key; long long value; } counters[] = {
+    {"lookahead_retries", h->la_retries},                      // evaluations re-run without look-ahead after a missed hand-over
+    {"factor_refined", h->factor_refine ? 1 : 0},              // 1: the resident GPR factor was built (and is solved) with refined leaves
+    {"small_n_fallbacks", h->small.fallbacks},                 // cooperative launches of the small path that gave up (redone launch by launch)
+    {"small_n_cooldown", h->small.cooldown},                   // evaluations the small path's back-off still sends launch by launch
+    {"leaves_plain", h->leaves_plain},                         // leaf launches in refine mode, by kind
+    {"leaves_refined", h->leaves_refined},
+    {"trsv_wave_fallbacks", (long long)h->wave_fallbacks},     // wavefront substitutions that gave up (handle fell back to the recursive one)
+  };
+  for (const auto& c : counters) {
+    if (strcmp(klass, c.key) != 0) continue;
+    if (launches) *launches = (int64_t)c.value;
+    if (ms) *ms = 0.0;
+    if (flops) *flops = 0.0;
+    if (bytes) *bytes = 0.0;
     return GPS_OK;
   }
   GPS_HIP(h, hipStreamSynchronize(h->stream));
@@ -169,13 +150,13 @@ extern "C" int gps_set_option(gps_handle_t h, const char* key, double value) {
   if (strcmp(key, "potrf_lookahead") == 0) { h->potrf_lookahead = (int)value; return GPS_OK; }
   if (strcmp(key, "la_fault_inject") == 0) { h->la_fault_inject = (int)value; return GPS_OK; }
   if (strcmp(key, "wave_fault_inject") == 0) { h->wave_fault_inject = (int)value; return GPS_OK; }
-  if (strcmp(key, "small_fault_inject") == 0) { h->small_fault_inject = (int)value; return GPS_OK; }
+  if (strcmp(key, "small_fault_inject") == 0) { h->small.fault_inject = (int)value; return GPS_OK; }
   if (strcmp(key, "svgp_kl_weight") == 0) { h->svgp_kl_weight = value; return GPS_OK; }
   if (strcmp(key, "dist_partitioned") == 0) { h->dist_partitioned = (int)value; return GPS_OK; }
   if (strcmp(key, "leaf_plain_kappa") == 0) { h->leaf_plain_kappa = value; h->plain_linv = nullptr; return GPS_OK; }
   if (strcmp(key, "follower_max_wgs") == 0) { h->follower_max_wgs = (int)value; return GPS_OK; }
   if (strcmp(key, "potrf_rl_group") == 0) { h->potrf_rl_group = (int)value < 1 ? 1 : (int)value; return GPS_OK; }
-  if (strcmp(key, "small_n") == 0) { h->small_n = (int)value; return GPS_OK; }
+  if (strcmp(key, "small_n") == 0) { h->small.on = (int)value; return GPS_OK; }
   if (strcmp(key, "trsm_panel") == 0) { h->trsm_panel = (int)value; return GPS_OK; }
   if (strcmp(key, "trsm_tall_ratio") == 0) { h->trsm_tall_ratio = (int)value; return GPS_OK; }
   if (strcmp(key, "trsm_panel_rows") == 0) {

@@ -324,13 +324,59 @@ static int classify_blocks(gps_handle_t h, const HipOps& ops, const double* L, i
   return GPS_OK;
 }
 
-// a cooperative launch of the small-N path gave up: counted; the fourth in a row sends the handle's next 256 evaluations of
-// that size launch by launch (a GPU shared with something that holds its CUs must not cost a bounded wait per optimiser step;
-// gps_profile_get "small_n_cooldown" reads what is left of the back-off)
-static void small_gave_up(gps_handle_t h) {
-  h->small_fallbacks++;
-  if (++h->small_consec >= 4) { h->small_cooldown = 256; h->small_consec = 0; }
+// The give-up protocol of the small path (gps_gpr.hip), for a cooperative launch one of whose bounded waits ran out: counted; the
+// fourth in a row sends the handle's next 256 evaluations of that size launch by launch (a GPU shared with something that holds
+// its CUs must not cost a bounded wait per optimiser step; gps_profile_get "small_n_cooldown" reads what is left of the
+// back-off); the launches' counters, in an unknown state now, go back to zero.  The caller then does again, launch by launch,
+// what the launch was to do.
+static int small_gave_up(gps_handle_t h) {
+  h->small.fallbacks++;
+  if (++h->small.consec >= 4) { h->small.cooldown = 256; h->small.consec = 0; }
+  return gps_small_factor_reset(h);
 }
+
+// The tail of a prediction (models/gpr.py:124-131) from A^T = Kx^T L^-T [nsp][np] (n_new real rows), alpha in dAlpha and the test
+// points in dXnew: mean and variance (or, full_cov, the covariance K(Xnew) - A^T A) on their way to the host.  Does not synchronise.
+static int predict_finish(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dAt, i64 np, i64 nsp, i64 n_new, i64 r,
+                          int full_cov, double* mean_out, double* var_out) {
+  const i64 d = h->d_all;
+  // fmean = A^T V ; sumsq = colsum(A*A)                          models/gpr.py:124,130
+  GPS_HIP(h, h->dMean.ensure((size_t)(n_new * (r > 0 ? r : 1) + n_new) * 8));
+  double* dmean = h->dMean.d();
+  double* dss = dmean + n_new * (r > 0 ? r : 1);
+  int rc = gps_launch_rowdot(h, dAt, np, n_new, np, h->dAlpha.d(), np, r, dmean, dss);
+  if (rc) return rc;
+  if (!full_cov) {
+    // Kdiag: one number, or (Linear / Polynomial, kernels.py:507-510, 553-554) one per test point
+    double kd = 0.0;
+    const double* dkd = nullptr;
+    if (gps_kdiag_is_const(prog, n_nodes)) rc = gps_launch_kdiag(h, prog, n_nodes, &kd);
+    else {
+      GPS_HIP(h, h->dKdiag.ensure((size_t)n_new * 8));
+      rc = gps_launch_kdiag_vec(h, prog, n_nodes, h->dXnew.d(), n_new, d, h->dKdiag.d(), nullptr);
+      dkd = h->dKdiag.d();
+    }
+    if (rc) return rc;
+    GPS_HIP(h, h->dVar.ensure((size_t)n_new * 8));
+    rc = gps_launch_var_finish(h, h->dVar.d(), dkd, kd, dss, n_new);
+    if (rc) return rc;
+    GPS_HIP(h, hipMemcpyAsync(var_out, h->dVar.p, (size_t)n_new * 8, hipMemcpyDeviceToHost, h->stream));
+  } else {
+    // K(Xnew) - A^T A                                             models/gpr.py:126
+    GPS_HIP(h, h->dVar.ensure((size_t)nsp * nsp * 8));
+    rc = gps_launch_kmat(h, prog, n_nodes, h->dXnew.d(), n_new, nullptr, n_new, d, 0.0, h->dVar.d(), nsp, nsp, nsp, 0, 0);
+    if (rc) return rc;
+    rc = gps_launch_gemm_nt(h, 0, 0, nsp, nsp, np, dAt, np, dAt, np, h->dVar.d(), nsp);
+    if (rc) return rc;
+    GPS_HIP(h, h->dTmp2.ensure((size_t)n_new * n_new * 8));
+    rc = gps_launch_extract(h, h->dVar.d(), nsp, n_new, n_new, h->dTmp2.d(), n_new, 0);
+    if (rc) return rc;
+    GPS_HIP(h, hipMemcpyAsync(var_out, h->dTmp2.p, (size_t)n_new * n_new * 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  if (r > 0) GPS_HIP(h, hipMemcpyAsync(mean_out, dmean, (size_t)n_new * r * 8, hipMemcpyDeviceToHost, h->stream));
+  return GPS_OK;
+}
+
 static int stage_time(gps_handle_t h, int a, int b, double* out) {
   float ms = 0.f;
   GPS_HIP(h, hipEventElapsedTime(&ms, h->ev[a], h->ev[b]));

@@ -996,7 +996,7 @@ int gps_launch_kdiag(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, d
   // Kdiag of every primitive but Linear / Polynomial is its variance (kernels.py:428-429, 803-804, 327-328);
   // Sum.Kdiag / Product.Kdiag fold them (kernels.py:1075-1076, 1083-1084).
   if (!gps_kdiag_is_const(prog, n_nodes))
-    return gps_fail(h, GPS_ERR_UNSUPPORTED, "Kdiag is not constant for a kernel program with Linear / Polynomial: this path takes constant-Kdiag kernels only");
+    return gps_fail(h, GPS_ERR_UNSUPPORTED, GPS_KDIAG_NOT_CONST_MSG);
   bool nkn = false;
   for (int i = 0; i < n_nodes; ++i) if (prog[i].op >= GPS_K_NKN_LINROW) nkn = true;
   if (nkn) {

@@ -468,7 +468,7 @@ int gps_launch_small_factor(gps_handle_t h, double* dK, i64 np, double* linv, do
   }
   // diagnostics ("small_fault_inject" = k): the k-th cooperative launch from now starts with its abort word set, as if one of
   // its bounded waits had run out -- the evaluation must come back right through the launch-by-launch path
-  if (h->small_fault_inject > 0 && --h->small_fault_inject == 0) {
+  if (h->small.fault_inject > 0 && --h->small.fault_inject == 0) {
     const u32 one = 1u;
     GPS_HIP(h, hipMemcpyAsync((u32*)h->dSmallSync.p + SN_ABORT, &one, 4, hipMemcpyHostToDevice, h->stream));
     GPS_HIP(h, hipStreamSynchronize(h->stream));
@@ -733,7 +733,7 @@ int gps_launch_small_inverse(gps_handle_t h, const double* dK, i64 np, const dou
   if (!rc0) rc0 = gps_dyn_lds(h, reinterpret_cast<const void*>(&small_inverse_kernel<true>), (int)lds);
   if (rc0) return rc0;
   LaunchScope ls(h, KC_GEMM, 2.0 * (double)np * np * np / 3.0, 16.0 * np * np);
-  if (h->small_fault_inject > 0 && --h->small_fault_inject == 0) {
+  if (h->small.fault_inject > 0 && --h->small.fault_inject == 0) {
     const u32 one = 1u;
     GPS_HIP(h, hipMemcpyAsync((u32*)h->dSmallSync.p + SN_WORDS + SN_ABORT, &one, 4, hipMemcpyHostToDevice, h->stream));
     GPS_HIP(h, hipStreamSynchronize(h->stream));

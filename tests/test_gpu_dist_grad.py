@@ -319,3 +319,61 @@ def test_full_size_eight_virtual_ranks(handle):
         assert _close(g, _flat(g_ref), 1e-9)
         assert nbytes <= 16 * n * n / P + 64 * n * nb, nbytes
         assert fl <= 1.25 * float(n) ** 3 / P, fl
+
+
+MIB = 1 << 20
+
+
+def test_release_buffers_releases_every_work_buffer(handle):
+    """Every work buffer of the handle is in its one registry (csrc/gps_common.hpp: DevBuf), whichever entry point allocated it:
+    the distributed gradient's dDistZ / dDistPT, the likelihoods' dLik*, the per-point dKdiag.  gps_device_bytes counts them
+    and gps_release_buffers gives all of them back; only the persistent ones stay."""
+    import gpflowSlim as gpf
+    import _lik_ref as lref
+    from gpflowSlim import _backend as be
+    from gpflowSlim.distributed import SingleComm, gpr_lml_grad_distributed
+    kname, n, nb, r = "nkn", 500, 128, 1                  # the smallest shape of test_single_comm_gradient_equals_fused
+    X, Y = _data(n, 3, r, seed=n)
+    gpr_lml_grad_distributed(_model(gpf, X, Y, kname), SingleComm(), nb=nb)
+    rng = np.random.default_rng(64)
+    mu, var, Yl, params = lref.sample_inputs("bernoulli", 64, 2, rng)
+    handle.lik_varexp(be.make_lik(lref.KIND_ID["bernoulli"], params, 20), mu, var, Yl)
+    Xl, Yr, Xs = orc.synthetic_gpr_data(200, 3, 10, seed=2)
+    gpf.models.GPR(Xl, Yr, gpf.kernels.Linear(3, variance=0.7), obs_var=0.1).predict_f(Xs)
+    # one rank owns all np / nb block columns: dDistZ [128 + np][np], and K with its augmented rows [np + 128][np], np = 512
+    np_ = -(-n // nb) * nb
+    assert handle.device_bytes() >= 2 * (128 + np_) * np_ * 8
+    handle.release_buffers()
+    # DevBuf rounds every allocation up to 1 MiB; the registry has five persistent buffers (dInfo, dScal, dWaveCtl, dSmallSync,
+    # dLaFlags), each a few words to a few KiB: at most 1 MiB a piece is what may stay
+    assert handle.device_bytes() <= 5 * MIB, handle.device_bytes()
+    Xg, Yg, _ = orc.synthetic_gpr_data(300, 3, 5, seed=4)
+    m = gpf.models.GPR(Xg, Yg, gpf.kernels.RBF(3, variance=1.1, lengthscales=1.3), obs_var=0.1)
+    ref = orc.gpr_lml({"type": "rbf", "variance": orc.constrained(1.1), "lengthscales": orc.constrained(1.3), "input_dim": 3},
+                      Xg, Yg, orc.constrained(0.1))
+    assert abs(m.compute_log_likelihood() - ref) <= 1e-8 * abs(ref)
+
+
+def test_destroy_frees_the_distributed_gradient_work_space(handle):
+    """gps_destroy frees dDistZ, [128 + n][n] doubles on one rank (35.7 MB at n = 2048, nb = 128): free device memory is back
+    to within half of that after the handle is closed (the slack: what the runtime keeps for streams and events)."""
+    import torch
+    import gpflowSlim as gpf
+    from gpflowSlim import _backend as be
+    from gpflowSlim.distributed import SingleComm, gpr_lml_grad_distributed
+    n, nb = 2048, 128
+    X, Y = _data(n, 3, 1, seed=11)
+    # throw-away evaluation of the same shape on the shared handle: code objects loaded, the caching allocator warm
+    gpr_lml_grad_distributed(_model(gpf, X, Y, "rbf_ard"), SingleComm(), nb=nb)
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    h = be.Handle(0)
+    try:
+        gpr_lml_grad_distributed(_bind(_model(gpf, X, Y, "rbf_ard"), h), SingleComm(), nb=nb)
+        assert h.device_bytes() >= (128 + n) * n * 8
+    finally:
+        h.close()
+    torch.cuda.synchronize()
+    free1 = torch.cuda.mem_get_info()[0]
+    print("free before %d, after %d, difference %d" % (free0, free1, free0 - free1))
+    assert free0 - free1 <= (128 + n) * n * 8 // 2, (free0, free1)
