@@ -90,8 +90,8 @@ struct PinnedRing {
 };
 
 // ---- per-kernel-class accounting -------------------------------------------
-enum { KC_GEMM = 0, KC_POTRF_BASE, KC_KMAT, KC_TRSV, KC_REDUCE, KC_OTHER, KC_COUNT };
-static const char* const kc_names[KC_COUNT] = {"gemm_f64", "potrf_base", "kmat", "trsv", "reduce", "other"};
+enum { KC_GEMM = 0, KC_POTRF_BASE, KC_KMAT, KC_TRSV, KC_REDUCE, KC_OTHER, KC_RFF_FEAT, KC_RFF_CONTRACT, KC_COUNT };
+static const char* const kc_names[KC_COUNT] = {"gemm_f64", "potrf_base", "kmat", "trsv", "reduce", "other", "rff_features", "rff_contract"};
 
 struct KClassStat {
   i64 launches = 0;
@@ -281,6 +281,9 @@ struct gps_handle_s {
     bool linvT_stale = false;    // the resident factor's transposed block inverses have not been produced yet (gpr_ensure_linvT)
   } small;
   DevBuf dGemmWs{bufs}, dGemmCnt{bufs};   // slice partials + arrival counters of the GEMM tail split
+  // ---- random-feature GPR (gps_rff.hip): L = chol(Phi^T Phi + s I) [pad(F), pad(F)] in dK / dLinv, L^-1 B and C in dAlpha ----
+  // valid while factor_gen still is what it was when the factor was made (every entry that rebuilds dK bumps it)
+  struct RffFactor { bool have = false; unsigned long long gen = 0; i64 F = 0, r = 0; int kind = -1, d = 0; bool refine = false; } rff;
   DevBuf dGemvWs{bufs}, dGemvCnt{bufs};   // slice partials + arrival counters of the split transposed gemv (blas1.hip)
 };
 
@@ -520,6 +523,17 @@ int gps_launch_psi_pk(gps_handle_t h, const PsiIn& in, const double* X, i64 ldx,
 int gps_launch_psi2_vjp(gps_handle_t h, const PsiIn& in, const double* PK, i64 ldpk, double* out_n, double* out_z, i64 ldz);
 int gps_launch_psi1_vjp(gps_handle_t h, const PsiIn& in, const double* Y, const double* Yt, i64 ldy, const double* Wt, i64 ldw, i64 r,
                         double* out_n, double* out_z, i64 ldz);
+// rff.hip : random-feature maps (kernel_kitchen_sink.py) and the contraction of their cotangent; all pointers on the device
+//   kind GPS_RFF_*; omega [d, F], offset [F], ls [d] (RBF only); c1, c2: the two factors behind the cosine (RBF) or c1 alone
+struct RffDev { int kind; int d; i64 F; double c1, c2; const double* omega; const double* offset; const double* ls; };
+// Pt (and St, optional: the sine features) [Fp][nc] feature-major from the rows [rows, d] at Xc; rows beyond F and columns beyond
+// `rows` are exact zeros.  nc, Fp multiples of 128.
+int gps_launch_rff_features(gps_handle_t h, const RffDev& p, const double* Xc, i64 rows, i64 nc, i64 Fp, double* Pt, double* St);
+// One pass over a chunk: G^T = C E^T inv_s - R Qt ; *acc (+)= sum G o Phi ; Qt <- G^T o St (St given).  Et [r][lde], Crows [r][ldc].
+// partial: room for (nc / 128) * (Fp / 32) doubles.
+int gps_launch_rff_contract(gps_handle_t h, const double* Pt, const double* St, double* Qt, const double* Et, i64 lde,
+                            const double* Crows, i64 ldc, i64 r, double inv_s, double R, i64 nc, i64 Fp, double* partial,
+                            double* acc, int first);
 // diag.hip
 int gps_run_mfma_diag(gps_handle_t h, int waves_per_simd, double* tflops, int* layout_ok);
 int gps_run_gemm_timeline(gps_handle_t h, int op, int lower, i64 m, i64 n, i64 k, int reps, long long* stamps_out,

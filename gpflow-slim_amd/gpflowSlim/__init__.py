@@ -9,6 +9,7 @@ from . import transforms
 from . import params
 from . import kernels
 from . import ekernels
+from . import kernel_kitchen_sink
 from . import mean_functions
 from . import densities
 from . import likelihoods

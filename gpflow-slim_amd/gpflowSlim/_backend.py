@@ -45,6 +45,38 @@ class LikDesc(ctypes.Structure):
                 ("gh_w", ctypes.POINTER(ctypes.c_double))]
 
 
+class RffDesc(ctypes.Structure):
+    """gps_rff_desc_t"""
+    _fields_ = [("kind", ctypes.c_int32),
+                ("input_dim", ctypes.c_int32),
+                ("n_components", ctypes.c_int32),
+                ("variance", ctypes.c_double),
+                ("ls", ctypes.POINTER(ctypes.c_double)),
+                ("n_ls", ctypes.c_int32),
+                ("omega", ctypes.POINTER(ctypes.c_double)),
+                ("offset", ctypes.POINTER(ctypes.c_double))]
+
+
+RFF_RBF, RFF_LINEAR, RFF_CONSTANT, RFF_EXPLICIT = 0, 1, 2, 3
+
+
+def make_rff(kind, input_dim, n_components, variance=1.0, ls=None, omega=None, offset=None):
+    """A gps_rff_desc_t and the arrays it points into (which the caller keeps alive)."""
+    d = RffDesc()
+    d.kind, d.input_dim, d.n_components, d.variance = int(kind), int(input_dim), int(n_components), float(variance)
+    keep = []
+    if kind == RFF_RBF:
+        ls = np.ascontiguousarray(np.atleast_1d(ls), dtype=np.float64).ravel()
+        omega = np.ascontiguousarray(omega, dtype=np.float64)
+        offset = np.ascontiguousarray(offset, dtype=np.float64).ravel()
+        if omega.shape != (d.input_dim, d.n_components) or offset.shape != (d.n_components,) or ls.size not in (1, d.input_dim):
+            raise ValueError("RBF sampler: omega must be [input_dim, n_components], offset [n_components], ls scalar or [input_dim]")
+        d.ls, d.n_ls = ls.ctypes.data_as(_c_double_p), int(ls.size)
+        d.omega, d.offset = omega.ctypes.data_as(_c_double_p), offset.ctypes.data_as(_c_double_p)
+        keep = [ls, omega, offset]
+    return d, keep
+
+
 LIK_MAX_GH = 64
 LIK_MULTICLASS = 5
 
@@ -140,6 +172,14 @@ _SIGNATURES = {
     "gps_bgplvm_grad": [ctypes.c_void_p, ctypes.POINTER(KernNode), ctypes.c_int, _c_double_p, _i64, _c_double_p, _c_double_p, _i64,
                         _i64, ctypes.c_double, ctypes.c_double, _c_double_p, _i64, _c_double_p, _c_double_p, ctypes.c_int, _c_int_p,
                         _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_int_p],
+    "gps_rff_features": [ctypes.c_void_p, ctypes.POINTER(RffDesc), _c_double_p, _i64, _c_double_p],
+    "gps_rff_gram": [ctypes.c_void_p, ctypes.POINTER(RffDesc), _c_double_p, _i64, _c_double_p, _i64, _c_double_p, _c_double_p],
+    "gps_rff_lml": [ctypes.c_void_p, ctypes.POINTER(RffDesc), _c_double_p, _i64, ctypes.c_double, _c_double_p, _i64, _i64,
+                    _c_double_p, _c_int_p],
+    "gps_rff_lml_grad": [ctypes.c_void_p, ctypes.POINTER(RffDesc), _c_double_p, _i64, ctypes.c_double, _c_double_p, _i64, _i64,
+                         _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_int_p],
+    "gps_rff_predict": [ctypes.c_void_p, ctypes.POINTER(RffDesc), _c_double_p, _i64, ctypes.c_double, _c_double_p, _i64, _i64,
+                        _c_double_p, _i64, ctypes.c_int, ctypes.c_int, _c_double_p, _c_double_p, _c_int_p],
     "gps_sparse_last_terms": [ctypes.c_void_p, _c_double_p],
     "gps_profile_enable": [ctypes.c_void_p, ctypes.c_int],
     "gps_profile_reset": [ctypes.c_void_p],
@@ -776,6 +816,86 @@ class Handle(object):
             raise NotPositiveDefiniteError(
                 "Cholesky decomposition was not successful: leading minor of order %d is not positive definite"
                 % info.value)
+        return mean, var
+
+    # ---- GPR on explicit features (kernel_kitchen_sink.py; models/gpr.py:63-67, 86-117)
+    def _rff_x(self, desc, X):
+        X = _f64(X)
+        _need(X.ndim == 2 and X.shape[0] > 0 and X.shape[1] == desc.input_dim, "X must be [N, %d] with N > 0" % desc.input_dim)
+        self.resident_token = None
+        self.factor_key = None
+        return X
+
+    def rff_features(self, desc, X):
+        """gps_rff_features: the feature map of the descriptor applied to X, host [N, F]."""
+        if np.shape(X)[0] == 0:
+            return np.empty((0, desc.n_components))
+        X = self._rff_x(desc, X)
+        out = np.empty((X.shape[0], desc.n_components))
+        self._check(self._lib.gps_rff_features(self._h, ctypes.byref(desc), _ptr(X), X.shape[0], _ptr(out)), "gps_rff_features")
+        return out
+
+    def rff_gram(self, desc, X, X2=None, want_K=True, want_diag=False):
+        """gps_rff_gram: (Phi(X) Phi(X2)^T or None, row sums of squares of Phi(X) or None)."""
+        X = self._rff_x(desc, X)
+        n = X.shape[0]
+        n2 = n
+        if X2 is not None:
+            X2 = _f64(X2)
+            _need(X2.ndim == 2 and X2.shape[0] > 0 and X2.shape[1] == desc.input_dim, "X2 must be [N2, %d]" % desc.input_dim)
+            n2 = X2.shape[0]
+        K = np.empty((n, n2)) if want_K else None
+        kd = np.empty(n) if want_diag else None
+        self._check(self._lib.gps_rff_gram(self._h, ctypes.byref(desc), _ptr(X), n, _ptr(X2) if X2 is not None else None, n2,
+                                           _ptr(K) if want_K else None, _ptr(kd) if want_diag else None), "gps_rff_gram")
+        return K, kd
+
+    @staticmethod
+    def _rff_info(info):
+        if info.value > 0:
+            raise NotPositiveDefiniteError(
+                "Cholesky decomposition was not successful: leading minor of order %d is not positive definite" % info.value)
+
+    def rff_lml(self, desc, X, noise_var, resid, chunk_rows=0):
+        X, resid = self._rff_x(desc, X), _f64(resid)
+        _need(resid.ndim == 2 and resid.shape[0] == X.shape[0] and resid.shape[1] > 0, "Y must have one row per row of X")
+        lml, info = ctypes.c_double(0), ctypes.c_int(0)
+        self._check(self._lib.gps_rff_lml(self._h, ctypes.byref(desc), _ptr(X), X.shape[0], float(noise_var), _ptr(resid),
+                                          resid.shape[1], int(chunk_rows), ctypes.byref(lml), ctypes.byref(info)), "gps_rff_lml")
+        self._rff_info(info)
+        return lml.value
+
+    def rff_lml_grad(self, desc, X, noise_var, resid, chunk_rows=0):
+        """(lml, d / d variance, d / d ls [n_ls], d / d noise_var, K_y^-1 resid [N, R]) -- gps_rff_lml_grad."""
+        X, resid = self._rff_x(desc, X), _f64(resid)
+        _need(resid.ndim == 2 and resid.shape[0] == X.shape[0] and resid.shape[1] > 0, "Y must have one row per row of X")
+        lml, gvar, gnoise, info = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0), ctypes.c_int(0)
+        gls = np.zeros(max(int(desc.n_ls), 1))
+        kinv_resid = np.empty(resid.shape)
+        self._check(self._lib.gps_rff_lml_grad(self._h, ctypes.byref(desc), _ptr(X), X.shape[0], float(noise_var), _ptr(resid),
+                                               resid.shape[1], int(chunk_rows), ctypes.byref(lml), ctypes.byref(gvar), _ptr(gls),
+                                               ctypes.byref(gnoise), _ptr(kinv_resid), ctypes.byref(info)), "gps_rff_lml_grad")
+        self._rff_info(info)
+        return lml.value, gvar.value, gls[:int(desc.n_ls)].copy(), gnoise.value, kinv_resid
+
+    def rff_predict(self, desc, X, noise_var, resid, Xnew, full_cov=False, refactor=True, chunk_rows=0):
+        resid, Xnew = _f64(resid), _f64(Xnew)
+        _need(Xnew.ndim == 2 and Xnew.shape[1] == desc.input_dim, "Xnew must be [N*, %d]" % desc.input_dim)
+        n_new, r = Xnew.shape[0], resid.shape[1]
+        mean = np.empty((n_new, r))
+        var = np.empty((n_new, n_new) if full_cov else (n_new,))
+        if n_new == 0:
+            return mean, var
+        if refactor:
+            X = self._rff_x(desc, X)
+        else:
+            X = _f64(X)
+        _need(resid.ndim == 2 and resid.shape[0] == X.shape[0] and r > 0, "Y must have one row per row of X")
+        info = ctypes.c_int(0)
+        self._check(self._lib.gps_rff_predict(self._h, ctypes.byref(desc), _ptr(X), X.shape[0], float(noise_var), _ptr(resid), r,
+                                              int(chunk_rows), _ptr(Xnew), n_new, 1 if full_cov else 0, 1 if refactor else 0,
+                                              _ptr(mean), _ptr(var), ctypes.byref(info)), "gps_rff_predict")
+        self._rff_info(info)
         return mean, var
 
     # ---- SGPR

@@ -51,3 +51,19 @@ def multivariate_normal(x, mu, L):
     ret += -num_col * np.sum(np.log(np.diag(L)))
     ret += -0.5 * np.sum(np.square(alpha))
     return ret
+
+
+def multivariate_normal_feature(x, mu, C, var):
+    """densities.py:98-124: log N(x; mu, C C^T + var I) for a host matrix of features C [N, F] in O(N F^2), columns of x
+    independent.  The Gram matrix, its factor and the solves run on the device (csrc/gps_rff.hip, the feature map being the
+    identity on C).  Two deliberate differences from the reference: it adds settings.jitter to diag(L) inside the logarithm
+    (a shift of about 2 sum 1e-6 / L_ii away from the density it names), which is left out here; and it leaves out the
+    number of columns R on the log-determinant and on N log 2 pi, which is kept here, so that the value equals
+    ``multivariate_normal`` on the factor of C C^T + var I for every R (at R = 1: the reference's value without its 1e-6)."""
+    x = np.asarray(x, dtype=np.float64)
+    d = x - mu
+    if d.ndim == 1:
+        d = d[:, None]
+    C = np.ascontiguousarray(C, dtype=np.float64)
+    desc, keep = be.make_rff(be.RFF_EXPLICIT, C.shape[1], C.shape[1])
+    return be.get_handle().rff_lml(desc, C, float(np.squeeze(var)), np.ascontiguousarray(d))

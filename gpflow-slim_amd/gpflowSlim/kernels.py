@@ -411,6 +411,8 @@ class Combination(Kernel):
             elif isinstance(k, _SCALARS):
                 self.const_list.append(float(k))
             elif isinstance(k, Kernel):
+                if callable(getattr(k, "_on_combine", None)):
+                    k._on_combine()                      # (kernels that cannot be part of a kernel program raise here)
                 self.kern_list.append(k)
             else:
                 raise TypeError("can only combine Kernel instances and scalars")

@@ -39,6 +39,8 @@ class GPR(GPModel):
         self.num_latent = Y.shape[1] if num_latent is None else num_latent
         # not in the reference: opt-in reuse of the resident factor by predict_f
         self.reuse_factor = False
+        # feature branch: rows of X per device chunk (0: the library chooses, about 1 GiB per chunk buffer)
+        self.rff_chunk_rows = 0
 
     # ---- device plumbing -------------------------------------------------------------------
     @property
@@ -68,9 +70,62 @@ class GPR(GPModel):
     def _resid(self):
         return np.ascontiguousarray(self.Y - self.mean_function(self.X))
 
+    # ---- feature branch (models/gpr.py:63-67, 86-117): kernels with a callable ``features`` ---------------------------
+    def _has_features(self):
+        return callable(getattr(self.kern, 'features', None))
+
+    def _rff(self, Xnew=None):
+        """(descriptor, arrays it points into, X, Xnew) for the device entries: the sampler's own descriptor where the
+        kernel has one (the feature map then runs on the device), else the kernel's features as explicit host matrices."""
+        sampler = getattr(self.kern, 'sampler', None)
+        if callable(getattr(sampler, '_descriptor', None)):
+            desc, keep = sampler._descriptor()
+            return desc, keep, self.X, Xnew
+        feat = np.ascontiguousarray(self.kern.features(self.X), dtype=settings.float_type)
+        desc, keep = be.make_rff(be.RFF_EXPLICIT, feat.shape[1], feat.shape[1])
+        fnew = None if Xnew is None else np.ascontiguousarray(self.kern.features(Xnew), dtype=settings.float_type)
+        return desc, keep, feat, fnew
+
+    def _rff_likelihood(self):
+        h = be.get_handle()
+        desc, keep, X, _ = self._rff()
+        self._factor_key = None
+        lml = h.rff_lml(desc, X, float(np.squeeze(self.likelihood.variance)), self._resid(), self.rff_chunk_rows)
+        self._factor_key = self._state_key()
+        return lml
+
+    def _rff_likelihood_and_gradients(self):
+        h = be.get_handle()
+        desc, keep, X, _ = self._rff()
+        if desc.kind == be.RFF_EXPLICIT:
+            raise NotImplementedError("gradients of the feature branch need a kernel_kitchen_sink sampler")
+        sampler = self.kern.sampler
+        self._factor_key = None
+        lml, gvar, gls, gnoise, kinv_resid = h.rff_lml_grad(desc, X, float(np.squeeze(self.likelihood.variance)),
+                                                            self._resid(), self.rff_chunk_rows)
+        self._factor_key = self._state_key()
+        layout, slots = [(sampler._variance, None)], [gvar]
+        if desc.kind == be.RFF_RBF:
+            layout += [(sampler._ls, None)] if gls.size == 1 else [(sampler._ls, i) for i in range(gls.size)]
+            slots += list(gls)
+        return lml, self._gradients_from_slots(layout, slots, gnoise, kinv_resid)
+
+    def _rff_predict(self, Xnew, full_cov):
+        h = be.get_handle()
+        desc, keep, X, Xn = self._rff(Xnew)
+        key = self._state_key()
+        warm = bool(self.reuse_factor) and self._factor_key is not None and self._factor_key == key
+        self._factor_key = None
+        mean, var = h.rff_predict(desc, X, float(np.squeeze(self.likelihood.variance)), self._resid(), Xn,
+                                  full_cov=full_cov, refactor=not warm, chunk_rows=self.rff_chunk_rows)
+        self._factor_key = key
+        return mean, var
+
     # ---- reference API ---------------------------------------------------------------------
     def _build_likelihood(self):
-        """models/gpr.py:69-72 + densities.py:73-95, fused on the device."""
+        """models/gpr.py:63-72 + densities.py:73-124, fused on the device."""
+        if self._has_features():
+            return self._rff_likelihood()
         h = self._handle()
         prog = self.kern._program(self.X.shape[1])
         self._factor_key = None
@@ -83,6 +138,8 @@ class GPR(GPModel):
         `tf.gradients(objective, variables)` yields in the reference (examples/gpr.py:53-54) up to the
         sign of `objective = -LML`.  Returns (lml, [(Parameter, gradient array shaped like
         Parameter.unconstrained_tensor), ...]) in `self.parameters` order.  Priors are not included."""
+        if self._has_features():
+            return self._rff_likelihood_and_gradients()
         h = self._handle()
         d_all = self.X.shape[1]
         prog = self.kern._program(d_all)
@@ -129,16 +186,19 @@ class GPR(GPModel):
         return out
 
     def _build_predict(self, Xnew, full_cov=False):
-        """models/gpr.py:119-131"""
+        """models/gpr.py:86-131"""
         Xnew = np.ascontiguousarray(Xnew, dtype=settings.float_type)
-        h = self._handle()
-        prog = self.kern._program(self.X.shape[1])
-        key = self._state_key()
-        warm = bool(self.reuse_factor) and self._factor_key is not None and self._factor_key == key
-        self._factor_key = None
-        mean, var = h.gpr_predict(prog, float(np.squeeze(self.likelihood.variance)), self._resid(), Xnew,
-                                  full_cov=full_cov, refactor=not warm)
-        self._factor_key = key
+        if self._has_features():
+            mean, var = self._rff_predict(Xnew, full_cov)
+        else:
+            h = self._handle()
+            prog = self.kern._program(self.X.shape[1])
+            key = self._state_key()
+            warm = bool(self.reuse_factor) and self._factor_key is not None and self._factor_key == key
+            self._factor_key = None
+            mean, var = h.gpr_predict(prog, float(np.squeeze(self.likelihood.variance)), self._resid(), Xnew,
+                                      full_cov=full_cov, refactor=not warm)
+            self._factor_key = key
         fmean = mean + self.mean_function(Xnew)
         R = self.Y.shape[1]
         if full_cov:

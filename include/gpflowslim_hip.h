@@ -171,6 +171,57 @@ int gps_gpr_predict(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes,
                     const double* Xnew, int64_t n_new, int full_cov,
                     int refactor, double* mean_out, double* var_out, int* info);
 
+/* ---- GPR on explicit (random) features: the Woodbury branch --------------------------------------
+ * kernel_kitchen_sink.py:80-118 (RBFSampler), :193-207 (LinearSampler), :304-318 (ConstantSampler), :694-709 (SamplerKernel);
+ * models/gpr.py:63-67, 86-117; densities.py:98-124.  Phi [n, F] is the feature map of the descriptor applied to X [n, input_dim]:
+ *   RBF       cos(X (omega / ls[:, None]) + offset) * sqrt(2 / F) * sqrt(variance)     omega [input_dim, F], offset [F],
+ *             ls [n_ls], n_ls = 1 or input_dim, input_dim <= GPS_RFF_MAX_DIMS
+ *   LINEAR    tile(X)[:, :F] * sqrt(variance * input_dim / F)                            input_dim <= GPS_RFF_MAX_DIMS
+ *   CONSTANT  ones * sqrt(variance / F)
+ *   EXPLICIT  X itself (input_dim == F): densities.multivariate_normal_feature on a host matrix of features
+ * All pointers of the descriptor are host pointers.  Phi never exists on the device: the entries walk X in chunks of
+ * chunk_rows rows (rounded up to a multiple of 128; 0: about 1 GiB per chunk buffer) and keep F^2 doubles plus a few chunks.
+ * With x = resid [n, r], s = noise_var, A = Phi^T Phi + s I, L = chol(A), B = Phi^T x, C = A^-1 B:
+ *   lml = -0.5 [ (|x|^2 - |L^-1 B|^2) / s + r (n log 2 pi + 2 sum log L_ii + (n - F) log s) ]
+ * which is the density densities.py:98-124 names: without the 1e-6 the reference adds to diag(L) inside the logarithm, and
+ * with the factor r on the log-determinant that it leaves out (equal at r = 1).                                            */
+#define GPS_RFF_MAX_DIMS 32   /* input dimensions of the RBF and LINEAR maps; more: GPS_ERR_UNSUPPORTED */
+enum { GPS_RFF_RBF = 0, GPS_RFF_LINEAR = 1, GPS_RFF_CONSTANT = 2, GPS_RFF_EXPLICIT = 3 };
+typedef struct gps_rff_desc {
+  int32_t kind;
+  int32_t input_dim;
+  int32_t n_components;       /* F */
+  double  variance;
+  const double* ls;
+  int32_t n_ls;
+  const double* omega;
+  const double* offset;
+} gps_rff_desc_t;
+
+/* sampler.transform(X) / SamplerKernel.features(X): out host [n, F].                                                      */
+int gps_rff_features(gps_handle_t h, const gps_rff_desc_t* desc, const double* X, int64_t n, double* out);
+/* SamplerKernel.K / Kdiag (kernel_kitchen_sink.py:699-706): K_out host [n, n2] = Phi(X) Phi(X2)^T (X2 == NULL: X2 = X, n2
+ * ignored), kdiag_out host [n] = row sums of squares of Phi(X); either may be NULL.                                         */
+int gps_rff_gram(gps_handle_t h, const gps_rff_desc_t* desc, const double* X, int64_t n, const double* X2, int64_t n2,
+                 double* K_out, double* kdiag_out);
+/* GPR._build_likelihood, feature branch (models/gpr.py:63-67).  Leaves L, L^-1 B and C resident.  r <= 128.
+ * info > 0: the factorisation failed at that order -- or, info = F, it went through but the value is not finite or the
+ * quadratic form |x|^2 - |L^-1 B|^2 (positive in exact arithmetic) came out negative, i.e. was lost to rounding.          */
+int gps_rff_lml(gps_handle_t h, const gps_rff_desc_t* desc, const double* X, int64_t n, double noise_var,
+                const double* resid, int64_t r, int64_t chunk_rows, double* lml, int* info);
+/* ... and its gradient with respect to the CONSTRAINED values: grad_var = d / d variance, grad_ls [n_ls] (RBF; may be NULL
+ * otherwise), grad_noise = d / d noise_var, kinv_resid (optional) host [n, r] = (x - Phi C) / s = K_y^-1 x.               */
+int gps_rff_lml_grad(gps_handle_t h, const gps_rff_desc_t* desc, const double* X, int64_t n, double noise_var,
+                     const double* resid, int64_t r, int64_t chunk_rows, double* lml, double* grad_var, double* grad_ls,
+                     double* grad_noise, double* kinv_resid, int* info);
+/* GPR._build_predict, feature branch (models/gpr.py:86-117) in the form  mean = Phi* C,  cov = s Phi* A^-1 Phi*^T
+ * (= the reference's expressions, since Ct_CCT_I_inv feat = I - s A^-1).  refactor as for gps_gpr_predict: 0 reuses the
+ * factor the last gps_rff_lml / _lml_grad / _predict left (desc, X, noise_var, resid unchanged -- the caller vouches).
+ * mean_out host [n_new, r]; var_out host [n_new] or, full_cov, [n_new, n_new].                                             */
+int gps_rff_predict(gps_handle_t h, const gps_rff_desc_t* desc, const double* X, int64_t n, double noise_var,
+                    const double* resid, int64_t r, int64_t chunk_rows, const double* Xnew, int64_t n_new, int full_cov,
+                    int refactor, double* mean_out, double* var_out, int* info);
+
 /* ---- conditionals.conditional / base_conditional ------------------------
  * (conditionals.py:24-66, 80-121; features.py:74-81 for Kuu/Kuf).
  * Device-resident form: Kmm = kern.K(Z) + jitter*I, Kmn = kern.K(Z, Xnew) are
@@ -427,7 +478,7 @@ int gps_sparse_last_terms(gps_handle_t h, double* out5);
  * gps_profile_enable(h, 1) brackets every launch with HIP events on the
  * handle's stream (adds a few us per launch); counters accumulate until
  * gps_profile_reset.  Classes: "gemm_f64", "potrf_base", "kmat", "trsv",
- * "reduce", "other".                                                        */
+ * "reduce", "other", "rff_features", "rff_contract".                        */
 int gps_profile_enable(gps_handle_t h, int on);
 int gps_profile_reset(gps_handle_t h);
 int gps_profile_get(gps_handle_t h, const char* klass, int64_t* launches,
