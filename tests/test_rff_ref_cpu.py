@@ -1,7 +1,16 @@
 """CPU tests of tests/_rff_ref.py, the restatement the GPU tests of the random-feature GPR branch compare against: against a
 50-digit mpmath fixture, against the N x N Cholesky form (the reference's own structural tests, models/gpr.py:135-203 and
 densities.py:159-174), its gradients against central differences -- and the part of gpflowSlim.kernel_kitchen_sink that needs
-no GPU."""
+no GPU.
+
+The named problems of the GPU tests (rr.CASES): the fp64 restatement against the long-double form rr.reference_ld, worst
+quantity under _rel, measured here: 2.3e-14 or less on the fifteen cases at s = 0.15 (cond(A) <= 4.4e3; worst: the
+lengthscale gradient of "r5-f130"); at s = 1e-5 2.2e-11 on "low-257" (cond(A) 1.7e7) and 5.1e-11 on "low-300" (cond(A) 9.1e6),
+both on the predicted mean.  The bound asserted is 1e-10 on every quantity of every case.
+
+What two chunkings may differ by (rr.chunking_spread: A summed in fp64 whole or in 128-row chunks, 8e-16 to 1.4e-15 |A| apart,
+everything after in long double), measured here: 7.6e-15 on "wide" (s = 0.15); 2.2e-11 on "low-257" and 2.4e-11 on "low-300"
+(s = 1e-5) -- more than the 1e-12 of the GPU tests, within rr.chunking_bound = eps cond(A) (3.9e-9, 2.0e-9)."""
 import os
 import sys
 
@@ -94,6 +103,79 @@ def test_linear_and_constant_maps():
     assert np.allclose(rr.linear_features(X, 2.0) @ rr.linear_features(X, 2.0).T, 2.0 * X @ X.T)
     C = rr.constant_features(X, 3.0, 5)
     assert C.shape == (4, 5) and np.allclose(C @ C.T, 3.0)
+
+
+@pytest.mark.parametrize("name", sorted(rr.CASES))
+def test_fp64_restatement_agrees_with_the_long_double_form(name):
+    """A condition on the inputs of tests/test_gpu_rff.py, not on the kernels: on every named case every quantity that lml,
+    predict and lml_grad return agrees between the fp64 restatement and the long-double form to 1e-10."""
+    c = rr.named_case(name)
+    a, b = rr.reference_of(c), rr.reference_of(c, ld=True)
+    want = {"lml", "kinv", "g_s", "mean", "var", "cov"} | ({"g_var"} if c["kind"] != "explicit" else set()) | (
+        {"g_ls"} if c["kind"] == "rbf" else set())
+    assert set(a) == want and set(b) == want
+    worst = {k: _rel(a[k], b[k]) for k in sorted(b)}
+    print(name, " ".join("%s %.1e" % kv for kv in worst.items()))
+    for k, w in worst.items():
+        assert np.shape(a[k]) == np.shape(b[k]) and w <= 1e-10, (name, k, w)
+
+
+@pytest.mark.parametrize("name", ["wide", "linear-13", "low-257", "low-300"])
+def test_what_the_order_of_summation_of_A_moves(name):
+    """The evidence behind the bound test_gpu_rff.py::test_low_noise puts on two chunkings.  At s = 0.15 the order in which fp64
+    sums A = Phi^T Phi moves the mean and K_y^-1 x by less than 1e-12; at s = 1e-5 (cond(A) ~ 1e7) by more than 1e-12 with every
+    later step in long double -- no device evaluation can hold 1e-12 there -- and by less than rr.chunking_bound = eps cond(A)."""
+    c = rr.named_case(name)
+    dA, moved, cond = rr.chunking_spread(c)
+    bound = rr.chunking_bound(c)
+    print("%s: A moved by %.1e |A|, results by %.2e, cond(A) %.1e, bound %.1e" % (name, dA, moved, cond, bound))
+    assert 0.0 < dA <= 16 * np.finfo(np.float64).eps
+    if c["s"] < 1e-3:
+        assert 1e-12 < moved <= bound and 1e-9 <= bound <= 1e-8
+    else:
+        assert moved <= 1e-12 and bound == 1e-12
+
+
+def test_long_double_form_is_long_double():
+    """The written-out Cholesky and substitutions keep np.longdouble (no silent fp64 LAPACK) and invert each other."""
+    rng = np.random.default_rng(2)
+    M = np.asarray(rng.normal(size=(9, 6)), dtype=np.longdouble)
+    A = M.T @ M + np.eye(6, dtype=np.longdouble)
+    L = rr._chol_ld(A)
+    B = np.asarray(rng.normal(size=(6, 2)), dtype=np.longdouble)
+    Z = rr._solve_t_ld(L, rr._solve_ld(L, B))
+    assert L.dtype == np.longdouble and Z.dtype == np.longdouble
+    tol = 64 * float(np.finfo(np.longdouble).eps)
+    assert float(np.abs(L @ L.T - A).max()) <= tol * float(np.abs(A).max())
+    assert float(np.abs(A @ Z - B).max()) <= tol * float(np.abs(A).max() * np.abs(Z).max())
+
+
+@pytest.mark.parametrize("name", ["linear-5", "linear-13", "linear-d32", "constant-1", "constant-33"])
+def test_linear_and_constant_gradients_against_central_differences(name):
+    """d / d variance and d / d s of the Linear and Constant maps at the GPU tests' shapes: central differences of lml, h = 1e-6
+    (truncation and rounding both about 1e-9 of the value: 1e-6 relative), for the fp64 and the long-double form."""
+    c = rr.named_case(name)
+    X, Y, var, s, h = c["X"], c["Y"], c["var"], c["s"], 1e-6
+
+    def f(var_, s_):
+        return rr.lml(rr.features_of(dict(c, var=var_), X), Y, s_)
+
+    fd_var, fd_s = (f(var + h, s) - f(var - h, s)) / (2 * h), (f(var, s + h) - f(var, s - h)) / (2 * h)
+    gv, gl, gs, _ = rr.lml_grad(rr.features_of(c, X), Y, s, var)
+    ld = rr.reference_of(c, ld=True)
+    assert gl is None and "g_ls" not in ld
+    assert _rel(gv, fd_var) <= 1e-6 and _rel(gs, fd_s) <= 1e-6
+    assert _rel(ld["g_var"], fd_var) <= 1e-6 and _rel(ld["g_s"], fd_s) <= 1e-6
+
+
+@pytest.mark.parametrize("k", [1, 2, 3])
+def test_tiled_linear_and_constant_maps_give_the_exact_kernels(k):
+    """linear_features(X, var, k D): Phi Phi^T = var X X^T (kernels.Linear); constant_features: var 1 1^T (kernels.Constant)."""
+    X = np.random.default_rng(k).normal(size=(17, 5))
+    P = rr.linear_features(X, 0.7, 5 * k)
+    assert P.shape == (17, 5 * k) and np.abs(P @ P.T - 0.7 * X @ X.T).max() <= 1e-13 * np.abs(X @ X.T).max()
+    Q = rr.constant_features(X, 1.9, 5 * k)
+    assert Q.shape == (17, 5 * k) and np.abs(Q @ Q.T - 1.9).max() <= 1e-14
 
 
 def test_samplers_construct_without_a_gpu():
