@@ -525,8 +525,8 @@ def test_kernel_matrix_input_vjp(handle, n, m_):
                     else:
                         fd = np.sum(W * (orc.K(spec, Xp, X2) - orc.K(spec, Xm, X2))) / (2 * hh)
                     worst = max(worst, abs(got[i, k] - fd) / max(1.0, abs(fd)))
-            # (Matern-1/2 has a kink at r = 0: the diagonal of K(X, X) contributes nothing in the product, one-sided slopes in
-            # a central difference cancel as well)
+            # (Matern-1/2 has a kink at r = 0; what the kernels do there, and 1e-5 from there, is checked entry by entry in
+            # tests/test_gpu_kmat_vjp.py::test_coincident_points and ::test_points_1e5_apart)
             assert worst <= 5e-6, (kind, worst)
         finally:
             orc.SQUARE_DIST_MODE = saved

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import _kern_ref as kr
+from _kern_ref import spec_of
 
 pytestmark = pytest.mark.gpu
 
@@ -14,33 +15,6 @@ EPS = np.finfo(np.float64).eps
 
 def rel(a, b):
     return float(np.abs(np.asarray(a) - np.asarray(b)).max() / np.abs(b).max())
-
-
-def spec_of(kern, d_all):
-    """the reference spec of a kernel tree, from the constrained values the product itself holds"""
-    import gpflowSlim as gpf
-    k = gpf.kernels
-    if isinstance(kern, (k.Sum, k.Product)):
-        assert not kern.const_list
-        return ("sum" if isinstance(kern, k.Sum) else "product", [spec_of(c, d_all) for c in kern.kern_list])
-    dims = kern._dims(False, d_all)
-
-    def val(x):
-        x = np.asarray(x, dtype=np.float64)
-        return x.copy() if x.size > 1 else float(np.squeeze(x))
-    if isinstance(kern, k.RatQuad):
-        return {"type": "ratquad", "dims": dims, "variance": val(kern.variance), "lengthscales": val(kern.lengthscales), "alpha": val(kern.alpha)}
-    if isinstance(kern, k.Polynomial):
-        return {"type": "polynomial", "dims": dims, "variance": val(kern.variance), "offset": val(kern.offset), "degree": kern.degree}
-    if isinstance(kern, k.Linear):
-        return {"type": "linear", "dims": dims, "variance": val(kern.variance)}
-    if isinstance(kern, k.RBF):
-        return {"type": "rbf", "dims": dims, "variance": val(kern.variance), "lengthscales": val(kern.lengthscales)}
-    if isinstance(kern, k.Periodic):
-        return {"type": "periodic", "dims": dims, "variance": val(kern.variance), "lengthscales": val(kern.lengthscales), "period": val(kern.period)}
-    if isinstance(kern, k.Constant):
-        return {"type": "constant", "dims": [], "variance": val(kern.variance)}
-    raise TypeError(type(kern))
 
 
 def _build_kernels(gpf, d):
