@@ -285,6 +285,10 @@ struct gps_handle_s {
   // valid while factor_gen still is what it was when the factor was made (every entry that rebuilds dK bumps it)
   struct RffFactor { bool have = false; unsigned long long gen = 0; i64 F = 0, r = 0; int kind = -1, d = 0; bool refine = false; } rff;
   DevBuf dGemvWs{bufs}, dGemvCnt{bufs};   // slice partials + arrival counters of the split transposed gemv (blas1.hip)
+  // ---- Kronecker GP regression (gps_kgpr.hip): alpha = (K1 (x) K2 + diag noise)^-1 y [pad(m), pad(n)] in dAlpha ----
+  // valid while factor_gen still is what it was when the solve was made
+  struct KgprSolve { bool have = false; unsigned long long gen = 0; i64 m = 0, n = 0; } kgpr;
+  int kron_cg_check_every = 8;            // option "kron_cg_check_every": the host reads the loop state every this many iterations
 };
 
 static inline int gps_fail(gps_handle_t h, int code, const std::string& msg) {
@@ -534,6 +538,33 @@ int gps_launch_rff_features(gps_handle_t h, const RffDev& p, const double* Xc, i
 int gps_launch_rff_contract(gps_handle_t h, const double* Pt, const double* St, double* Qt, const double* Et, i64 lde,
                             const double* Crows, i64 ldc, i64 r, double inv_s, double R, i64 nc, i64 Fp, double* partial,
                             double* acc, int first);
+// kron.hip : the conjugate-gradient loop of Kronecker GP regression (conjugate_gradient.py:28-55) and the spectrum sums of its
+// log-determinant (kgpr.py:67-74).  Vectors are [pad(m), pad(n)] row-major, zero padded; total = pad(m) * pad(n).
+#define KRON_MAX_BLOCKS 2048
+// loop state on the device, slots by iteration parity (see kron.hip)
+struct KronCgState { double rr[2]; double delta, bb; long long k[2]; int done[2]; int max_iter, pad; };
+int gps_kron_blocks(i64 total);                 // workgroups (= partial sums) of the vector kernels
+int gps_kron_spectrum_blocks(i64 m);            // ... of the rows pass of the spectrum
+// Ys, Ms [m, n] as uploaded -> Yp, C = (noise_var + GPS_KGPR_MASK_NOISE * mask)^(-1/2), B = C o Y
+int gps_launch_kron_prep(gps_handle_t h, const double* Ys, const double* Ms, i64 m, i64 n, double noise_var, double* Yp, double* C,
+                         double* B);
+// r holds b: p = b, x = 0, S = C o b, slot 0 of the state; part: room for gps_kron_blocks doubles
+int gps_launch_kron_cg_init(gps_handle_t h, KronCgState* st, const double* r, const double* C, double* p, double* x, double* S,
+                            i64 total, double tol, int max_iter, double* part);
+// iteration `it` after Z = K1 (C o p) K2:  Ap = C o Z + p over Z ; x, r ; p, S and the next state
+int gps_launch_kron_cg_apply(gps_handle_t h, const KronCgState* st, int it, const double* C, double* ZAp, const double* p, i64 total,
+                             double* part);
+int gps_launch_kron_cg_update(gps_handle_t h, const KronCgState* st, int it, const double* part_pap, const double* p,
+                              const double* Ap, double* x, double* r, i64 total, double* part_rr);
+int gps_launch_kron_cg_dir(gps_handle_t h, KronCgState* st, int it, const double* part_rr, const double* r, double* p,
+                           const double* C, double* S, i64 total);
+// alpha = C o x ; part2 [gps_kron_blocks][2] = partial sums of Y o alpha (Y may be null) and alpha^2
+int gps_launch_kron_alpha(gps_handle_t h, const double* C, const double* x, const double* Y, double* alpha, i64 total,
+                          double* part2);
+// sorted e1 [m], e2 [n], per-row ranges rng [m][2] of e2 (0 <= lo <= hi <= n: the caller checks), den_ij = s e1_i e2_j + noise_var:
+// part2 [gps_kron_spectrum_blocks][2] = partial sums of log den and 1 / den, w1 [m] ; w2 [n] (null: no columns pass)
+int gps_launch_kron_spectrum(gps_handle_t h, const double* e1, const double* e2, const int* rng, i64 m, i64 n, double s,
+                             double noise_var, double* w1, double* w2, double* part2);
 // diag.hip
 int gps_run_mfma_diag(gps_handle_t h, int waves_per_simd, double* tflops, int* layout_ok);
 int gps_run_gemm_timeline(gps_handle_t h, int op, int lower, i64 m, i64 n, i64 k, int reps, long long* stamps_out,

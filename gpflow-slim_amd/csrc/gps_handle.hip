@@ -165,6 +165,7 @@ extern "C" int gps_set_option(gps_handle_t h, const char* key, double value) {
   }
   if (strcmp(key, "predict_inverse_blocks") == 0) { h->predict_inv_blocks = (int)value; return GPS_OK; }
   if (strcmp(key, "trsv_wave_refine") == 0) { h->trsv_wave_refine = (int)value; return GPS_OK; }
+  if (strcmp(key, "kron_cg_check_every") == 0) { h->kron_cg_check_every = (int)value < 1 ? 1 : (int)value; return GPS_OK; }
   return gps_fail(h, GPS_ERR_ARG, "unknown option");
 }
 

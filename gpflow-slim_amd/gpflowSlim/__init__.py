@@ -16,6 +16,7 @@ from . import likelihoods
 from . import conditionals
 from . import features
 from . import kullback_leiblers
+from . import conjugate_gradient
 from . import models
 from . import neural_kernel_network
 from ._backend import NotPositiveDefiniteError, get_handle, set_handle, Handle, load_library

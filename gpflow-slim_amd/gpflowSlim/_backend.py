@@ -180,6 +180,18 @@ _SIGNATURES = {
                          _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_int_p],
     "gps_rff_predict": [ctypes.c_void_p, ctypes.POINTER(RffDesc), _c_double_p, _i64, ctypes.c_double, _c_double_p, _i64, _i64,
                         _c_double_p, _i64, ctypes.c_int, ctypes.c_int, _c_double_p, _c_double_p, _c_int_p],
+    "gps_kron_cg": [ctypes.c_void_p, _c_double_p, _i64, _c_double_p, _i64, _c_double_p, _c_double_p, ctypes.c_int, ctypes.c_double,
+                    _c_double_p, ctypes.POINTER(_i64), _c_double_p, _c_double_p],
+    "gps_kgpr_lml": [ctypes.c_void_p, ctypes.POINTER(KernNode), ctypes.c_int, _c_double_p, _i64, _i64, ctypes.POINTER(KernNode),
+                     ctypes.c_int, _c_double_p, _i64, _i64, _c_double_p, _c_double_p, ctypes.c_double, _c_double_p, _c_double_p,
+                     ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_double, _c_double_p],
+    "gps_kgpr_lml_grad": [ctypes.c_void_p, ctypes.POINTER(KernNode), ctypes.c_int, _c_double_p, _i64, _i64,
+                          ctypes.POINTER(KernNode), ctypes.c_int, _c_double_p, _i64, _i64, _c_double_p, _c_double_p,
+                          ctypes.c_double, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_double,
+                          _c_double_p, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int, _c_int_p, _c_double_p, ctypes.c_int,
+                          _c_int_p, _c_double_p],
+    "gps_kgpr_predict": [ctypes.c_void_p, ctypes.POINTER(KernNode), ctypes.c_int, _c_double_p, _i64, _i64, _c_double_p, _i64,
+                         ctypes.POINTER(KernNode), ctypes.c_int, _c_double_p, _i64, _i64, _c_double_p, _i64, _c_double_p],
     "gps_sparse_last_terms": [ctypes.c_void_p, _c_double_p],
     "gps_profile_enable": [ctypes.c_void_p, ctypes.c_int],
     "gps_profile_reset": [ctypes.c_void_p],
@@ -897,6 +909,83 @@ class Handle(object):
                                               _ptr(mean), _ptr(var), ctypes.byref(info)), "gps_rff_predict")
         self._rff_info(info)
         return mean, var
+
+    # ---- Kronecker GP regression (conjugate_gradient.py, models/kgpr.py)
+    def kron_cg(self, K1, K2, B, C, max_iter=100, tol=1e-6):
+        """gps_kron_cg: cgsolver on (I + C o (K1 (C o .) K2)) x = B with every vector the [m, n] matrix it came from:
+        (x [m, n], iterations, the last r^T r, delta = tol * |B|)."""
+        K1, K2, B, C = _f64(K1), _f64(K2), _f64(B), _f64(C)
+        _need(K1.ndim == 2 and K1.shape[0] == K1.shape[1] and K2.ndim == 2 and K2.shape[0] == K2.shape[1],
+              "K1 and K2 must be square")
+        m, n = K1.shape[0], K2.shape[0]
+        _need(B.shape == (m, n) and C.shape == (m, n), "b and C must be [%d, %d]" % (m, n))
+        x = np.zeros((m, n))
+        iters, rr, delta = _i64(0), ctypes.c_double(0), ctypes.c_double(0)
+        self.resident_token = None
+        self.factor_key = None
+        self._check(self._lib.gps_kron_cg(self._h, _ptr(K1), m, _ptr(K2), n, _ptr(B), _ptr(C), int(max_iter), float(tol), _ptr(x),
+                                          ctypes.byref(iters), ctypes.byref(rr), ctypes.byref(delta)), "gps_kron_cg")
+        return x, iters.value, rr.value, delta.value
+
+    @staticmethod
+    def _kgpr_args(X1, X2, Y, mask, e1, e2, sel):
+        X1, X2, Y, mask, e1, e2 = _f64(X1), _f64(X2), _f64(Y), _f64(mask), _f64(e1), _f64(e2)
+        sel = np.ascontiguousarray(sel, dtype=np.int32)
+        _need(X1.ndim == 2 and X2.ndim == 2 and X1.shape[0] > 0 and X2.shape[0] > 0 and X1.shape[1] > 0 and X2.shape[1] > 0,
+              "KGPR needs non-empty X1 [m, d1] and X2 [n, d2]")
+        m, n = X1.shape[0], X2.shape[0]
+        _need(Y.shape == (m, n) and mask.shape == (m, n), "Y and mask must be [%d, %d]" % (m, n))
+        _need(e1.shape == (m,) and e2.shape == (n,) and sel.shape == (m, 2), "e1 [m], e2 [n] and the ranges [m, 2] do not fit the grid")
+        return X1, X2, Y, mask, e1, e2, sel, m, n
+
+    @staticmethod
+    def _kgpr_out(out):
+        return dict(lml=out[0], quadratic=out[1], logdet=out[2], iters=int(out[3]), rr=out[4], delta=out[5])
+
+    def kgpr_lml(self, prog1, X1, prog2, X2, Y, mask, noise_var, e1, e2, sel, max_iter=100, tol=1e-6):
+        """gps_kgpr_lml: dict(lml, quadratic, logdet, iters, rr, delta); alpha stays resident for kgpr_predict."""
+        X1, X2, Y, mask, e1, e2, sel, m, n = self._kgpr_args(X1, X2, Y, mask, e1, e2, sel)
+        out = np.zeros(6)
+        self.resident_token = None
+        self.factor_key = None
+        self._check(self._lib.gps_kgpr_lml(self._h, prog1, len(prog1), _ptr(X1), m, X1.shape[1], prog2, len(prog2), _ptr(X2), n,
+                                           X2.shape[1], _ptr(Y), _ptr(mask), float(noise_var), _ptr(e1), _ptr(e2),
+                                           sel.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(max_iter), float(tol),
+                                           _ptr(out)), "gps_kgpr_lml")
+        return self._kgpr_out(out)
+
+    def kgpr_lml_grad(self, prog1, X1, prog2, X2, Y, mask, noise_var, e1, e2, sel, V1, V2, max_iter=100, tol=1e-6):
+        """gps_kgpr_lml_grad: (the dict of kgpr_lml, slots of prog1, slots of prog2, d / d noise_var)."""
+        X1, X2, Y, mask, e1, e2, sel, m, n = self._kgpr_args(X1, X2, Y, mask, e1, e2, sel)
+        V1, V2 = _f64(V1), _f64(V2)
+        _need(V1.shape == (m, m) and V2.shape == (n, n), "V1 must be [m, m] and V2 [n, n]")
+        out = np.zeros(6)
+        cap = 700
+        s1, s2 = np.zeros(cap), np.zeros(cap)
+        n1, n2 = ctypes.c_int(0), ctypes.c_int(0)
+        gnoise = ctypes.c_double(0)
+        self.resident_token = None
+        self.factor_key = None
+        self._check(self._lib.gps_kgpr_lml_grad(self._h, prog1, len(prog1), _ptr(X1), m, X1.shape[1], prog2, len(prog2), _ptr(X2),
+                                                n, X2.shape[1], _ptr(Y), _ptr(mask), float(noise_var), _ptr(e1), _ptr(e2),
+                                                sel.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(max_iter), float(tol),
+                                                _ptr(out), _ptr(V1), _ptr(V2), _ptr(s1), cap, ctypes.byref(n1), _ptr(s2), cap,
+                                                ctypes.byref(n2), ctypes.byref(gnoise)), "gps_kgpr_lml_grad")
+        return self._kgpr_out(out), s1[:n1.value].copy(), s2[:n2.value].copy(), gnoise.value
+
+    def kgpr_predict(self, prog1, X1, Xnew1, prog2, X2, Xnew2):
+        """gps_kgpr_predict: K1u^T alpha K2u [m*, n*] from the alpha the last kgpr_lml / kgpr_lml_grad left resident."""
+        X1, X2, Xnew1, Xnew2 = _f64(X1), _f64(X2), _f64(Xnew1), _f64(Xnew2)
+        _need(X1.ndim == 2 and X2.ndim == 2 and X1.shape[0] > 0 and X2.shape[0] > 0, "KGPR needs non-empty X1 [m, d1] and X2 [n, d2]")
+        _need(Xnew1.ndim == 2 and Xnew1.shape[1] == X1.shape[1], "Xnew1 must be [m*, %d]" % X1.shape[1])
+        _need(Xnew2.ndim == 2 and Xnew2.shape[1] == X2.shape[1], "Xnew2 must be [n*, %d]" % X2.shape[1])
+        mean = np.empty((Xnew1.shape[0], Xnew2.shape[0]))
+        if mean.size == 0:
+            return mean
+        self._check(self._lib.gps_kgpr_predict(self._h, prog1, len(prog1), _ptr(X1), X1.shape[0], X1.shape[1], _ptr(Xnew1),
+                                               Xnew1.shape[0], prog2, len(prog2), _ptr(X2), X2.shape[0], X2.shape[1], _ptr(Xnew2),
+                                               Xnew2.shape[0], _ptr(mean)), "gps_kgpr_predict")
+        return mean
 
     # ---- SGPR
     def sgpr(self, prog, Z, X, resid, jitter, noise_var, Xnew=None, full_cov=False, want_bound=True, fitc=False):

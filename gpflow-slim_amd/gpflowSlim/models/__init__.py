@@ -3,3 +3,4 @@ from .gpr import GPR
 from .svgp import SVGP
 from .sgpr import SGPR, GPRFITC
 from .gplvm import BayesianGPLVM, PCA_reduce
+from .kgpr import KGPR

@@ -222,6 +222,41 @@ int gps_rff_predict(gps_handle_t h, const gps_rff_desc_t* desc, const double* X,
                     const double* resid, int64_t r, int64_t chunk_rows, const double* Xnew, int64_t n_new, int full_cov,
                     int refactor, double* mean_out, double* var_out, int* info);
 
+/* ---- Kronecker GP regression: conjugate gradients on K1 (x) K2 -------------------------------------
+ * models/kgpr.py:28-117 over conjugate_gradient.py:18-55.  Observations Y [m, n] on the grid X1 [m, d1] x X2 [n, d2], covariance
+ * K1 (x) K2 with K1 = kern1.K(X1), K2 = kern2.K(X2); mask [m, n] (1.0 = missing cell) adds GPS_KGPR_MASK_NOISE to that cell's noise
+ * (kgpr.py:52).  The reference's vec is column-major (conjugate_gradient.py:22-25); every vector here is the [m, n] matrix it
+ * came from, row-major, and no N x N matrix (N = m n) is formed.                                                            */
+#define GPS_KGPR_MASK_NOISE 1e6
+/* cgsolver (conjugate_gradient.py:28-55) on host matrices: (I + C o (K1 (C o .) K2)) x = B by plain CG from x = 0 in the
+ * reference's update order, while tol * |B| < r^T r and k < max_iter (a norm against a squared norm, :29, :46-49).
+ * K1 [m, m], K2 [n, n], B, C, X_out [m, n]; iters, rr (the last r^T r), delta (tol * |B|) optional.  m == 0 or n == 0: nothing. */
+int gps_kron_cg(gps_handle_t h, const double* K1, int64_t m, const double* K2, int64_t n, const double* B, const double* C,
+                int max_iter, double tol, double* X_out, int64_t* iters, double* rr, double* delta);
+/* KGPR._build_likelihood (kgpr.py:57-83) with cgsolver(max_iter, tol).  e1 [m], e2 [n]: the eigenvalues of K1 and K2, each
+ * sorted (either direction); sel [m][2]: per row i of e1 the range [lo, hi) of e2 whose products e1_i e2_j are among the
+ * M = N - sum(mask) largest (kgpr.py:72: tf.nn.top_k) -- the ranges must hold M pairs in all.  The eigenvalues are not clamped.
+ * out [6] = lml, the quadratic term sum Y o alpha, logdet, CG iterations, the last r^T r, delta.
+ * Leaves alpha = (K + diag noise)^-1 y resident for gps_kgpr_predict.                                                      */
+int gps_kgpr_lml(gps_handle_t h, const gps_kern_node_t* prog1, int n_nodes1, const double* X1, int64_t m, int64_t d1,
+                 const gps_kern_node_t* prog2, int n_nodes2, const double* X2, int64_t n, int64_t d2, const double* Y,
+                 const double* mask, double noise_var, const double* e1, const double* e2, const int32_t* sel, int max_iter,
+                 double tol, double* out);
+/* ... and its gradient with respect to the CONSTRAINED values, analytic at the solution (exact once CG has converged; the
+ * reference differentiates through the unrolled loop): V1 [m, m], V2 [n, n] the eigenvectors, column k belonging to e1[k] /
+ * e2[k]; slots1 / slots2 in the slot layout of gps_kmat_vjp for prog1 / prog2; grad_noise = d / d noise_var.                */
+int gps_kgpr_lml_grad(gps_handle_t h, const gps_kern_node_t* prog1, int n_nodes1, const double* X1, int64_t m, int64_t d1,
+                      const gps_kern_node_t* prog2, int n_nodes2, const double* X2, int64_t n, int64_t d2, const double* Y,
+                      const double* mask, double noise_var, const double* e1, const double* e2, const int32_t* sel, int max_iter,
+                      double tol, double* out, const double* V1, const double* V2, double* slots1, int cap1, int* n_slots1,
+                      double* slots2, int cap2, int* n_slots2, double* grad_noise);
+/* KGPR._build_predict (kgpr.py:86-110): mean_out host [m_new, n_new] = K1u^T alpha K2u from the alpha the last gps_kgpr_lml /
+ * _lml_grad left on the handle (X1, X2, the programs unchanged -- the caller vouches); GPS_ERR_STATE if there is none.  The mean
+ * only, as in the reference.                                                                                                */
+int gps_kgpr_predict(gps_handle_t h, const gps_kern_node_t* prog1, int n_nodes1, const double* X1, int64_t m, int64_t d1,
+                     const double* Xnew1, int64_t m_new, const gps_kern_node_t* prog2, int n_nodes2, const double* X2, int64_t n,
+                     int64_t d2, const double* Xnew2, int64_t n_new, double* mean_out);
+
 /* ---- conditionals.conditional / base_conditional ------------------------
  * (conditionals.py:24-66, 80-121; features.py:74-81 for Kuu/Kuf).
  * Device-resident form: Kmm = kern.K(Z) + jitter*I, Kmn = kern.K(Z, Xnew) are
@@ -641,6 +676,9 @@ int gps_dist_finish(gps_handle_t h, double* lml, int* info);
  *                     programs too; 0: never
  *   "svgp_kl_weight"  weight of the KL term of gps_svgp_elbo(_grad) (default 1; 1 / P on every rank of a data-sharded run)
  *   "dist_partitioned" 1 (default): a rank of the block-column factorisation stores only its own block columns (8 N^2 / P bytes)
+ *   "kron_cg_check_every" 8 (default): the conjugate-gradient loop of gps_kron_cg / gps_kgpr_* keeps its state on the device; the
+ *                     host reads it every this many iterations and stops launching once the stop rule holds (the result does
+ *                     not depend on the value)
  *   "la_fault_inject" / "wave_fault_inject" / "small_fault_inject"  test hooks: the k-th look-ahead join / wavefront substitution /
  *                     cooperative small-N launch from now takes its give-up path (the evaluation is then re-run once through the
  *                     launch-by-launch forms; gps_profile_get(h, "lookahead_retries" | "trsv_wave_fallbacks" | "small_n_fallbacks",
