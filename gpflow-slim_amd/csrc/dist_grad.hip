@@ -33,75 +33,67 @@ __global__ __launch_bounds__(256) void dist_grad_eye_kernel(double* __restrict__
 }
 
 static inline i64 dg_owned_upto(gps_handle_t h, i64 j) {          // owned block columns c <= j
-  if (j < h->dist_rank) return 0;
-  const i64 k = (j - h->dist_rank) / h->dist_P + 1;
-  return k < h->dist_ncl ? k : h->dist_ncl;
+  if (j < h->dist.rank) return 0;
+  const i64 k = (j - h->dist.rank) / h->dist.P + 1;
+  return k < h->dist.ncl ? k : h->dist.ncl;
 }
 
-#define DG_CHECK(h, j, buf)                                                                                        \
-  if (!h || !h->dist_grad_ready || !h->dist_have_part_factor || h->dist_nb <= 0 || j < 0 || j * h->dist_nb >= h->dist_np) \
-    return gps_fail(h, GPS_ERR_STATE, "gps_dist_grad_*: bad panel index or gps_dist_grad_begin not called");        \
-  if (buf < 0 || buf >= h->dist_ncomm || !h->dist_comm[buf])                                                       \
-    return gps_fail(h, GPS_ERR_STATE, "gps_dist_set_comm has not been called");                                     \
-  GPS_HIP(h, hipSetDevice(h->device));                                                                             \
-  h->refine_now = h->factor_refine;                                                                                \
-  const i64 np = h->dist_np, nb = h->dist_nb;                                                                      \
-  const i64 rows = np + GPS_TILE - j * nb, nbb = nb / GPS_TILE;                                                    \
-  const i64 below = np - (j + 1) * nb;                                                                             \
-  double* const msg = h->dist_comm[buf];                                                                           \
-  double* const Z = h->dDistZ.d();                                                                                 \
-  HipOps ops{h, msg + rows * nb, msg + rows * nb + nbb * GPS_TILE * GPS_TILE, (int*)h->dInfo.p};                     \
-  Blocked<HipOps> bl(ops);
+// every step of the two streams starts here: the view of panel j, its message in comm slot buf
+static int dg_step(gps_handle_t h, i64 j, int buf, DistPanel* v, double** msg) {
+  static const char* const what = "gps_dist_grad_*: bad panel index or gps_dist_grad_begin not called";
+  if (!h || !h->dist.grad_ready || !h->dist.have_part_factor) return gps_fail(h, GPS_ERR_STATE, what);
+  int rc = dist_panel(h, j, v, GPS_ERR_STATE, what);
+  return rc ? rc : dist_slot(h, buf, msg);
+}
 
 extern "C" int gps_dist_grad_begin(gps_handle_t h) {
   if (!h) return GPS_ERR_ARG;
-  if (!h->dist_have_part_factor || !h->dist_part || h->dist_nb <= 0)
+  if (!h->dist.have_part_factor || !h->dist.part || h->dist.nb <= 0)
     return gps_fail(h, GPS_ERR_STATE, "gps_dist_grad_begin: no partitioned factor (run the distributed factorisation first)");
   GPS_HIP(h, hipSetDevice(h->device));
-  const i64 np = h->dist_np, nb = h->dist_nb, ncols = h->dist_ncl * nb;
+  const i64 np = h->dist.np, nb = h->dist.nb, ncols = h->dist.ncl * nb;
   GPS_HIP(h, h->dDistZ.ensure((size_t)(GPS_TILE + ncols) * np * 8));
   GPS_HIP(h, h->dDistPT.ensure((size_t)nb * np * 8));
   GPS_HIP(h, hipMemsetAsync(h->dDistZ.p, 0, (size_t)(GPS_TILE + ncols) * np * 8, h->stream));
   if (ncols > 0) {
     LaunchScope ls(h, KC_OTHER, 0.0, 8.0 * (double)ncols);
     hipLaunchKernelGGL(dist_grad_eye_kernel, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, h->stream, h->dDistZ.d(), np, ncols,
-                       nb, h->dist_P, h->dist_rank);
+                       nb, h->dist.P, h->dist.rank);
     GPS_HIP(h, hipGetLastError());
   }
-  h->dist_grad_ready = true;
+  h->dist.grad_ready = true;
   return GPS_OK;
 }
 
-// forward stream, panel j (any comm slot; the message of gps_dist_solve_pack)
+// forward stream, panel j (any comm slot; the message of gps_dist_solve_pack): the step of gps_dist_solve_apply with the identity
+// columns as right-hand sides -- block column j of Z^T [m, nb], ld np -- and alpha_j^T picked up as the panel passes
 extern "C" int gps_dist_grad_fwd_apply(gps_handle_t h, int64_t j, int buf) {
-  DG_CHECK(h, j, buf)
-  // alpha_j^T: the augmented rows of the panel
-  if (h->dist_r > 0)
-    GPS_HIP(h, hipMemcpy2DAsync(Z + j * nb, (size_t)np * 8, msg + (rows - GPS_TILE) * nb, (size_t)nb * 8, (size_t)nb * 8,
-                                (size_t)h->dist_r, hipMemcpyDeviceToDevice, h->stream));
-  const i64 m = dg_owned_upto(h, j) * nb;
-  if (m == 0) return GPS_OK;
-  double* Bj = Z + GPS_TILE * np + j * nb;                       // [m, nb] block column j of Z^T, ld np
-  int rc = bl.trsm_rec(msg, nb, nb, 0, Bj, np, m);               // Z^T_j <- Z^T_j L_jj^-T
+  DistPanel v;
+  double* msg;
+  int rc = dg_step(h, j, buf, &v, &msg);
   if (rc) return rc;
-  if (below > 0) rc = gps_launch_gemm_nt(h, 0, 0, m, below, nb, Bj, np, msg + nb * nb, nb, Bj + nb, np);   // Z^T_{>j} -= Z^T_j L[>j, j]^T
-  return rc;
+  double* Z = h->dDistZ.d();
+  return dist_forward_step(h, v, msg, Z + GPS_TILE * v.np + j * v.nb, v.np, dg_owned_upto(h, j) * v.nb, Z + j * v.nb);
 }
 
 // backward stream, panel j (j descending), in place over Z^T; rows 0..127 carry alpha^T -> A^T
 extern "C" int gps_dist_grad_bwd_apply(gps_handle_t h, int64_t j, int buf) {
-  DG_CHECK(h, j, buf)
-  const i64 m = GPS_TILE + dg_owned_upto(h, j) * nb;
+  DistPanel v;
+  double* msg;
+  int rc = dg_step(h, j, buf, &v, &msg);
+  if (rc) return rc;
+  const i64 np = v.np, nb = v.nb, m = GPS_TILE + dg_owned_upto(h, j) * nb;
   double* PT = h->dDistPT.d();
   // U = [L_jj ; L[>j, j]]^T  [nb, np - j nb]: L_jj^T (the upper factor trsm_rn_rec takes) then L[>j, j]^T (the B operand)
-  int rc = gps_launch_transpose(h, msg, nb, np - j * nb, nb, PT, np);
+  rc = gps_launch_transpose(h, v.body(msg), nb, np - j * nb, nb, PT, np);
   if (rc) return rc;
-  double* Xj = Z + j * nb;
-  if (below > 0) {
-    rc = gps_launch_gemm_nt(h, 0, 0, m, nb, below, Xj + nb, np, PT + nb, np, Xj, np);     // X^T_j -= X^T_{>j} L[>j, j]
+  double* Xj = h->dDistZ.d() + j * nb;
+  if (v.below > 0) {
+    rc = gps_launch_gemm_nt(h, 0, 0, m, nb, v.below, Xj + nb, np, PT + nb, np, Xj, np);     // X^T_j -= X^T_{>j} L[>j, j]
     if (rc) return rc;
   }
-  return bl.trsm_rn_rec(PT, np, nb, 0, Xj, np, m);              // X^T_j <- X^T_j L_jj^-1
+  HipOps ops = dist_msg_ops(h, v, msg);
+  return Blocked<HipOps>(ops).trsm_rn_rec(PT, np, nb, 0, Xj, np, m);              // X^T_j <- X^T_j L_jj^-1
 }
 
 // this rank's raw slot sums (no lengthscale division: gps_dist_grad_fold adds the ranks' sums first) and K_y^-1 resid
@@ -110,7 +102,7 @@ extern "C" int gps_dist_grad_local(gps_handle_t h, const gps_kern_node_t* prog, 
                                    int* n_slots_out, double* kinv_resid_out) {
   if (!h || !prog || !sums_out) return gps_fail(h, GPS_ERR_ARG, "gps_dist_grad_local: bad argument");
   // (the partitioned factor the streams ran on must still be there: gpr_set_data and every other factorisation drop it)
-  if (!h->dist_grad_ready || !h->dist_have_part_factor)
+  if (!h->dist.grad_ready || !h->dist.have_part_factor)
     return gps_fail(h, GPS_ERR_STATE, "gps_dist_grad_local: gps_dist_grad_begin has not been called on the current partitioned factor");
   GPS_HIP(h, hipSetDevice(h->device));
   int ns = 0;
@@ -118,7 +110,7 @@ extern "C" int gps_dist_grad_local(gps_handle_t h, const gps_kern_node_t* prog, 
   if (rc) return rc;
   if (n_slots_out) *n_slots_out = ns;
   if (ns + 1 > cap) return gps_fail(h, GPS_ERR_ARG, "gps_dist_grad_local: sums_out too small (n_slots + 1)");
-  const i64 n = h->n, np = h->dist_np, nb = h->dist_nb, r = h->dist_r;
+  const i64 n = h->n, np = h->dist.np, nb = h->dist.nb, r = h->dist.r;
   const double* At = h->dDistZ.d();                              // [r][np]
   const double* Kt = h->dDistZ.d() + GPS_TILE * np;              // [ncl nb][np]
   if (kinv_resid_out && r > 0) {
@@ -129,7 +121,7 @@ extern "C" int gps_dist_grad_local(gps_handle_t h, const gps_kern_node_t* prog, 
     GPS_HIP(h, hipStreamSynchronize(h->stream));
   }
   GradCyclic cyc;
-  cyc.P = h->dist_P; cyc.rank = h->dist_rank; cyc.nb = nb; cyc.ncols = h->dist_ncl * nb; cyc.kinv_t = 1;
+  cyc.P = h->dist.P; cyc.rank = h->dist.rank; cyc.nb = nb; cyc.ncols = h->dist.ncl * nb; cyc.kinv_t = 1;
   return gps_launch_grad(h, prog, n_nodes, h->dX.d(), n, h->d_all, np, Kt, np, At, np, r, &cyc, sums_out, sums_out + ns);
 }
 
@@ -157,35 +149,17 @@ extern "C" int gps_dist_grad_fold(gps_handle_t h, const gps_kern_node_t* prog, i
 }
 
 // ---- the whole distributed gradient driven from here (native communicator; no host language per panel) --------------------
-// gpflowSlim/distributed.py::grad_stream_schedule, statement for statement: 2 n_panels steps k (forward: panel k; backward:
-// panel 2 n_panels - 1 - k), two comm slots alternating, the exchange of step k + 1 in flight while step k is applied (the
-// pack of step k + 1 is stream-ordered after apply(k - 1), the last reader of its slot).
+// panel_stream_schedule (dist_schedule.hpp; gpflowSlim/distributed.py::grad_stream_schedule is its Python caller): 2 n_panels
+// steps k, forward over panel k, then backward over panel 2 n_panels - 1 - k, on the comm buffers gps_dist_lml left.
 static int dg_streams(gps_handle_t h, int exchange_mode) {
-  const int P = h->comm_world, rank = h->comm_rank;
-  const i64 n_panels = h->dist_np / h->dist_nb;
+  const i64 n_panels = h->dist.np / h->dist.nb;
   void* bufs[2] = {h->dDistComm[0].p, h->dDistComm[1].p};
   int rc = gps_dist_set_comm_bufs(h, bufs, 2);
   if (rc) return rc;
   rc = gps_dist_grad_begin(h);
   if (rc) return rc;
-  auto panel = [&](i64 k) -> i64 { return k < n_panels ? k : 2 * n_panels - 1 - k; };
-  auto send = [&](i64 k) -> int {
-    const i64 j = panel(k);
-    const int buf = (int)(k % 2);
-    if (rank == (int)(j % P)) { int rcc = gps_dist_solve_pack(h, j, buf); if (rcc) return rcc; }
-    int64_t n = 0;
-    int rcc = gps_dist_msg_doubles(h, j, &n);
-    if (rcc) return rcc;
-    return gps_comm_exchange(h, bufs[buf], ((n + P - 1) / P) * P, (int)(j % P), exchange_mode, (int)(k % 8));
-  };
-  rc = send(0);
-  for (i64 k = 0; k < 2 * n_panels && !rc; ++k) {
-    rc = gps_comm_wait(h, (int)(k % 8));
-    if (!rc && k + 1 < 2 * n_panels) rc = send(k + 1);
-    if (!rc) rc = k < n_panels ? gps_dist_grad_fwd_apply(h, panel(k), (int)(k % 2)) : gps_dist_grad_bwd_apply(h, panel(k), (int)(k % 2));
-  }
-  if (rc) { (void)hipStreamSynchronize(h->stream); if (h->comm_stream) (void)hipStreamSynchronize(h->comm_stream); }
-  return rc;
+  return dist_stream_panels(h, exchange_mode, 2 * n_panels, [=](i64 k) { return k < n_panels ? k : 2 * n_panels - 1 - k; },
+                            [=](i64 k, i64 j, int buf) { return k < n_panels ? gps_dist_grad_fwd_apply(h, j, buf) : gps_dist_grad_bwd_apply(h, j, buf); });
 }
 
 extern "C" int gps_dist_lml_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double noise_var, const double* resid,
@@ -193,7 +167,7 @@ extern "C" int gps_dist_lml_grad(gps_handle_t h, const gps_kern_node_t* prog, in
                                  int n_slots_cap, int* n_slots_out, double* grad_noise, double* kinv_resid, int* info) {
   if (!h || !prog || !lml || !grad_slots || !grad_noise || r <= 0) return gps_fail(h, GPS_ERR_ARG, "gps_dist_lml_grad: bad argument");
   if (!h->comm) return gps_fail(h, GPS_ERR_STATE, "gps_dist_lml_grad: the handle has no communicator (gps_comm_init)");
-  if (!h->dist_partitioned) return gps_fail(h, GPS_ERR_STATE, "gps_dist_lml_grad: needs partitioned storage (option dist_partitioned = 1)");
+  if (!h->dist.partitioned) return gps_fail(h, GPS_ERR_STATE, "gps_dist_lml_grad: needs partitioned storage (option dist_partitioned = 1)");
   int ns = 0;
   int rc = gps_grad_slots(h, prog, n_nodes, &ns);
   if (rc) return rc;

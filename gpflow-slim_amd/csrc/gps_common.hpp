@@ -213,33 +213,35 @@ struct gps_handle_s {
   DevBuf dVar{bufs};      // [n_new] or [nspad, nspad]
   DevBuf dKdiag{bufs};    // [n] per-point Kdiag of a program with Linear / Polynomial (gps_launch_kdiag_vec)
   // ---- block-column distributed factorisation (gps_dist_*) ----
-  int dist_P = 0, dist_rank = 0;
-  i64 dist_nb = 0, dist_np = 0, dist_r = 0;
-  double* dist_comm[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  int dist_ncomm = 0;
-  // partitioned storage (option "dist_partitioned", default 1): dK holds ONLY the owned block columns, side by side
-  // ([np + 128 rows][ncl * nb], ncl = owned block columns): 8 N^2 / P bytes per rank; a panel is read by the trailing
-  // updates straight from the comm buffer it arrived in (slot = panel % number of comm buffers, >= 3 of them)
-  int dist_partitioned = 1;
-  bool dist_part = false;          // mode of the factorisation gps_dist_begin started
-  i64 dist_ld = 0, dist_ncl = 0;
-  bool dist_have_part_factor = false;
-  i64 dist_solve_n = 0;            // test points of the running gps_dist_solve_* pass
+  struct Dist {
+    int P = 0, rank = 0;
+    i64 nb = 0, np = 0, r = 0;
+    double* comm[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    int ncomm = 0;
+    // partitioned storage (option "dist_partitioned", default 1): dK holds ONLY the owned block columns, side by side
+    // ([np + 128 rows][ncl * nb], ncl = owned block columns): 8 N^2 / P bytes per rank; a panel is read by the trailing
+    // updates straight from the comm buffer it arrived in (slot = panel % number of comm buffers, >= 3 of them)
+    int partitioned = 1;
+    bool part = false;               // mode of the factorisation gps_dist_begin started
+    i64 ld = 0, ncl = 0;
+    bool have_part_factor = false;
+    i64 solve_n = 0;                 // test points of the running gps_dist_solve_* pass
+    hipStream_t bulk_stream = nullptr; bool bulk_set = false;   // second lane of the distributed schedule
+    // gps_dist_lml's own two lanes (high / low priority) and its event pool: created once per handle, not per evaluation
+    hipStream_t chain = nullptr, bulk_own = nullptr;
+    std::vector<hipEvent_t> events; size_t event_next = 0;
+    bool grad_ready = false;         // gps_dist_grad_begin ran on the current partitioned factor
+  } dist;
   // native collectives (comm_rccl.hip): an RCCL communicator of this handle's own, its stream and events
   void* comm = nullptr; int comm_rank = 0, comm_world = 1;
   hipStream_t comm_stream = nullptr;
   hipEvent_t comm_ready = nullptr, comm_done[8] = {};
-  hipStream_t dist_bulk_stream = nullptr; bool dist_bulk_set = false;   // second lane of the distributed schedule
-  // gps_dist_lml's own two lanes (high / low priority) and its event pool: created once per handle, not per evaluation
-  hipStream_t dist_chain = nullptr, dist_bulk_own = nullptr;
-  std::vector<hipEvent_t> dist_events; size_t dist_event_next = 0;
   DevBuf dDistScal{bufs};                 // [n_panels][4] per-panel sum log L_ii, sum alpha^2, info
   DevBuf dDistComm[3]{{bufs}, {bufs}, {bufs}};   // comm buffers of gps_dist_lml (the all-native driver; other callers bring their own)
   // distributed gradient (dist_grad.hip): [128 + ncl * nb][np] rows 0..127 = alpha^T then A^T = (K_y^-1 resid)^T (r real rows),
   // then one row per owned column of (L^-1 E_own)^T, in place (L^-T L^-1 E_own)^T = the owned columns of K_y^-1
   DevBuf dDistZ{bufs};
   DevBuf dDistPT{bufs};                   // [nb][np] the transposed panel of the backward stream
-  bool dist_grad_ready = false;     // gps_dist_grad_begin ran on the current partitioned factor
 
   DevBuf dA{bufs};        // [r][npad]  K_y^-1 (Y - m)                         (gradient path)
   DevBuf dY{bufs};        // [npad, npad]  L^-T                                 (gradient path)
@@ -307,6 +309,59 @@ static inline int gps_dyn_lds(gps_handle_t h, const void* fn, int bytes);
       return gps_fail(h, GPS_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
     }                                                                            \
   } while (0)
+
+// dK / dLinv are about to be rewritten (or were released): no factor of any kind is resident any more.  Callers that also give
+// up the data set zero n / npad / r next to the call.
+static inline void drop_resident_factors(gps_handle_t h) {
+  h->have_factor = false; h->factor_gen++; h->dist.have_part_factor = false; h->dist.grad_ready = false;
+}
+
+// ---- one panel of the block-column distributed factor (gps_dist.hip, dist_grad.hip) ----
+// Its message in a comm slot:  body [rows][nb] (L_jj, the rows below it, the 128 augmented rows) | the nbb 128 x 128 inverses of
+// its diagonal blocks | their transposes | DIST_TAIL doubles: sum log L_ii, sum alpha^2, info, (spare)
+#define DIST_TAIL 4
+struct DistPanel {
+  i64 np, nb, ld;
+  i64 rows;                    // panel rows incl. the augmented ones
+  i64 blk0, nbb;               // first 128-block of the panel, 128-blocks per panel
+  i64 below;                   // rows under the diagonal block, without the augmented ones
+  double* panel;               // the panel in this rank's storage (partitioned: only meaningful on the owner)
+  i64 inv_doubles() const { return nbb * GPS_TILE * GPS_TILE; }
+  i64 msg_doubles() const { return rows * nb + 2 * inv_doubles() + DIST_TAIL; }
+  double* body(double* msg) const { return msg; }
+  double* linv(double* msg) const { return msg + rows * nb; }
+  double* linvT(double* msg) const { return linv(msg) + inv_doubles(); }
+  double* tail(double* msg) const { return linvT(msg) + inv_doubles(); }
+  double* aug(double* msg) const { return msg + (rows - GPS_TILE) * nb; }
+};
+static inline bool dist_has_panel(gps_handle_t h, i64 j) { return h && h->dist.nb > 0 && j >= 0 && j * h->dist.nb < h->dist.np; }
+static inline DistPanel dist_view(gps_handle_t h, i64 j) {          // (unchecked)
+  const i64 np = h->dist.np, nb = h->dist.nb, ld = h->dist.ld;
+  return DistPanel{np, nb, ld, np + GPS_TILE - j * nb, j * nb / GPS_TILE, nb / GPS_TILE, np - (j + 1) * nb,
+                   h->dK.d() + j * nb * ld + (h->dist.part ? (j / h->dist.P) * nb : j * nb)};
+}
+static inline i64 dist_msg_doubles(gps_handle_t h, i64 j) { return dist_view(h, j).msg_doubles(); }
+// every per-panel entry point starts here: the index check (in the caller's words), the device, the leaves' mode, the view
+static inline int dist_panel(gps_handle_t h, i64 j, DistPanel* v, int code = GPS_ERR_ARG,
+                             const char* what = "gps_dist_*: bad panel index or gps_dist_begin not called") {
+  if (!dist_has_panel(h, j)) return gps_fail(h, code, what);
+  GPS_HIP(h, hipSetDevice(h->device));
+  h->refine_now = h->factor_refine;
+  *v = dist_view(h, j);
+  return GPS_OK;
+}
+static inline int dist_slot(gps_handle_t h, int buf, double** msg) {
+  if (buf < 0 || buf >= h->dist.ncomm || !h->dist.comm[buf]) return gps_fail(h, GPS_ERR_STATE, "gps_dist_set_comm has not been called");
+  *msg = h->dist.comm[buf];
+  return GPS_OK;
+}
+// the native exchange of panel j through comm slot `buf` (root = its owner; event slot `step % 8`): the count is rounded up to
+// whole chunks for the scatter + all-gather
+static inline i64 dist_chunked(i64 n, int P) { return ((n + P - 1) / P) * P; }
+static inline int dist_exchange(gps_handle_t h, i64 step, i64 j, int buf, int mode) {
+  const int P = h->comm_world;
+  return gps_comm_exchange(h, h->dist.comm[buf], dist_chunked(dist_msg_doubles(h, j), P), (int)(j % P), mode, (int)(step % 8));
+}
 
 // Bracket one kernel launch for the per-class accounting.  The launch itself is
 // the lambda body; events are only recorded when profiling is enabled.

@@ -119,7 +119,7 @@ extern "C" int gps_trsm_lower(gps_handle_t h, const double* L, int64_t n, double
 extern "C" int gps_gpr_set_data(gps_handle_t h, const double* X, int64_t n, int64_t d_all) {
   if (!h || !X || n <= 0 || d_all <= 0) return gps_fail(h, GPS_ERR_ARG, "gps_gpr_set_data: bad argument");
   GPS_HIP(h, hipSetDevice(h->device));
-  h->have_factor = false; h->factor_gen++; h->dist_have_part_factor = false;
+  drop_resident_factors(h);
   h->n = n; h->d_all = d_all; h->npad = gps_pad(n);
   GPS_HIP(h, h->dX.ensure((size_t)n * d_all * 8));
   GPS_HIP(h, hipMemcpyAsync(h->dX.p, X, (size_t)n * d_all * 8, hipMemcpyHostToDevice, h->stream));
@@ -315,7 +315,7 @@ static int gpr_factor(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, 
   if (h->n <= 0) return gps_fail(h, GPS_ERR_STATE, "gps_gpr_set_data has not been called");
   if (r < 0 || (r > 0 && !resid)) return gps_fail(h, GPS_ERR_ARG, "resid missing");
   const i64 np = h->npad;
-  h->have_factor = false; h->factor_gen++; h->dist_have_part_factor = false;
+  drop_resident_factors(h);
   h->small.valid = false;
   FactorPlan p;
   int rc = gpr_plan(h, prog, n_nodes, noise_var, r, &p);

@@ -41,8 +41,8 @@ extern "C" int gps_release_buffers(gps_handle_t h) {
   if (h->def_stream) GPS_HIP(h, hipStreamSynchronize(h->def_stream));
   gps_profile_collect(h);
   release_buffers(h, false);
-  h->have_factor = false; h->factor_gen++; h->dist_have_part_factor = false; h->dist_grad_ready = false; h->n = 0; h->npad = 0; h->r = 0;
-  h->dist_np = 0; h->dist_nb = 0;          // (a distributed factorisation must start over with gps_dist_begin)
+  drop_resident_factors(h); h->n = 0; h->npad = 0; h->r = 0;
+  h->dist.np = 0; h->dist.nb = 0;          // (a distributed factorisation must start over with gps_dist_begin)
   return GPS_OK;
 }
 
@@ -57,9 +57,9 @@ extern "C" int gps_destroy(gps_handle_t h) {
   (void)hipStreamDestroy(h->ext_stream ? h->own_stream : h->stream);
   if (h->side_stream) { (void)hipStreamSynchronize(h->side_stream); (void)hipStreamDestroy(h->side_stream); }
   if (h->def_stream) { (void)hipStreamSynchronize(h->def_stream); (void)hipStreamDestroy(h->def_stream); }
-  if (h->dist_chain) { (void)hipStreamSynchronize(h->dist_chain); (void)hipStreamDestroy(h->dist_chain); }
-  if (h->dist_bulk_own) { (void)hipStreamSynchronize(h->dist_bulk_own); (void)hipStreamDestroy(h->dist_bulk_own); }
-  for (auto e : h->dist_events) (void)hipEventDestroy(e);
+  if (h->dist.chain) { (void)hipStreamSynchronize(h->dist.chain); (void)hipStreamDestroy(h->dist.chain); }
+  if (h->dist.bulk_own) { (void)hipStreamSynchronize(h->dist.bulk_own); (void)hipStreamDestroy(h->dist.bulk_own); }
+  for (auto e : h->dist.events) (void)hipEventDestroy(e);
   if (h->ev_def_fork) (void)hipEventDestroy(h->ev_def_fork);
   if (h->ev_def_join) (void)hipEventDestroy(h->ev_def_join);
   release_buffers(h, true);          // (behind the side streams: their hand-over kernels read dLaFlags)
@@ -152,7 +152,7 @@ extern "C" int gps_set_option(gps_handle_t h, const char* key, double value) {
   if (strcmp(key, "wave_fault_inject") == 0) { h->wave_fault_inject = (int)value; return GPS_OK; }
   if (strcmp(key, "small_fault_inject") == 0) { h->small.fault_inject = (int)value; return GPS_OK; }
   if (strcmp(key, "svgp_kl_weight") == 0) { h->svgp_kl_weight = value; return GPS_OK; }
-  if (strcmp(key, "dist_partitioned") == 0) { h->dist_partitioned = (int)value; return GPS_OK; }
+  if (strcmp(key, "dist_partitioned") == 0) { h->dist.partitioned = (int)value; return GPS_OK; }
   if (strcmp(key, "leaf_plain_kappa") == 0) { h->leaf_plain_kappa = value; h->plain_linv = nullptr; return GPS_OK; }
   if (strcmp(key, "follower_max_wgs") == 0) { h->follower_max_wgs = (int)value; return GPS_OK; }
   if (strcmp(key, "potrf_rl_group") == 0) { h->potrf_rl_group = (int)value < 1 ? 1 : (int)value; return GPS_OK; }
@@ -421,3 +421,54 @@ extern "C" int gps_diag_trsm_leaf(gps_handle_t h, int64_t m, int mode, int upper
   return GPS_OK;
 }
 
+// ---- external streams ------------------------------------------------------------------------------
+extern "C" int gps_set_stream(gps_handle_t h, void* hip_stream, int external) {
+  if (!h) return GPS_ERR_ARG;
+  GPS_HIP(h, hipSetDevice(h->device));
+  GPS_HIP(h, hipStreamSynchronize(h->stream));
+  gps_profile_collect(h);
+  if (external) {                       // hip_stream may be NULL: the legacy default stream
+    if (!h->ext_stream) { h->own_stream = h->stream; h->ext_stream = true; }
+    h->stream = (hipStream_t)hip_stream;
+    // The look-ahead side stream comes from hipExtStreamCreateWithCUMask, which has no "non-blocking" flag: while it
+    // exists, every launch on the legacy default stream is ordered against it (measured: the block-column run on the
+    // default stream 2.6x slower).  It is not used with an external stream, so it goes; lookahead() re-creates it.
+    if (h->side_stream) {
+      (void)hipStreamSynchronize(h->side_stream);
+      (void)hipStreamDestroy(h->side_stream);
+      h->side_stream = nullptr;
+    }
+    if (h->def_stream) {
+      (void)hipStreamSynchronize(h->def_stream);
+      (void)hipStreamDestroy(h->def_stream);
+      h->def_stream = nullptr;
+    }
+  } else if (h->ext_stream) {
+    h->stream = h->own_stream; h->ext_stream = false;
+  }
+  return GPS_OK;
+}
+
+// diagnostics: replace the handle's own stream by one restricted to the CUs of `mask` (hipExtStreamCreateWithCUMask)
+extern "C" int gps_diag_set_cu_mask(gps_handle_t h, const uint32_t* mask, int n_words) {
+  if (!h || !mask || n_words <= 0 || h->ext_stream) return GPS_ERR_ARG;
+  GPS_HIP(h, hipSetDevice(h->device));
+  GPS_HIP(h, hipStreamSynchronize(h->stream));
+  gps_profile_collect(h);
+  hipStream_t s = nullptr;
+  GPS_HIP(h, hipExtStreamCreateWithCUMask(&s, (uint32_t)n_words, mask));
+  (void)hipStreamDestroy(h->stream);
+  h->stream = s;
+  return GPS_OK;
+}
+
+// device memory the handle holds right now: every buffer of its registry (gps_common.hpp: DevBuf), the comm buffers of the
+// all-native driver (gps_dist_lml / gps_dist_predict allocate them on the handle) included; comm buffers a caller brings
+// (gps_dist_set_comm_bufs) are its own
+extern "C" int gps_device_bytes(gps_handle_t h, int64_t* bytes) {
+  if (!h || !bytes) return GPS_ERR_ARG;
+  int64_t tot = 0;
+  for (const DevBuf* b : h->bufs) tot += (int64_t)b->cap;
+  *bytes = tot;
+  return GPS_OK;
+}

@@ -8,7 +8,7 @@
 // Every entry that builds Kuu into the handle's dK / dLinv starts here: the resident GPR factor and data are gone after it.
 static int begin_inducing_call(gps_handle_t h, int* info) {
   GPS_HIP(h, hipSetDevice(h->device));
-  h->have_factor = false; h->factor_gen++; h->dist_have_part_factor = false; h->n = 0;
+  drop_resident_factors(h); h->n = 0;
   h->refine_now = (h->leaf_refine != 0);
   if (info) *info = 0;
   return GPS_OK;

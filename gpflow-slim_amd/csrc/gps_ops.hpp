@@ -5,6 +5,7 @@
 #pragma once
 #include "gps_common.hpp"
 #include "blocked.hpp"
+#include "dist_schedule.hpp"
 #include <climits>
 #include <cmath>
 #include <algorithm>
@@ -399,4 +400,40 @@ static int chol_adjoint2(gps_handle_t h, Blocked<HipOps>& bl, const double* U, c
   rc = gps_launch_transpose(h, P, mp, mp, mp, out, mp);                                // Y^T
   if (rc) return rc;
   return bl.trsm_rn_rec(U, mp, mp, 0, out, mp, mp);                                    // Y^T L^-1 = (L^-T Y)^T  (symmetric)
+}
+
+// ---- pieces the block-column distributed entries share (gps_dist.hip, dist_grad.hip) ---------------------------------------
+// the operations of a panel that sits in comm slot `msg`: its own block inverses travel with it
+static inline HipOps dist_msg_ops(gps_handle_t h, const DistPanel& v, double* msg) {
+  return HipOps{h, v.linv(msg), v.linvT(msg), (int*)h->dInfo.p};
+}
+// One step of the forward substitution at panel granularity, on the panel in `msg`.  B [m_rows][..], ld ldb: the block column
+// of the right-hand sides that belongs to the panel, the columns to its right behind it.  alpha_dst (ld np): where alpha_j^T,
+// the augmented rows of the panel, goes.
+static int dist_forward_step(gps_handle_t h, const DistPanel& v, double* msg, double* B, i64 ldb, i64 m_rows, double* alpha_dst) {
+  if (h->dist.r > 0)
+    GPS_HIP(h, hipMemcpy2DAsync(alpha_dst, (size_t)v.np * 8, v.aug(msg), (size_t)v.nb * 8, (size_t)v.nb * 8, (size_t)h->dist.r,
+                                hipMemcpyDeviceToDevice, h->stream));
+  if (m_rows == 0) return GPS_OK;
+  HipOps ops = dist_msg_ops(h, v, msg);
+  int rc = Blocked<HipOps>(ops).trsm_rec(v.body(msg), v.nb, v.nb, 0, B, ldb, m_rows);                     // B_j <- B_j L_jj^-T
+  if (rc || v.below <= 0) return rc;
+  return gps_launch_gemm_nt(h, 0, 0, m_rows, v.below, v.nb, B, ldb, v.body(msg) + v.nb * v.nb, v.nb, B + v.nb, ldb);   // B_{>j} -= B_j L[>j, j]^T
+}
+
+// panel_stream_schedule (dist_schedule.hpp) over the handle's native communicator and the two comm slots that are set: the
+// owner packs with gps_dist_solve_pack, `apply(k, j, buf)` is the caller's.  A failure drains the streams before it returns.
+template <class Apply>
+struct DistStreamOps {
+  gps_handle_t h; int mode; Apply apply;
+  int pack(i64 j, int buf) { return gps_dist_solve_pack(h, j, buf); }
+  int exchange(i64 k, i64 j, int buf) { return dist_exchange(h, k, j, buf, mode); }
+  int wait_exchange(i64 k) { return gps_comm_wait(h, (int)(k % 8)); }
+};
+template <class PanelOf, class Apply>
+static int dist_stream_panels(gps_handle_t h, int exchange_mode, i64 steps, PanelOf panel_of, Apply apply) {
+  DistStreamOps<Apply> ops{h, exchange_mode, apply};
+  int rc = panel_stream_schedule(ops, h->comm_world, h->comm_rank, steps, panel_of);
+  if (rc) { (void)hipStreamSynchronize(h->stream); if (h->comm && h->comm_stream) (void)hipStreamSynchronize(h->comm_stream); }
+  return rc;
 }

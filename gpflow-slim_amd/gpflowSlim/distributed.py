@@ -30,6 +30,9 @@ gloo (CPU tests; CUDA tensors only support broadcast there) falls back to one br
 tests: a numpy emulation with a vector-clock race detector over the two lanes + gloo
 (tests/test_dist_cpu.py).
 """
+import contextlib
+import types
+
 import numpy as np
 
 CHAIN, BULK = 0, 1
@@ -106,42 +109,47 @@ def block_column_schedule(ops, comm, n_panels, lookahead=2):
         ops.wait(CHAIN, tok)
 
 
-def grad_stream_schedule(ops, comm, n_panels):
-    """The two streams of the distributed LML gradient, over a factor that stays partitioned.
+def panel_stream_schedule(ops, comm, steps, panel_of):
+    """A stream of panels over a factor that stays partitioned: step k = 0 .. steps - 1 handles panel j = panel_of(k).  The owner of
+    panel j packs it again (the message of the factorisation), the panel is exchanged, every rank applies it.  One lane; two comm
+    slots alternate (slot k % 2): the exchange of step k + 1 is in flight while step k is applied, and its pack / receive is
+    ordered after apply(k - 1), the last reader of that slot.  (csrc/dist_schedule.hpp has the same function for the library's own
+    communicator; tests/test_dist_schedule_cpu.py holds the two against each other call by call.)
 
-    Step k = 0 .. 2 n_panels - 1 handles panel j = k (forward stream, Z^T <- Z^T L^-T on this rank's identity columns) and then
-    j = 2 n_panels - 1 - k (backward stream, X^T L = Z^T: the owned block columns of K_y^-1, and A = K_y^-1 resid on every rank).
-    The owner of panel j packs it again (the message of the factorisation), the panel is exchanged, every rank applies it.
-    One lane; two comm slots alternate (slot k % 2): the exchange of step k + 1 is in flight while step k is applied, and its
-    pack / receive is ordered after apply(k - 1), the last reader of that slot.
-
-    `ops`: begin(), pack(j, buf), message(j, buf) -> buffer object for comm, fwd_apply(j, buf), bwd_apply(j, buf), local() ->
-    this rank's result, and the context manager comm_lane().  `comm`: rank, world, exchange(buffer, src) -> object with wait().
-    Returns ops.local()."""
+    `ops`: pack(j, buf), message(j, buf) -> buffer object for comm, apply(k, j, buf), and the context manager comm_lane().
+    `comm`: rank, world, exchange(buffer, src) -> object with wait()."""
     P, rank = comm.world, comm.rank
-    steps = 2 * n_panels
-
-    def panel(k):
-        return k if k < n_panels else steps - 1 - k
 
     def send(k):
-        j, buf = panel(k), k % 2
+        j, buf = panel_of(k), k % 2
         if rank == j % P:
             ops.pack(j, buf)
         with ops.comm_lane():
             return comm.exchange(ops.message(j, buf), j % P)
 
-    ops.begin()
     pending = send(0)
     for k in range(steps):
         with ops.comm_lane():
             pending.wait()
         if k + 1 < steps:
-            pending = send(k + 1)
-        if k < n_panels:
-            ops.fwd_apply(panel(k), k % 2)
-        else:
-            ops.bwd_apply(panel(k), k % 2)
+            pending = send(k + 1)                        # in flight ...
+        ops.apply(k, panel_of(k), k % 2)                 # ... while step k is applied
+
+
+def grad_stream_schedule(ops, comm, n_panels):
+    """The two streams of the distributed LML gradient, over a factor that stays partitioned:
+    panel_stream_schedule over 2 n_panels steps.  Step k handles panel j = k (forward stream, Z^T <- Z^T L^-T on this rank's
+    identity columns) and then j = 2 n_panels - 1 - k (backward stream, X^T L = Z^T: the owned block columns of K_y^-1, and
+    A = K_y^-1 resid on every rank).
+
+    `ops`: begin(), pack(j, buf), message(j, buf) -> buffer object for comm, fwd_apply(j, buf), bwd_apply(j, buf), local() ->
+    this rank's result, and the context manager comm_lane().  `comm`: rank, world, exchange(buffer, src) -> object with wait().
+    Returns ops.local()."""
+    steps = 2 * n_panels
+    ops.begin()
+    up_then_down = types.SimpleNamespace(pack=ops.pack, message=ops.message, comm_lane=ops.comm_lane,
+                                         apply=lambda k, j, buf: (ops.fwd_apply if k < n_panels else ops.bwd_apply)(j, buf))
+    panel_stream_schedule(up_then_down, comm, steps, lambda k: k if k < n_panels else steps - 1 - k)
     return ops.local()
 
 
@@ -442,37 +450,35 @@ class SingleComm(object):
         return tensor
 
 
-class HipPanelOps(object):
-    """Per-step pieces on one GPU through the C ABI.  Comm buffers are torch tensors and the two lanes are torch
-    streams (device-memory / stream plumbing only): the CHAIN lane -- a high-priority stream on which the library's
-    kernels and the collectives are ordered -- and the BULK lane for the trailing updates.  Use as a context manager:
-    leaving it always gives the handle its own stream back."""
+@contextlib.contextmanager
+def _handle_on_stream(handle, stream):
+    """`stream` (a torch stream, ordered after the current one) as the handle's stream; on the way out the current stream waits
+    for it and the handle gets its own stream back."""
+    import torch
+    stream.wait_stream(torch.cuda.current_stream())
+    handle.set_stream(stream.cuda_stream, True)
+    try:
+        yield stream
+    finally:
+        torch.cuda.current_stream().wait_stream(stream)
+        handle.set_stream(0, False)
 
-    def __init__(self, handle, prog, noise_var, resid, nparts, part, nb, two_lanes=True, partitioned=None):
+
+def _whole_chunks(n, nparts):
+    """The length of an n-double message in a comm buffer: rounded up to whole chunks for the scatter + all-gather."""
+    return -(-n // nparts) * nparts
+
+
+class _HipOps(object):
+    """What the ops of the schedules share on one GPU: the C ABI handle with a torch stream installed as its stream -- the lane
+    on which the library's kernels and the collectives are ordered (device-memory / stream plumbing only) -- and comm buffers
+    that are torch tensors.  Use as a context manager: leaving it always gives the handle its own stream back."""
+
+    def __init__(self, handle, lane, nparts):
         import torch
-        self.h = handle
-        self.torch = torch
-        self.nparts = max(int(nparts), 1)
-        if partitioned is not None:
-            handle.set_option("dist_partitioned", 1 if partitioned else 0)
-        self.n_bufs = handle.dist_comm_bufs_needed()          # 3: partitioned storage (panels are read from the buffers); 2: replicated
-        lo, hi = torch.cuda.Stream.priority_range() if hasattr(torch.cuda.Stream, "priority_range") else (0, -1)
-        self.chain = torch.cuda.Stream(priority=hi)
-        self.bulk = torch.cuda.Stream(priority=lo) if two_lanes else self.chain
-        self._installed = False
-        try:
-            self.chain.wait_stream(torch.cuda.current_stream())
-            handle.set_stream(self.chain.cuda_stream, True)
-            self._installed = True
-            handle.dist_set_bulk_stream(self.bulk.cuda_stream if two_lanes else 0)
-            self.n_panels, mx = handle.dist_begin(prog, noise_var, resid, nparts, part, nb)
-            mx = -(-mx // max(nparts, 1)) * max(nparts, 1)          # room for equal chunks
-            with torch.cuda.stream(self.chain):
-                self.bufs = [torch.empty(mx, dtype=torch.float64, device="cuda") for _ in range(self.n_bufs)]
-            handle.dist_set_comm_bufs([b.data_ptr() for b in self.bufs])
-        except Exception:
-            self.close()
-            raise
+        self.h, self.torch, self.lane, self.nparts = handle, torch, lane, max(int(nparts), 1)
+        self._leave = contextlib.ExitStack()
+        self._leave.enter_context(_handle_on_stream(handle, lane))
 
     def __enter__(self):
         return self
@@ -482,28 +488,49 @@ class HipPanelOps(object):
         return False
 
     def close(self):
-        if self._installed:
-            self._installed = False
-            # both lanes are drained on every exit path: when the schedule, an exchange or the finish raised (a
-            # not-positive-definite panel raises on every rank), trailing updates may still be running on the BULK lane
-            # and the caller's next launch on the handle's own stream would rebuild K under them
-            if self.bulk is not self.chain:
-                self.chain.wait_stream(self.bulk)
-            self.torch.cuda.current_stream().wait_stream(self.chain)
-            try:
-                self.h.dist_set_bulk_stream(0)
-            finally:
-                self.h.set_stream(0, False)
+        self._leave.close()
 
     def comm_lane(self):
-        return self.torch.cuda.stream(self.chain)
+        return self.torch.cuda.stream(self.lane)
+
+    def message(self, t, buf):
+        return self.bufs[buf][: _whole_chunks(self.h.dist_msg_doubles(t), self.nparts)]
+
+
+class HipPanelOps(_HipOps):
+    """block_column_schedule's pieces.  Two lanes: the CHAIN lane -- a high-priority stream, the handle's -- and the BULK lane
+    for the trailing updates."""
+
+    def __init__(self, handle, prog, noise_var, resid, nparts, part, nb, two_lanes=True, partitioned=None):
+        import torch
+        if partitioned is not None:
+            handle.set_option("dist_partitioned", 1 if partitioned else 0)
+        self.n_bufs = handle.dist_comm_bufs_needed()          # 3: partitioned storage (panels are read from the buffers); 2: replicated
+        lo, hi = torch.cuda.Stream.priority_range() if hasattr(torch.cuda.Stream, "priority_range") else (0, -1)
+        self.chain = torch.cuda.Stream(priority=hi)
+        self.bulk = torch.cuda.Stream(priority=lo) if two_lanes else self.chain
+        _HipOps.__init__(self, handle, self.chain, nparts)
+        try:
+            self._leave.callback(self._drain_bulk)
+            handle.dist_set_bulk_stream(self.bulk.cuda_stream if two_lanes else 0)
+            self.n_panels, mx = handle.dist_begin(prog, noise_var, resid, nparts, part, nb)
+            with torch.cuda.stream(self.chain):
+                self.bufs = [torch.empty(_whole_chunks(mx, self.nparts), dtype=torch.float64, device="cuda") for _ in range(self.n_bufs)]
+            handle.dist_set_comm_bufs([b.data_ptr() for b in self.bufs])
+        except Exception:
+            self.close()
+            raise
+
+    def _drain_bulk(self):
+        # both lanes are drained on every exit path (the CHAIN lane by _handle_on_stream, after this): when the schedule, an
+        # exchange or the finish raised (a not-positive-definite panel raises on every rank), trailing updates may still be
+        # running on the BULK lane and the caller's next launch on the handle's own stream would rebuild K under them
+        if self.bulk is not self.chain:
+            self.chain.wait_stream(self.bulk)
+        self.h.dist_set_bulk_stream(0)
 
     def panel_factor(self, t, buf):
         self.h.dist_panel_factor(t, buf)
-
-    def message(self, t, buf):
-        n = self.h.dist_msg_doubles(t)
-        return self.bufs[buf][: -(-n // self.nparts) * self.nparts]      # whole chunks for the scatter + all-gather
 
     def unpack(self, t, buf):
         self.h.dist_unpack(t, buf)
@@ -538,7 +565,7 @@ def _count_native_exchanges(comm, h, n_panels, mode, passes):
     if comm.world == 1:
         return
     for j in range(n_panels):
-        cnt = -(-h.dist_msg_doubles(j) // comm.world) * comm.world
+        cnt = _whole_chunks(h.dist_msg_doubles(j), comm.world)
         root = (j % comm.world) == comm.rank
         comm.bytes_sent += passes * ((8 * (cnt // comm.world) * (comm.world - 1) * (2 if root else 1)) if mode == 1
                                      else (8 * cnt * (comm.world - 1) if root else 0))
@@ -626,91 +653,59 @@ def predict_f_distributed(model, Xnew, comm=None):
     return both[:, :R], both[:, R:]
 
 
+class HipSolveOps(_HipOps):
+    """panel_stream_schedule's pieces for predict_f from a partitioned factor (gps_dist_solve_*) on a stream of their own.
+    `bufs`: the comm buffers of the factorisation (>= 2).  A rank without test points packs and exchanges only."""
+
+    def __init__(self, handle, prog, Xmine, bufs, nparts):
+        import torch
+        _HipOps.__init__(self, handle, torch.cuda.Stream(), nparts)
+        self.bufs, self.mine = bufs, Xmine.shape[0] > 0
+        try:
+            handle.dist_set_comm_bufs([b.data_ptr() for b in bufs])
+            if self.mine:
+                handle.dist_solve_begin(prog, Xmine)
+        except Exception:
+            self.close()
+            raise
+
+    def pack(self, j, buf):
+        self.h.dist_solve_pack(j, buf)
+
+    def apply(self, k, j, buf):
+        if self.mine:
+            self.h.dist_solve_apply(j, buf)
+
+
 def predict_streamed(h, prog, Xmine, comm, n_panels, bufs, nparts, R):
-    """predict_f for this rank's test points from a PARTITIONED factor on handle `h` (gps_dist_solve_*): the owner of panel
-    j packs it again, the panel is exchanged like during the factorisation, every rank applies it to its right-hand sides;
-    the exchange of panel j + 1 is in flight while panel j is applied.  Returns (A^T alpha [n*, R] -- the caller adds the
-    mean function --, fvar [n*]); models/gpr.py:119-131.  `bufs`: the comm buffers of the factorisation (>= 2)."""
-    import torch
-    P, rank = comm.world, comm.rank
-    mine = Xmine.shape[0] > 0
-    lane = torch.cuda.Stream()
-    lane.wait_stream(torch.cuda.current_stream())
-    h.set_stream(lane.cuda_stream, True)
-    try:
-        h.dist_set_comm_bufs([b.data_ptr() for b in bufs])
-        if mine:
-            h.dist_solve_begin(prog, Xmine)
-
-        def send(j):
-            buf = j % 2
-            if rank == j % P:
-                h.dist_solve_pack(j, buf)
-            n = h.dist_msg_doubles(j)
-            with torch.cuda.stream(lane):
-                return comm.exchange(bufs[buf][: -(-n // nparts) * nparts], j % P)
-        pending = send(0)
-        for j in range(n_panels):
-            with torch.cuda.stream(lane):
-                pending.wait()
-            if j + 1 < n_panels:
-                pending = send(j + 1)          # (stream-ordered after apply(j - 1), the last reader of that buffer) in flight ...
-            if mine:
-                h.dist_solve_apply(j, j % 2)   # ... while panel j is applied
-        if mine:
-            mu, var = h.dist_solve_finish(prog, Xmine.shape[0], R)
-        else:
-            mu, var = np.zeros((0, R)), np.zeros((0,))
-    finally:
-        torch.cuda.current_stream().wait_stream(lane)
-        h.set_stream(0, False)
-    return mu, var
+    """predict_f for this rank's test points from a PARTITIONED factor on handle `h`: panel_stream_schedule, one step per panel,
+    over HipSolveOps.  Returns (A^T alpha [n*, R] -- the caller adds the mean function --, fvar [n*]); models/gpr.py:119-131."""
+    with HipSolveOps(h, prog, Xmine, bufs, nparts) as ops:
+        panel_stream_schedule(ops, comm, n_panels, lambda k: k)
+        if ops.mine:
+            return h.dist_solve_finish(prog, Xmine.shape[0], R)
+    return np.zeros((0, R)), np.zeros((0,))
 
 
-class HipGradOps(object):
-    """grad_stream_schedule's pieces on one GPU through the C ABI (gps_dist_solve_pack / gps_dist_grad_*), on one torch
-    stream installed as the handle's stream (device-memory / stream plumbing only).  `bufs`: the comm buffers the partitioned
-    factorisation left in h.dist_state.  Use as a context manager: leaving it always gives the handle its own stream back."""
+class HipGradOps(_HipOps):
+    """grad_stream_schedule's pieces (gps_dist_solve_pack / gps_dist_grad_*) on a stream of their own.  `bufs`: the comm buffers
+    the partitioned factorisation left in h.dist_state."""
 
     def __init__(self, handle, prog, n, r, bufs, nparts):
         import torch
-        self.h, self.torch, self.prog, self.n, self.r = handle, torch, prog, n, r
-        self.bufs, self.nparts = bufs, max(int(nparts), 1)
-        self.lane = torch.cuda.Stream()
-        self.lane.wait_stream(torch.cuda.current_stream())
-        handle.set_stream(self.lane.cuda_stream, True)
-        self._installed = True
+        _HipOps.__init__(self, handle, torch.cuda.Stream(), nparts)
+        self.prog, self.n, self.r, self.bufs = prog, n, r, bufs
         try:
             handle.dist_set_comm_bufs([b.data_ptr() for b in bufs])
         except Exception:
             self.close()
             raise
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def close(self):
-        if self._installed:
-            self._installed = False
-            self.torch.cuda.current_stream().wait_stream(self.lane)
-            self.h.set_stream(0, False)
-
-    def comm_lane(self):
-        return self.torch.cuda.stream(self.lane)
-
     def begin(self):
         self.h.dist_grad_begin()
 
     def pack(self, j, buf):
         self.h.dist_solve_pack(j, buf)
-
-    def message(self, j, buf):
-        n = self.h.dist_msg_doubles(j)
-        return self.bufs[buf][: -(-n // self.nparts) * self.nparts]
 
     def fwd_apply(self, j, buf):
         self.h.dist_grad_fwd_apply(j, buf)

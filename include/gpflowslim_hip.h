@@ -565,7 +565,7 @@ int gps_dist_set_comm(gps_handle_t h, void* dev_buf0, void* dev_buf1);
 int gps_dist_set_comm_bufs(gps_handle_t h, void* const* dev_bufs, int count);
 int gps_dist_comm_bufs_needed(gps_handle_t h, int* count);
 /* The whole factorisation from inside the library: gps_dist_begin ... gps_dist_finish with the two-lane look-ahead schedule
- * (gpflowSlim/distributed.py::block_column_schedule ported statement for statement), the handle's native communicator
+ * (csrc/dist_schedule.hpp; gpflowSlim/distributed.py::block_column_schedule call for call, tests/test_dist_schedule_cpu.py), the handle's native communicator
  * (gps_comm_init) for the panel exchange and HIP streams / events for the lanes -- no host-language call per panel.
  * Collective: every rank calls it with the same arguments; same result bits on every rank; info as gps_dist_finish.
  * exchange_mode: 0 broadcast, 1 scatter + all-gather.                                                            */

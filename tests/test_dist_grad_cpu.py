@@ -1,7 +1,8 @@
 """The streams of the distributed LML gradient on CPU: grad_stream_schedule of gpflowSlim/distributed.py -- the SAME function
 the GPU path runs -- with the per-step pieces emulated in numpy/scipy (test infrastructure only) and the panel exchange carried
 by torch.distributed/gloo (world 2, 3) or SingleComm (world 1).  Checks that every rank ends with exactly its own block columns
-of K^-1 (rows >= the column), A = K^-1 resid on every rank, and that the zero blocks are never read."""
+of K^-1 (rows >= the column), A = K^-1 resid on every rank, and that the zero blocks are never read.  The streamed prediction
+(predict_streamed's schedule: panel_stream_schedule, one step per panel) runs the same way over NumpySolveOps."""
 import os
 import socket
 import sys
@@ -187,3 +188,93 @@ def test_grad_streams_gloo(world, n, nb, r):
     for rank, err, errA, held, failed in res:
         assert failed is None, failed
         assert err <= 1e-10 and errA <= 1e-10 and held, (rank, err, errA, held)
+
+
+# ---- the streamed prediction: panel_stream_schedule, one step per panel ----------------------------------------------------
+class NumpySolveOps(NumpyGradOps):
+    """Emulates gps_dist_solve_pack / gps_dist_solve_apply: the forward step is fwd_apply's, with this rank's right-hand sides
+    Bt [m, n] (m may be 0: the rank packs and exchanges only) in the place of the identity columns, all of them at every step."""
+
+    def __init__(self, K, resid, nb, nparts, part, Bt):
+        NumpyGradOps.__init__(self, K, resid, nb, nparts, part)
+        self.m = Bt.shape[0]
+        self.Zt = np.zeros((self.r + self.m, self.np_))
+        self.Zt[self.r:, :Bt.shape[1]] = Bt
+
+    def _upto(self, j):
+        return self.m
+
+    def apply(self, k, j, buf):
+        assert k == j
+        self.fwd_apply(j, buf)
+
+
+def _solve_shards(world, n_rhs):
+    """n_rhs right-hand sides over the ranks; from world 2 on the last rank gets none"""
+    takers = max(world - 1, 1)
+    bounds = [n_rhs * t // takers for t in range(takers + 1)] + [n_rhs] * (world - takers)
+    return [(bounds[t], bounds[t + 1]) for t in range(world)]
+
+
+def _solve_errors(K, resid, nb, world, rank, comm):
+    """Run the schedule for one rank: (right-hand sides held, max relative error of the mean B^T K^-1 resid and of the quadratic
+    form rowsum((B^T L^-T)^2) = diag(B^T K^-1 B) against numpy.linalg.solve, of alpha against L^-1 resid)"""
+    from gpflowSlim.distributed import panel_stream_schedule
+    n = K.shape[0]
+    B = np.random.default_rng(11).standard_normal((n, 7))
+    lo, hi = _solve_shards(world, 7)[rank]
+    ops = NumpySolveOps(K, resid, nb, world, rank, B[:, lo:hi].T)
+    panel_stream_schedule(ops, comm, ops.n_panels, lambda k: k)
+    At, alpha_t = ops.local()
+    alpha = sl.solve_triangular(np.linalg.cholesky(K), resid, lower=True)
+    err_alpha = float(np.abs(alpha_t[:, :n].T - alpha).max() / np.abs(alpha).max())
+    assert not At[:, n:].any() and not alpha_t[:, n:].any()          # (the padding stays zero)
+    if hi == lo:
+        return 0, 0.0, 0.0, err_alpha
+    mean, quad = At @ alpha_t.T, (At ** 2).sum(1)
+    KinvB = np.linalg.solve(K, B[:, lo:hi])
+    want_mean, want_quad = KinvB.T @ resid, (B[:, lo:hi] * KinvB).sum(0)
+    return (hi - lo, float(np.abs(mean - want_mean).max() / np.abs(want_mean).max()),
+            float(np.abs(quad - want_quad).max() / np.abs(want_quad).max()), err_alpha)
+
+
+def test_single_rank_streamed_solve_matches_numpy():
+    sys.path.insert(0, os.path.join(ROOT, "gpflow-slim_amd"))
+    from gpflowSlim.distributed import SingleComm
+    K, resid = _problem(300, 2)
+    held, err_mean, err_quad, err_alpha = _solve_errors(K, resid, 64, 1, 0, SingleComm())
+    assert held == 7 and err_mean <= 1e-10 and err_quad <= 1e-10 and err_alpha <= 1e-10
+
+
+def _solve_worker(rank, world, port, q):
+    sys.path.insert(0, os.path.join(ROOT, "gpflow-slim_amd"))
+    import torch.distributed as dist
+    from gpflowSlim.distributed import TorchComm
+    dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
+    try:
+        K, resid = _problem(300, 2)
+        try:
+            q.put((rank,) + _solve_errors(K, resid, 64, world, rank, TorchComm(mode="broadcast")) + (None,))
+        except AssertionError as e:
+            q.put((rank, None, None, None, None, str(e)))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_streamed_solve_gloo(world):
+    """n = 300, nb = 64 (5 panels: at world 3 the ranks own 2, 2 and 1), 7 right-hand sides, none of them on the last rank."""
+    import torch.multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_solve_worker, args=(k, world, port, q)) for k in range(world)]
+    for p in procs:
+        p.start()
+    res = sorted(q.get(timeout=120) for _ in range(world))
+    for p in procs:
+        p.join(timeout=60)
+    assert [r[1] for r in res] == [hi - lo for lo, hi in _solve_shards(world, 7)] and res[-1][1] == 0 and sum(r[1] for r in res) == 7
+    for rank, held, err_mean, err_quad, err_alpha, failed in res:
+        assert failed is None, failed
+        assert err_mean <= 1e-10 and err_quad <= 1e-10 and err_alpha <= 1e-10, (rank, err_mean, err_quad, err_alpha)
