@@ -583,28 +583,26 @@ def gpr_lml_distributed(model, comm=None, nb=512, lookahead=2, partitioned=True)
     comm = comm or _default_comm()
     h = model._handle()
     prog = model.kern._program(model.X.shape[1])
-    model._factor_key = None               # (the handle's setter also drops any partitioned-factor claim)
-    if isinstance(comm, RcclComm) and comm.native_schedule and comm.h is h:
-        # the library's own communicator: the whole schedule runs inside the library too (gps_dist_lml) -- no Python per panel
-        h.set_option("dist_partitioned", 1 if partitioned else 0)
-        mode = 1 if comm.mode == "scatter_allgather" else 0
-        lml = h.dist_lml(prog, float(np.squeeze(model.likelihood.variance)), model._resid(), nb, 2 if lookahead is True else int(lookahead), mode)
-        _count_native_exchanges(comm, h, -(-model.X.shape[0] // nb), mode, 1)
-        if partitioned:
-            h.dist_state = {"key": model._state_key(), "native": True, "world": comm.world}
+    key = model._state_key()
+    # Replicated: L and alpha are resident on every rank, claimed like any resident factor.  Partitioned: no such claim; the
+    # partitioned-factor claim (dist_state) is recorded AFTER the key was reset, whose setter drops any earlier one.
+    with h.factor_claim(None if partitioned else key):
+        if isinstance(comm, RcclComm) and comm.native_schedule and comm.h is h:
+            # the library's own communicator: the whole schedule runs inside the library too (gps_dist_lml) -- no Python per panel
+            h.set_option("dist_partitioned", 1 if partitioned else 0)
+            mode = 1 if comm.mode == "scatter_allgather" else 0
+            lml = h.dist_lml(prog, float(np.squeeze(model.likelihood.variance)), model._resid(), nb, 2 if lookahead is True else int(lookahead), mode)
+            _count_native_exchanges(comm, h, -(-model.X.shape[0] // nb), mode, 1)
+            claim = {"key": key, "native": True, "world": comm.world}
         else:
-            model._factor_key = model._state_key()
-        return lml
-    with HipPanelOps(h, prog, float(np.squeeze(model.likelihood.variance)), model._resid(), comm.world, comm.rank,
-                     nb, two_lanes=bool(lookahead), partitioned=partitioned) as ops:
-        block_column_schedule(ops, comm, ops.n_panels, lookahead=lookahead)
-        lml = ops.finish()
-        if partitioned:
-            # what predict_f_distributed needs to stream the panels again (the comm buffers stay alive with it)
-            h.dist_state = {"key": model._state_key(), "n_panels": ops.n_panels, "bufs": ops.bufs, "nparts": ops.nparts,
-                            "world": comm.world}
-    if not partitioned:
-        model._factor_key = model._state_key()      # L and alpha are resident (replicated) on every rank
+            with HipPanelOps(h, prog, float(np.squeeze(model.likelihood.variance)), model._resid(), comm.world, comm.rank,
+                             nb, two_lanes=bool(lookahead), partitioned=partitioned) as ops:
+                block_column_schedule(ops, comm, ops.n_panels, lookahead=lookahead)
+                lml = ops.finish()
+                # what predict_f_distributed needs to stream the panels again (the comm buffers stay alive with it)
+                claim = {"key": key, "n_panels": ops.n_panels, "bufs": ops.bufs, "nparts": ops.nparts, "world": comm.world}
+    if partitioned:
+        h.dist_state = claim
     return lml
 
 
@@ -734,10 +732,10 @@ def gpr_lml_grad_distributed(model, comm=None, nb=512, lookahead=2):
     layout = model.kern._grad_layout(d_all)
     noise = float(np.squeeze(model.likelihood.variance))
     if isinstance(comm, RcclComm) and comm.native_schedule and comm.h is h:
-        model._factor_key = None
         h.set_option("dist_partitioned", 1)
         mode = 1 if comm.mode == "scatter_allgather" else 0
-        lml, slots, gnoise, kinv_resid = h.dist_lml_grad(prog, noise, model._resid(), nb, 2 if lookahead is True else int(lookahead), mode)
+        with h.factor_claim(None):             # (partitioned: the claim is dist_state, recorded below)
+            lml, slots, gnoise, kinv_resid = h.dist_lml_grad(prog, noise, model._resid(), nb, 2 if lookahead is True else int(lookahead), mode)
         # the factorisation's exchanges, the two gradient streams' and the all-reduce that gathers the [P][n_slots + 1] sums
         # and K_y^-1 resid
         _count_native_exchanges(comm, h, -(-model.X.shape[0] // nb), mode, 3)

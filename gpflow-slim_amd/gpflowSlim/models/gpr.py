@@ -89,9 +89,8 @@ class GPR(GPModel):
     def _rff_likelihood(self):
         h = be.get_handle()
         desc, keep, X, _ = self._rff()
-        self._factor_key = None
-        lml = h.rff_lml(desc, X, float(np.squeeze(self.likelihood.variance)), self._resid(), self.rff_chunk_rows)
-        self._factor_key = self._state_key()
+        with h.factor_claim(self._state_key()):
+            lml = h.rff_lml(desc, X, float(np.squeeze(self.likelihood.variance)), self._resid(), self.rff_chunk_rows)
         return lml
 
     def _rff_likelihood_and_gradients(self):
@@ -100,10 +99,9 @@ class GPR(GPModel):
         if desc.kind == be.RFF_EXPLICIT:
             raise NotImplementedError("gradients of the feature branch need a kernel_kitchen_sink sampler")
         sampler = self.kern.sampler
-        self._factor_key = None
-        lml, gvar, gls, gnoise, kinv_resid = h.rff_lml_grad(desc, X, float(np.squeeze(self.likelihood.variance)),
-                                                            self._resid(), self.rff_chunk_rows)
-        self._factor_key = self._state_key()
+        with h.factor_claim(self._state_key()):
+            lml, gvar, gls, gnoise, kinv_resid = h.rff_lml_grad(desc, X, float(np.squeeze(self.likelihood.variance)),
+                                                                self._resid(), self.rff_chunk_rows)
         layout, slots = [(sampler._variance, None)], [gvar]
         if desc.kind == be.RFF_RBF:
             layout += [(sampler._ls, None)] if gls.size == 1 else [(sampler._ls, i) for i in range(gls.size)]
@@ -115,10 +113,9 @@ class GPR(GPModel):
         desc, keep, X, Xn = self._rff(Xnew)
         key = self._state_key()
         warm = bool(self.reuse_factor) and self._factor_key is not None and self._factor_key == key
-        self._factor_key = None
-        mean, var = h.rff_predict(desc, X, float(np.squeeze(self.likelihood.variance)), self._resid(), Xn,
-                                  full_cov=full_cov, refactor=not warm, chunk_rows=self.rff_chunk_rows)
-        self._factor_key = key
+        with h.factor_claim(key):
+            mean, var = h.rff_predict(desc, X, float(np.squeeze(self.likelihood.variance)), self._resid(), Xn,
+                                      full_cov=full_cov, refactor=not warm, chunk_rows=self.rff_chunk_rows)
         return mean, var
 
     # ---- reference API ---------------------------------------------------------------------
@@ -128,9 +125,8 @@ class GPR(GPModel):
             return self._rff_likelihood()
         h = self._handle()
         prog = self.kern._program(self.X.shape[1])
-        self._factor_key = None
-        lml = h.gpr_lml(prog, float(np.squeeze(self.likelihood.variance)), self._resid())
-        self._factor_key = self._state_key()
+        with h.factor_claim(self._state_key()):
+            lml = h.gpr_lml(prog, float(np.squeeze(self.likelihood.variance)), self._resid())
         return lml
 
     def compute_log_likelihood_and_gradients(self):
@@ -145,9 +141,8 @@ class GPR(GPModel):
         prog = self.kern._program(d_all)
         layout = self.kern._grad_layout(d_all)
         resid = self._resid()
-        self._factor_key = None
-        lml, slots, gnoise, kinv_resid = h.gpr_lml_grad(prog, float(np.squeeze(self.likelihood.variance)), resid)
-        self._factor_key = self._state_key()
+        with h.factor_claim(self._state_key()):
+            lml, slots, gnoise, kinv_resid = h.gpr_lml_grad(prog, float(np.squeeze(self.likelihood.variance)), resid)
         return lml, self._gradients_from_slots(layout, slots, gnoise, kinv_resid)
 
     def _gradients_from_slots(self, layout, slots, gnoise, kinv_resid):
@@ -195,10 +190,9 @@ class GPR(GPModel):
             prog = self.kern._program(self.X.shape[1])
             key = self._state_key()
             warm = bool(self.reuse_factor) and self._factor_key is not None and self._factor_key == key
-            self._factor_key = None
-            mean, var = h.gpr_predict(prog, float(np.squeeze(self.likelihood.variance)), self._resid(), Xnew,
-                                      full_cov=full_cov, refactor=not warm)
-            self._factor_key = key
+            with h.factor_claim(key):
+                mean, var = h.gpr_predict(prog, float(np.squeeze(self.likelihood.variance)), self._resid(), Xnew,
+                                          full_cov=full_cov, refactor=not warm)
         fmean = mean + self.mean_function(Xnew)
         R = self.Y.shape[1]
         if full_cov:

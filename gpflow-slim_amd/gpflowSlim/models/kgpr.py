@@ -135,10 +135,9 @@ class KGPR(Model):
         h = be.get_handle()
         prog1, prog2 = self._programs()
         e1, e2, sel, _, _ = self._spectra(prog1, prog2, False)
-        h.factor_key = None
-        res = h.kgpr_lml(prog1, self.X1, prog2, self.X2, self.Y, self.mask, float(np.squeeze(self.likelihood.variance)),
-                         e1, e2, sel, max_iter=self.cg_max_iter, tol=self.cg_tol)
-        h.factor_key = self._state_key()
+        with h.factor_claim(self._state_key()):
+            res = h.kgpr_lml(prog1, self.X1, prog2, self.X2, self.Y, self.mask, float(np.squeeze(self.likelihood.variance)),
+                             e1, e2, sel, max_iter=self.cg_max_iter, tol=self.cg_tol)
         self.last_solve = res
         return res["lml"]
 
@@ -149,11 +148,10 @@ class KGPR(Model):
         prog1, prog2 = self._programs()
         layout = self.kern1._grad_layout(self.X1.shape[1]) + self.kern2._grad_layout(self.X2.shape[1])
         e1, e2, sel, V1, V2 = self._spectra(prog1, prog2, True)
-        h.factor_key = None
-        res, s1, s2, gnoise = h.kgpr_lml_grad(prog1, self.X1, prog2, self.X2, self.Y, self.mask,
-                                              float(np.squeeze(self.likelihood.variance)), e1, e2, sel, V1, V2,
-                                              max_iter=self.cg_max_iter, tol=self.cg_tol)
-        h.factor_key = self._state_key()
+        with h.factor_claim(self._state_key()):
+            res, s1, s2, gnoise = h.kgpr_lml_grad(prog1, self.X1, prog2, self.X2, self.Y, self.mask,
+                                                  float(np.squeeze(self.likelihood.variance)), e1, e2, sel, V1, V2,
+                                                  max_iter=self.cg_max_iter, tol=self.cg_tol)
         self.last_solve = res
         slots = list(s1) + list(s2)
         if len(layout) != len(slots):

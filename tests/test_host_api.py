@@ -35,6 +35,83 @@ def test_library_exports_every_declared_symbol(gpf):
     assert declared == set(_backend.EXPORTED_SYMBOLS), "ctypes binding and header disagree"
 
 
+def _header_prototypes():
+    """{name: [C parameter type, ...]} of every gps_* prototype of the public header, comments stripped, `const` and the
+    parameter names dropped ("void* const*" keeps its inner const: it is a type of its own below)."""
+    src = open(os.path.join(ROOT, "include", "gpflowslim_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", " ", src)
+    protos = {}
+    for ret, name, params in re.findall(r"\b(int|const\s+char\s*\*)\s+(gps_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        types = []
+        for p in params.split(","):
+            p = " ".join(p.replace("*", " * ").split())
+            if p == "void":
+                continue
+            words = p.split(" ")
+            assert len(words) >= 2 and re.match(r"^[A-Za-z_][A-Za-z0-9_]*$", words[-1]), "%s: cannot read parameter %r" % (name, p)
+            words = words[:-1]                                    # the parameter's name
+            if words[0] == "const":
+                words = words[1:]
+            types.append(" ".join(words).replace(" *", "*"))
+        protos[name] = types
+    return src, protos
+
+
+def test_ctypes_argument_lists_match_the_header():
+    """_SIGNATURES against the header, argument by argument: a 28-argument prototype with one int / int64_t slip would
+    corrupt the call frame silently.  Needs neither a GPU nor the built library."""
+    from gpflowSlim import _abi
+    c = ctypes
+    P = c.POINTER
+    ctype = {"int": c.c_int, "int64_t": c.c_int64, "double": c.c_double,
+             "int*": P(c.c_int), "int64_t*": P(c.c_int64), "double*": P(c.c_double),
+             "int32_t*": P(c.c_int32), "uint32_t*": P(c.c_uint32), "long long*": P(c.c_longlong),
+             "char*": c.c_char_p, "void*": c.c_void_p, "gps_handle_t": c.c_void_p, "gps_allreduce_fn": c.c_void_p,
+             "gps_handle_t*": P(c.c_void_p), "void* const*": P(c.c_void_p),
+             "gps_kern_node_t*": P(_abi.KernNode), "gps_lik_t*": P(_abi.LikDesc), "gps_rff_desc_t*": P(_abi.RffDesc)}
+    src, protos = _header_prototypes()
+    # every gps_* name followed by "(" is a prototype the parser read (the function-pointer typedef is "(*gps_allreduce_fn)")
+    assert set(protos) == set(re.findall(r"\b(gps_[a-z0-9_]+)\s*\(", src)), "a prototype of the header could not be parsed"
+    assert set(protos) == set(_abi.EXPORTED_SYMBOLS)
+    assert protos.pop("gps_last_error") == ["gps_handle_t"] and protos.pop("gps_comm_load_error") == []
+    assert set(protos) == set(_abi._SIGNATURES)
+    for name, types in sorted(protos.items()):
+        unknown = [t for t in types if t not in ctype]
+        assert not unknown, "%s: no ctypes class for %s" % (name, unknown)
+        want = [ctype[t] for t in types]
+        got = _abi._SIGNATURES[name]
+        assert len(got) == len(want), "%s: %d arguments bound, %d declared" % (name, len(got), len(want))
+        for i, (g, w, t) in enumerate(zip(got, want, types)):
+            assert g is w, "%s: argument %d is %s in the header, bound as %s" % (name, i, t, g.__name__)
+
+
+def test_factor_claim_sets_the_key_on_a_clean_exit_only():
+    """Handle.factor_claim on a handle that never saw a device: no claim inside the block, the key after a clean exit, no
+    claim after an exception; every assignment of the key drops the partitioned-factor claim (dist_state)."""
+    from gpflowSlim import _backend as be
+    h = object.__new__(be.Handle)
+    h.factor_key = "old"
+    h.dist_state = {"key": "old"}
+    with h.factor_claim("new"):
+        assert h.factor_key is None and h.dist_state is None
+        h.dist_state = {"key": "inside"}
+    assert h.factor_key == "new" and h.dist_state is None
+    h.dist_state = {"key": "new"}
+    with pytest.raises(ZeroDivisionError):
+        with h.factor_claim("never"):
+            assert h.factor_key is None and h.dist_state is None
+            h.dist_state = {"key": "inside"}
+            1 / 0
+    assert h.factor_key is None
+    h.factor_key = None
+    assert h.dist_state is None
+    h.dist_state = {"key": "again"}
+    h._drop_resident()
+    assert h.factor_key is None and h.dist_state is None and h.resident_token is None
+    h._h = None                                                    # (nothing to destroy)
+
+
 def test_documented_options_are_the_accepted_options():
     """Every key gps_set_option accepts is documented in the public header's option list, and the list names no key the
     library does not take (option keys missing from the header; round 6 removed 25 keys with their designs)."""
