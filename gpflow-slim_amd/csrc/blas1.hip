@@ -8,6 +8,7 @@
 // All of them stream each matrix element exactly once with 16-byte loads; wave
 // reductions use 64-wide shuffles.
 #include "gps_common.hpp"
+#include <algorithm>
 
 typedef double v2d __attribute__((ext_vector_type(2)));
 
@@ -676,6 +677,43 @@ int gps_launch_rows_axpby(gps_handle_t h, double* X, i64 ldx, const double* Y, i
   LaunchScope ls(h, KC_OTHER, 3.0 * rows * cols, 24.0 * rows * cols);
   dim3 grid((unsigned)((cols + 255) / 256), (unsigned)(rows < 32768 ? rows : 32768));
   hipLaunchKernelGGL(rows_axpby_kernel, grid, dim3(256), 0, h->stream, X, ldx, Y, ldy, rows, cols, a, b);
+  GPS_HIP(h, hipGetLastError());
+  return GPS_OK;
+}
+// D = X + sign Y (sign = +-1) on [rows, cols] blocks with their own leading dimensions: the operand sums of the Strassen level
+// (strassen.hpp).  Two doubles per access; grid-stride over column pairs (x) and rows (y), four rows in flight per thread.
+typedef double sum_v2d __attribute__((ext_vector_type(2)));
+__global__ __launch_bounds__(256) void block_sum_kernel(double* __restrict__ D, i64 ldd, const double* __restrict__ X, i64 ldx,
+                                                        const double* __restrict__ Y, i64 ldy, i64 rows, i64 cols2, double sign) {
+  for (i64 c = (i64)blockIdx.x * blockDim.x + threadIdx.x; c < cols2; c += (i64)gridDim.x * blockDim.x) {
+    i64 rr = blockIdx.y;
+    for (; rr + 3 * (i64)gridDim.y < rows; rr += 4 * (i64)gridDim.y) {
+      sum_v2d x[4], y[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        x[u] = *reinterpret_cast<const sum_v2d*>(X + (rr + u * (i64)gridDim.y) * ldx + 2 * c);
+        y[u] = *reinterpret_cast<const sum_v2d*>(Y + (rr + u * (i64)gridDim.y) * ldy + 2 * c);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) *reinterpret_cast<sum_v2d*>(D + (rr + u * (i64)gridDim.y) * ldd + 2 * c) = x[u] + sign * y[u];
+    }
+    for (; rr < rows; rr += gridDim.y)
+      *reinterpret_cast<sum_v2d*>(D + rr * ldd + 2 * c) =
+          *reinterpret_cast<const sum_v2d*>(X + rr * ldx + 2 * c) + sign * *reinterpret_cast<const sum_v2d*>(Y + rr * ldy + 2 * c);
+  }
+}
+// Counted with the GEMM class: the sums are part of the price of the products they feed (roofline.frac of the class stays whole).
+int gps_launch_block_sum(gps_handle_t h, double* D, i64 ldd, const double* X, i64 ldx, const double* Y, i64 ldy, i64 rows, i64 cols,
+                         int sign) {
+  if (rows <= 0 || cols <= 0) return GPS_OK;
+  if ((cols & 1) || (ldd & 1) || (ldx & 1) || (ldy & 1) || (((uintptr_t)D | (uintptr_t)X | (uintptr_t)Y) & 15))
+    return gps_fail(h, GPS_ERR_ARG, "block_sum: blocks must be 16-byte aligned with even widths and leading dimensions");
+  LaunchScope ls(h, KC_GEMM, (double)rows * (double)cols, 24.0 * (double)rows * (double)cols);
+  ls.tag[0] = rows; ls.tag[1] = cols; ls.tag[3] = -1;
+  const i64 cols2 = cols / 2;
+  const unsigned gx = (unsigned)std::min<i64>((cols2 + 255) / 256, 64);
+  const unsigned gy = (unsigned)std::min<i64>(rows, std::max<i64>(1, 4096 / gx));
+  hipLaunchKernelGGL(block_sum_kernel, dim3(gx, gy), dim3(256), 0, h->stream, D, ldd, X, ldx, Y, ldy, rows, cols2, sign < 0 ? -1.0 : 1.0);
   GPS_HIP(h, hipGetLastError());
   return GPS_OK;
 }

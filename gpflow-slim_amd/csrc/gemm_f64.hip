@@ -71,6 +71,8 @@ struct GemmArgs {
   // kernel STARTS -- on an in-order stream that means "everything launched before this kernel has completed".
   unsigned long long* sig_ptr; unsigned long long sig_val;
   long long* stamps;  // diagnostics (gps_diag_gemm_timeline): [blockIdx][6] = start, end, HW_ID, XCC_ID, K loop start, K loop end (100 MHz ticks); else null
+  // Second target of the DUAL kernel (gps_launch_gemm_nt_dual): the same tile also goes to C2 (op2 0: -=, 2: +=); unread otherwise
+  double* C2 = nullptr; i64 ldc2 = 0; int op2 = 0;
 };
 
 // bijective XCD remap: blocks b, b+8, b+16 ... (same XCD) get consecutive ids
@@ -130,7 +132,7 @@ __device__ __forceinline__ void decode_tile(int id, int Tm, int Tn, int& tm, int
 // BKT: K-slab depth.  The per-slab cost of the staging and the barrier (~0.3 us) is fixed, so the small tiles, whose
 // slab holds only 4-16 MFMAs per wave, use deeper slabs (fewer of them); the square MFMA-bound tiles keep 16.
 #define GEMM_KERNEL_NAME gemm_nt_f64_kernel
-#define GEMM_PAIR_TPARAM
+#define GEMM_PAIR_TPARAM , bool DUAL = false
 #include "gemm_f64_kernel.inc"
 #undef GEMM_KERNEL_NAME
 #undef GEMM_PAIR_TPARAM
@@ -312,6 +314,39 @@ int gps_launch_gemm_nt_ex(gps_handle_t h, int op, int lower, int tri, i64 M, i64
   if (tb == 128) return launch_cfg<128, 128, 2>(h, op, lower, g, M, N);
   if (tb == 64) return launch_cfg<64, 64, 2>(h, op, lower, g, M, N);
   return launch_cfg<32, 32, 2>(h, op, lower, g, M, N);
+}
+
+// One product, two targets (the Strassen level, strassen.hpp):  C -= A B^T ;  C2 -= / += A B^T  (op2 0 / 2).  Always the scheduled
+// 128 x 128 tile, whole K per tile (no tail split: its last-arriving slice knows one target), no triangle, no batch.
+int gps_launch_gemm_nt_dual(gps_handle_t h, i64 M, i64 N, i64 K, const double* A, i64 lda, const double* B, i64 ldb,
+                            double* C, i64 ldc, double* C2, i64 ldc2, int op2) {
+  if (M <= 0 || N <= 0 || K <= 0) return GPS_OK;
+  if (M % 128 || N % 128 || K % BK_MIN || !C || !C2 || (op2 != 0 && op2 != 2))
+    return gps_fail(h, GPS_ERR_ARG, "gemm_nt_dual: M,N must be multiples of 128 and K of 16, two targets, op2 0 or 2");
+  if ((lda & 1) || (ldb & 1) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15))
+    return gps_fail(h, GPS_ERR_ARG, "gemm_nt_dual: operands must be 16-byte aligned with even leading dimension");
+  if (C == A || C2 == A || C == C2) return gps_fail(h, GPS_ERR_ARG, "gemm_nt_dual: no in-place form");
+  if ((M / 128) * (N / 128) > 0x7fffffff) return gps_fail(h, GPS_ERR_ARG, "gemm_nt: too many tiles");
+  GemmArgs g;
+  g.A = A; g.B = B; g.C = C; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.K = (int)K; g.triA = 0;
+  g.batch = 1; g.pair = 0;
+  g.a_rs = g.a_cs = g.b_rs = g.b_cs = g.c_rs = g.c_cs = g.a_cm = g.b_cm = g.c_cm = 0;
+  g.cb_tiles = 0; g.cb_stride = 0;
+  g.Tm = (int)(M / 128); g.Tn = (int)(N / 128);
+  g.ntiles = g.Tm * g.Tn; g.tpb = g.ntiles;
+  g.nfull = g.ntiles; g.nsplit = 1; g.ws = nullptr; g.cnt = nullptr;
+  g.stamps = nullptr;
+  g.sig_ptr = h->next_sig_ptr; g.sig_val = h->next_sig_val; h->next_sig_ptr = nullptr;      // consumed by this launch
+  g.C2 = C2; g.ldc2 = ldc2; g.op2 = op2;
+  const double t128 = (double)g.ntiles;
+  LaunchScope ls(h, KC_GEMM, 2.0 * t128 * 128.0 * 128.0 * (double)K, t128 * 4.0 * 128.0 * 128.0 * 8.0 + 8.0 * (double)K * (double)(M + N));
+  ls.tag[0] = M; ls.tag[1] = N; ls.tag[2] = K; ls.tag[3] = 50 + op2;      // (two targets: no single-target launch has these tags)
+  const size_t lds = (size_t)(2 * (128 + 128) * (16 + 2)) * sizeof(double);
+  int rc = gps_dyn_lds(h, reinterpret_cast<const void*>(&gemm_nt_f64_kernel<128, 128, 2, false, 0, 2, 16, true>), (int)lds);
+  if (rc) return rc;
+  hipLaunchKernelGGL((gemm_nt_f64_kernel<128, 128, 2, false, 0, 2, 16, true>), dim3(g.ntiles), dim3(256), lds, h->stream, g);
+  GPS_HIP(h, hipGetLastError());
+  return GPS_OK;
 }
 
 // Trailing update of the block-column (multi-GPU) factorisation in one launch:  for every owned column block

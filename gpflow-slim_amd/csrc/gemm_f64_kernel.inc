@@ -4,8 +4,12 @@
 // the K ranges of every workgroup add up to the same length.  (Without it a launch whose tiles all fit the GPU at once takes as long
 // as its longest tile -- the dense time -- whatever the triangle saves.)  Two instantiations of ONE text rather than a run-time
 // loop around the body: the loop cost the one-tile kernel 0.6 % at N = 32768 (same-box A/B, round 6).
+// DUAL (one-tile kernel, 128 x 128, C -= A B^T only): the tile is applied to a second target C2 as well (GemmArgs::C2 / ldc2 / op2).
 template <int BM, int BN, int WGM, bool LOWER, int OP, int PIPE = 0, int BKT = 16 GEMM_PAIR_TPARAM>
 __global__ __launch_bounds__(256, 2) void GEMM_KERNEL_NAME(GemmArgs g) {
+#ifdef GEMM_PAIRED
+  constexpr bool DUAL = false;                    // (two targets: the one-tile kernel only)
+#endif
   constexpr int BK = BKT, LS = BKT + 2;           // (shadow the file-level defaults)
   constexpr int TPR = BKT / 2, RPP = 256 / TPR;   // threads per staged row (16 bytes each), rows per pass
   constexpr int WGN = 4 / WGM;
@@ -328,6 +332,31 @@ __global__ __launch_bounds__(256, 2) void GEMM_KERNEL_NAME(GemmArgs g) {
           else if (OP == 3) *cp = -av;
           else *cp = av;
         }
+  }
+  if (DUAL) {
+    // the same product into a second target (C2 -= / += : g.op2), by the same batched read-modify-write
+    double* gC2 = g.C2;
+    const bool sub2 = g.op2 == 0;
+#pragma unroll
+    for (int i0 = 0; i0 < MI; i0 += IB) {
+      double cv[IB][NI][4];
+#pragma unroll
+      for (int ii = 0; ii < IB; ++ii)
+#pragma unroll
+        for (int j = 0; j < NI; ++j)
+#pragma unroll
+          for (int rg = 0; rg < 4; ++rg)
+            cv[ii][j][rg] = gC2[(row0 + (i0 + ii) * 16 + 4 * rg) * g.ldc2 + col0 + j * 16];
+#pragma unroll
+      for (int ii = 0; ii < IB; ++ii)
+#pragma unroll
+        for (int j = 0; j < NI; ++j)
+#pragma unroll
+          for (int rg = 0; rg < 4; ++rg) {
+            const double av = acc[0][i0 + ii][j][rg];
+            gC2[(row0 + (i0 + ii) * 16 + 4 * rg) * g.ldc2 + col0 + j * 16] = sub2 ? cv[ii][j][rg] - av : cv[ii][j][rg] + av;
+          }
+    }
   }
 #ifdef GEMM_PAIRED
   }   // rep

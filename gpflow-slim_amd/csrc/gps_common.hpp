@@ -283,6 +283,10 @@ struct gps_handle_s {
     bool linvT_stale = false;    // the resident factor's transposed block inverses have not been produced yet (gpr_ensure_linvT)
   } small;
   DevBuf dGemmWs{bufs}, dGemmCnt{bufs};   // slice partials + arrival counters of the GEMM tail split
+  // One Strassen level for the largest rectangular updates (strassen.hpp; HipOps::gemm decides): seven half-size products for
+  // eight, when every quadrant edge is at least this many elements (option "gemm_strassen_min": a multiple of 128, 0 = off).
+  int gemm_strassen_min = 4096;
+  DevBuf dStrS{bufs}, dStrT{bufs};        // its operand sums S [M/2, K/2], T [N/2, K/2] (main stream only: one product in flight)
   // ---- random-feature GPR (gps_rff.hip): L = chol(Phi^T Phi + s I) [pad(F), pad(F)] in dK / dLinv, L^-1 B and C in dAlpha ----
   // valid while factor_gen still is what it was when the factor was made (every entry that rebuilds dK bumps it)
   struct RffFactor { bool have = false; unsigned long long gen = 0; i64 F = 0, r = 0; int kind = -1, d = 0; bool refine = false; } rff;
@@ -425,6 +429,13 @@ int gps_launch_gemm_nt_ex(gps_handle_t h, int op, int lower, int tri, i64 M, i64
                           double* C, i64 ldc, const GemmBatch* bt);
 int gps_launch_gemm_nt_cyclic(gps_handle_t h, i64 M, i64 nblocks, i64 nb, i64 stride, i64 K, const double* A, i64 lda,
                               double* C, i64 ldc, int c_packed = 0);
+// one product into two targets:  C -= A B^T  and  C2 (op2 0: -=, 2: +=) A B^T  (128 x 128 tiles; C, C2 disjoint from each other
+// and from the operands) -- the products of the Strassen level (strassen.hpp) that feed two quadrants
+int gps_launch_gemm_nt_dual(gps_handle_t h, i64 M, i64 N, i64 K, const double* A, i64 lda, const double* B, i64 ldb,
+                            double* C, i64 ldc, double* C2, i64 ldc2, int op2);
+// blas1.hip : D = X + sign Y on [rows, cols] blocks (cols, leading dimensions even; 16-byte aligned)
+int gps_launch_block_sum(gps_handle_t h, double* D, i64 ldd, const double* X, i64 ldx, const double* Y, i64 ldy, i64 rows, i64 cols,
+                         int sign);
 // potrf_base.hip : factor one 128x128 diagonal block in place (lower), write its
 // inverse (full 128x128, zero upper) to Linv_blk; info word gets min(index+1) of a
 // non-positive pivot (index counted from row0).

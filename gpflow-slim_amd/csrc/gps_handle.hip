@@ -141,6 +141,10 @@ extern "C" int gps_set_option(gps_handle_t h, const char* key, double value) {
   if (!h || !key) return GPS_ERR_ARG;
   if (strcmp(key, "gemm_force_tile") == 0) { h->gemm_force_tb = (int)value; return GPS_OK; }
   if (strcmp(key, "gemm_tail_split") == 0) { h->gemm_tail_split = (int)value; return GPS_OK; }
+  if (strcmp(key, "gemm_strassen_min") == 0) {
+    if (value < 0 || value != (double)((i64)value) || (i64)value % 128) return gps_fail(h, GPS_ERR_ARG, "gemm_strassen_min: 0 or a multiple of 128");
+    h->gemm_strassen_min = (int)value; return GPS_OK;
+  }
   if (strcmp(key, "kmat_fast") == 0) { h->kmat_fast = (int)value; return GPS_OK; }
   if (strcmp(key, "kmat_mfma") == 0) { h->kmat_mfma = (int)value; return GPS_OK; }
   if (strcmp(key, "trsv_wave") == 0) { h->trsv_wave = (int)value; return GPS_OK; }
@@ -186,8 +190,12 @@ extern "C" int gps_diag_gemm_nt(gps_handle_t h, int op, int lower, int64_t m, in
   GPS_HIP(h, hipMemcpyAsync(h->dTmp2.p, B, bb, hipMemcpyHostToDevice, h->stream));
   GPS_HIP(h, hipMemcpyAsync(h->dTmp3.p, C, cb, hipMemcpyHostToDevice, h->stream));
   // (lower 3 / 4: A lower triangular / B lower triangular -- the forms behind the wide inverse blocks of predict_f)
+  // lower 0 / 1 go the way the recursion's updates go (HipOps::gemm): with "gemm_strassen_min" lowered, through the Strassen level
+  h->refine_now = false;
+  HipOps ops{h, nullptr, nullptr, nullptr};
   int rc = lower >= 3 ? gps_launch_gemm_nt_ex(h, op, 0, lower - 1, m, n, k, h->dTmp.d(), k, h->dTmp2.d(), k, h->dTmp3.d(), n, nullptr)
-                      : gps_launch_gemm_nt(h, op, lower, m, n, k, h->dTmp.d(), k, h->dTmp2.d(), k, h->dTmp3.d(), n);
+         : lower == 2 ? gps_launch_gemm_nt(h, op, lower, m, n, k, h->dTmp.d(), k, h->dTmp2.d(), k, h->dTmp3.d(), n)
+                      : ops.gemm(op, lower, m, n, k, h->dTmp.d(), k, h->dTmp2.d(), k, h->dTmp3.d(), n);
   if (rc) return rc;
   GPS_HIP(h, hipMemcpyAsync(C, h->dTmp3.p, cb, hipMemcpyDeviceToHost, h->stream));
   GPS_HIP(h, hipStreamSynchronize(h->stream));

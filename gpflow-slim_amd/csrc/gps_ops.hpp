@@ -5,6 +5,7 @@
 #pragma once
 #include "gps_common.hpp"
 #include "blocked.hpp"
+#include "strassen.hpp"
 #include "dist_schedule.hpp"
 #include <climits>
 #include <cmath>
@@ -50,8 +51,42 @@ struct HipOps {
     const double* W = (transposed ? linvT : linv) + blk * GPS_TILE * GPS_TILE;
     return gps_launch_trsm_panel(h, B, ldb, m, D, ldd, W, transposed);
   }
+  // The handle's main stream: not the side, follower / deferred or bulk streams, whose launches must stay short-lived and which
+  // would share the Strassen work buffers with the chain.
+  bool on_main_stream() const {
+    if (saved_stream || saved_stream_d) return false;
+    if (h->side_stream && h->stream == h->side_stream) return false;
+    if (h->def_stream && h->stream == h->def_stream) return false;
+    if (h->dist.bulk_set && h->stream == h->dist.bulk_stream) return false;
+    return true;
+  }
+  // C (op)= A B^T.  The largest plain updates (C -= A B^T on the main stream, plain leaves) take one Strassen level
+  // (strassen.hpp): rectangular ones whose quadrants reach "gemm_strassen_min", and the off-diagonal square of a lower /
+  // trapezoid update twice that size.  Everything else, and every product of the level itself, is gemm_plain.
   int gemm(int op, int lower, i64 M, i64 N, i64 K, const double* A, i64 lda, const double* B,
            i64 ldb, double* C, i64 ldc) {
+    const i64 smin = h->gemm_strassen_min;
+    if (smin > 0 && op == 0 && !h->refine_now && C != A && on_main_stream()) {
+      if (lower == 0 && strassen_shape_ok(M, N, K, smin)) {
+        GPS_HIP(h, h->dStrS.ensure((size_t)(M / 2) * (size_t)(K / 2) * 8));
+        GPS_HIP(h, h->dStrT.ensure((size_t)(N / 2) * (size_t)(K / 2) * 8));
+        const int rc = strassen_nt(*this, M, N, K, A, lda, B, ldb, C, ldc, h->dStrS.d(), h->dStrT.d());
+        return rc < 0 ? gps_fail(h, GPS_ERR_ARG, "strassen_nt: bad shape") : rc;
+      }
+      int rc = 0;
+      if (lower == 1 && strassen_lower_split(*this, M, N, K, A, lda, B, ldb, C, ldc, smin, &rc)) return rc;
+    }
+    return gemm_plain(op, lower, M, N, K, A, lda, B, ldb, C, ldc);
+  }
+  int add(double* D, i64 ldd, const double* X, i64 ldx, const double* Y, i64 ldy, i64 rows, i64 cols, int sign) {
+    return gps_launch_block_sum(h, D, ldd, X, ldx, Y, ldy, rows, cols, sign);
+  }
+  int gemm2(i64 M, i64 N, i64 K, const double* A, i64 lda, const double* B, i64 ldb, double* C, i64 ldc, double* C2, i64 ldc2, int op2) {
+    if (!C2) return gps_launch_gemm_nt(h, 0, 0, M, N, K, A, lda, B, ldb, C, ldc);
+    return gps_launch_gemm_nt_dual(h, M, N, K, A, lda, B, ldb, C, ldc, C2, ldc2, op2);
+  }
+  int gemm_plain(int op, int lower, i64 M, i64 N, i64 K, const double* A, i64 lda, const double* B,
+                 i64 ldb, double* C, i64 ldc) {
     // Beside a latency chain (the follower / deferred stream) a rectangular update goes out in launches of at most
     // follower_max_wgs 128 x 128 tiles: a launch with more workgroups than the GPU holds keeps handing freed slots to its own
     // waiting workgroups, and the chain's launches -- a few hundred short workgroups each -- queue behind them (measured,
