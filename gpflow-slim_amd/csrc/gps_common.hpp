@@ -295,6 +295,9 @@ struct gps_handle_s {
   // valid while factor_gen still is what it was when the solve was made
   struct KgprSolve { bool have = false; unsigned long long gen = 0; i64 m = 0, n = 0; } kgpr;
   int kron_cg_check_every = 8;            // option "kron_cg_check_every": the host reads the loop state every this many iterations
+  // ---- GPMC (gps_gpmc.hip): L = chol(K + jitter I) in dK / dLinv, V^T in dAlpha, G^T in dS2, U^T in dS3 (planes [k][pad(n)]) ----
+  // valid while factor_gen still is what it was when gps_gpmc_lik_grad left them (gps_diag_gpmc_front times its kernels on them)
+  struct GpmcState { bool have = false; unsigned long long gen = 0; i64 n = 0, k = 0; } gpmc;
 };
 
 static inline int gps_fail(gps_handle_t h, int code, const std::string& msg) {
@@ -522,6 +525,10 @@ int gps_lik_prepare(gps_handle_t h, const gps_lik_t* lik, i64 k, LikHost* out);
 int gps_lik_launch(gps_handle_t h, const LikHost* L, const double* fmu, const double* mean, const double* fvar, i64 v_si, i64 v_sq,
                    const double* Y, i64 n, i64 k, int want_grad, double oscale, double* dmu, double* dvar, i64 o_si, i64 o_sq,
                    double* ve_sum, double* dparam_sum, double* dvar_sum);
+// log p(Y | F + mean) itself, no q(f): F through (f_si, f_sq) on the device, mean (or NULL) and Y [n, k] row-major; G (or NULL)
+// = d log p / d F through (g_si, g_sq).  *sum / *dparam_sum on return; the stream is synchronised.  Not for MultiClass.
+int gps_lik_point_launch(gps_handle_t h, const LikHost* L, const double* F, i64 f_si, i64 f_sq, const double* mean, const double* Y,
+                         i64 n, i64 k, double* G, i64 g_si, i64 g_sq, double* sum, double* dparam_sum);
 int gps_launch_lik_var_plane(gps_handle_t h, const double* base, const double* extra, i64 n, double* out);
 int gps_launch_lik_rowsq(gps_handle_t h, const double* A, i64 lda, i64 rows, i64 cols, const double* Ht, i64 ldh, i64 k, double* out);
 int gps_launch_lik_abar(gps_handle_t h, const double* Bt, i64 ld, i64 rows, i64 cols, const double* Et, const double* Ht, i64 lde,
@@ -631,6 +638,15 @@ int gps_launch_kron_alpha(gps_handle_t h, const double* C, const double* x, cons
 // part2 [gps_kron_spectrum_blocks][2] = partial sums of log den and 1 / den, w1 [m] ; w2 [n] (null: no columns pass)
 int gps_launch_kron_spectrum(gps_handle_t h, const double* e1, const double* e2, const int* rng, i64 m, i64 n, double s,
                              double noise_var, double* w1, double* w2, double* part2);
+// gps_gpmc.hip : products of a lower-triangular L [n, n] (only i >= j is read) with skinny right-hand sides kept as planes
+// [r][ld] (one row per column of the [n, r] matrix), and the rank-r seed of the Cholesky adjoint
+//   trans 0: Ft[q][i] = sum_{j <= i} L[i][j] Bt[q][j] ;  trans 1: Ft[q][j] = sum_{i >= j} L[i][j] Bt[q][i]
+// part (trans 1): room for gps_tri_skinny_part_doubles(n, r) doubles
+size_t gps_tri_skinny_part_doubles(i64 n, i64 r);
+int gps_launch_tri_skinny(gps_handle_t h, int trans, const double* L, i64 ldl, i64 n, const double* Bt, i64 ldb, i64 r, double* Ft,
+                          i64 ldf, double* part);
+// P[i][j] = sum_q Ut[q][max(i, j)] Vt[q][min(i, j)] for i, j < n, zero up to np
+int gps_launch_chol_seed(gps_handle_t h, const double* Ut, i64 ldu, const double* Vt, i64 ldv, i64 r, i64 n, double* P, i64 ldp, i64 np);
 // diag.hip
 int gps_run_mfma_diag(gps_handle_t h, int waves_per_simd, double* tflops, int* layout_ok);
 int gps_run_gemm_timeline(gps_handle_t h, int op, int lower, i64 m, i64 n, i64 k, int reps, long long* stamps_out,

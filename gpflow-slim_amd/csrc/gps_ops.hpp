@@ -422,19 +422,27 @@ static int stage_time(gps_handle_t h, int a, int b, double* out) {
 
 // Cholesky adjoint on the device (Murray 2016, eq. 10):  for L = chol(K) and a lower-triangular cotangent Lbar, the symmetric
 // Kbar with <Kbar, dK> = <Lbar, dL> is  L^-T (Phi(P) + Phi(P)^T) L^-1 / 2,  P = L^T Lbar, Phi = lower triangle with halved
-// diagonal.  U = L^T (upper, row-major; `bl` carries L's block inverses).  out <- 2 Kbar (the callers fold the 1/2); P: scratch.
-static int chol_adjoint2(gps_handle_t h, Blocked<HipOps>& bl, const double* U, const double* Lbar, double* out, double* P, i64 mp) {
-  int rc = gps_launch_transpose(h, Lbar, mp, mp, mp, out, mp);
-  if (rc) return rc;
-  rc = gps_launch_gemm_nt(h, 1, 0, mp, mp, mp, U, mp, out, mp, P, mp);                 // P[i][j] = sum_k L[k][i] Lbar[k][j]
-  if (rc) return rc;
-  rc = gps_launch_tri_map(h, P, mp, mp, 0);               // Phi(P) + Phi(P)^T = the lower triangle of P mirrored
-  if (rc) return rc;
-  rc = bl.trsm_rn_rec(U, mp, mp, 0, P, mp, mp);                                        // Y = Psym L^-1
+// diagonal.  U = L^T (upper, row-major; `bl` carries L's block inverses).
+// Second half, from P = Phi(P) + Phi(P)^T (symmetric, overwritten): out <- 2 Kbar (the callers fold the 1/2).
+static int chol_adjoint2_solves(gps_handle_t h, Blocked<HipOps>& bl, const double* U, double* P, double* out, i64 mp) {
+  int rc = bl.trsm_rn_rec(U, mp, mp, 0, P, mp, mp);                                    // Y = Psym L^-1
   if (rc) return rc;
   rc = gps_launch_transpose(h, P, mp, mp, mp, out, mp);                                // Y^T
   if (rc) return rc;
   return bl.trsm_rn_rec(U, mp, mp, 0, out, mp, mp);                                    // Y^T L^-1 = (L^-T Y)^T  (symmetric)
+}
+// First half for a general Lbar: P by one product (gps_gpmc.hip seeds it from its rank-r form instead); P: scratch.
+static int chol_adjoint2_front(gps_handle_t h, const double* U, const double* Lbar, double* out, double* P, i64 mp) {
+  int rc = gps_launch_transpose(h, Lbar, mp, mp, mp, out, mp);
+  if (rc) return rc;
+  rc = gps_launch_gemm_nt(h, 1, 0, mp, mp, mp, U, mp, out, mp, P, mp);                 // P[i][j] = sum_k L[k][i] Lbar[k][j]
+  if (rc) return rc;
+  return gps_launch_tri_map(h, P, mp, mp, 0);             // Phi(P) + Phi(P)^T = the lower triangle of P mirrored
+}
+static int chol_adjoint2(gps_handle_t h, Blocked<HipOps>& bl, const double* U, const double* Lbar, double* out, double* P, i64 mp) {
+  int rc = chol_adjoint2_front(h, U, Lbar, out, P, mp);
+  if (rc) return rc;
+  return chol_adjoint2_solves(h, bl, U, P, out, mp);
 }
 
 // ---- pieces the block-column distributed entries share (gps_dist.hip, dist_grad.hip) ---------------------------------------

@@ -1,6 +1,7 @@
 // Variational expectations of the non-Gaussian likelihoods (likelihoods.py:121-152 and the special cases :191-487) with
 // their derivatives in the moments of q(f): the per-point term of the SVGP bound and the two per-point cotangents its
-// backward pass starts from (gps_svgp.hip: gps_svgp_elbo_lik / gps_svgp_elbo_lik_grad), and gps_lik_varexp on its own.
+// backward pass starts from (gps_svgp.hip: gps_svgp_elbo_lik / gps_svgp_elbo_lik_grad), and gps_lik_varexp on its own.  Also
+// log p(y | f) itself with its derivative (lik_point_kernel: the likelihood of gps_gpmc.hip, and gps_lik_logp on its own).
 //   quadrature kinds   var_exp = sum_h w_h l(f_h),  f_h = mu + sqrt(2 var) x_h,  w_h = hermgauss weight / sqrt(pi)   (:140-152)
 //                      dmu = sum_h w_h l'(f_h) ;  dvar = sum_h w_h l'(f_h) x_h / sqrt(2 var)     (autodiff through :147)
 //   closed forms       Poisson / Exponential with the exp link                                       (:220-224, :240-243)
@@ -107,6 +108,51 @@ __global__ __launch_bounds__(256) void lik_elem_kernel(const LikDev L, const dou
   if (lane == 0) { sh[0][wave] = s_ve; sh[1][wave] = s_dp; sh[2][wave] = s_hv; }
   __syncthreads();
   if (threadIdx.x < 3) partial[3 * blockIdx.x + threadIdx.x] = (sh[threadIdx.x][0] + sh[threadIdx.x][1]) + (sh[threadIdx.x][2] + sh[threadIdx.x][3]);
+}
+
+// log p(y | f) itself at f = F + mean, no q(f): the likelihood of the MCMC models (models/gpmc.py:75-77), one thread per (point,
+// latent).  Bernoulli and Student-t are lik_logp; the other three are the closed forms above at fvar = 0, written out (the
+// quadrature path at fvar = 0 would divide by sqrt(2 var), and its weights do not add up to exactly 1).  F and G = d log p / d F
+// through strided views, so they can stay planes [k][ld] between the triangular products of gps_gpmc.hip.
+template <int KIND>
+__global__ __launch_bounds__(256) void lik_point_kernel(const LikDev L, const double* __restrict__ F, LikView fv,
+                                                        const double* __restrict__ mean, const double* __restrict__ Y, i64 n, int k,
+                                                        double* __restrict__ G, LikView gv, double* __restrict__ partial) {
+  __shared__ double sh[2][4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const i64 total = n * (i64)k;
+  const i64 stride = (i64)gridDim.x * blockDim.x;
+  double s_lp = 0.0, s_dp = 0.0;
+  for (i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+    const i64 i = e / k;
+    const int q = (int)(e - i * k);
+    double f = F[i * fv.si + q * fv.sq];
+    if (mean) f += mean[e];
+    const double y = Y[e];
+    double lp, g, gp = 0.0;
+    if (KIND == GPS_LIK_GAUSSIAN) {                    // densities.gaussian through likelihoods.py:181
+      const double s2 = L.p[0], d = y - f;
+      lp = -0.5 * log(2.0 * M_PI) - 0.5 * log(s2) - 0.5 * (d * d) / s2;
+      g = d / s2; gp = -0.5 / s2 + 0.5 * (d * d) / (s2 * s2);
+    } else if (KIND == GPS_LIK_POISSON) {              // densities.poisson(exp(f) binsize, y), :213
+      const double b = L.p[0];
+      const double ex = exp(f) * b;
+      lp = y * f - ex - lgamma(y + 1.0) + y * log(b);
+      g = y - ex;
+    } else if (KIND == GPS_LIK_EXPONENTIAL) {          // densities.exponential(exp(f), y), :231
+      const double ex = exp(-f) * y;
+      lp = -ex - f;
+      g = ex - 1.0;
+    } else {
+      lik_logp<KIND>(L, f, y, lp, g, gp);
+    }
+    s_lp += lp; s_dp += gp;
+    if (G) G[i * gv.si + q * gv.sq] = g;
+  }
+  s_lp = lik_wave_sum(s_lp); s_dp = lik_wave_sum(s_dp);
+  if (lane == 0) { sh[0][wave] = s_lp; sh[1][wave] = s_dp; }
+  __syncthreads();
+  if (threadIdx.x < 2) partial[2 * blockIdx.x + threadIdx.x] = (sh[threadIdx.x][0] + sh[threadIdx.x][1]) + (sh[threadIdx.x][2] + sh[threadIdx.x][3]);
 }
 
 // MultiClass with RobustMax: one thread per point, one wavefront per workgroup.  prob_is_largest (likelihoods.py:404-425):
@@ -350,7 +396,69 @@ int gps_lik_launch(gps_handle_t h, const LikHost* LH, const double* fmu, const d
   return GPS_OK;
 }
 
+// The pointwise launch (lik_point_kernel).  The sums come back like gps_lik_launch's: one partial pair per workgroup, added in
+// index order on the host.
+int gps_lik_point_launch(gps_handle_t h, const LikHost* LH, const double* F, i64 f_si, i64 f_sq, const double* mean, const double* Y,
+                         i64 n, i64 k, double* G, i64 g_si, i64 g_sq, double* sum, double* dparam_sum) {
+  const LikDev& L = *reinterpret_cast<const LikDev*>(LH);
+  if (L.kind == GPS_LIK_MULTICLASS)
+    return gps_fail(h, GPS_ERR_UNSUPPORTED, "likelihood: log p(y | f) of MultiClass is piecewise constant in f: no pointwise form with a gradient");
+  const LikView fv{f_si, f_sq}, gv{g_si, g_sq};
+  const i64 nb = (n * k + 255) / 256;
+  const unsigned grid = (unsigned)(nb < 8192 ? nb : 8192);
+  GPS_HIP(h, h->dLikPart.ensure((size_t)grid * 16));
+  double* part = h->dLikPart.d();
+  {
+    LaunchScope ls(h, KC_OTHER, 40.0 * n * k, 8.0 * n * k * (G ? 4.0 : 3.0));
+#define LIK_GO(KIND) hipLaunchKernelGGL((lik_point_kernel<KIND>), dim3(grid), dim3(256), 0, h->stream, L, F, fv, mean, Y, n, (int)k, G, gv, part)
+    switch (L.kind) {
+      case GPS_LIK_GAUSSIAN: LIK_GO(GPS_LIK_GAUSSIAN); break;
+      case GPS_LIK_BERNOULLI: LIK_GO(GPS_LIK_BERNOULLI); break;
+      case GPS_LIK_POISSON: LIK_GO(GPS_LIK_POISSON); break;
+      case GPS_LIK_EXPONENTIAL: LIK_GO(GPS_LIK_EXPONENTIAL); break;
+      case GPS_LIK_STUDENT_T: LIK_GO(GPS_LIK_STUDENT_T); break;
+      default: return gps_fail(h, GPS_ERR_ARG, "likelihood: unknown kind");
+    }
+#undef LIK_GO
+  }
+  GPS_HIP(h, hipGetLastError());
+  std::vector<double> hp((size_t)grid * 2);
+  GPS_HIP(h, hipMemcpyAsync(hp.data(), part, hp.size() * 8, hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipStreamSynchronize(h->stream));
+  double lp = 0.0, dp = 0.0;
+  for (unsigned b = 0; b < grid; ++b) { lp += hp[2 * b]; dp += hp[2 * b + 1]; }
+  if (sum) *sum = lp;
+  if (dparam_sum) *dparam_sum = dp;
+  return GPS_OK;
+}
+
 // ---- C ABI: the kernels on their own (host arrays in and out) -------------------------------------------------------------
+extern "C" int gps_lik_logp(gps_handle_t h, const gps_lik_t* lik, const double* F, const double* Y, int64_t n, int64_t k,
+                            double* logp_sum, double* dF_out, double* dparam_out) {
+  if (!h || !lik || !F || !Y || !logp_sum || n <= 0 || k <= 0) return gps_fail(h, GPS_ERR_ARG, "gps_lik_logp: bad argument");
+  if (k > GPS_TILE) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gps_lik_logp: at most 128 latent functions");
+  GPS_HIP(h, hipSetDevice(h->device));
+  LikHost LH;
+  int rc = gps_lik_prepare(h, lik, k, &LH);
+  if (rc) return rc;
+  const size_t nk = (size_t)n * k;
+  GPS_HIP(h, h->dLikIn.ensure(2 * nk * 8));              // F | Y
+  double* dF = h->dLikIn.d(); double* dY = dF + nk; double* dG = nullptr;
+  GPS_HIP(h, hipMemcpyAsync(dF, F, nk * 8, hipMemcpyHostToDevice, h->stream));
+  GPS_HIP(h, hipMemcpyAsync(dY, Y, nk * 8, hipMemcpyHostToDevice, h->stream));
+  if (dF_out) { GPS_HIP(h, h->dLikOut.ensure(nk * 8)); dG = h->dLikOut.d(); }
+  double lp = 0.0, dp = 0.0;
+  rc = gps_lik_point_launch(h, &LH, dF, k, 1, nullptr, dY, n, k, dG, k, 1, &lp, &dp);
+  if (rc) return rc;
+  if (dF_out) {
+    GPS_HIP(h, hipMemcpyAsync(dF_out, dG, nk * 8, hipMemcpyDeviceToHost, h->stream));
+    GPS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  *logp_sum = lp;
+  if (dparam_out) *dparam_out = dp;
+  return GPS_OK;
+}
+
 extern "C" int gps_lik_varexp(gps_handle_t h, const gps_lik_t* lik, const double* fmu, const double* fvar, const double* Y,
                               int64_t n, int64_t k, double* var_exp_out, double* dmu_out, double* dvar_out, double* dparam_out) {
   if (!h || !lik || !fmu || !fvar || !Y || !var_exp_out || n <= 0 || k <= 0 || (!dmu_out) != (!dvar_out))

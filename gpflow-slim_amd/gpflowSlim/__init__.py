@@ -12,6 +12,7 @@ from . import ekernels
 from . import kernel_kitchen_sink
 from . import mean_functions
 from . import densities
+from . import priors
 from . import likelihoods
 from . import conditionals
 from . import features

@@ -160,6 +160,7 @@ _SVGP = [_vp, _prog, _int, _dp, _i64, _i64, _dbl, _dp, _i64]                   #
 _SPARSE = [_vp, _prog, _int, _dp, _i64, _dp, _i64, _i64, _dbl, _dbl, _dp, _i64]    # h, prog, n, Z, m, X, n, d, jitter, noise, resid, r
 _GPLVM = [_vp, _prog, _int, _dp, _i64, _dp, _dp, _i64, _i64]                   # h, prog, n, Z, m, Xmu, Xvar, n, q
 _KGPR = [_vp, _prog, _int, _dp, _i64, _i64, _prog, _int, _dp, _i64, _i64, _dp, _dp, _dbl, _dp, _dp, _i32p, _int, _dbl, _dp]
+_GPMC = [_vp, _prog, _int, _dp, _i64, _i64, _dbl, _dp, _i64, _dp, _dp, _lik]    # h, prog, n, X, n, d, jitter, V, k, Y, mean, lik
 
 _SIGNATURES = {
     "gps_create": [_int, ctypes.POINTER(_vp)],
@@ -181,6 +182,11 @@ _SIGNATURES = {
     "gps_svgp_elbo_lik": _SVGP + [_dp, _dp, _dp, _i64, _dp, _int, _int, _lik, _dbl, _dp, _dp, _dp, _ip],
     "gps_svgp_elbo_lik_grad": _SVGP + [_dp, _dp, _dp, _i64, _dp, _int, _int, _lik, _dbl, _dp, _dp, _int, _ip, _dp, _dp, _dp, _dp,
                                        _dp, _ip],
+    "gps_lik_logp": [_vp, _lik, _dp, _dp, _i64, _i64, _dp, _dp, _dp],
+    "gps_tri_skinny": [_vp, _dp, _i64, _dp, _i64, _int, _dp],
+    "gps_chol_seed": [_vp, _dp, _dp, _i64, _i64, _dp],
+    "gps_gpmc_lik": _GPMC + [_dp, _ip],
+    "gps_gpmc_lik_grad": _GPMC + [_dp, _dp, _int, _ip, _dp, _dp, _dp, _ip],
     "gps_kmat_vjp": [_vp, _prog, _int, _dp, _i64, _dp, _i64, _i64, _dp, _dp, _int, _ip],
     "gps_kmat_input_vjp": [_vp, _prog, _int, _dp, _i64, _dp, _i64, _i64, _dp, _dp],
     "gps_gauss_kl": [_vp, _dp, _i64, _dp, _i64, _dp, _int, _dp, _ip],
@@ -249,6 +255,7 @@ _SIGNATURES = {
     "gps_diag_trsm512": [_vp, _i64, _int, _int, _int, _dp, _dp],
     "gps_diag_trsm512_stamps": [_vp, _i64, _int, _int, _dp, _llp, _i64],
     "gps_diag_trsm_leaf": [_vp, _i64, _int, _int, _int, _dp, _dp],
+    "gps_diag_gpmc_front": [_vp, _int, _dp],
     "gps_diag_set_cu_mask": [_vp, _u32p, _int],
     "gps_diag_gemm_timeline": [_vp, _int, _int, _i64, _i64, _i64, _int, _llp, _i64, _i64p, _dp],
 }

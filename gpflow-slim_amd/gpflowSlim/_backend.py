@@ -90,10 +90,12 @@ class Handle(object):
     tests/test_gpu_residency.py):
 
       drops X and factor   release_buffers, gpr_set_data, conditional, base_conditional, svgp_elbo*, sgpr, sgpr_grad,
-                           psi_stats, bgplvm*, rff_features, rff_gram, rff_lml*, rff_predict(refactor), kron_cg, kgpr_lml*
+                           psi_stats, bgplvm*, rff_features, rff_gram, rff_lml*, rff_predict(refactor), kron_cg, kgpr_lml*,
+                           gpmc_lik*
       drops the factor     gpr_lml, gpr_lml_grad, gpr_predict(refactor), dist_begin, dist_lml, dist_lml_grad
       keeps both           kmat, potrf, trsm_lower, kmat_vjp, kmat_input_vjp (scratch: dXnew, dTmp*), gauss_kl (dS2-dS4),
-                           lik_varexp (dLik*), gpr_predict / rff_predict(refactor=False), kgpr_predict, sparse_last_terms,
+                           lik_varexp, lik_logp (dLik*), tri_skinny, chol_seed (dTmp*, dStage), gpr_predict /
+                           rff_predict(refactor=False), kgpr_predict, sparse_last_terms,
                            the per-panel dist_*, comm_*, diag_*, options, profiling
     """
 
@@ -971,6 +973,87 @@ class Handle(object):
         _raise_if_not_pd(info, _PD_KUU)
         out = (elbo.value, slots[:ns.value].copy(), glik.value, g_qmu, self._q_sqrt_grad(g_q, qnd), g_mean)
         return out + (g_Z,) if want_grad_Z else out
+
+    # ---- GPMC: the whitened model for MCMC, and its kernels on their own
+    def lik_logp(self, lik, F, Y, want_grad=False):
+        """Sum over points and latents of log p(Y | F) of a device likelihood (``lik`` from make_lik; not MultiClass), F and
+        Y [N, K].  want_grad: also (d log p / d F [N, K], d sum / d parameter 0)."""
+        desc, keep = lik
+        F, Y = _f64(F), _f64(Y)
+        _need(F.ndim == 2 and Y.shape == F.shape and F.size > 0, "F and Y must both be [N, K]")
+        if desc.kind == LIK_MULTICLASS:
+            raise NotImplementedError("log p(y | f) of MultiClass is piecewise constant in f: no pointwise form with a gradient")
+        n, k = F.shape
+        lp, dpar = ctypes.c_double(0), ctypes.c_double(0)
+        G = np.zeros((n, k)) if want_grad else None
+        self._call("gps_lik_logp", _byref(desc), _ptr(F), _ptr(Y), n, k, _byref(lp), _opt(G), _byref(dpar) if want_grad else None)
+        del keep
+        return (lp.value, G, dpar.value) if want_grad else lp.value
+
+    def tri_skinny(self, L, B, trans=False):
+        """tril(L) @ B, or tril(L).T @ B with trans, for L [N, N] and a skinny B [N, R]: whatever L holds above its diagonal
+        is never read."""
+        L, B = _f64(L), _f64(B)
+        n = L.shape[0]
+        _need(L.shape == (n, n) and B.ndim == 2 and B.shape[0] == n, "L must be [N, N] and B [N, R]")
+        out = np.zeros_like(B)
+        self._call("gps_tri_skinny", _ptr(L), n, _ptr(B), B.shape[1], 1 if trans else 0, _ptr(out))
+        return out
+
+    def chol_seed(self, U, V):
+        """P [Np, Np], Np = N rounded up to a multiple of 128: P[i, j] = U[max(i, j)] . V[min(i, j)] for i, j < N, zero in
+        the padding -- Phi(P) + Phi(P)^T of the Cholesky adjoint for the cotangent tril(G V^T), with U = L^T G."""
+        U, V = _f64(U), _f64(V)
+        _need(U.ndim == 2 and V.shape == U.shape and U.size > 0, "U and V must both be [N, R]")
+        n, r = U.shape
+        npad = -(-n // 128) * 128
+        P = np.empty((npad, npad))
+        self._call("gps_chol_seed", _ptr(U), _ptr(V), n, r, _ptr(P))
+        return P
+
+    def _gpmc_args(self, lik, X, V, Y, mean):
+        desc, _ = lik
+        X, V, Y = _f64(X), _f64(V), _f64(Y)
+        _need(X.ndim == 2 and V.ndim == 2 and V.shape[0] == X.shape[0] and V.size > 0, "X must be [N, D] and V [N, K]")
+        if desc.kind == LIK_MULTICLASS:
+            raise NotImplementedError("log p(y | f) of MultiClass is piecewise constant in f: no pointwise form with a gradient")
+        n, d = X.shape
+        k = V.shape[1]
+        _need(Y.shape == (n, k), "Y must be [N, K] with K = number of latent functions")
+        if mean is not None:
+            mean = _f64(np.broadcast_to(mean, (n, k)))
+        return desc, X, V, Y, mean, n, d, k
+
+    def gpmc_lik(self, prog, X, V, Y, jitter, lik, mean=None):
+        """sum log p(Y | L V + mean), L = chol(K(X) + jitter I)  (models/gpmc.py:72-77); mean: mean_function(X) or None."""
+        desc, X, V, Y, mean, n, d, k = self._gpmc_args(lik, X, V, Y, mean)
+        ll, info = ctypes.c_double(0), ctypes.c_int(0)
+        self._drop_resident()
+        self._call("gps_gpmc_lik", prog, len(prog), _ptr(X), n, d, float(jitter), _ptr(V), k, _ptr(Y), _opt(mean), _byref(desc),
+                   _byref(ll), _byref(info))
+        _raise_if_not_pd(info, _PD_CHOL)
+        return ll.value
+
+    def gpmc_lik_grad(self, prog, X, V, Y, jitter, lik, mean=None):
+        """(loglik, grad_slots, d/d likelihood parameter 0, grad_V [N, K], d/d mean(X) [N, K]) -- gradients w.r.t. the
+        constrained values (gps_gpmc_lik_grad)."""
+        desc, X, V, Y, mean, n, d, k = self._gpmc_args(lik, X, V, Y, mean)
+        ll, glik, info = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_int(0)
+        slots, ns = self._slot_buffer()
+        g_V, g_mean = np.zeros((n, k)), np.zeros((n, k))
+        self._drop_resident()
+        self._call("gps_gpmc_lik_grad", prog, len(prog), _ptr(X), n, d, float(jitter), _ptr(V), k, _ptr(Y), _opt(mean),
+                   _byref(desc), _byref(ll), _ptr(slots), SLOT_CAP, _byref(ns), _byref(glik), _ptr(g_V), _ptr(g_mean),
+                   _byref(info))
+        _raise_if_not_pd(info, _PD_CHOL)
+        return ll.value, slots[:ns.value].copy(), glik.value, g_V, g_mean
+
+    def diag_gpmc_front(self, reps=5):
+        """Microseconds of (F = L V, U = L^T G, the rank-R seed, the seed by the generic adjoint's transpose + N^3 product +
+        mirror) on what the last gpmc_lik_grad left on the device."""
+        out = np.zeros(4)
+        self._call("gps_diag_gpmc_front", int(reps), _ptr(out))
+        return out
 
     def gauss_kl(self, q_mu, q_sqrt, K=None):
         """kullback_leiblers.py:26-105"""

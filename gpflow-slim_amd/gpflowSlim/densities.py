@@ -1,7 +1,8 @@
 """Log-densities.
 
 Mirrors gpflowSlim/densities.py: gaussian :24-25, bernoulli / poisson / exponential / student_t :33-70 (what the
-likelihoods' logp are made of; numpy on the host), multivariate_normal :73-95.  The triangular
+likelihoods' logp are made of; numpy on the host), lognormal / gamma / beta / laplace (what gpflowSlim.priors is made of),
+multivariate_normal :73-95.  The triangular
 solve of multivariate_normal runs on the GPU (csrc: recursive trsm); the scalar reductions of
 an [N, R] host array stay on the host.
 """
@@ -37,6 +38,28 @@ def student_t(x, mean, scale, deg_free):
         - 0.5 * (np.log(np.square(scale)) + np.log(deg_free) + np.log(np.pi))
     return const - 0.5 * (deg_free + 1.) * \
         np.log(1. + (1. / deg_free) * (np.square((x - mean) / scale)))
+
+
+def lognormal(x, mu, var):
+    """densities.py:28-30"""
+    lnx = np.log(x)
+    return gaussian(lnx, mu, var) - lnx
+
+
+def gamma(shape, scale, x):
+    """densities.py:45-47"""
+    return -shape * np.log(scale) - gammaln(shape) + (shape - 1.) * np.log(x) - x / scale
+
+
+def beta(alpha, beta, y):
+    """densities.py:60-66 (y clipped to [1e-6, 1 - 1e-6] as there)"""
+    y = np.clip(y, 1e-6, 1 - 1e-6)
+    return (alpha - 1.) * np.log(y) + (beta - 1.) * np.log(1. - y) + gammaln(alpha + beta) - gammaln(alpha) - gammaln(beta)
+
+
+def laplace(mu, sigma, y):
+    """densities.py:69-70"""
+    return -np.abs(mu - y) / sigma - np.log(2. * sigma)
 
 
 def multivariate_normal(x, mu, L):

@@ -4,3 +4,4 @@ from .svgp import SVGP
 from .sgpr import SGPR, GPRFITC
 from .gplvm import BayesianGPLVM, PCA_reduce
 from .kgpr import KGPR
+from .gpmc import GPMC

@@ -73,8 +73,8 @@ class Model(object):
         lp = 0.0
         if any(p.prior is not None for p in self.parameters):
             # log-priors (params.py:176-194: log p(constrained) + log |d constrained / d unconstrained|) are host functions of
-            # one parameter each, whatever object the caller supplied as `prior`: central differences over that parameter's own
-            # unconstrained entries
+            # one parameter each, whatever object the caller supplied as `prior`: the closed form where the prior has `dlogp`
+            # and the transform `log_jacobian_grad`, else central differences over that parameter's own unconstrained entries
             gp, lp = self._prior_and_grad([p for p, _ in grads])
             g = g + gp
         return -float(lml + lp), -g
@@ -89,7 +89,15 @@ class Model(object):
                 def lp_at(u, p=p):
                     return p._build_prior(u, p.transform.forward(u))
                 total += lp_at(u0)
-                if getattr(p, "trainable", True):
+                dlogp = getattr(p.prior, "dlogp", None)
+                djac = getattr(p.transform, "log_jacobian_grad", None)
+                if getattr(p, "trainable", True) and dlogp is not None and djac is not None:
+                    # the closed form where prior and transform both have it (gpflowSlim.priors; Identity, Exp, Log1pe):
+                    # d/du [log p(forward(u)) + log |d forward / du|], one pass over the parameter
+                    u1 = np.atleast_1d(u0)
+                    gpiece = (np.broadcast_to(dlogp(p.transform.forward(u1)), u1.shape) * p.transform.forward_grad(u1)
+                              + djac(u1)).astype(np.float64).ravel()
+                elif getattr(p, "trainable", True):
                     flat = u0.ravel()
                     for i in range(flat.size):
                         hh = 1e-6 * max(1.0, abs(flat[i]))

@@ -1,6 +1,7 @@
 """Parameter transforms (host-side fp64 scalar math).
 
-Mirrors gpflowSlim/transforms.py: Identity :40-57, Log1pe :117-181, Exp :80-114, positive :377.
+Mirrors gpflowSlim/transforms.py: Identity :40-57, Log1pe :117-181, Exp :80-114, positive :377; ``forward_grad`` and
+``log_jacobian_grad`` are this package's (the reference gets both from autodiff).
 Hyper-parameters are stored unconstrained and read through ``forward`` on every use, exactly as
 the reference does (params.py:142-145,164-166), so e.g. ``variance=1.0`` round-trips through
 softplus(.)+1e-6 before it reaches the device.
@@ -28,6 +29,9 @@ class Transform(object):
         """d forward(x) / d x, elementwise (chain rule from constrained to unconstrained gradients)."""
         raise NotImplementedError
 
+    # Identity, Exp and Log1pe also have log_jacobian_grad(x) = d log_jacobian_tensor(x) / d x, elementwise; a transform
+    # without it is differentiated numerically (Model._prior_and_grad)
+
 
 class Identity(Transform):
     """transforms.py:40-57"""
@@ -40,6 +44,9 @@ class Identity(Transform):
 
     def log_jacobian_tensor(self, x):
         return 0.0
+
+    def log_jacobian_grad(self, x):
+        return np.zeros_like(np.asarray(x, dtype=settings.float_type))
 
     def forward_grad(self, x):
         return np.ones_like(np.asarray(x, dtype=settings.float_type))
@@ -62,6 +69,9 @@ class Exp(Transform):
 
     def log_jacobian_tensor(self, x):
         return float(np.sum(x))
+
+    def log_jacobian_grad(self, x):
+        return np.ones_like(np.asarray(x, dtype=settings.float_type))
 
     def forward_grad(self, x):
         return np.exp(np.asarray(x, dtype=settings.float_type))
@@ -89,6 +99,11 @@ class Log1pe(Transform):
     def log_jacobian_tensor(self, x):
         # transforms.py:148-149
         return float(-np.sum(np.logaddexp(0.0, -np.asarray(x, dtype=settings.float_type))))
+
+    def log_jacobian_grad(self, x):
+        # d / dx of -softplus(-x) = sigmoid(-x)
+        x = np.asarray(x, dtype=settings.float_type)
+        return np.exp(-np.logaddexp(0.0, x))
 
     def forward_grad(self, x):
         # d softplus / dx = sigmoid(x)

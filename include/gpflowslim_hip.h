@@ -370,6 +370,36 @@ int gps_svgp_elbo_lik_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_no
                            double* elbo, double* grad_slots, int n_slots_cap, int* n_slots_out, double* grad_lik,
                            double* grad_q_mu, double* grad_q_sqrt, double* grad_mean, double* grad_Z, int* info);
 
+/* ---- GPMC: the whitened model for MCMC (models/gpmc.py:28-93) ------------------------------------------------------------
+ * log p(Y | F) itself (Likelihood.logp, no q(f)) summed over points and latents: F, Y host [n, k].  Optional dF_out host
+ * [n, k] = d log p / d F; optional dparam_out = d sum / d param[0] (the Gaussian variance, the Student-t scale; 0 otherwise).
+ * Every kind except GPS_LIK_MULTICLASS, whose log p is piecewise constant in F (GPS_ERR_UNSUPPORTED).  Partial sums are
+ * added in a fixed order: bit-reproducible.                                                                              */
+int gps_lik_logp(gps_handle_t h, const gps_lik_t* lik, const double* F, const double* Y, int64_t n, int64_t k,
+                 double* logp_sum, double* dF_out, double* dparam_out);
+/* Products of a lower-triangular L host [n, n] with a skinny B host [n, r]: out host [n, r] = L B (trans == 0) or L^T B
+ * (trans != 0).  Only the entries of L on and below the diagonal are read.  No atomics; bit-reproducible.               */
+int gps_tri_skinny(gps_handle_t h, const double* L, int64_t n, const double* B, int64_t r, int trans, double* out);
+/* The rank-r seed of the Cholesky adjoint: P_out host [np, np], np = n rounded up to a multiple of 128, with
+ * P[i][j] = sum_q U[max(i, j)][q] V[min(i, j)][q] for i, j < n and zero elsewhere; U, V host [n, r].  For a loss that
+ * depends on L = chol(K) through F = L V only, with G = d loss / d F and U = L^T G, this is Phi(P) + Phi(P)^T of
+ * P = L^T tril(G V^T) (Murray 2016; Phi: lower triangle with halved diagonal) without the n x n x n product.            */
+int gps_chol_seed(gps_handle_t h, const double* U, const double* V, int64_t n, int64_t r, double* P_out);
+/* loglik = sum log p(Y | L V + mean), L = chol(kern.K(X) + jitter I)  (gpmc.py:72-77): X host [n, d_all], V, Y host [n, k],
+ * mean host [n, k] = mean_function(X) or NULL.  *info > 0: not positive definite, as in gps_potrf (loglik is not set).  */
+int gps_gpmc_lik(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                 double jitter, const double* V, int64_t k, const double* Y, const double* mean, const gps_lik_t* lik,
+                 double* loglik, int* info);
+/* ... and its gradient with respect to the constrained values: grad_slots in the slot layout of gps_gpr_lml_grad, grad_lik =
+ * d / d param[0], grad_V host [n, k] (= L^T G, G = d loglik / d F) and, optional, grad_mean host [n, k] (= G).  The seed
+ * above, two triangular solves and the kernel-matrix VJP; K, L, the seed and Kbar stay on the device; the jitter has no
+ * gradient.  With profiling on, gps_last_stage_ms: K and its factor, F and the likelihood, U and the seed, the two solves,
+ * the VJP.                                                                                                                */
+int gps_gpmc_lik_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                      double jitter, const double* V, int64_t k, const double* Y, const double* mean, const gps_lik_t* lik,
+                      double* loglik, double* grad_slots, int n_slots_cap, int* n_slots_out, double* grad_lik,
+                      double* grad_V, double* grad_mean, int* info);
+
 /* Vector-Jacobian product of the kernel-matrix build -- reverse-mode autodiff through kern.K(X, X2) (kernels.py:408-439,
  * 1071-1084; neural_kernel_network.py:41-47):  grad_slots[s] = sum_ij W[i][j] d k(X_i, X2_j) / d theta_s  for a
  * caller-supplied cotangent W host [n, m] (X2 == NULL: K(X, X), W [n, n] used as given).  Slot layout of
@@ -738,6 +768,10 @@ int gps_diag_trsm512_stamps(gps_handle_t h, int64_t m, int backward, int reps, d
  * resid_out: scaled residual of the solve, checked on the host                                                  */
 int gps_diag_trsm_leaf(gps_handle_t h, int64_t m, int mode, int upper, int reps, double* us_per_launch,
                        double* resid_out);
+/* the GPMC kernels on what the last gps_gpmc_lik_grad left resident (GPS_ERR_STATE without one), average microseconds over
+ * `reps`: us_out4[0] F = L V, [1] U = L^T G, [2] the rank-R seed, [3] the seed by the generic route of the Cholesky
+ * adjoint instead (transpose of the cotangent, the n x n x n product, the mirror)                                    */
+int gps_diag_gpmc_front(gps_handle_t h, int reps, double* us_out4);
 
 #ifdef __cplusplus
 }
