@@ -581,6 +581,9 @@ int gps_launch_kmat_input_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n
                               const double* dXc, i64 nc, i64 d_all, const double* Wd, i64 ldw, double factor,
                               double* grad_X_host);
 int gps_kdiag_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, double kbar, double* grad_slots_host);
+// ... and of a program with Linear, whose Kdiag depends on the point: X host [n, d_all], one kbar per point (host), added to the slots
+int gps_kdiag_vjp_points(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, const double* X, i64 n, const double* kbar,
+                         double* grad_slots_host);
 int gps_launch_kmat_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dXr, i64 nr, const double* dXc,
                         i64 nc, i64 d_all, const double* Wd, i64 ldw, int accumulate, double* grad_slots_host);
 // psi.hip : expectations of the RBF kernel under q(x_n) = N(mu_n, diag S_n) and their VJPs (all pointers on the device)
@@ -645,8 +648,9 @@ int gps_launch_kron_spectrum(gps_handle_t h, const double* e1, const double* e2,
 size_t gps_tri_skinny_part_doubles(i64 n, i64 r);
 int gps_launch_tri_skinny(gps_handle_t h, int trans, const double* L, i64 ldl, i64 n, const double* Bt, i64 ldb, i64 r, double* Ft,
                           i64 ldf, double* part);
-// P[i][j] = sum_q Ut[q][max(i, j)] Vt[q][min(i, j)] for i, j < n, zero up to np
-int gps_launch_chol_seed(gps_handle_t h, const double* Ut, i64 ldu, const double* Vt, i64 ldv, i64 r, i64 n, double* P, i64 ldp, i64 np);
+// P[i][j] = sum_q Ut[q][max(i, j)] Vt[q][min(i, j)] for i, j < n, zero up to np ; accumulate: added to what P holds for i, j < n
+int gps_launch_chol_seed(gps_handle_t h, const double* Ut, i64 ldu, const double* Vt, i64 ldv, i64 r, i64 n, double* P, i64 ldp, i64 np,
+                         int accumulate = 0);
 // diag.hip
 int gps_run_mfma_diag(gps_handle_t h, int waves_per_simd, double* tflops, int* layout_ok);
 int gps_run_gemm_timeline(gps_handle_t h, int op, int lower, i64 m, i64 n, i64 k, int reps, long long* stamps_out,

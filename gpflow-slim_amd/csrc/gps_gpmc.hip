@@ -257,12 +257,13 @@ int gps_launch_tri_skinny(gps_handle_t h, int trans, const double* L, i64 ldl, i
   return GPS_OK;
 }
 
-int gps_launch_chol_seed(gps_handle_t h, const double* Ut, i64 ldu, const double* Vt, i64 ldv, i64 r, i64 n, double* P, i64 ldp, i64 np) {
+int gps_launch_chol_seed(gps_handle_t h, const double* Ut, i64 ldu, const double* Vt, i64 ldv, i64 r, i64 n, double* P, i64 ldp, i64 np,
+                         int accumulate) {
   if (np <= 0) return GPS_OK;
-  if (r <= 0) { GPS_HIP(h, hipMemset2DAsync(P, (size_t)ldp * 8, 0, (size_t)np * 8, (size_t)np, h->stream)); return GPS_OK; }
+  if (r <= 0) { if (!accumulate) GPS_HIP(h, hipMemset2DAsync(P, (size_t)ldp * 8, 0, (size_t)np * 8, (size_t)np, h->stream)); return GPS_OK; }
   const dim3 grid((unsigned)((np + 255) / 256), (unsigned)((np + SEED_ROWS - 1) / SEED_ROWS));
   for (i64 q0 = 0; q0 < r; q0 += 16) {
-    const int rc = (int)(r - q0 < 16 ? r - q0 : 16), acc = q0 > 0;
+    const int rc = (int)(r - q0 < 16 ? r - q0 : 16), acc = accumulate || q0 > 0;
     const double* U = Ut + q0 * ldu; const double* V = Vt + q0 * ldv;
     LaunchScope ls(h, KC_OTHER, 2.0 * n * n * rc, 8.0 * np * np);
     ls.tag[0] = n; ls.tag[1] = rc; ls.tag[3] = 12;

@@ -11,6 +11,13 @@
 #include <cmath>
 #include <algorithm>
 
+// gps_sgpmc.hip : Gt[q][j] (+)= sum_i X[i][j] Et[q][i] over the rows of a row-major chunk X [rows, mp] (a chunk of A^T as
+// trsm_rec leaves it; ld even, mp a multiple of 128): planes [r][ldg >= mp] from planes [r][lde >= rows]; the row chunks'
+// partials (part) are added in index order -- bit-reproducible
+size_t gps_skinny_xt_part_doubles(i64 rows, i64 mp, i64 r);
+int gps_launch_skinny_xt(gps_handle_t h, const double* X, i64 ld, i64 rows, i64 mp, const double* Et, i64 lde, i64 r, double* Gt, i64 ldg,
+                         int accumulate, double* part);
+
 // ---- the HIP "Ops" policy for blocked.hpp ----------------------------------------------------
 struct HipOps {
   gps_handle_t h;

@@ -698,6 +698,59 @@ int gps_kdiag_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 
   return GPS_OK;
 }
 
+// The same for a program with Linear, whose Kdiag_i = sum_d v_d x_id^2 depends on the point (kernels.py:507-510): X host
+// [n, d_all], kbar host [n], added to the slots.  O(n) work on the host from what the caller holds there anyway; forward mode
+// over the fold per point and primitive.  Polynomial and network programs are not taken.
+int gps_kdiag_vjp_points(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, const double* X, i64 n, const double* kbar,
+                         double* grad_slots_host) {
+  GGBuilt B;
+  int rc = gg_build(h, prog, n_nodes, d_all, B);
+  if (rc) return rc;
+  if (B.P.nkn) return gps_fail(h, GPS_ERR_UNSUPPORTED, "Kdiag gradient: neural-kernel-network programs are not supported here");
+  for (int nd = 0; nd < B.P.n_nodes; ++nd)
+    if (B.P.nodes[nd].op == GPS_K_POLYNOMIAL) return gps_fail(h, GPS_ERR_UNSUPPORTED, "Kdiag gradient: Polynomial is not supported here");
+  std::vector<double> acc((size_t)B.prims.n_slots, 0.0);
+  for (i64 i = 0; i < n; ++i) {
+    const double* x = X + i * d_all;
+    double val[GRAD_MAX_NODES];
+    for (int nd = 0; nd < B.P.n_nodes; ++nd) {
+      const GradNode& g = B.P.nodes[nd];
+      if (g.op == GPS_K_ADD || g.op == GPS_K_MUL) continue;
+      val[nd] = g.variance;
+      if (g.op == GPS_K_LINEAR) {
+        double s = 0.0;
+        for (int f = 0; f < g.nf; ++f) { const GradFeat& ft = B.prims.feats[(size_t)(g.f0 + f)]; const double v = x[ft.dim] * ft.param; s += v * v; }
+        val[nd] = s;
+      }
+    }
+    for (int p = 0; p < B.P.n_prims; ++p) {
+      double sv[GPS_MAX_STACK + 1], st[GPS_MAX_STACK + 1]; int sp = 0;
+      const GradNode* mine = nullptr;
+      for (int nd = 0; nd < B.P.n_nodes; ++nd) {
+        const GradNode& g = B.P.nodes[nd];
+        if (g.op == GPS_K_ADD || g.op == GPS_K_MUL) {
+          const double b = sv[--sp], tb = st[sp], a = sv[--sp], ta = st[sp];
+          sv[sp] = (g.op == GPS_K_ADD) ? a + b : a * b;
+          st[sp] = (g.op == GPS_K_ADD) ? ta + tb : ta * b + a * tb;
+          ++sp;
+        } else {
+          sv[sp] = val[nd]; st[sp] = (g.prim == p) ? 1.0 : 0.0; ++sp;
+          if (g.prim == p) mine = &g;
+        }
+      }
+      if (!mine) continue;
+      const double c = kbar[i] * st[0];
+      if (mine->op == GPS_K_LINEAR) {
+        for (int f = 0; f < mine->nf; ++f) { const double xd = x[B.prims.feats[(size_t)(mine->f0 + f)].dim]; acc[(size_t)(mine->slot0 + f)] += c * xd * xd; }
+      } else {
+        acc[(size_t)mine->slot0] += c;
+      }
+    }
+  }
+  for (int s = 0; s < B.prims.n_slots; ++s) grad_slots_host[s] += acc[(size_t)s];
+  return GPS_OK;
+}
+
 // grad_X_host [nr, d_all] += factor * sum_j Wd[i][j] d k(xr_i, xc_j) / d xr_i  for a device-resident cotangent Wd [nr, nc];
 // dXc == nullptr: k(xr_i, xr_j) differentiated in its FIRST argument only (for a symmetric Wd the full gradient of
 // sum_ij Wd_ij k(x_i, x_j) with respect to x is twice that).

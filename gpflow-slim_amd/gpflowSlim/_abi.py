@@ -187,6 +187,8 @@ _SIGNATURES = {
     "gps_chol_seed": [_vp, _dp, _dp, _i64, _i64, _dp],
     "gps_gpmc_lik": _GPMC + [_dp, _ip],
     "gps_gpmc_lik_grad": _GPMC + [_dp, _dp, _int, _ip, _dp, _dp, _dp, _ip],
+    "gps_sgpmc_lik": _SVGP + [_dp, _dp, _dp, _i64, _lik, _i64, _dp, _ip],
+    "gps_sgpmc_lik_grad": _SVGP + [_dp, _dp, _dp, _i64, _lik, _i64, _dp, _dp, _int, _ip, _dp, _dp, _dp, _dp, _ip],
     "gps_kmat_vjp": [_vp, _prog, _int, _dp, _i64, _dp, _i64, _i64, _dp, _dp, _int, _ip],
     "gps_kmat_input_vjp": [_vp, _prog, _int, _dp, _i64, _dp, _i64, _i64, _dp, _dp],
     "gps_gauss_kl": [_vp, _dp, _i64, _dp, _i64, _dp, _int, _dp, _ip],

@@ -91,7 +91,7 @@ class Handle(object):
 
       drops X and factor   release_buffers, gpr_set_data, conditional, base_conditional, svgp_elbo*, sgpr, sgpr_grad,
                            psi_stats, bgplvm*, rff_features, rff_gram, rff_lml*, rff_predict(refactor), kron_cg, kgpr_lml*,
-                           gpmc_lik*
+                           gpmc_lik*, sgpmc_lik*
       drops the factor     gpr_lml, gpr_lml_grad, gpr_predict(refactor), dist_begin, dist_lml, dist_lml_grad
       keeps both           kmat, potrf, trsm_lower, kmat_vjp, kmat_input_vjp (scratch: dXnew, dTmp*), gauss_kl (dS2-dS4),
                            lik_varexp, lik_logp (dLik*), tri_skinny, chol_seed (dTmp*, dStage), gpr_predict /
@@ -1054,6 +1054,51 @@ class Handle(object):
         out = np.zeros(4)
         self._call("gps_diag_gpmc_front", int(reps), _ptr(out))
         return out
+
+    # ---- SGPMC: the sparse model for MCMC, streamed over row chunks of the data
+    def _sgpmc_args(self, lik, Z, X, Y, V, mean, chunk_rows):
+        desc, _ = lik
+        Z, X, Y, V = _f64(Z), _f64(X), _f64(Y), _f64(V)
+        _need(Z.ndim == 2 and X.ndim == 2 and Z.shape[1] == X.shape[1] and Z.size > 0 and X.size > 0,
+              "Z must be [M, D] and X [N, D]")
+        _need(V.ndim == 2 and V.shape[0] == Z.shape[0] and V.size > 0, "V must be [M, K]")
+        _need(int(chunk_rows) >= 0 and int(chunk_rows) % 128 == 0, "chunk_rows must be 0 or a multiple of 128")
+        (m, d), n, k = Z.shape, X.shape[0], V.shape[1]
+        if desc.kind == LIK_MULTICLASS:
+            _need(Y.size == n, "MultiClass takes one class label per point")
+            _need(np.all(Y == np.floor(Y)) and Y.min() >= 0 and Y.max() < k, "class labels must be integers in [0, K)")
+        else:
+            _need(Y.shape == (n, k), "Y must be [N, K] with K = number of latent functions")
+        if mean is not None:
+            mean = _f64(np.broadcast_to(mean, (n, k)))
+        return desc, Z, X, Y, V, mean, m, d, n, k
+
+    def sgpmc_lik(self, prog, Z, X, Y, V, jitter, lik, mean=None, chunk_rows=0):
+        """sum of the variational expectations at fmean = A^T V + mean, fvar = Kdiag - colsum(A^2), A = Lm^-1 Kuf
+        (models/sgpmc.py:83-89), the data taken chunk_rows rows at a time (0: the library's choice)."""
+        desc, Z, X, Y, V, mean, m, d, n, k = self._sgpmc_args(lik, Z, X, Y, V, mean, chunk_rows)
+        ll, info = ctypes.c_double(0), ctypes.c_int(0)
+        self._drop_resident()
+        self._call("gps_sgpmc_lik", prog, len(prog), _ptr(Z), m, d, float(jitter), _ptr(X), n, _ptr(Y), _opt(mean), _ptr(V), k,
+                   _byref(desc), int(chunk_rows), _byref(ll), _byref(info))
+        _raise_if_not_pd(info, _PD_KUU)
+        return ll.value
+
+    def sgpmc_lik_grad(self, prog, Z, X, Y, V, jitter, lik, mean=None, chunk_rows=0, want_grad_Z=False, want_grad_mean=True):
+        """(loglik, grad_slots, d/d likelihood parameter 0, grad_V [M, K], d/d mean(X) [N, K][, grad_Z]) -- gradients w.r.t.
+        the constrained values, in the same single pass over the data (gps_sgpmc_lik_grad); want_grad_mean=False: the library is
+        not asked for d/d mean(X) and None stands in its place."""
+        desc, Z, X, Y, V, mean, m, d, n, k = self._sgpmc_args(lik, Z, X, Y, V, mean, chunk_rows)
+        ll, glik, info = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_int(0)
+        slots, ns = self._slot_buffer()
+        g_V, g_mean, g_Z = np.zeros((m, k)), (np.zeros((n, k)) if want_grad_mean else None), np.zeros((m, d))
+        self._drop_resident()
+        self._call("gps_sgpmc_lik_grad", prog, len(prog), _ptr(Z), m, d, float(jitter), _ptr(X), n, _ptr(Y), _opt(mean), _ptr(V),
+                   k, _byref(desc), int(chunk_rows), _byref(ll), _ptr(slots), SLOT_CAP, _byref(ns), _byref(glik), _ptr(g_V),
+                   _opt(g_mean), _ptr(g_Z) if want_grad_Z else None, _byref(info))
+        _raise_if_not_pd(info, _PD_KUU)
+        out = (ll.value, slots[:ns.value].copy(), glik.value, g_V, g_mean)
+        return out + (g_Z,) if want_grad_Z else out
 
     def gauss_kl(self, q_mu, q_sqrt, K=None):
         """kullback_leiblers.py:26-105"""

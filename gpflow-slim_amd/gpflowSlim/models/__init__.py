@@ -5,3 +5,4 @@ from .sgpr import SGPR, GPRFITC
 from .gplvm import BayesianGPLVM, PCA_reduce
 from .kgpr import KGPR
 from .gpmc import GPMC
+from .sgpmc import SGPMC

@@ -21,10 +21,11 @@ from ..params import Parameter
 from .model import GPModel
 
 
-def device_likelihood(likelihood):
-    """((descriptor, arrays it points into), Parameter behind its scalar or None) for a likelihood whose log p(y | f) the
-    device evaluates pointwise; None for everything else.  MultiClass raises."""
-    if isinstance(likelihood, likelihoods.MultiClass):
+def device_likelihood(likelihood, allow_multiclass=False):
+    """((descriptor, arrays it points into), Parameter behind its scalar or None) for a likelihood the device evaluates; None
+    for everything else.  MultiClass raises unless allow_multiclass (SGPMC: its variational expectation is smooth; GPMC's
+    pointwise log p is not)."""
+    if isinstance(likelihood, likelihoods.MultiClass) and not allow_multiclass:
         raise NotImplementedError("GPMC / SGPMC with MultiClass: log p(y | f) of the RobustMax link is piecewise constant in f "
                                   "(its gradient is zero almost everywhere), so there is nothing to sample or optimise with")
     if type(likelihood) is likelihoods.Gaussian:

@@ -400,6 +400,25 @@ int gps_gpmc_lik_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, 
                       double* loglik, double* grad_slots, int n_slots_cap, int* n_slots_out, double* grad_lik,
                       double* grad_V, double* grad_mean, int* info);
 
+/* ---- SGPMC: the sparse model for MCMC (models/sgpmc.py:58-104), streamed over row chunks of the data ---------------------- */
+/* loglik = sum_i var_exp(fmean_i, fvar_i, Y_i) with fmean = A^T V + mean, fvar = Kdiag - colsum(A^2), A = Lm^-1 Kuf,
+ * Lm = chol(Kuu + jitter I)  (sgpmc.py:83-89; the whitened conditional with q_sqrt = None): Z host [m, d_all], X host
+ * [n, d_all], Y host [n, k] ([n] class labels for GPS_LIK_MULTICLASS), mean host [n, k] = mean_function(X) or NULL, V host
+ * [m, k].  All six likelihood kinds.  The data are taken chunk_rows rows at a time (a multiple of 128; 0: the library's
+ * choice): device memory is O(m^2 + m chunk_rows), no [m, n] array exists.  *info > 0: Kuu + jitter I is not positive
+ * definite (nothing else is set).                                                                                        */
+int gps_sgpmc_lik(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m, int64_t d_all,
+                  double jitter, const double* X, int64_t n, const double* Y, const double* mean, const double* V, int64_t k,
+                  const gps_lik_t* lik, int64_t chunk_rows, double* loglik, int* info);
+/* ... and its gradient with respect to the constrained values in the same single pass: grad_slots in the slot layout of
+ * gps_gpr_lml_grad, grad_lik = d / d param[0], grad_V host [m, k], optional grad_mean host [n, k] and grad_Z host
+ * [m, d_all].  With profiling on, gps_last_stage_ms: Kuu and its factor, the forward half summed over the chunks, the
+ * backward half summed over the chunks, the Kuu adjoint, the Kuu VJPs.                                                    */
+int gps_sgpmc_lik_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m, int64_t d_all,
+                       double jitter, const double* X, int64_t n, const double* Y, const double* mean, const double* V, int64_t k,
+                       const gps_lik_t* lik, int64_t chunk_rows, double* loglik, double* grad_slots, int n_slots_cap,
+                       int* n_slots_out, double* grad_lik, double* grad_V, double* grad_mean, double* grad_Z, int* info);
+
 /* Vector-Jacobian product of the kernel-matrix build -- reverse-mode autodiff through kern.K(X, X2) (kernels.py:408-439,
  * 1071-1084; neural_kernel_network.py:41-47):  grad_slots[s] = sum_ij W[i][j] d k(X_i, X2_j) / d theta_s  for a
  * caller-supplied cotangent W host [n, m] (X2 == NULL: K(X, X), W [n, n] used as given).  Slot layout of
