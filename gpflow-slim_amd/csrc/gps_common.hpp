@@ -295,6 +295,10 @@ struct gps_handle_s {
   // valid while factor_gen still is what it was when the solve was made
   struct KgprSolve { bool have = false; unsigned long long gen = 0; i64 m = 0, n = 0; } kgpr;
   int kron_cg_check_every = 8;            // option "kron_cg_check_every": the host reads the loop state every this many iterations
+  // ---- kernel expectations of a Sum of RBF parts (psi_sum.hip, gps_gplvm.hip) ----
+  int psi_sum_chunk = 0;                  // gps_psi_sum_set_chunk: points per chunk of the streamed cross terms (0: gps_psi_sum_chunking decides)
+  DevBuf dPsiParts{bufs};                 // the packed part views (gplvm_upload) and one Psi2 [mp, mp] per part
+  DevBuf dPsiWork{bufs};                  // the chunk's Psi1 blocks of every part, their sums and the dense cotangent: O(P M chunk)
   // ---- GPMC (gps_gpmc.hip): L = chol(K + jitter I) in dK / dLinv, V^T in dAlpha, G^T in dS2, U^T in dS3 (planes [k][pad(n)]) ----
   // valid while factor_gen still is what it was when gps_gpmc_lik_grad left them (gps_diag_gpmc_front times its kernels on them)
   struct GpmcState { bool have = false; unsigned long long gen = 0; i64 n = 0, k = 0; } gpmc;
@@ -603,6 +607,30 @@ int gps_launch_psi_pk(gps_handle_t h, const PsiIn& in, const double* X, i64 ldx,
 int gps_launch_psi2_vjp(gps_handle_t h, const PsiIn& in, const double* PK, i64 ldpk, double* out_n, double* out_z, i64 ldz);
 int gps_launch_psi1_vjp(gps_handle_t h, const PsiIn& in, const double* Y, const double* Yt, i64 ldy, const double* Wt, i64 ldw, i64 r,
                         double* out_n, double* out_z, i64 ldz);
+// ... with a dense cotangent on top of the rank-r one, for the points n0 .. n1-1 only: Psi1_bar[n][m] = sum_r Y W + Bar[n - n0][m],
+// Bar [n1 - n0][ldb] and its transpose BarT [m][ldbt].  out_n [2 q + 1][n] gets its columns n0 .. n1-1; the z pass writes the nz
+// partials [q][ldz] from part_z on (zchunk points each), which gps_launch_psi_fold sums in order once every chunk has run.
+int gps_launch_psi1_vjp_dense(gps_handle_t h, const PsiIn& in, const double* Y, const double* Yt, i64 ldy, const double* Wt, i64 ldw,
+                              i64 r, i64 n0, i64 n1, const double* Bar, i64 ldb, const double* BarT, i64 ldbt, double* out_n,
+                              double* part_z, i64 nz, i64 zchunk, i64 ldz);
+int gps_launch_psi_fold(gps_handle_t h, const double* part, int nchunks, i64 rows, i64 cols, i64 ldp, double* out, i64 ldo);
+// psi_sum.hip : what a Sum of RBF parts on pairwise disjoint latent dimensions adds to the expectations of its parts
+struct PsiDims { int d[GPS_MAX_DIMS]; };
+// points per chunk of the streamed cross terms (a multiple of 16) and the number of chunks; opt > 0 asks for a chunk length
+void gps_psi_sum_chunking(i64 n, i64 m, int opt, i64* chunk, int* nchunks);
+// dst [rows, qp] <- the columns dims.d[0 .. qp-1] of src [rows, q]
+int gps_launch_psi_gather(gps_handle_t h, const double* src, i64 rows, int q, const PsiDims& dims, int qp, double* dst);
+int gps_launch_psi_add(gps_handle_t h, double* dst, const double* src, i64 count);                 // dst += src
+// out [prows, pcols] (leading dimension ldo) <- sum over the blocks p' of T [P][stride] (each [rows, cols], leading dimension ldt),
+// p' > p (after == 1) or p' != p (after == 0), in ascending p'; exact zeros outside [rows, cols]
+int gps_launch_psi_others(gps_handle_t h, const double* T, int P, i64 stride, int p, int after, i64 rows, i64 cols, i64 ldt,
+                          double* out, i64 prows, i64 pcols, i64 ldo);
+// A [m, m] += C + C^T, the lower triangle mirrored: exactly symmetric if A was
+int gps_launch_psi_sym_add(gps_handle_t h, double* A, i64 lda, const double* C, i64 ldc, i64 m);
+// S [mp, mp] <- (X + X^T) / 2 on the leading [m, m] block, exact zeros outside
+int gps_launch_psi_sym_half(gps_handle_t h, const double* X, i64 ldx, i64 m, double* S, i64 mp);
+// psi2n [n, m, m] += sum_{p < p'} T_p[n, :, None] T_p'[n, None, :] + its transpose, T [P][n * m]
+int gps_launch_psi2n_cross(gps_handle_t h, const double* T, int P, i64 n, i64 m, double* psi2n);
 // rff.hip : random-feature maps (kernel_kitchen_sink.py) and the contraction of their cotangent; all pointers on the device
 //   kind GPS_RFF_*; omega [d, F], offset [F], ls [d] (RBF only); c1, c2: the two factors behind the cosine (RBF) or c1 alone
 struct RffDev { int kind; int d; i64 F; double c1, c2; const double* omega; const double* offset; const double* ls; };

@@ -326,14 +326,16 @@ __global__ __launch_bounds__(64) void psi2_vjp_z_kernel(const double* __restrict
 //   per point: t_n = sum_m T, SA = sum_m T d, SB = sum_m T d^2  ->  mu_bar = -a SA ; S_bar = -a t / 2 + a^2 SB / 2
 //   Z_bar[m][q] = sum_n T a d ; d / d l_q = sum_n (2 l_q S_bar_nq + t_n / l_q) ; d / d var = sum T / var
 // Yt [R][ldy] (points along the rows), Wt [R][ldw].  out [2 Q + 1][N] as above (no chunks: the loop over m is short).
-template <int QT>
+// DENSE (the Sum of RBF parts, psi_sum.hip): only the points n0 .. n1-1, and Psi1_bar gets BarT[m][n - n0] on top of the rank-R term.
+template <int QT, bool DENSE>
 __global__ __launch_bounds__(256) void psi1_vjp_n_kernel(const double* __restrict__ Z, const double* __restrict__ Xmu,
                                                          const double* __restrict__ A1, const double* __restrict__ C1,
                                                          const double* __restrict__ par, const double* __restrict__ Yt, i64 ldy,
                                                          const double* __restrict__ Wt, i64 ldw, int R, i64 N, int M, int Q,
-                                                         double* __restrict__ out) {
-  const i64 n = (i64)blockIdx.x * 256 + threadIdx.x;
-  if (n >= N) return;
+                                                         double* __restrict__ out, i64 n0, i64 n1,
+                                                         const double* __restrict__ BarT, i64 ldb) {
+  const i64 n = (DENSE ? n0 : 0) + (i64)blockIdx.x * 256 + threadIdx.x;
+  if (n >= (DENSE ? n1 : N)) return;
   double mu[QT], a[QT], SA[QT], SB[QT];
 #pragma unroll
   for (int q = 0; q < QT; ++q) {
@@ -346,6 +348,7 @@ __global__ __launch_bounds__(256) void psi1_vjp_n_kernel(const double* __restric
   for (int m = 0; m < M; ++m) {
     double bar = 0.0;
     for (int r = 0; r < R; ++r) bar += Yt[(i64)r * ldy + n] * Wt[(i64)r * ldw + m];
+    if (DENSE) bar += BarT[(i64)m * ldb + (n - n0)];
     double d[QT], e = 0.0;
 #pragma unroll
     for (int q = 0; q < QT; ++q) {
@@ -364,23 +367,26 @@ __global__ __launch_bounds__(256) void psi1_vjp_n_kernel(const double* __restric
 }
 
 // thread = inducing point m; blockIdx.y = chunk of points.  Y [N][R] row-major (uniform reads).  part[chunk][q][m] = sum T a d
-template <int QT>
+// DENSE: the chunks cut the points n0 .. N-1 (N = the end of the range), and Psi1_bar gets Bar[n - n0][m] on top.
+template <int QT, bool DENSE>
 __global__ __launch_bounds__(64) void psi1_vjp_z_kernel(const double* __restrict__ Z, const double* __restrict__ Xmu,
                                                         const double* __restrict__ A1, const double* __restrict__ C1,
                                                         const double* __restrict__ par, const double* __restrict__ Y,
                                                         const double* __restrict__ Wt, i64 ldw, int R, i64 N, int M, int Q,
-                                                        i64 chunk, i64 ldp, double* __restrict__ part) {
+                                                        i64 chunk, i64 ldp, double* __restrict__ part, i64 nbase,
+                                                        const double* __restrict__ Bar, i64 ldb) {
   const int m = blockIdx.x * 64 + threadIdx.x;
   if (m >= M) return;
   double z[QT], ZB[QT];
 #pragma unroll
   for (int q = 0; q < QT; ++q) { z[q] = q < Q ? Z[(i64)m * Q + q] : 0.0; ZB[q] = 0.0; }
   const double var = par[0];
-  const i64 n0 = (i64)blockIdx.y * chunk;
+  const i64 n0 = (DENSE ? nbase : 0) + (i64)blockIdx.y * chunk;
   const i64 n1 = n0 + chunk < N ? n0 + chunk : N;
   for (i64 n = n0; n < n1; ++n) {
     double bar = 0.0;
     for (int r = 0; r < R; ++r) bar += Y[n * R + r] * Wt[(i64)r * ldw + m];
+    if (DENSE) bar += Bar[(n - nbase) * ldb + m];
     double d[QT], e = 0.0;
 #pragma unroll
     for (int q = 0; q < QT; ++q) {
@@ -562,7 +568,7 @@ int gps_launch_psi1_vjp(gps_handle_t h, const PsiIn& in, const double* Y, const 
   {
     LaunchScope ls(h, KC_KMAT, work, 8.0 * (2 * Q + 1) * N);
     const dim3 grid((unsigned)cdiv(N, 256));
-#define CALL(QT) hipLaunchKernelGGL((psi1_vjp_n_kernel<QT>), grid, dim3(256), 0, h->stream, in.Z, in.Xmu, in.A1, in.C1, in.par, Yt, ldy, Wt, ldw, R, N, M, Q, out_n)
+#define CALL(QT) hipLaunchKernelGGL((psi1_vjp_n_kernel<QT, false>), grid, dim3(256), 0, h->stream, in.Z, in.Xmu, in.A1, in.C1, in.par, Yt, ldy, Wt, ldw, R, N, M, Q, out_n, (i64)0, (i64)0, (const double*)nullptr, (i64)0)
     PSI_QT_DISPATCH(Q, CALL);
 #undef CALL
     GPS_HIP(h, hipGetLastError());
@@ -570,10 +576,38 @@ int gps_launch_psi1_vjp(gps_handle_t h, const PsiIn& in, const double* Y, const 
   {
     LaunchScope ls(h, KC_KMAT, work, 8.0 * nzch * Q * M);
     const dim3 grid((unsigned)mb, (unsigned)nzch);
-#define CALL(QT) hipLaunchKernelGGL((psi1_vjp_z_kernel<QT>), grid, dim3(64), 0, h->stream, in.Z, in.Xmu, in.A1, in.C1, in.par, Y, Wt, ldw, R, N, M, Q, zchunk, ldz, part_z)
+#define CALL(QT) hipLaunchKernelGGL((psi1_vjp_z_kernel<QT, false>), grid, dim3(64), 0, h->stream, in.Z, in.Xmu, in.A1, in.C1, in.par, Y, Wt, ldw, R, N, M, Q, zchunk, ldz, part_z, (i64)0, (const double*)nullptr, (i64)0)
     PSI_QT_DISPATCH(Q, CALL);
 #undef CALL
     GPS_HIP(h, hipGetLastError());
   }
   return fold(h, part_z, (int)nzch, Q, M, ldz, out_z, ldz);
+}
+
+int gps_launch_psi_fold(gps_handle_t h, const double* part, int nchunks, i64 rows, i64 cols, i64 ldp, double* out, i64 ldo) {
+  return fold(h, part, nchunks, rows, cols, ldp, out, ldo);
+}
+
+// the dense-cotangent form over the points n0 .. n1-1 (a chunk of the Sum's stream): see gps_common.hpp
+int gps_launch_psi1_vjp_dense(gps_handle_t h, const PsiIn& in, const double* Y, const double* Yt, i64 ldy, const double* Wt, i64 ldw,
+                              i64 r, i64 n0, i64 n1, const double* Bar, i64 ldb, const double* BarT, i64 ldbt, double* out_n,
+                              double* part_z, i64 nz, i64 zchunk, i64 ldz) {
+  const i64 N = in.n; const int M = (int)in.m, Q = in.q, R = (int)r;
+  if (n0 < 0 || n1 > N || n0 >= n1 || nz * zchunk < n1 - n0) return gps_fail(h, GPS_ERR_ARG, "gps_launch_psi1_vjp_dense: bad range");
+  const double work = (double)(n1 - n0) * M * (2.0 * R + 6.0 * Q + 42.0);
+  {
+    LaunchScope ls(h, KC_KMAT, work, 8.0 * ((2 * Q + 1) + M) * (n1 - n0));
+    const dim3 grid((unsigned)cdiv(n1 - n0, 256));
+#define CALL(QT) hipLaunchKernelGGL((psi1_vjp_n_kernel<QT, true>), grid, dim3(256), 0, h->stream, in.Z, in.Xmu, in.A1, in.C1, in.par, Yt, ldy, Wt, ldw, R, N, M, Q, out_n, n0, n1, BarT, ldbt)
+    PSI_QT_DISPATCH(Q, CALL);
+#undef CALL
+    GPS_HIP(h, hipGetLastError());
+  }
+  LaunchScope ls(h, KC_KMAT, work, 8.0 * (nz * Q + (n1 - n0)) * M);
+  const dim3 grid((unsigned)cdiv(M, 64), (unsigned)nz);
+#define CALL(QT) hipLaunchKernelGGL((psi1_vjp_z_kernel<QT, true>), grid, dim3(64), 0, h->stream, in.Z, in.Xmu, in.A1, in.C1, in.par, Y, Wt, ldw, R, n1, M, Q, zchunk, ldz, part_z, n0, Bar, ldb)
+  PSI_QT_DISPATCH(Q, CALL);
+#undef CALL
+  GPS_HIP(h, hipGetLastError());
+  return GPS_OK;
 }

@@ -150,6 +150,17 @@ def psi2_chunking(n, m):
     return tm, nt, chunk, -(-n // chunk)
 
 
+def psi_sum_chunking(n, m, opt=0):
+    """(points per chunk, chunks) of the streamed cross terms of a Sum of RBF parts for n points and m inducing points; opt is the
+    value given to gps_psi_sum_set_chunk (0: automatic)  (csrc/psi_sum.hip: gps_psi_sum_chunking)."""
+    if opt > 0:
+        ch = min(int(opt), 32768)
+    else:
+        ch = min(max((1 << 22) // (128 * -(-m // 128)), 128), 8192)
+    ch = 16 * -(-min(ch, n) // 16)
+    return ch, -(-n // ch)
+
+
 # ---- argument types of every exported function, in the header's order of parameters (tests/test_host_api.py compares the two)
 _int, _dbl, _vp, _str = ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_char_p
 _dp, _ip, _i64p = _c_double_p, _c_int_p, ctypes.POINTER(_i64)
@@ -197,6 +208,7 @@ _SIGNATURES = {
     "gps_fitc_grad": _SPARSE + [_dp, _dp, _int, _ip, _dp, _dp, _dp, _ip],
     "gps_fitc": _SPARSE + [_dp, _i64, _int, _dp, _dp, _dp, _ip],
     "gps_psi_stats": _GPLVM + [_dp, _dp, _dp],
+    "gps_psi_sum_set_chunk": [_vp, _i64],
     "gps_bgplvm": _GPLVM + [_dbl, _dbl, _dp, _i64, _dp, _i64, _int, _dp, _dp, _dp, _ip],
     "gps_bgplvm_grad": _GPLVM + [_dbl, _dbl, _dp, _i64, _dp, _dp, _int, _ip, _dp, _dp, _dp, _dp, _ip],
     "gps_rff_features": [_vp, _rff, _dp, _i64, _dp],

@@ -16,7 +16,7 @@ from ._abi import (GPS_MAX_DIMS, GPS_MAX_NODES, GPS_MAX_STACK,                  
                    K_SQDIST, K_EUCLID, K_RATQUAD, K_LINEAR, K_POLYNOMIAL, K_ADD, K_MUL,
                    K_NKN_LINROW, K_NKN_PRODUCT, K_NKN_ACT, KernNode, LikDesc, RffDesc,
                    RFF_RBF, RFF_LINEAR, RFF_CONSTANT, RFF_EXPLICIT, LIK_MAX_GH, LIK_MULTICLASS,
-                   make_rff, make_lik, make_program, primitive_node, op_node, psi2_chunking,
+                   make_rff, make_lik, make_program, primitive_node, op_node, psi2_chunking, psi_sum_chunking,
                    _SIGNATURES, EXPORTED_SYMBOLS, ALLREDUCE_FN, _c_double_p, _c_int_p, _i64,
                    lib_path, load_library, comm_load, comm_unique_id, comm_version)
 
@@ -713,8 +713,14 @@ class Handle(object):
         _need(Xvar.shape == Xmu.shape, "Xvar must be [N, Q] like Xmu")
         return Z, Xmu, Xvar
 
+    def psi_sum_set_chunk(self, chunk):
+        """gps_psi_sum_set_chunk: points per chunk of the streamed cross terms of a Sum of RBF parts (0: automatic; see
+        psi_sum_chunking)."""
+        self._call("gps_psi_sum_set_chunk", int(chunk))
+
     def psi_stats(self, prog, Z, Xmu, Xvar, want_psi1=False, want_psi2=False, want_psi2n=False):
-        """gps_psi_stats: (Psi1 [N, M], Psi2 [M, M], psi2n [N, M, M]) of one RBF kernel under q(x_n) = N(Xmu_n, diag Xvar_n);
+        """gps_psi_stats: (Psi1 [N, M], Psi2 [M, M], psi2n [N, M, M]) of one RBF kernel, or of a Sum of RBF kernels on pairwise
+        disjoint latent dimensions (cross terms included), under q(x_n) = N(Xmu_n, diag Xvar_n);
         None for what was not asked for."""
         Z, Xmu, Xvar = self._psi_args(Z, Xmu, Xvar)
         (m, q), n = Z.shape, Xmu.shape[0]
@@ -726,7 +732,7 @@ class Handle(object):
         return p1, p2, p2n
 
     def bgplvm(self, prog, Z, Xmu, Xvar, Y, jitter, noise_var, Xnew=None, full_cov=False, want_bound=True):
-        """gps_bgplvm: (bound without the KL term, mean [N*, R], var [N*] or [N*, N*])."""
+        """gps_bgplvm: (bound without the KL term, mean [N*, R], var [N*] or [N*, N*]); prog as for psi_stats."""
         Z, Xmu, Xvar = self._psi_args(Z, Xmu, Xvar)
         Y = _f64(Y)
         (m, q), n = Z.shape, Xmu.shape[0]
@@ -747,7 +753,7 @@ class Handle(object):
 
     def bgplvm_grad(self, prog, Z, Xmu, Xvar, Y, jitter, noise_var):
         """gps_bgplvm_grad: (bound without the KL term, grad_slots, grad_noise, grad_Z [M, Q], grad_Xmu [N, Q], grad_Xvar [N, Q]),
-        gradients with respect to the constrained values."""
+        gradients with respect to the constrained values; the slots are (variance, lengthscales) part by part for a Sum."""
         Z, Xmu, Xvar = self._psi_args(Z, Xmu, Xvar)
         Y = _f64(Y)
         (m, q), n = Z.shape, Xmu.shape[0]

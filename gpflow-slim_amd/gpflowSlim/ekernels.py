@@ -1,10 +1,12 @@
 """Kernels with expectations under a Gaussian q(x) (the reference's ekernels.py).
 
-Implemented: ``RBF`` (ARD or isotropic, over all input dimensions in order) with diagonal covariances given as ``[N, Q]`` --
-ekernels.py:13-47, 120-149 restricted to diagonal ``Xcov``.  The expectations run on the GPU (csrc/psi.hip, gps_psi_stats);
-Psi2 = sum_n eKzxKxz is evaluated without the reference's [N, Q, M, M] temporary (``eKzxKxz_sum``).  Full ``[N, Q, Q]``
-covariances, ``active_dims`` subsets, ``Linear`` / ``Sum`` / ``Product`` kernels with their cross terms and the quadrature
-fall-back, and ``exKxz*`` raise ``NotImplementedError``.
+Implemented: ``RBF`` (ARD or isotropic, over all input dimensions in order) and ``Sum`` of two or more such ``RBF`` kernels on
+pairwise disjoint ``active_dims`` (slices or index lists), with diagonal covariances given as ``[N, Q]`` -- ekernels.py:13-47,
+120-149 and the separate-dimensions branch 224-249, restricted to diagonal ``Xcov``.  The expectations run on the GPU (csrc/psi.hip,
+csrc/psi_sum.hip, gps_psi_stats); Psi2 = sum_n eKzxKxz is evaluated without the reference's [N, Q, M, M] temporary, and for a Sum
+without any [N, M] array (``eKzxKxz_sum``).  Full ``[N, Q, Q]`` covariances, a stand-alone ``RBF`` on an ``active_dims`` subset,
+``Linear`` / ``Product`` kernels, sums with overlapping parts (the quadrature fall-back), and ``exKxz*`` raise
+``NotImplementedError``.
 """
 import numpy as np
 
@@ -62,11 +64,69 @@ class RBF(kernels.RBF):
 def _unsupported(name):
     class _Unsupported(object):
         def __init__(self, *args, **kwargs):
-            raise NotImplementedError("ekernels.%s is not implemented: the kernel expectations cover a single RBF kernel" % name)
+            raise NotImplementedError("ekernels.%s is not implemented: the kernel expectations cover an RBF kernel and a Sum of RBF "
+                                      "kernels on separate dimensions" % name)
     _Unsupported.__name__ = name
     return _Unsupported
 
 
+_SUM_SCOPE = ("ekernels.Sum is implemented for a list of at least two ekernels.RBF kernels that act on pairwise disjoint "
+              "active_dims (no overlapping parts, no other kernel types, no scalars)")
+
+
+def _part_dims(k, d_all=None):
+    """The columns an RBF part reads; without the input width an open-ended slice counts input_dim columns from its start."""
+    if d_all is not None or not isinstance(k.active_dims, slice):
+        return k._dims(False, d_all)
+    a = k.active_dims
+    start, step = a.start or 0, a.step or 1
+    return list(range(start, start + step * k.input_dim, step)) if a.stop is None else list(range(start, a.stop, step))
+
+
+class Sum(kernels.Sum):
+    """ekernels.py:224-249, the branch ``on_separate_dimensions``: Psi1 is the sum of the parts' Psi1, Psi2 the sum of the parts'
+    Psi2 plus the cross terms eKxz_p^T eKxz_p' + eKxz_p'^T eKxz_p (csrc/psi_sum.hip)."""
+
+    def __init__(self, kern_list, name='kernel'):
+        if not isinstance(kern_list, (list, tuple)) or len(kern_list) < 2 or not all(type(k) is RBF for k in kern_list):
+            raise NotImplementedError(_SUM_SCOPE)
+        kernels.Sum.__init__(self, list(kern_list), name=name)
+        self._check_separate(None)
+
+    def _check_separate(self, d_all):
+        seen = set()
+        for k in self.kern_list:
+            dims = _part_dims(k, d_all)
+            if len(dims) != k.input_dim:
+                raise ValueError("active_dims of a part do not match its input_dim")
+            if seen.intersection(dims):
+                raise NotImplementedError(_SUM_SCOPE + ": the parts overlap")
+            seen.update(dims)
+
+    @property
+    def on_separate_dimensions(self):
+        """True by construction (also for slices, which the reference's property does not look into)."""
+        return True
+
+    def _psi_program(self, Xmu):
+        q = np.shape(Xmu)[1]
+        self._check_separate(q)
+        if any(d < 0 or d >= q for k in self.kern_list for d in k._dims(False, q)):
+            raise NotImplementedError(_SUM_SCOPE + ": active_dims outside the latent dimensions")
+        return self._program(q)
+
+    _psi = RBF._psi
+
+    def eKdiag(self, X, Xcov=None):
+        """psi0 per point, [N]: the sum of the parts' variances"""
+        return self.Kdiag(X)
+
+    eKxz = RBF.eKxz
+    eKzxKxz = RBF.eKzxKxz
+    eKzxKxz_sum = RBF.eKzxKxz_sum
+    exKxz = RBF.exKxz
+    exKxz_pairwise = RBF.exKxz_pairwise
+
+
 Linear = _unsupported("Linear")
-Sum = _unsupported("Sum")
 Product = _unsupported("Product")

@@ -5,8 +5,9 @@ sum Kdiag, Kuf and Kuf Kuf^T replaced by the kernel expectations psi0, Psi1, Psi
 the expectations, both factorisations, the prediction and the whole gradient run in gps_bgplvm / gps_bgplvm_grad on the GPU.
 The KL[q(x) || p(x)] term (gplvm.py:150-156) is elementwise over [N, Q] and is evaluated here with its gradient.
 
-Scope: one ``ekernels.RBF`` over all Q latent dimensions and diagonal ``X_var`` [N, Q]; no minibatching, no sharding over
-ranks.  The point-estimate ``GPLVM`` is not implemented.
+Scope: one ``ekernels.RBF`` over all Q latent dimensions, or an ``ekernels.Sum`` of RBF kernels on pairwise disjoint latent
+dimensions (the kernel of the reference's examples/gplvm.py; gradients arrive per part in ``kern.kern_list[i]``), and diagonal
+``X_var`` [N, Q]; no minibatching, no sharding over ranks.  The point-estimate ``GPLVM`` is not implemented.
 """
 import numpy as np
 
@@ -28,9 +29,12 @@ class BayesianGPLVM(GPModel):
         Y = np.ascontiguousarray(Y, dtype=settings.float_type)
         if X_var.ndim == 3:
             raise NotImplementedError("full [N, Q, Q] covariances of q(x) are not implemented: pass the diagonals as [N, Q]")
-        if not isinstance(kern, ekernels.RBF):
-            raise NotImplementedError("BayesianGPLVM is implemented for a single ekernels.RBF kernel")
-        if kern._dims(False, X_mean.shape[1]) != list(range(X_mean.shape[1])):
+        if not isinstance(kern, (ekernels.RBF, ekernels.Sum)):
+            raise NotImplementedError("BayesianGPLVM is implemented for an ekernels.RBF kernel or an ekernels.Sum of such kernels "
+                                      "on separate latent dimensions")
+        if isinstance(kern, ekernels.Sum):
+            kern._psi_program(X_mean)                                 # (overlapping parts, active_dims outside 0 .. Q-1)
+        elif kern._dims(False, X_mean.shape[1]) != list(range(X_mean.shape[1])):
             raise NotImplementedError("the RBF kernel must act on all latent dimensions, in order (no active_dims subset)")
         GPModel.__init__(self, X_mean, Y, kern, likelihood=likelihoods.Gaussian(obs_var), mean_function=Zero())
         del self.X                      # in the GPLVM this is a parameter

@@ -471,9 +471,13 @@ int gps_fitc_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes,
 /* ---- Bayesian GPLVM (models/gplvm.py:54-204) and the kernel expectations behind it (ekernels.py:13-149) ----------------
  * The SGPR collapsed bound with sum Kdiag, Kuf and Kuf Kuf^T replaced by psi0, Psi1, Psi2 = the expectations of the kernel
  * under q(x_n) = N(Xmu_n, diag Xvar_n).  Scope: prog is ONE GPS_K_RBF node (ARD or isotropic) over the latent dimensions
- * 0 .. q-1 in order, and the covariances of q are diagonal, Xvar host [n, q]; anything else (active_dims subsets, Linear / Sum /
- * Product kernels and their cross terms, full [n, q, q] covariances) returns GPS_ERR_UNSUPPORTED.  Not available while the data
- * are sharded over ranks (gps_set_allreduce).  Z host [m, q], Xmu host [n, q], Y host [n, r].
+ * 0 .. q-1 in order, or the program of a Sum of two or more GPS_K_RBF nodes (RBF RBF ADD [RBF ADD ...]) whose active_dims are
+ * pairwise disjoint subsets of 0 .. q-1 -- any order, gaps allowed (ekernels.py:239-249): Psi1 = sum_p T_p and
+ * Psi2 = sum_p Psi2_p + sum_{p < p'} (T_p^T T_p' + T_p'^T T_p), T_p = Psi1 of part p on its own columns; the cross terms stream over
+ * chunks of points through the fp64 GEMM (gps_psi_sum_set_chunk), so that no [n, m] array exists on the device.  The covariances
+ * of q are diagonal, Xvar host [n, q]; anything else (a single RBF on an active_dims subset, overlapping parts, Linear / Product
+ * kernels and their cross terms, full [n, q, q] covariances) returns GPS_ERR_UNSUPPORTED.  Not available while the data are
+ * sharded over ranks (gps_set_allreduce).  Z host [m, q], Xmu host [n, q], Y host [n, r].
  *
  * gps_psi_stats: any of psi1_out host [n, m] (eKxz), psi2_out host [m, m] (sum_n eKzxKxz, O(m^2) device memory whatever n) and
  * psi2n_out host [n, m, m] (eKzxKxz point by point: small sizes) may be NULL.  psi0 = n * variance needs no device.
@@ -481,6 +485,9 @@ int gps_fitc_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes,
 int gps_psi_stats(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
                   const double* Xmu, const double* Xvar, int64_t n, int64_t q,
                   double* psi1_out, double* psi2_out, double* psi2n_out);
+/* Points per chunk of the streamed cross terms of a Sum: 0 (default) = about 4 M / pad(m) points, 128 .. 8192; > 0: this many,
+ * rounded up to a multiple of 16 (at most 32768).  The result depends on the chunk only through the order of the sums.   */
+int gps_psi_sum_set_chunk(gps_handle_t h, int64_t chunk);
 /* bound (optional) receives the bound WITHOUT the KL[q(x) || p(x)] term (gplvm.py:150-156: elementwise over [n, q], the
  * caller's).  If n_new > 0: prediction at Xnew host [n_new, q] as gps_sgpr (gplvm.py:169-204).  info > 0: a factorisation
  * met a non-positive pivot.                                                                                             */
@@ -489,8 +496,10 @@ int gps_bgplvm(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const d
                const double* Y, int64_t r, const double* Xnew, int64_t n_new, int full_cov,
                double* bound, double* mean_out, double* var_out, int* info);
 /* The same bound and its gradient with respect to the constrained values: grad_slots (slot layout of gps_gpr_lml_grad: variance,
- * then q lengthscale slots even for an isotropic kernel), grad_noise, grad_Z host [m, q], grad_Xmu and grad_Xvar host [n, q]
- * (the last three optional).  Reverse mode at the matrix level; Psi2's vector-Jacobian product recomputes psi2n in two passes. */
+ * then q lengthscale slots even for an isotropic kernel; for a Sum, variance and n_dims lengthscale slots part by part),
+ * grad_noise, grad_Z host [m, q], grad_Xmu and grad_Xvar host [n, q] (the last three optional; columns in no part of a Sum get
+ * zero).  Reverse mode at the matrix level; Psi2's vector-Jacobian product recomputes psi2n in two passes; for a Sum the cotangent
+ * of T_p, Y W^T + (Psi1 - T_p) (Psi2_bar + Psi2_bar^T), is dense and is formed chunk by chunk on the fp64 GEMM. */
 int gps_bgplvm_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
                     const double* Xmu, const double* Xvar, int64_t n, int64_t q, double jitter, double noise_var,
                     const double* Y, int64_t r, double* bound, double* grad_slots, int n_slots_cap, int* n_slots_out,
