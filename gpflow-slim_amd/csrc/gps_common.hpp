@@ -211,7 +211,7 @@ struct gps_handle_s {
   int predict_inv_blocks = 1;   // option "predict_inverse_blocks"
   DevBuf dMean{bufs};     // [n_new, r]
   DevBuf dVar{bufs};      // [n_new] or [nspad, nspad]
-  DevBuf dKdiag{bufs};    // [n] per-point Kdiag of a program with Linear / Polynomial (gps_launch_kdiag_vec)
+  DevBuf dKdiag{bufs};    // [n] per-point Kdiag of a program with Linear / Polynomial / ArcCosine (gps_launch_kdiag_vec)
   // ---- block-column distributed factorisation (gps_dist_*) ----
   struct Dist {
     int P = 0, rank = 0;
@@ -547,7 +547,7 @@ int gps_launch_kmat_block(gps_handle_t h, const gps_kern_node_t* prog, int n_nod
                           i64 n, i64 d_all, i64 npad, double diag_add, double* dKb, i64 ldk, i64 r0,
                           i64 nrows, i64 c0, i64 ncols, int prep);
 int gps_launch_kdiag(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double* kdiag_const);
-// Kdiag of a program that contains Linear / Polynomial depends on the point: gps_launch_kdiag refuses those, and
+// Kdiag of a program that contains Linear / Polynomial / ArcCosine depends on the point: gps_launch_kdiag refuses those, and
 // gps_launch_kdiag_vec writes Kdiag(X)[i] for the n resident points dX [n, d_all] to d_out [n] (any program; uses dFeat).
 // sum_out (optional): sum_i Kdiag_i on the host -- that one synchronises.
 bool gps_kdiag_is_const(const gps_kern_node_t* prog, int n_nodes);
@@ -585,7 +585,7 @@ int gps_launch_kmat_input_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n
                               const double* dXc, i64 nc, i64 d_all, const double* Wd, i64 ldw, double factor,
                               double* grad_X_host);
 int gps_kdiag_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, double kbar, double* grad_slots_host);
-// ... and of a program with Linear, whose Kdiag depends on the point: X host [n, d_all], one kbar per point (host), added to the slots
+// ... and of a program with Linear or ArcCosine, whose Kdiag depends on the point: X host [n, d_all], one kbar per point (host), added to the slots
 int gps_kdiag_vjp_points(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, const double* X, i64 n, const double* kbar,
                          double* grad_slots_host);
 int gps_launch_kmat_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dXr, i64 nr, const double* dXc,

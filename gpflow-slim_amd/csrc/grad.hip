@@ -12,7 +12,8 @@
 // program order: [variance] then, stationary kernels: one slot per active dim (d k / d lengthscale_d;
 // an isotropic kernel's gradient is the sum of its slots), Periodic: [lengthscale, period],
 // White / Constant: nothing more, RatQuad: the stationary slots and then [alpha]; Linear: one slot per active dim
-// (d k / d v_d; no variance slot), Polynomial: the same and then [offset].  The noise variance has its own output.
+// (d k / d v_d; no variance slot), Polynomial: the same and then [offset]; Cosine: [variance, l_0 .., w_0 ..]; ArcCosine:
+// [variance, bias variance, w_0 ..].  The noise variance has its own output.
 #include "grad_common.hpp"
 
 #define GT_R 64            // tile rows
@@ -35,7 +36,7 @@ struct GArgs {
   int cyc_P, cyc_rank; i64 cyc_nb; int kinv_t;
 };
 
-// EXT: the instance that also knows RatQuad, Linear and Polynomial.  Programs without them run the other one, whose code --
+// EXT: the instance that also knows RatQuad, Linear, Polynomial, Cosine and ArcCosine.  Programs without them run the other one, whose code --
 // registers, no scratch -- is what it was before those primitives existed (with them in one kernel the compiler spilled).
 template <bool EXT>
 __global__ __launch_bounds__(256) void grad_kernel(GArgs a, GProg P) {
@@ -95,7 +96,7 @@ __global__ __launch_bounds__(256) void grad_kernel(GArgs a, GProg P) {
         }
       } else {
         __syncthreads();
-        const int nfd = (node.op == GPS_K_PERIODIC) ? 2 * node.ndims : node.ndims;   // cos/sin or scaled x
+        const int nfd = (node.op == GPS_K_PERIODIC) ? 2 * node.ndims : ((EXT && node.op == GPS_K_COSINE) ? 2 : node.ndims);   // cos/sin or scaled x
         for (int idx = tid; idx < nfd * GT_R; idx += 256) {
           const int f = idx >> 6, pp = idx & 63;
           Fr_s[f * GT_R + pp] = a.Ft[(i64)(node.f0 + f) * a.ldf + gi0 + pp];
@@ -108,7 +109,31 @@ __global__ __launch_bounds__(256) void grad_kernel(GArgs a, GProg P) {
         double acc8[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc8[e] = 0.0;
-        if (node.op == GPS_K_PERIODIC || (EXT && grad_is_dot(node.op))) {
+        if (EXT && node.op == GPS_K_COSINE) {            // rr keeps sin(a_i - a_j)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const int ri = ty * 4 + (e >> 1), cj = tx * 2 + (e & 1);
+            const double ci = Fr_s[ri], si = Fr_s[GT_R + ri], cj_ = Fc_s[cj], sj = Fc_s[GT_C + cj];
+            val[e] = node.variance * fma(si, sj, ci * cj_); rr[e] = si * cj_ - ci * sj;
+          }
+        } else if (EXT && node.op == GPS_K_ARCCOSINE) {   // rr keeps P; the derivatives are pass 2's
+          double ni[4] = {0.0, 0.0, 0.0, 0.0}, nj[2] = {0.0, 0.0};
+          for (int f = 0; f < nfd; ++f) {
+            double fr[4], fc[2];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { fr[q] = Fr_s[f * GT_R + ty * 4 + q]; ni[q] = fma(fr[q], fr[q], ni[q]); }
+#pragma unroll
+            for (int q = 0; q < 2; ++q) { fc[q] = Fc_s[f * GT_C + tx * 2 + q]; nj[q] = fma(fc[q], fc[q], nj[q]); }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc8[e] = fma(fr[e >> 1], fc[e & 1], acc8[e]);
+          }
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const i64 i = gi0 + ty * 4 + (e >> 1), j = gj0 + tx * 2 + (e & 1);
+            rr[e] = acc8[e] + node.ls0;
+            val[e] = grad_arccosine(node.variance, (int)node.period, rr[e], ni[e >> 1] + node.ls0, nj[e & 1] + node.ls0, i == j).k;
+          }
+        } else if (node.op == GPS_K_PERIODIC || (EXT && grad_is_dot(node.op))) {
           for (int f = 0; f < nfd; ++f) {
             double fr[4], fc[2];
 #pragma unroll
@@ -208,6 +233,72 @@ __global__ __launch_bounds__(256) void grad_kernel(GArgs a, GProg P) {
         if (lane == 0) acc_s[wave][node.slot0] += s;
       }
       if (node.op == GPS_K_WHITE || node.op == GPS_K_CONSTANT) continue;
+      if (EXT && (node.op == GPS_K_COSINE || node.op == GPS_K_ARCCOSINE)) {
+        const bool cosine = node.op == GPS_K_COSINE;
+        const int fs = cosine ? 2 : 0, nfd = cosine ? 2 * node.ndims : node.ndims;       // Cosine: the F and G rows
+        __syncthreads();
+        for (int idx = tid; idx < nfd * GT_R; idx += 256) {
+          const int f = idx >> 6, pp = idx & 63;
+          Fr_s[f * GT_R + pp] = a.Ft[(i64)(node.f0 + fs + f) * a.ldf + gi0 + pp];
+        }
+        for (int idx = tid; idx < nfd * GT_C; idx += 256) {
+          const int f = idx >> 5, pp = idx & 31;
+          Fc_s[f * GT_C + pp] = a.Ft[(i64)(node.f0 + fs + f) * a.ldf + gj0 + pp];
+        }
+        __syncthreads();
+        if (cosine) {
+          // Q_e = c W adj * variance sin(a_i - a_j) ; d k / d l_d = Q (G_id - G_jd) / l_d ; d k / d w_d = -Q (F_id - F_jd)
+          double Q[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) Q[e] = f8[e] * node.variance * r2[p][e];
+          for (int d = 0; d < 2 * node.ndims; ++d) {
+            double fr[4], fc[2];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) fr[q] = Fr_s[d * GT_R + ty * 4 + q];
+#pragma unroll
+            for (int q = 0; q < 2; ++q) fc[q] = Fc_s[d * GT_C + tx * 2 + q];
+            double s = 0.0;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s += Q[e] * (fr[e >> 1] - fc[e & 1]);
+            s = grad_wave_sum(s);
+            // rows 0 .. ndims - 1 are F (the weights' slots, after the lengthscales'), the others G (the host divides by l_d)
+            if (lane == 0) acc_s[wave][node.slot0 + 1 + (d < node.ndims ? node.ndims + d : d - node.ndims)] += (d < node.ndims) ? -s : s;
+          }
+          continue;
+        }
+        // ArcCosine: d k / d b = D_P + D_ni + D_nj ; d k / d w_d = (D_P H_id H_jd + D_ni H_id^2 + D_nj H_jd^2) / w_d (the host divides)
+        double ni[4] = {0.0, 0.0, 0.0, 0.0}, nj[2] = {0.0, 0.0};
+        for (int f = 0; f < nfd; ++f) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) { const double v = Fr_s[f * GT_R + ty * 4 + q]; ni[q] = fma(v, v, ni[q]); }
+#pragma unroll
+          for (int q = 0; q < 2; ++q) { const double v = Fc_s[f * GT_C + tx * 2 + q]; nj[q] = fma(v, v, nj[q]); }
+        }
+        double DP[8], Di[8], Dj[8];
+        double sb = 0.0;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const i64 i = gi0 + ty * 4 + (e >> 1), j = gj0 + tx * 2 + (e & 1);
+          const GradArc g = grad_arccosine(node.variance, (int)node.period, r2[p][e], ni[e >> 1] + node.ls0, nj[e & 1] + node.ls0, i == j);
+          DP[e] = f8[e] * g.dP; Di[e] = f8[e] * g.dni; Dj[e] = f8[e] * g.dnj;
+          sb += DP[e] + Di[e] + Dj[e];
+        }
+        sb = grad_wave_sum(sb);
+        if (lane == 0) acc_s[wave][node.slot0 + 1] += sb;
+        for (int d = 0; d < node.ndims; ++d) {
+          double fr[4], fc[2];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) fr[q] = Fr_s[d * GT_R + ty * 4 + q];
+#pragma unroll
+          for (int q = 0; q < 2; ++q) fc[q] = Fc_s[d * GT_C + tx * 2 + q];
+          double s = 0.0;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) s += DP[e] * (fr[e >> 1] * fc[e & 1]) + Di[e] * (fr[e >> 1] * fr[e >> 1]) + Dj[e] * (fc[e & 1] * fc[e & 1]);
+          s = grad_wave_sum(s);
+          if (lane == 0) acc_s[wave][node.slot0 + 2 + d] += s;
+        }
+        continue;
+      }
       if (node.op == GPS_K_PERIODIC) {
         const double l = node.ls0, l2 = l * l;
         // d k / d l = k S / l^3
@@ -365,7 +456,8 @@ static int grad_run(gps_handle_t h, const GradPost& post, i64 n, i64 npad, const
     LaunchScope ls(h, KC_REDUCE, 0.5 * (double)npad * cols * (60.0 + 4.0 * nfeat), 4.0 * (double)npad * cols);
     bool ext = false;
     for (int i = 0; i < P.n_nodes; ++i)
-      if (P.nodes[i].op == GPS_K_RATQUAD || P.nodes[i].op == GPS_K_LINEAR || P.nodes[i].op == GPS_K_POLYNOMIAL) ext = true;
+      if (P.nodes[i].op == GPS_K_RATQUAD || P.nodes[i].op == GPS_K_LINEAR || P.nodes[i].op == GPS_K_POLYNOMIAL ||
+          P.nodes[i].op == GPS_K_COSINE || P.nodes[i].op == GPS_K_ARCCOSINE) ext = true;
     if (ext) hipLaunchKernelGGL(grad_kernel<true>, dim3(nblocks), dim3(256), 0, h->stream, a, P);
     else hipLaunchKernelGGL(grad_kernel<false>, dim3(nblocks), dim3(256), 0, h->stream, a, P);
     GPS_HIP(h, hipGetLastError());

@@ -14,7 +14,10 @@
 #define GRAD_MAXF 64       // feature rows of one primitive: periodic = 3 per dim (<= 21 dims)
 
 struct GradFeat { int dim; int kind; double param; };   // 0: x/param ; 1: cos(2pi x/param) ; 2: sin ; 3: 2pi x/param ; 4: x*param
-// variance: Polynomial: the offset (Linear: 1) ; period: RatQuad: alpha, Polynomial: degree
+// 5 / 6: cos / sin of a = sum_q x[tab[dim + q].dim] * tab[dim + q].param over the (int)param table entries from index `dim` on
+// (Cosine: its kind-4 rows G_d = x_d w_d / l_d)
+// variance: Polynomial: the offset (Linear: 1) ; period: RatQuad: alpha, Polynomial: degree, ArcCosine: order ; ls0: Periodic:
+// the lengthscale, ArcCosine: the bias variance
 struct GradNode { int op; int prim; int f0; int nf; int slot0; int ndims; double variance; double ls0; double period; };
 
 // ---- feature prep: Ft[f][i] = feature f of point i (zero in the padding) ------------------------------------------------------
@@ -30,12 +33,18 @@ __global__ __launch_bounds__(256) void grad_prep_kernel(const double* __restrict
     double v = 0.0;
     if (i < n) {
       const GradFeat pf = tab.f[f];
-      const double xv = X[i * d_all + pf.dim];
-      if (pf.kind == 0) v = xv / pf.param;
-      else if (pf.kind == 4) v = xv * pf.param;
-      else {
-        const double ang = 2.0 * M_PI * xv / pf.param;
-        v = (pf.kind == 1) ? cos(ang) : (pf.kind == 2 ? sin(ang) : ang);
+      if (pf.kind >= 5) {
+        double ang = 0.0;
+        for (int q = 0; q < (int)pf.param; ++q) { const GradFeat cf = tab.f[pf.dim + q]; ang = fma(X[i * d_all + cf.dim], cf.param, ang); }
+        v = (pf.kind == 5) ? cos(ang) : sin(ang);
+      } else {
+        const double xv = X[i * d_all + pf.dim];
+        if (pf.kind == 0) v = xv / pf.param;
+        else if (pf.kind == 4) v = xv * pf.param;
+        else {
+          const double ang = 2.0 * M_PI * xv / pf.param;
+          v = (pf.kind == 1) ? cos(ang) : (pf.kind == 2 ? sin(ang) : ang);
+        }
       }
     }
     Ft[(i64)f * ldf + i] = v;
@@ -151,6 +160,41 @@ __device__ __forceinline__ double grad_dot_dlin(int op, double lin, double offse
   return op == GPS_K_LINEAR ? 1.0 : degree * grad_powi(lin + offset, (int)degree - 1);
 }
 
+// Cosine (kernels.py:633-646): k = variance cos(a_i - a_j) from the feature rows [cos a, sin a, F_d = x_d / l_d, G_d = x_d w_d / l_d]:
+//   d k / d w_d = -variance sin(a_i - a_j) (F_id - F_jd) ;  d k / d l_d = variance sin(a_i - a_j) (G_id - G_jd) / l_d (the host
+//   divides) ;  d k / d x_id = -variance sin(a_i - a_j) w_d / l_d.   sin(a_i - a_j) = sin a_i cos a_j - cos a_i sin a_j.
+//
+// ArcCosine (kernels.py:722-758) from P = sum_d H_id H_jd + b, n_i = sum_d H_id^2 + b (H_d = x_d sqrt(w_d)):
+//   u = P / (sqrt(n_i) sqrt(n_j)),  c = 1e-15 + kappa u,  kappa = 1 - 2e-15,  theta = acos(c),
+//   k = variance / pi J(theta) (n_i n_j)^(order / 2) ;  with A = variance / pi kappa (d J / d c) (n_i n_j)^(order / 2):
+//   d k / d P = A / (sqrt(n_i) sqrt(n_j)),  d k / d n_i = (order k - A u) / (2 n_i),  d k / d n_j likewise;
+//   d J_0 / d c = 1 / sin(theta),  d J_1 / d c = J_0,  d J_2 / d c = 4 J_1.
+// diag: the entry is one point against itself (i == j of one point set).  There cos(theta) does not depend on anything, and
+// for order 0 -- whose d J / d c = 1 / sin(theta) is 2e7 at the jitter's theta -- the derivative through c is set to exactly 0
+// (autodiff of the reference's expression returns rounding noise times 2e7 there).
+struct GradArc { double k, dP, dni, dnj; };
+__device__ __forceinline__ GradArc grad_arccosine(double variance, int order, double P, double ni, double nj, bool diag) {
+  const double kappa = 1.0 - 2.0 * 1e-15;
+  const double sij = sqrt(ni) * sqrt(nj);
+  const double u = diag ? 1.0 : P / sij;                           // (exactly 1 there: gps_arccosine of kmat.hip has the reason)
+  double c = 1e-15 + kappa * u;
+  c = (c > 1.0) ? 1.0 : c;
+  const double theta = diag ? 4.4721359549995794e-08 : acos(c), pt = M_PI - theta;     // (GPS_ARCCOS_THETA0 of kmat.hip)
+  const double st = diag ? theta : sqrt((1.0 - c) * (1.0 + c)), ct = c;    // sin(theta), cos(theta): as the kernel-matrix build has them
+  const double J1 = st + pt * ct;
+  double J, dJ, scale;
+  if (order == 0) { J = pt; dJ = diag ? 0.0 : 1.0 / st; scale = 1.0; }
+  else if (order == 1) { J = J1; dJ = pt; scale = sij; }
+  else { J = 3.0 * st * ct + pt * (1.0 + 2.0 * (ct * ct)); dJ = 4.0 * J1; scale = sij * sij; }
+  GradArc r;
+  r.k = variance * (1.0 / M_PI) * J * scale;
+  const double A = variance * (1.0 / M_PI) * kappa * dJ * scale;
+  r.dP = A / sij;
+  const double h = 0.5 * ((double)order * r.k - A * u);
+  r.dni = h / ni; r.dnj = h / nj;
+  return r;
+}
+
 // plain (Sum / Product) program over the primitive values pv: d out / d prim_p by forward mode
 template <int MAXP, class Prog>
 __device__ __forceinline__ double grad_prog_tangent(const Prog& P, const double (&pv)[MAXP], int p) {
@@ -182,7 +226,7 @@ __device__ __forceinline__ double grad_prog_tangent(const Prog& P, const double 
 static inline bool grad_is_prim(int op) {
   return op == GPS_K_RBF || op == GPS_K_MATERN12 || op == GPS_K_MATERN32 || op == GPS_K_MATERN52 || op == GPS_K_PERIODIC ||
          op == GPS_K_WHITE || op == GPS_K_CONSTANT || op == GPS_K_EXPONENTIAL || op == GPS_K_RATQUAD || op == GPS_K_LINEAR ||
-         op == GPS_K_POLYNOMIAL;
+         op == GPS_K_POLYNOMIAL || op == GPS_K_COSINE || op == GPS_K_ARCCOSINE;
 }
 
 // what the analysis hands back beside the device nodes: the feature table, the lengthscale (Linear / Polynomial: the
@@ -196,7 +240,8 @@ struct GradPrims {
 // nodes [0, n_nodes) of `prog` -- primitives and, unless the program feeds a network (nkn), Sum / Product -- into `nodes`:
 // stack discipline, parameter ranges, feature rows and slots ([variance] then one slot per active dim, Periodic:
 // [lengthscale, period], White / Constant: nothing more, RatQuad: [alpha] after the dims; Linear: one slot per active dim and
-// no variance slot, Polynomial: the same and then [offset]), at most max_prims primitives (too_many: the kernel's own message)
+// no variance slot, Polynomial: the same and then [offset]; Cosine: [variance, l_0 .., w_0 ..]; ArcCosine: [variance, bias
+// variance, w_0 ..]), at most max_prims primitives (too_many: the kernel's own message)
 static int grad_analyse_prims(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, int max_prims, const char* too_many,
                               bool nkn, GradNode* nodes, GradPrims& R) {
   if (n_nodes <= 0 || n_nodes > GRAD_MAX_NODES) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: program too long");
@@ -233,6 +278,31 @@ static int grad_analyse_prims(gps_handle_t h, const gps_kern_node_t* prog, int n
       for (int d = 0; d < nd.n_dims; ++d) feats.push_back({nd.active_dims[d], 3, nd.period});
       g.nf = 3 * nd.n_dims; g.ls0 = nd.lengthscales[0];
       R.n_slots += 3; ls_of_slot.push_back(0.0); ls_of_slot.push_back(0.0);
+    } else if (nd.op == GPS_K_COSINE) {
+      // rows [cos a, sin a, F_0 .., G_0 ..]; the G rows are also the coefficients of a
+      if (nd.n_dims > GPS_MAX_DIMS / 2) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: Cosine takes at most 16 active dims");
+      feats.push_back({g.f0 + 2 + nd.n_dims, 5, (double)nd.n_dims}); feats.push_back({g.f0 + 2 + nd.n_dims, 6, (double)nd.n_dims});
+      for (int d = 0; d < nd.n_dims; ++d) {
+        if (!(nd.lengthscales[d] > 0.0)) return gps_fail(h, GPS_ERR_ARG, "gradient: lengthscale must be positive");
+        feats.push_back({nd.active_dims[d], 0, nd.lengthscales[d]}); ls_of_slot.push_back(nd.lengthscales[d]);
+      }
+      for (int d = 0; d < nd.n_dims; ++d) {
+        feats.push_back({nd.active_dims[d], 4, nd.lengthscales[nd.n_dims + d] / nd.lengthscales[d]}); ls_of_slot.push_back(0.0);
+      }
+      g.nf = 2 + 2 * nd.n_dims;
+      R.n_slots += 1 + 2 * nd.n_dims;
+    } else if (nd.op == GPS_K_ARCCOSINE) {
+      if (nd.n_dims > GPS_MAX_DIMS - 1) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: ArcCosine takes at most 31 active dims");
+      if (nd.period != 0.0 && nd.period != 1.0 && nd.period != 2.0) return gps_fail(h, GPS_ERR_ARG, "gradient: ArcCosine order must be 0, 1 or 2");
+      if (!(nd.lengthscales[nd.n_dims] > 0.0)) return gps_fail(h, GPS_ERR_ARG, "gradient: ArcCosine bias variance must be positive");
+      g.ls0 = nd.lengthscales[nd.n_dims];
+      ls_of_slot.push_back(0.0);                           // the bias variance
+      for (int d = 0; d < nd.n_dims; ++d) {
+        if (!(nd.lengthscales[d] > 0.0)) return gps_fail(h, GPS_ERR_ARG, "gradient: ArcCosine weight variance must be positive");
+        feats.push_back({nd.active_dims[d], 4, sqrt(nd.lengthscales[d])}); ls_of_slot.push_back(nd.lengthscales[d]);
+      }
+      g.nf = nd.n_dims;
+      R.n_slots += 2 + nd.n_dims;
     } else if (dot) {
       if (nd.op == GPS_K_LINEAR && nd.variance != 1.0) return gps_fail(h, GPS_ERR_ARG, "gradient: the variance field of Linear must be 1");
       if (nd.op == GPS_K_POLYNOMIAL && (!(nd.period >= 1.0) || nd.period != floor(nd.period) || nd.period > 64.0))

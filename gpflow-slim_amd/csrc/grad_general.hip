@@ -13,7 +13,7 @@
 // added on the host (bit-reproducible, no floating-point atomics).
 //
 // Slot layout (host and device agree on it): primitives first, as in grad.hip ([variance], then one slot per active
-// dim, or [lengthscale, period] for Periodic; RatQuad, Linear, Polynomial: see grad.hip); then, for every Linear layer in network order and every output o:
+// dim, or [lengthscale, period] for Periodic; RatQuad, Linear, Polynomial, Cosine, ArcCosine: see grad.hip); then, for every Linear layer in network order and every output o:
 // [W[o][0 .. in-1], bias[o]].
 #include "grad_common.hpp"
 
@@ -59,7 +59,30 @@ __device__ __forceinline__ void gg_stage(const GGArgs& a, int f0, int nf, i64 gi
   __syncthreads();
 }
 
-// value and (squared distance | periodic sum) of one primitive at the thread's four entries
+// feature rows that the VALUE of a primitive needs, from node.f0 on
+__device__ __forceinline__ int gg_value_rows(const GradNode& node) {
+  return node.op == GPS_K_PERIODIC ? 2 * node.ndims : (node.op == GPS_K_COSINE ? 2 : node.ndims);
+}
+
+// ArcCosine at the thread's four entries from the staged rows H_d: value and the three partial derivatives (grad_arccosine)
+__device__ __forceinline__ void gg_arc(const GradNode& node, const double* Fr_s, const double* Fc_s, int ty, int tx, i64 gi0, i64 gj0,
+                                       bool same_points, GradArc (&g)[GG_E]) {
+  double acc[GG_E] = {0.0, 0.0, 0.0, 0.0}, ni[2] = {0.0, 0.0}, nj[2] = {0.0, 0.0};
+  for (int f = 0; f < node.ndims; ++f) {
+    const double r0 = Fr_s[f * GG_T + ty * 2], r1 = Fr_s[f * GG_T + ty * 2 + 1];
+    const double c0 = Fc_s[f * GG_T + tx * 2], c1 = Fc_s[f * GG_T + tx * 2 + 1];
+    acc[0] = fma(r0, c0, acc[0]); acc[1] = fma(r0, c1, acc[1]); acc[2] = fma(r1, c0, acc[2]); acc[3] = fma(r1, c1, acc[3]);
+    ni[0] = fma(r0, r0, ni[0]); ni[1] = fma(r1, r1, ni[1]); nj[0] = fma(c0, c0, nj[0]); nj[1] = fma(c1, c1, nj[1]);
+  }
+#pragma unroll
+  for (int e = 0; e < GG_E; ++e) {
+    const i64 i = gi0 + ty * 2 + (e >> 1), j = gj0 + tx * 2 + (e & 1);
+    g[e] = grad_arccosine(node.variance, (int)node.period, acc[e] + node.ls0, ni[e >> 1] + node.ls0, nj[e & 1] + node.ls0, same_points && i == j);
+  }
+}
+
+// value and (squared distance | periodic sum | Linear / Polynomial: lin | Cosine: sin(a_i - a_j)) of one primitive at the thread's
+// four entries
 __device__ __forceinline__ void gg_prim(const GradNode& node, const double* Fr_s, const double* Fc_s, int ty, int tx, i64 gi0,
                                         i64 gj0, bool same_points, double (&val)[GG_E], double (&rr)[GG_E]) {
   if (node.op == GPS_K_CONSTANT) {
@@ -73,6 +96,22 @@ __device__ __forceinline__ void gg_prim(const GradNode& node, const double* Fr_s
       const i64 i = gi0 + ty * 2 + (e >> 1), j = gj0 + tx * 2 + (e & 1);
       val[e] = (same_points && i == j) ? node.variance : 0.0; rr[e] = 0.0;
     }
+    return;
+  }
+  if (node.op == GPS_K_COSINE) {                   // rows 0, 1: cos a, sin a
+#pragma unroll
+    for (int e = 0; e < GG_E; ++e) {
+      const int ri = ty * 2 + (e >> 1), cj = tx * 2 + (e & 1);
+      const double ci = Fr_s[ri], si = Fr_s[GG_T + ri], cj_ = Fc_s[cj], sj = Fc_s[GG_T + cj];
+      val[e] = node.variance * fma(si, sj, ci * cj_); rr[e] = si * cj_ - ci * sj;
+    }
+    return;
+  }
+  if (node.op == GPS_K_ARCCOSINE) {
+    GradArc g[GG_E];
+    gg_arc(node, Fr_s, Fc_s, ty, tx, gi0, gj0, same_points, g);
+#pragma unroll
+    for (int e = 0; e < GG_E; ++e) { val[e] = g[e].k; rr[e] = 0.0; }
     return;
   }
   double acc[GG_E];
@@ -116,7 +155,7 @@ __device__ __forceinline__ void gg_values(const GGArgs& a, const GGProg& P, i64 
   for (int nd = 0; nd < P.n_nodes; ++nd) {
     const GradNode node = P.nodes[nd];
     if (node.prim < 0) continue;
-    if (node.nf > 0) gg_stage(a, node.f0, (node.op == GPS_K_PERIODIC) ? 2 * node.ndims : node.ndims, gi0, gj0, Fr_s, Fc_s, tid);
+    if (node.nf > 0) gg_stage(a, node.f0, gg_value_rows(node), gi0, gj0, Fr_s, Fc_s, tid);
     double val[GG_E], rr[GG_E];
     gg_prim(node, Fr_s, Fc_s, ty, tx, gi0, gj0, same_points, val, rr);
 #pragma unroll
@@ -304,6 +343,44 @@ __global__ __launch_bounds__(256) void gg_kernel(GGArgs a, GGProg P) {
         if (lane == 0) acc_s[wave][node.slot0] += s;
       }
       if (node.op == GPS_K_WHITE || node.op == GPS_K_CONSTANT) continue;
+      if (node.op == GPS_K_COSINE) {
+        // Q_e = f variance sin(a_i - a_j) ; d k / d l_d = Q (G_id - G_jd) / l_d (the host divides) ; d k / d w_d = -Q (F_id - F_jd)
+        gg_stage(a, node.f0, node.nf, gi0, gj0, Fr_s, Fc_s, tid);
+        double val[GG_E], sn[GG_E], Q[GG_E];
+        gg_prim(node, Fr_s, Fc_s, ty, tx, gi0, gj0, same_points, val, sn);
+#pragma unroll
+        for (int e = 0; e < GG_E; ++e) Q[e] = f4[e] * node.variance * sn[e];
+        for (int d = 0; d < 2 * node.ndims; ++d) {           // rows 2 ..: F_0 .., then G_0 ..
+          const double r0 = Fr_s[(2 + d) * GG_T + ty * 2], r1 = Fr_s[(2 + d) * GG_T + ty * 2 + 1];
+          const double c0 = Fc_s[(2 + d) * GG_T + tx * 2], c1 = Fc_s[(2 + d) * GG_T + tx * 2 + 1];
+          double s = Q[0] * (r0 - c0) + Q[1] * (r0 - c1) + Q[2] * (r1 - c0) + Q[3] * (r1 - c1);
+          s = grad_wave_sum(s);
+          if (lane == 0) acc_s[wave][node.slot0 + 1 + (d < node.ndims ? node.ndims + d : d - node.ndims)] += (d < node.ndims) ? -s : s;
+        }
+        continue;
+      }
+      if (node.op == GPS_K_ARCCOSINE) {
+        // d k / d b = D_P + D_ni + D_nj ; d k / d w_d = (D_P H_id H_jd + D_ni H_id^2 + D_nj H_jd^2) / w_d (the host divides)
+        gg_stage(a, node.f0, node.ndims, gi0, gj0, Fr_s, Fc_s, tid);
+        GradArc g[GG_E];
+        gg_arc(node, Fr_s, Fc_s, ty, tx, gi0, gj0, same_points, g);
+        double sb = 0.0;
+#pragma unroll
+        for (int e = 0; e < GG_E; ++e) sb += f4[e] * (g[e].dP + g[e].dni + g[e].dnj);
+        sb = grad_wave_sum(sb);
+        if (lane == 0) acc_s[wave][node.slot0 + 1] += sb;
+        for (int d = 0; d < node.ndims; ++d) {
+          const double r0 = Fr_s[d * GG_T + ty * 2], r1 = Fr_s[d * GG_T + ty * 2 + 1];
+          const double c0 = Fc_s[d * GG_T + tx * 2], c1 = Fc_s[d * GG_T + tx * 2 + 1];
+          double s = f4[0] * (g[0].dP * (r0 * c0) + g[0].dni * (r0 * r0) + g[0].dnj * (c0 * c0)) +
+                     f4[1] * (g[1].dP * (r0 * c1) + g[1].dni * (r0 * r0) + g[1].dnj * (c1 * c1)) +
+                     f4[2] * (g[2].dP * (r1 * c0) + g[2].dni * (r1 * r1) + g[2].dnj * (c0 * c0)) +
+                     f4[3] * (g[3].dP * (r1 * c1) + g[3].dni * (r1 * r1) + g[3].dnj * (c1 * c1));
+          s = grad_wave_sum(s);
+          if (lane == 0) acc_s[wave][node.slot0 + 2 + d] += s;
+        }
+        continue;
+      }
       if (node.op == GPS_K_PERIODIC) {
         gg_stage(a, node.f0, 3 * node.ndims, gi0, gj0, Fr_s, Fc_s, tid);
         double val[GG_E], S4[GG_E];
@@ -364,6 +441,8 @@ __global__ __launch_bounds__(256) void gg_kernel(GGArgs a, GGProg P) {
 // through the program as gg_kernel; then, per primitive, the chain through its argument:
 //   stationary  r2 = sum_d (F_id - F_jd)^2, F = x / l :  d k / d x_id = (d k / d r2) 2 (F_id - F_jd) / l_d
 //   Periodic    S = sum_d sin^2((a_id - a_jd) / 2), a = 2 pi x / p :  d k / d x_id = -k / (2 l^2) (1/2) sin(a_id - a_jd) 2 pi / p
+//   Cosine      d k / d x_id = -variance sin(a_i - a_j) w_d / l_d
+//   ArcCosine   d k / d x_id = (d k / d P) H_jd sqrt(w_d) + (d k / d n_i) 2 H_id sqrt(w_d),  H = x sqrt(w)
 // Workgroup (ti, slice) owns 32 rows and a slice of the column tiles; row sums over the 16 threads of a patch row by
 // shuffles, over the tiles in LDS; the slices' partial sums [slices][rows][d_all] are added in order on the host.
 struct GIArgs { const GradFeat* feats; double* part; int d_all; int slices; i64 rows_pad; };
@@ -428,7 +507,41 @@ __global__ __launch_bounds__(256) void gg_input_kernel(GGArgs a, GGProg P, GIArg
         }
         continue;
       }
+      if (node.op == GPS_K_COSINE) {
+        gg_stage(a, node.f0, 2, gi0, gj0, Fr_s, Fc_s, tid);
+        double val[GG_E], sn[GG_E];
+        gg_prim(node, Fr_s, Fc_s, ty, tx, gi0, gj0, same_points, val, sn);
+        // the sum over the columns is the same for every dim; the coefficient w_d / l_d is the G row's table entry
+        double s0 = -node.variance * (f4[0] * sn[0] + f4[1] * sn[1]);
+        double s1 = -node.variance * (f4[2] * sn[2] + f4[3] * sn[3]);
+#pragma unroll
+        for (int off = 1; off < 16; off <<= 1) { s0 += __shfl_xor(s0, off, 64); s1 += __shfl_xor(s1, off, 64); }
+        if (tx == 0) {
+          for (int d = 0; d < node.ndims; ++d) {
+            const GradFeat ft = gi.feats[node.f0 + 2 + node.ndims + d];
+            rowacc[ty * 2][ft.dim] += s0 * ft.param; rowacc[ty * 2 + 1][ft.dim] += s1 * ft.param;
+          }
+        }
+        continue;
+      }
       gg_stage(a, node.f0, node.ndims, gi0, gj0, Fr_s, Fc_s, tid);
+      if (node.op == GPS_K_ARCCOSINE) {
+        GradArc g[GG_E];
+        gg_arc(node, Fr_s, Fc_s, ty, tx, gi0, gj0, same_points, g);
+        for (int d = 0; d < node.ndims; ++d) {
+          const double r0 = Fr_s[d * GG_T + ty * 2], r1 = Fr_s[d * GG_T + ty * 2 + 1];
+          const double c0 = Fc_s[d * GG_T + tx * 2], c1 = Fc_s[d * GG_T + tx * 2 + 1];
+          double s0 = f4[0] * (g[0].dP * c0 + 2.0 * g[0].dni * r0) + f4[1] * (g[1].dP * c1 + 2.0 * g[1].dni * r0);
+          double s1 = f4[2] * (g[2].dP * c0 + 2.0 * g[2].dni * r1) + f4[3] * (g[3].dP * c1 + 2.0 * g[3].dni * r1);
+#pragma unroll
+          for (int off = 1; off < 16; off <<= 1) { s0 += __shfl_xor(s0, off, 64); s1 += __shfl_xor(s1, off, 64); }
+          if (tx == 0) {
+            const GradFeat ft = gi.feats[node.f0 + d];
+            rowacc[ty * 2][ft.dim] += s0 * ft.param; rowacc[ty * 2 + 1][ft.dim] += s1 * ft.param;
+          }
+        }
+        continue;
+      }
       double val[GG_E], q4[GG_E];
       gg_prim(node, Fr_s, Fc_s, ty, tx, gi0, gj0, same_points, val, q4);
       if (grad_is_dot(node.op)) {
@@ -485,6 +598,8 @@ int gps_grad_slots(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, int
     else if (op == GPS_K_RATQUAD) s += 2 + prog[i].n_dims;
     else if (op == GPS_K_LINEAR) s += prog[i].n_dims;
     else if (op == GPS_K_POLYNOMIAL) s += prog[i].n_dims + 1;
+    else if (op == GPS_K_COSINE) s += 1 + 2 * prog[i].n_dims;
+    else if (op == GPS_K_ARCCOSINE) s += 2 + prog[i].n_dims;
     else if (op == GPS_K_NKN_LINROW) s += prog[i].n_dims + 1;
     else if (grad_is_prim(op)) s += 1 + prog[i].n_dims;
     else return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: unknown op");
@@ -700,7 +815,8 @@ int gps_kdiag_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 
 
 // The same for a program with Linear, whose Kdiag_i = sum_d v_d x_id^2 depends on the point (kernels.py:507-510): X host
 // [n, d_all], kbar host [n], added to the slots.  O(n) work on the host from what the caller holds there anyway; forward mode
-// over the fold per point and primitive.  Polynomial and network programs are not taken.
+// over the fold per point and primitive.  ArcCosine likewise: Kdiag_i = variance jfac n_i^order, n_i = sum_d w_d x_id^2 + b,
+// jfac = 1, 1, 3 (kernels.py:760-766).  Polynomial and network programs are not taken.
 int gps_kdiag_vjp_points(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, const double* X, i64 n, const double* kbar,
                          double* grad_slots_host) {
   GGBuilt B;
@@ -722,6 +838,12 @@ int gps_kdiag_vjp_points(gps_handle_t h, const gps_kern_node_t* prog, int n_node
         for (int f = 0; f < g.nf; ++f) { const GradFeat& ft = B.prims.feats[(size_t)(g.f0 + f)]; const double v = x[ft.dim] * ft.param; s += v * v; }
         val[nd] = s;
       }
+      if (g.op == GPS_K_ARCCOSINE) {
+        double s = g.ls0;
+        for (int f = 0; f < g.nf; ++f) { const GradFeat& ft = B.prims.feats[(size_t)(g.f0 + f)]; const double v = x[ft.dim] * ft.param; s += v * v; }
+        const int order = (int)g.period;
+        val[nd] = order == 0 ? g.variance : (order == 1 ? g.variance * s : g.variance * 3.0 * (s * s));
+      }
     }
     for (int p = 0; p < B.P.n_prims; ++p) {
       double sv[GPS_MAX_STACK + 1], st[GPS_MAX_STACK + 1]; int sp = 0;
@@ -742,6 +864,15 @@ int gps_kdiag_vjp_points(gps_handle_t h, const gps_kern_node_t* prog, int n_node
       const double c = kbar[i] * st[0];
       if (mine->op == GPS_K_LINEAR) {
         for (int f = 0; f < mine->nf; ++f) { const double xd = x[B.prims.feats[(size_t)(mine->f0 + f)].dim]; acc[(size_t)(mine->slot0 + f)] += c * xd * xd; }
+      } else if (mine->op == GPS_K_ARCCOSINE) {
+        // slots in true units: [variance, b, w_0 ..]
+        double s = mine->ls0;
+        for (int f = 0; f < mine->nf; ++f) { const GradFeat& ft = B.prims.feats[(size_t)(mine->f0 + f)]; const double v = x[ft.dim] * ft.param; s += v * v; }
+        const int order = (int)mine->period;
+        const double dn = order == 0 ? 0.0 : (order == 1 ? mine->variance : mine->variance * 6.0 * s);
+        acc[(size_t)mine->slot0] += c * (order == 0 ? 1.0 : (order == 1 ? s : 3.0 * (s * s)));
+        acc[(size_t)(mine->slot0 + 1)] += c * dn;
+        for (int f = 0; f < mine->nf; ++f) { const double xd = x[B.prims.feats[(size_t)(mine->f0 + f)].dim]; acc[(size_t)(mine->slot0 + 2 + f)] += c * dn * xd * xd; }
       } else {
         acc[(size_t)mine->slot0] += c;
       }

@@ -8,6 +8,9 @@
 //   RatQuad.K                kernels.py:467-471   (same distance; (1 + r2 / (2 alpha))^-alpha = exp(-alpha log1p(r2 / (2 alpha))))
 //   Linear.K / Polynomial.K  kernels.py:499-505, 550-551 (features x_d sqrt(v_d): the dot product IS the kernel, and
 //                                                  K(X, X) is symmetric to the bit; no norm row)
+//   Cosine.K                 kernels.py:633-646   (features cos a, sin a with a = sum_d x_d w_d / l_d over the SLICED columns:
+//                                                  variance * dot product; the reference divides before it slices)
+//   ArcCosine.K              kernels.py:722-758   (features x_d sqrt(w_d) and their norm row; + b in the formula)
 //   Periodic.K               kernels.py:806-819   (via u = (cos, sin) features: the docstring's
 //                                                  own mapping, kernels.py:776 -- avoids the
 //                                                  reference's [N,M,D] temporary and D*N*M sin())
@@ -29,12 +32,14 @@
 #define KMAXF 64       // features per primitive (32 dims x {cos, sin})
 
 struct PrepFeat { int dim; int kind; double param; };   // kind 0: x/param ; 1: cos(2 pi x/param) ; 2: sin(...) ; 3: x*param
+// kind 4 / 5: cos / sin of a linear combination of columns, a = sum_q x[tab[dim + q].dim] * tab[dim + q].param over the
+// (int)param table entries from index `dim` on (Cosine: kind-3 entries x_d (w_d / l_d), which follow the pair in the table)
 struct PrepNorm { int f0; int nf; };
 
 struct KNodeDev {
   int op; int f0; int nf; int norm_row;   // norm_row: row index in Ft holding |a|^2 (or -1)
-  double variance; double c0;             // c0: periodic lengthscale ; RatQuad: alpha ; Polynomial: degree (variance: its offset)
-  double c1;                              // periodic: -1 / (4 c0^2) ; RatQuad: 1 / alpha
+  double variance; double c0;             // c0: periodic lengthscale ; RatQuad: alpha ; Polynomial: degree (variance: its offset) ; ArcCosine: order
+  double c1;                              // periodic: -1 / (4 c0^2) ; RatQuad: 1 / alpha ; ArcCosine: bias variance
 };
 struct KProgDev {
   int n_nodes;
@@ -73,13 +78,19 @@ __global__ __launch_bounds__(256) void kmat_prep_kernel(const double* __restrict
   const double* x = X + i * d_all;
   for (int f = 0; f < nfeat; ++f) {
     const PrepFeat pf = tab.f[f];
-    const double xv = x[pf.dim];
     double v;
-    if (pf.kind == 0) v = xv / pf.param;
-    else if (pf.kind == 3) v = xv * pf.param;
-    else {
-      const double ang = 2.0 * M_PI * xv / pf.param;
-      v = (pf.kind == 1) ? cos(ang) : sin(ang);
+    if (pf.kind >= 4) {
+      double ang = 0.0;
+      for (int q = 0; q < (int)pf.param; ++q) { const PrepFeat cf = tab.f[pf.dim + q]; ang = fma(x[cf.dim], cf.param, ang); }
+      v = (pf.kind == 4) ? cos(ang) : sin(ang);
+    } else {
+      const double xv = x[pf.dim];
+      if (pf.kind == 0) v = xv / pf.param;
+      else if (pf.kind == 3) v = xv * pf.param;
+      else {
+        const double ang = 2.0 * M_PI * xv / pf.param;
+        v = (pf.kind == 1) ? cos(ang) : sin(ang);
+      }
     }
     Ft[(i64)f * ldf + i] = v;
   }
@@ -205,6 +216,38 @@ __device__ __forceinline__ double gps_polynomial(double lin, double offset, doub
   return p;
 }
 
+// ArcCosine (kernels.py:727-758) from P = sum_d w_d x_d x'_d + b and n = P(x, x), n' = P(x', x'):
+//   c = 1e-15 + (1 - 2e-15) P / (sqrt(n) sqrt(n')),  theta = acos(c),  k = variance / pi J_order(theta) (sqrt(n) sqrt(n'))^order
+// sqrt(n) sqrt(n') is symmetric in the two points, so K(X, X) is symmetric to the bit.  same: one point against itself on the
+// diagonal of K(X, X) -- there P / (sqrt(n) sqrt(n)) is 1 and theta = acos(1 - 1e-15) = sqrt(2e-15) to 1e-16, and both are taken
+// as exactly that: the roundings of the quotient and of c, whose spacing next to 1 is 1.1e-16, move theta = 4.5e-8 by up to
+// 10 % and with it an order-0 entry by 2e-9 variance.  For two nearly parallel points c is clamped to 1 (where
+// tf.acos would return NaN).
+#define GPS_ARCCOS_THETA0 4.4721359549995794e-08
+#define GPS_ARCCOS_JITTER 1e-15
+// (cos(theta) = c and sin(theta) = sqrt((1 - c)(1 + c)) instead of tf.cos / tf.sin of the computed theta: the same numbers to
+// rounding, without two range reductions per entry)
+__device__ __forceinline__ double gps_arccos_J(int order, double theta, double c, bool same) {
+  const double pt = M_PI - theta;
+  if (order == 0) return pt;
+  const double s = same ? theta : sqrt((1.0 - c) * (1.0 + c));     // (same: sin(theta) = theta to 1e-23, not the sine of the rounded c)
+  if (order == 1) return s + pt * c;
+  return 3.0 * s * c + pt * (1.0 + 2.0 * (c * c));
+}
+__device__ __forceinline__ double gps_arccosine(double variance, int order, double P, double ni, double nj, bool same) {
+  const double sij = sqrt(ni) * sqrt(nj);
+  double c = GPS_ARCCOS_JITTER + (1.0 - 2.0 * GPS_ARCCOS_JITTER) * (same ? 1.0 : P / sij);
+  c = (c > 1.0) ? 1.0 : c;
+  const double theta = same ? GPS_ARCCOS_THETA0 : acos(c);
+  const double J = gps_arccos_J(order, theta, c, same);
+  const double scale = (order == 0) ? 1.0 : (order == 1 ? sij : sij * sij);
+  return variance * (1.0 / M_PI) * J * scale;
+}
+// ... and on the diagonal (theta = 0: J = pi, pi, 3 pi; kernels.py:760-766)
+__device__ __forceinline__ double gps_arccosine_diag(double variance, int order, double n) {
+  return order == 0 ? variance : (order == 1 ? variance * n : variance * 3.0 * (n * n));
+}
+
 // ---- the pieces the tile kernels share ---------------------------------------------------------------------------------------
 // Expression grouping in the formulas is part of the result: the compiler contracts multiply-adds by expression shape, so
 // -r2 / 2.0 stays -r2 / 2.0 and (ni + nj) keeps its parentheses (grad_common.hpp says the same of the gradient's formulas).
@@ -254,12 +297,15 @@ __device__ __forceinline__ void kmat_dots(const KSlabs& s, int nf, int r0, int c
   }
 }
 
-// The value of a primitive with features from its dot product and the two squared norms, for the four VALU users.
-// OP >= 0: that op at compile time (kmat_single_kernel); OP < 0: `op` at run time.  EXT: RatQuad, Linear, Polynomial and the
-// distance ops too -- the interpreter, the network kernel and kmat_single_kernel<RATQUAD>; kmat_chain_kernel is routed none of
+// The value of a primitive with features from its dot product and the two squared norms, for the four VALU users.  same (read by
+// ArcCosine alone): the entry is one point against itself, on the diagonal of K(X, X).
+// OP >= 0: that op at compile time (kmat_single_kernel); OP < 0: `op` at run time.  EXT: RatQuad, Linear, Polynomial, Cosine,
+// ArcCosine and the distance ops too -- the interpreter, the network kernel and kmat_single_kernel<RATQUAD>; kmat_chain_kernel is routed none of
 // them (is_left_deep_chain) and does not pay registers for their formulas.
-template <int OP, bool EXT>
-__device__ __forceinline__ double kmat_prim_value(const KNodeDev& node, int op, double dot, double ni, double nj) {
+// EXT: 0 none of them, 1 all but Cosine / ArcCosine (the instances that existed before those two keep their code), 2: Cosine
+// too (one multiplication), 3: ArcCosine too (acos, a division and three square roots per entry: one wave per SIMD less).
+template <int OP, int EXT>
+__device__ __forceinline__ double kmat_prim_value(const KNodeDev& node, int op, double dot, double ni, double nj, bool same = false) {
   const int o = (OP >= 0) ? OP : op;
   if (o == GPS_K_PERIODIC) {
     // sum_d sin^2(pi (x - x')/p) / l^2 = (D - sum_d cos(a_d - b_d)) / (2 l^2): kernels.py:813-819 in cos / sin feature form
@@ -269,6 +315,8 @@ __device__ __forceinline__ double kmat_prim_value(const KNodeDev& node, int op, 
     return node.variance * gps_exp_nonpos(-0.5 * rs);
   }
   if (EXT && o == GPS_K_LINEAR) return dot;
+  if (EXT >= 2 && o == GPS_K_COSINE) return node.variance * dot;        // cos a cos a' + sin a sin a' (kernels.py:637-646)
+  if (EXT >= 3 && o == GPS_K_ARCCOSINE) return gps_arccosine(node.variance, (int)node.c0, dot + node.c1, ni + node.c1, nj + node.c1, same);
   if (EXT && o == GPS_K_POLYNOMIAL) return gps_polynomial(dot, node.variance, node.c0);
   const double sq3 = 1.7320508075688772, sq5 = 2.23606797749979;
   double r2 = -2.0 * dot + (ni + nj);                                          // kernels.py:409-421
@@ -286,7 +334,7 @@ __device__ __forceinline__ double kmat_prim_value(const KNodeDev& node, int op, 
 
 // One node of a program on the 4 x 4 patch (rows 4 ty .., columns 4 tx ..) of the interpreter and the chain kernel: Constant
 // and White without features, every other primitive through its staged slabs
-template <bool EXT>
+template <int EXT>
 __device__ __forceinline__ void kmat_patch_value(const KmatArgs& a, const KNodeDev& node, const KSlabs& s, i64 gi0, i64 gj0, int tid,
                                                  double (&v)[16]) {
   const int tx = tid & 15, ty = tid >> 4;
@@ -308,7 +356,8 @@ __device__ __forceinline__ void kmat_patch_value(const KmatArgs& a, const KNodeD
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const double ni = has_norm ? s.nr[ty * 4 + (e >> 2)] : 0.0, nj = has_norm ? s.nc[tx * 4 + (e & 3)] : 0.0;
-      v[e] = kmat_prim_value<-1, EXT>(node, node.op, v[e], ni, nj);
+      const bool same = EXT >= 3 && a.sym && a.row_off + gi0 + ty * 4 + (e >> 2) == a.col_off + gj0 + tx * 4 + (e & 3);
+      v[e] = kmat_prim_value<-1, EXT>(node, node.op, v[e], ni, nj, same);
     }
   }
 }
@@ -335,6 +384,9 @@ __device__ __forceinline__ void kmat_store_patch(const KmatArgs& a, const double
 }
 
 // ---- tile pass: the interpreter ------------------------------------------------------------------
+// EXT = 2 / 3: the instances for programs with Cosine / with ArcCosine (kmat_prim_value); every other program runs EXT = 1, the
+// interpreter as it was before those two primitives.
+template <int EXT>
 __global__ __launch_bounds__(256) void kmat_tile_kernel(KmatArgs a, KProgDev P) {
   const int ti = blockIdx.y, tj = blockIdx.x;
   if (kmat_upper_tile(a, ti, tj)) return;
@@ -361,7 +413,7 @@ __global__ __launch_bounds__(256) void kmat_tile_kernel(KmatArgs a, KProgDev P) 
       continue;
     }
     double v[16];
-    kmat_patch_value<true>(a, node, lds, gi0, gj0, tid, v);
+    kmat_patch_value<EXT>(a, node, lds, gi0, gj0, tid, v);
     // push
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
@@ -421,7 +473,7 @@ __global__ __launch_bounds__(256, 4) void kmat_single_kernel(KmatArgs a, KNodeDe
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const i64 gj = a.col_off + gj0 + (c < 2 ? c_lo + c : c_hi + c - 2);
-      o[c] = kmat_finish(a, kmat_prim_value<OP, true>(node, OP, dot[q * 4 + c], ni, ncol[c]), a.row_off + li, gj);
+      o[c] = kmat_finish(a, kmat_prim_value<OP, 1>(node, OP, dot[q * 4 + c], ni, ncol[c]), a.row_off + li, gj);
     }
     double* dst = a.K + li * a.ldk + gj0;
     *reinterpret_cast<double2*>(dst + c_lo) = make_double2(o[0], o[1]);
@@ -450,7 +502,7 @@ __global__ __launch_bounds__(256, 2) void kmat_chain_kernel(KmatArgs a, KProgDev
     const KNodeDev node = P.nodes[nd];
     const int op = (nd == 0) ? -1 : P.nodes[nd + 1].op;
     double v[16];
-    kmat_patch_value<false>(a, node, lds, gi0, gj0, tid, v);
+    kmat_patch_value<0>(a, node, lds, gi0, gj0, tid, v);
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = (op < 0) ? v[e] : ((op == GPS_K_ADD) ? (acc[e] + v[e]) : (acc[e] * v[e]));
   }
@@ -632,11 +684,12 @@ __global__ __launch_bounds__(256, 3) void kmat_mfma_kernel(KmatArgs a, KProgDev 
 // p0 (p_i op_i)* with op in {ADD, MUL}
 static bool is_left_deep_chain(const KProgDev& P) {
   if (P.n_nodes < 3 || (P.n_nodes & 1) == 0) return false;
-  // (the distance ops are evaluated by the interpreter only: they are helpers, not kernels of a model; so are RatQuad, Linear
-  // and Polynomial: the two chain kernels do not know their formulas, and a chain with one of them goes to kmat_tile_kernel)
+  // (the distance ops are evaluated by the interpreter only: they are helpers, not kernels of a model; so are RatQuad, Linear,
+  // Polynomial, Cosine and ArcCosine: the two chain kernels do not know their formulas, and a chain with one of them goes to
+  // kmat_tile_kernel)
   auto prim = [](int op) {
     return op != GPS_K_ADD && op != GPS_K_MUL && op != GPS_K_SQDIST && op != GPS_K_EUCLID && op != GPS_K_RATQUAD && op != GPS_K_LINEAR &&
-           op != GPS_K_POLYNOMIAL && op < GPS_K_NKN_LINROW;
+           op != GPS_K_POLYNOMIAL && op != GPS_K_COSINE && op != GPS_K_ARCCOSINE && op < GPS_K_NKN_LINROW;
   };
   if (!prim(P.nodes[0].op)) return false;
   for (int i = 1; i < P.n_nodes; i += 2) {
@@ -644,6 +697,16 @@ static bool is_left_deep_chain(const KProgDev& P) {
     if (P.nodes[i + 1].op != GPS_K_ADD && P.nodes[i + 1].op != GPS_K_MUL) return false;
   }
   return true;
+}
+
+// the EXT level (kmat_prim_value) a program needs of the interpreter
+static int kmat_ext_level(const KProgDev& P) {
+  int ext = 1;
+  for (int i = 0; i < P.n_nodes; ++i) {
+    if (P.nodes[i].op == GPS_K_COSINE && ext < 2) ext = 2;
+    if (P.nodes[i].op == GPS_K_ARCCOSINE) ext = 3;
+  }
+  return ext;
 }
 
 // ---- Neural Kernel Network epilogue ---------------------------------------------------------------
@@ -696,6 +759,7 @@ __device__ __forceinline__ void nkn_forward(const NknNet& net, const double* W, 
   }
 }
 
+template <int EXT>      // (as kmat_tile_kernel; programs with Cosine or ArcCosine: 3)
 __global__ __launch_bounds__(256) void nkn_tile_kernel(KmatArgs a, KProgDev P, NknNet net,
                                                        const double* __restrict__ Wg) {
   const int ti = blockIdx.y, tj = blockIdx.x;
@@ -735,7 +799,7 @@ __global__ __launch_bounds__(256) void nkn_tile_kernel(KmatArgs a, KProgDev P, N
           for (int f = 0; f < node.nf; ++f) dot = fma(Fr_s[(node.f0 + f) * KT + li], Fc_s[(node.f0 + f) * KT + lj], dot);
           double ni = 0.0, nj = 0.0;
           if (node.norm_row >= 0) { ni = Fr_s[node.norm_row * KT + li]; nj = Fc_s[node.norm_row * KT + lj]; }
-          val = kmat_prim_value<-1, true>(node, node.op, dot, ni, nj);
+          val = kmat_prim_value<-1, EXT>(node, node.op, dot, ni, nj, a.sym && gi == gj);
         }
         vin[p] = val;
       }
@@ -790,7 +854,7 @@ static int compile_prog(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes
         break;
       case GPS_K_RBF: case GPS_K_MATERN12: case GPS_K_MATERN32: case GPS_K_MATERN52:
       case GPS_K_EXPONENTIAL: case GPS_K_PERIODIC: case GPS_K_SQDIST: case GPS_K_EUCLID: case GPS_K_RATQUAD:
-      case GPS_K_LINEAR: case GPS_K_POLYNOMIAL: {
+      case GPS_K_LINEAR: case GPS_K_POLYNOMIAL: case GPS_K_COSINE: case GPS_K_ARCCOSINE: {
         if (nd.n_dims <= 0 || nd.n_dims > GPS_MAX_DIMS)
           return gps_fail(h, GPS_ERR_ARG, "kernel program: n_dims out of range");
         kd.f0 = (int)out.feats.size();
@@ -808,6 +872,31 @@ static int compile_prog(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes
           kd.nf = 2 * nd.n_dims;
           kd.c0 = nd.lengthscales[0];
           kd.c1 = -1.0 / (4.0 * kd.c0 * kd.c0);
+        } else if (nd.op == GPS_K_COSINE) {
+          // two feature rows, cos a and sin a; the coefficients w_d / l_d of a follow them in the table as kind-3 entries (their
+          // rows are written and not read)
+          if (nd.n_dims > GPS_MAX_DIMS / 2)
+            return gps_fail(h, GPS_ERR_UNSUPPORTED, "kernel program: Cosine takes at most 16 active dims (lengthscales and weights share one field)");
+          out.feats.push_back({kd.f0 + 2, 4, (double)nd.n_dims});
+          out.feats.push_back({kd.f0 + 2, 5, (double)nd.n_dims});
+          for (int d = 0; d < nd.n_dims; ++d) {
+            if (!(nd.lengthscales[d] > 0.0)) return gps_fail(h, GPS_ERR_ARG, "kernel program: lengthscale must be positive");
+            out.feats.push_back({nd.active_dims[d], 3, nd.lengthscales[nd.n_dims + d] / nd.lengthscales[d]});
+          }
+          kd.nf = 2;
+        } else if (nd.op == GPS_K_ARCCOSINE) {
+          if (nd.n_dims > GPS_MAX_DIMS - 1)
+            return gps_fail(h, GPS_ERR_UNSUPPORTED, "kernel program: ArcCosine takes at most 31 active dims (the bias variance follows the weight variances)");
+          if (nd.period != 0.0 && nd.period != 1.0 && nd.period != 2.0)
+            return gps_fail(h, GPS_ERR_ARG, "kernel program: ArcCosine order must be 0, 1 or 2");
+          if (!(nd.lengthscales[nd.n_dims] > 0.0)) return gps_fail(h, GPS_ERR_ARG, "kernel program: ArcCosine bias variance must be positive");
+          for (int d = 0; d < nd.n_dims; ++d) {
+            if (!(nd.lengthscales[d] > 0.0)) return gps_fail(h, GPS_ERR_ARG, "kernel program: ArcCosine weight variance must be positive");
+            out.feats.push_back({nd.active_dims[d], 3, sqrt(nd.lengthscales[d])});
+          }
+          kd.nf = nd.n_dims; kd.c0 = nd.period; kd.c1 = nd.lengthscales[nd.n_dims];
+          kd.norm_row = (int)out.norms.size();
+          out.norms.push_back({kd.f0, kd.nf});
         } else if (nd.op == GPS_K_LINEAR || nd.op == GPS_K_POLYNOMIAL) {
           if (nd.op == GPS_K_LINEAR && nd.variance != 1.0)
             return gps_fail(h, GPS_ERR_ARG, "kernel program: Linear carries its variances per dim, the variance field must be 1");
@@ -957,11 +1046,12 @@ static int launch_tiles(gps_handle_t h, const KCompiled& kc, KmatArgs& a, i64 pr
     if (rc) return rc;
     const int rows_f = kc.net.ftot + kc.net.nnorm;
     const size_t lds = ((size_t)2 * rows_f * KT + (size_t)kc.net.n_layers * NKN_W * (NKN_W + 1)) * 8;
-    int rcl = gps_dyn_lds(h, reinterpret_cast<const void*>(&nkn_tile_kernel), 160 * 1024);
+    auto* nkn_kern = kmat_ext_level(kc.prog) > 1 ? &nkn_tile_kernel<3> : &nkn_tile_kernel<1>;
+    int rcl = gps_dyn_lds(h, reinterpret_cast<const void*>(nkn_kern), 160 * 1024);
     if (rcl) return rcl;
     if (lds > 160 * 1024) return gps_fail(h, GPS_ERR_UNSUPPORTED, "NKN program: feature slabs exceed LDS");
     LaunchScope ls(h, KC_KMAT, tiles * KT * KT * (2.0 * nfeat_total + 600.0 * kc.net.n_layers), tiles * KT * KT * 8.0);
-    hipLaunchKernelGGL(nkn_tile_kernel, kmat_grid(prow, pcol), dim3(256), lds, h->stream, a, kc.prog, kc.net, (const double*)h->dNkn.p);
+    hipLaunchKernelGGL(nkn_kern, kmat_grid(prow, pcol), dim3(256), lds, h->stream, a, kc.prog, kc.net, (const double*)h->dNkn.p);
     GPS_HIP(h, hipGetLastError());
     return GPS_OK;
   }
@@ -982,18 +1072,22 @@ static int launch_tiles(gps_handle_t h, const KCompiled& kc, KmatArgs& a, i64 pr
   if (h->kmat_fast && is_left_deep_chain(kc.prog))                                     // Sum / Product of primitives
     return launch_program(h, &kmat_chain_kernel, kmat_grid(prow, pcol), a, kc.prog, maxnf, KLS,
                           2.0 * nfeat_total + 30.0 * ((kc.prog.n_nodes + 1) / 2), tiles);
-  return launch_program(h, &kmat_tile_kernel, kmat_grid(prow, pcol), a, kc.prog, maxnf, KLS, 2.0 * nfeat_total + 30.0, tiles);
+  const int ext = kmat_ext_level(kc.prog);
+  return launch_program(h, ext == 3 ? &kmat_tile_kernel<3> : (ext == 2 ? &kmat_tile_kernel<2> : &kmat_tile_kernel<1>), kmat_grid(prow, pcol), a,
+                        kc.prog, maxnf, KLS, 2.0 * nfeat_total + 30.0, tiles);
 }
 
-// Kdiag is one number for every point unless the program holds Linear or Polynomial (kernels.py:507-510, 553-554)
+// Kdiag is one number for every point unless the program holds Linear, Polynomial or ArcCosine (kernels.py:507-510, 553-554,
+// 760-766)
 bool gps_kdiag_is_const(const gps_kern_node_t* prog, int n_nodes) {
   for (int i = 0; i < n_nodes; ++i)
-    if (prog[i].op == GPS_K_LINEAR || prog[i].op == GPS_K_POLYNOMIAL) return false;
+    if (prog[i].op == GPS_K_LINEAR || prog[i].op == GPS_K_POLYNOMIAL || prog[i].op == GPS_K_ARCCOSINE) return false;
   return true;
 }
 
 int gps_launch_kdiag(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double* kdiag_const) {
-  // Kdiag of every primitive but Linear / Polynomial is its variance (kernels.py:428-429, 803-804, 327-328);
+  // Kdiag of every primitive but Linear / Polynomial / ArcCosine is its variance (kernels.py:428-429, 803-804, 327-328; Cosine
+  // is a Stationary);
   // Sum.Kdiag / Product.Kdiag fold them (kernels.py:1075-1076, 1083-1084).
   if (!gps_kdiag_is_const(prog, n_nodes))
     return gps_fail(h, GPS_ERR_UNSUPPORTED, GPS_KDIAG_NOT_CONST_MSG);
@@ -1070,16 +1164,17 @@ static int run_prep(gps_handle_t h, const KCompiled& kc, const double* dX, i64 n
 // ---- per-point Kdiag ----------------------------------------------------------------------------------------------------------
 // Kdiag(X)[i] of any program: one thread per point runs the program over the primitives' diagonals -- the variance
 // (kernels.py:428-429, 803-804, 327-328), sum_d v_d x_d^2 for Linear (:507-510: the squared norm of the point's feature
-// rows), its (. + offset)^degree for Polynomial (:553-554) -- through the Sum / Product folds (:1075-1076, 1083-1084) or the
+// rows), its (. + offset)^degree for Polynomial (:553-554), variance J(0) / pi (. + b)^order for ArcCosine (:760-766) -- through the Sum / Product folds (:1075-1076, 1083-1084) or the
 // network layers (NeuralKernelNetwork.Kdiag, neural_kernel_network.py:35-39).  Wg: the layers' weights [n_layers][16][17].
 __global__ __launch_bounds__(256) void kdiag_vec_kernel(const double* __restrict__ Ft, i64 ldf, i64 n, KProgDev P, NknNet net, int nkn,
                                                         const double* __restrict__ Wg, double* __restrict__ out) {
   const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   auto prim_diag = [&](const KNodeDev& node) -> double {
-    if (node.op != GPS_K_LINEAR && node.op != GPS_K_POLYNOMIAL) return node.variance;
+    if (node.op != GPS_K_LINEAR && node.op != GPS_K_POLYNOMIAL && node.op != GPS_K_ARCCOSINE) return node.variance;
     double s = 0.0;
     for (int f = 0; f < node.nf; ++f) { const double v = Ft[(i64)(node.f0 + f) * ldf + i]; s = fma(v, v, s); }
+    if (node.op == GPS_K_ARCCOSINE) return gps_arccosine_diag(node.variance, (int)node.c0, s + node.c1);
     return node.op == GPS_K_LINEAR ? s : gps_polynomial(s, node.variance, node.c0);
   };
   if (!nkn) {

@@ -13,7 +13,7 @@ import numpy as np
 
 from ._abi import (GPS_MAX_DIMS, GPS_MAX_NODES, GPS_MAX_STACK,                                        # noqa: F401
                    K_RBF, K_MATERN12, K_MATERN32, K_MATERN52, K_PERIODIC, K_WHITE, K_CONSTANT, K_EXPONENTIAL,
-                   K_SQDIST, K_EUCLID, K_RATQUAD, K_LINEAR, K_POLYNOMIAL, K_ADD, K_MUL,
+                   K_SQDIST, K_EUCLID, K_RATQUAD, K_LINEAR, K_POLYNOMIAL, K_COSINE, K_ARCCOSINE, K_ADD, K_MUL,
                    K_NKN_LINROW, K_NKN_PRODUCT, K_NKN_ACT, KernNode, LikDesc, RffDesc,
                    RFF_RBF, RFF_LINEAR, RFF_CONSTANT, RFF_EXPLICIT, LIK_MAX_GH, LIK_MULTICLASS,
                    make_rff, make_lik, make_program, primitive_node, op_node, psi2_chunking, psi_sum_chunking,

@@ -3,7 +3,7 @@
 API mirror of gpflowSlim/kernels.py for the kernels on the hot path: Kernel (active-dims
 slicing :217-253, ``+`` / ``*`` :277-281), Static/White/Constant/Bias :308-357, Stationary
 :360-429, RBF :432-439, RatQuad :447-471, Linear :474-515, Polynomial :518-554, Exponential :557-565,
-Matern12/32/52 :569-610, Periodic :769-819, Combination/Sum/Product :1000-1084.
+Matern12/32/52 :569-610, Cosine :617-646, ArcCosine :649-766, Periodic :769-819, Combination/Sum/Product :1000-1084.
 
 Differences from the reference, on purpose: values are eager numpy fp64 arrays (there is no
 TensorFlow graph); ``K`` compiles the kernel *tree* into one reverse-Polish program and
@@ -351,6 +351,118 @@ class Matern32(Stationary):
 class Matern52(Stationary):
     """kernels.py:601-610"""
     _op = be.K_MATERN52
+
+
+class Cosine(Stationary):
+    """kernels.py:617-646: variance * cos(a - a'), a = sum_d x_d w_d / l_d; parameters [variance, lengthscales, weights].
+
+    ``weights`` is an untransformed [input_dim, 1] parameter drawn from ``np.random.normal`` as in the reference; the
+    ``weights=`` argument (not in the reference) fixes it.  Unlike the reference, which divides X by the lengthscales before
+    it slices (kernels.py:634-636: wrong or failing with ``active_dims`` on a subset), the active columns are sliced first.
+    The device op keeps lengthscales and weights in one 32-entry field: at most 16 active dims."""
+    _op = be.K_COSINE
+
+    def __init__(self, input_dim, variance=1.0, lengthscales=None, active_dims=None, ARD=False, min_ls=1e-6, name='kernel',
+                 weights=None):
+        super().__init__(input_dim, variance=variance, lengthscales=lengthscales, active_dims=active_dims, ARD=ARD,
+                         min_ls=min_ls, name=name)
+        if self.input_dim > be.GPS_MAX_DIMS // 2:
+            raise ValueError("Cosine supports at most %d active dims" % (be.GPS_MAX_DIMS // 2))
+        if weights is None:
+            weights = np.random.normal(size=[self.input_dim, 1])
+        weights = np.asarray(weights, dtype=settings.float_type).reshape(self.input_dim, 1)
+        self._weights = Parameter(weights, name='weights')
+        self._parameters = self._parameters + [self._weights]
+
+    @property
+    def weights(self):
+        return self._weights.value
+
+    def _nodes(self, presliced, d_all):
+        dims = self._dims(presliced, d_all)
+        ls = np.atleast_1d(self.lengthscales)
+        w = np.asarray(self.weights, dtype=settings.float_type).ravel()
+        if ls.size not in (1, len(dims)) or w.size != len(dims):
+            raise ValueError("lengthscales / weights do not match the active dims")
+        if len(dims) > be.GPS_MAX_DIMS // 2:
+            raise ValueError("Cosine supports at most %d active dims" % (be.GPS_MAX_DIMS // 2))
+        ls = ls * np.ones(len(dims), dtype=settings.float_type)
+        return [be.primitive_node(be.K_COSINE, np.squeeze(self.variance), dims, np.concatenate([ls, w]))]
+
+    def _grad_layout(self, d_all):
+        nd = len(self._dims(False, d_all))
+        return super()._grad_layout(d_all) + [(self._weights, d) for d in range(nd)]
+
+    def dimwise(self, dim):
+        raise NotImplementedError("Cosine has no one-dimensional factors")
+
+
+class ArcCosine(Kernel):
+    """kernels.py:649-766 (Cho & Saul 2009): with P(x, x') = sum_d w_d x_d x'_d + b, n = P(x, x),
+    theta = acos(1e-15 + (1 - 2e-15) P / (sqrt(n) sqrt(n'))):  variance / pi * J_order(theta) * (n n')^(order / 2).
+    Parameters [variance, bias_variance, weight_variances].  Kdiag depends on the point, so the device paths that assume a
+    constant Kdiag refuse this kernel exactly where they refuse Linear.  The device op keeps the weight variances and the
+    bias variance in one 32-entry field: at most 31 active dims."""
+    implemented_orders = {0, 1, 2}
+
+    def __init__(self, input_dim, order=0, variance=1.0, weight_variances=1., bias_variance=1.0, active_dims=None, ARD=False,
+                 name='kernel'):
+        super().__init__(input_dim, active_dims, name=name)
+        if order not in self.implemented_orders:
+            raise ValueError('Requested kernel order is not implemented.')
+        if self.input_dim > be.GPS_MAX_DIMS - 1:
+            raise ValueError("ArcCosine supports at most %d active dims" % (be.GPS_MAX_DIMS - 1))
+        self.order = order
+        self._variance = Parameter(variance, transform=transforms.positive, name='variance')
+        self._bias_variance = Parameter(bias_variance, transform=transforms.positive, name='bias_variance')
+        if ARD:
+            weight_variances = (1.0 if weight_variances is None else weight_variances) * np.ones(self.input_dim, dtype=settings.float_type)
+        elif weight_variances is None:
+            weight_variances = 1.0
+        self.ARD = ARD
+        self._weight_variances = Parameter(weight_variances, transform=transforms.positive, name='weight_variances')
+        self._parameters = self._parameters + [self._variance, self._bias_variance, self._weight_variances]
+
+    @property
+    def variance(self):
+        return self._variance.value
+
+    @property
+    def bias_variance(self):
+        return self._bias_variance.value
+
+    @property
+    def weight_variances(self):
+        return self._weight_variances.value
+
+    def _dim_weights(self, presliced, d_all):
+        dims = self._dims(presliced, d_all)
+        w = np.atleast_1d(self.weight_variances)
+        if w.size not in (1, len(dims)):
+            raise ValueError("weight variances do not match the active dims")
+        if len(dims) > be.GPS_MAX_DIMS - 1:
+            raise ValueError("ArcCosine supports at most %d active dims" % (be.GPS_MAX_DIMS - 1))
+        return dims, w * np.ones(len(dims), dtype=settings.float_type)
+
+    def _nodes(self, presliced, d_all):
+        dims, w = self._dim_weights(presliced, d_all)
+        b = float(np.squeeze(self.bias_variance))
+        return [be.primitive_node(be.K_ARCCOSINE, np.squeeze(self.variance), dims, np.concatenate([w, [b]]), period=float(self.order))]
+
+    def _J0(self):
+        return (np.pi, np.pi, 3.0 * np.pi)[self.order]
+
+    def Kdiag(self, X, presliced=False):
+        """kernels.py:760-766"""
+        X = np.asarray(X, dtype=settings.float_type)
+        dims, w = self._dim_weights(presliced, X.shape[1])
+        n = np.sum(np.square(X[:, dims]) * w, 1) + self.bias_variance
+        return self.variance * (1. / np.pi) * self._J0() * n ** self.order
+
+    def _grad_layout(self, d_all):
+        nd = len(self._dims(False, d_all))
+        ard = np.atleast_1d(self.weight_variances).size > 1
+        return [(self._variance, None), (self._bias_variance, None)] + [(self._weight_variances, d if ard else None) for d in range(nd)]
 
 
 class Periodic(Kernel):

@@ -68,6 +68,17 @@ enum gps_kern_op {
   GPS_K_RATQUAD  = 11, /* RatQuad.K    kernels.py:467-471: variance * (1 + 0.5 r2 / alpha)^(-alpha), r2 as in SQDIST    */
   GPS_K_LINEAR   = 12, /* Linear.K     kernels.py:499-505: sum_d v_d x_d x'_d                                          */
   GPS_K_POLYNOMIAL = 13, /* Polynomial.K kernels.py:550-551: (Linear + offset)^degree                                   */
+  /* The next two re-use the fields as well (layout unchanged):
+   *   op          variance        lengthscales[]                                         period
+   *   COSINE      variance        [0, n_dims): lengthscale l_d (> 0);                     unused
+   *                               [n_dims, 2 n_dims): weight w_d (any sign)               -> n_dims <= 16
+   *   ARCCOSINE   variance        [0, n_dims): weight variance w_d (> 0);                 order: 0, 1 or 2 (fixed)
+   *                               [n_dims]: bias variance b (> 0)                         -> n_dims <= 31
+   * More active dims than that are GPS_ERR_UNSUPPORTED.  Kdiag of COSINE is its variance; Kdiag of ARCCOSINE depends on the
+   * point (variance J(0) / pi (sum_d w_d x_d^2 + b)^order) and the kernel is taken and refused where LINEAR is.
+   * Gradient slots: COSINE [variance, l_0 .., w_0 ..]; ARCCOSINE [variance, b, w_0 ..].                                     */
+  GPS_K_COSINE   = 14, /* Cosine.K     kernels.py:633-646: variance * cos(a - a'), a = sum_d x_d w_d / l_d (sliced first)  */
+  GPS_K_ARCCOSINE = 15, /* ArcCosine.K kernels.py:740-758: variance / pi * J_order(theta) (n n')^(order / 2)               */
   GPS_K_ADD      = 16, /* Sum.K     reduce(tf.add, ...)      :1073          */
   GPS_K_MUL      = 17, /* Product.K reduce(tf.multiply, ...) :1081          */
   /* Neural Kernel Network (neural_kernel_network/neural_kernel_network.py:41-47): a program that
@@ -84,8 +95,9 @@ typedef struct gps_kern_node {
   int32_t n_dims;                       /* active dims of a primitive        */
   int32_t active_dims[GPS_MAX_DIMS];    /* column indices into X (Kernel._slice, kernels.py:217-253) */
   double  variance;                     /* constrained value (Polynomial: the offset; Linear: 1.0)           */
-  double  period;                       /* Periodic: period; RatQuad: alpha; Polynomial: degree              */
-  double  lengthscales[GPS_MAX_DIMS];   /* per active dim (ARD) or repeated; Linear / Polynomial: variances  */
+  double  period;                       /* Periodic: period; RatQuad: alpha; Polynomial: degree; ArcCosine: order */
+  double  lengthscales[GPS_MAX_DIMS];   /* per active dim (ARD) or repeated; Linear / Polynomial: variances;
+                                           Cosine: lengthscales then weights; ArcCosine: weight variances then the bias variance */
 } gps_kern_node_t;
 
 typedef struct gps_handle_s* gps_handle_t;
