@@ -229,7 +229,7 @@ extern "C" int gps_gauss_kl(gps_handle_t h, const double* K, int64_t m, const do
   GPS_HIP(h, h->dS4.ensure(linv_bytes(mp)));
   GPS_HIP(h, h->dS3.ensure((size_t)k * mp * 8));
   GPS_HIP(h, h->dTmp.ensure((size_t)mp * mp * 8));
-  GPS_HIP(h, h->dTmp2.ensure((size_t)mp * mp * 8));
+  GPS_HIP(h, h->dTmp2.ensure((size_t)(mp * mp > m * k ? mp * mp : m * k) * 8));     // q_mu [m, k] first (k may exceed mp), then L_q^T [mp, mp]
   GPS_HIP(h, hipMemcpyAsync(h->dTmp.p, K, (size_t)m * m * 8, hipMemcpyHostToDevice, h->stream));
   int rc = gps_launch_pad_copy(h, h->dTmp.d(), m, m, m, h->dS2.d(), mp, mp, mp, 1, 0.0);
   if (rc) return rc;
