@@ -614,6 +614,21 @@ int gps_launch_psi1_vjp_dense(gps_handle_t h, const PsiIn& in, const double* Y, 
                               i64 r, i64 n0, i64 n1, const double* Bar, i64 ldb, const double* BarT, i64 ldbt, double* out_n,
                               double* part_z, i64 nz, i64 zchunk, i64 ldz);
 int gps_launch_psi_fold(gps_handle_t h, const double* part, int nchunks, i64 rows, i64 cols, i64 ldp, double* out, i64 ldo);
+// out [b][ldo] <- sum_{m, m'} psi2n_n[m][m'] W_b[m][m'] point by point, psi2n never stored: see psi.hip
+int gps_launch_psi2_contract(gps_handle_t h, const PsiIn& in, const double* W, i64 ldw, i64 sw, int b, double* PKW, i64 ldpk,
+                             double* out, i64 ldo);
+// gps_gplvm.hip : what every entry on the kernel expectations starts with -- the scope check of the program (who: the entry's name
+// for the message), the check of Xvar, begin_inducing_call, the uploads (Z -> dX, the inputs -> dA, the part views of a Sum ->
+// dPsiParts) and the per-point terms.  parts <- one view per RBF part, in part order, with the part's node in the program.
+struct PsiPart { int node; PsiIn in; };
+int gps_psi_setup(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes, const double* Z, i64 m, const double* Xmu,
+                  const double* Xvar, i64 n, i64 q, std::vector<PsiPart>* parts);
+// the rows n0 .. n0 + cnt - 1 of a view
+static inline PsiIn gps_psi_rows(const PsiIn& in, i64 n0, i64 cnt) {
+  PsiIn s = in;
+  s.Xmu += n0 * in.q; s.Xvar += n0 * in.q; s.A1 += n0 * in.q; s.A2 += n0 * in.q; s.C1 += n0; s.C2 += n0; s.n = cnt;
+  return s;
+}
 // psi_sum.hip : what a Sum of RBF parts on pairwise disjoint latent dimensions adds to the expectations of its parts
 struct PsiDims { int d[GPS_MAX_DIMS]; };
 // points per chunk of the streamed cross terms (a multiple of 16) and the number of chunks; opt > 0 asks for a chunk length
@@ -629,6 +644,8 @@ int gps_launch_psi_others(gps_handle_t h, const double* T, int P, i64 stride, in
 int gps_launch_psi_sym_add(gps_handle_t h, double* A, i64 lda, const double* C, i64 ldc, i64 m);
 // S [mp, mp] <- (X + X^T) / 2 on the leading [m, m] block, exact zeros outside
 int gps_launch_psi_sym_half(gps_handle_t h, const double* X, i64 ldx, i64 m, double* S, i64 mp);
+// dst[i] += full[i] - sum_p own[p][i] for i < cnt, own [P][stride], the parts in part order
+int gps_launch_psi_cross_add(gps_handle_t h, double* dst, const double* full, const double* own, int P, i64 stride, i64 cnt);
 // psi2n [n, m, m] += sum_{p < p'} T_p[n, :, None] T_p'[n, None, :] + its transpose, T [P][n * m]
 int gps_launch_psi2n_cross(gps_handle_t h, const double* T, int P, i64 n, i64 m, double* psi2n);
 // rff.hip : random-feature maps (kernel_kitchen_sink.py) and the contraction of their cotangent; all pointers on the device

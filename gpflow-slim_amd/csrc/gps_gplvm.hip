@@ -47,11 +47,7 @@ static int gplvm_check_prog(gps_handle_t h, const char* who, const gps_kern_node
 // arrays (in = what gplvm_upload always made); the parts of a Sum are packed [*, qp] copies of their columns (dPsiParts).
 struct GplvmPart { int node, qp; PsiDims dims; PsiIn in; double* psi2; };     // psi2 [mp, mp]: this part's Psi2 (the bound)
 
-static PsiIn psi_rows(const PsiIn& in, i64 n0, i64 cnt) {
-  PsiIn s = in;
-  s.Xmu += n0 * in.q; s.Xvar += n0 * in.q; s.A1 += n0 * in.q; s.A2 += n0 * in.q; s.C1 += n0; s.C2 += n0; s.n = cnt;
-  return s;
-}
+static PsiIn psi_rows(const PsiIn& in, i64 n0, i64 cnt) { return gps_psi_rows(in, n0, cnt); }
 
 // The part views of a Sum: per part [Z [m, qp] | Xmu | Xvar | A1 | A2 [n, qp] each | C1 | C2 [n] | par [40]], then (with_psi2)
 // one [mp, mp] matrix per part.  Z is in dX, Xmu and Xvar are at dMu / dVar (gplvm_upload).
@@ -171,6 +167,25 @@ static int gplvm_check_inputs(gps_handle_t h, const char* who, const double* Xva
   for (i64 i = 0; i < n * q; ++i)
     if (!(Xvar[i] > 0.0) && !(allow_zero && Xvar[i] == 0.0))
       return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": the variances of q(x) must be positive");
+  return GPS_OK;
+}
+
+// the common start of the entries on the kernel expectations outside this file (gps_uncond.hip): see gps_common.hpp
+int gps_psi_setup(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes, const double* Z, i64 m, const double* Xmu,
+                  const double* Xvar, i64 n, i64 q, std::vector<PsiPart>* out) {
+  std::vector<int> nodes;
+  int rc = gplvm_check_prog(h, who, prog, n_nodes, q, &nodes);
+  if (rc) return rc;
+  rc = gplvm_check_inputs(h, who, Xvar, n, q, true);
+  if (rc) return rc;
+  rc = begin_inducing_call(h, nullptr);
+  if (rc) return rc;
+  PsiIn in;
+  std::vector<GplvmPart> parts;
+  rc = gplvm_upload(h, prog, nodes, Z, m, Xmu, Xvar, n, q, nullptr, 0, false, &in, nullptr, &parts);
+  if (rc) return rc;
+  out->clear();
+  for (const GplvmPart& pt : parts) out->push_back(PsiPart{pt.node, pt.in});
   return GPS_OK;
 }
 

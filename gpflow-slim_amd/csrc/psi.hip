@@ -1,5 +1,6 @@
 // Kernel expectations of the RBF kernel under q(x_n) = N(mu_n, diag S_n) -- the "psi statistics" of the Bayesian GPLVM
-// (ekernels.py:22-47, 120-149 restricted to diagonal covariances) -- and their vector-Jacobian products.
+// (ekernels.py:22-47, 120-149 restricted to diagonal covariances) -- their vector-Jacobian products, and the contraction of psi2n
+// with weight matrices point by point (the conditional at Gaussian inputs, gps_uncond.hip).
 //   Psi1[n][m]   = var   prod_q (1 +   S_nq / l_q^2)^-1/2 exp(-1/2 sum_q (mu_nq - z_mq)^2 / (l_q^2 + S_nq))
 //   psi2n[m][m'] = var^2 prod_q (1 + 2 S_nq / l_q^2)^-1/2 exp(-sum_q (z_mq - z_m'q)^2 / (4 l_q^2) - sum_q (mu_nq - zbar_q)^2 / (l_q^2 + 2 S_nq))
 // with zbar = (z_m + z_m') / 2; Psi2 = sum_n psi2n.  The exponents are evaluated in this difference form (expanded into a
@@ -321,6 +322,62 @@ __global__ __launch_bounds__(64) void psi2_vjp_z_kernel(const double* __restrict
     if (q < Q) part[((i64)blockIdx.y * Q + q) * ldp + m] = 2.0 * ZB[q];
 }
 
+// ---- contraction of psi2n with symmetric weights (the uncertain conditional, gps_uncond.hip) ------------------------------------
+//   out[b][n] = sum_{m, m'} psi2n_n[m][m'] W_b[m][m']     for B weight matrices, psi2n never stored.
+// PKW[b][m][m'], m' <= m only: (W_b[m][m'] + W_b[m'][m]) / 2 * var^2 exp(-sum_q (z_mq - z_m'q)^2 / (4 l_q^2)), off-diagonal pairs twice.
+// W [B][sw] with leading dimension ldw; blockIdx.z = b.
+__global__ __launch_bounds__(256) void psi_pkw_kernel(const double* __restrict__ Z, const double* __restrict__ par,
+                                                      const double* __restrict__ W, i64 ldw, i64 sw, int M, int Q,
+                                                      double* __restrict__ PKW, i64 ldpk, i64 spk) {
+  const int mc = blockIdx.x * 256 + threadIdx.x, m = blockIdx.y;
+  if (mc > m) return;
+  double s = 0.0;
+  for (int q = 0; q < Q; ++q) {
+    const double l = par[1 + q], dz = Z[(i64)m * Q + q] - Z[(i64)mc * Q + q];
+    s += dz * dz / (4.0 * l * l);
+  }
+  const double* Wb = W + (i64)blockIdx.z * sw;
+  const double w = mc == m ? Wb[(i64)m * ldw + m] : Wb[(i64)m * ldw + mc] + Wb[(i64)mc * ldw + m];
+  PKW[(i64)blockIdx.z * spk + (i64)m * ldpk + mc] = w * par[0] * par[0] * exp(-s);
+}
+
+// The shape of psi2_vjp_n_kernel: thread = point n; blockIdx.y = pair-row chunk (rows m = blockIdx.y, + gridDim.y, ...; pairs
+// m' <= m); blockIdx.z = a group of BT weights, which share one exponential per pair.  part[chunk][b][n].  (m, m', q, b are
+// uniform: z and PKW come through scalar loads.)  A group's last weights beyond B read weight B-1 and are not written.
+template <int QT, int BT>
+__global__ __launch_bounds__(256) void psi2_contract_kernel(const double* __restrict__ Z, const double* __restrict__ Xmu,
+                                                            const double* __restrict__ A2, const double* __restrict__ C2,
+                                                            const double* __restrict__ PKW, i64 ldpk, i64 spk, i64 N, int M, int Q,
+                                                            int B, double* __restrict__ part) {
+  const i64 n = (i64)blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  double mu[QT], a[QT], acc[BT];
+#pragma unroll
+  for (int q = 0; q < QT; ++q) {
+    mu[q] = q < Q ? Xmu[n * Q + q] : 0.0;
+    a[q] = q < Q ? A2[n * Q + q] : 0.0;
+  }
+  const int b0 = blockIdx.z * BT;
+  const double* pk[BT];
+#pragma unroll
+  for (int j = 0; j < BT; ++j) { acc[j] = 0.0; pk[j] = PKW + (i64)(b0 + j < B ? b0 + j : B - 1) * spk; }
+  const double cn = C2[n];
+  for (int m = blockIdx.y; m < M; m += gridDim.y) {
+    for (int mc = 0; mc <= m; ++mc) {
+      double e = 0.0;
+#pragma unroll
+      for (int q = 0; q < QT; ++q)
+        if (q < Q) { const double d = mu[q] - 0.5 * (Z[(i64)m * Q + q] + Z[(i64)mc * Q + q]); e += d * d * a[q]; }
+      const double v = exp(cn - e);
+#pragma unroll
+      for (int j = 0; j < BT; ++j) acc[j] += pk[j][(i64)m * ldpk + mc] * v;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < BT; ++j)
+    if (b0 + j < B) part[((i64)blockIdx.y * B + b0 + j) * N + n] = acc[j];
+}
+
 // The same two passes for <Psi1_bar, dPsi1>, Psi1_bar[n][m] = sum_r Y[n][r] W[m][r] formed on the fly (rank R, never stored).
 // With T = Psi1_bar Psi1, d = mu_nq - z_mq, a = 1 / (l_q^2 + S_nq):
 //   per point: t_n = sum_m T, SA = sum_m T d, SB = sum_m T d^2  ->  mu_bar = -a SA ; S_bar = -a t / 2 + a^2 SB / 2
@@ -552,6 +609,40 @@ int gps_launch_psi2_vjp(gps_handle_t h, const PsiIn& in, const double* PK, i64 l
     GPS_HIP(h, hipGetLastError());
   }
   return fold(h, part_z, (int)nzch, Q, M, ldz, out_z, ldz);
+}
+
+// out [b][ldo] (one plane of n values per weight) <- sum_{m, m'} psi2n_n[m][m'] W_b[m][m'] for the b weights W [b][sw] (leading
+// dimension ldw; only their symmetric parts count).  PKW: room for b * ldpk * ldpk doubles, ldpk >= m; partials in dLikPart.
+int gps_launch_psi2_contract(gps_handle_t h, const PsiIn& in, const double* W, i64 ldw, i64 sw, int b, double* PKW, i64 ldpk,
+                             double* out, i64 ldo) {
+  const i64 N = in.n; const int M = (int)in.m, Q = in.q;
+  if (b < 1 || b > 65535 || ldpk < M || ldo < N) return gps_fail(h, GPS_ERR_ARG, "gps_launch_psi2_contract: bad argument");
+  const i64 spk = ldpk * ldpk;
+  {
+    LaunchScope ls(h, KC_OTHER, 0.5 * b * M * M * (3.0 * Q + 40.0), 12.0 * b * M * M);
+    hipLaunchKernelGGL(psi_pkw_kernel, dim3((unsigned)cdiv(M, 256), (unsigned)M, (unsigned)b), dim3(256), 0, h->stream, in.Z, in.par, W,
+                       ldw, sw, M, Q, PKW, ldpk, spk);
+    GPS_HIP(h, hipGetLastError());
+  }
+  const int pch = (int)clampi(cdiv(131072, N), 1, M);
+  GPS_HIP(h, h->dLikPart.ensure((size_t)pch * b * N * 8));
+  double* part = h->dLikPart.d();
+  {
+    const int bt = b == 1 ? 1 : 4;
+    LaunchScope ls(h, KC_KMAT, 0.5 * N * M * (M + 1.0) * (cdiv(b, bt) * (3.0 * Q + 40.0) + 2.0 * b), 8.0 * pch * b * N);
+    const dim3 grid((unsigned)cdiv(N, 256), (unsigned)pch, (unsigned)cdiv(b, bt));
+#define CALL(QT)                                                                                                                   \
+  do {                                                                                                                             \
+    if (bt == 1) hipLaunchKernelGGL((psi2_contract_kernel<QT, 1>), grid, dim3(256), 0, h->stream, in.Z, in.Xmu, in.A2, in.C2, PKW, \
+                                    ldpk, spk, N, M, Q, b, part);                                                                  \
+    else hipLaunchKernelGGL((psi2_contract_kernel<QT, 4>), grid, dim3(256), 0, h->stream, in.Z, in.Xmu, in.A2, in.C2, PKW, ldpk,   \
+                            spk, N, M, Q, b, part);                                                                                \
+  } while (0)
+    PSI_QT_DISPATCH(Q, CALL);
+#undef CALL
+    GPS_HIP(h, hipGetLastError());
+  }
+  return fold(h, part, pch, b, N, N, out, ldo);
 }
 
 // the same for <Y W^T, dPsi1>: Y [n][r], Yt [r][ldy], Wt [r][ldw] on the device

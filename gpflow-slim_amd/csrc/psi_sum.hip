@@ -74,6 +74,24 @@ __global__ __launch_bounds__(256) void psi2n_cross_kernel(const double* __restri
   psi2n[(n * M + a) * M + b] += s;
 }
 
+// dst[i] += full[i] - sum_p own[p][i], the parts in part order: the cross terms' share of sum_{m, m'} psi2n_n[m][m'] W[m][m'],
+// full = rowdot(T, T W) with T = sum_p T_p and own[p] = rowdot(T_p, T_p W)
+__global__ __launch_bounds__(256) void psi_cross_add_kernel(double* __restrict__ dst, const double* __restrict__ full,
+                                                            const double* __restrict__ own, int P, i64 stride, i64 cnt) {
+  const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+  if (i >= cnt) return;
+  double s = 0.0;
+  for (int p = 0; p < P; ++p) s += own[(i64)p * stride + i];
+  dst[i] += full[i] - s;
+}
+
+int gps_launch_psi_cross_add(gps_handle_t h, double* dst, const double* full, const double* own, int P, i64 stride, i64 cnt) {
+  LaunchScope ls(h, KC_OTHER, (P + 2.0) * cnt, 8.0 * (P + 3.0) * cnt);
+  hipLaunchKernelGGL(psi_cross_add_kernel, dim3((unsigned)cdiv(cnt, 256)), dim3(256), 0, h->stream, dst, full, own, P, stride, cnt);
+  GPS_HIP(h, hipGetLastError());
+  return GPS_OK;
+}
+
 int gps_launch_psi_gather(gps_handle_t h, const double* src, i64 rows, int q, const PsiDims& dims, int qp, double* dst) {
   LaunchScope ls(h, KC_OTHER, 0.0, 16.0 * rows * qp);
   hipLaunchKernelGGL(psi_gather_kernel, dim3((unsigned)cdiv(rows * qp, 256)), dim3(256), 0, h->stream, src, rows, q, dims, qp, dst);

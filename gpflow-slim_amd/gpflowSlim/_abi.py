@@ -212,6 +212,8 @@ _SIGNATURES = {
     "gps_psi_sum_set_chunk": [_vp, _i64],
     "gps_bgplvm": _GPLVM + [_dbl, _dbl, _dp, _i64, _dp, _i64, _int, _dp, _dp, _dp, _ip],
     "gps_bgplvm_grad": _GPLVM + [_dbl, _dbl, _dp, _i64, _dp, _dp, _int, _ip, _dp, _dp, _dp, _dp, _ip],
+    "gps_psi2_contract": _GPLVM + [_dp, _i64, _dp],
+    "gps_uncertain_conditional": _GPLVM + [_dbl, _dp, _i64, _dp, _int, _int, _int, _dp, _dp, _ip],
     "gps_rff_features": [_vp, _rff, _dp, _i64, _dp],
     "gps_rff_gram": [_vp, _rff, _dp, _i64, _dp, _i64, _dp, _dp],
     "gps_rff_lml": [_vp, _rff, _dp, _i64, _dbl, _dp, _i64, _i64, _dp, _ip],

@@ -90,7 +90,7 @@ class Handle(object):
     tests/test_gpu_residency.py):
 
       drops X and factor   release_buffers, gpr_set_data, conditional, base_conditional, svgp_elbo*, sgpr, sgpr_grad,
-                           psi_stats, bgplvm*, rff_features, rff_gram, rff_lml*, rff_predict(refactor), kron_cg, kgpr_lml*,
+                           psi_stats, psi2_contract, uncertain_conditional, bgplvm*, rff_features, rff_gram, rff_lml*, rff_predict(refactor), kron_cg, kgpr_lml*,
                            gpmc_lik*, sgpmc_lik*
       drops the factor     gpr_lml, gpr_lml_grad, gpr_predict(refactor), dist_begin, dist_lml, dist_lml_grad
       keeps both           kmat, potrf, trsm_lower, kmat_vjp, kmat_input_vjp (scratch: dXnew, dTmp*), gauss_kl (dS2-dS4),
@@ -730,6 +730,43 @@ class Handle(object):
         self._drop_resident()
         self._call("gps_psi_stats", prog, len(prog), _ptr(Z), m, _ptr(Xmu), _ptr(Xvar), n, q, _opt(p1), _opt(p2), _opt(p2n))
         return p1, p2, p2n
+
+    def psi2_contract(self, prog, Z, Xmu, Xvar, W):
+        """gps_psi2_contract: out [N, B], out[n, b] = sum_{m, m'} eKzxKxz[n, m, m'] W[b, m, m'] for W [B, M, M] (or one [M, M]
+        matrix: out [N]); only the symmetric part of each W counts.  eKzxKxz [N, M, M] is never formed; prog as for psi_stats."""
+        Z, Xmu, Xvar = self._psi_args(Z, Xmu, Xvar)
+        W = _f64(W)
+        (m, q), n = Z.shape, Xmu.shape[0]
+        single = W.ndim == 2
+        if single:
+            W = W[None]
+        _need(W.ndim == 3 and W.shape[0] > 0 and W.shape[1:] == (m, m), "W must be [B, M, M] or [M, M]")
+        W = _f64(W)
+        out = np.empty((n, W.shape[0]))
+        self._drop_resident()
+        self._call("gps_psi2_contract", prog, len(prog), _ptr(Z), m, _ptr(Xmu), _ptr(Xvar), n, q, _ptr(W), W.shape[0], _ptr(out))
+        return out[:, 0].copy() if single else out
+
+    def uncertain_conditional(self, prog, Z, Xmu, Xvar, q_mu, q_sqrt, jitter, white=False, full_cov_output=False):
+        """gps_uncertain_conditional: (fmean [N, K], fvar [N, K] or, full_cov_output, [N, K, K]) of f(x_n), x_n ~ N(Xmu_n, diag
+        Xvar_n), under q(u) = N(q_mu, q_sqrt q_sqrt^T) at Z; prog as for psi_stats, q_sqrt [M, K] or [M, M, K] as conditional."""
+        Z, Xmu, Xvar = self._psi_args(Z, Xmu, Xvar)
+        q_mu = _f64(q_mu)
+        (m, q), n = Z.shape, Xmu.shape[0]
+        _need(q_mu.ndim == 2 and q_mu.shape[0] == m and q_mu.shape[1] > 0, "q_mu must be [M, K]")
+        k = q_mu.shape[1]
+        qs, qnd = self._prep_q_sqrt(q_sqrt)
+        if qs is None:
+            raise ValueError("uncertain_conditional needs q_sqrt")
+        self._check_q_sqrt(qs, qnd, m, k)
+        fmean = np.empty((n, k))
+        fvar = np.empty((n, k, k) if full_cov_output else (n, k))
+        info = ctypes.c_int(0)
+        self._drop_resident()
+        self._call("gps_uncertain_conditional", prog, len(prog), _ptr(Z), m, _ptr(Xmu), _ptr(Xvar), n, q, float(jitter), _ptr(q_mu),
+                   k, _ptr(qs), qnd, 1 if white else 0, 1 if full_cov_output else 0, _ptr(fmean), _ptr(fvar), _byref(info))
+        _raise_if_not_pd(info, _PD_ORDER)
+        return fmean, fvar
 
     def bgplvm(self, prog, Z, Xmu, Xvar, Y, jitter, noise_var, Xnew=None, full_cov=False, want_bound=True):
         """gps_bgplvm: (bound without the KL term, mean [N*, R], var [N*] or [N*, N*]); prog as for psi_stats."""

@@ -4,7 +4,8 @@ Implemented: ``RBF`` (ARD or isotropic, over all input dimensions in order) and 
 pairwise disjoint ``active_dims`` (slices or index lists), with diagonal covariances given as ``[N, Q]`` -- ekernels.py:13-47,
 120-149 and the separate-dimensions branch 224-249, restricted to diagonal ``Xcov``.  The expectations run on the GPU (csrc/psi.hip,
 csrc/psi_sum.hip, gps_psi_stats); Psi2 = sum_n eKzxKxz is evaluated without the reference's [N, Q, M, M] temporary, and for a Sum
-without any [N, M] array (``eKzxKxz_sum``).  Full ``[N, Q, Q]`` covariances, a stand-alone ``RBF`` on an ``active_dims`` subset,
+without any [N, M] array (``eKzxKxz_sum``); ``eKzxKxz_contract`` contracts eKzxKxz with weight matrices point by point without
+storing it (gps_psi2_contract: what conditionals.uncertain_conditional rests on).  Full ``[N, Q, Q]`` covariances, a stand-alone ``RBF`` on an ``active_dims`` subset,
 ``Linear`` / ``Product`` kernels, sums with overlapping parts (the quadrature fall-back), and ``exKxz*`` raise
 ``NotImplementedError``.
 """
@@ -53,6 +54,12 @@ class RBF(kernels.RBF):
     def eKzxKxz_sum(self, Z, Xmu, Xcov):
         """Psi2 = sum_n eKzxKxz, [M, M], in O(M^2) device memory; exactly symmetric and bitwise reproducible."""
         return self._psi(Z, Xmu, Xcov, want_psi2=True)[1]
+
+    def eKzxKxz_contract(self, Z, Xmu, Xcov, W):
+        """sum_{m, m'} eKzxKxz[n, m, m'] W[b, m, m'], [N, B] for W [B, M, M] ([N] for one [M, M] matrix), without forming
+        eKzxKxz; only the symmetric part of each W counts.  Bitwise reproducible."""
+        prog, Xvar = self._psi_program(Xmu), _diag_cov(Xcov)
+        return be.get_handle().psi2_contract(prog, Z, Xmu, Xvar, W)
 
     def exKxz(self, Z, Xmu, Xcov):
         raise NotImplementedError("exKxz is not implemented")
@@ -124,6 +131,7 @@ class Sum(kernels.Sum):
     eKxz = RBF.eKxz
     eKzxKxz = RBF.eKzxKxz
     eKzxKxz_sum = RBF.eKzxKxz_sum
+    eKzxKxz_contract = RBF.eKzxKxz_contract
     exKxz = RBF.exKxz
     exKxz_pairwise = RBF.exKxz_pairwise
 

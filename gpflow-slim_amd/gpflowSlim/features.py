@@ -38,6 +38,14 @@ class InducingPoints(InducingFeature):
         """features.py:79-81"""
         return kern.K(self.Z, Xnew)
 
+    def eKfu(self, kern, mean, cov):
+        """features.py:83-84: <K(x, Z)> under x_n ~ N(mean_n, diag cov_n), [N, M]"""
+        return kern.eKxz(self.Z, mean, cov)
+
+    def eKufKfu(self, kern, mean, cov):
+        """features.py:86-87: <K(Z, x) K(x, Z)> point by point, [N, M, M] (small sizes: see ekernels.RBF.eKzxKxz_contract)"""
+        return kern.eKzxKxz(self.Z, mean, cov)
+
 
 @singledispatch
 def conditional(feat, kern, Xnew, f, *, full_cov=False, q_sqrt=None, white=False):

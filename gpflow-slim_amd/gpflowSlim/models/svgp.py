@@ -187,3 +187,14 @@ class SVGP(GPModel):
         mu, var = features.conditional(self.feature, self.kern, Xnew, self.q_mu, q_sqrt=self.q_sqrt,
                                        full_cov=full_cov, white=self.whiten)
         return mu + self.mean_function(Xnew), var
+
+    def predict_f_uncertain(self, Xnew_mu, Xnew_var, full_cov_output=False):
+        """Mean [N, K] and variance ([N, K], or [N, K, K] with full_cov_output) of f(x_n) for x_n ~ N(Xnew_mu_n, diag Xnew_var_n):
+        conditionals.uncertain_conditional on the model's own (Z, q_mu, q_sqrt, whiten).  The kernel must be an ekernels.RBF or
+        ekernels.Sum; a mean function other than Zero would need its own moments under q(x) and is refused."""
+        from .. import conditionals
+        from ..mean_functions import Zero
+        if not isinstance(self.mean_function, Zero):
+            raise NotImplementedError("predict_f_uncertain is implemented for the Zero mean function only")
+        return conditionals.uncertain_conditional(Xnew_mu, Xnew_var, self.feature, self.kern, self.q_mu, self.q_sqrt,
+                                                  full_cov_output=full_cov_output, white=self.whiten)

@@ -517,6 +517,25 @@ int gps_bgplvm_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, co
                     const double* Y, int64_t r, double* bound, double* grad_slots, int n_slots_cap, int* n_slots_out,
                     double* grad_noise, double* grad_Z, double* grad_Xmu, double* grad_Xvar, int* info);
 
+/* ---- the conditional at Gaussian inputs (conditionals.py:125-203) and the contraction it rests on ----------------------
+ * Scope of prog, Z, Xmu, Xvar exactly as gps_psi_stats.  Neither entry ever holds eKzxKxz [n, m, m] or an [n, m] array beyond one
+ * chunk of points (gps_psi_sum_set_chunk), and every sum runs in a fixed order: results are bitwise identical from run to run.
+ *
+ * gps_psi2_contract: out host [n, b], out[i][j] = sum_{a, c} eKzxKxz[i][a][c] W[j][a][c] for the b matrices W host [b, m, m]; only
+ * the symmetric part of each counts.                                                                                   */
+int gps_psi2_contract(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
+                      const double* Xmu, const double* Xvar, int64_t n, int64_t q,
+                      const double* W, int64_t b, double* out);
+/* gps_uncertain_conditional: mean and variance of f(x_i), x_i ~ N(Xmu_i, diag Xvar_i), under q(u) = N(q_mu, q_sqrt q_sqrt^T) at the
+ * inducing points Z.  q_mu host [m, k]; q_sqrt host [m, k] (q_sqrt_ndim 2: diagonal) or [k, m, m] (3: lower triangles), as
+ * gps_conditional; white: q(u) is given for v = L^-1 u, L = chol(Kuu + jitter I).  fmean host [n, k]; fvar host [n, k], or
+ * [n, k, k] with full_cov_output (exactly symmetric).  k <= 128, and k <= 16 with full_cov_output: GPS_ERR_UNSUPPORTED beyond.
+ * Device memory: O(m^2) per weight matrix, 8 at a time, plus the outputs.  info > 0: Kuu + jitter I met a non-positive pivot. */
+int gps_uncertain_conditional(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
+                              const double* Xmu, const double* Xvar, int64_t n, int64_t q, double jitter,
+                              const double* q_mu, int64_t k, const double* q_sqrt, int q_sqrt_ndim, int white,
+                              int full_cov_output, double* fmean, double* fvar, int* info);
+
 /* GP regression with the FITC approximation: models.GPRFITC._build_likelihood / _build_predict
  * (models/sgpr.py:229-318: Luu = chol(Kuu), V = Luu^-1 Kuf, nu = Kdiag - colsumsq(V) + sigma^2,
  * L = chol(I + (V/nu) V^T), gamma = L^-1 V (err/nu)).  Same arguments, layouts and outputs as gps_sgpr;
