@@ -524,7 +524,7 @@ int gps_launch_scale_add_eye(gps_handle_t h, double* B, i64 ldb, i64 n, i64 n_re
 int gps_launch_var_finish(gps_handle_t h, double* var, const double* kdiag_or_null,
                           double kdiag_const, const double* sumsq, i64 n);
 // lik.hip : variational expectations of the non-Gaussian likelihoods and the pieces of their backward pass
-struct LikHost { double raw[8 + 2 * GPS_LIK_MAX_GH]; };      // the descriptor as the kernels take it (opaque outside lik.hip)
+struct LikHost { double raw[8 + 2 * GPS_LIK_MAX_GH + GPS_LIK_MAX_EDGES]; };      // the descriptor as the kernels take it (opaque outside lik.hip)
 int gps_lik_prepare(gps_handle_t h, const gps_lik_t* lik, i64 k, LikHost* out);
 int gps_lik_launch(gps_handle_t h, const LikHost* L, const double* fmu, const double* mean, const double* fvar, i64 v_si, i64 v_sq,
                    const double* Y, i64 n, i64 k, int want_grad, double oscale, double* dmu, double* dvar, i64 o_si, i64 o_sq,

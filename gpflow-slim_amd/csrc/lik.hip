@@ -6,17 +6,26 @@
 //                      dmu = sum_h w_h l'(f_h) ;  dvar = sum_h w_h l'(f_h) x_h / sqrt(2 var)     (autodiff through :147)
 //   closed forms       Poisson / Exponential with the exp link                                       (:220-224, :240-243)
 //   MultiClass         p log(1 - eps) + (1 - p) log(eps / (K - 1)),  p = RobustMax.prob_is_largest     (:404-425, :449-454)
+//   Gamma              closed form with the exp link, the shape a trainable                               (:301-333)
+//   Beta               quadrature of densities.beta(m s, s - m s, y), m = probit(f), the scale s trainable  (:336-376)
+//   Ordinal            quadrature of log(probit(a_y / sigma - f / sigma) - probit(a_{y-1} / sigma - f / sigma) + 1e-6), sigma
+//                      trainable, a = the table of bin edges with a_{-1} = -inf and a_{n_edges} = +inf          (:554-631)
 // The Gauss-Hermite rule travels BY VALUE in the kernel arguments: the nodes are wave-uniform, indexed by a uniform loop
 // counter, so the compiler reads them with scalar loads from the kernarg segment -- no per-lane global loads, no
-// __constant__ symbol shared between handles.  Sums over the points: one partial per workgroup, added up on the host in
-// index order (no floating-point atomics: the bound is bit-reproducible run to run).
+// __constant__ symbol shared between handles.  Ordinal's edge table travels the same way (1328 bytes of arguments in all,
+// far below the 4 KB limit); it is indexed by the point's label, once per point and outside the node loop.  Sums over the
+// points: one partial per workgroup, added up on the host in index order (no floating-point atomics: the bound is
+// bit-reproducible run to run).
 #include "gps_common.hpp"
+#include "lik_math.hpp"
 
 struct LikDev {
-  int kind, n_gh, n_class, pad_;
-  double p[4];                       // kind parameters (see gps_lik_t); STUDENT_T: p[2] = the constant of densities.student_t
+  int kind, n_gh, n_class, n_edges;
+  double p[4];                       // kind parameters (see gps_lik_t); STUDENT_T: p[2] = the constant of densities.student_t;
+                                     // GAMMA / BETA: p[2] = lgamma(p[0]), p[3] = digamma(p[0])
   double x[GPS_LIK_MAX_GH];          // hermgauss nodes
   double w[GPS_LIK_MAX_GH];          // hermgauss weights / sqrt(pi)
+  double edges[GPS_LIK_MAX_EDGES];   // ORDINAL: the bin edges, strictly increasing; [n_edges ..) zero
 };
 
 // strided views: element (i, q) of a moment array at  i * si + q * sq  ([n, k] row-major: (k, 1); k planes of n: (1, n))
@@ -31,10 +40,62 @@ __device__ __forceinline__ double lik_wave_sum(double v) {
 #define LIK_SQRT1_2   0.70710678118654752440
 #define LIK_INV_S2PI  0.39894228040143267794     // 1 / sqrt(2 pi)
 
-// log p(y | f) and d/df (and d/dscale for Student-t) of the quadrature kinds
+#define LIK_SQUASH    (1.0 - 2e-3)               // the probit's squash (likelihoods.py:270): Phi (1 - 2e-3) + 1e-3
+
+// What a quadrature kind needs of a point's target, worked out once outside the node loop.
+//   BETA      a = log(yc), b = log(1 - yc), yc = y clipped to [1e-6, 1 - 1e-6]                       (densities.py:60-66)
+//   ORDINAL   a = edges[y] / sigma (+inf for the top label), b = edges[y - 1] / sigma (-inf for label 0)   (:600-603); the
+//             label is clamped into [0, n_edges] first, so that no value of Y -- NaN included -- indexes outside the table
+struct LikTarget { double y, a, b; };
 template <int KIND>
-__device__ __forceinline__ void lik_logp(const LikDev& L, double f, double y, double& lp, double& dlp, double& dpar) {
-  if (KIND == GPS_LIK_BERNOULLI) {
+__device__ __forceinline__ LikTarget lik_target(const LikDev& L, double y) {
+  LikTarget t{y, 0.0, 0.0};
+  if (KIND == GPS_LIK_BETA) {
+    const double yc = fmin(fmax(y, 1e-6), 1.0 - 1e-6);
+    t.a = log(yc); t.b = log(1.0 - yc);
+  } else if (KIND == GPS_LIK_ORDINAL) {
+    const int j = (int)fmin(fmax(y, 0.0), (double)L.n_edges);          // (fmax(NaN, 0) = 0)
+    t.a = j < L.n_edges ? L.edges[j] / L.p[0] : INFINITY;
+    t.b = j > 0 ? L.edges[j - 1] / L.p[0] : -INFINITY;
+  }
+  return t;
+}
+
+// log p(y | f) and d/df (and d/d param[0]: the Student-t scale, the Beta scale, the Ordinal sigma) of the quadrature kinds
+template <int KIND>
+__device__ __forceinline__ void lik_logp(const LikDev& L, double f, const LikTarget& t, double& lp, double& dlp, double& dpar) {
+  const double y = t.y;
+  if (KIND == GPS_LIK_BETA) {
+    // :365-369 and densities.beta; alpha, beta >= 1e-3 s > 0 through the squash.  lgamma(alpha + beta) = lgamma(s) = p[2].
+    const double s = L.p[0];
+    const double m = 0.5 * (1.0 + erf(f * LIK_SQRT1_2)) * LIK_SQUASH + 1e-3;
+    const double dm = LIK_SQUASH * LIK_INV_S2PI * exp(-0.5 * f * f);
+    const double alpha = m * s, beta = s - alpha;
+    lp = (alpha - 1.0) * t.a + (beta - 1.0) * t.b + L.p[2] - lgamma(alpha) - lgamma(beta);
+    const double pa = digamma(alpha), pb = digamma(beta);
+    dlp = s * dm * (t.a - t.b - pa + pb);
+    dpar = m * t.a + (1.0 - m) * t.b + L.p[3] - m * pa - (1.0 - m) * pb;
+  } else if (KIND == GPS_LIK_ORDINAL) {
+    // :598-606.  An infinite edge has probit(+-inf) and contributes exactly zero to both derivatives: its z is replaced by 0
+    // and its terms are dropped by selects (inf * 0 would be NaN); no lane branches.
+    const double s = L.p[0], fs = f / s;
+    const bool top = t.a == INFINITY, bot = t.b == -INFINITY;
+    const double zl = top ? 0.0 : t.a - fs, zr = bot ? 0.0 : t.b - fs;
+    // probit(zl) - probit(zr) = (1 - 2e-3) (Phi(zl) - Phi(zr)): the 1e-3 of the squash cancels.  Taken as written, two numbers
+    // near 1 (or near 1e-3) are subtracted where the point lies in a far tail of its bin, and their rounding, eps / 2 each, is
+    // then all that stands next to the 1e-6 floor: 1e-10 relative in P, in log P and in every derivative (each carries 1 / P),
+    // and 707 times that in dvar at var = 1e-6.  Taken on the side where both Phi are small, as a difference of two erfc, it is
+    // the same number to a few eps of ITSELF:  up (both z mostly positive): (erfc(zr / sqrt 2) - erfc(zl / sqrt 2)) / 2, else
+    // (erfc(-zl / sqrt 2) - erfc(-zr / sqrt 2)) / 2.  An infinite edge is always the second term, which is then exactly 0.
+    const bool up = top || (!bot && zl + zr > 0.0);
+    const double ea = erfc((up ? zr : -zl) * LIK_SQRT1_2);
+    const double eb = (top || bot) ? 0.0 : erfc((up ? zl : -zr) * LIK_SQRT1_2);
+    const double nl = top ? 0.0 : LIK_INV_S2PI * exp(-0.5 * zl * zl), nr = bot ? 0.0 : LIK_INV_S2PI * exp(-0.5 * zr * zr);
+    const double P = LIK_SQUASH * (0.5 * (ea - eb)) + 1e-6;
+    lp = log(P);
+    dlp = -(1.0 / s) * LIK_SQUASH * (nl - nr) / P;
+    dpar = LIK_SQUASH * (-nl * zl + nr * zr) / (s * P);            // d z / d sigma = -z / sigma
+  } else if (KIND == GPS_LIK_BERNOULLI) {
     // probit (likelihoods.py:269-270) ; densities.bernoulli: log(where(y == 1, p, 1 - p))
     const double p = 0.5 * (1.0 + erf(f * LIK_SQRT1_2)) * (1.0 - 2e-3) + 1e-3;
     const double dp = (1.0 - 2e-3) * LIK_INV_S2PI * exp(-0.5 * f * f);
@@ -84,13 +145,19 @@ __global__ __launch_bounds__(256) void lik_elem_kernel(const LikDev L, const dou
       const double ex = exp(-mu + var / 2) * y;
       ve = -ex - mu;
       gm = ex - 1.0; gv = -0.5 * ex;
+    } else if (KIND == GPS_LIK_GAMMA) {                // :328-331
+      const double a = L.p[0], ly = log(y);
+      const double ex = y * exp(-mu + var / 2);
+      ve = -a * mu - L.p[2] + (a - 1.0) * ly - ex;
+      gm = -a + ex; gv = -0.5 * ex; gp = -mu - L.p[3] + ly;
     } else {                                           // Gauss-Hermite, :140-152
       const double sd = sqrt(2.0 * var);
+      const LikTarget t = lik_target<KIND>(L, y);
       ve = 0.0; gm = 0.0; gv = 0.0;
       for (int hh = 0; hh < L.n_gh; ++hh) {
         const double xh = L.x[hh], wh = L.w[hh];
         double lp, dlp, dpar;
-        lik_logp<KIND>(L, xh * sd + mu, y, lp, dlp, dpar);
+        lik_logp<KIND>(L, xh * sd + mu, t, lp, dlp, dpar);
         ve += lp * wh;
         if (GRAD) { gm += dlp * wh; gv += dlp * wh * xh; gp += dpar * wh; }
       }
@@ -111,7 +178,7 @@ __global__ __launch_bounds__(256) void lik_elem_kernel(const LikDev L, const dou
 }
 
 // log p(y | f) itself at f = F + mean, no q(f): the likelihood of the MCMC models (models/gpmc.py:75-77), one thread per (point,
-// latent).  Bernoulli and Student-t are lik_logp; the other three are the closed forms above at fvar = 0, written out (the
+// latent).  Bernoulli, Student-t, Beta and Ordinal are lik_logp; the other four are the closed forms above at fvar = 0, written out (the
 // quadrature path at fvar = 0 would divide by sqrt(2 var), and its weights do not add up to exactly 1).  F and G = d log p / d F
 // through strided views, so they can stay planes [k][ld] between the triangular products of gps_gpmc.hip.
 template <int KIND>
@@ -143,8 +210,13 @@ __global__ __launch_bounds__(256) void lik_point_kernel(const LikDev L, const do
       const double ex = exp(-f) * y;
       lp = -ex - f;
       g = ex - 1.0;
+    } else if (KIND == GPS_LIK_GAMMA) {                // densities.gamma(a, exp(f), y), :319
+      const double a = L.p[0], ly = log(y);
+      const double ex = y * exp(-f);
+      lp = -a * f - L.p[2] + (a - 1.0) * ly - ex;
+      g = -a + ex; gp = -f - L.p[3] + ly;
     } else {
-      lik_logp<KIND>(L, f, y, lp, g, gp);
+      lik_logp<KIND>(L, f, lik_target<KIND>(L, y), lp, g, gp);
     }
     s_lp += lp; s_dp += gp;
     if (G) G[i * gv.si + q * gv.sq] = g;
@@ -320,8 +392,29 @@ int gps_lik_prepare(gps_handle_t h, const gps_lik_t* lik, i64 k, LikHost* out) {
   memset(out, 0, sizeof(LikHost));
   L.kind = lik->kind; L.n_gh = 0; L.n_class = (int)k;
   for (int j = 0; j < 4; ++j) L.p[j] = lik->param[j];
-  const bool quad = lik->kind == GPS_LIK_BERNOULLI || lik->kind == GPS_LIK_STUDENT_T || lik->kind == GPS_LIK_MULTICLASS;
+  const bool quad = lik->kind == GPS_LIK_BERNOULLI || lik->kind == GPS_LIK_STUDENT_T || lik->kind == GPS_LIK_MULTICLASS ||
+                    lik->kind == GPS_LIK_BETA || lik->kind == GPS_LIK_ORDINAL;
   switch (lik->kind) {
+    case GPS_LIK_GAMMA:
+      if (!(L.p[0] > 0.0) || !std::isfinite(L.p[0])) return gps_fail(h, GPS_ERR_ARG, "likelihood: the Gamma shape must be positive");
+      L.p[2] = lgamma(L.p[0]); L.p[3] = digamma(L.p[0]);
+      break;
+    case GPS_LIK_BETA:
+      if (!(L.p[0] > 0.0) || !std::isfinite(L.p[0])) return gps_fail(h, GPS_ERR_ARG, "likelihood: the Beta scale must be positive");
+      L.p[2] = lgamma(L.p[0]); L.p[3] = digamma(L.p[0]);
+      break;
+    case GPS_LIK_ORDINAL:
+      if (!(L.p[0] > 0.0) || !std::isfinite(L.p[0])) return gps_fail(h, GPS_ERR_ARG, "likelihood: the Ordinal sigma must be positive");
+      if (lik->n_edges < 1 || lik->n_edges > GPS_LIK_MAX_EDGES || !lik->edges)
+        return gps_fail(h, GPS_ERR_ARG, "likelihood: Ordinal needs 1..32 bin edges (n_edges, edges)");
+      for (int j = 0; j < lik->n_edges; ++j) {
+        // (a table that is not increasing makes probit(left) - probit(right) + 1e-6 negative: the logarithm of a negative number)
+        if (!std::isfinite(lik->edges[j]) || (j > 0 && !(lik->edges[j] > lik->edges[j - 1])))
+          return gps_fail(h, GPS_ERR_ARG, "likelihood: the Ordinal bin edges must be finite and strictly increasing");
+        L.edges[j] = lik->edges[j];
+      }
+      L.n_edges = lik->n_edges;
+      break;
     case GPS_LIK_GAUSSIAN: if (!(L.p[0] > 0.0)) return gps_fail(h, GPS_ERR_ARG, "likelihood: the Gaussian variance must be positive"); break;
     case GPS_LIK_BERNOULLI: case GPS_LIK_EXPONENTIAL: break;
     case GPS_LIK_POISSON: if (!(L.p[0] > 0.0)) return gps_fail(h, GPS_ERR_ARG, "likelihood: the Poisson binsize must be positive"); break;
@@ -379,6 +472,9 @@ int gps_lik_launch(gps_handle_t h, const LikHost* LH, const double* fmu, const d
       case GPS_LIK_POISSON: LIK_GO(GPS_LIK_POISSON); break;
       case GPS_LIK_EXPONENTIAL: LIK_GO(GPS_LIK_EXPONENTIAL); break;
       case GPS_LIK_STUDENT_T: LIK_GO(GPS_LIK_STUDENT_T); break;
+      case GPS_LIK_GAMMA: LIK_GO(GPS_LIK_GAMMA); break;
+      case GPS_LIK_BETA: LIK_GO(GPS_LIK_BETA); break;
+      case GPS_LIK_ORDINAL: LIK_GO(GPS_LIK_ORDINAL); break;
       default: return gps_fail(h, GPS_ERR_ARG, "likelihood: unknown kind");
     }
 #undef LIK_GO
@@ -417,6 +513,9 @@ int gps_lik_point_launch(gps_handle_t h, const LikHost* LH, const double* F, i64
       case GPS_LIK_POISSON: LIK_GO(GPS_LIK_POISSON); break;
       case GPS_LIK_EXPONENTIAL: LIK_GO(GPS_LIK_EXPONENTIAL); break;
       case GPS_LIK_STUDENT_T: LIK_GO(GPS_LIK_STUDENT_T); break;
+      case GPS_LIK_GAMMA: LIK_GO(GPS_LIK_GAMMA); break;
+      case GPS_LIK_BETA: LIK_GO(GPS_LIK_BETA); break;
+      case GPS_LIK_ORDINAL: LIK_GO(GPS_LIK_ORDINAL); break;
       default: return gps_fail(h, GPS_ERR_ARG, "likelihood: unknown kind");
     }
 #undef LIK_GO

@@ -41,7 +41,9 @@ class LikDesc(ctypes.Structure):
                 ("n_gh", ctypes.c_int),
                 ("param", ctypes.c_double * 4),
                 ("gh_x", ctypes.POINTER(ctypes.c_double)),
-                ("gh_w", ctypes.POINTER(ctypes.c_double))]
+                ("gh_w", ctypes.POINTER(ctypes.c_double)),
+                ("n_edges", ctypes.c_int),
+                ("edges", ctypes.POINTER(ctypes.c_double))]
 
 
 class RffDesc(ctypes.Structure):
@@ -77,13 +79,22 @@ def make_rff(kind, input_dim, n_components, variance=1.0, ls=None, omega=None, o
 
 
 LIK_MAX_GH = 64
+LIK_MAX_EDGES = 32
 LIK_MULTICLASS = 5
+LIK_ORDINAL = 8
 
 
-def make_lik(kind, params=(), n_gh=20):
+def make_lik(kind, params=(), n_gh=20, edges=None):
     """A gps_lik_t (and the arrays it points into, which the caller keeps alive): kind of include/gpflowslim_hip.h, up to four
-    scalar parameters, and the Gauss-Hermite rule computed here exactly as the reference does (numpy's hermgauss)."""
+    scalar parameters, the Gauss-Hermite rule computed here exactly as the reference does (numpy's hermgauss) and, for
+    Ordinal, the table of bin edges (1..32 of them)."""
     params = [float(v) for v in params]
+    if edges is not None:
+        edges = np.ascontiguousarray(edges, dtype=np.float64).ravel()
+        if not 1 <= edges.size <= LIK_MAX_EDGES:
+            raise ValueError("the device Ordinal likelihood takes 1..%d bin edges, got %d" % (LIK_MAX_EDGES, edges.size))
+    elif int(kind) == LIK_ORDINAL:
+        raise ValueError("the Ordinal likelihood needs its bin edges")
     if len(params) > 4:
         raise ValueError("a likelihood has at most four scalar parameters")
     if not 1 <= int(n_gh) <= LIK_MAX_GH:
@@ -95,7 +106,10 @@ def make_lik(kind, params=(), n_gh=20):
     for i in range(4):
         d.param[i] = params[i] if i < len(params) else 0.0
     d.gh_x, d.gh_w = gx.ctypes.data_as(_c_double_p), gw.ctypes.data_as(_c_double_p)
-    return d, (gx, gw)
+    if edges is None:
+        return d, (gx, gw)
+    d.n_edges, d.edges = int(edges.size), edges.ctypes.data_as(_c_double_p)
+    return d, (gx, gw, edges)
 
 
 def make_program(nodes):

@@ -15,7 +15,7 @@ from ._abi import (GPS_MAX_DIMS, GPS_MAX_NODES, GPS_MAX_STACK,                  
                    K_RBF, K_MATERN12, K_MATERN32, K_MATERN52, K_PERIODIC, K_WHITE, K_CONSTANT, K_EXPONENTIAL,
                    K_SQDIST, K_EUCLID, K_RATQUAD, K_LINEAR, K_POLYNOMIAL, K_COSINE, K_ARCCOSINE, K_ADD, K_MUL,
                    K_NKN_LINROW, K_NKN_PRODUCT, K_NKN_ACT, KernNode, LikDesc, RffDesc,
-                   RFF_RBF, RFF_LINEAR, RFF_CONSTANT, RFF_EXPLICIT, LIK_MAX_GH, LIK_MULTICLASS,
+                   RFF_RBF, RFF_LINEAR, RFF_CONSTANT, RFF_EXPLICIT, LIK_MAX_GH, LIK_MAX_EDGES, LIK_MULTICLASS, LIK_ORDINAL,
                    make_rff, make_lik, make_program, primitive_node, op_node, psi2_chunking, psi_sum_chunking,
                    _SIGNATURES, EXPORTED_SYMBOLS, ALLREDUCE_FN, _c_double_p, _c_int_p, _i64,
                    lib_path, load_library, comm_load, comm_unique_id, comm_version)
@@ -54,6 +54,14 @@ def _need(cond, msg):
 
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _need_ordinal_labels(desc, Y):
+    """Ordinal: the labels index the table of bin edges, so they are checked here, before any device call (the kernels clamp
+    them, which keeps a bad label from reading outside the table but not from being wrong)."""
+    if desc.kind == LIK_ORDINAL:
+        _need(bool(np.all(np.isfinite(Y)) and np.all(Y == np.floor(Y)) and Y.min() >= 0 and Y.max() <= desc.n_edges),
+              "Ordinal labels must be integers in [0, %d] (the number of bin edges)" % desc.n_edges)
 
 
 def _ptr(a):
@@ -966,6 +974,7 @@ class Handle(object):
         n, k = Fmu.shape
         _need(n > 0 and k > 0, "empty moments")
         _need(Y.size == (n if desc.kind == LIK_MULTICLASS else n * k), "Y must be [N, K] (one label per point for MultiClass)")
+        _need_ordinal_labels(desc, Y)
         ve, dpar = ctypes.c_double(0), ctypes.c_double(0)
         dmu = np.zeros((n, k)) if want_grad else None
         dvar = np.zeros((n, k)) if want_grad else None
@@ -985,6 +994,7 @@ class Handle(object):
             _need(np.all(Y == np.floor(Y)) and Y.min() >= 0 and Y.max() < k, "class labels must be integers in [0, K)")
         else:
             _need(Y.shape == (n, k), "Y must be [N, K] with K = number of latent functions")
+            _need_ordinal_labels(desc, Y)
         if mean is not None:
             mean = _f64(np.broadcast_to(mean, (n, k)))
         return desc, Z, X, Y, mean, q_mu, q, qnd, m, d, n, k
@@ -1026,6 +1036,7 @@ class Handle(object):
         _need(F.ndim == 2 and Y.shape == F.shape and F.size > 0, "F and Y must both be [N, K]")
         if desc.kind == LIK_MULTICLASS:
             raise NotImplementedError("log p(y | f) of MultiClass is piecewise constant in f: no pointwise form with a gradient")
+        _need_ordinal_labels(desc, Y)
         n, k = F.shape
         lp, dpar = ctypes.c_double(0), ctypes.c_double(0)
         G = np.zeros((n, k)) if want_grad else None
@@ -1063,6 +1074,7 @@ class Handle(object):
         n, d = X.shape
         k = V.shape[1]
         _need(Y.shape == (n, k), "Y must be [N, K] with K = number of latent functions")
+        _need_ordinal_labels(desc, Y)
         if mean is not None:
             mean = _f64(np.broadcast_to(mean, (n, k)))
         return desc, X, V, Y, mean, n, d, k
@@ -1112,6 +1124,7 @@ class Handle(object):
             _need(np.all(Y == np.floor(Y)) and Y.min() >= 0 and Y.max() < k, "class labels must be integers in [0, K)")
         else:
             _need(Y.shape == (n, k), "Y must be [N, K] with K = number of latent functions")
+            _need_ordinal_labels(desc, Y)
         if mean is not None:
             mean = _f64(np.broadcast_to(mean, (n, k)))
         return desc, Z, X, Y, V, mean, m, d, n, k

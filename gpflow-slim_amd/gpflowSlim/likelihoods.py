@@ -1,14 +1,14 @@
 """Likelihoods.
 
 Mirrors gpflowSlim/likelihoods.py: the generic Gauss-Hermite routines of ``Likelihood`` (:45-152), Gaussian (:158-188),
-Poisson (:191-224), Exponential (:226-243), StudentT (:246-266), probit / Bernoulli (:269-298), RobustMax / MultiClass
-(:379-487).  Everything here is host numpy: it serves prediction (``predict_y`` / ``predict_density`` at modest N*) and is
+Poisson (:191-224), Exponential (:226-243), StudentT (:246-266), probit / Bernoulli (:269-298), Gamma (:301-333), Beta
+(:336-376), RobustMax / MultiClass (:379-487), Ordinal (:554-631).  Everything here is host numpy: it serves prediction (``predict_y`` / ``predict_density`` at modest N*) and is
 the slow path of the SVGP bound for user-defined likelihoods and links.  The built-in classes additionally describe
 themselves to the backend (``_device_spec``): for them the per-point term of the SVGP bound, its derivatives and the whole
 backward pass run on the device (csrc/lik.hip, gps_svgp_elbo_lik / gps_svgp_elbo_lik_grad).
 """
 import numpy as np
-from scipy.special import erf, gammaln
+from scipy.special import erf, erfc, gammaln
 
 from . import densities
 from . import transforms
@@ -16,7 +16,7 @@ from ._settings import settings
 from .params import Parameter
 
 # kinds of include/gpflowslim_hip.h
-LIK_GAUSSIAN, LIK_BERNOULLI, LIK_POISSON, LIK_EXPONENTIAL, LIK_STUDENT_T, LIK_MULTICLASS = range(6)
+LIK_GAUSSIAN, LIK_BERNOULLI, LIK_POISSON, LIK_EXPONENTIAL, LIK_STUDENT_T, LIK_MULTICLASS, LIK_GAMMA, LIK_BETA, LIK_ORDINAL = range(9)
 
 
 def hermgauss(n):
@@ -49,8 +49,8 @@ class Likelihood(object):
         raise NotImplementedError
 
     def _device_spec(self):
-        """(kind, [up to four scalar parameters], trainable Parameter behind parameter 0 or None) when the device kernels
-        implement this likelihood, else None (host path)."""
+        """(kind, [up to four scalar parameters], trainable Parameter behind parameter 0 or None[, Ordinal's bin edges]) when
+        the device kernels implement this likelihood, else None (host path)."""
         return None
 
     def predict_mean_and_var(self, Fmu, Fvar):
@@ -207,6 +207,19 @@ def probit(x):
     return 0.5 * (1.0 + erf(x / np.sqrt(2.0))) * (1 - 2e-3) + 1e-3
 
 
+def probit_difference(zl, zr):
+    """probit(zl) - probit(zr) for zl >= zr, = (1 - 2e-3) (Phi(zl) - Phi(zr)): the number :605-606 subtract, taken on the side
+    where both Phi are small, as a difference of two erfc.  As written there, two numbers near 1 (or 1e-3) are subtracted where
+    both arguments lie in the same far tail, and what is left next to the 1e-6 floor of Ordinal.logp is their rounding: 1e-10
+    relative in log p, measured 1.35e-11 of max(1, |log p|).  This form is within a few eps of its own value everywhere, and
+    it is what the device kernels compute (csrc/lik.hip), term by term."""
+    zl, zr = np.broadcast_arrays(np.asarray(zl, dtype=settings.float_type), np.asarray(zr, dtype=settings.float_type))
+    up = (zl + zr) > 0.0                    # (zl = +inf: up, its erfc is 0; zr = -inf: down, likewise; never both)
+    ea = erfc(np.where(up, zr, -zl) / np.sqrt(2.0))
+    eb = erfc(np.where(up, zl, -zr) / np.sqrt(2.0))
+    return (1 - 2e-3) * (0.5 * (ea - eb))
+
+
 class Bernoulli(Likelihood):
     """likelihoods.py:273-298"""
 
@@ -236,6 +249,128 @@ class Bernoulli(Likelihood):
 
     def _device_spec(self):
         return (LIK_BERNOULLI, [], None) if self.invlink is probit else None
+
+
+class Gamma(Likelihood):
+    """likelihoods.py:301-333: the transformed GP gives the *scale* (inverse rate) of the Gamma"""
+
+    def __init__(self, invlink=np.exp):
+        Likelihood.__init__(self)
+        self.invlink = invlink
+        self._shape = Parameter(1.0, transform=transforms.positive, dtype=settings.float_type, name='shape')
+        self._parameters = self._parameters + [self._shape]
+
+    @property
+    def shape(self):
+        return self._shape.value
+
+    def logp(self, F, Y):
+        return densities.gamma(self.shape, self.invlink(F), Y)
+
+    def conditional_mean(self, F):
+        return self.shape * self.invlink(F)
+
+    def conditional_variance(self, F):
+        scale = self.invlink(F)
+        return self.shape * np.square(scale)
+
+    def variational_expectations(self, Fmu, Fvar, Y):
+        if self.invlink is np.exp:
+            return -self.shape * Fmu - gammaln(self.shape) \
+                + (self.shape - 1.) * np.log(Y) - Y * np.exp(-Fmu + Fvar / 2.)
+        return Likelihood.variational_expectations(self, Fmu, Fvar, Y)
+
+    def _device_spec(self):
+        return (LIK_GAMMA, [float(np.squeeze(self.shape))], self._shape) if self.invlink is np.exp else None
+
+
+class Beta(Likelihood):
+    """likelihoods.py:336-376: the mean of the Beta density is the transformed process, m = invlink(f), with a scale
+    parameter: alpha = scale * m, beta = scale * (1 - m)."""
+
+    def __init__(self, invlink=probit, scale=1.0):
+        Likelihood.__init__(self)
+        self._scale = Parameter(scale, transform=transforms.positive, dtype=settings.float_type, name='scale')
+        self.invlink = invlink
+        self._parameters = self._parameters + [self._scale]
+
+    @property
+    def scale(self):
+        return self._scale.value
+
+    def logp(self, F, Y):
+        mean = self.invlink(F)
+        alpha = mean * self.scale
+        beta = self.scale - alpha
+        return densities.beta(alpha, beta, Y)
+
+    def conditional_mean(self, F):
+        return self.invlink(F)
+
+    def conditional_variance(self, F):
+        mean = self.invlink(F)
+        return (mean - np.square(mean)) / (self.scale + 1.)
+
+    def _device_spec(self):
+        return (LIK_BETA, [float(np.squeeze(self.scale))], self._scale) if self.invlink is probit else None
+
+
+class Ordinal(Likelihood):
+    """likelihoods.py:554-631: ordinal regression (Chu and Ghahramani 2005).  The data are the integers 0 .. K and the K bin
+    edges a_0 < ... < a_{K-1} say where the label switches:
+        p(Y = 0 | F) = phi((a_0 - F) / sigma),  p(Y = j | F) = phi((a_j - F) / sigma) - phi((a_{j-1} - F) / sigma),
+        p(Y = K | F) = 1 - phi((a_{K-1} - F) / sigma)
+    with phi the (squashed) probit and sigma a parameter to be learned."""
+
+    def __init__(self, bin_edges):
+        Likelihood.__init__(self)
+        self.bin_edges = np.asarray(bin_edges, dtype=settings.float_type).ravel()
+        self.num_bins = self.bin_edges.size + 1
+        self._sigma = Parameter(1.0, transform=transforms.positive, dtype=settings.float_type, name='sigma')
+        self._parameters = self._parameters + [self._sigma]
+
+    @property
+    def sigma(self):
+        return self._sigma.value
+
+    def _labels(self, Y):
+        """tf.cast(Y, tf.int64) + tf.gather (:599-603), which refuses an index outside the table"""
+        Y = np.asarray(Y)
+        if not (np.all(np.isfinite(Y)) and np.all(Y == np.floor(Y)) and Y.min() >= 0 and Y.max() <= self.bin_edges.size):
+            raise ValueError("Ordinal labels must be integers in [0, %d] (the number of bin edges)" % self.bin_edges.size)
+        return Y.astype(np.int64)
+
+    def logp(self, F, Y):
+        Y = self._labels(Y)
+        scaled_bins_left = np.concatenate([self.bin_edges / self.sigma, np.array([np.inf])], 0)
+        scaled_bins_right = np.concatenate([np.array([-np.inf]), self.bin_edges / self.sigma], 0)
+        selected_bins_left = scaled_bins_left[Y]
+        selected_bins_right = scaled_bins_right[Y]
+        return np.log(probit_difference(selected_bins_left - F / self.sigma,
+                                        selected_bins_right - F / self.sigma) + 1e-6)
+
+    def _make_phi(self, F):
+        """:608-619: one row per entry of F (flattened), one column per label: the probability of that label"""
+        scaled_bins_left = np.concatenate([self.bin_edges / self.sigma, np.array([np.inf])], 0)
+        scaled_bins_right = np.concatenate([np.array([-np.inf]), self.bin_edges / self.sigma], 0)
+        return probit(scaled_bins_left - np.reshape(F, (-1, 1)) / self.sigma) \
+            - probit(scaled_bins_right - np.reshape(F, (-1, 1)) / self.sigma)
+
+    def conditional_mean(self, F):
+        phi = self._make_phi(F)
+        Ys = np.reshape(np.arange(self.num_bins, dtype=np.float64), (-1, 1))
+        return np.reshape(np.matmul(phi, Ys), np.shape(F))
+
+    def conditional_variance(self, F):
+        phi = self._make_phi(F)
+        Ys = np.reshape(np.arange(self.num_bins, dtype=np.float64), (-1, 1))
+        E_y = np.matmul(phi, Ys)
+        E_y2 = np.matmul(phi, np.square(Ys))
+        return np.reshape(E_y2 - np.square(E_y), np.shape(F))
+
+    def _device_spec(self):
+        """a fourth element: the table of bin edges (at most 32 on the device; _backend.make_lik raises beyond)"""
+        return (LIK_ORDINAL, [float(np.squeeze(self.sigma))], self._sigma, self.bin_edges)
 
 
 class RobustMax(object):

@@ -2,7 +2,7 @@
 
 Mirrors gpflowSlim/models/gpmc.py:28-93:  v ~ N(0, I),  f = L v + m(x),  L L^T = K + jitter I, and the model's likelihood is
 log p(Y | f) -- the N(0, 1) prior on V enters through ``Parameter.prior`` like every other prior.  With one of the built-in
-likelihoods (Gaussian, Bernoulli, Poisson, Exponential, StudentT with their default links) the likelihood is one device call
+likelihoods (Gaussian, Bernoulli, Poisson, Exponential, StudentT, Gamma, Beta, Ordinal with their default links) the likelihood is one device call
 (gps_gpmc_lik: K, its factor, F = L V and the pointwise sum stay in HBM) and so is its gradient in every kernel parameter, the
 likelihood's parameter, V and the mean (gps_gpmc_lik_grad); any other likelihood object with a ``logp`` gets F from the
 device and is summed on the host (value only: there is no autodiff to differentiate it).  MultiClass is refused: its
@@ -34,8 +34,9 @@ def device_likelihood(likelihood, allow_multiclass=False):
         spec = getattr(likelihood, "_device_spec", lambda: None)()
     if spec is None:
         return None
-    kind, params, trainable = spec
-    return be.make_lik(kind, params, min(likelihood.num_gauss_hermite_points, be.LIK_MAX_GH)), trainable
+    kind, params, trainable = spec[:3]
+    edges = spec[3] if len(spec) > 3 else None                   # (Ordinal's table of bin edges)
+    return be.make_lik(kind, params, min(likelihood.num_gauss_hermite_points, be.LIK_MAX_GH), edges=edges), trainable
 
 
 class GPMC(GPModel):
@@ -80,7 +81,7 @@ class GPMC(GPModel):
         dl = device_likelihood(self.likelihood)
         if dl is None:
             raise NotImplementedError("analytic gradients of GPMC need one of the built-in likelihoods (Gaussian, Bernoulli, "
-                                      "Poisson, Exponential, StudentT) with its default link")
+                                      "Poisson, Exponential, StudentT, Gamma, Beta, Ordinal) with its default link")
         X = self.X
         d_all = X.shape[1]
         layout = self.kern._grad_layout(d_all)

@@ -5,8 +5,8 @@ Mirrors gpflowSlim/models/sgpmc.py:58-104:  v ~ N(0, I),  u = Lm v,  Lm Lm^T = K
 sum of the variational expectations at the exact marginals of p(f | u = Lm v) -- the N(0, 1) prior on V enters through
 ``Parameter.prior`` like every other prior.  It is GPMC's sampler-facing model at M inducing points instead of N data points.
 
-With one of the built-in likelihoods (Gaussian, Bernoulli, Poisson, Exponential, StudentT, MultiClass with their default links)
-the likelihood is one device call that streams the data in row chunks (gps_sgpmc_lik: device memory O(M^2 + M chunk), no
+With one of the built-in likelihoods (Gaussian, Bernoulli, Poisson, Exponential, StudentT, MultiClass, Gamma, Beta, Ordinal
+with their default links) the likelihood is one device call that streams the data in row chunks (gps_sgpmc_lik: device memory O(M^2 + M chunk), no
 [M, N] array), and so is its gradient in every kernel parameter, the likelihood's parameter, V, the mean and, with
 ``train_inducing``, Z (gps_sgpmc_lik_grad: the same single pass).  MultiClass is fine here, unlike in GPMC: the variational
 expectation at fvar > 0 is smooth.  Any other likelihood object with a ``variational_expectations`` gets the marginals from
@@ -76,7 +76,7 @@ class SGPMC(GPModel):
         dl = device_likelihood(self.likelihood)
         if dl is None:
             raise NotImplementedError("analytic gradients of SGPMC need one of the built-in likelihoods (Gaussian, Bernoulli, "
-                                      "Poisson, Exponential, StudentT, MultiClass) with its default link")
+                                      "Poisson, Exponential, StudentT, MultiClass, Gamma, Beta, Ordinal) with its default link")
         X = self.X
         d_all = X.shape[1]
         layout = self.kern._grad_layout(d_all)

@@ -71,10 +71,11 @@ class SVGP(GPModel):
         spec = getattr(self.likelihood, "_device_spec", lambda: None)()
         if spec is None or type(self.likelihood) is likelihoods.Gaussian:
             return None
-        kind, params, trainable = spec
+        kind, params, trainable = spec[:3]
         if self.likelihood.num_gauss_hermite_points > be.LIK_MAX_GH:
             return None
-        return be.make_lik(kind, params, self.likelihood.num_gauss_hermite_points), trainable
+        edges = spec[3] if len(spec) > 3 else None               # (Ordinal's table of bin edges)
+        return be.make_lik(kind, params, self.likelihood.num_gauss_hermite_points, edges=edges), trainable
 
     def _mean_on(self, X):
         mean = np.asarray(self.mean_function(X), dtype=settings.float_type)
@@ -121,7 +122,8 @@ class SVGP(GPModel):
         dl = None if gaussian else self._device_lik()
         if not gaussian and dl is None:
             raise NotImplementedError("analytic gradients of the SVGP bound need the Gaussian likelihood or one of the built-in "
-                                      "likelihoods (Bernoulli, Poisson, Exponential, StudentT, MultiClass) with its default link")
+                                      "likelihoods (Bernoulli, Poisson, Exponential, StudentT, MultiClass, Gamma, Beta, Ordinal) "
+                                      "with its default link")
         d_all = X.shape[1]
         prog = self.kern._program(d_all)
         layout = self.kern._grad_layout(d_all)

@@ -326,7 +326,7 @@ int gps_svgp_elbo_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes,
                        double* elbo, double* grad_slots, int n_slots_cap, int* n_slots_out, double* grad_noise,
                        double* grad_q_mu, double* grad_q_sqrt, double* grad_mean, double* grad_Z, int* info);
 
-/* ---- non-Gaussian likelihoods (likelihoods.py:191-487): the variational expectations  int log p(y | f) q(f) df  of a point
+/* ---- non-Gaussian likelihoods (likelihoods.py:191-631): the variational expectations  int log p(y | f) q(f) df  of a point
  * with q(f) = N(mu, var), their derivatives in mu and var, and the SVGP bound / gradient built on them.
  *   kind                  param[]                            per-point term
  *   GPS_LIK_GAUSSIAN      [0] variance                       likelihoods.py:186-188 (closed form; kept for checking the general
@@ -338,25 +338,43 @@ int gps_svgp_elbo_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes,
  *   GPS_LIK_STUDENT_T     [0] scale, [1] deg_free            Gauss-Hermite of densities.student_t(y, f, scale, deg_free)      (:246-266)
  *   GPS_LIK_MULTICLASS    [0] RobustMax epsilon              p log(1 - eps) + (1 - p) log(eps / (K - 1)), p = prob_is_largest  (:379-454),
  *                                                            K = the number of latent functions; Y holds ONE class label per point
+ *   GPS_LIK_GAMMA         [0] shape a                        -a mu - lgamma(a) + (a - 1) log y - y exp(-mu + var/2)            (:301-333;
+ *                                                            exp link, the latent gives the scale; targets y > 0)
+ *   GPS_LIK_BETA          [0] scale s                        Gauss-Hermite of densities.beta(m s, s - m s, y), m = probit(f)  (:336-376;
+ *                                                            y clipped to [1e-6, 1 - 1e-6] as densities.beta does)
+ *   GPS_LIK_ORDINAL       [0] sigma, edges[n_edges]          Gauss-Hermite of log(probit(edges[y] / sigma - f / sigma) -
+ *                                                            probit(edges[y - 1] / sigma - f / sigma) + 1e-6)                 (:554-631)
+ *                                                            with probit(+inf) for the top label y = n_edges and probit(-inf) for
+ *                                                            y = 0; the difference of the two probits is taken as a difference of
+ *                                                            erfc, so that no rounding is left next to the floor.  Y holds the labels 0 .. n_edges as doubles, [n, k]; edges is
+ *                                                            strictly increasing and finite, 1 <= n_edges <= GPS_LIK_MAX_EDGES
+ *                                                            (GPS_ERR_ARG otherwise).  The kernels clamp every label into
+ *                                                            [0, n_edges] before they index the table: a label outside it is the
+ *                                                            caller's error, but never an address outside the table.
  * The Gauss-Hermite rule is the caller's: gh_x, gh_w = numpy.polynomial.hermite.hermgauss(n_gh) as the reference calls it
  * (:140; unnormalised weights, the library divides by sqrt(pi) as :142 does), 1 <= n_gh <= GPS_LIK_MAX_GH; ignored by the
- * closed forms.  The inverse links are the reference's defaults (probit, exp); any other link stays with the caller.      */
+ * closed forms (Gaussian, Poisson, Exponential, Gamma).  n_edges and edges are read by GPS_LIK_ORDINAL only; every other kind
+ * ignores them.  The inverse links are the reference's defaults (probit, exp); any other link stays with the caller.      */
 enum { GPS_LIK_GAUSSIAN = 0, GPS_LIK_BERNOULLI = 1, GPS_LIK_POISSON = 2, GPS_LIK_EXPONENTIAL = 3, GPS_LIK_STUDENT_T = 4,
-       GPS_LIK_MULTICLASS = 5 };
+       GPS_LIK_MULTICLASS = 5, GPS_LIK_GAMMA = 6, GPS_LIK_BETA = 7, GPS_LIK_ORDINAL = 8 };
 #define GPS_LIK_MAX_GH 64
+#define GPS_LIK_MAX_EDGES 32
 typedef struct {
   int kind;
   int n_gh;
   double param[4];
   const double* gh_x;   /* host [n_gh] */
   const double* gh_w;   /* host [n_gh] */
+  int n_edges;          /* GPS_LIK_ORDINAL: the number of bin edges (labels are 0 .. n_edges) */
+  const double* edges;  /* GPS_LIK_ORDINAL: host [n_edges], strictly increasing */
 } gps_lik_t;
 
 /* The likelihood kernels on their own (the building block of models assembled by the caller): fmu, fvar host [n, k]; Y host
  * [n, k] ([n] labels for GPS_LIK_MULTICLASS).  *var_exp_sum = sum over points and latents of the variational expectations
  * (Likelihood.variational_expectations, :121-152; per-workgroup partial sums added up in a fixed order: bit-reproducible).
  * Optional (both or neither): dmu_out, dvar_out host [n, k] = d var_exp_i / d fmu[i][q], d fvar[i][q] (for MultiClass every
- * latent of the point).  Optional dparam_out: d sum / d param[0] (the Student-t scale, the Gaussian variance; 0 otherwise). */
+ * latent of the point).  Optional dparam_out: d sum / d param[0] (the Student-t scale, the Gaussian variance, the Gamma shape,
+ * the Beta scale, the Ordinal sigma; 0 otherwise).                                                                        */
 int gps_lik_varexp(gps_handle_t h, const gps_lik_t* lik, const double* fmu, const double* fvar, const double* Y,
                    int64_t n, int64_t k, double* var_exp_sum, double* dmu_out, double* dvar_out, double* dparam_out);
 
@@ -370,7 +388,8 @@ int gps_svgp_elbo_lik(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes,
                       const double* q_mu, int64_t k, const double* q_sqrt, int q_sqrt_ndim,
                       int white, const gps_lik_t* lik, double scale,
                       double* elbo, double* kl, double* var_exp_sum, int* info);
-/* ... and its gradient: outputs of the Gaussian gradient above, grad_lik = d/d param[0] in place of grad_noise.  Backward
+/* ... and its gradient: outputs of the Gaussian gradient above, grad_lik = d/d param[0] (see gps_lik_varexp) in place of
+ * grad_noise.  Backward
  * pass for per-point cotangents E = scale dmu, H = scale dvar (the Gaussian's H is a constant, which lets it share one
  * [n, m] x [m, m] product between the latents; here a full q_sqrt costs one such product and one A diag(H_q) A^T per latent).
  * Not available while the data are sharded over ranks through gps_set_allreduce (GPS_ERR_UNSUPPORTED).             */
@@ -384,7 +403,8 @@ int gps_svgp_elbo_lik_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_no
 
 /* ---- GPMC: the whitened model for MCMC (models/gpmc.py:28-93) ------------------------------------------------------------
  * log p(Y | F) itself (Likelihood.logp, no q(f)) summed over points and latents: F, Y host [n, k].  Optional dF_out host
- * [n, k] = d log p / d F; optional dparam_out = d sum / d param[0] (the Gaussian variance, the Student-t scale; 0 otherwise).
+ * [n, k] = d log p / d F; optional dparam_out = d sum / d param[0] (the Gaussian variance, the Student-t scale, the Gamma
+ * shape, the Beta scale, the Ordinal sigma; 0 otherwise).
  * Every kind except GPS_LIK_MULTICLASS, whose log p is piecewise constant in F (GPS_ERR_UNSUPPORTED).  Partial sums are
  * added in a fixed order: bit-reproducible.                                                                              */
 int gps_lik_logp(gps_handle_t h, const gps_lik_t* lik, const double* F, const double* Y, int64_t n, int64_t k,
@@ -416,7 +436,7 @@ int gps_gpmc_lik_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, 
 /* loglik = sum_i var_exp(fmean_i, fvar_i, Y_i) with fmean = A^T V + mean, fvar = Kdiag - colsum(A^2), A = Lm^-1 Kuf,
  * Lm = chol(Kuu + jitter I)  (sgpmc.py:83-89; the whitened conditional with q_sqrt = None): Z host [m, d_all], X host
  * [n, d_all], Y host [n, k] ([n] class labels for GPS_LIK_MULTICLASS), mean host [n, k] = mean_function(X) or NULL, V host
- * [m, k].  All six likelihood kinds.  The data are taken chunk_rows rows at a time (a multiple of 128; 0: the library's
+ * [m, k].  Every likelihood kind.  The data are taken chunk_rows rows at a time (a multiple of 128; 0: the library's
  * choice): device memory is O(m^2 + m chunk_rows), no [m, n] array exists.  *info > 0: Kuu + jitter I is not positive
  * definite (nothing else is set).                                                                                        */
 int gps_sgpmc_lik(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m, int64_t d_all,
