@@ -717,6 +717,69 @@ int gps_launch_block_sum(gps_handle_t h, double* D, i64 ldd, const double* X, i6
   GPS_HIP(h, hipGetLastError());
   return GPS_OK;
 }
+// The five operand sums of one side of the Strassen level in one pass (strassen.hpp: strassen_nt_presummed): X [2 rows, 2 cols]
+// is read once, quadrant by quadrant, and the five blocks [rows, cols] (leading dimension cols) go to out + q ostride.  Every
+// output element is the one add or subtract of the same two inputs that block_sum_kernel makes (x + 1.0 y and x + -1.0 y round
+// as x + y and x - y): the products get bit-identical operands.  Two doubles per access; grid-stride over column pairs (x) and
+// rows (y), two rows -- eight loads -- in flight per thread.
+__device__ __forceinline__ void strassen_sums_store(int side, sum_v2d q11, sum_v2d q12, sum_v2d q21, sum_v2d q22, double* orow, i64 ostride,
+                                                    unsigned at) {
+  sum_v2d s1, s2, s3, s4;
+  if (side == 0) { s1 = q21 + q22; s2 = q11 + q12; s3 = q21 - q11; s4 = q12 - q22; }
+  else           { s1 = q21 - q22; s2 = q12 - q11; s3 = q11 + q21; s4 = q12 + q22; }
+  *reinterpret_cast<sum_v2d*>(orow + at) = q11 + q22;
+  *reinterpret_cast<sum_v2d*>(orow + ostride + at) = s1;
+  *reinterpret_cast<sum_v2d*>(orow + 2 * ostride + at) = s2;
+  *reinterpret_cast<sum_v2d*>(orow + 3 * ostride + at) = s3;
+  *reinterpret_cast<sum_v2d*>(orow + 4 * ostride + at) = s4;
+}
+// (A row is the workgroup's, so every row pointer is uniform and a thread adds only its 32-bit column offset: cols < 2^28.)
+__global__ __launch_bounds__(256) void strassen_sums_kernel(const double* __restrict__ X, i64 ldx, i64 rows, unsigned cols2, int side,
+                                                            double* __restrict__ out, i64 ostride) {
+  const i64 cols = 2 * (i64)cols2, gy = gridDim.y;
+  for (unsigned c = blockIdx.x * blockDim.x + threadIdx.x; c < cols2; c += gridDim.x * blockDim.x) {
+    const unsigned at = 2 * c;
+    i64 rr = blockIdx.y;
+    for (; rr + gy < rows; rr += 2 * gy) {
+      sum_v2d q[2][4];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const double* __restrict__ x1 = X + (rr + u * gy) * ldx;      // row of the upper quadrants, of the lower ones
+        const double* __restrict__ x2 = x1 + rows * ldx;
+        q[u][0] = *reinterpret_cast<const sum_v2d*>(x1 + at);
+        q[u][1] = *reinterpret_cast<const sum_v2d*>(x1 + cols + at);
+        q[u][2] = *reinterpret_cast<const sum_v2d*>(x2 + at);
+        q[u][3] = *reinterpret_cast<const sum_v2d*>(x2 + cols + at);
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) strassen_sums_store(side, q[u][0], q[u][1], q[u][2], q[u][3], out + (rr + u * gy) * cols, ostride, at);
+    }
+    for (; rr < rows; rr += gy) {
+      const double* __restrict__ x1 = X + rr * ldx;
+      const double* __restrict__ x2 = x1 + rows * ldx;
+      strassen_sums_store(side, *reinterpret_cast<const sum_v2d*>(x1 + at), *reinterpret_cast<const sum_v2d*>(x1 + cols + at),
+                          *reinterpret_cast<const sum_v2d*>(x2 + at), *reinterpret_cast<const sum_v2d*>(x2 + cols + at),
+                          out + rr * cols, ostride, at);
+    }
+  }
+}
+// Counted with the GEMM class like the sums it replaces: four quadrants read, five blocks written.
+int gps_launch_strassen_sums(gps_handle_t h, int side, const double* X, i64 ldx, i64 rows, i64 cols, double* out, i64 ostride) {
+  if (rows <= 0 || cols <= 0) return GPS_OK;
+  if (side != 0 && side != 1) return gps_fail(h, GPS_ERR_ARG, "strassen_sums: side 0 or 1");
+  if ((cols & 1) || (ldx & 1) || ldx < 2 * cols || (ostride & 1) || ostride < rows * cols || (((uintptr_t)X | (uintptr_t)out) & 15))
+    return gps_fail(h, GPS_ERR_ARG, "strassen_sums: blocks must be 16-byte aligned with even widths, strides and leading dimensions");
+  if (cols >= ((i64)1 << 28)) return gps_fail(h, GPS_ERR_ARG, "strassen_sums: at most 2^28 - 2 columns");
+  LaunchScope ls(h, KC_GEMM, 5.0 * (double)rows * (double)cols, 72.0 * (double)rows * (double)cols);
+  ls.tag[0] = rows; ls.tag[1] = cols; ls.tag[2] = side; ls.tag[3] = -2;
+  const unsigned cols2 = (unsigned)(cols / 2);
+  const unsigned gx = (unsigned)std::min<i64>((cols2 + 255) / 256, 64);
+  // (block_sum's grid, but at least three rows to a thread: blocks of a few tiles run the paired loop and the remainder too)
+  const unsigned gy = (unsigned)std::min<i64>((rows + 2) / 3, std::max<i64>(1, 4096 / gx));
+  hipLaunchKernelGGL(strassen_sums_kernel, dim3(gx, gy), dim3(256), 0, h->stream, X, ldx, rows, cols2, side, out, ostride);
+  GPS_HIP(h, hipGetLastError());
+  return GPS_OK;
+}
 int gps_launch_axpby_eye(gps_handle_t h, double* A, i64 ld, i64 n, i64 n_real, double alpha, double beta) {
   if (n <= 0) return GPS_OK;
   LaunchScope ls(h, KC_OTHER, (double)n * n, 16.0 * n * n);

@@ -285,8 +285,24 @@ struct gps_handle_s {
   DevBuf dGemmWs{bufs}, dGemmCnt{bufs};   // slice partials + arrival counters of the GEMM tail split
   // One Strassen level for the largest rectangular updates (strassen.hpp; HipOps::gemm decides): seven half-size products for
   // eight, when every quadrant edge is at least this many elements (option "gemm_strassen_min": a multiple of 128, 0 = off).
-  int gemm_strassen_min = 4096;
+  // 2048 since the sums of a level take one pass per operand (below): 16384 x 4096 x 4096 and 8192 x 4096 x 4096 gain, LAB_NOTES.
+  int gemm_strassen_min = 2048;
+  // The off-diagonal square of a lower / trapezoid update goes through the level when its own quadrants reach this (option
+  // "gemm_strassen_lower_min"; strassen_lower_split's condition): the two triangles of an 8192-column update cost more than the
+  // level saves, so this one stays at 4096.  Setting "gemm_strassen_min" sets both -- one threshold, as before the two were told
+  // apart -- except that its built-in value puts both back to their built-in values; "gemm_strassen_lower_min" moves this alone.
+  static constexpr int strassen_min_builtin = 2048, strassen_lower_min_builtin = 4096;
+  int gemm_strassen_lower_min = strassen_lower_min_builtin;
   DevBuf dStrS{bufs}, dStrT{bufs};        // its operand sums S [M/2, K/2], T [N/2, K/2] (main stream only: one product in flight)
+  // A level whose quadrant edges all reach this forms its ten sums in two passes, one per operand (strassen_nt_presummed; option
+  // "gemm_strassen_presum_min": a multiple of 128, 0 = off).  Below it a sum is a few microseconds of launch, not bandwidth.
+  // Five S and five T blocks: 5 x the two buffers above (N = 32768: 2 x 1.34 GB), growing as N^2 -- where they cannot be had, or
+  // exceed "gemm_strassen_presum_max_bytes" (0 = no cap), the level takes the two-buffer form and the fallback is counted
+  // (gps_profile_get "strassen_presum_fallbacks").
+  int gemm_strassen_presum_min = 1024;
+  double gemm_strassen_presum_max_bytes = 0.0;
+  long long strassen_presum_fallbacks = 0;
+  DevBuf dStrS5{bufs}, dStrT5{bufs};
   // ---- random-feature GPR (gps_rff.hip): L = chol(Phi^T Phi + s I) [pad(F), pad(F)] in dK / dLinv, L^-1 B and C in dAlpha ----
   // valid while factor_gen still is what it was when the factor was made (every entry that rebuilds dK bumps it)
   struct RffFactor { bool have = false; unsigned long long gen = 0; i64 F = 0, r = 0; int kind = -1, d = 0; bool refine = false; } rff;
@@ -443,6 +459,9 @@ int gps_launch_gemm_nt_dual(gps_handle_t h, i64 M, i64 N, i64 K, const double* A
 // blas1.hip : D = X + sign Y on [rows, cols] blocks (cols, leading dimensions even; 16-byte aligned)
 int gps_launch_block_sum(gps_handle_t h, double* D, i64 ldd, const double* X, i64 ldx, const double* Y, i64 ldy, i64 rows, i64 cols,
                          int sign);
+// blas1.hip : the five operand sums of one side of the Strassen level (strassen.hpp: Ops::sums) from X [2 rows, 2 cols] in one
+// pass, to the blocks [rows, cols] at out + q ostride (same alignment and evenness as gps_launch_block_sum)
+int gps_launch_strassen_sums(gps_handle_t h, int side, const double* X, i64 ldx, i64 rows, i64 cols, double* out, i64 ostride);
 // potrf_base.hip : factor one 128x128 diagonal block in place (lower), write its
 // inverse (full 128x128, zero upper) to Linv_blk; info word gets min(index+1) of a
 // non-positive pivot (index counted from row0).

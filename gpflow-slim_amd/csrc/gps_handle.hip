@@ -109,6 +109,7 @@ extern "C" int gps_profile_get(gps_handle_t h, const char* klass, int64_t* launc
     {"leaves_plain", h->leaves_plain},                         // leaf launches in refine mode, by kind
     {"leaves_refined", h->leaves_refined},
     {"trsv_wave_fallbacks", (long long)h->wave_fallbacks},     // wavefront substitutions that gave up (handle fell back to the recursive one)
+    {"strassen_presum_fallbacks", h->strassen_presum_fallbacks},   // Strassen levels that wanted the one-pass sums and took the two-buffer form (no room for the ten blocks)
   };
   for (const auto& c : counters) {
     if (strcmp(klass, c.key) != 0) continue;
@@ -137,14 +138,35 @@ extern "C" int gps_last_stage_ms(gps_handle_t h, double* out5) {
   return GPS_OK;
 }
 
+// The further keys of the "gemm_strassen_min" family (documented with it in the public header): "gemm_strassen_" + sub.
+static int set_strassen_tuning(gps_handle_t h, const char* sub, double value) {
+  const bool lower_min = strcmp(sub, "lower_min") == 0;
+  if (lower_min || strcmp(sub, "presum_min") == 0) {
+    if (value < 0 || value > 1e9 || value != (double)((i64)value) || (i64)value % 128)
+      return gps_fail(h, GPS_ERR_ARG, std::string("gemm_strassen_") + sub + ": 0 or a multiple of 128");
+    (lower_min ? h->gemm_strassen_lower_min : h->gemm_strassen_presum_min) = (int)value;
+    return GPS_OK;
+  }
+  if (strcmp(sub, "presum_max_bytes") == 0) {
+    if (!(value >= 0)) return gps_fail(h, GPS_ERR_ARG, "gemm_strassen_presum_max_bytes: 0 (no cap) or a number of bytes");
+    h->gemm_strassen_presum_max_bytes = value;
+    return GPS_OK;
+  }
+  return gps_fail(h, GPS_ERR_ARG, "unknown option");
+}
+
 extern "C" int gps_set_option(gps_handle_t h, const char* key, double value) {
   if (!h || !key) return GPS_ERR_ARG;
   if (strcmp(key, "gemm_force_tile") == 0) { h->gemm_force_tb = (int)value; return GPS_OK; }
   if (strcmp(key, "gemm_tail_split") == 0) { h->gemm_tail_split = (int)value; return GPS_OK; }
   if (strcmp(key, "gemm_strassen_min") == 0) {
     if (value < 0 || value != (double)((i64)value) || (i64)value % 128) return gps_fail(h, GPS_ERR_ARG, "gemm_strassen_min: 0 or a multiple of 128");
-    h->gemm_strassen_min = (int)value; return GPS_OK;
+    // one threshold for both forms, as ever; the built-in value restores the built-in pair (the lower form's is larger)
+    h->gemm_strassen_min = (int)value;
+    h->gemm_strassen_lower_min = (int)value == gps_handle_s::strassen_min_builtin ? gps_handle_s::strassen_lower_min_builtin : (int)value;
+    return GPS_OK;
   }
+  if (strncmp(key, "gemm_strassen_", 14) == 0) return set_strassen_tuning(h, key + 14, value);
   if (strcmp(key, "kmat_fast") == 0) { h->kmat_fast = (int)value; return GPS_OK; }
   if (strcmp(key, "kmat_mfma") == 0) { h->kmat_mfma = (int)value; return GPS_OK; }
   if (strcmp(key, "trsv_wave") == 0) { h->trsv_wave = (int)value; return GPS_OK; }

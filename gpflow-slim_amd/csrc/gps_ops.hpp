@@ -69,21 +69,52 @@ struct HipOps {
   }
   // C (op)= A B^T.  The largest plain updates (C -= A B^T on the main stream, plain leaves) take one Strassen level
   // (strassen.hpp): rectangular ones whose quadrants reach "gemm_strassen_min", and the off-diagonal square of a lower /
-  // trapezoid update twice that size.  Everything else, and every product of the level itself, is gemm_plain.
+  // trapezoid update whose own quadrants reach "gemm_strassen_lower_min".  Everything else, and every product of the level
+  // itself, is gemm_plain.
   int gemm(int op, int lower, i64 M, i64 N, i64 K, const double* A, i64 lda, const double* B,
            i64 ldb, double* C, i64 ldc) {
     const i64 smin = h->gemm_strassen_min;
     if (smin > 0 && op == 0 && !h->refine_now && C != A && on_main_stream()) {
       if (lower == 0 && strassen_shape_ok(M, N, K, smin)) {
-        GPS_HIP(h, h->dStrS.ensure((size_t)(M / 2) * (size_t)(K / 2) * 8));
-        GPS_HIP(h, h->dStrT.ensure((size_t)(N / 2) * (size_t)(K / 2) * 8));
+        const size_t sb = (size_t)(M / 2) * (size_t)(K / 2) * 8, tb = (size_t)(N / 2) * (size_t)(K / 2) * 8;
+        // the sums of each side in one pass, where the quadrants are large enough for a sum to be bandwidth and the ten blocks fit
+        if (strassen_shape_ok(M, N, K, h->gemm_strassen_presum_min) && presum_buffers(5 * sb, 5 * tb)) {
+          const int rc = strassen_nt_presummed(*this, M, N, K, A, lda, B, ldb, C, ldc, h->dStrS5.d(), h->dStrT5.d());
+          return rc < 0 ? gps_fail(h, GPS_ERR_ARG, "strassen_nt_presummed: bad shape") : rc;
+        }
+        GPS_HIP(h, h->dStrS.ensure(sb));
+        GPS_HIP(h, h->dStrT.ensure(tb));
         const int rc = strassen_nt(*this, M, N, K, A, lda, B, ldb, C, ldc, h->dStrS.d(), h->dStrT.d());
         return rc < 0 ? gps_fail(h, GPS_ERR_ARG, "strassen_nt: bad shape") : rc;
       }
       int rc = 0;
-      if (lower == 1 && strassen_lower_split(*this, M, N, K, A, lda, B, ldb, C, ldc, smin, &rc)) return rc;
+      if (lower == 1 && strassen_lower_split(*this, M, N, K, A, lda, B, ldb, C, ldc, h->gemm_strassen_lower_min, &rc)) return rc;
     }
     return gemm_plain(op, lower, M, N, K, A, lda, B, ldb, C, ldc);
+  }
+  // The ten blocks of the one-pass sums.  They grow as N^2 beside a kernel matrix that may fill the device: a request over the
+  // option's cap or over what the device has free, or an allocation that fails all the same, is no error -- the level then takes
+  // its two-buffer form -- but it is counted.
+  bool presum_buffers(size_t s_bytes, size_t t_bytes) {
+    const double cap = h->gemm_strassen_presum_max_bytes;
+    bool ok = !(cap > 0.0 && (double)s_bytes + (double)t_bytes > cap);
+    if (ok && (s_bytes > h->dStrS5.cap || t_bytes > h->dStrT5.cap)) {
+      // (ensure gives a buffer that has to grow back before it asks for the larger one)
+      size_t need = 0, back = 0, free_b = 0, total_b = 0;
+      if (s_bytes > h->dStrS5.cap) { need += s_bytes + ((size_t)1 << 20); back += h->dStrS5.cap; }
+      if (t_bytes > h->dStrT5.cap) { need += t_bytes + ((size_t)1 << 20); back += h->dStrT5.cap; }
+      ok = hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= free_b + back;
+      if (ok) {
+        ok = h->dStrS5.ensure(s_bytes) == hipSuccess && h->dStrT5.ensure(t_bytes) == hipSuccess;
+        if (!ok) { h->dStrS5.release(); h->dStrT5.release(); }
+      }
+      if (!ok) (void)hipGetLastError();          // (a refused allocation must not surface at the next launch check)
+    }
+    if (!ok) h->strassen_presum_fallbacks++;
+    return ok;
+  }
+  int sums(int side, const double* X, i64 ldx, i64 r, i64 c, double* out, i64 out_stride) {
+    return gps_launch_strassen_sums(h, side, X, ldx, r, c, out, out_stride);
   }
   int add(double* D, i64 ldd, const double* X, i64 ldx, const double* Y, i64 ldy, i64 rows, i64 cols, int sign) {
     return gps_launch_block_sum(h, D, ldd, X, ldx, Y, ldy, rows, cols, sign);

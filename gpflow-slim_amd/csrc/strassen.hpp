@@ -67,6 +67,41 @@ int strassen_nt(Ops& ops, int64_t M, int64_t N, int64_t K, const double* A, int6
   return ops.gemm2(m, n, k, S, k, T, k, C11, ldc, nullptr, 0, 0);
 }
 
+// The same level with the ten sums formed first, each side in one pass over its operand: a sum launched alone reads two quadrants
+// and writes one (30 quadrant passes per level, every quadrant read two or three times); a launch that reads the four quadrants
+// of one operand once and writes that side's five sums needs 4 + 5 = 9 (18 per level).  The products are the seven of
+// strassen_nt -- same operands element for element, same targets, signs and order -- so the result is bit for bit the same.
+//
+//   Ops::sums(side, X, ldx, r, c, out, out_stride)   X [2r, 2c] (ld ldx); the five blocks [r, c] (ld c) at out + q out_stride:
+//     side 0:  X11 + X22,  X21 + X22,  X11 + X12,  X21 - X11,  X12 - X22      (S of P1, P2, P5, P6, P7)
+//     side 1:  X11 + X22,  X21 - X22,  X12 - X11,  X11 + X21,  X12 + X22      (T of P1, P3, P4, P6, P7)
+//
+// S5, T5: five blocks [M/2, K/2] and five blocks [N/2, K/2], back to back.
+template <class Ops>
+int strassen_nt_presummed(Ops& ops, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda, const double* B, int64_t ldb,
+                          double* C, int64_t ldc, double* S5, double* T5) {
+  typedef int64_t i64;
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  if (M % 256 || N % 256 || K % 256) return -1;
+  const i64 m = M / 2, n = N / 2, k = K / 2;
+  const double* A11 = A;            const double* A22 = A + m * lda + k;
+  const double* B11 = B;            const double* B22 = B + n * ldb + k;
+  double* C11 = C;            double* C12 = C + n;
+  double* C21 = C + m * ldc;  double* C22 = C21 + n;
+  const double* S[5]; const double* T[5];
+  for (int q = 0; q < 5; ++q) { S[q] = S5 + q * m * k; T[q] = T5 + q * n * k; }
+  int rc;
+  if ((rc = ops.sums(0, A, lda, m, k, S5, m * k))) return rc;
+  if ((rc = ops.sums(1, B, ldb, n, k, T5, n * k))) return rc;
+  if ((rc = ops.gemm2(m, n, k, S[0], k, T[0], k, C11, ldc, C22, ldc, 0))) return rc;      // P1
+  if ((rc = ops.gemm2(m, n, k, S[1], k, B11, ldb, C21, ldc, C22, ldc, 2))) return rc;     // P2
+  if ((rc = ops.gemm2(m, n, k, A11, lda, T[1], k, C12, ldc, C22, ldc, 0))) return rc;     // P3
+  if ((rc = ops.gemm2(m, n, k, A22, lda, T[2], k, C11, ldc, C21, ldc, 0))) return rc;     // P4
+  if ((rc = ops.gemm2(m, n, k, S[2], k, B22, ldb, C12, ldc, C11, ldc, 2))) return rc;     // P5
+  if ((rc = ops.gemm2(m, n, k, S[3], k, T[3], k, C22, ldc, nullptr, 0, 0))) return rc;    // P6
+  return ops.gemm2(m, n, k, S[4], k, T[4], k, C11, ldc, nullptr, 0, 0);                   // P7
+}
+
 // Where one level applies to  C -= A B^T  (Ops-independent: the shape part of HipOps::gemm's gate): halves that are whole tiles,
 // every quadrant edge at least `min_quadrant` (0: never).
 static inline bool strassen_shape_ok(int64_t M, int64_t N, int64_t K, int64_t min_quadrant) {

@@ -737,13 +737,24 @@ int gps_dist_finish(gps_handle_t h, double* lml, int* info);
  *   "gemm_force_tile" pin the GEMM tile edge to 128 / 64 / 32 (0 = automatic: the largest tile that still gives 512 workgroups)
  *   "gemm_tail_split" 1 (default): the tiles of a partial last round of a 128x128 launch are cut into
  *                     K-slices over the idle workgroup slots; 0: one workgroup per tile
- *   "gemm_strassen_min" quadrant edge, in elements (a multiple of 128; 0 = off; default 4096, the smallest value with a measured
+ *   "gemm_strassen_min" quadrant edge, in elements (a multiple of 128; 0 = off; default 2048, the smallest value with a measured
  *                     gain on every shape it admits: docs/LAB_NOTES.md), from which a plain update C -= A B^T on the
  *                     handle's main stream takes one Strassen level: seven half-size products for eight, each applied to its
  *                     one or two C quadrants by its own epilogue, ten operand sums through two work buffers.  Rectangular
  *                     updates with min(M, N, K) / 2 >= the value; of a lower / trapezoid update with N / 2 >= twice the value
  *                     the off-diagonal square (the two triangles stay plain launches).  Never with refined leaves.  The result
  *                     differs from the classical product in rounding only (error bound x 3); deterministic.
+ *                     Further keys of the same family, each 0 or a multiple of 128 unless said otherwise:
+ *                       gemm_strassen_lower_min        the threshold of the lower / trapezoid form alone (default 4096: N / 2 >=
+ *                                                      8192).  Setting "gemm_strassen_min" sets both (its default value: both
+ *                                                      defaults); this key afterwards moves the one
+ *                       gemm_strassen_presum_min       quadrant edge (default 1024; 0 = off) from which a level forms the five
+ *                                                      sums of each operand in ONE pass over it (two launches, 18 quadrant
+ *                                                      passes for 30) into ten work blocks -- the same bits
+ *                       gemm_strassen_presum_max_bytes cap in bytes on those ten blocks (default 0 = none).  Over the cap, or
+ *                                                      where the device has no room for them, a level silently takes the
+ *                                                      two-buffer form; gps_profile_get(h, "strassen_presum_fallbacks", &count,
+ *                                                      ...) counts these
  *   "potrf_rl_max"    diagonal blocks of at most this many columns (default 4096) are factored by a right-looking
  *                     sweep over 128-column panels instead of the recursion (tf.cholesky, models/gpr.py:70); 0: recursion only
  *   "potrf_rl_group"  panels per remainder update of that sweep (default 2: K = 256)
