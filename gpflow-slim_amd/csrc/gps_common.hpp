@@ -638,8 +638,12 @@ int gps_launch_psi2_contract(gps_handle_t h, const PsiIn& in, const double* W, i
                              double* out, i64 ldo);
 // gps_gplvm.hip : what every entry on the kernel expectations starts with -- the scope check of the program (who: the entry's name
 // for the message), the check of Xvar, begin_inducing_call, the uploads (Z -> dX, the inputs -> dA, the part views of a Sum ->
-// dPsiParts) and the per-point terms.  parts <- one view per RBF part, in part order, with the part's node in the program.
-struct PsiPart { int node; PsiIn in; };
+// dPsiParts) and the per-point terms.  parts <- one view per RBF part, in part order.
+// One RBF part: its node in the program, its qp columns `dims` of the latent space, and the inputs psi.hip takes.  A single RBF
+// is the part list of length one, on the full arrays in place; the parts of a Sum are packed [*, qp] copies of their columns.
+// psi2 [mp, mp]: where the bound keeps this part's own Psi2 for its gradient (nullptr: not kept).
+struct PsiDims { int d[GPS_MAX_DIMS]; };
+struct PsiPart { int node, qp; PsiDims dims; PsiIn in; double* psi2; };
 int gps_psi_setup(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes, const double* Z, i64 m, const double* Xmu,
                   const double* Xvar, i64 n, i64 q, std::vector<PsiPart>* parts);
 // the rows n0 .. n0 + cnt - 1 of a view
@@ -649,7 +653,6 @@ static inline PsiIn gps_psi_rows(const PsiIn& in, i64 n0, i64 cnt) {
   return s;
 }
 // psi_sum.hip : what a Sum of RBF parts on pairwise disjoint latent dimensions adds to the expectations of its parts
-struct PsiDims { int d[GPS_MAX_DIMS]; };
 // points per chunk of the streamed cross terms (a multiple of 16) and the number of chunks; opt > 0 asks for a chunk length
 void gps_psi_sum_chunking(i64 n, i64 m, int opt, i64* chunk, int* nchunks);
 // dst [rows, qp] <- the columns dims.d[0 .. qp-1] of src [rows, q]
@@ -705,16 +708,6 @@ int gps_launch_kron_alpha(gps_handle_t h, const double* C, const double* x, cons
 // part2 [gps_kron_spectrum_blocks][2] = partial sums of log den and 1 / den, w1 [m] ; w2 [n] (null: no columns pass)
 int gps_launch_kron_spectrum(gps_handle_t h, const double* e1, const double* e2, const int* rng, i64 m, i64 n, double s,
                              double noise_var, double* w1, double* w2, double* part2);
-// gps_gpmc.hip : products of a lower-triangular L [n, n] (only i >= j is read) with skinny right-hand sides kept as planes
-// [r][ld] (one row per column of the [n, r] matrix), and the rank-r seed of the Cholesky adjoint
-//   trans 0: Ft[q][i] = sum_{j <= i} L[i][j] Bt[q][j] ;  trans 1: Ft[q][j] = sum_{i >= j} L[i][j] Bt[q][i]
-// part (trans 1): room for gps_tri_skinny_part_doubles(n, r) doubles
-size_t gps_tri_skinny_part_doubles(i64 n, i64 r);
-int gps_launch_tri_skinny(gps_handle_t h, int trans, const double* L, i64 ldl, i64 n, const double* Bt, i64 ldb, i64 r, double* Ft,
-                          i64 ldf, double* part);
-// P[i][j] = sum_q Ut[q][max(i, j)] Vt[q][min(i, j)] for i, j < n, zero up to np ; accumulate: added to what P holds for i, j < n
-int gps_launch_chol_seed(gps_handle_t h, const double* Ut, i64 ldu, const double* Vt, i64 ldv, i64 r, i64 n, double* P, i64 ldp, i64 np,
-                         int accumulate = 0);
 // diag.hip
 int gps_run_mfma_diag(gps_handle_t h, int waves_per_simd, double* tflops, int* layout_ok);
 int gps_run_gemm_timeline(gps_handle_t h, int op, int lower, i64 m, i64 n, i64 k, int reps, long long* stamps_out,

@@ -8,11 +8,11 @@ static int conditional_predict(gps_handle_t h, InducingSetup& c, const double* f
                                int white, int full_cov, double* fmean_out, double* fvar_out, int* info) {
   const i64 n_new = c.n_new, nsp = c.nsp, k = c.k, mp = c.mp;
   int* d_info = (int*)h->dInfo.p;
-  int rc = gps_launch_fill_info(h, d_info, INT_MAX);
+  KuuFactor kf;
+  int rc = factor_dK(h, mp, true, kf);
   if (rc) return rc;
-  HipOps ops = factor_ops(h, c.linv, mp, d_info);
-  Blocked<HipOps> bl(ops);
-  rc = cond_solve(h, c, ops, bl, f, white, full_cov);
+  Blocked<HipOps>& bl = kf.bl;
+  rc = cond_solve(h, c, bl, f, white, full_cov);
   if (rc) return rc;
   double* dmean; double* dss;
   rc = cond_mean(h, c, &dmean, &dss);
@@ -153,10 +153,8 @@ extern "C" int gps_kmat_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_n
   GPS_HIP(h, hipSetDevice(h->device));
   if (!X2) m = n;
   int ns = 0;
-  int rc = gps_grad_slots(h, prog, n_nodes, &ns);
+  int rc = grad_slot_count(h, "gps_kmat_vjp", prog, n_nodes, n_slots_cap, n_slots_out, &ns);
   if (rc) return rc;
-  if (n_slots_out) *n_slots_out = ns;
-  if (ns > n_slots_cap) return gps_fail(h, GPS_ERR_ARG, "gps_kmat_vjp: grad_slots too small");
   GPS_HIP(h, h->dXnew.ensure((size_t)n * d_all * 8));
   GPS_HIP(h, hipMemcpyAsync(h->dXnew.p, X, (size_t)n * d_all * 8, hipMemcpyHostToDevice, h->stream));
   const double* dX2 = nullptr;
@@ -240,9 +238,7 @@ extern "C" int gps_gauss_kl(gps_handle_t h, const double* K, int64_t m, const do
   Blocked<HipOps> bl(ops);
   rc = bl.potrf_rec(h->dS2.d(), mp, mp, 0, 0);                                       // Lp          :51
   if (rc) return rc;
-  GPS_HIP(h, hipMemcpyAsync(h->dTmp2.p, q_mu, (size_t)m * k * 8, hipMemcpyHostToDevice, h->stream));
-  GPS_HIP(h, hipMemsetAsync(h->dS3.p, 0, (size_t)k * mp * 8, h->stream));
-  rc = gps_launch_transpose(h, h->dTmp2.d(), k, m, k, h->dS3.d(), mp);
+  rc = planes_upload(h, q_mu, m, k, h->dTmp2.d(), h->dS3.d(), mp);
   if (rc) return rc;
   rc = bl.trsv_rec(h->dS2.d(), mp, mp, 0, h->dS3.d(), mp, k);                          // alpha       :52
   if (rc) return rc;

@@ -43,92 +43,72 @@ static int gplvm_check_prog(gps_handle_t h, const char* who, const gps_kern_node
   return GPS_OK;
 }
 
-// One RBF part: its node, its columns of the latent space, and the inputs psi.hip takes.  A single RBF is one part on the full
-// arrays (in = what gplvm_upload always made); the parts of a Sum are packed [*, qp] copies of their columns (dPsiParts).
-struct GplvmPart { int node, qp; PsiDims dims; PsiIn in; double* psi2; };     // psi2 [mp, mp]: this part's Psi2 (the bound)
-
-static PsiIn psi_rows(const PsiIn& in, i64 n0, i64 cnt) { return gps_psi_rows(in, n0, cnt); }
-
-// The part views of a Sum: per part [Z [m, qp] | Xmu | Xvar | A1 | A2 [n, qp] each | C1 | C2 [n] | par [40]], then (with_psi2)
-// one [mp, mp] matrix per part.  Z is in dX, Xmu and Xvar are at dMu / dVar (gplvm_upload).
-static int gplvm_part_views(gps_handle_t h, const gps_kern_node_t* prog, const std::vector<int>& nodes, const double* dMu,
-                            const double* dVar, i64 n, i64 m, i64 q, bool with_psi2, std::vector<GplvmPart>* parts) {
+// Z -> dX ; into dA: [Xmu | Xvar | A1 | A2] [n, q] each, [C1 | C2] [n], par [1 + 32], Y [n, r] (optional, *dY) ; then, part by part,
+// the part's view of them (PsiPart, gps_common.hpp) and its per-point terms.  A single RBF is one part on these arrays in place.
+// The parts of a Sum are packed copies in dPsiParts: per part [Z [m, qp] | Xmu | Xvar | A1 | A2 [n, qp] each | C1 | C2 [n] |
+// par [40]], then (psi2_total given) one [mp, mp] matrix per part for its own Psi2.  psi2_total [mp, mp]: where the caller will
+// form the whole Psi2 -- which is a single part's own, kept there without a copy.
+static int gplvm_upload(gps_handle_t h, const gps_kern_node_t* prog, const std::vector<int>& nodes, const double* Z, i64 m,
+                        const double* Xmu, const double* Xvar, i64 n, i64 q, const double* Y, i64 r, double* psi2_total, double** dY,
+                        std::vector<PsiPart>* parts) {
   const i64 mp = gps_pad(m);
-  size_t total = 0;
-  for (int nd : nodes) total += (size_t)prog[nd].n_dims * (m + 4 * n) + 2 * (size_t)n + 40;
-  if (with_psi2) total += nodes.size() * (size_t)mp * mp;
-  GPS_HIP(h, h->dPsiParts.ensure(total * 8));
-  double* at = h->dPsiParts.d();
+  GPS_HIP(h, h->dX.ensure((size_t)m * q * 8));
+  GPS_HIP(h, hipMemcpyAsync(h->dX.p, Z, (size_t)m * q * 8, hipMemcpyHostToDevice, h->stream));
+  const size_t nq = (size_t)n * q;
+  GPS_HIP(h, h->dA.ensure((4 * nq + 2 * (size_t)n + 40 + (size_t)n * r) * 8));
+  double* dMu = h->dA.d(); double* dVar = dMu + nq; double* dYraw = dVar + 3 * nq + 2 * (size_t)n + 40;
+  GPS_HIP(h, hipMemcpyAsync(dMu, Xmu, nq * 8, hipMemcpyHostToDevice, h->stream));
+  GPS_HIP(h, hipMemcpyAsync(dVar, Xvar, nq * 8, hipMemcpyHostToDevice, h->stream));
+  if (Y) GPS_HIP(h, hipMemcpyAsync(dYraw, Y, (size_t)n * r * 8, hipMemcpyHostToDevice, h->stream));
+  if (dY) *dY = dYraw;
+  const bool packed = nodes.size() > 1;
+  double* at = dVar + nq;                                           // (one part: A1 | A2 | C1 | C2 | par behind Xvar)
+  if (packed) {
+    size_t total = 0;
+    for (int nd : nodes) total += (size_t)prog[nd].n_dims * (m + 4 * n) + 2 * (size_t)n + 40;
+    if (psi2_total) total += nodes.size() * (size_t)mp * mp;
+    GPS_HIP(h, h->dPsiParts.ensure(total * 8));
+    at = h->dPsiParts.d();
+  }
   parts->clear();
   for (int nd : nodes) {
-    GplvmPart pt;
-    pt.node = nd; pt.qp = prog[nd].n_dims; pt.psi2 = nullptr;
+    PsiPart pt;
+    pt.node = nd; pt.qp = prog[nd].n_dims; pt.psi2 = packed ? nullptr : psi2_total;
     for (int k = 0; k < GPS_MAX_DIMS; ++k) pt.dims.d[k] = k < pt.qp ? prog[nd].active_dims[k] : 0;
-    const size_t nq = (size_t)n * pt.qp;
-    double* dZ = at; double* pMu = dZ + (size_t)m * pt.qp; double* pVar = pMu + nq; double* A1 = pVar + nq; double* A2 = A1 + nq;
-    double* C1 = A2 + nq; double* C2 = C1 + n; double* dPar = C2 + n;
+    const size_t nqp = (size_t)n * pt.qp;
+    double* dZ = h->dX.d(); double* pMu = dMu; double* pVar = dVar;
+    if (packed) {
+      dZ = at; pMu = dZ + (size_t)m * pt.qp; pVar = pMu + nqp; at = pVar + nqp;
+      int rc = gps_launch_psi_gather(h, h->dX.d(), m, (int)q, pt.dims, pt.qp, dZ);
+      if (rc) return rc;
+      rc = gps_launch_psi_gather(h, dMu, n, (int)q, pt.dims, pt.qp, pMu);
+      if (rc) return rc;
+      rc = gps_launch_psi_gather(h, dVar, n, (int)q, pt.dims, pt.qp, pVar);
+      if (rc) return rc;
+    }
+    double* A1 = at; double* A2 = A1 + nqp; double* C1 = A2 + nqp; double* C2 = C1 + n; double* dPar = C2 + n;
     at = dPar + 40;
-    int rc = gps_launch_psi_gather(h, h->dX.d(), m, (int)q, pt.dims, pt.qp, dZ);
-    if (rc) return rc;
-    rc = gps_launch_psi_gather(h, dMu, n, (int)q, pt.dims, pt.qp, pMu);
-    if (rc) return rc;
-    rc = gps_launch_psi_gather(h, dVar, n, (int)q, pt.dims, pt.qp, pVar);
-    if (rc) return rc;
     double par[1 + GPS_MAX_DIMS] = {};
     par[0] = prog[nd].variance;
     for (int k = 0; k < pt.qp; ++k) par[1 + k] = prog[nd].lengthscales[k];
     GPS_HIP(h, h->ring.upload(dPar, par, sizeof(par), h->stream));
     pt.in = PsiIn{dZ, pMu, pVar, dPar, A1, C1, A2, C2, n, m, pt.qp};
-    rc = gps_launch_psi_prep(h, pt.in);
+    int rc = gps_launch_psi_prep(h, pt.in);
     if (rc) return rc;
     parts->push_back(pt);
   }
-  if (with_psi2)
-    for (GplvmPart& pt : *parts) { pt.psi2 = at; at += (size_t)mp * mp; }
+  if (packed && psi2_total)
+    for (PsiPart& pt : *parts) { pt.psi2 = at; at += (size_t)mp * mp; }
   return GPS_OK;
 }
 
-// Z -> dX ; into dA: [Xmu | Xvar | A1 | A2] [n, q] each, [C1 | C2] [n], par [1 + 32], Y [n, r] (optional) ; then the per-point terms
-// parts <- the one part of a single RBF (on these arrays), or the packed views of a Sum's parts (with_psi2: see gplvm_part_views)
-static int gplvm_upload(gps_handle_t h, const gps_kern_node_t* prog, const std::vector<int>& nodes, const double* Z, i64 m,
-                        const double* Xmu, const double* Xvar, i64 n, i64 q, const double* Y, i64 r, bool with_psi2, PsiIn* in,
-                        double** dY, std::vector<GplvmPart>* parts) {
-  GPS_HIP(h, h->dX.ensure((size_t)m * q * 8));
-  GPS_HIP(h, hipMemcpyAsync(h->dX.p, Z, (size_t)m * q * 8, hipMemcpyHostToDevice, h->stream));
-  const size_t nq = (size_t)n * q;
-  GPS_HIP(h, h->dA.ensure((4 * nq + 2 * (size_t)n + 40 + (size_t)n * r) * 8));
-  double* base = h->dA.d();
-  double* dMu = base; double* dVar = dMu + nq; double* dA1 = dVar + nq; double* dA2 = dA1 + nq;
-  double* dC1 = dA2 + nq; double* dC2 = dC1 + n; double* dPar = dC2 + n; double* dYraw = dPar + 40;
-  GPS_HIP(h, hipMemcpyAsync(dMu, Xmu, nq * 8, hipMemcpyHostToDevice, h->stream));
-  GPS_HIP(h, hipMemcpyAsync(dVar, Xvar, nq * 8, hipMemcpyHostToDevice, h->stream));
-  if (nodes.size() > 1) {
-    if (Y) GPS_HIP(h, hipMemcpyAsync(dYraw, Y, (size_t)n * r * 8, hipMemcpyHostToDevice, h->stream));
-    if (dY) *dY = dYraw;
-    *in = PsiIn{h->dX.d(), dMu, dVar, dPar, dA1, dC1, dA2, dC2, n, m, (int)q};       // (the full arrays: no kernel of psi.hip runs on them)
-    return gplvm_part_views(h, prog, nodes, dMu, dVar, n, m, q, with_psi2, parts);
-  }
-  double par[1 + GPS_MAX_DIMS] = {};
-  par[0] = prog[0].variance;
-  for (i64 i = 0; i < q; ++i) par[1 + i] = prog[0].lengthscales[i];
-  GPS_HIP(h, h->ring.upload(dPar, par, sizeof(par), h->stream));
-  if (Y) GPS_HIP(h, hipMemcpyAsync(dYraw, Y, (size_t)n * r * 8, hipMemcpyHostToDevice, h->stream));
-  if (dY) *dY = dYraw;
-  *in = PsiIn{h->dX.d(), dMu, dVar, dPar, dA1, dC1, dA2, dC2, n, m, (int)q};
-  GplvmPart pt;
-  pt.node = 0; pt.qp = (int)q; pt.in = *in; pt.psi2 = nullptr;
-  for (int k = 0; k < GPS_MAX_DIMS; ++k) pt.dims.d[k] = k < (int)q ? k : 0;
-  parts->assign(1, pt);
-  return gps_launch_psi_prep(h, *in);
-}
-
-// ---- what a Sum adds to its parts' Psi2 ------------------------------------------------------------------------------------
-// Psi2 [mp, mp] <- sum_p Psi2_p (each kept at parts[p].psi2 when that is set, else formed in `tmp`) + C + C^T with
+// ---- Psi2 of a part list ---------------------------------------------------------------------------------------------------
+// Psi2 [mp, mp] <- sum_p Psi2_p (each kept at parts[p].psi2 when that is set, else formed in `tmp`) and, for two or more parts, + C + C^T with
 // C = sum_{p < p'} T_p^T T_p' streamed over chunks of points: per chunk every T_p block [cnt, m] (psi1_kernel on the rows of the
 // part view), transposed to [mp, chunk] with exact zeros around it, then C += T_p^T U_p, U_p = sum_{p' > p} T_p', on the fp64
 // GEMM -- chunks in chunk order, parts in part order.  C [mp, mp] and tmp [mp, mp] are scratch.  Device memory beyond them:
-// (2 P + 1) blocks of pad(m) x chunk in dPsiWork; no [N, M] array exists.
-static int gplvm_sum_psi2(gps_handle_t h, const std::vector<GplvmPart>& parts, double* Psi2, double* C, double* tmp, i64 mp) {
+// (2 P + 1) blocks of pad(m) x chunk in dPsiWork; no [N, M] array exists.  One part: C and tmp are not touched.
+static int gplvm_psi2(gps_handle_t h, const std::vector<PsiPart>& parts, double* Psi2, double* C, double* tmp, i64 mp) {
   const int P = (int)parts.size();
   const i64 n = parts[0].in.n, m = parts[0].in.m;
   int rc;
@@ -136,9 +116,11 @@ static int gplvm_sum_psi2(gps_handle_t h, const std::vector<GplvmPart>& parts, d
     double* dst = p == 0 ? Psi2 : (parts[p].psi2 ? parts[p].psi2 : tmp);
     rc = gps_launch_psi2(h, parts[p].in, dst, mp);
     if (rc) return rc;
-    if (p == 0 && parts[0].psi2) GPS_HIP(h, hipMemcpyAsync(parts[0].psi2, Psi2, (size_t)mp * mp * 8, hipMemcpyDeviceToDevice, h->stream));
+    if (p == 0 && parts[0].psi2 && parts[0].psi2 != Psi2)         // (a single part's own Psi2 is the total: kept where it is)
+      GPS_HIP(h, hipMemcpyAsync(parts[0].psi2, Psi2, (size_t)mp * mp * 8, hipMemcpyDeviceToDevice, h->stream));
     if (p > 0) { rc = gps_launch_psi_add(h, Psi2, dst, mp * mp); if (rc) return rc; }
   }
+  if (P == 1) return GPS_OK;                                       // no cross terms
   i64 ch; int nchunks;
   gps_psi_sum_chunking(n, m, h->psi_sum_chunk, &ch, &nchunks);
   const size_t blk_d = (size_t)ch * m, blk_t = (size_t)mp * ch;
@@ -148,7 +130,7 @@ static int gplvm_sum_psi2(gps_handle_t h, const std::vector<GplvmPart>& parts, d
     const i64 n0 = (i64)c * ch, cnt = n0 + ch < n ? ch : n - n0, k16 = 16 * ((cnt + 15) / 16);
     GPS_HIP(h, hipMemsetAsync(Tt, 0, (size_t)P * blk_t * 8, h->stream));
     for (int p = 0; p < P; ++p) {
-      rc = gps_launch_psi1(h, psi_rows(parts[p].in, n0, cnt), Td + p * blk_d);
+      rc = gps_launch_psi1(h, gps_psi_rows(parts[p].in, n0, cnt), Td + p * blk_d);
       if (rc) return rc;
       rc = gps_launch_transpose(h, Td + p * blk_d, m, cnt, m, Tt + p * blk_t, ch);
       if (rc) return rc;
@@ -170,33 +152,40 @@ static int gplvm_check_inputs(gps_handle_t h, const char* who, const double* Xva
   return GPS_OK;
 }
 
-// the common start of the entries on the kernel expectations outside this file (gps_uncond.hip): see gps_common.hpp
+// the common start of the entries on the kernel expectations, here and in gps_uncond.hip: see gps_common.hpp
 int gps_psi_setup(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes, const double* Z, i64 m, const double* Xmu,
-                  const double* Xvar, i64 n, i64 q, std::vector<PsiPart>* out) {
+                  const double* Xvar, i64 n, i64 q, std::vector<PsiPart>* parts) {
   std::vector<int> nodes;
   int rc = gplvm_check_prog(h, who, prog, n_nodes, q, &nodes);
   if (rc) return rc;
   rc = gplvm_check_inputs(h, who, Xvar, n, q, true);
   if (rc) return rc;
-  rc = begin_inducing_call(h, nullptr);
+  rc = begin_inducing_call(h, nullptr);                          // (dX is overwritten: a resident GPR factor is gone)
   if (rc) return rc;
-  PsiIn in;
-  std::vector<GplvmPart> parts;
-  rc = gplvm_upload(h, prog, nodes, Z, m, Xmu, Xvar, n, q, nullptr, 0, false, &in, nullptr, &parts);
-  if (rc) return rc;
-  out->clear();
-  for (const GplvmPart& pt : parts) out->push_back(PsiPart{pt.node, pt.in});
+  return gplvm_upload(h, prog, nodes, Z, m, Xmu, Xvar, n, q, nullptr, 0, nullptr, nullptr, parts);
+}
+
+extern "C" int gps_psi_sum_set_chunk(gps_handle_t h, int64_t chunk) {
+  if (!h || chunk < 0) return gps_fail(h, GPS_ERR_ARG, "gps_psi_sum_set_chunk: bad argument");
+  h->psi_sum_chunk = chunk > 32768 ? 32768 : (int)chunk;
   return GPS_OK;
 }
 
-// gps_psi_stats for a Sum: the parts' expectations added up, plus the cross terms (streamed for Psi2, a map kernel for psi2n)
-static int psi_stats_sum(gps_handle_t h, const std::vector<GplvmPart>& parts, double* psi1_out, double* psi2_out, double* psi2n_out) {
+// The parts' expectations added up in part order, plus -- two or more parts -- the cross terms (streamed for Psi2, a map kernel
+// for psi2n over the parts' Psi1).
+extern "C" int gps_psi_stats(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
+                             const double* Xmu, const double* Xvar, int64_t n, int64_t q, double* psi1_out, double* psi2_out,
+                             double* psi2n_out) {
+  if (!h || !Z || !Xmu || !Xvar || m <= 0 || n <= 0 || q <= 0) return gps_fail(h, GPS_ERR_ARG, "gps_psi_stats: bad argument");
+  std::vector<PsiPart> parts;
+  int rc = gps_psi_setup(h, "gps_psi_stats", prog, n_nodes, Z, m, Xmu, Xvar, n, q, &parts);
+  if (rc) return rc;
   const int P = (int)parts.size();
-  const i64 n = parts[0].in.n, m = parts[0].in.m, mp = gps_pad(m);
+  const bool cross = P > 1;
+  const i64 mp = gps_pad(m);
   const size_t nm = (size_t)n * m;
-  int rc;
   if (psi1_out) {
-    GPS_HIP(h, h->dLikOut.ensure(2 * nm * 8));
+    GPS_HIP(h, h->dLikOut.ensure((cross ? 2 : 1) * nm * 8));
     double* acc = h->dLikOut.d();
     for (int p = 0; p < P; ++p) {
       rc = gps_launch_psi1(h, parts[p].in, p == 0 ? acc : acc + nm);
@@ -208,73 +197,27 @@ static int psi_stats_sum(gps_handle_t h, const std::vector<GplvmPart>& parts, do
   }
   if (psi2_out) {
     GPS_HIP(h, h->dS1.ensure((size_t)mp * mp * 8));
-    GPS_HIP(h, h->dS2.ensure((size_t)mp * mp * 8));
-    GPS_HIP(h, h->dS3.ensure((size_t)mp * mp * 8));
-    rc = gplvm_sum_psi2(h, parts, h->dS1.d(), h->dS2.d(), h->dS3.d(), mp);
+    if (cross) {                                                   // (the scratch of the cross terms)
+      GPS_HIP(h, h->dS2.ensure((size_t)mp * mp * 8));
+      GPS_HIP(h, h->dS3.ensure((size_t)mp * mp * 8));
+    }
+    rc = gplvm_psi2(h, parts, h->dS1.d(), h->dS2.d(), h->dS3.d(), mp);
     if (rc) return rc;
     GPS_HIP(h, hipMemcpy2DAsync(psi2_out, (size_t)m * 8, h->dS1.p, (size_t)mp * 8, (size_t)m * 8, (size_t)m, hipMemcpyDeviceToHost, h->stream));
     GPS_HIP(h, hipStreamSynchronize(h->stream));
   }
   if (psi2n_out) {
     const size_t nmm = nm * m;
-    GPS_HIP(h, h->dLikOut.ensure((2 * nmm + (size_t)P * nm) * 8));
+    GPS_HIP(h, h->dLikOut.ensure((cross ? 2 * nmm + (size_t)P * nm : nmm) * 8));
     double* acc = h->dLikOut.d(); double* tmp = acc + nmm; double* T = tmp + nmm;
     for (int p = 0; p < P; ++p) {
       rc = gps_launch_psi2n(h, parts[p].in, p == 0 ? acc : tmp);
       if (rc) return rc;
       if (p > 0) { rc = gps_launch_psi_add(h, acc, tmp, (i64)nmm); if (rc) return rc; }
-      rc = gps_launch_psi1(h, parts[p].in, T + p * nm);
-      if (rc) return rc;
+      if (cross) { rc = gps_launch_psi1(h, parts[p].in, T + p * nm); if (rc) return rc; }
     }
-    rc = gps_launch_psi2n_cross(h, T, P, n, m, acc);
-    if (rc) return rc;
+    if (cross) { rc = gps_launch_psi2n_cross(h, T, P, n, m, acc); if (rc) return rc; }
     GPS_HIP(h, hipMemcpyAsync(psi2n_out, acc, nmm * 8, hipMemcpyDeviceToHost, h->stream));
-  }
-  GPS_HIP(h, hipStreamSynchronize(h->stream));
-  return GPS_OK;
-}
-
-extern "C" int gps_psi_sum_set_chunk(gps_handle_t h, int64_t chunk) {
-  if (!h || chunk < 0) return gps_fail(h, GPS_ERR_ARG, "gps_psi_sum_set_chunk: bad argument");
-  h->psi_sum_chunk = chunk > 32768 ? 32768 : (int)chunk;
-  return GPS_OK;
-}
-
-extern "C" int gps_psi_stats(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, int64_t m,
-                             const double* Xmu, const double* Xvar, int64_t n, int64_t q, double* psi1_out, double* psi2_out,
-                             double* psi2n_out) {
-  if (!h || !Z || !Xmu || !Xvar || m <= 0 || n <= 0 || q <= 0) return gps_fail(h, GPS_ERR_ARG, "gps_psi_stats: bad argument");
-  std::vector<int> nodes;
-  int rc = gplvm_check_prog(h, "gps_psi_stats", prog, n_nodes, q, &nodes);
-  if (rc) return rc;
-  rc = gplvm_check_inputs(h, "gps_psi_stats", Xvar, n, q, true);
-  if (rc) return rc;
-  rc = begin_inducing_call(h, nullptr);                          // (dX is overwritten: a resident GPR factor is gone)
-  if (rc) return rc;
-  PsiIn in;
-  std::vector<GplvmPart> parts;
-  rc = gplvm_upload(h, prog, nodes, Z, m, Xmu, Xvar, n, q, nullptr, 0, false, &in, nullptr, &parts);
-  if (rc) return rc;
-  if (parts.size() > 1) return psi_stats_sum(h, parts, psi1_out, psi2_out, psi2n_out);
-  if (psi1_out) {
-    GPS_HIP(h, h->dLikOut.ensure((size_t)n * m * 8));
-    rc = gps_launch_psi1(h, in, h->dLikOut.d());
-    if (rc) return rc;
-    GPS_HIP(h, hipMemcpyAsync(psi1_out, h->dLikOut.p, (size_t)n * m * 8, hipMemcpyDeviceToHost, h->stream));
-    GPS_HIP(h, hipStreamSynchronize(h->stream));
-  }
-  if (psi2_out) {
-    GPS_HIP(h, h->dLikOut.ensure((size_t)m * m * 8));
-    rc = gps_launch_psi2(h, in, h->dLikOut.d(), m);
-    if (rc) return rc;
-    GPS_HIP(h, hipMemcpyAsync(psi2_out, h->dLikOut.p, (size_t)m * m * 8, hipMemcpyDeviceToHost, h->stream));
-    GPS_HIP(h, hipStreamSynchronize(h->stream));
-  }
-  if (psi2n_out) {
-    GPS_HIP(h, h->dLikOut.ensure((size_t)n * m * m * 8));
-    rc = gps_launch_psi2n(h, in, h->dLikOut.d());
-    if (rc) return rc;
-    GPS_HIP(h, hipMemcpyAsync(psi2n_out, h->dLikOut.p, (size_t)n * m * m * 8, hipMemcpyDeviceToHost, h->stream));
   }
   GPS_HIP(h, hipStreamSynchronize(h->stream));
   return GPS_OK;
@@ -287,7 +230,7 @@ extern "C" int gps_psi_stats(gps_handle_t h, const gps_kern_node_t* prog, int n_
 // (gplvm.py:131-165 without the KL term, which is elementwise over [N, Q] and stays with the caller.)
 // Left on the device for the gradient: dK / dLinv = L ; dS3 / dS4 = LB ; dS2 = G (symmetric) ; dS1 = Psi2 [mp, mp] ; dX = Z ;
 // dA = the inputs (gplvm_upload) ; dAlpha = [Y^T [r][np] | v^T [r][mp] | u^T [r][mp]].
-struct GplvmFwd { PsiIn in; std::vector<GplvmPart> parts; double* dY; double yy, trG, u2, slogLB, psi0; };
+struct GplvmFwd { std::vector<PsiPart> parts; double* dY; double yy, trG, u2, slogLB, psi0; };
 
 static int gplvm_forward(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, i64 m, const double* Xmu,
                          const double* Xvar, i64 n, i64 q, double jitter, double noise_var, const double* Y, i64 r,
@@ -299,30 +242,20 @@ static int gplvm_forward(gps_handle_t h, const gps_kern_node_t* prog, int n_node
   std::vector<int> nodes;
   rc = gplvm_check_prog(h, "gps_bgplvm", prog, n_nodes, q, &nodes);
   if (rc) return rc;
-  rc = gplvm_upload(h, prog, nodes, Z, m, Xmu, Xvar, n, q, Y, r, true, &f->in, &f->dY, &f->parts);
-  if (rc) return rc;
-  const bool sum = f->parts.size() > 1;
-  GPS_HIP(h, h->dK.ensure((size_t)mp * mp * 8));
-  GPS_HIP(h, h->dLinv.ensure(linv_bytes(mp)));
   GPS_HIP(h, h->dS1.ensure((size_t)mp * mp * 8));
   GPS_HIP(h, h->dS2.ensure((size_t)mp * mp * 8));
   GPS_HIP(h, h->dS3.ensure((size_t)mp * mp * 8));
   GPS_HIP(h, h->dS4.ensure(linv_bytes(mp)));
-  int* d_info = (int*)h->dInfo.p;
-  rc = gps_launch_fill_info(h, d_info, INT_MAX);
-  if (rc) return rc;
-  rc = inducing_kuu(h, prog, n_nodes, m, q, jitter);
-  if (rc) return rc;
-  HipOps opsL = factor_ops(h, h->dLinv.d(), mp, d_info);
-  Blocked<HipOps> blL(opsL);
-  rc = blL.potrf_rec(h->dK.d(), mp, mp, 0, 0);
-  if (rc) return rc;
-  rc = classify_blocks(h, opsL, h->dK.d(), mp, mp);
-  if (rc) return rc;
-  // Psi2 -> dS1 ; G = L^-1 Psi2 L^-T -> dS2 through dS3: (Psi2 L^-T)^T L^-T
   double* Psi2 = h->dS1.d(); double* G = h->dS2.d(); double* LB = h->dS3.d();
-  if (sum) rc = gplvm_sum_psi2(h, f->parts, Psi2, G, LB, mp);            // (G, LB: scratch until they are written below)
-  else { rc = gps_launch_psi2(h, f->in, Psi2, mp); f->parts[0].psi2 = Psi2; }
+  rc = gplvm_upload(h, prog, nodes, Z, m, Xmu, Xvar, n, q, Y, r, Psi2, &f->dY, &f->parts);
+  if (rc) return rc;
+  KuuFactor kfL;                                                   // (d_info is read back once, with the reductions below)
+  rc = kuu_factor(h, prog, n_nodes, m, q, jitter, true, kfL);
+  if (rc) return rc;
+  Blocked<HipOps>& blL = kfL.bl;
+  int* d_info = kfL.ops.d_info;
+  // Psi2 -> dS1 ; G = L^-1 Psi2 L^-T -> dS2 through dS3: (Psi2 L^-T)^T L^-T
+  rc = gplvm_psi2(h, f->parts, Psi2, G, LB, mp);                   // (G, LB: scratch until they are written below)
   if (rc) return rc;
   GPS_HIP(h, hipMemcpyAsync(LB, Psi2, (size_t)mp * mp * 8, hipMemcpyDeviceToDevice, h->stream));
   rc = blL.trsm_rec(h->dK.d(), mp, mp, 0, LB, mp, mp);
@@ -351,15 +284,11 @@ static int gplvm_forward(gps_handle_t h, const gps_kern_node_t* prog, int n_node
   GPS_HIP(h, hipMemsetAsync(dYt, 0, (size_t)r * np * 8, h->stream));
   rc = gps_launch_transpose(h, f->dY, r, n, r, dYt, np);
   if (rc) return rc;
-  if (sum) {                                                       // p = sum_p T_p^T Y, part by part through dU (free until v is copied there)
-    for (size_t p = 0; p < f->parts.size() && !rc; ++p) {
-      rc = gps_launch_psi1_py(h, f->parts[p].in, f->dY, r, p == 0 ? dV : dU, mp);
-      if (!rc && p > 0) rc = gps_launch_psi_add(h, dV, dU, r * mp);
-    }
-  } else {
-    rc = gps_launch_psi1_py(h, f->in, f->dY, r, dV, mp);
+  for (size_t p = 0; p < f->parts.size(); ++p) {                   // p = sum_p T_p^T Y, part by part through dU (free until v is copied there)
+    rc = gps_launch_psi1_py(h, f->parts[p].in, f->dY, r, p == 0 ? dV : dU, mp);
+    if (!rc && p > 0) rc = gps_launch_psi_add(h, dV, dU, r * mp);
+    if (rc) return rc;
   }
-  if (rc) return rc;
   rc = blL.trsv_rec(h->dK.d(), mp, mp, 0, dV, mp, r);
   if (rc) return rc;
   GPS_HIP(h, hipMemcpyAsync(dU, dV, (size_t)r * mp * 8, hipMemcpyDeviceToDevice, h->stream));
@@ -379,7 +308,7 @@ static int gplvm_forward(gps_handle_t h, const gps_kern_node_t* prog, int n_node
   for (int b = 0; b < 64; ++b) { f->slogLB += hp[2 * b]; f->u2 += hp[2 * b + 1]; }
   for (i64 i = 0; i < n * r; ++i) f->yy += Y[i] * Y[i];
   double vsum = 0.0;
-  for (const GplvmPart& pt : f->parts) vsum += prog[pt.node].variance;
+  for (const PsiPart& pt : f->parts) vsum += prog[pt.node].variance;
   f->psi0 = N * vsum;
   if (bound_out) {
     const double psi0 = f->psi0;
@@ -393,9 +322,9 @@ static int gplvm_args(gps_handle_t h, const char* who, const gps_kern_node_t* pr
                       const double* Xmu, const double* Xvar, i64 n, i64 q, double noise_var, const double* Y, i64 r) {
   if (!h || !Z || !Xmu || !Xvar || !Y || m <= 0 || n <= 0 || q <= 0 || r <= 0 || !(noise_var > 0.0))
     return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": bad argument");
-  if (h->allreduce) return gps_fail(h, GPS_ERR_UNSUPPORTED, std::string(who) + ": not available with the data sharded over ranks");
-  if (r > GPS_TILE) return gps_fail(h, GPS_ERR_UNSUPPORTED, std::string(who) + ": at most 128 outputs");
-  int rc = gplvm_check_prog(h, who, prog, n_nodes, q);
+  int rc = refuse_unsupported(h, who, true, r, "outputs");
+  if (rc) return rc;
+  rc = gplvm_check_prog(h, who, prog, n_nodes, q);
   if (rc) return rc;
   return gplvm_check_inputs(h, who, Xvar, n, q, true);
 }
@@ -441,7 +370,7 @@ extern "C" int gps_bgplvm(gps_handle_t h, const gps_kern_node_t* prog, int n_nod
 // sum, not as a difference), Bar = D sym(P2) on the fp64 GEMM (P2 = 2 Psi2_bar as the caller holds it, sym(P2) = (P2 + P2^T) / 2),
 // its transpose for the per-point pass, and the two passes of psi.hip with the dense term added.  out_n[p] [2 qp + 1][n],
 // out_z[p] [qp][mp]; the z partials of all chunks are folded once, in chunk order.  Workspace in dPsiWork: O(P M chunk).
-static int gplvm_sum_psi1_vjp(gps_handle_t h, const std::vector<GplvmPart>& parts, const double* dY, const double* dYt, i64 ldy,
+static int gplvm_sum_psi1_vjp(gps_handle_t h, const std::vector<PsiPart>& parts, const double* dY, const double* dYt, i64 ldy,
                               const double* dW, i64 mp, i64 r, const double* P2, const std::vector<double*>& out_n,
                               const std::vector<double*>& out_z) {
   const int P = (int)parts.size();
@@ -454,7 +383,7 @@ static int gplvm_sum_psi1_vjp(gps_handle_t h, const std::vector<GplvmPart>& part
   const i64 zchunk = (ch + nz - 1) / nz;
   nz = (ch + zchunk - 1) / zchunk;
   int qsum = 0;
-  for (const GplvmPart& pt : parts) qsum += pt.qp;
+  for (const PsiPart& pt : parts) qsum += pt.qp;
   const size_t blk_d = (size_t)ch * m, blk_b = (size_t)cpad * mp, zslots = (size_t)nchunks * nz;
   GPS_HIP(h, h->dPsiWork.ensure(((size_t)P * blk_d + 3 * blk_b + (size_t)mp * mp + zslots * qsum * mp) * 8));
   double* Td = h->dPsiWork.d(); double* D = Td + (size_t)P * blk_d; double* Bar = D + blk_b; double* BarT = Bar + blk_b;
@@ -466,7 +395,7 @@ static int gplvm_sum_psi1_vjp(gps_handle_t h, const std::vector<GplvmPart>& part
   for (int c = 0; c < nchunks; ++c) {
     const i64 n0 = (i64)c * ch, cnt = n0 + ch < n ? ch : n - n0, cp = gps_pad(cnt);
     for (int p = 0; p < P; ++p) {
-      rc = gps_launch_psi1(h, psi_rows(parts[p].in, n0, cnt), Td + p * blk_d);
+      rc = gps_launch_psi1(h, gps_psi_rows(parts[p].in, n0, cnt), Td + p * blk_d);
       if (rc) return rc;
     }
     for (int p = 0; p < P; ++p) {
@@ -493,10 +422,8 @@ static int bgplvm_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_n
                             double* bound, double* grad_slots, int n_slots_cap, int* n_slots_out, double* grad_noise, double* grad_Z,
                             double* grad_Xmu, double* grad_Xvar, int* info) {
   int ns = 0;
-  int rc = gps_grad_slots(h, prog, n_nodes, &ns);
+  int rc = grad_slot_count(h, "gps_bgplvm_grad", prog, n_nodes, n_slots_cap, n_slots_out, &ns);
   if (rc) return rc;
-  if (n_slots_out) *n_slots_out = ns;
-  if (ns > n_slots_cap) return gps_fail(h, GPS_ERR_ARG, "gps_bgplvm_grad: grad_slots too small");
   {
     int want = 0;                                                   // one variance and n_dims lengthscale slots per RBF node, in program order
     for (int i = 0; i < n_nodes; ++i) if (prog[i].op == GPS_K_RBF) want += 1 + prog[i].n_dims;
@@ -544,9 +471,7 @@ static int bgplvm_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_n
   GPS_HIP(h, h->dTmp.ensure((size_t)mp * mp * 8));
   GPS_HIP(h, h->dTmp2.ensure((size_t)mp * mp * 8));
   double* U = h->dTmp.d(); double* T1 = h->dG1.d(); double* P2 = h->dTmp2.d();
-  rc = gps_launch_transpose(h, L, mp, mp, mp, U, mp);
-  if (rc) return rc;
-  rc = gps_launch_tri_map(h, U, mp, mp, 3);
+  rc = upper_factor(h, L, mp, U);
   if (rc) return rc;
   GPS_HIP(h, hipMemcpyAsync(T1, B2, (size_t)mp * mp * 8, hipMemcpyDeviceToDevice, h->stream));
   rc = blL.trsm_rn_rec(U, mp, mp, 0, T1, mp, mp);                // 2 G_bar L^-1
@@ -580,8 +505,10 @@ static int bgplvm_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_n
     rc = gps_launch_psi2_vjp(h, f.parts[p].in, PK, mp, po[p].d2n, po[p].d2z, mp);
     if (rc) return rc;
   }
+  // The one place where a single RBF and a Sum take different algorithms: one part's Psi1_bar = Y W^T has rank R and is formed
+  // inside the VJP; with more parts T_p_bar gets the dense term (Psi1 - T_p) (Psi2_bar + Psi2_bar^T) and is streamed over chunks.
   if (P == 1) {
-    rc = gps_launch_psi1_vjp(h, f.in, f.dY, dYt, np, dW, mp, r, po[0].d1n, po[0].d1z, mp);
+    rc = gps_launch_psi1_vjp(h, f.parts[0].in, f.dY, dYt, np, dW, mp, r, po[0].d1n, po[0].d1z, mp);
   } else {
     std::vector<double*> d1n, d1z;
     for (PartOut& o : po) { d1n.push_back(o.d1n); d1z.push_back(o.d1z); }
@@ -624,24 +551,22 @@ static int bgplvm_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_n
   if (rc) return rc;
   GPS_HIP(h, hipStreamSynchronize(h->stream));                                    // (the read-backs above; P2 = dTmp2 was copied before the adjoint reused it)
   for (int sI = 0; sI < ns; ++sI) grad_slots[sI] = 0.0;
-  {
-    std::vector<double> uu((size_t)ns, 0.0);
-    rc = gps_launch_kmat_vjp(h, prog, n_nodes, h->dX.d(), m, nullptr, 0, q, Kbar2, mp, 0, uu.data());
-    if (rc) return rc;
-    for (int sI = 0; sI < ns; ++sI) grad_slots[sI] += 0.5 * uu[sI];
-  }
   std::vector<double> gz((size_t)m * q, 0.0);
-  rc = gps_launch_kmat_input_vjp(h, prog, n_nodes, h->dX.d(), m, nullptr, 0, q, Kbar2, mp, 1.0, gz.data());
+  rc = kuu_side_vjp(h, prog, n_nodes, m, q, Kbar2, mp, ns, grad_slots, gz.data());
   if (rc) return rc;
   GPS_HIP(h, hipStreamSynchronize(h->stream));
   // ---- assembly of the expectation VJPs on the host, part by part into the part's columns: O(N Q + M^2 Q) in all
-  if (P > 1) {                                                      // (columns in no part get nothing from the bound)
+  i64 qcov = 0;
+  for (const PsiPart& pt : f.parts) qcov += pt.qp;
+  // Columns in no part get nothing from the bound.  Every other entry is assigned (=, not +=) exactly once by the loop below: the
+  // parts' dims are pairwise disjoint (gplvm_check_prog), so qcov counts the covered columns and nothing needs a zero first.
+  if (qcov < q) {
     if (grad_Xmu) for (i64 i = 0; i < n * q; ++i) grad_Xmu[i] = 0.0;
     if (grad_Xvar) for (i64 i = 0; i < n * q; ++i) grad_Xvar[i] = 0.0;
   }
   int slot0 = 0;
   for (int p = 0; p < P; ++p) {
-    const GplvmPart& pt = f.parts[p];
+    const PsiPart& pt = f.parts[p];
     const PartOut& o = po[p];
     const i64 qp = pt.qp;
     const double var = prog[pt.node].variance;

@@ -1,6 +1,8 @@
 // What the inducing-point entry points share (gps_cond.hip: conditionals.py and kullback_leiblers.py; gps_svgp.hip: the SVGP
-// bounds and their gradients; gps_sparse.hip: SGPR / FITC): the start of a call, the Kuu / Kuf set-up, base_conditional in
-// stages, the pieces of KL[q(u) || p(u)] and the backward pass from Abar^T to the kernel parameters and Z.
+// bounds and their gradients; gps_sparse.hip: SGPR / FITC; gps_gpmc.hip, gps_sgpmc.hip: the MCMC models; gps_gplvm.hip,
+// gps_uncond.hip: the models on kernel expectations): the start of a call, the Kuu / Kuf set-up and the Kuu factor,
+// base_conditional in stages, the pieces of KL[q(u) || p(u)], the Kuu side of a gradient and the backward pass from Abar^T to the
+// kernel parameters and Z.
 #pragma once
 #include "gps_ops.hpp"
 
@@ -17,11 +19,10 @@ static int begin_inducing_call(gps_handle_t h, int* info) {
 // Input of the stages of base_conditional below:
 //   Kmm  [mp, mp]  device, padded with identity (jitter already added), lower triangle valid; the factor Lm after cond_solve
 //   Bt   [nsp, mp] device = Kmn^T zero padded; A^T after cond_solve
-//   linv           Lm's block inverses and their transposes (factor_ops)
 //   knn_const / dKnnDiag / dKnnFull describe Knn.
 struct InducingSetup {
   i64 m, mp, n_new, nsp, k;
-  double* Kmm; double* Bt; double* linv;
+  double* Kmm; double* Bt;
   const double* dKnnDiag; double knn_const; double* dKnnFull /* [nsp,nsp], overwritten */;
 };
 
@@ -50,12 +51,67 @@ static int inducing_buffers(gps_handle_t h, i64 m, i64 n, i64 k, InducingSetup& 
   GPS_HIP(h, h->dK.ensure((size_t)c.mp * c.mp * 8));
   GPS_HIP(h, h->dLinv.ensure(linv_bytes(c.mp)));
   GPS_HIP(h, h->dB.ensure((size_t)c.nsp * c.mp * 8));
-  c.Kmm = h->dK.d(); c.Bt = h->dB.d(); c.linv = h->dLinv.d();
+  c.Kmm = h->dK.d(); c.Bt = h->dB.d();
   c.dKnnDiag = nullptr; c.dKnnFull = nullptr; c.knn_const = 0.0;
   return GPS_OK;
 }
-// the conditionals' order: both uploads, then Kuu + jitter I, then Kuf^T  (SGPR / FITC factor Kuu before they build Kuf and
-// whitening needs no Kuf: they put the three pieces above together themselves)
+// ---- the Kuu factor ---------------------------------------------------------------------------------------------------------
+// The policy over dLinv and the recursion over it, for the solves that follow.  (Blocked refers to `ops`: not copyable.)
+struct KuuFactor {
+  HipOps ops{};
+  Blocked<HipOps> bl{ops};
+  KuuFactor() = default;
+  KuuFactor(const KuuFactor&) = delete;
+  KuuFactor& operator=(const KuuFactor&) = delete;
+};
+// dK [mp, mp] (symmetric positive definite, identity padded, lower triangle valid) -> its Cholesky factor in place, the block
+// inverses in dLinv, and (classify) the diagonal blocks classified for refine mode.  d_info is filled here and NOT read back:
+// every caller has its own synchronisation point (read_info) -- at once where it returns early on a matrix that is not positive
+// definite, at the end of its forward pass where that saves a synchronisation.
+static int factor_dK(gps_handle_t h, i64 mp, bool classify, KuuFactor& kf) {
+  GPS_HIP(h, h->dLinv.ensure(linv_bytes(mp)));
+  int* d_info = (int*)h->dInfo.p;
+  int rc = gps_launch_fill_info(h, d_info, INT_MAX);
+  if (rc) return rc;
+  kf.ops = factor_ops(h, h->dLinv.d(), mp, d_info);
+  rc = kf.bl.potrf_rec(h->dK.d(), mp, mp, 0, 0);
+  if (rc || !classify) return rc;
+  return classify_blocks(h, kf.ops, h->dK.d(), mp, mp);           // (refined leaves only against ill-conditioned diagonal blocks)
+}
+// The same from the m points in dX: sizes dK / dLinv, dK = K(Z) + jitter I, then factor_dK.  (GPMC: Z := X, m := n.)  The build
+// goes before the fill of d_info; the two touch different buffers, so either order gives the same values -- this is the one kept.
+static int kuu_factor(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 m, i64 d_all, double jitter, bool classify,
+                      KuuFactor& kf) {
+  const i64 mp = gps_pad(m);
+  GPS_HIP(h, h->dK.ensure((size_t)mp * mp * 8));
+  GPS_HIP(h, h->dLinv.ensure(linv_bytes(mp)));
+  int rc = inducing_kuu(h, prog, n_nodes, m, d_all, jitter);
+  if (rc) return rc;
+  return factor_dK(h, mp, classify, kf);
+}
+// U [mp, mp] = L^T, upper triangular with exact zeros below the diagonal (above the diagonal blocks the factor's own buffer was
+// never written: the transpose alone would carry that over)
+static int upper_factor(gps_handle_t h, const double* L, i64 mp, double* U) {
+  int rc = gps_launch_transpose(h, L, mp, mp, mp, U, mp);
+  if (rc) return rc;
+  return gps_launch_tri_map(h, U, mp, mp, 3);
+}
+// The Kuu side of a gradient, from Kbar2 = 2 Kuu_bar [mp, mp] and the m points in dX: grad_slots [ns] += 0.5 <2 Kuu_bar, dKuu> and,
+// grad_Z given, grad_Z [m, d_all] += the input VJP (cotangent Kuu_bar / 2 on the full symmetric matrix, and both arguments move:
+// the factor is 1).  Into zeroed slots (GPMC) this is zero plus half the VJP: the same values as the VJP taken straight into the slots and halved
+// (only a negative zero would come out as +0).
+static int kuu_side_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 m, i64 d_all, const double* Kbar2, i64 mp, int ns,
+                        double* grad_slots, double* grad_Z) {
+  std::vector<double> uu((size_t)ns, 0.0);
+  int rc = gps_launch_kmat_vjp(h, prog, n_nodes, h->dX.d(), m, nullptr, 0, d_all, Kbar2, mp, 0, uu.data());
+  if (rc) return rc;
+  for (int s = 0; s < ns; ++s) grad_slots[s] += 0.5 * uu[(size_t)s];
+  if (!grad_Z) return GPS_OK;
+  return gps_launch_kmat_input_vjp(h, prog, n_nodes, h->dX.d(), m, nullptr, 0, d_all, Kbar2, mp, 1.0, grad_Z);
+}
+
+// the conditionals' order: both uploads, then Kuu + jitter I, then Kuf^T; conditional_predict / svgp_forward factor it
+// (factor_dK) once Knn is under way.  (SGPR / FITC factor Kuu before they build Kuf and whitening needs no Kuf: kuu_factor.)
 static int inducing_setup(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, i64 m, const double* X,
                           i64 n, i64 d_all, double jitter, i64 k, InducingSetup& c) {
   int rc = inducing_upload(h, Z, m, X, n, n, d_all);
@@ -76,24 +132,17 @@ static int upload_tril(gps_handle_t h, const double* Lq, i64 m, double* dst, i64
 
 // ---- base_conditional in stages (conditionals.py:79-121) -----------------------------------------------------------------
 // Shared by prediction (gps_cond.hip: conditional_predict assembles fmean / fvar on the host) and the SVGP bounds
-// (gps_svgp.hip: svgp_forward reduces them on the device).  The caller fills d_info, makes `ops` = factor_ops(c.linv) and
-// `bl` over it, and reads d_info back at its own synchronisation point.
-// Stage 1: Lm = chol(Kmm) in place, A^T = Bt Lm^-T in place, dAlpha [k][mp] = f^T (white) or (Lm^-1 f)^T ...
-static int cond_solve(gps_handle_t h, const InducingSetup& c, HipOps& ops, Blocked<HipOps>& bl, const double* f, int white,
-                      int full_cov) {
+// (gps_svgp.hip: svgp_forward reduces them on the device).  The caller factors Kmm first (factor_dK: Lm = chol(Kmm) in place,
+// conditionals.py:84; `bl` is that KuuFactor's) and reads d_info back at its own synchronisation point.
+// Stage 1: A^T = Bt Lm^-T in place, dAlpha [k][mp] = f^T (white) or (Lm^-1 f)^T ...
+static int cond_solve(gps_handle_t h, const InducingSetup& c, Blocked<HipOps>& bl, const double* f, int white, int full_cov) {
   const i64 m = c.m, mp = c.mp, n_new = c.n_new, nsp = c.nsp, k = c.k;
-  int rc = bl.potrf_rec(c.Kmm, mp, mp, 0, 0);                      // Lm   conditionals.py:84
-  if (rc) return rc;
-  rc = classify_blocks(h, ops, c.Kmm, mp, mp);                     // (refined leaves only against ill-conditioned diagonal blocks)
-  if (rc) return rc;
-  rc = bl.trsm_rec(c.Kmm, mp, mp, 0, c.Bt, mp, nsp);               // A^T  conditionals.py:87
+  int rc = bl.trsm_rec(c.Kmm, mp, mp, 0, c.Bt, mp, nsp);           // A^T  conditionals.py:87
   if (rc) return rc;
   // f -> [k][mp]; white: fmean = A^T f ; else fmean = A^T (Lm^-1 f)   conditionals.py:99-103
   GPS_HIP(h, h->dAlpha.ensure((size_t)k * mp * 8));
   GPS_HIP(h, h->dTmp2.ensure((size_t)((full_cov && n_new * n_new > m * k) ? n_new * n_new : m * k) * 8 + 64));
-  GPS_HIP(h, hipMemcpyAsync(h->dTmp2.p, f, (size_t)m * k * 8, hipMemcpyHostToDevice, h->stream));
-  GPS_HIP(h, hipMemsetAsync(h->dAlpha.p, 0, (size_t)k * mp * 8, h->stream));
-  rc = gps_launch_transpose(h, h->dTmp2.d(), k, m, k, h->dAlpha.d(), mp);
+  rc = planes_upload(h, f, m, k, h->dTmp2.d(), h->dAlpha.d(), mp);
   if (rc) return rc;
   return white ? GPS_OK : bl.trsv_rec(c.Kmm, mp, mp, 0, h->dAlpha.d(), mp, k);
 }
@@ -306,9 +355,7 @@ static int sparse_lb_bar(gps_handle_t h, Blocked<HipOps>& blB, const std::vector
     *lbar_dot_lb = dots[0];
   }
   double* U = h->dTmp.d();
-  rc = gps_launch_transpose(h, LB, mp, mp, mp, U, mp);
-  if (rc) return rc;
-  rc = gps_launch_tri_map(h, U, mp, mp, 3);
+  rc = upper_factor(h, LB, mp, U);
   if (rc) return rc;
   return chol_adjoint2(h, blB, U, LBbar, h->dG2.d(), h->dTmp2.d(), mp);
 }
@@ -350,9 +397,7 @@ static int inducing_backward(gps_handle_t h, Blocked<HipOps>& bl, const Inducing
   // Kuf_bar^T = Abar^T L^-1  (X L = Abar^T through U = L^T), then Kuf_bar [mp, np]
   GPS_HIP(h, bufU.ensure((size_t)mp * mp * 8));
   double* U = bufU.d();
-  int rc = gps_launch_transpose(h, h->dK.d(), mp, mp, mp, U, mp);
-  if (rc) return rc;
-  rc = gps_launch_tri_map(h, U, mp, mp, 3);            // (above the diagonal blocks the factor's buffer was never written)
+  int rc = upper_factor(h, h->dK.d(), mp, U);
   if (rc) return rc;
   rc = bl.trsm_rn_rec(U, mp, mp, 0, AbarT, mp, np);
   if (rc) return rc;
@@ -375,25 +420,19 @@ static int inducing_backward(gps_handle_t h, Blocked<HipOps>& bl, const Inducing
   double* Kbar2 = bufKbar2.d();
   rc = chol_adjoint2(h, bl, U, Lbar, Kbar2, bufP.d(), mp);
   if (rc) return rc;
-  // contractions with the kernel derivatives
+  // contractions with the kernel derivatives: the Kuf side, the Kuu side, Kdiag -- each sum in that order
   for (int sI = 0; sI < ns; ++sI) g.grad_slots[sI] = 0.0;
   rc = gps_launch_kmat_vjp(h, g.prog, g.n_nodes, h->dX.d(), m, h->dXnew.d(), n, d_all, KufBar, np, 0, g.grad_slots);
-  if (rc) return rc;
-  {
-    std::vector<double> uu((size_t)ns, 0.0);
-    rc = gps_launch_kmat_vjp(h, g.prog, g.n_nodes, h->dX.d(), m, nullptr, 0, d_all, Kbar2, mp, 0, uu.data());
-    if (rc) return rc;
-    for (int sI = 0; sI < ns; ++sI) g.grad_slots[sI] += 0.5 * uu[sI];
-  }
-  rc = gps_kdiag_vjp(h, g.prog, g.n_nodes, d_all, g.kdiag_bar, g.grad_slots);
   if (rc) return rc;
   if (g.grad_Z) {
     for (i64 i = 0; i < m * d_all; ++i) g.grad_Z[i] = 0.0;
     rc = gps_launch_kmat_input_vjp(h, g.prog, g.n_nodes, h->dX.d(), m, h->dXnew.d(), n, d_all, KufBar, np, 1.0, g.grad_Z);
     if (rc) return rc;
-    rc = gps_launch_kmat_input_vjp(h, g.prog, g.n_nodes, h->dX.d(), m, nullptr, 0, d_all, Kbar2, mp, 1.0, g.grad_Z);
-    if (rc) return rc;
   }
+  rc = kuu_side_vjp(h, g.prog, g.n_nodes, m, d_all, Kbar2, mp, ns, g.grad_slots, g.grad_Z);
+  if (rc) return rc;
+  rc = gps_kdiag_vjp(h, g.prog, g.n_nodes, d_all, g.kdiag_bar, g.grad_slots);
+  if (rc) return rc;
   GPS_HIP(h, hipStreamSynchronize(h->stream));
   return GPS_OK;
 }

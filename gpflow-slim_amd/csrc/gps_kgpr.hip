@@ -109,7 +109,7 @@ extern "C" int gps_kron_cg(gps_handle_t h, const double* K1, int64_t m, const do
   if (delta) *delta = 0.0;
   if (m == 0 || n == 0) return GPS_OK;
   if (!K1 || !K2 || !B || !C || !X_out) return gps_fail(h, GPS_ERR_ARG, "gps_kron_cg: bad argument");
-  if (h->allreduce) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gps_kron_cg: not available with the data sharded over ranks");
+  if (int rf = refuse_unsupported(h, "gps_kron_cg", true)) return rf;
   int rc = begin_inducing_call(h, nullptr);                         // (dK, dAlpha, ... are overwritten)
   if (rc) return rc;
   h->kgpr.have = false;
@@ -148,8 +148,7 @@ static int kgpr_check(gps_handle_t h, const char* who, const KgprArgs& a) {
       a.n_nodes2 <= 0)
     return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": bad argument");
   if (a.m > INT_MAX / 2 || a.n > INT_MAX / 2) return gps_fail(h, GPS_ERR_UNSUPPORTED, std::string(who) + ": grid side too long");
-  if (h->allreduce) return gps_fail(h, GPS_ERR_UNSUPPORTED, std::string(who) + ": not available with the data sharded over ranks");
-  return GPS_OK;
+  return refuse_unsupported(h, who, true);
 }
 
 // X1 -> dX, X2 -> dXnew
@@ -272,13 +271,12 @@ extern "C" int gps_kgpr_lml_grad(gps_handle_t h, const gps_kern_node_t* prog1, i
   if (rc) return rc;
   if (!V1 || !V2 || !slots1 || !slots2 || !grad_noise) return gps_fail(h, GPS_ERR_ARG, "gps_kgpr_lml_grad: bad argument");
   int ns1 = 0, ns2 = 0;
-  rc = gps_grad_slots(h, prog1, n_nodes1, &ns1);
+  // both counts are reported before either capacity is judged: a caller sizes both buffers from one refused call
+  rc = grad_slot_count(h, "gps_kgpr_lml_grad", prog1, n_nodes1, INT_MAX, n_slots1, &ns1);
   if (rc) return rc;
-  rc = gps_grad_slots(h, prog2, n_nodes2, &ns2);
+  rc = grad_slot_count(h, "gps_kgpr_lml_grad", prog2, n_nodes2, cap2, n_slots2, &ns2);
   if (rc) return rc;
-  if (n_slots1) *n_slots1 = ns1;
-  if (n_slots2) *n_slots2 = ns2;
-  if (ns1 > cap1 || ns2 > cap2) return gps_fail(h, GPS_ERR_ARG, "gps_kgpr_lml_grad: grad_slots too small");
+  if (ns1 > cap1) return grad_slot_count(h, "gps_kgpr_lml_grad", prog1, n_nodes1, cap1, nullptr, &ns1);
   KgprFwd f;
   rc = kgpr_forward(h, a, Y, mask, noise_var, e1, e2, sel, max_iter, tol, true, out, &f);
   if (rc) return rc;

@@ -1,7 +1,8 @@
 // Host orchestration shared by the entry-point families of libgpflowslim_hip.so (gps_handle.hip, gps_gpr.hip, gps_cond.hip,
 // gps_svgp.hip, gps_dist.hip, gps_sparse.hip): the HIP "Ops" policy of blocked.hpp and the helpers around a factorisation.
-// Every arithmetic step is a HIP kernel from the sibling .hip files.  (What the inducing-point entries of gps_cond.hip,
-// gps_svgp.hip and gps_sparse.hip share beyond that is in gps_inducing.hpp.)
+// Every arithmetic step is a HIP kernel from the sibling .hip files.  Also here: the declarations of skinny.hip, planes_upload /
+// planes_download, and the refusals and the slot count that every model entry words the same way.  (What the inducing-point
+// entries share beyond that is in gps_inducing.hpp.)
 #pragma once
 #include "gps_common.hpp"
 #include "blocked.hpp"
@@ -11,12 +12,54 @@
 #include <cmath>
 #include <algorithm>
 
-// gps_sgpmc.hip : Gt[q][j] (+)= sum_i X[i][j] Et[q][i] over the rows of a row-major chunk X [rows, mp] (a chunk of A^T as
-// trsm_rec leaves it; ld even, mp a multiple of 128): planes [r][ldg >= mp] from planes [r][lde >= rows]; the row chunks'
-// partials (part) are added in index order -- bit-reproducible
+// skinny.hip : products with skinny right-hand sides kept as planes [r][ld] (one row per column of the [n, r] matrix)
+// A lower-triangular L [n, n] (only i >= j is read):
+//   trans 0: Ft[q][i] = sum_{j <= i} L[i][j] Bt[q][j] ;  trans 1: Ft[q][j] = sum_{i >= j} L[i][j] Bt[q][i]
+// part (trans 1): room for gps_tri_skinny_part_doubles(n, r) doubles
+size_t gps_tri_skinny_part_doubles(i64 n, i64 r);
+int gps_launch_tri_skinny(gps_handle_t h, int trans, const double* L, i64 ldl, i64 n, const double* Bt, i64 ldb, i64 r, double* Ft,
+                          i64 ldf, double* part);
+// the rank-r seed of the Cholesky adjoint:
+// P[i][j] = sum_q Ut[q][max(i, j)] Vt[q][min(i, j)] for i, j < n, zero up to np ; accumulate: added to what P holds for i, j < n
+int gps_launch_chol_seed(gps_handle_t h, const double* Ut, i64 ldu, const double* Vt, i64 ldv, i64 r, i64 n, double* P, i64 ldp, i64 np,
+                         int accumulate = 0);
+// Gt[q][j] (+)= sum_i X[i][j] Et[q][i] over the rows of a row-major chunk X [rows, mp] (a chunk of A^T as trsm_rec leaves it; ld
+// even, mp a multiple of 128): planes [r][ldg >= mp] from planes [r][lde >= rows]; the row chunks' partials (part) are added in
+// index order -- bit-reproducible
 size_t gps_skinny_xt_part_doubles(i64 rows, i64 mp, i64 r);
 int gps_launch_skinny_xt(gps_handle_t h, const double* X, i64 ld, i64 rows, i64 mp, const double* Et, i64 lde, i64 r, double* Gt, i64 ldg,
                          int accumulate, double* part);
+
+// ---- host [n, k] <-> planes [k][np], zero padded: through `stage` (device, n * k doubles), transposed on the device -------------
+static int planes_upload(gps_handle_t h, const double* src, i64 n, i64 k, double* stage, double* planes, i64 np) {
+  GPS_HIP(h, hipMemcpyAsync(stage, src, (size_t)n * k * 8, hipMemcpyHostToDevice, h->stream));
+  GPS_HIP(h, hipMemsetAsync(planes, 0, (size_t)k * np * 8, h->stream));
+  return gps_launch_transpose(h, stage, k, n, k, planes, np);
+}
+static int planes_download(gps_handle_t h, const double* planes, i64 np, i64 n, i64 k, double* stage, double* dst) {
+  int rc = gps_launch_transpose(h, planes, np, k, n, stage, k);
+  if (rc) return rc;
+  GPS_HIP(h, hipMemcpyAsync(dst, stage, (size_t)n * k * 8, hipMemcpyDeviceToHost, h->stream));
+  return GPS_OK;
+}
+
+// ---- what the entries refuse, in one wording -------------------------------------------------------------------------------------
+// more than 128 `noun` ("latent functions" / "outputs"; count 0: the entry has no such limit) and, sharded_too, a handle with an
+// all-reduce set (gps_set_allreduce: each rank holds a shard of the data; the entries that reduce partial sums pass false)
+static int refuse_unsupported(gps_handle_t h, const char* who, bool sharded_too, i64 count = 0, const char* noun = "") {
+  if (count > GPS_TILE) return gps_fail(h, GPS_ERR_UNSUPPORTED, std::string(who) + ": at most 128 " + noun);
+  if (sharded_too && h->allreduce)
+    return gps_fail(h, GPS_ERR_UNSUPPORTED, std::string(who) + ": not available with the data sharded over ranks");
+  return GPS_OK;
+}
+// the number of gradient slots of a program, reported through n_slots_out (optional) and checked against the caller's capacity
+static int grad_slot_count(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes, int cap, int* n_slots_out, int* ns) {
+  int rc = gps_grad_slots(h, prog, n_nodes, ns);
+  if (rc) return rc;
+  if (n_slots_out) *n_slots_out = *ns;
+  if (*ns > cap) return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": grad_slots too small");
+  return GPS_OK;
+}
 
 // ---- the HIP "Ops" policy for blocked.hpp ----------------------------------------------------
 struct HipOps {

@@ -193,9 +193,7 @@ static int rff_lml_args(gps_handle_t h, const char* who, const gps_rff_desc_t* d
   int rc = rff_check(h, who, desc, X, n);
   if (rc) return rc;
   if (!resid || r <= 0 || !(noise_var > 0.0)) return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": bad argument");
-  if (r > GPS_TILE) return gps_fail(h, GPS_ERR_UNSUPPORTED, std::string(who) + ": at most 128 outputs");
-  if (h->allreduce) return gps_fail(h, GPS_ERR_UNSUPPORTED, std::string(who) + ": not available with the data sharded over ranks");
-  return GPS_OK;
+  return refuse_unsupported(h, who, true, r, "outputs");
 }
 
 extern "C" int gps_rff_lml(gps_handle_t h, const gps_rff_desc_t* desc, const double* X, int64_t n, double noise_var,

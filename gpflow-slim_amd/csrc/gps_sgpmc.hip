@@ -25,6 +25,7 @@
 //                dA     E^T planes [k][cp]        dLikH  H^T planes [k][cp]        dLikOut 2 h [cp]
 //                dS1    A [mp, cp], later Kuf_bar [mp, cp]                         dY     A diag(2 h) [mp, cp], later Abar^T, then Kuf_bar^T [cp, mp]
 //                dG4    partials of grad_V        dStage what goes back to the host
+// Host path, plus the one map kernel below; grad_V's product (gps_launch_skinny_xt) and the seed (gps_launch_chol_seed) are in skinny.hip.
 // (gps_launch_kmat, gps_launch_kdiag_vec and the kernel-matrix VJPs use dFeat, dFeat2, dProg, dNkn and dTmp2; gps_lik_launch dLikPart.)
 #include "gps_inducing.hpp"
 
@@ -38,106 +39,6 @@ __global__ __launch_bounds__(256) void sgpmc_hsum_kernel(const double* __restric
   double s = 0.0;
   for (int q = 0; q < k; ++q) s += Ht[(i64)q * ldh + i];
   out[i] = scale * s;
-}
-
-#define SKT_COLS  128     // skinny transposed product: columns per workgroup, two per lane
-#define SKT_ROWS  256     // ... rows per workgroup (one partial each), their E staged in LDS
-
-// part[(ci * r + q) * ldp + j] = sum over the rows i of chunk ci of X[i][j] Et[q][i].  Workgroup (column tile, row chunk); a lane
-// two adjacent columns, a wavefront every fourth row of the chunk, four rows per step; the chunk's E sits in LDS (every lane
-// reads one address: a broadcast); the four wavefronts' sums are added through LDS in a fixed order.
-template <int RC>
-__global__ __launch_bounds__(256) void skinny_xt_kernel(const double* __restrict__ X, i64 ld, i64 rows, const double* __restrict__ Et,
-                                                        i64 lde, int r, double* __restrict__ part, i64 ldp) {
-  __shared__ double Es[RC][SKT_ROWS];
-  __shared__ double2 red[4][64];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const i64 j = (i64)blockIdx.x * SKT_COLS + lane * 2, ci = blockIdx.y;
-  const i64 r0 = ci * SKT_ROWS;
-  const int cnt = (int)(r0 + SKT_ROWS < rows ? SKT_ROWS : rows - r0);
-  for (int e = threadIdx.x; e < RC * SKT_ROWS; e += 256) {
-    const int q = e / SKT_ROWS, i = e % SKT_ROWS;
-    Es[q][i] = (q < r && i < cnt) ? Et[(i64)q * lde + r0 + i] : 0.0;
-  }
-  __syncthreads();
-  double2 acc[RC];
-#pragma unroll
-  for (int q = 0; q < RC; ++q) acc[q] = make_double2(0.0, 0.0);
-  for (int ib = wave; ib < cnt; ib += 16) {
-    double2 l[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = ib + 4 * u;
-      l[u] = make_double2(0.0, 0.0);
-      if (i < cnt) l[u] = *reinterpret_cast<const double2*>(X + (r0 + i) * ld + j);
-    }
-#pragma unroll
-    for (int q = 0; q < RC; ++q) {
-      if (q < r) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int i = ib + 4 * u;
-          const double g = i < cnt ? Es[q][i] : 0.0;
-          acc[q].x = fma(l[u].x, g, acc[q].x);
-          acc[q].y = fma(l[u].y, g, acc[q].y);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < RC; ++q) {
-    if (q < r) {                                                   // (r is the same in every thread)
-      __syncthreads();
-      red[wave][lane] = acc[q];
-      __syncthreads();
-      if (wave == 0) {
-        const double2 a = red[0][lane], b = red[1][lane], c = red[2][lane], d = red[3][lane];
-        *reinterpret_cast<double2*>(part + (ci * r + q) * ldp + j) = make_double2((a.x + b.x) + (c.x + d.x), (a.y + b.y) + (c.y + d.y));
-      }
-    }
-  }
-}
-// Gt[q][j] (+)= the partials of column j added in the order of the chunks
-__global__ __launch_bounds__(256) void skinny_xt_reduce_kernel(const double* __restrict__ part, i64 ldp, i64 mp, int r, int nch,
-                                                               double* __restrict__ Gt, i64 ldg, int accumulate) {
-  const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-  const int q = blockIdx.y;
-  if (j >= mp) return;
-  double s = 0.0;
-  for (i64 c = 0; c < nch; ++c) s += part[(c * r + q) * ldp + j];
-  Gt[(i64)q * ldg + j] = accumulate ? Gt[(i64)q * ldg + j] + s : s;
-}
-
-size_t gps_skinny_xt_part_doubles(i64 rows, i64 mp, i64 r) {
-  return (size_t)((rows + SKT_ROWS - 1) / SKT_ROWS) * (size_t)(r < 16 ? r : 16) * (size_t)mp;
-}
-template <int RC>
-static void skinny_xt_go(gps_handle_t h, const double* X, i64 ld, i64 rows, i64 mp, const double* Et, i64 lde, int r, double* Gt, i64 ldg,
-                         int accumulate, double* part) {
-  const int nch = (int)((rows + SKT_ROWS - 1) / SKT_ROWS);
-  hipLaunchKernelGGL(skinny_xt_kernel<RC>, dim3((unsigned)(mp / SKT_COLS), (unsigned)nch), dim3(256), 0, h->stream, X, ld, rows, Et, lde, r,
-                     part, mp);
-  hipLaunchKernelGGL(skinny_xt_reduce_kernel, dim3((unsigned)((mp + 255) / 256), (unsigned)r), dim3(256), 0, h->stream, part, mp, mp, r, nch,
-                     Gt, ldg, accumulate);
-}
-// X [rows, mp] (ld even, 16-byte aligned), Et planes [r][lde >= rows], Gt planes [r][ldg >= mp]; part: gps_skinny_xt_part_doubles
-int gps_launch_skinny_xt(gps_handle_t h, const double* X, i64 ld, i64 rows, i64 mp, const double* Et, i64 lde, i64 r, double* Gt, i64 ldg,
-                         int accumulate, double* part) {
-  if (rows <= 0 || mp <= 0 || r <= 0) return GPS_OK;
-  if (mp % SKT_COLS || ld < mp || (ld & 1) || lde < rows || ldg < mp || (rows + SKT_ROWS - 1) / SKT_ROWS > 65535)
-    return gps_fail(h, GPS_ERR_ARG, "skinny_xt: mp must be a multiple of 128, ld even and at least mp");
-  for (i64 q0 = 0; q0 < r; q0 += 16) {                             // more than 16 planes: 16 at a time
-    const int rc = (int)(r - q0 < 16 ? r - q0 : 16);
-    const double* E = Et + q0 * lde; double* G = Gt + q0 * ldg;
-    LaunchScope ls(h, KC_REDUCE, 2.0 * rows * mp * rc, 8.0 * rows * mp + 8.0 * rows * rc);
-    ls.tag[0] = mp; ls.tag[1] = rc; ls.tag[2] = rows; ls.tag[3] = 22;
-    if (rc == 1) skinny_xt_go<1>(h, X, ld, rows, mp, E, lde, rc, G, ldg, accumulate, part);
-    else if (rc <= 4) skinny_xt_go<4>(h, X, ld, rows, mp, E, lde, rc, G, ldg, accumulate, part);
-    else skinny_xt_go<16>(h, X, ld, rows, mp, E, lde, rc, G, ldg, accumulate, part);
-    GPS_HIP(h, hipGetLastError());
-  }
-  return GPS_OK;
 }
 
 namespace {
@@ -155,9 +56,7 @@ static int sgpmc_check(gps_handle_t h, const char* who, const SgpmcArgs& a, cons
   if (!h || !a.prog || !a.Z || !a.X || !a.V || !a.Y || !a.lik || !loglik || a.m <= 0 || a.n <= 0 || a.k <= 0 || a.d_all <= 0 ||
       a.n_nodes <= 0 || !(a.jitter >= 0.0) || a.chunk_rows < 0 || a.chunk_rows % GPS_TILE)
     return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": bad argument (chunk_rows: 0 or a multiple of 128)");
-  if (a.k > GPS_TILE) return gps_fail(h, GPS_ERR_UNSUPPORTED, std::string(who) + ": at most 128 latent functions");
-  if (h->allreduce) return gps_fail(h, GPS_ERR_UNSUPPORTED, std::string(who) + ": not available with the data sharded over ranks");
-  return GPS_OK;
+  return refuse_unsupported(h, who, true, a.k, "latent functions");
 }
 
 // gps_last_stage_ms (profiling on): [0] Kuu and its factor  [1] the forward half, summed over the chunks  [2] the backward half,
@@ -168,10 +67,8 @@ static int sgpmc_body(gps_handle_t h, const char* who, const SgpmcArgs& a, int w
   if (want_grad && (!o.grad_slots || !o.grad_lik || !o.grad_V)) return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": bad argument");
   int ns = 0;
   if (want_grad) {
-    rc = gps_grad_slots(h, a.prog, a.n_nodes, &ns);
+    rc = grad_slot_count(h, who, a.prog, a.n_nodes, o.n_slots_cap, o.n_slots_out, &ns);
     if (rc) return rc;
-    if (o.n_slots_out) *o.n_slots_out = ns;
-    if (ns > o.n_slots_cap) return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": grad_slots too small");
   }
   const i64 m = a.m, n = a.n, k = a.k, d_all = a.d_all, mp = gps_pad(m);
   const i64 ky = (a.lik->kind == GPS_LIK_MULTICLASS) ? 1 : k;
@@ -189,33 +86,22 @@ static int sgpmc_body(gps_handle_t h, const char* who, const SgpmcArgs& a, int w
   if (kd_const) { rc = gps_launch_kdiag(h, a.prog, a.n_nodes, &kd); if (rc) return rc; }
 
   // ---- set-up: Z, X, Y, mean up; Lm; U = Lm^T; V as planes
-  GPS_HIP(h, h->dK.ensure((size_t)mp * mp * 8));
-  GPS_HIP(h, h->dLinv.ensure(linv_bytes(mp)));
-  int* d_info = (int*)h->dInfo.p;
-  rc = gps_launch_fill_info(h, d_info, INT_MAX);
-  if (rc) return rc;
   if (h->prof_on) GPS_HIP(h, hipEventRecord(h->ev[0], h->stream));
   rc = inducing_upload(h, a.Z, m, a.X, n, n, d_all);
   if (rc) return rc;
-  rc = inducing_kuu(h, a.prog, a.n_nodes, m, d_all, a.jitter);
+  KuuFactor kf;
+  rc = kuu_factor(h, a.prog, a.n_nodes, m, d_all, a.jitter, true, kf);
   if (rc) return rc;
-  HipOps ops = factor_ops(h, h->dLinv.d(), mp, d_info);
-  Blocked<HipOps> bl(ops);
-  rc = bl.potrf_rec(h->dK.d(), mp, mp, 0, 0);
-  if (rc) return rc;
-  rc = read_info(h, d_info, &linfo);
+  Blocked<HipOps>& bl = kf.bl;
+  rc = read_info(h, kf.ops.d_info, &linfo);
   if (o.info) *o.info = linfo;
   if (rc || linfo) return rc;
-  rc = classify_blocks(h, ops, h->dK.d(), mp, mp);
-  if (rc) return rc;
   const double* Lm = h->dK.d();
   double* U = nullptr;
   if (want_grad) {
     GPS_HIP(h, h->dTmp.ensure((size_t)mp * mp * 8));
     U = h->dTmp.d();
-    rc = gps_launch_transpose(h, Lm, mp, mp, mp, U, mp);
-    if (rc) return rc;
-    rc = gps_launch_tri_map(h, U, mp, mp, 3);            // (above the diagonal blocks the factor's buffer was never written)
+    rc = upper_factor(h, Lm, mp, U);
     if (rc) return rc;
   }
   GPS_HIP(h, h->dLikIn.ensure((size_t)n * (ky + k) * 8));
@@ -224,6 +110,8 @@ static int sgpmc_body(gps_handle_t h, const char* who, const SgpmcArgs& a, int w
   if (dMeanAll) GPS_HIP(h, hipMemcpyAsync(dMeanAll, a.mean, (size_t)n * k * 8, hipMemcpyHostToDevice, h->stream));
   GPS_HIP(h, h->dAlpha.ensure((size_t)k * mp * 8));
   double* Vt = h->dAlpha.d();
+  // (V reaches the device in host-built layouts, once each: its planes here and, for the gradient, the packed V | -1 | -V^T
+  // below, which no other path uses -- planes_upload would put a transpose launch where there is a copy today)
   std::vector<double> hv((size_t)k * mp, 0.0), up;
   for (i64 j = 0; j < m; ++j) for (i64 q = 0; q < k; ++q) hv[(size_t)q * mp + j] = a.V[j * k + q];
   GPS_HIP(h, hipMemcpyAsync(Vt, hv.data(), hv.size() * 8, hipMemcpyHostToDevice, h->stream));
@@ -312,9 +200,8 @@ static int sgpmc_body(gps_handle_t h, const char* who, const SgpmcArgs& a, int w
       rc = gps_launch_gemm_nt(h, acc ? 2 : 1, 1, mp, mp, cnp, Abar, cnp, KufBar, cnp, W2, mp);                // 2 W (+)= A diag(2 h) A^T, lower
       if (rc) return rc;
       if (o.grad_mean) {
-        rc = gps_launch_transpose(h, Et, cnp, k, cn, h->dStage.d(), k);
+        rc = planes_download(h, Et, cnp, cn, k, h->dStage.d(), o.grad_mean + c0 * k);
         if (rc) return rc;
-        GPS_HIP(h, hipMemcpyAsync(o.grad_mean + c0 * k, h->dStage.p, (size_t)cn * k * 8, hipMemcpyDeviceToHost, h->stream));
       }
       rc = gps_launch_lik_abar(h, At, mp, cnp, mp, Et, Ht, cnp, dQmu, dCq, k, Abar);                          // Abar^T = E V^T - 2 diag(h) A^T
       if (rc) return rc;
@@ -355,24 +242,15 @@ static int sgpmc_body(gps_handle_t h, const char* who, const SgpmcArgs& a, int w
   if (rc) return rc;
   rc = gps_launch_chol_seed(h, negVt, mp, gVt, mp, k, m, W2, mp, mp, 1);
   if (rc) return rc;
-  rc = gps_launch_transpose(h, gVt, mp, k, m, h->dStage.d(), k);
+  rc = planes_download(h, gVt, mp, m, k, h->dStage.d(), o.grad_V);
   if (rc) return rc;
-  GPS_HIP(h, hipMemcpyAsync(o.grad_V, h->dStage.p, (size_t)m * k * 8, hipMemcpyDeviceToHost, h->stream));
   GPS_HIP(h, h->dG1.ensure((size_t)mp * mp * 8));
   double* Kbar2 = h->dG1.d();
   rc = chol_adjoint2_solves(h, bl, U, W2, Kbar2, mp);
   if (rc) return rc;
   if (h->prof_on) GPS_HIP(h, hipEventRecord(h->ev[6], h->stream));
-  {
-    std::vector<double> uu((size_t)ns, 0.0);
-    rc = gps_launch_kmat_vjp(h, a.prog, a.n_nodes, h->dX.d(), m, nullptr, 0, d_all, Kbar2, mp, 0, uu.data());
-    if (rc) return rc;
-    for (int s = 0; s < ns; ++s) o.grad_slots[s] += 0.5 * uu[(size_t)s];
-  }
-  if (o.grad_Z) {
-    rc = gps_launch_kmat_input_vjp(h, a.prog, a.n_nodes, h->dX.d(), m, nullptr, 0, d_all, Kbar2, mp, 1.0, o.grad_Z);
-    if (rc) return rc;
-  }
+  rc = kuu_side_vjp(h, a.prog, a.n_nodes, m, d_all, Kbar2, mp, ns, o.grad_slots, o.grad_Z);
+  if (rc) return rc;
   if (h->prof_on) GPS_HIP(h, hipEventRecord(h->ev[7], h->stream));
   GPS_HIP(h, hipStreamSynchronize(h->stream));
   if (kd_const) rc = gps_kdiag_vjp(h, a.prog, a.n_nodes, d_all, hsum, o.grad_slots);

@@ -22,24 +22,16 @@ static int sparse_gpr_impl(gps_handle_t h, int fitc, const gps_kern_node_t* prog
   //          dS2 <- A [mp, np] ; dS3 <- B / LB [mp, mp] ; dS4 <- inverses of LB (2 sets)
   rc = inducing_upload(h, Z, m, X, n, n > n_new ? n : n_new, d_all);
   if (rc) return rc;
-  GPS_HIP(h, h->dK.ensure((size_t)mp * mp * 8));
-  GPS_HIP(h, h->dLinv.ensure(linv_bytes(mp)));
   GPS_HIP(h, h->dS1.ensure((size_t)np * mp * 8));
   GPS_HIP(h, h->dS2.ensure((size_t)mp * np * 8));
   GPS_HIP(h, h->dS3.ensure((size_t)mp * mp * 8));
   GPS_HIP(h, h->dS4.ensure(linv_bytes(mp)));
-  int* d_info = (int*)h->dInfo.p;
-  rc = gps_launch_fill_info(h, d_info, INT_MAX);
-  if (rc) return rc;
   // Kuu + jitter I -> L                                                 (features.py:74-77, sgpr.py:133-135)
-  rc = inducing_kuu(h, prog, n_nodes, m, d_all, jitter);
+  KuuFactor kfL;                                                 // (d_info is read back once, after the second factor)
+  rc = kuu_factor(h, prog, n_nodes, m, d_all, jitter, true, kfL);
   if (rc) return rc;
-  HipOps opsL = factor_ops(h, h->dLinv.d(), mp, d_info);
-  Blocked<HipOps> blL(opsL);
-  rc = blL.potrf_rec(h->dK.d(), mp, mp, 0, 0);
-  if (rc) return rc;
-  rc = classify_blocks(h, opsL, h->dK.d(), mp, mp);
-  if (rc) return rc;
+  Blocked<HipOps>& blL = kfL.bl;
+  int* d_info = kfL.ops.d_info;
   // At = K(X, Z) L^-T  = (L^-1 Kuf)^T   [np, mp]                         (sgpr.py:139, without the 1/sigma)
   rc = inducing_kuf(h, prog, n_nodes, n, m, d_all, h->dS1.d());
   if (rc) return rc;
@@ -82,9 +74,7 @@ static int sparse_gpr_impl(gps_handle_t h, int fitc, const gps_kern_node_t* prog
   double* dErrT = h->dAlpha.d();                                 // [r][np]
   double* dC = dErrT + (size_t)r * np;                           // [r][mp]
   GPS_HIP(h, h->dTmp2.ensure((size_t)n * r * 8));
-  GPS_HIP(h, hipMemcpyAsync(h->dTmp2.p, resid, (size_t)n * r * 8, hipMemcpyHostToDevice, h->stream));
-  GPS_HIP(h, hipMemsetAsync(dErrT, 0, (size_t)r * np * 8, h->stream));
-  rc = gps_launch_transpose(h, h->dTmp2.d(), r, n, r, dErrT, np);
+  rc = planes_upload(h, resid, n, r, h->dTmp2.d(), dErrT, np);
   if (rc) return rc;
   if (fitc) {                                                    // beta * sqrt(nu) = err / sqrt(nu)
     rc = gps_launch_scale_cols(h, dErrT, np, r, n, h->dTmp3.d(), dErrT, np);
@@ -211,14 +201,12 @@ static int sgpr_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_nod
                              const double* X, int64_t n, int64_t d_all, double jitter, double noise_var,
                              const double* resid, int64_t r, double* bound, double* grad_slots, int n_slots_cap,
                              int* n_slots_out, double* grad_noise, double* grad_mean, double* grad_Z, int* info) {
-  if (h && h->allreduce) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradients of the sparse bounds are not available with the data sharded over ranks");
   if (!h || !bound || !grad_slots || !grad_noise) return gps_fail(h, GPS_ERR_ARG, "gps_sgpr_grad: bad argument");
-  if (r > GPS_TILE) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gps_sgpr_grad: at most 128 outputs");
-  int ns = 0;
-  int rc = gps_grad_slots(h, prog, n_nodes, &ns);
+  int rc = refuse_unsupported(h, "gps_sgpr_grad", true, r, "outputs");
   if (rc) return rc;
-  if (n_slots_out) *n_slots_out = ns;
-  if (ns > n_slots_cap) return gps_fail(h, GPS_ERR_ARG, "gps_sgpr_grad: grad_slots too small");
+  int ns = 0;
+  rc = grad_slot_count(h, "gps_sgpr_grad", prog, n_nodes, n_slots_cap, n_slots_out, &ns);
+  if (rc) return rc;
   int linfo = 0;
   rc = gps_sgpr(h, prog, n_nodes, Z, m, X, n, d_all, jitter, noise_var, resid, r, nullptr, 0, 0, bound, nullptr, nullptr, &linfo);
   if (info) *info = linfo;
@@ -309,14 +297,12 @@ static int fitc_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_nod
                              const double* X, int64_t n, int64_t d_all, double jitter, double noise_var,
                              const double* resid, int64_t r, double* bound, double* grad_slots, int n_slots_cap,
                              int* n_slots_out, double* grad_noise, double* grad_mean, double* grad_Z, int* info) {
-  if (h && h->allreduce) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradients of the sparse bounds are not available with the data sharded over ranks");
   if (!h || !bound || !grad_slots || !grad_noise) return gps_fail(h, GPS_ERR_ARG, "gps_fitc_grad: bad argument");
-  if (r > GPS_TILE) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gps_fitc_grad: at most 128 outputs");
-  int ns = 0;
-  int rc = gps_grad_slots(h, prog, n_nodes, &ns);
+  int rc = refuse_unsupported(h, "gps_fitc_grad", true, r, "outputs");
   if (rc) return rc;
-  if (n_slots_out) *n_slots_out = ns;
-  if (ns > n_slots_cap) return gps_fail(h, GPS_ERR_ARG, "gps_fitc_grad: grad_slots too small");
+  int ns = 0;
+  rc = grad_slot_count(h, "gps_fitc_grad", prog, n_nodes, n_slots_cap, n_slots_out, &ns);
+  if (rc) return rc;
   int linfo = 0;
   rc = gps_fitc(h, prog, n_nodes, Z, m, X, n, d_all, jitter, noise_var, resid, r, nullptr, 0, 0, bound, nullptr, nullptr, &linfo);
   if (info) *info = linfo;

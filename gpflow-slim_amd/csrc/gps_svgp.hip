@@ -38,11 +38,11 @@ static int svgp_forward(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes
   if (rc) return rc;
   const i64 mp = c.mp, nsp = c.nsp;
   int* d_info = (int*)h->dInfo.p;
-  rc = gps_launch_fill_info(h, d_info, INT_MAX);
+  KuuFactor kf;
+  rc = factor_dK(h, mp, true, kf);
   if (rc) return rc;
-  HipOps ops = factor_ops(h, c.linv, mp, d_info);
-  Blocked<HipOps> bl(ops);
-  rc = cond_solve(h, c, ops, bl, q_mu, white, 0);
+  Blocked<HipOps>& bl = kf.bl;
+  rc = cond_solve(h, c, bl, q_mu, white, 0);
   if (rc) return rc;
   // sum log diag Lm and the Mahalanobis term sum (Lm^-1 q_mu)^2 (white: sum q_mu^2)    kullback_leiblers.py:68-69,98-103
   double kl_hp[2 * 64];
@@ -159,9 +159,10 @@ extern "C" int gps_svgp_elbo_lik(gps_handle_t h, const gps_kern_node_t* prog, in
   if (!h || !Z || !X || !Y || !q_mu || !q_sqrt || !lik || !elbo || m <= 0 || n <= 0 || k <= 0 || d_all <= 0)
     return gps_fail(h, GPS_ERR_ARG, "gps_svgp_elbo_lik: bad argument");
   if (q_sqrt_ndim != 2 && q_sqrt_ndim != 3) return gps_fail(h, GPS_ERR_ARG, "gps_svgp_elbo_lik: q_sqrt_ndim must be 2 or 3");
-  if (k > GPS_TILE) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gps_svgp_elbo_lik: at most 128 latent functions");
+  int rc = refuse_unsupported(h, "gps_svgp_elbo_lik", false, k, "latent functions");      // (the bound itself takes sharded data)
+  if (rc) return rc;
   LikHost LH;
-  int rc = gps_lik_prepare(h, lik, k, &LH);
+  rc = gps_lik_prepare(h, lik, k, &LH);
   if (rc) return rc;
   SvgpAcc sv; sv.yres = Y; sv.noise_var = 0.0; sv.lik = &LH; sv.mean = mean; sv.scale = scale;
   sv.ky = (lik->kind == GPS_LIK_MULTICLASS) ? 1 : k;
@@ -201,22 +202,13 @@ static int svgp_whiten(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes,
   const i64 mp = gps_pad(m);
   rc = inducing_upload(h, Z, m, nullptr, 0, 0, d_all);
   if (rc) return rc;
-  GPS_HIP(h, h->dK.ensure((size_t)mp * mp * 8));
-  GPS_HIP(h, h->dLinv.ensure(linv_bytes(mp)));
-  rc = inducing_kuu(h, prog, n_nodes, m, d_all, jitter);
+  KuuFactor kf;
+  rc = kuu_factor(h, prog, n_nodes, m, d_all, jitter, true, kf);
   if (rc) return rc;
-  int* d_info = (int*)h->dInfo.p;
-  rc = gps_launch_fill_info(h, d_info, INT_MAX);
-  if (rc) return rc;
-  HipOps ops = factor_ops(h, h->dLinv.d(), mp, d_info);
-  Blocked<HipOps> bl(ops);
-  rc = bl.potrf_rec(h->dK.d(), mp, mp, 0, 0);
-  if (rc) return rc;
-  rc = read_info(h, d_info, info);
+  Blocked<HipOps>& bl = kf.bl;
+  rc = read_info(h, kf.ops.d_info, info);
   if (rc || (info && *info)) return rc;
-  rc = classify_blocks(h, ops, h->dK.d(), mp, mp);
-  if (rc) return rc;
-  // m_w^T = (Lm^-1 q_mu)^T : right-hand sides as rows
+  // m_w^T = (Lm^-1 q_mu)^T : right-hand sides as rows (built on the host: the same buffer brings the solution back)
   std::vector<double> buf((size_t)GPS_TILE * mp, 0.0);
   for (i64 j = 0; j < m; ++j) for (i64 q = 0; q < k; ++q) buf[(size_t)q * mp + j] = q_mu[j * k + q];
   GPS_HIP(h, h->dG3.ensure(buf.size() * 8));
@@ -271,10 +263,8 @@ struct SvgpGradHead {
 static int svgp_grad_head(gps_handle_t h, const char* entry, const gps_kern_node_t* prog, int n_nodes, const double* Z, i64 m,
                           i64 d_all, double jitter, const double* q_mu, i64 k, const double* q_sqrt, int q_sqrt_ndim, int white,
                           int n_slots_cap, int* n_slots_out, double* grad_q_sqrt, int* info, int* linfo, SvgpGradHead& hd) {
-  int rc = gps_grad_slots(h, prog, n_nodes, &hd.ns);
+  int rc = grad_slot_count(h, entry, prog, n_nodes, n_slots_cap, n_slots_out, &hd.ns);
   if (rc) return rc;
-  if (n_slots_out) *n_slots_out = hd.ns;
-  if (hd.ns > n_slots_cap) return gps_fail(h, GPS_ERR_ARG, std::string(entry) + ": grad_slots too small");
   hd.unwhite = !white; hd.ndim_in = q_sqrt_ndim;
   hd.q_mu = q_mu; hd.q_sqrt = q_sqrt; hd.ndim = q_sqrt_ndim;
   hd.grad_q_sqrt = hd.grad_q_sqrt_out = grad_q_sqrt;
@@ -299,9 +289,8 @@ static int svgp_grad_mid(gps_handle_t h, const SvgpGradHead& hd, i64 m, i64 n, i
   int rc;
   if (grad_mean) {                                       // d ELBO / d mean_function(X) = E   [n, k]
     GPS_HIP(h, h->dTmp2.ensure((size_t)n * k * 8));
-    rc = gps_launch_transpose(h, Et, nsp, k, n, h->dTmp2.d(), k);
+    rc = planes_download(h, Et, nsp, n, k, h->dTmp2.d(), grad_mean);
     if (rc) return rc;
-    GPS_HIP(h, hipMemcpyAsync(grad_mean, h->dTmp2.p, (size_t)n * k * 8, hipMemcpyDeviceToHost, h->stream));
   }
   GPS_HIP(h, h->dS2.ensure((size_t)mp * nsp * 8));
   double* Am = h->dS2.d();
@@ -398,7 +387,7 @@ static int svgp_elbo_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int 
                                   double* grad_mean, double* grad_Z, int* info) {
   if (!h || !elbo || !grad_slots || !grad_noise || !grad_q_mu || !grad_q_sqrt)
     return gps_fail(h, GPS_ERR_ARG, "gps_svgp_elbo_grad: bad argument");
-  if (k > GPS_TILE) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gps_svgp_elbo_grad: at most 128 latent functions");
+  if (int rf = refuse_unsupported(h, "gps_svgp_elbo_grad", false, k, "latent functions")) return rf;   // (sharded data: each rank its share)
   if (!Z || !q_mu || !q_sqrt || m <= 0 || k <= 0 || (q_sqrt_ndim != 2 && q_sqrt_ndim != 3))
     return gps_fail(h, GPS_ERR_ARG, "gps_svgp_elbo_grad: bad argument");
   SvgpGradHead hd;
@@ -530,8 +519,7 @@ static int svgp_elbo_lik_grad_body(gps_handle_t h, const gps_kern_node_t* prog, 
                                    double* grad_mean, double* grad_Z, int* info) {
   if (!h || !elbo || !grad_slots || !grad_q_mu || !grad_q_sqrt || !lik)
     return gps_fail(h, GPS_ERR_ARG, "gps_svgp_elbo_lik_grad: bad argument");
-  if (h->allreduce) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gps_svgp_elbo_lik_grad: not available with the data sharded over ranks");
-  if (k > GPS_TILE) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gps_svgp_elbo_lik_grad: at most 128 latent functions");
+  if (int rf = refuse_unsupported(h, "gps_svgp_elbo_lik_grad", true, k, "latent functions")) return rf;
   if (!Z || !X || !Y || !q_mu || !q_sqrt || m <= 0 || n <= 0 || k <= 0 || d_all <= 0 || (q_sqrt_ndim != 2 && q_sqrt_ndim != 3))
     return gps_fail(h, GPS_ERR_ARG, "gps_svgp_elbo_lik_grad: bad argument");
   LikHost LH;

@@ -119,7 +119,7 @@ static int uncond_contract(gps_handle_t h, const std::vector<PsiPart>& parts, co
 static int uncond_common_args(gps_handle_t h, const char* who, const double* Z, i64 m, const double* Xmu, const double* Xvar, i64 n,
                               i64 q) {
   if (!h || !Z || !Xmu || !Xvar || m <= 0 || n <= 0 || q <= 0) return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": bad argument");
-  if (h->allreduce) return gps_fail(h, GPS_ERR_UNSUPPORTED, std::string(who) + ": not available with the data sharded over ranks");
+  if (int rf = refuse_unsupported(h, who, true)) return rf;
   if (m > 65535) return gps_fail(h, GPS_ERR_UNSUPPORTED, std::string(who) + ": at most 65535 inducing points");
   return GPS_OK;
 }
@@ -142,9 +142,8 @@ extern "C" int gps_psi2_contract(gps_handle_t h, const gps_kern_node_t* prog, in
     if (rc) return rc;
   }
   GPS_HIP(h, h->dB.ensure((size_t)b * n * 8));
-  rc = gps_launch_transpose(h, h->dVar.d(), n, b, n, h->dB.d(), b);                // planes [b][n] -> [n, b]
+  rc = planes_download(h, h->dVar.d(), n, n, b, h->dB.d(), out);                   // planes [b][n] -> [n, b]
   if (rc) return rc;
-  GPS_HIP(h, hipMemcpyAsync(out, h->dB.p, (size_t)b * n * 8, hipMemcpyDeviceToHost, h->stream));
   GPS_HIP(h, hipStreamSynchronize(h->stream));
   return GPS_OK;
 }
@@ -160,8 +159,6 @@ static int uncond_body(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes,
   const i64 mp = gps_pad(m);
   const size_t mm = (size_t)mp * mp;
   const i64 nw = full ? k * (k + 1) / 2 : k;                          // weight matrices = planes of the contraction
-  GPS_HIP(h, h->dK.ensure(mm * 8));
-  GPS_HIP(h, h->dLinv.ensure(linv_bytes(mp)));
   GPS_HIP(h, h->dTmp.ensure(mm * 8));
   GPS_HIP(h, h->dS1.ensure(mm * 8));
   GPS_HIP(h, h->dS2.ensure(mm * 8));
@@ -172,28 +169,18 @@ static int uncond_body(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes,
   GPS_HIP(h, h->dMean.ensure((size_t)(n * k + n) * 8));
   GPS_HIP(h, h->dVar.ensure((size_t)nw * n * 8));
   GPS_HIP(h, h->dB.ensure((size_t)n * k * (full ? k : 1) * 8));
-  int* d_info = (int*)h->dInfo.p;
-  rc = gps_launch_fill_info(h, d_info, INT_MAX);
+  // L = chol(Kuu + jitter I) -> dK (d_info is read back with the results) ; U = L^T -> dTmp
+  KuuFactor kf;
+  rc = kuu_factor(h, prog, n_nodes, m, q, jitter, true, kf);
   if (rc) return rc;
-  // L = chol(Kuu + jitter I) -> dK ; U = L^T -> dTmp
-  rc = inducing_kuu(h, prog, n_nodes, m, q, jitter);
-  if (rc) return rc;
-  HipOps ops = factor_ops(h, h->dLinv.d(), mp, d_info);
-  Blocked<HipOps> bl(ops);
+  Blocked<HipOps>& bl = kf.bl;
+  int* d_info = kf.ops.d_info;
   double* L = h->dK.d(); double* U = h->dTmp.d();
-  rc = bl.potrf_rec(L, mp, mp, 0, 0);
-  if (rc) return rc;
-  rc = classify_blocks(h, ops, L, mp, mp);
-  if (rc) return rc;
-  rc = gps_launch_transpose(h, L, mp, mp, mp, U, mp);
-  if (rc) return rc;
-  rc = gps_launch_tri_map(h, U, mp, mp, 3);
+  rc = upper_factor(h, L, mp, U);
   if (rc) return rc;
   // a^T [k][mp] and b^T = (L^-T a)^T [k][mp] -> dAlpha
   double* dA = h->dAlpha.d(); double* dBv = dA + (size_t)k * mp;
-  GPS_HIP(h, hipMemcpyAsync(h->dTmp2.p, q_mu, (size_t)m * k * 8, hipMemcpyHostToDevice, h->stream));
-  GPS_HIP(h, hipMemsetAsync(dA, 0, (size_t)k * mp * 8, h->stream));
-  rc = gps_launch_transpose(h, h->dTmp2.d(), k, m, k, dA, mp);
+  rc = planes_upload(h, q_mu, m, k, h->dTmp2.d(), dA, mp);
   if (rc) return rc;
   if (!white) { rc = bl.trsv_rec(L, mp, mp, 0, dA, mp, k); if (rc) return rc; }
   GPS_HIP(h, hipMemcpyAsync(dBv, dA, (size_t)k * mp * 8, hipMemcpyDeviceToDevice, h->stream));
@@ -292,7 +279,7 @@ extern "C" int gps_uncertain_conditional(gps_handle_t h, const gps_kern_node_t* 
   if (rc) return rc;
   if (!q_mu || !q_sqrt || !fmean || !fvar || k <= 0) return gps_fail(h, GPS_ERR_ARG, "gps_uncertain_conditional: bad argument");
   if (q_sqrt_ndim != 2 && q_sqrt_ndim != 3) return gps_fail(h, GPS_ERR_ARG, "gps_uncertain_conditional: q_sqrt_ndim must be 2 or 3");
-  if (k > GPS_TILE) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gps_uncertain_conditional: at most 128 outputs");
+  if (int rf = refuse_unsupported(h, "gps_uncertain_conditional", false, k, "outputs")) return rf;   // (sharded: refused above)
   if (full_cov_output && k > 16)
     return gps_fail(h, GPS_ERR_UNSUPPORTED, "gps_uncertain_conditional: full_cov_output takes at most 16 outputs");
   return with_la_retry(h, [&]() -> int {

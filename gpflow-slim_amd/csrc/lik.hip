@@ -16,7 +16,7 @@
 // far below the 4 KB limit); it is indexed by the point's label, once per point and outside the node loop.  Sums over the
 // points: one partial per workgroup, added up on the host in index order (no floating-point atomics: the bound is
 // bit-reproducible run to run).
-#include "gps_common.hpp"
+#include "gps_ops.hpp"
 #include "lik_math.hpp"
 
 struct LikDev {
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(256) void lik_elem_kernel(const LikDev L, const dou
 // log p(y | f) itself at f = F + mean, no q(f): the likelihood of the MCMC models (models/gpmc.py:75-77), one thread per (point,
 // latent).  Bernoulli, Student-t, Beta and Ordinal are lik_logp; the other four are the closed forms above at fvar = 0, written out (the
 // quadrature path at fvar = 0 would divide by sqrt(2 var), and its weights do not add up to exactly 1).  F and G = d log p / d F
-// through strided views, so they can stay planes [k][ld] between the triangular products of gps_gpmc.hip.
+// through strided views, so they can stay planes [k][ld] between the triangular products of skinny.hip (GPMC).
 template <int KIND>
 __global__ __launch_bounds__(256) void lik_point_kernel(const LikDev L, const double* __restrict__ F, LikView fv,
                                                         const double* __restrict__ mean, const double* __restrict__ Y, i64 n, int k,
@@ -395,12 +395,10 @@ int gps_lik_prepare(gps_handle_t h, const gps_lik_t* lik, i64 k, LikHost* out) {
   const bool quad = lik->kind == GPS_LIK_BERNOULLI || lik->kind == GPS_LIK_STUDENT_T || lik->kind == GPS_LIK_MULTICLASS ||
                     lik->kind == GPS_LIK_BETA || lik->kind == GPS_LIK_ORDINAL;
   switch (lik->kind) {
-    case GPS_LIK_GAMMA:
-      if (!(L.p[0] > 0.0) || !std::isfinite(L.p[0])) return gps_fail(h, GPS_ERR_ARG, "likelihood: the Gamma shape must be positive");
-      L.p[2] = lgamma(L.p[0]); L.p[3] = digamma(L.p[0]);
-      break;
-    case GPS_LIK_BETA:
-      if (!(L.p[0] > 0.0) || !std::isfinite(L.p[0])) return gps_fail(h, GPS_ERR_ARG, "likelihood: the Beta scale must be positive");
+    case GPS_LIK_GAMMA: case GPS_LIK_BETA:
+      if (!(L.p[0] > 0.0) || !std::isfinite(L.p[0]))
+        return gps_fail(h, GPS_ERR_ARG, lik->kind == GPS_LIK_GAMMA ? "likelihood: the Gamma shape must be positive"
+                                                                   : "likelihood: the Beta scale must be positive");
       L.p[2] = lgamma(L.p[0]); L.p[3] = digamma(L.p[0]);
       break;
     case GPS_LIK_ORDINAL:
@@ -439,6 +437,33 @@ int gps_lik_prepare(gps_handle_t h, const gps_lik_t* lik, i64 k, LikHost* out) {
   return GPS_OK;
 }
 
+// GO(KIND) with the likelihood kind as a compile-time constant: the eight kinds whose kernels take one element per thread
+#define LIK_BY_KIND(kind, GO) \
+  switch (kind) { \
+    case GPS_LIK_GAUSSIAN: GO(GPS_LIK_GAUSSIAN); break; \
+    case GPS_LIK_BERNOULLI: GO(GPS_LIK_BERNOULLI); break; \
+    case GPS_LIK_POISSON: GO(GPS_LIK_POISSON); break; \
+    case GPS_LIK_EXPONENTIAL: GO(GPS_LIK_EXPONENTIAL); break; \
+    case GPS_LIK_STUDENT_T: GO(GPS_LIK_STUDENT_T); break; \
+    case GPS_LIK_GAMMA: GO(GPS_LIK_GAMMA); break; \
+    case GPS_LIK_BETA: GO(GPS_LIK_BETA); break; \
+    case GPS_LIK_ORDINAL: GO(GPS_LIK_ORDINAL); break; \
+    default: return gps_fail(h, GPS_ERR_ARG, "likelihood: unknown kind"); \
+  }
+
+// sums [width] <- the `width` partial sums that each of the `grid` workgroups left in dLikPart, added in index order on the host;
+// the stream is synchronised
+static int lik_read_partials(gps_handle_t h, unsigned grid, int width, double* sums) {
+  GPS_HIP(h, hipGetLastError());
+  std::vector<double> part((size_t)grid * width);
+  GPS_HIP(h, hipMemcpyAsync(part.data(), h->dLikPart.p, part.size() * 8, hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipStreamSynchronize(h->stream));
+  for (int j = 0; j < width; ++j) sums[j] = 0.0;
+  for (unsigned b = 0; b < grid; ++b)
+    for (int j = 0; j < width; ++j) sums[j] += part[(size_t)width * b + j];
+  return GPS_OK;
+}
+
 // Launch on device-resident moments.  fmu [n, k] row-major (+ mean [n, k] or NULL); fvar through (v_si, v_sq); Y [n, k] ([n] labels
 // for MultiClass).  want_grad: dmu / dvar through (o_si, o_sq), multiplied by oscale.  *ve_sum / *dparam_sum (unscaled) and
 // *dvar_sum (= sum of what went to dvar) on return; the stream is synchronised.
@@ -466,29 +491,16 @@ int gps_lik_launch(gps_handle_t h, const LikHost* LH, const double* fmu, const d
 #define LIK_GO(KIND) do { \
       if (want_grad) hipLaunchKernelGGL((lik_elem_kernel<KIND, 1>), dim3(grid), dim3(256), 0, h->stream, L, fmu, mean, fvar, vv, Y, n, (int)k, oscale, dmu, dvar, ov, part); \
       else hipLaunchKernelGGL((lik_elem_kernel<KIND, 0>), dim3(grid), dim3(256), 0, h->stream, L, fmu, mean, fvar, vv, Y, n, (int)k, oscale, dmu, dvar, ov, part); } while (0)
-    switch (L.kind) {
-      case GPS_LIK_GAUSSIAN: LIK_GO(GPS_LIK_GAUSSIAN); break;
-      case GPS_LIK_BERNOULLI: LIK_GO(GPS_LIK_BERNOULLI); break;
-      case GPS_LIK_POISSON: LIK_GO(GPS_LIK_POISSON); break;
-      case GPS_LIK_EXPONENTIAL: LIK_GO(GPS_LIK_EXPONENTIAL); break;
-      case GPS_LIK_STUDENT_T: LIK_GO(GPS_LIK_STUDENT_T); break;
-      case GPS_LIK_GAMMA: LIK_GO(GPS_LIK_GAMMA); break;
-      case GPS_LIK_BETA: LIK_GO(GPS_LIK_BETA); break;
-      case GPS_LIK_ORDINAL: LIK_GO(GPS_LIK_ORDINAL); break;
-      default: return gps_fail(h, GPS_ERR_ARG, "likelihood: unknown kind");
-    }
+    LIK_BY_KIND(L.kind, LIK_GO)
 #undef LIK_GO
   }
   }
-  GPS_HIP(h, hipGetLastError());
-  std::vector<double> part((size_t)grid * 3);
-  GPS_HIP(h, hipMemcpyAsync(part.data(), h->dLikPart.p, part.size() * 8, hipMemcpyDeviceToHost, h->stream));
-  GPS_HIP(h, hipStreamSynchronize(h->stream));
-  double ve = 0.0, dp = 0.0, hv = 0.0;
-  for (unsigned b = 0; b < grid; ++b) { ve += part[3 * b]; dp += part[3 * b + 1]; hv += part[3 * b + 2]; }
-  if (ve_sum) *ve_sum = ve;
-  if (dparam_sum) *dparam_sum = dp;
-  if (dvar_sum) *dvar_sum = hv;
+  double sums[3];                                                  // var_exp, d / d param[0], dvar
+  const int rc = lik_read_partials(h, grid, 3, sums);
+  if (rc) return rc;
+  if (ve_sum) *ve_sum = sums[0];
+  if (dparam_sum) *dparam_sum = sums[1];
+  if (dvar_sum) *dvar_sum = sums[2];
   return GPS_OK;
 }
 
@@ -507,27 +519,14 @@ int gps_lik_point_launch(gps_handle_t h, const LikHost* LH, const double* F, i64
   {
     LaunchScope ls(h, KC_OTHER, 40.0 * n * k, 8.0 * n * k * (G ? 4.0 : 3.0));
 #define LIK_GO(KIND) hipLaunchKernelGGL((lik_point_kernel<KIND>), dim3(grid), dim3(256), 0, h->stream, L, F, fv, mean, Y, n, (int)k, G, gv, part)
-    switch (L.kind) {
-      case GPS_LIK_GAUSSIAN: LIK_GO(GPS_LIK_GAUSSIAN); break;
-      case GPS_LIK_BERNOULLI: LIK_GO(GPS_LIK_BERNOULLI); break;
-      case GPS_LIK_POISSON: LIK_GO(GPS_LIK_POISSON); break;
-      case GPS_LIK_EXPONENTIAL: LIK_GO(GPS_LIK_EXPONENTIAL); break;
-      case GPS_LIK_STUDENT_T: LIK_GO(GPS_LIK_STUDENT_T); break;
-      case GPS_LIK_GAMMA: LIK_GO(GPS_LIK_GAMMA); break;
-      case GPS_LIK_BETA: LIK_GO(GPS_LIK_BETA); break;
-      case GPS_LIK_ORDINAL: LIK_GO(GPS_LIK_ORDINAL); break;
-      default: return gps_fail(h, GPS_ERR_ARG, "likelihood: unknown kind");
-    }
+    LIK_BY_KIND(L.kind, LIK_GO)
 #undef LIK_GO
   }
-  GPS_HIP(h, hipGetLastError());
-  std::vector<double> hp((size_t)grid * 2);
-  GPS_HIP(h, hipMemcpyAsync(hp.data(), part, hp.size() * 8, hipMemcpyDeviceToHost, h->stream));
-  GPS_HIP(h, hipStreamSynchronize(h->stream));
-  double lp = 0.0, dp = 0.0;
-  for (unsigned b = 0; b < grid; ++b) { lp += hp[2 * b]; dp += hp[2 * b + 1]; }
-  if (sum) *sum = lp;
-  if (dparam_sum) *dparam_sum = dp;
+  double sums[2];                                                  // log p, d / d param[0]
+  const int rc = lik_read_partials(h, grid, 2, sums);
+  if (rc) return rc;
+  if (sum) *sum = sums[0];
+  if (dparam_sum) *dparam_sum = sums[1];
   return GPS_OK;
 }
 
@@ -535,7 +534,7 @@ int gps_lik_point_launch(gps_handle_t h, const LikHost* LH, const double* F, i64
 extern "C" int gps_lik_logp(gps_handle_t h, const gps_lik_t* lik, const double* F, const double* Y, int64_t n, int64_t k,
                             double* logp_sum, double* dF_out, double* dparam_out) {
   if (!h || !lik || !F || !Y || !logp_sum || n <= 0 || k <= 0) return gps_fail(h, GPS_ERR_ARG, "gps_lik_logp: bad argument");
-  if (k > GPS_TILE) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gps_lik_logp: at most 128 latent functions");
+  if (int rf = refuse_unsupported(h, "gps_lik_logp", false, k, "latent functions")) return rf;
   GPS_HIP(h, hipSetDevice(h->device));
   LikHost LH;
   int rc = gps_lik_prepare(h, lik, k, &LH);
@@ -562,7 +561,7 @@ extern "C" int gps_lik_varexp(gps_handle_t h, const gps_lik_t* lik, const double
                               int64_t n, int64_t k, double* var_exp_out, double* dmu_out, double* dvar_out, double* dparam_out) {
   if (!h || !lik || !fmu || !fvar || !Y || !var_exp_out || n <= 0 || k <= 0 || (!dmu_out) != (!dvar_out))
     return gps_fail(h, GPS_ERR_ARG, "gps_lik_varexp: bad argument");
-  if (k > GPS_TILE) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gps_lik_varexp: at most 128 latent functions");
+  if (int rf = refuse_unsupported(h, "gps_lik_varexp", false, k, "latent functions")) return rf;
   GPS_HIP(h, hipSetDevice(h->device));
   LikHost LH;
   int rc = gps_lik_prepare(h, lik, k, &LH);

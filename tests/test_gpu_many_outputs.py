@@ -1,7 +1,7 @@
 """The models at 5 to 129 output columns (latent functions), where the device code handles the columns in groups: pairs of
 right-hand sides (csrc/trsv_wave.hip), 4 at a time (the gemv kernels of csrc/blas1.hip and the Psi1 VJPs of csrc/psi.hip), the first
 8 in registers (svgp_abar_kernel), 8 per workgroup row (lik_rowsq_kernel), 1 / 4 / 16 planes and then 16 at a time
-(skinny_xt_kernel of csrc/gps_sgpmc.hip, tri_skinny and chol_seed of csrc/gps_gpmc.hip), up to 16 columns in the one-launch
+(skinny_xt_kernel, tri_skinny and chol_seed of csrc/skinny.hip), up to 16 columns in the one-launch
 small-N path and up to 128 augmented rows (csrc/gps_gpr.hip).  R = 5, 9, 17 are a full group plus a remainder for the group sizes
 2, 4, 8 and 16; R = 128 is the last count every entry point takes and 129 the first that the capped ones refuse.
 
