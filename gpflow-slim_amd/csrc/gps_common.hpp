@@ -2,6 +2,7 @@
 // libgpflowslim_hip.so.  Not part of the public ABI (include/gpflowslim_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -566,13 +567,59 @@ int gps_launch_kmat_block(gps_handle_t h, const gps_kern_node_t* prog, int n_nod
                           i64 n, i64 d_all, i64 npad, double diag_add, double* dKb, i64 ldk, i64 r0,
                           i64 nrows, i64 c0, i64 ncols, int prep);
 int gps_launch_kdiag(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double* kdiag_const);
-// Kdiag of a program that contains Linear / Polynomial / ArcCosine depends on the point: gps_launch_kdiag refuses those, and
+// Kdiag of a program that contains Linear / Polynomial / ArcCosine / Coregion depends on the point: gps_launch_kdiag refuses those, and
 // gps_launch_kdiag_vec writes Kdiag(X)[i] for the n resident points dX [n, d_all] to d_out [n] (any program; uses dFeat).
 // sum_out (optional): sum_i Kdiag_i on the host -- that one synchronises.
 bool gps_kdiag_is_const(const gps_kern_node_t* prog, int n_nodes);
 #define GPS_KDIAG_NOT_CONST_MSG "Kdiag is not constant for a kernel program with Linear / Polynomial: this path takes constant-Kdiag kernels only"
 int gps_launch_kdiag_vec(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n, i64 d_all, double* d_out,
                          double* sum_out);
+// ---- Coregion (kernels.py:822-881): k = B[a_i, a_j], B = W W^T + diag(kappa), a = the integer label in one column of X.  What the
+// kernel-matrix build and the gradient kernels share: the node's fields (output_dim P in `period`, rank R in active_dims[1], W
+// row-major then kappa in lengthscales[]), the label, and the looked-up feature value.
+static inline int gps_coregion_check(gps_handle_t h, const gps_kern_node_t& nd, i64 d_all, const char* who, int* P_out, int* R_out) {
+  char msg[200];
+  const int P = (int)nd.period, R = nd.active_dims[1];
+  if (nd.n_dims != 1 || !(nd.period >= 1.0) || nd.period != floor(nd.period) || R < 0) {
+    snprintf(msg, sizeof(msg), "%s: Coregion takes one index column, output_dim >= 1 and rank >= 0", who);
+    return gps_fail(h, GPS_ERR_ARG, msg);
+  }
+  if (nd.variance != 1.0) {
+    snprintf(msg, sizeof(msg), "%s: Coregion carries W and kappa, the variance field must be 1", who);
+    return gps_fail(h, GPS_ERR_ARG, msg);
+  }
+  if (nd.active_dims[0] < 0 || nd.active_dims[0] >= d_all) {
+    snprintf(msg, sizeof(msg), "%s: active dim outside X", who);
+    return gps_fail(h, GPS_ERR_ARG, msg);
+  }
+  if (nd.period > (double)GPS_MAX_DIMS || R > GPS_MAX_DIMS || P * (R + 1) > GPS_MAX_DIMS) {
+    snprintf(msg, sizeof(msg), "%s: Coregion takes at most output_dim (rank + 1) = 32 values (W and kappa share one field)", who);
+    return gps_fail(h, GPS_ERR_UNSUPPORTED, msg);
+  }
+  for (int p = 0; p < P; ++p)
+    if (!(nd.lengthscales[P * R + p] > 0.0)) {
+      snprintf(msg, sizeof(msg), "%s: Coregion kappa must be positive", who);
+      return gps_fail(h, GPS_ERR_ARG, msg);
+    }
+  *P_out = P; *R_out = R;
+  return GPS_OK;
+}
+// (offset into the table, P or p, stride) of a looked-up feature as one exactly representable double
+static inline double gps_lookup_code(int off, int p, int stride) { return (double)(off | (p << 16) | (stride << 24)); }
+#ifdef __HIPCC__
+// the label of a point: x truncated toward zero like tf.cast (kernels.py:869), or -1 where x is not finite or the label lies
+// outside [0, P) -- the caller then reads nothing
+__device__ __forceinline__ int gps_label(double x, int P) { return (x > -1.0 && x < (double)P) ? (int)x : -1; }
+// w_column: lut[off + a * stride] for a label a in [0, P) ; otherwise lut[off] where the label is p ; 0 for every other point
+__device__ __forceinline__ double gps_lookup_feature(bool w_column, double x, int code, const double* __restrict__ lut) {
+  const int off = code & 0xffff, p = (code >> 16) & 0xff, stride = (code >> 24) & 0xff;
+  if (w_column) {
+    const int a = gps_label(x, p);
+    return a < 0 ? 0.0 : lut[off + a * stride];
+  }
+  return gps_label(x, p + 1) == p ? lut[off] : 0.0;
+}
+#endif
 // grad.hip, grad_general.hip (what the two share among themselves: grad_common.hpp)
 // slot count and, per slot, the lengthscale that divides its raw sum (0: none) -- of any program, whichever kernel takes it
 int gps_grad_slots(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, int* n_slots);

@@ -396,11 +396,12 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const double* __restri
   if (threadIdx.x == 0) out[s] = red[0];
 }
 
-// programs this file's kernel does not take go to grad_general.hip
+// programs this file's kernel does not take go to grad_general.hip: network programs, more than four primitives, and every
+// program with a Coregion node (its formulas live in grad_general.hip alone, so that the instances here keep their code)
 bool gps_grad_is_simple(const gps_kern_node_t* prog, int n_nodes) {
   int prims = 0;
   for (int i = 0; i < n_nodes; ++i) {
-    if (prog[i].op >= GPS_K_NKN_LINROW) return false;
+    if (prog[i].op >= GPS_K_NKN_LINROW || prog[i].op == GPS_K_COREGION) return false;
     if (prog[i].op != GPS_K_ADD && prog[i].op != GPS_K_MUL) ++prims;
   }
   return prims <= G_MAXP;
@@ -416,6 +417,8 @@ static int grad_prepare(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes
   GProg& P = *reinterpret_cast<GProg*>(post->blob.data());
   for (int i = 0; i < n_nodes; ++i)
     if (prog[i].op >= GPS_K_NKN_LINROW) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: neural-kernel-network programs are not supported yet");
+  for (int i = 0; i < n_nodes; ++i)
+    if (prog[i].op == GPS_K_COREGION) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: programs with Coregion belong to the general kernel");
   GradPrims R;
   int rc = grad_analyse_prims(h, prog, n_nodes, d_all, G_MAXP, "gradient: kernel programs with more than 4 primitive nodes are not supported yet",
                               false, P.nodes, R);

@@ -16,14 +16,21 @@
 struct GradFeat { int dim; int kind; double param; };   // 0: x/param ; 1: cos(2pi x/param) ; 2: sin ; 3: 2pi x/param ; 4: x*param
 // 5 / 6: cos / sin of a = sum_q x[tab[dim + q].dim] * tab[dim + q].param over the (int)param table entries from index `dim` on
 // (Cosine: its kind-4 rows G_d = x_d w_d / l_d)
+// 7 / 8: looked up by the integer label a = (int)x[dim] (Coregion; gps_lookup_feature of gps_common.hpp) in the table of doubles
+// that follows the feature table: 7: W[a, r], 8: sqrt(kappa_p) where a == p; zero for a label outside [0, P)
 // variance: Polynomial: the offset (Linear: 1) ; period: RatQuad: alpha, Polynomial: degree, ArcCosine: order ; ls0: Periodic:
 // the lengthscale, ArcCosine: the bias variance
+// Coregion: ndims = nf = R + P (rows F_0 .. F_{R-1}, E_0 .. E_{P-1}), ls0: P, period: R
 struct GradNode { int op; int prim; int f0; int nf; int slot0; int ndims; double variance; double ls0; double period; };
 
 // ---- feature prep: Ft[f][i] = feature f of point i (zero in the padding) ------------------------------------------------------
 #define GRAD_PREP_SMALL_F 24
 struct GradTabPtr { const GradFeat* __restrict__ f; };
 struct GradTabVal { GradFeat f[GRAD_PREP_SMALL_F]; };    // (a small table travels in the kernel arguments: no copy command in front of the launch)
+// programs with looked-up features (Coregion): only this instance knows kinds 7 / 8, the other two keep the code they had
+struct GradTabLut { const GradFeat* __restrict__ f; const double* __restrict__ lut; };
+template <class Tab> struct grad_tab_has_lut { static constexpr bool value = false; };
+template <> struct grad_tab_has_lut<GradTabLut> { static constexpr bool value = true; };
 template <class Tab>
 __global__ __launch_bounds__(256) void grad_prep_kernel(const double* __restrict__ X, i64 n, i64 d_all, i64 npad, Tab tab, int nfeat,
                                                         double* __restrict__ Ft, i64 ldf) {
@@ -33,6 +40,12 @@ __global__ __launch_bounds__(256) void grad_prep_kernel(const double* __restrict
     double v = 0.0;
     if (i < n) {
       const GradFeat pf = tab.f[f];
+      if constexpr (grad_tab_has_lut<Tab>::value) {
+        if (pf.kind >= 7) {
+          Ft[(i64)f * ldf + i] = gps_lookup_feature(pf.kind == 7, X[i * d_all + pf.dim], (int)pf.param, tab.lut);
+          continue;
+        }
+      }
       if (pf.kind >= 5) {
         double ang = 0.0;
         for (int q = 0; q < (int)pf.param; ++q) { const GradFeat cf = tab.f[pf.dim + q]; ang = fma(X[i * d_all + cf.dim], cf.param, ang); }
@@ -53,10 +66,22 @@ __global__ __launch_bounds__(256) void grad_prep_kernel(const double* __restrict
 
 // features of `n` points (padded to npad) into Ft [nfeat][npad].  in_args: a small table goes by value; otherwise (and always
 // for callers whose kernels read the table later) it is uploaded to dProg and stays there.
+// lut: the table of the looked-up features (Coregion), uploaded behind the feature table.
 static int grad_launch_prep(gps_handle_t h, const std::vector<GradFeat>& feats, const double* dX, i64 n, i64 d_all, i64 npad, double* Ft,
-                            bool in_args) {
+                            bool in_args, const std::vector<double>* lut = nullptr) {
   const int nfeat = (int)feats.size();
   const dim3 grid((unsigned)((npad + 255) / 256));
+  if (lut && !lut->empty()) {
+    const size_t fb = (size_t)nfeat * sizeof(GradFeat), lb = lut->size() * sizeof(double);
+    GPS_HIP(h, h->dProg.ensure(fb + lb + 64));
+    GPS_HIP(h, h->ring.upload(h->dProg.p, feats.data(), fb, h->stream));
+    GPS_HIP(h, h->ring.upload((char*)h->dProg.p + fb, lut->data(), lb, h->stream));
+    LaunchScope ls(h, KC_KMAT, 0.0, 8.0 * (double)npad * nfeat);
+    hipLaunchKernelGGL(grad_prep_kernel<GradTabLut>, grid, dim3(256), 0, h->stream, dX, n, d_all, npad,
+                       GradTabLut{(const GradFeat*)h->dProg.p, (const double*)((char*)h->dProg.p + fb)}, nfeat, Ft, npad);
+    GPS_HIP(h, hipGetLastError());
+    return GPS_OK;
+  }
   in_args = in_args && nfeat <= GRAD_PREP_SMALL_F;
   if (!in_args) {
     GPS_HIP(h, h->dProg.ensure((size_t)nfeat * sizeof(GradFeat) + 64));
@@ -226,7 +251,7 @@ __device__ __forceinline__ double grad_prog_tangent(const Prog& P, const double 
 static inline bool grad_is_prim(int op) {
   return op == GPS_K_RBF || op == GPS_K_MATERN12 || op == GPS_K_MATERN32 || op == GPS_K_MATERN52 || op == GPS_K_PERIODIC ||
          op == GPS_K_WHITE || op == GPS_K_CONSTANT || op == GPS_K_EXPONENTIAL || op == GPS_K_RATQUAD || op == GPS_K_LINEAR ||
-         op == GPS_K_POLYNOMIAL || op == GPS_K_COSINE || op == GPS_K_ARCCOSINE;
+         op == GPS_K_POLYNOMIAL || op == GPS_K_COSINE || op == GPS_K_ARCCOSINE || op == GPS_K_COREGION;
 }
 
 // what the analysis hands back beside the device nodes: the feature table, the lengthscale (Linear / Polynomial: the
@@ -235,13 +260,14 @@ struct GradPrims {
   int n_prims = 0, n_slots = 0;
   std::vector<GradFeat> feats;
   std::vector<double> ls_of_slot;
+  std::vector<double> lut;       // Coregion: per node W row-major, then sqrt(kappa) (the table of the looked-up features)
 };
 
 // nodes [0, n_nodes) of `prog` -- primitives and, unless the program feeds a network (nkn), Sum / Product -- into `nodes`:
 // stack discipline, parameter ranges, feature rows and slots ([variance] then one slot per active dim, Periodic:
 // [lengthscale, period], White / Constant: nothing more, RatQuad: [alpha] after the dims; Linear: one slot per active dim and
 // no variance slot, Polynomial: the same and then [offset]; Cosine: [variance, l_0 .., w_0 ..]; ArcCosine: [variance, bias
-// variance, w_0 ..]), at most max_prims primitives (too_many: the kernel's own message)
+// variance, w_0 ..]; Coregion: [W row-major, kappa_0 ..] and no variance slot), at most max_prims primitives (too_many: the kernel's own message)
 static int grad_analyse_prims(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, int max_prims, const char* too_many,
                               bool nkn, GradNode* nodes, GradPrims& R) {
   if (n_nodes <= 0 || n_nodes > GRAD_MAX_NODES) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: program too long");
@@ -266,14 +292,30 @@ static int grad_analyse_prims(gps_handle_t h, const gps_kern_node_t* prog, int n
     if (!nkn && depth > GPS_MAX_STACK) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: expression too deep");
     if (!(nd.variance > 0.0)) return gps_fail(h, GPS_ERR_ARG, "gradient: variance must be positive");
     const bool dot = nd.op == GPS_K_LINEAR || nd.op == GPS_K_POLYNOMIAL;
-    if (!dot) ls_of_slot.push_back(0.0);
+    if (!dot && nd.op != GPS_K_COREGION) ls_of_slot.push_back(0.0);
     if (nd.op == GPS_K_WHITE || nd.op == GPS_K_CONSTANT) { R.n_slots += 1; continue; }
     if (nd.n_dims <= 0 || nd.n_dims > GPS_MAX_DIMS) return gps_fail(h, GPS_ERR_ARG, "gradient: n_dims out of range");
     for (int d = 0; d < nd.n_dims; ++d)
       if (nd.active_dims[d] < 0 || nd.active_dims[d] >= d_all) return gps_fail(h, GPS_ERR_ARG, "gradient: active dim outside X");
     g.ndims = nd.n_dims;
     g.f0 = (int)feats.size();
-    if (nd.op == GPS_K_PERIODIC) {
+    if (nd.op == GPS_K_COREGION) {
+      // rows F_r = W[a, r] and E_p = sqrt(kappa_p) [a == p]: k = sum of their products.  The raw sums of the kernel carry E_p where
+      // the derivative has the indicator [a == p]: the host divides a W slot by sqrt(kappa_p) and a kappa slot by kappa_p.
+      int P = 0, Rk = 0;
+      int rcc = gps_coregion_check(h, nd, d_all, "gradient", &P, &Rk);
+      if (rcc) return rcc;
+      const int l0 = (int)R.lut.size();
+      for (int q = 0; q < P * Rk; ++q) R.lut.push_back(nd.lengthscales[q]);
+      for (int p = 0; p < P; ++p) R.lut.push_back(sqrt(nd.lengthscales[P * Rk + p]));
+      for (int r = 0; r < Rk; ++r) feats.push_back({nd.active_dims[0], 7, gps_lookup_code(l0 + r, P, Rk)});
+      for (int p = 0; p < P; ++p) feats.push_back({nd.active_dims[0], 8, gps_lookup_code(l0 + P * Rk + p, p, 0)});
+      g.ndims = Rk + P; g.nf = Rk + P; g.ls0 = (double)P; g.period = (double)Rk;
+      for (int p = 0; p < P; ++p)
+        for (int r = 0; r < Rk; ++r) ls_of_slot.push_back(sqrt(nd.lengthscales[P * Rk + p]));
+      for (int p = 0; p < P; ++p) ls_of_slot.push_back(nd.lengthscales[P * Rk + p]);
+      R.n_slots += P * (Rk + 1);
+    } else if (nd.op == GPS_K_PERIODIC) {
       for (int d = 0; d < nd.n_dims; ++d) { feats.push_back({nd.active_dims[d], 1, nd.period}); feats.push_back({nd.active_dims[d], 2, nd.period}); }
       for (int d = 0; d < nd.n_dims; ++d) feats.push_back({nd.active_dims[d], 3, nd.period});
       g.nf = 3 * nd.n_dims; g.ls0 = nd.lengthscales[0];

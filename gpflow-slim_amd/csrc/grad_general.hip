@@ -15,6 +15,12 @@
 // Slot layout (host and device agree on it): primitives first, as in grad.hip ([variance], then one slot per active
 // dim, or [lengthscale, period] for Periodic; RatQuad, Linear, Polynomial, Cosine, ArcCosine: see grad.hip); then, for every Linear layer in network order and every output o:
 // [W[o][0 .. in-1], bias[o]].
+//
+// Coregion (kernels.py:822-881; every program that holds one comes here, gps_grad_is_simple): k = sum_f F_f F'_f over the looked-up
+// rows F_r = W[a, r], E_p = sqrt(kappa_p) [a == p], so d k / d kappa_p = [a_i == p] [a_j == p] = E_p E'_p / kappa_p and
+// d k / d W[p][r] = [a_i == p] F'_r + F_r [a_j == p] = (E_p F'_r + F_r E'_p) / sqrt(kappa_p); slots [W row-major, kappa_0 ..].  The
+// label column receives no input gradient.  The formulas are compiled into instances of their own (CRG: gg_coregion_kernel,
+// gg_input_coregion_kernel); gg_kernel and gg_input_kernel keep the code they had.
 #include "grad_common.hpp"
 
 #define GG_T 32            // tile edge
@@ -83,6 +89,7 @@ __device__ __forceinline__ void gg_arc(const GradNode& node, const double* Fr_s,
 
 // value and (squared distance | periodic sum | Linear / Polynomial: lin | Cosine: sin(a_i - a_j)) of one primitive at the thread's
 // four entries
+template <bool CRG = false>
 __device__ __forceinline__ void gg_prim(const GradNode& node, const double* Fr_s, const double* Fc_s, int ty, int tx, i64 gi0,
                                         i64 gj0, bool same_points, double (&val)[GG_E], double (&rr)[GG_E]) {
   if (node.op == GPS_K_CONSTANT) {
@@ -117,7 +124,8 @@ __device__ __forceinline__ void gg_prim(const GradNode& node, const double* Fr_s
   double acc[GG_E];
 #pragma unroll
   for (int e = 0; e < GG_E; ++e) acc[e] = 0.0;
-  if (node.op == GPS_K_PERIODIC || grad_is_dot(node.op)) {
+  const bool coregion = CRG && node.op == GPS_K_COREGION;      // its value is Linear's: the dot product of its rows
+  if (node.op == GPS_K_PERIODIC || grad_is_dot(node.op) || coregion) {
     const int nfd = (node.op == GPS_K_PERIODIC) ? 2 * node.ndims : node.ndims;
     for (int f = 0; f < nfd; ++f) {
       const double r0 = Fr_s[f * GG_T + ty * 2], r1 = Fr_s[f * GG_T + ty * 2 + 1];
@@ -128,6 +136,9 @@ __device__ __forceinline__ void gg_prim(const GradNode& node, const double* Fr_s
       const double l2 = node.ls0 * node.ls0;
 #pragma unroll
       for (int e = 0; e < GG_E; ++e) val[e] = grad_periodic_value(node.variance, node.ndims, acc[e], l2, &rr[e]);
+    } else if (coregion) {
+#pragma unroll
+      for (int e = 0; e < GG_E; ++e) { rr[e] = acc[e]; val[e] = acc[e]; }
     } else {                                 // Linear / Polynomial: rr keeps lin
 #pragma unroll
       for (int e = 0; e < GG_E; ++e) { rr[e] = acc[e]; val[e] = grad_dot_value(node.op, acc[e], node.variance, node.period); }
@@ -146,6 +157,7 @@ __device__ __forceinline__ void gg_prim(const GradNode& node, const double* Fr_s
 }
 
 // ---- pass 1: values of all primitives at the thread's four entries of tile (gi0, gj0)
+template <bool CRG = false>
 __device__ __forceinline__ void gg_values(const GGArgs& a, const GGProg& P, i64 gi0, i64 gj0, bool same_points, double* Fr_s,
                                           double* Fc_s, int tid, int ty, int tx, double (&pv)[GG_MAXP][GG_E]) {
 #pragma unroll
@@ -157,7 +169,7 @@ __device__ __forceinline__ void gg_values(const GGArgs& a, const GGProg& P, i64 
     if (node.prim < 0) continue;
     if (node.nf > 0) gg_stage(a, node.f0, gg_value_rows(node), gi0, gj0, Fr_s, Fc_s, tid);
     double val[GG_E], rr[GG_E];
-    gg_prim(node, Fr_s, Fc_s, ty, tx, gi0, gj0, same_points, val, rr);
+    gg_prim<CRG>(node, Fr_s, Fc_s, ty, tx, gi0, gj0, same_points, val, rr);
 #pragma unroll
     for (int p = 0; p < GG_MAXP; ++p)
       if (node.prim == p) {
@@ -260,7 +272,9 @@ __device__ __forceinline__ void gg_adjoints(const GGProg& P, const double* W_s, 
     }
 }
 
-__global__ __launch_bounds__(256) void gg_kernel(GGArgs a, GGProg P) {
+// CRG: the instance that knows Coregion
+template <bool CRG>
+__device__ __forceinline__ void gg_body(GGArgs a, GGProg P) {
   __shared__ double Fr_s[GRAD_MAXF * GG_T];
   __shared__ double Fc_s[GRAD_MAXF * GG_T];
   __shared__ double acc_s[4][GG_MAXSLOT + 1];
@@ -300,7 +314,7 @@ __global__ __launch_bounds__(256) void gg_kernel(GGArgs a, GGProg P) {
     }
     // ---- pass 1: primitive values ; pass 2: adjoints  fp[p][e] = c W d k / d prim_p (network weights on the way)
     double pv[GG_MAXP][GG_E], fp[GG_MAXP][GG_E];
-    gg_values(a, P, gi0, gj0, same_points, Fr_s, Fc_s, tid, ty, tx, pv);
+    gg_values<CRG>(a, P, gi0, gj0, same_points, Fr_s, Fc_s, tid, ty, tx, pv);
     gg_adjoints<true>(P, W_s, w, pv, fp, acc_s, lane, wave);
     // ---- pass 3: the primitives' own parameters
     for (int nd = 0; nd < P.n_nodes; ++nd) {
@@ -315,6 +329,29 @@ __global__ __launch_bounds__(256) void gg_kernel(GGArgs a, GGProg P) {
 #pragma unroll
           for (int e = 0; e < GG_E; ++e) { f4[e] = fp[p][e]; k4[e] = pv[p][e]; }
         }
+      if (CRG && node.op == GPS_K_COREGION) {
+        // rows [F_0 .. F_{R-1}, E_0 .. E_{P-1}], d k / d (dot product) = 1: kappa_p <- f E_p E'_p, W[p][r] <- f (E_p F'_r + F_r E'_p);
+        // the host divides by kappa_p and sqrt(kappa_p).  An output that no point carries has E_p = 0 everywhere: exact zeros.
+        gg_stage(a, node.f0, node.ndims, gi0, gj0, Fr_s, Fc_s, tid);
+        const int Pn = (int)node.ls0, Rn = (int)node.period;
+        for (int p = 0; p < Pn; ++p) {
+          const int ep = Rn + p;
+          const double er0 = Fr_s[ep * GG_T + ty * 2], er1 = Fr_s[ep * GG_T + ty * 2 + 1];
+          const double ec0 = Fc_s[ep * GG_T + tx * 2], ec1 = Fc_s[ep * GG_T + tx * 2 + 1];
+          double s = f4[0] * (er0 * ec0) + f4[1] * (er0 * ec1) + f4[2] * (er1 * ec0) + f4[3] * (er1 * ec1);
+          s = grad_wave_sum(s);
+          if (lane == 0) acc_s[wave][node.slot0 + Pn * Rn + p] += s;
+          for (int r = 0; r < Rn; ++r) {
+            const double r0 = Fr_s[r * GG_T + ty * 2], r1 = Fr_s[r * GG_T + ty * 2 + 1];
+            const double c0 = Fc_s[r * GG_T + tx * 2], c1 = Fc_s[r * GG_T + tx * 2 + 1];
+            double t = f4[0] * (er0 * c0 + r0 * ec0) + f4[1] * (er0 * c1 + r0 * ec1) + f4[2] * (er1 * c0 + r1 * ec0) +
+                       f4[3] * (er1 * c1 + r1 * ec1);
+            t = grad_wave_sum(t);
+            if (lane == 0) acc_s[wave][node.slot0 + p * Rn + r] += t;
+          }
+        }
+        continue;
+      }
       if (grad_is_dot(node.op)) {
         // Linear / Polynomial: Q_e = f dk/d(lin) ; d k / d v_d = Q F_d F'_d / v_d ; d k / d offset = Q
         gg_stage(a, node.f0, node.ndims, gi0, gj0, Fr_s, Fc_s, tid);
@@ -433,6 +470,8 @@ __global__ __launch_bounds__(256) void gg_kernel(GGArgs a, GGProg P) {
   for (int s = tid; s < GG_MAXSLOT + 1; s += 256)
     a.partial[(i64)blockIdx.x * (GG_MAXSLOT + 1) + s] = (acc_s[0][s] + acc_s[1][s]) + (acc_s[2][s] + acc_s[3][s]);
 }
+__global__ __launch_bounds__(256) void gg_kernel(GGArgs a, GGProg P) { gg_body<false>(a, P); }
+__global__ __launch_bounds__(256) void gg_coregion_kernel(GGArgs a, GGProg P) { gg_body<true>(a, P); }
 
 // ---- gradient with respect to the INPUT points of the first argument ------------------------------------------------
 //   G[i][d] = sum_j Wd[i][j] d k(xr_i, xc_j) / d xr_i[d]
@@ -443,11 +482,13 @@ __global__ __launch_bounds__(256) void gg_kernel(GGArgs a, GGProg P) {
 //   Periodic    S = sum_d sin^2((a_id - a_jd) / 2), a = 2 pi x / p :  d k / d x_id = -k / (2 l^2) (1/2) sin(a_id - a_jd) 2 pi / p
 //   Cosine      d k / d x_id = -variance sin(a_i - a_j) w_d / l_d
 //   ArcCosine   d k / d x_id = (d k / d P) H_jd sqrt(w_d) + (d k / d n_i) 2 H_id sqrt(w_d),  H = x sqrt(w)
+//   Coregion    nothing: the label column is an index (its value still enters the product rule of the other columns)
 // Workgroup (ti, slice) owns 32 rows and a slice of the column tiles; row sums over the 16 threads of a patch row by
 // shuffles, over the tiles in LDS; the slices' partial sums [slices][rows][d_all] are added in order on the host.
 struct GIArgs { const GradFeat* feats; double* part; int d_all; int slices; i64 rows_pad; };
 
-__global__ __launch_bounds__(256) void gg_input_kernel(GGArgs a, GGProg P, GIArgs gi) {
+template <bool CRG>
+__device__ __forceinline__ void gg_input_body(GGArgs a, GGProg P, GIArgs gi) {
   __shared__ double Fr_s[GRAD_MAXF * GG_T];
   __shared__ double Fc_s[GRAD_MAXF * GG_T];
   __shared__ double W_s[GG_MAXL * GG_W * (GG_W + 1)];
@@ -471,11 +512,12 @@ __global__ __launch_bounds__(256) void gg_input_kernel(GGArgs a, GGProg P, GIArg
       w[e] = (i < a.nr && j < a.nc) ? a.Wd[i * a.ldw + j] : 0.0;
     }
     double pv[GG_MAXP][GG_E], fp[GG_MAXP][GG_E];
-    gg_values(a, P, gi0, gj0, same_points, Fr_s, Fc_s, tid, ty, tx, pv);
+    gg_values<CRG>(a, P, gi0, gj0, same_points, Fr_s, Fc_s, tid, ty, tx, pv);
     gg_adjoints<false>(P, W_s, w, pv, fp, nullptr, lane, wave);
     for (int nd = 0; nd < P.n_nodes; ++nd) {
       const GradNode node = P.nodes[nd];
       if (node.prim < 0 || node.op == GPS_K_WHITE || node.op == GPS_K_CONSTANT) continue;
+      if (CRG && node.op == GPS_K_COREGION) continue;
       double f4[GG_E], k4[GG_E];
 #pragma unroll
       for (int e = 0; e < GG_E; ++e) { f4[e] = 0.0; k4[e] = 0.0; }
@@ -583,6 +625,8 @@ __global__ __launch_bounds__(256) void gg_input_kernel(GGArgs a, GGProg P, GIArg
     gi.part[((i64)slice * gi.rows_pad + gi0 + r) * gi.d_all + d] = rowacc[r][d];
   }
 }
+__global__ __launch_bounds__(256) void gg_input_kernel(GGArgs a, GGProg P, GIArgs gi) { gg_input_body<false>(a, P, gi); }
+__global__ __launch_bounds__(256) void gg_input_coregion_kernel(GGArgs a, GGProg P, GIArgs gi) { gg_input_body<true>(a, P, gi); }
 
 // ---- host side ------------------------------------------------------------------------------------
 #define GG_BLOCKS 2048
@@ -600,6 +644,11 @@ int gps_grad_slots(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, int
     else if (op == GPS_K_POLYNOMIAL) s += prog[i].n_dims + 1;
     else if (op == GPS_K_COSINE) s += 1 + 2 * prog[i].n_dims;
     else if (op == GPS_K_ARCCOSINE) s += 2 + prog[i].n_dims;
+    else if (op == GPS_K_COREGION) {
+      if (!(prog[i].period >= 1.0) || prog[i].period > (double)GPS_MAX_DIMS || prog[i].active_dims[1] < 0 || prog[i].active_dims[1] > GPS_MAX_DIMS)
+        return gps_fail(h, GPS_ERR_ARG, "gradient: Coregion output_dim / rank out of range");
+      s += (int)prog[i].period * (prog[i].active_dims[1] + 1);
+    }
     else if (op == GPS_K_NKN_LINROW) s += prog[i].n_dims + 1;
     else if (grad_is_prim(op)) s += 1 + prog[i].n_dims;
     else return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: unknown op");
@@ -613,6 +662,7 @@ struct GGBuilt {
   GGProg P;
   GradPrims prims;           // feature table, lengthscale of every slot (the network's slots: 0)
   std::vector<double> W;
+  bool coregion = false;     // a Coregion node: the CRG instances of the kernels
 };
 
 static int gg_build(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, GGBuilt& B) {
@@ -627,6 +677,8 @@ static int gg_build(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i6
                               P.nkn != 0, P.nodes, B.prims);
   if (rc) return rc;
   P.n_nodes = n_prim_nodes; P.n_prims = B.prims.n_prims;
+  for (int i = 0; i < n_prim_nodes; ++i) if (P.nodes[i].op == GPS_K_COREGION) B.coregion = true;
+  if (B.coregion && P.nkn) return gps_fail(h, GPS_ERR_UNSUPPORTED, "gradient: Coregion is not a network primitive");
   int& n_slots = B.prims.n_slots;
   // ---- network layers (kernel-program encoding of gpflowSlim/neural_kernel_network: see kmat.hip compile_prog)
   if (P.nkn) {
@@ -679,7 +731,7 @@ static int gg_features(gps_handle_t h, const GGBuilt& B, const double* dX, i64 n
   const size_t nfeat = B.prims.feats.size();
   GPS_HIP(h, feat.ensure((nfeat > 0 ? nfeat : 1) * npad * 8));
   if (nfeat == 0) return GPS_OK;
-  return grad_launch_prep(h, B.prims.feats, dX, n, d_all, npad, feat.d(), false);
+  return grad_launch_prep(h, B.prims.feats, dX, n, d_all, npad, feat.d(), false, &B.prims.lut);
 }
 
 static int gg_upload_net(gps_handle_t h, const GGBuilt& B, GGArgs& a) {
@@ -703,7 +755,7 @@ static int gg_run(gps_handle_t h, const GGBuilt& B, GGArgs& a, double flops, dou
   a.partial = h->dTmp2.d();
   {
     LaunchScope ls(h, KC_REDUCE, flops, bytes);
-    hipLaunchKernelGGL(gg_kernel, dim3(GG_BLOCKS), dim3(256), 0, h->stream, a, P);
+    hipLaunchKernelGGL(B.coregion ? gg_coregion_kernel : gg_kernel, dim3(GG_BLOCKS), dim3(256), 0, h->stream, a, P);
     GPS_HIP(h, hipGetLastError());
   }
   std::vector<double> part((size_t)GG_BLOCKS * (GG_MAXSLOT + 1));
@@ -816,7 +868,9 @@ int gps_kdiag_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 
 // The same for a program with Linear, whose Kdiag_i = sum_d v_d x_id^2 depends on the point (kernels.py:507-510): X host
 // [n, d_all], kbar host [n], added to the slots.  O(n) work on the host from what the caller holds there anyway; forward mode
 // over the fold per point and primitive.  ArcCosine likewise: Kdiag_i = variance jfac n_i^order, n_i = sum_d w_d x_id^2 + b,
-// jfac = 1, 1, 3 (kernels.py:760-766).  Polynomial and network programs are not taken.
+// jfac = 1, 1, 3 (kernels.py:760-766).  Coregion: Kdiag_i = sum_r W[a_i, r]^2 + kappa[a_i] (kernels.py:877-881), 0 for a label
+// outside [0, P).  Polynomial and network programs are not taken.
+static inline int gg_host_label(double x, int P) { return (x > -1.0 && x < (double)P) ? (int)x : -1; }     // gps_label on the host
 int gps_kdiag_vjp_points(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, const double* X, i64 n, const double* kbar,
                          double* grad_slots_host) {
   GGBuilt B;
@@ -844,6 +898,15 @@ int gps_kdiag_vjp_points(gps_handle_t h, const gps_kern_node_t* prog, int n_node
         const int order = (int)g.period;
         val[nd] = order == 0 ? g.variance : (order == 1 ? g.variance * s : g.variance * 3.0 * (s * s));
       }
+      if (g.op == GPS_K_COREGION) {
+        const int Pn = (int)g.ls0, Rn = (int)g.period, a = gg_host_label(x[prog[nd].active_dims[0]], Pn);
+        double s = 0.0;
+        if (a >= 0) {
+          for (int r = 0; r < Rn; ++r) s += prog[nd].lengthscales[a * Rn + r] * prog[nd].lengthscales[a * Rn + r];
+          s += prog[nd].lengthscales[Pn * Rn + a];
+        }
+        val[nd] = s;
+      }
     }
     for (int p = 0; p < B.P.n_prims; ++p) {
       double sv[GPS_MAX_STACK + 1], st[GPS_MAX_STACK + 1]; int sp = 0;
@@ -864,6 +927,14 @@ int gps_kdiag_vjp_points(gps_handle_t h, const gps_kern_node_t* prog, int n_node
       const double c = kbar[i] * st[0];
       if (mine->op == GPS_K_LINEAR) {
         for (int f = 0; f < mine->nf; ++f) { const double xd = x[B.prims.feats[(size_t)(mine->f0 + f)].dim]; acc[(size_t)(mine->slot0 + f)] += c * xd * xd; }
+      } else if (mine->op == GPS_K_COREGION) {
+        // d Kdiag_i / d W[a][r] = 2 W[a][r], d Kdiag_i / d kappa_a = 1, for the point's own label a alone
+        const gps_kern_node_t& cn = prog[mine - B.P.nodes];
+        const int Pn = (int)mine->ls0, Rn = (int)mine->period, a = gg_host_label(x[cn.active_dims[0]], Pn);
+        if (a >= 0) {
+          for (int r = 0; r < Rn; ++r) acc[(size_t)(mine->slot0 + a * Rn + r)] += c * 2.0 * cn.lengthscales[a * Rn + r];
+          acc[(size_t)(mine->slot0 + Pn * Rn + a)] += c;
+        }
       } else if (mine->op == GPS_K_ARCCOSINE) {
         // slots in true units: [variance, b, w_0 ..]
         double s = mine->ls0;
@@ -904,7 +975,8 @@ int gps_launch_kmat_input_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n
   {
     const double rows = (double)nrp, cols = (double)a.tiles_c * GG_T;
     LaunchScope ls(h, KC_REDUCE, gg_work(B, rows, cols, 6.0), 8.0 * rows * cols);
-    hipLaunchKernelGGL(gg_input_kernel, dim3((unsigned)a.tiles, (unsigned)slices), dim3(256), 0, h->stream, a, B.P, gi);
+    hipLaunchKernelGGL(B.coregion ? gg_input_coregion_kernel : gg_input_kernel, dim3((unsigned)a.tiles, (unsigned)slices), dim3(256), 0,
+                       h->stream, a, B.P, gi);
     GPS_HIP(h, hipGetLastError());
   }
   std::vector<double> part((size_t)slices * nrp * d_all);

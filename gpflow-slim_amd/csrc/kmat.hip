@@ -11,6 +11,8 @@
 //   Cosine.K                 kernels.py:633-646   (features cos a, sin a with a = sum_d x_d w_d / l_d over the SLICED columns:
 //                                                  variance * dot product; the reference divides before it slices)
 //   ArcCosine.K              kernels.py:722-758   (features x_d sqrt(w_d) and their norm row; + b in the formula)
+//   Coregion.K               kernels.py:822-881   (B[x, y], B = W W^T + diag(kappa), as a dot product of looked-up feature rows
+//                                                  W[a, r] and sqrt(kappa_p) [a == p], a = (int)x: Linear's value path)
 //   Periodic.K               kernels.py:806-819   (via u = (cos, sin) features: the docstring's
 //                                                  own mapping, kernels.py:776 -- avoids the
 //                                                  reference's [N,M,D] temporary and D*N*M sin())
@@ -34,6 +36,9 @@
 struct PrepFeat { int dim; int kind; double param; };   // kind 0: x/param ; 1: cos(2 pi x/param) ; 2: sin(...) ; 3: x*param
 // kind 4 / 5: cos / sin of a linear combination of columns, a = sum_q x[tab[dim + q].dim] * tab[dim + q].param over the
 // (int)param table entries from index `dim` on (Cosine: kind-3 entries x_d (w_d / l_d), which follow the pair in the table)
+// kind 6 / 7: looked up by the integer label a = (int)x[dim] (Coregion; gps_label, gps_common.hpp), from a table of doubles that
+// travels beside the feature table (PrepTabLut): 6: lut[off + a * stride] for a in [0, P), else 0 ; 7: lut[off] where a == p, else 0,
+// with (off, P or p, stride) packed into param (gps_lookup_code)
 struct PrepNorm { int f0; int nf; };
 
 struct KNodeDev {
@@ -64,6 +69,11 @@ struct KmatArgs {
 #define PREP_SMALL_N 8
 struct PrepTabPtr { const PrepFeat* f; const PrepNorm* n; };
 struct PrepTabVal { PrepFeat f[PREP_SMALL_F]; PrepNorm n[PREP_SMALL_N]; };
+// ... and for programs with looked-up features (Coregion): the table of W and sqrt(kappa) values behind the other two.  Only this
+// instance knows the lookup kinds; the other two keep the code they had.
+struct PrepTabLut { const PrepFeat* f; const PrepNorm* n; const double* lut; };
+template <class Tab> struct prep_has_lut { static constexpr bool value = false; };
+template <> struct prep_has_lut<PrepTabLut> { static constexpr bool value = true; };
 
 // (one kernel over both table forms, as grad_prep_kernel<Tab> of grad_common.hpp)
 template <class Tab>
@@ -79,6 +89,12 @@ __global__ __launch_bounds__(256) void kmat_prep_kernel(const double* __restrict
   for (int f = 0; f < nfeat; ++f) {
     const PrepFeat pf = tab.f[f];
     double v;
+    if constexpr (prep_has_lut<Tab>::value) {
+      if (pf.kind >= 6) {
+        Ft[(i64)f * ldf + i] = gps_lookup_feature(pf.kind == 6, x[pf.dim], (int)pf.param, tab.lut);
+        continue;
+      }
+    }
     if (pf.kind >= 4) {
       double ang = 0.0;
       for (int q = 0; q < (int)pf.param; ++q) { const PrepFeat cf = tab.f[pf.dim + q]; ang = fma(x[cf.dim], cf.param, ang); }
@@ -814,6 +830,7 @@ struct KCompiled {
   KProgDev prog;
   std::vector<PrepFeat> feats;
   std::vector<PrepNorm> norms;
+  std::vector<double> lut;     // Coregion: per node W row-major, then sqrt(kappa)
   bool has_nkn = false;
   NknNet net;
   std::vector<double> W;       // [n_layers][16][17]
@@ -830,6 +847,9 @@ static int compile_prog(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes
   int n_prim_nodes = n_nodes;
   if (out.has_nkn) {
     n_prim_nodes = 0;
+    for (int i = 0; i < n_nodes; ++i)        // (its op number lies above ADD / MUL, where the primitives of a network program end)
+      if (prog[i].op == GPS_K_COREGION)
+        return gps_fail(h, GPS_ERR_UNSUPPORTED, "NKN program: Coregion is not a network primitive");
     while (n_prim_nodes < n_nodes && prog[n_prim_nodes].op < GPS_K_ADD) ++n_prim_nodes;
     if (n_prim_nodes == 0 || n_prim_nodes > NKN_MAXP)
       return gps_fail(h, GPS_ERR_UNSUPPORTED, "NKN program: 1..8 primitive kernels first");
@@ -927,6 +947,22 @@ static int compile_prog(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes
           kd.norm_row = (int)out.norms.size();     // fixed up below (offset by total features)
           out.norms.push_back({kd.f0, kd.nf});
         }
+        depth += 1;
+        break;
+      }
+      case GPS_K_COREGION: {
+        // R + P feature rows looked up by the label in column active_dims[0]: F_r = W[a, r], E_p = sqrt(kappa_p) [a == p]; their dot
+        // product is B[a_i, a_j], so from here on the node IS a Linear one (every tile kernel, and the per-point Kdiag: the squared
+        // norm of the rows is sum_r W[a, r]^2 + kappa_a).  A label outside [0, P) gives zero rows.
+        int P = 0, R = 0;
+        int rcc = gps_coregion_check(h, nd, d_all, "kernel program", &P, &R);
+        if (rcc) return rcc;
+        const int l0 = (int)out.lut.size();
+        kd.op = GPS_K_LINEAR; kd.f0 = (int)out.feats.size(); kd.nf = R + P;
+        for (int q = 0; q < P * R; ++q) out.lut.push_back(nd.lengthscales[q]);
+        for (int p = 0; p < P; ++p) out.lut.push_back(sqrt(nd.lengthscales[P * R + p]));
+        for (int r = 0; r < R; ++r) out.feats.push_back({nd.active_dims[0], 6, gps_lookup_code(l0 + r, P, R)});
+        for (int p = 0; p < P; ++p) out.feats.push_back({nd.active_dims[0], 7, gps_lookup_code(l0 + P * R + p, p, 0)});
         depth += 1;
         break;
       }
@@ -1077,11 +1113,12 @@ static int launch_tiles(gps_handle_t h, const KCompiled& kc, KmatArgs& a, i64 pr
                         kc.prog, maxnf, KLS, 2.0 * nfeat_total + 30.0, tiles);
 }
 
-// Kdiag is one number for every point unless the program holds Linear, Polynomial or ArcCosine (kernels.py:507-510, 553-554,
-// 760-766)
+// Kdiag is one number for every point unless the program holds Linear, Polynomial, ArcCosine or Coregion (kernels.py:507-510,
+// 553-554, 760-766, 877-881)
 bool gps_kdiag_is_const(const gps_kern_node_t* prog, int n_nodes) {
   for (int i = 0; i < n_nodes; ++i)
-    if (prog[i].op == GPS_K_LINEAR || prog[i].op == GPS_K_POLYNOMIAL || prog[i].op == GPS_K_ARCCOSINE) return false;
+    if (prog[i].op == GPS_K_LINEAR || prog[i].op == GPS_K_POLYNOMIAL || prog[i].op == GPS_K_ARCCOSINE || prog[i].op == GPS_K_COREGION)
+      return false;
   return true;
 }
 
@@ -1137,6 +1174,20 @@ static int run_prep(gps_handle_t h, const KCompiled& kc, const double* dX, i64 n
   *ldf_out = npad;
   if (rows == 0) return GPS_OK;
   GPS_HIP(h, feat.ensure((size_t)rows * npad * sizeof(double)));
+  if (!kc.lut.empty()) {
+    // looked-up features: the three tables go up behind one another (pinned slots, as below)
+    const size_t fb = (size_t)nfeat * sizeof(PrepFeat), nb = (size_t)nnorm * sizeof(PrepNorm), lb = kc.lut.size() * sizeof(double);
+    GPS_HIP(h, tables.ensure(fb + nb + lb + 64));
+    GPS_HIP(h, h->ring.upload(tables.p, kc.feats.data(), fb, h->stream));
+    if (nb) GPS_HIP(h, h->ring.upload((char*)tables.p + fb, kc.norms.data(), nb, h->stream));
+    GPS_HIP(h, h->ring.upload((char*)tables.p + fb + nb, kc.lut.data(), lb, h->stream));
+    LaunchScope ls(h, KC_KMAT, 0.0, 8.0 * (double)npad * (double)(rows + d_all));
+    const PrepTabLut tab{(const PrepFeat*)tables.p, (const PrepNorm*)((char*)tables.p + fb), (const double*)((char*)tables.p + fb + nb)};
+    hipLaunchKernelGGL(kmat_prep_kernel<PrepTabLut>, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, h->stream, dX, n, d_all, npad, tab,
+                       nfeat, nnorm, feat.d(), npad);
+    GPS_HIP(h, hipGetLastError());
+    return GPS_OK;
+  }
   if (nfeat <= PREP_SMALL_F && nnorm <= PREP_SMALL_N) {
     PrepTabVal tab;
     memset(&tab, 0, sizeof(tab));

@@ -18,6 +18,7 @@ K_SQDIST, K_EUCLID = 9, 10
 K_RATQUAD, K_LINEAR, K_POLYNOMIAL = 11, 12, 13      # (below K_ADD: network programs find their primitives with op < K_ADD)
 K_COSINE, K_ARCCOSINE = 14, 15
 K_ADD, K_MUL = 16, 17
+K_COREGION = 18                                     # (above K_ADD: not a network primitive)
 K_NKN_LINROW, K_NKN_PRODUCT, K_NKN_ACT = 32, 33, 34
 
 _c_double_p = ctypes.POINTER(ctypes.c_double)
@@ -145,6 +146,21 @@ def primitive_node(op, variance, dims=(), lengthscales=(), period=0.0, alpha=Non
     elif ls.size:
         m = min(ls.size, GPS_MAX_DIMS)
         nd.lengthscales[:m] = ls[:m].tolist()
+    return nd
+
+
+def coregion_node(column, W, kappa):
+    """The Coregion primitive (include/gpflowslim_hip.h): the index column in active_dims[0], the rank in active_dims[1], output_dim
+    where Periodic keeps the period, W row-major and then kappa where the others keep their lengthscales."""
+    W = np.asarray(W, dtype=np.float64)
+    kappa = np.asarray(kappa, dtype=np.float64).ravel()
+    P, R = W.shape
+    if kappa.size != P:
+        raise ValueError("Coregion: kappa must have output_dim entries")
+    if P * (R + 1) > GPS_MAX_DIMS:
+        raise ValueError("Coregion supports at most output_dim * (rank + 1) = %d values, got %d" % (GPS_MAX_DIMS, P * (R + 1)))
+    nd = primitive_node(K_COREGION, 1.0, [column], np.concatenate([W.ravel(), kappa]), period=float(P))
+    nd.active_dims[1] = int(R)
     return nd
 
 

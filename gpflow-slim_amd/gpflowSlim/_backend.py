@@ -13,10 +13,10 @@ import numpy as np
 
 from ._abi import (GPS_MAX_DIMS, GPS_MAX_NODES, GPS_MAX_STACK,                                        # noqa: F401
                    K_RBF, K_MATERN12, K_MATERN32, K_MATERN52, K_PERIODIC, K_WHITE, K_CONSTANT, K_EXPONENTIAL,
-                   K_SQDIST, K_EUCLID, K_RATQUAD, K_LINEAR, K_POLYNOMIAL, K_COSINE, K_ARCCOSINE, K_ADD, K_MUL,
+                   K_SQDIST, K_EUCLID, K_RATQUAD, K_LINEAR, K_POLYNOMIAL, K_COSINE, K_ARCCOSINE, K_ADD, K_MUL, K_COREGION,
                    K_NKN_LINROW, K_NKN_PRODUCT, K_NKN_ACT, KernNode, LikDesc, RffDesc,
                    RFF_RBF, RFF_LINEAR, RFF_CONSTANT, RFF_EXPLICIT, LIK_MAX_GH, LIK_MAX_EDGES, LIK_MULTICLASS, LIK_ORDINAL,
-                   make_rff, make_lik, make_program, primitive_node, op_node, psi2_chunking, psi_sum_chunking,
+                   make_rff, make_lik, make_program, primitive_node, coregion_node, op_node, psi2_chunking, psi_sum_chunking,
                    _SIGNATURES, EXPORTED_SYMBOLS, ALLREDUCE_FN, _c_double_p, _c_int_p, _i64,
                    lib_path, load_library, comm_load, comm_unique_id, comm_version)
 

@@ -16,6 +16,7 @@ def conditional(Xnew, X, kern, f, *, full_cov=False, q_sqrt=None, white=False):
     """conditionals.py:24-66"""
     Xnew = np.asarray(Xnew, dtype=settings.float_type)
     X = np.asarray(X, dtype=settings.float_type)
+    kern._check_inputs(X, Xnew)
     prog = kern._program(X.shape[1])
     return be.get_handle().conditional(prog, X, Xnew, f, settings.numerics.jitter_level,
                                        q_sqrt=q_sqrt, white=white, full_cov=full_cov)

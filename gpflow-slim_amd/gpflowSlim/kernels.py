@@ -3,7 +3,8 @@
 API mirror of gpflowSlim/kernels.py for the kernels on the hot path: Kernel (active-dims
 slicing :217-253, ``+`` / ``*`` :277-281), Static/White/Constant/Bias :308-357, Stationary
 :360-429, RBF :432-439, RatQuad :447-471, Linear :474-515, Polynomial :518-554, Exponential :557-565,
-Matern12/32/52 :569-610, Cosine :617-646, ArcCosine :649-766, Periodic :769-819, Combination/Sum/Product :1000-1084.
+Matern12/32/52 :569-610, Cosine :617-646, ArcCosine :649-766, Periodic :769-819, Coregion :822-881,
+Combination/Sum/Product :1000-1084.
 
 Differences from the reference, on purpose: values are eager numpy fp64 arrays (there is no
 TensorFlow graph); ``K`` compiles the kernel *tree* into one reverse-Polish program and
@@ -65,10 +66,16 @@ class Kernel(object):
         into the parameter's flattened value or None = add to every element)."""
         raise NotImplementedError
 
+    def _check_inputs(self, *Xs):
+        """Raise ValueError for inputs this kernel cannot take, before anything reaches the device (None entries are
+        skipped).  Only kernels that read a column as something other than a real number have anything to check."""
+
     # ---- reference API -------------------------------------------------------------------
     def K(self, X, X2=None, presliced=False):
         X = np.asarray(X, dtype=settings.float_type)
         prog = self._program(X.shape[1], presliced)
+        if not presliced:
+            self._check_inputs(X, X2)
         return be.get_handle().kmat(prog, X, None if X2 is None else np.asarray(X2, dtype=settings.float_type))
 
     def Kdiag(self, X, presliced=False):
@@ -465,6 +472,76 @@ class ArcCosine(Kernel):
         return [(self._variance, None), (self._bias_variance, None)] + [(self._weight_variances, d if ard else None) for d in range(nd)]
 
 
+class Coregion(Kernel):
+    """kernels.py:822-881: K(x, y) = B[x, y] with B = W W^T + diag(kappa), indexed by the integer in one column of X (cast from
+    float by truncation toward zero, as tf.cast does).  ``RBF(active_dims=inputs) * Coregion(1, P, R, active_dims=[label])`` is
+    the intrinsic coregionalisation model: P correlated outputs, observed at inputs of their own, stacked into one exact GP.
+
+    W starts at zero as in the reference, where there is a symmetry between its elements and so a stationary point: start an
+    optimisation from a random W.  Kdiag depends on the point, so the device paths that assume a constant Kdiag refuse this
+    kernel exactly where they refuse Linear.  The device op keeps W and kappa in one 32-entry field:
+    output_dim * (rank + 1) <= 32.  Unlike the reference, whose tf.gather fails on the CPU for such input, a label that is
+    not finite or whose truncated value lies outside [0, output_dim) raises ValueError before anything reaches the device."""
+
+    def __init__(self, input_dim, output_dim, rank, active_dims=None, name='kernel'):
+        assert input_dim == 1, "Coregion kernel in 1D only"
+        super().__init__(input_dim, active_dims, name=name)
+        self.output_dim, self.rank = int(output_dim), int(rank)
+        if self.output_dim < 1 or self.rank < 0:
+            raise ValueError("Coregion needs output_dim >= 1 and rank >= 0")
+        self._W = Parameter(np.zeros((self.output_dim, self.rank), dtype=settings.float_type), name='W')
+        self._kappa = Parameter(np.ones(self.output_dim, dtype=settings.float_type), transform=transforms.positive, name='kappa')
+        self._parameters = self._parameters + [self._W, self._kappa]
+
+    @property
+    def W(self):
+        return self._W.value
+
+    @property
+    def kappa(self):
+        return self._kappa.value
+
+    def _column(self, presliced, d_all):
+        dims = self._dims(presliced, d_all)
+        if len(dims) != 1:
+            raise ValueError("Input 1st dimension does not match kernel dimension.")
+        return dims[0]
+
+    def _labels(self, X, presliced=False):
+        """The integer labels of X's index column; ValueError for one that is not finite or outside [0, output_dim)."""
+        X = np.asarray(X, dtype=settings.float_type)
+        x = X[:, self._column(presliced, X.shape[1])]
+        if not np.all(np.isfinite(x)):
+            raise ValueError("Coregion: the index column holds a value that is not finite")
+        a = np.trunc(x)
+        if np.any(a < 0) or np.any(a >= self.output_dim):
+            raise ValueError("Coregion: the index column holds a label outside [0, %d)" % self.output_dim)
+        return a.astype(np.int64)
+
+    def _check_inputs(self, *Xs):
+        for X in Xs:
+            if X is not None:
+                self._labels(X)
+
+    def _nodes(self, presliced, d_all):
+        return [be.coregion_node(self._column(presliced, d_all), np.reshape(self.W, (self.output_dim, self.rank)), self.kappa)]
+
+    def K(self, X, X2=None, presliced=False):
+        if presliced:
+            self._labels(X, True)
+            if X2 is not None:
+                self._labels(X2, True)
+        return super().K(X, X2, presliced)
+
+    def Kdiag(self, X, presliced=False):
+        """kernels.py:877-881"""
+        a = self._labels(X, presliced)
+        return (np.sum(np.square(np.reshape(self.W, (self.output_dim, self.rank))), 1) + self.kappa)[a]
+
+    def _grad_layout(self, d_all):
+        return [(self._W, q) for q in range(self.output_dim * self.rank)] + [(self._kappa, p) for p in range(self.output_dim)]
+
+
 class Periodic(Kernel):
     """kernels.py:769-819 (no ARD for lengthscale or period, as in the reference)"""
 
@@ -571,6 +648,10 @@ class Combination(Kernel):
             out.extend(k._grad_layout(d_all))
         out.extend([(None, None)] * len(self.const_list))     # scalar constants: slot exists, no parameter
         return out
+
+    def _check_inputs(self, *Xs):
+        for k in self.kern_list:
+            k._check_inputs(*Xs)
 
     def Kdiag(self, X, presliced=False):
         return self._fold([k.Kdiag(X) for k in self.kern_list] + self.const_list)

@@ -66,6 +66,7 @@ class GPMC(GPModel):
     def _build_likelihood(self):
         """models/gpmc.py:64-77: log p(Y | F = L V + m(X))"""
         dl = device_likelihood(self.likelihood)
+        self.kern._check_inputs(self.X)
         prog = self.kern._program(self.X.shape[1])
         h = be.get_handle()
         if dl is not None:
@@ -83,6 +84,7 @@ class GPMC(GPModel):
             raise NotImplementedError("analytic gradients of GPMC need one of the built-in likelihoods (Gaussian, Bernoulli, "
                                       "Poisson, Exponential, StudentT, Gamma, Beta, Ordinal) with its default link")
         X = self.X
+        self.kern._check_inputs(X)
         d_all = X.shape[1]
         layout = self.kern._grad_layout(d_all)
         ll, slots, glik, g_V, g_mean = be.get_handle().gpmc_lik_grad(

@@ -123,6 +123,7 @@ class GPR(GPModel):
         """models/gpr.py:63-72 + densities.py:73-124, fused on the device."""
         if self._has_features():
             return self._rff_likelihood()
+        self.kern._check_inputs(self.X)
         h = self._handle()
         prog = self.kern._program(self.X.shape[1])
         with h.factor_claim(self._state_key()):
@@ -136,6 +137,7 @@ class GPR(GPModel):
         Parameter.unconstrained_tensor), ...]) in `self.parameters` order.  Priors are not included."""
         if self._has_features():
             return self._rff_likelihood_and_gradients()
+        self.kern._check_inputs(self.X)
         h = self._handle()
         d_all = self.X.shape[1]
         prog = self.kern._program(d_all)
@@ -186,6 +188,7 @@ class GPR(GPModel):
         if self._has_features():
             mean, var = self._rff_predict(Xnew, full_cov)
         else:
+            self.kern._check_inputs(self.X, Xnew)
             h = self._handle()
             prog = self.kern._program(self.X.shape[1])
             key = self._state_key()

@@ -62,6 +62,7 @@ class SGPMC(GPModel):
     def _build_likelihood(self):
         """models/sgpmc.py:83-89: the sum of the variational expectations at the marginals of p(f | u = Lm V)"""
         dl = device_likelihood(self.likelihood)
+        self.kern._check_inputs(self.feature.Z, self.X)
         if dl is not None:
             return be.get_handle().sgpmc_lik(self.kern._program(self.X.shape[1]), self.feature.Z, self.X, self.Y, self.V,
                                              settings.numerics.jitter_level, dl[0], mean=self._mean_on(self.X),
@@ -78,6 +79,7 @@ class SGPMC(GPModel):
             raise NotImplementedError("analytic gradients of SGPMC need one of the built-in likelihoods (Gaussian, Bernoulli, "
                                       "Poisson, Exponential, StudentT, MultiClass, Gamma, Beta, Ordinal) with its default link")
         X = self.X
+        self.kern._check_inputs(self.feature.Z, X)
         d_all = X.shape[1]
         layout = self.kern._grad_layout(d_all)
         zparam = getattr(self.feature, "_Z", None)

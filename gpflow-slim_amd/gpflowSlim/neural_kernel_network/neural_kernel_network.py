@@ -5,7 +5,7 @@ pass (all primitives and the whole network per matrix entry, no [N*M, k] stack i
 """
 import numpy as np
 
-from ..kernels import Kernel, Combination
+from ..kernels import Kernel, Combination, Coregion
 
 
 class NeuralKernelNetwork(Kernel):
@@ -17,6 +17,9 @@ class NeuralKernelNetwork(Kernel):
         for kern in self._primitive_kernels:
             if isinstance(kern, Combination):
                 raise NotImplementedError("NKN primitives must be primitive kernels (no Sum / Product) on the device path")
+            if isinstance(kern, Coregion):
+                raise NotImplementedError("Coregion is not a network primitive on the device path (its op lies above Sum / "
+                                          "Product, where the primitives of a network program end)")
             self._parameters = self._parameters + kern.parameters
 
     def Kdiag(self, X, presliced=False):

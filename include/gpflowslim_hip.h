@@ -81,6 +81,16 @@ enum gps_kern_op {
   GPS_K_ARCCOSINE = 15, /* ArcCosine.K kernels.py:740-758: variance / pi * J_order(theta) (n n')^(order / 2)               */
   GPS_K_ADD      = 16, /* Sum.K     reduce(tf.add, ...)      :1073          */
   GPS_K_MUL      = 17, /* Product.K reduce(tf.multiply, ...) :1081          */
+  /* A primitive numbered above ADD / MUL (network programs find their primitives with op < GPS_K_ADD: Coregion is not a
+   * Neural-Kernel-Network primitive, GPS_ERR_UNSUPPORTED there).  Layout unchanged, fields re-used:
+   *   op          n_dims   active_dims[]                  variance      period            lengthscales[]
+   *   COREGION    1        [0]: the index column          must be 1.0   output_dim P      W row-major [P, R] (any sign), then
+   *                        [1]: rank R (>= 0)                           (>= 1)            kappa [P] (> 0)   -> P (R + 1) <= 32
+   * More values than that are GPS_ERR_UNSUPPORTED.  a = (int) X[i, column], truncated toward zero; a point whose label is not
+   * finite or lies outside [0, P) has covariance exactly 0 with every point (itself included), and nothing outside the table is
+   * read.  Kdiag depends on the point (sum_r W[a, r]^2 + kappa_a): taken and refused where LINEAR is.
+   * Gradient slots: COREGION [W row-major, kappa_0 ..] (no variance slot); the index column's input gradient is exactly 0.     */
+  GPS_K_COREGION = 18, /* Coregion.K   kernels.py:867-875: B[a_i, a_j], B = W W^T + diag(kappa)                              */
   /* Neural Kernel Network (neural_kernel_network/neural_kernel_network.py:41-47): a program that
    * contains these ops is "layered": up to 8 primitive nodes first (their values form the input
    * vector), then the layers in order.  active_dims[0] = layer index.                           */
@@ -94,10 +104,11 @@ typedef struct gps_kern_node {
   int32_t op;                           /* enum gps_kern_op                  */
   int32_t n_dims;                       /* active dims of a primitive        */
   int32_t active_dims[GPS_MAX_DIMS];    /* column indices into X (Kernel._slice, kernels.py:217-253) */
-  double  variance;                     /* constrained value (Polynomial: the offset; Linear: 1.0)           */
-  double  period;                       /* Periodic: period; RatQuad: alpha; Polynomial: degree; ArcCosine: order */
+  double  variance;                     /* constrained value (Polynomial: the offset; Linear, Coregion: 1.0)  */
+  double  period;                       /* Periodic: period; RatQuad: alpha; Polynomial: degree; ArcCosine: order; Coregion: output_dim */
   double  lengthscales[GPS_MAX_DIMS];   /* per active dim (ARD) or repeated; Linear / Polynomial: variances;
-                                           Cosine: lengthscales then weights; ArcCosine: weight variances then the bias variance */
+                                           Cosine: lengthscales then weights; ArcCosine: weight variances then the bias variance;
+                                           Coregion: W row-major then kappa */
 } gps_kern_node_t;
 
 typedef struct gps_handle_s* gps_handle_t;
@@ -158,7 +169,7 @@ int gps_gpr_lml(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes,
  * stationary kernels one entry per active dim (d/d lengthscale_d; an isotropic kernel sums them),
  * Periodic [d/d lengthscale, d/d period], White / Constant nothing more; RatQuad [d/d variance, d/d lengthscale_d per
  * active dim, d/d alpha]; Linear [d/d v_d per active dim] (no variance slot; an isotropic kernel sums them);
- * Polynomial [d/d v_d per active dim, d/d offset] -- all w.r.t. the CONSTRAINED
+ * Polynomial [d/d v_d per active dim, d/d offset]; Coregion [d/d W[p][r] row-major, d/d kappa_p] -- all w.r.t. the CONSTRAINED
  * values; the caller applies the transform's chain rule.  grad_noise = d/d noise_var.
  * kinv_resid (optional) host [n, r] = A = d LML / d resid (chain rule for mean-function parameters).
  * Neural-Kernel-Network programs (GPS_K_NKN_*: neural_kernel_network_wrapper.py:90-173, whose Linear weights and biases the
