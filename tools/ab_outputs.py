@@ -23,8 +23,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLASSES = ("gemm_f64", "potrf_base", "kmat", "trsv", "reduce", "other")
-LIK_KINDS = {"gaussian": 0, "bernoulli": 1, "poisson": 2, "exponential": 3, "student_t": 4, "multiclass": 5, "gamma": 6, "beta": 7,
-             "ordinal": 8}
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+# (the likelihood table and the input helpers are shared with the call-order tests)
+from _entry_catalogue import LIK_KINDS, _psi_kernels, lik_table as _lik, psi_inputs as _psi_inputs, tril_stack as _tril_stack  # noqa: E402
 
 
 class Recorder(object):
@@ -51,48 +52,12 @@ class Recorder(object):
         self.out["%s/launches" % name] = np.array([h.profile_get(c)["launches"] for c in CLASSES], dtype=np.int64)
 
 
-def _lik(be, kind, k):
-    """(descriptor, targets sampler) of a likelihood kind with fixed parameters"""
-    edges = np.linspace(-1.5, 1.5, 4)
-    table = {
-        "gaussian": (be.make_lik(0, [0.3]), lambda r, s: r.standard_normal(s)),
-        "bernoulli": (be.make_lik(1, [], 20), lambda r, s: (r.random(s) < 0.5).astype(float)),
-        "poisson": (be.make_lik(2, [1.0]), lambda r, s: r.poisson(2.0, s).astype(float)),
-        "exponential": (be.make_lik(3, []), lambda r, s: r.exponential(1.0, s) + 1e-3),
-        "student_t": (be.make_lik(4, [0.7, 4.0], 20), lambda r, s: r.standard_normal(s)),
-        "multiclass": (be.make_lik(5, [1e-3], 20), lambda r, s: r.integers(0, k, (s[0], 1)).astype(float)),
-        "gamma": (be.make_lik(6, [1.7]), lambda r, s: r.gamma(2.0, 1.0, s) + 1e-3),
-        "beta": (be.make_lik(7, [3.0], 20), lambda r, s: r.beta(2.0, 3.0, s)),
-        "ordinal": (be.make_lik(8, [0.7], 20, edges=edges), lambda r, s: r.integers(0, 5, s).astype(float)),
-    }
-    return table[kind]
-
-
 def _kernels(gpf, d):
     ls = np.linspace(0.8, 1.3, d)
     # "linear": Kdiag depends on the point (a Linear part alone would leave Kuu with rank d)
     return {"rbf": gpf.kernels.RBF(d, variance=1.3, lengthscales=ls, ARD=True),
             "linear": gpf.kernels.Matern52(d, variance=0.9, lengthscales=ls, ARD=True)
                       + gpf.kernels.Linear(d, variance=np.linspace(0.2, 0.4, d), ARD=True)}
-
-
-def _psi_kernels(gpf, q):
-    E = gpf.ekernels
-    ls = np.linspace(0.7, 1.2, q)
-    return {"single": E.RBF(q, variance=1.4, lengthscales=ls, ARD=True),
-            "sum": E.Sum([E.RBF(1, variance=1.7, lengthscales=ls[:1], active_dims=[0], ARD=True),
-                          E.RBF(q - 1, variance=1.1, lengthscales=ls[1:], active_dims=list(range(1, q)), ARD=True)])}
-
-
-def _psi_inputs(rng, n, m, q):
-    return rng.standard_normal((m, q)), rng.standard_normal((n, q)), np.exp(rng.uniform(np.log(0.05), np.log(0.5), (n, q)))
-
-
-def _tril_stack(rng, m, k):
-    """q_sqrt [M, M, K]: lower triangular with a positive diagonal"""
-    L = 0.1 * np.tril(rng.standard_normal((k, m, m)))
-    L[:, np.arange(m), np.arange(m)] = 0.5 + rng.random((k, m))
-    return np.ascontiguousarray(np.transpose(L, (1, 2, 0)))
 
 
 def case_gpmc(gpf, be, rec):

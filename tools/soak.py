@@ -1,5 +1,6 @@
-"""Soak: a long mixed sequence of every entry point on two handles, one line of progress per step (flushed), so that a stall
-shows where it happened.  usage: soak.py [steps=400] [seed=0]"""
+"""Soak: a long mixed sequence of the GPR (LML, gradient, predict_f), conditional, SVGP, SGPR and FITC entry points on two handles
+(nothing else: the other entries' call-order coverage is tests/test_gpu_call_order.py), one line of progress per step (flushed), so
+that a stall shows where it happened; results are only asserted finite.  usage: soak.py [steps=400] [seed=0]"""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,7 +48,7 @@ summary = {"steps": steps, "seconds": round(time.perf_counter() - t_start, 1), "
            "lookahead_retries": [h.profile_get("lookahead_retries")["launches"], h2.profile_get("lookahead_retries")["launches"]],
            "trsv_wave_fallbacks": [h.profile_get("trsv_wave_fallbacks")["launches"], h2.profile_get("trsv_wave_fallbacks")["launches"]],
            "small_n_fallbacks": [h.profile_get("small_n_fallbacks")["launches"], h2.profile_get("small_n_fallbacks")["launches"]],
-           "what": "tools/soak.py: mixed sequence of every entry point (GPR LML / gradient / predict_f, conditional, SVGP / SGPR / FITC gradients) on two "
+           "what": "tools/soak.py: mixed sequence of the GPR LML / gradient / predict_f, conditional and SVGP / SGPR / FITC gradient entry points only, on two "
                    "handles, sizes 130 .. 16384 (the one-launch small-N path, the look-ahead sweeps, the wavefront substitution all take part)"}
 print("done: %d steps in %.1f s, slowest step %.2f s, look-ahead retries %s, wavefront fall-backs %s, small-N fall-backs %s" % (
     steps, summary["seconds"], worst, summary["lookahead_retries"], summary["trsv_wave_fallbacks"], summary["small_n_fallbacks"]), flush=True)
