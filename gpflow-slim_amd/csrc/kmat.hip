@@ -167,8 +167,11 @@ __device__ __forceinline__ double gps_exp_poly(double x, double k, const ExpTab&
 // k = round(x log2 e) by adding 1.5 * 2^52: the sum's low mantissa bits ARE the integer k (two's complement), and 2^k is
 // applied by adding k to the exponent field of the polynomial's value -- no v_rndne_f64 / v_cvt_i32_f64 / v_ldexp_f64 (each
 // a multi-cycle fp64 instruction; the kernel-matrix kernels are VALU-issue-bound).  Returns 2^ki exp(r), good for
-// ki >= -1021 (p in [0.70, 1.42]: the exponent field cannot wrap); what becomes of smaller ki (arguments below -708: results
-// below 2.2e-308, where exp() would go through the denormals) and of a NaN argument (clamped to -1100 here) is the callers' tail.
+// ki >= -1021 (p in [0.70, 1.42]: the exponent field cannot wrap); what becomes of smaller ki and of a NaN argument (clamped
+// to -1100 here) is the callers' tail: both flush to 0 at ki < -1021, that is for x log2 e < -1021.5, x < -708.05, where the
+// result would be below 2^-1021.5 = 3.15e-308 (NOT at the smallest normal number 2.2e-308: the last binade of the normal
+// range and the denormals, through which exp() goes down to -745.13, are given up).  Pinned contract, tests/_kmat_tail.py: no
+// flush and full relative accuracy for x >= -708; below, a result in [0, 2^-1021] within 2^-1021 of exp(x).
 __device__ __forceinline__ double gps_exp_scaled(double x, const ExpTab& t, int& ki) {
   const double magic = 6755399441055744.0;
   const double kd = fma(fmax(x, -1100.0), t.c[13], magic);
