@@ -260,6 +260,7 @@ struct gps_handle_s {
   DevBuf dSmallOut{bufs};           // everything a small-N likelihood + gradient hands back, contiguous (one copy)
   DevBuf dFeatG{bufs};              // features of the gradient kernel (its own buffer: they may be prepared before the kernel matrix is built)
   DevBuf dGradSums{bufs};           // reduced sums of the gradient kernel (grad.hip)
+  DevBuf dGxPart{bufs}, dGxTab{bufs}, dGxOut{bufs};   // d LML / d X (grad_x.hip): per-slice partials, the feature table, the result [n][d_all]
   void* hRes = nullptr;       // pinned host landing area of small read-backs (GPS_HRES_BYTES)
   DevBuf dBlkCond{bufs};            // kappa_1 of the diagonal blocks (classify_blocks)
   DevBuf dSmallSync{bufs, DevBuf::PERSISTENT};   // counters of the two cooperative launches of the small path (small_n.hip): allocated and cleared once, left zero by every launch
@@ -650,6 +651,15 @@ void gps_grad_finish(const GradPost& post, const double* sums, double* grad_slot
 int gps_launch_kmat_input_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dXr, i64 nr,
                               const double* dXc, i64 nc, i64 d_all, const double* Wd, i64 ldw, double factor,
                               double* grad_X_host);
+// grad_x.hip : d LML / d X [n][d_all] into d_out (device) from what the likelihood's gradient left in dKinv (lower triangle) and
+// dA; for the programs grad.hip takes it reads the feature slabs that gradient left in dFeatG.  Two launches, no synchronisation.
+void gps_grad_x_slicing(i64 npad, int* tiles, int* slices);
+int gps_launch_grad_x(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n, i64 d_all, i64 npad,
+                      const double* dKinv, i64 ldk, const double* dA, i64 lda, i64 r, double* d_out);
+int gps_launch_grad_x_reduce(gps_handle_t h, const double* part, int slices, i64 rows_pad, i64 n, i64 d_all, double* d_out);
+// grad_general.hip : the walk of the other programs (partials only; gps_launch_grad_x decides and reduces)
+int gps_launch_grad_x_general(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n, i64 d_all, i64 npad,
+                              const double* dKinv, i64 ldk, const double* dA, i64 lda, i64 r, int slices, double* d_part);
 int gps_kdiag_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, double kbar, double* grad_slots_host);
 // ... and of a program with Linear or ArcCosine, whose Kdiag depends on the point: X host [n, d_all], one kbar per point (host), added to the slots
 int gps_kdiag_vjp_points(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 d_all, const double* X, i64 n, const double* kbar,

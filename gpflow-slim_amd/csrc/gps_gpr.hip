@@ -430,28 +430,44 @@ static int gpr_grad_readback(gps_handle_t h, const gps_kern_node_t* prog, int n_
   return GPS_OK;
 }
 
+// d LML / d X behind the gradient, on its way to the host (no synchronisation: the caller's final one covers it).  Its work
+// buffers are its own (dGxPart / dGxTab / dGxOut): nothing here touches dTmp2, where the gradient's sums and the transposed A live.
+static int gpr_grad_x_readback(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 r, double* grad_X) {
+  const i64 n = h->n, np = h->npad;
+  GPS_HIP(h, h->dGxOut.ensure((size_t)n * h->d_all * 8));
+  int rc = gps_launch_grad_x(h, prog, n_nodes, h->dX.d(), n, h->d_all, np, h->dKinv.d(), np, h->dA.d(), np, r, h->dGxOut.d());
+  if (rc) return rc;
+  GPS_HIP(h, hipMemcpyAsync(grad_X, h->dGxOut.p, (size_t)n * h->d_all * 8, hipMemcpyDeviceToHost, h->stream));
+  return GPS_OK;
+}
+
 // What follows the (not yet read back) one-launch factorisation of a small problem in gps_gpr_lml_grad: the inverse and the
 // gradient sums enqueued behind it, and everything the host needs back in one pinned copy behind ONE synchronisation.
 // *done = false: a bounded wait of one of the two cooperative launches gave up, nothing of the outputs is valid.
 static int gpr_small_grad_tail(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 r, double* lml, double* grad_slots,
-                               double* grad_noise, double* kinv_resid, int* info, bool* done) {
+                               double* grad_noise, double* kinv_resid, double* grad_X, int* info, bool* done) {
   const i64 n = h->n, np = h->npad;
   *done = false;
   int rc = ensure_hres(h);
   if (rc) return rc;
   GPS_HIP(h, hipEventRecord(h->ev[5], h->stream));
   // dSmallOut: [0..3] the factorisation's results (already on their way), [4] the inverse launch's abort word, [5 ..] the
-  // gradient sums, then K^-1 resid as [n][r] -- one copy brings all of it back
+  // gradient sums, then K^-1 resid as [n][r], then d LML / d X as [n][d_all] -- one copy brings all of it back
   double* d_res = h->dSmallOut.d();
+  const i64 off_x = 5 + GPS_GRAD_SUMS + (kinv_resid ? n * r : 0);
   rc = gpr_kinv_small(h, r, d_res + 4, kinv_resid ? d_res + 5 + GPS_GRAD_SUMS : nullptr);
   if (rc) return rc;                   // (the factorisation took this shape: so does the inverse)
   // (launching the gradient kernel's features in front of the factorisation instead -- the first half of gps_grad_enqueue -- was measured: no gain)
   GradPost post;
   rc = gps_grad_enqueue(h, prog, n_nodes, h->dX.d(), n, h->d_all, np, h->dKinv.d(), np, h->dA.d(), np, r, d_res + 5, &post);
   if (rc) return rc;
+  if (grad_X) {                        // two more launches behind the gradient sums, from the same feature slabs
+    rc = gps_launch_grad_x(h, prog, n_nodes, h->dX.d(), n, h->d_all, np, h->dKinv.d(), np, h->dA.d(), np, r, d_res + off_x);
+    if (rc) return rc;
+  }
   double* res = (double*)h->hRes;
   res[3] = 1.0; res[4] = 1.0;
-  GPS_HIP(h, hipMemcpyAsync(res, d_res, (size_t)(5 + GPS_GRAD_SUMS + (kinv_resid ? n * r : 0)) * 8, hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipMemcpyAsync(res, d_res, (size_t)(off_x + (grad_X ? n * h->d_all : 0)) * 8, hipMemcpyDeviceToHost, h->stream));
   GPS_HIP(h, hipEventRecord(h->ev[6], h->stream));
   GPS_HIP(h, hipStreamSynchronize(h->stream));
   if (res[3] != 0.0 || res[4] != 0.0) return GPS_OK;
@@ -463,17 +479,18 @@ static int gpr_small_grad_tail(gps_handle_t h, const gps_kern_node_t* prog, int 
   stage_time(h, 5, 6, &h->stage_ms[3]);
   gps_grad_finish(post, res + 5, grad_slots, grad_noise);
   if (kinv_resid) memcpy(kinv_resid, res + 5 + GPS_GRAD_SUMS, (size_t)n * r * 8);
+  if (grad_X) memcpy(grad_X, res + off_x, (size_t)n * h->d_all * 8);
   return GPS_OK;
 }
 
 // LML and its gradient: d/d(kernel parameter slots), d/d(noise variance), d/d(resid) = -K_y^-1 resid ... see header
 //   factor  ->  K_y^-1 and A (one cooperative launch, or launch by launch)  ->  gradient  ->  read-back
-extern "C" int gps_gpr_lml_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double noise_var,
-                                const double* resid, int64_t r, double* lml, double* grad_slots,
-                                int n_slots_cap, int* n_slots_out, double* grad_noise, double* kinv_resid,
-                                int* info) {
-  if (!h || !lml || !grad_slots || !grad_noise || r <= 0)
-    return gps_fail(h, GPS_ERR_ARG, "gps_gpr_lml_grad: bad argument");
+// grad_X (gps_gpr_lml_grad_x; nullptr: gps_gpr_lml_grad, whose launches and results are what they were): d LML / d X [n][d_all]
+// behind the gradient on every route, recomputed with the rest wherever a route is given up and redone.
+static int gpr_lml_grad_body(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double noise_var,
+                             const double* resid, int64_t r, double* lml, double* grad_slots,
+                             int n_slots_cap, int* n_slots_out, double* grad_noise, double* kinv_resid,
+                             double* grad_X, int* info) {
   // (a hand-over of the look-ahead or of the backward wavefront substitution that gives up invalidates this call, not the
   // next one: the body runs again, once, through the recursive forms -- with_la_retry)
   return with_la_retry(h, [&]() -> int {
@@ -486,8 +503,11 @@ extern "C" int gps_gpr_lml_grad(gps_handle_t h, const gps_kern_node_t* prog, int
   int linfo = 0;
   // Small problems (the reference's own size: examples/gpr.py): factorisation, inverse and gradient sums are enqueued
   // back to back -- six launches -- and everything the host needs comes back in one pinned copy behind ONE synchronisation.
+  const size_t out_doubles = (size_t)(5 + GPS_GRAD_SUMS + (kinv_resid ? h->n * r : 0) + (grad_X ? h->n * h->d_all : 0));
   h->small.defer = h->small.on > 0 && r <= 16 && h->npad <= h->small_n_max && gps_grad_is_simple(prog, n_nodes) &&
-                   (!kinv_resid || (size_t)(5 + GPS_GRAD_SUMS + h->n * r) * 8 <= GPS_HRES_BYTES);
+                   ((!kinv_resid && !grad_X) || out_doubles * 8 <= GPS_HRES_BYTES);
+  // (the factorisation sizes dSmallOut for its own results, the sums and K^-1 resid: d LML / d X behind them needs the room first)
+  if (h->small.defer && grad_X) GPS_HIP(h, h->dSmallOut.ensure(out_doubles * 8));
   h->small.pending = false;
   rc = gpr_factor(h, prog, n_nodes, noise_var, resid, r, &linfo);
   h->small.defer = false;
@@ -495,7 +515,7 @@ extern "C" int gps_gpr_lml_grad(gps_handle_t h, const gps_kern_node_t* prog, int
   if (h->small.pending) {
     h->small.pending = false;
     bool done = false;
-    rc = gpr_small_grad_tail(h, prog, n_nodes, r, lml, grad_slots, grad_noise, kinv_resid, &linfo, &done);
+    rc = gpr_small_grad_tail(h, prog, n_nodes, r, lml, grad_slots, grad_noise, kinv_resid, grad_X, &linfo, &done);
     if (rc) return rc;
     if (done) { if (info) *info = linfo; return GPS_OK; }
     rc = gpr_small_refactor(h, prog, n_nodes, noise_var, resid, r, &linfo);
@@ -511,6 +531,7 @@ extern "C" int gps_gpr_lml_grad(gps_handle_t h, const gps_kern_node_t* prog, int
     rc = gpr_kinv_small(h, r, d_abort, nullptr);
     if (rc == GPS_OK) {
       rc = gpr_grad_readback(h, prog, n_nodes, r, grad_slots, grad_noise, kinv_resid);
+      if (!rc && grad_X) rc = gpr_grad_x_readback(h, prog, n_nodes, r, grad_X);
       if (rc) return rc;
       // (the launch-by-launch path touches neither the info word nor a hand-over: the only thing to read back is whether a
       // bounded wait of the cooperative launch ran out -- never seen -- and then the same again launch by launch, below)
@@ -529,6 +550,7 @@ extern "C" int gps_gpr_lml_grad(gps_handle_t h, const gps_kern_node_t* prog, int
   }
   rc = gpr_kinv_blocked(h, r);
   if (!rc) rc = gpr_grad_readback(h, prog, n_nodes, r, grad_slots, grad_noise, kinv_resid);
+  if (!rc && grad_X) rc = gpr_grad_x_readback(h, prog, n_nodes, r, grad_X);
   if (rc) return rc;
   GPS_HIP(h, hipEventRecord(h->ev[6], h->stream));
   // synchronises, and surfaces a backward wavefront substitution that gave up (its result would poison dA and every
@@ -538,6 +560,29 @@ extern "C" int gps_gpr_lml_grad(gps_handle_t h, const gps_kern_node_t* prog, int
   stage_time(h, 5, 6, &h->stage_ms[3]);
   return GPS_OK;
   });
+}
+
+extern "C" int gps_gpr_lml_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double noise_var,
+                                const double* resid, int64_t r, double* lml, double* grad_slots,
+                                int n_slots_cap, int* n_slots_out, double* grad_noise, double* kinv_resid,
+                                int* info) {
+  if (!h || !lml || !grad_slots || !grad_noise || r <= 0)
+    return gps_fail(h, GPS_ERR_ARG, "gps_gpr_lml_grad: bad argument");
+  return gpr_lml_grad_body(h, prog, n_nodes, noise_var, resid, r, lml, grad_slots, n_slots_cap, n_slots_out, grad_noise, kinv_resid,
+                           nullptr, info);
+}
+
+// ... and d LML / d X with it (grad_x.hip): see the header
+extern "C" int gps_gpr_lml_grad_x(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double noise_var,
+                                  const double* resid, int64_t r, double* lml, double* grad_slots,
+                                  int n_slots_cap, int* n_slots_out, double* grad_noise, double* kinv_resid,
+                                  double* grad_X, int* info) {
+  if (!h || !lml || !grad_slots || !grad_noise || !grad_X || r <= 0)
+    return gps_fail(h, GPS_ERR_ARG, "gps_gpr_lml_grad_x: bad argument");
+  if (h->d_all > GPS_MAX_DIMS)
+    return gps_fail(h, GPS_ERR_UNSUPPORTED, "gps_gpr_lml_grad_x: X has more columns than GPS_MAX_DIMS = 32, the limit of the input gradient");
+  return gpr_lml_grad_body(h, prog, n_nodes, noise_var, resid, r, lml, grad_slots, n_slots_cap, n_slots_out, grad_noise, kinv_resid,
+                           grad_X, info);
 }
 
 // ---- predict_f on few test points: wide inverse blocks of the resident factor ------------------------------------------------

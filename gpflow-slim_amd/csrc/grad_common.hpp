@@ -128,6 +128,39 @@ __device__ __forceinline__ double grad_lml_weight(const Args& a, i64 i, i64 j, i
   return val;
 }
 
+// The FULL likelihood weight W_ij = (A A^T - r K_y^-1)_ij -- no halving, no triangle mask, 0 in the padding -- at a thread's 2 x 2
+// patch of the 32 x 32 tile (ti, tj) of the square: what the gradient with respect to the inputs takes (grad_x.hip, and the
+// likelihood instances of gg_input_body).  Only the lower triangle of Kinv is valid: a tile above the diagonal reads the block
+// (tj, ti) and indexes it transposed, the tile on the diagonal reads entry (max, min).  The block goes through S (32 x 33
+// doubles of LDS), so the global reads run along rows either way.  Starts with a barrier (S may be a slab that earlier code of
+// the workgroup still reads); whoever writes S next synchronises first.
+template <class Args>
+__device__ __forceinline__ void grad_lml_weight_tile(const Args& a, int ti, int tj, double* S, int tid, int ty, int tx, double (&w)[4]) {
+  const bool upper = tj > ti;
+  const i64 gi0 = (i64)ti * 32, gj0 = (i64)tj * 32;
+  const i64 br = upper ? gj0 : gi0, bc = upper ? gi0 : gj0;
+  __syncthreads();
+  for (int idx = tid; idx < 32 * 32; idx += 256) {
+    const int rr = idx >> 5, cc = idx & 31;
+    S[rr * 33 + cc] = a.Kinv[(br + rr) * a.ldk + bc + cc];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int li = ty * 2 + (e >> 1), lj = tx * 2 + (e & 1);
+    const i64 i = gi0 + li, j = gj0 + lj;
+    double val = 0.0;
+    if (i < a.n && j < a.n) {
+      double s = 0.0;
+      for (int q = 0; q < a.r; ++q) s += a.A[(i64)q * a.lda + i] * a.A[(i64)q * a.lda + j];
+      int sr = upper ? lj : li, sc = upper ? li : lj;
+      if (ti == tj && sr < sc) { const int t = sr; sr = sc; sc = t; }
+      val = s - (double)a.r * S[sr * 33 + sc];
+    }
+    w[e] = val;
+  }
+}
+
 #define GRAD_SQRT3 1.7320508075688772
 #define GRAD_SQRT5 2.23606797749979
 

@@ -487,7 +487,10 @@ __global__ __launch_bounds__(256) void gg_coregion_kernel(GGArgs a, GGProg P) { 
 // shuffles, over the tiles in LDS; the slices' partial sums [slices][rows][d_all] are added in order on the host.
 struct GIArgs { const GradFeat* feats; double* part; int d_all; int slices; i64 rows_pad; };
 
-template <bool CRG>
+// LML: the weight is not a stored cotangent but the likelihood's own W = A A^T - R K_y^-1, read mirrored from the lower triangle
+// of Kinv (grad_lml_weight_tile; the block is staged in Fr_s, which the values' staging overwrites behind a barrier): d LML / d X
+// of gps_gpr_lml_grad_x for the programs grad_x.hip does not take.  The stored-cotangent instances keep their code.
+template <bool CRG, bool LML = false>
 __device__ __forceinline__ void gg_input_body(GGArgs a, GGProg P, GIArgs gi) {
   __shared__ double Fr_s[GRAD_MAXF * GG_T];
   __shared__ double Fc_s[GRAD_MAXF * GG_T];
@@ -506,10 +509,14 @@ __device__ __forceinline__ void gg_input_body(GGArgs a, GGProg P, GIArgs gi) {
   for (int tj = tj0; tj < tj1; ++tj) {
     const i64 gj0 = (i64)tj * GG_T;
     double w[GG_E];
+    if constexpr (LML) {
+      grad_lml_weight_tile(a, ti, tj, Fr_s, tid, ty, tx, w);
+    } else {
 #pragma unroll
-    for (int e = 0; e < GG_E; ++e) {
-      const i64 i = gi0 + ty * 2 + (e >> 1), j = gj0 + tx * 2 + (e & 1);
-      w[e] = (i < a.nr && j < a.nc) ? a.Wd[i * a.ldw + j] : 0.0;
+      for (int e = 0; e < GG_E; ++e) {
+        const i64 i = gi0 + ty * 2 + (e >> 1), j = gj0 + tx * 2 + (e & 1);
+        w[e] = (i < a.nr && j < a.nc) ? a.Wd[i * a.ldw + j] : 0.0;
+      }
     }
     double pv[GG_MAXP][GG_E], fp[GG_MAXP][GG_E];
     gg_values<CRG>(a, P, gi0, gj0, same_points, Fr_s, Fc_s, tid, ty, tx, pv);
@@ -627,6 +634,8 @@ __device__ __forceinline__ void gg_input_body(GGArgs a, GGProg P, GIArgs gi) {
 }
 __global__ __launch_bounds__(256) void gg_input_kernel(GGArgs a, GGProg P, GIArgs gi) { gg_input_body<false>(a, P, gi); }
 __global__ __launch_bounds__(256) void gg_input_coregion_kernel(GGArgs a, GGProg P, GIArgs gi) { gg_input_body<true>(a, P, gi); }
+__global__ __launch_bounds__(256) void gg_input_lml_kernel(GGArgs a, GGProg P, GIArgs gi) { gg_input_body<false, true>(a, P, gi); }
+__global__ __launch_bounds__(256) void gg_input_lml_coregion_kernel(GGArgs a, GGProg P, GIArgs gi) { gg_input_body<true, true>(a, P, gi); }
 
 // ---- host side ------------------------------------------------------------------------------------
 #define GG_BLOCKS 2048
@@ -988,5 +997,32 @@ int gps_launch_kmat_input_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n
       for (int q = 0; q < slices; ++q) tot += part[((size_t)q * nrp + i) * d_all + d];
       grad_X_host[i * d_all + d] += factor * tot;
     }
+  return GPS_OK;
+}
+
+// d LML / d X for the programs grad_x.hip's own kernel does not take (gps_launch_grad_x decides; not called otherwise): the
+// per-slice partial sums [slices][npad][d_all] into d_part, from dKinv (lower triangle) and dA.  One launch behind the feature
+// launch and the uploads, no synchronisation; gps_launch_grad_x reduces the slices.
+int gps_launch_grad_x_general(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n, i64 d_all, i64 npad,
+                              const double* dKinv, i64 ldk, const double* dA, i64 lda, i64 r, int slices, double* d_part) {
+  if (d_all > GPS_MAX_DIMS) return gps_fail(h, GPS_ERR_UNSUPPORTED, "input gradient: X has more columns than GPS_MAX_DIMS = 32");
+  GGBuilt B;
+  int rc = gg_build(h, prog, n_nodes, d_all, B);
+  if (rc) return rc;
+  rc = gg_features(h, B, dX, n, d_all, npad, h->dFeat);
+  if (rc) return rc;
+  GGArgs a;
+  memset(&a, 0, sizeof(a));
+  a.Ft = h->dFeat.d(); a.ldf = npad; a.Ftc = a.Ft; a.ldfc = npad; a.Kinv = dKinv; a.ldk = ldk; a.A = dA; a.lda = lda; a.r = (int)r;
+  a.n = n; a.npad = npad; a.tiles = (int)(npad / GG_T); a.tiles_c = a.tiles; a.same_points = 1; a.nr = n; a.nc = n;
+  rc = gg_upload_net(h, B, a);
+  if (rc) return rc;
+  GIArgs gi;
+  gi.feats = (const GradFeat*)h->dProg.p; gi.d_all = (int)d_all; gi.rows_pad = npad; gi.slices = slices; gi.part = d_part;      // (gg_features left the table there)
+  const double sq = (double)npad * (double)npad;
+  LaunchScope ls(h, KC_REDUCE, gg_work(B, (double)npad, (double)npad, 6.0), 8.0 * sq);
+  hipLaunchKernelGGL(B.coregion ? gg_input_lml_coregion_kernel : gg_input_lml_kernel, dim3((unsigned)a.tiles, (unsigned)slices), dim3(256),
+                     0, h->stream, a, B.P, gi);
+  GPS_HIP(h, hipGetLastError());
   return GPS_OK;
 }

@@ -192,6 +192,15 @@ def psi_sum_chunking(n, m, opt=0):
     return ch, -(-n // ch)
 
 
+def grad_x_slicing(n):
+    """(32-row blocks, slices of the column tiles, column tiles per slice) of the walk that d LML / d X makes over the padded
+    square of n points: workgroup (block, slice) owns 32 rows and `per` 32-column tiles  (csrc/grad_x.hip: gps_grad_x_slicing;
+    the kernels' `per`)."""
+    tiles = 128 * -(-n // 128) // 32
+    per = -(-tiles // max(1, min(2048 // tiles, tiles, 64)))
+    return tiles, -(-tiles // per), per
+
+
 # ---- argument types of every exported function, in the header's order of parameters (tests/test_host_api.py compares the two)
 _int, _dbl, _vp, _str = ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_char_p
 _dp, _ip, _i64p = _c_double_p, _c_int_p, ctypes.POINTER(_i64)
@@ -215,6 +224,7 @@ _SIGNATURES = {
     "gps_gpr_set_data": [_vp, _dp, _i64, _i64],
     "gps_gpr_lml": [_vp, _prog, _int, _dbl, _dp, _i64, _dp, _ip],
     "gps_gpr_lml_grad": [_vp, _prog, _int, _dbl, _dp, _i64, _dp, _dp, _int, _ip, _dp, _dp, _ip],
+    "gps_gpr_lml_grad_x": [_vp, _prog, _int, _dbl, _dp, _i64, _dp, _dp, _int, _ip, _dp, _dp, _dp, _ip],
     "gps_gpr_predict": [_vp, _prog, _int, _dbl, _dp, _i64, _dp, _i64, _int, _int, _dp, _dp, _ip],
     "gps_conditional": [_vp, _prog, _int, _dp, _i64, _i64, _dbl, _dp, _i64, _dp, _i64, _dp, _int, _int, _int, _dp, _dp, _ip],
     "gps_base_conditional": [_vp, _dp, _dp, _dp, _i64, _i64, _dp, _i64, _dp, _int, _int, _int, _dp, _dp, _ip],

@@ -16,7 +16,7 @@ from ._abi import (GPS_MAX_DIMS, GPS_MAX_NODES, GPS_MAX_STACK,                  
                    K_SQDIST, K_EUCLID, K_RATQUAD, K_LINEAR, K_POLYNOMIAL, K_COSINE, K_ARCCOSINE, K_ADD, K_MUL, K_COREGION,
                    K_NKN_LINROW, K_NKN_PRODUCT, K_NKN_ACT, KernNode, LikDesc, RffDesc,
                    RFF_RBF, RFF_LINEAR, RFF_CONSTANT, RFF_EXPLICIT, LIK_MAX_GH, LIK_MAX_EDGES, LIK_MULTICLASS, LIK_ORDINAL,
-                   make_rff, make_lik, make_program, primitive_node, coregion_node, op_node, psi2_chunking, psi_sum_chunking,
+                   make_rff, make_lik, make_program, primitive_node, coregion_node, op_node, psi2_chunking, psi_sum_chunking, grad_x_slicing,
                    _SIGNATURES, EXPORTED_SYMBOLS, ALLREDUCE_FN, _c_double_p, _c_int_p, _i64,
                    lib_path, load_library, comm_load, comm_unique_id, comm_version)
 
@@ -494,8 +494,9 @@ class Handle(object):
         _raise_if_not_pd(info, _PD_CHOL)
         return lml.value
 
-    def gpr_lml_grad(self, prog, noise_var, resid):
-        """(lml, grad_slots, grad_noise, K_y^-1 resid)  -- see gps_gpr_lml_grad in the header."""
+    def gpr_lml_grad(self, prog, noise_var, resid, want_grad_X=False):
+        """(lml, grad_slots, grad_noise, K_y^-1 resid)  -- see gps_gpr_lml_grad in the header.  want_grad_X: d LML / d X [N, D]
+        as a fifth item (gps_gpr_lml_grad_x; the chain through a mean function is the caller's)."""
         resid = _f64(resid)
         shape = self.resident_shape
         _need(shape is not None and resid.ndim == 2 and resid.shape[0] == shape[0] and resid.shape[1] > 0,
@@ -505,6 +506,12 @@ class Handle(object):
         slots, ns = self._slot_buffer()
         kinv_resid = np.empty((n, r))
         self._drop_resident(data=False)
+        if want_grad_X:
+            grad_X = np.empty((n, shape[1]))
+            self._call("gps_gpr_lml_grad_x", prog, len(prog), float(noise_var), _ptr(resid), r, _byref(lml), _ptr(slots), SLOT_CAP,
+                       _byref(ns), _byref(gnoise), _ptr(kinv_resid), _ptr(grad_X), _byref(info))
+            _raise_if_not_pd(info, _PD_CHOL)
+            return lml.value, slots[:ns.value].copy(), gnoise.value, kinv_resid, grad_X
         self._call("gps_gpr_lml_grad", prog, len(prog), float(noise_var), _ptr(resid), r, _byref(lml), _ptr(slots), SLOT_CAP,
                    _byref(ns), _byref(gnoise), _ptr(kinv_resid), _byref(info))
         _raise_if_not_pd(info, _PD_CHOL)

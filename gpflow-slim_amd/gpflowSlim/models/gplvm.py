@@ -1,4 +1,11 @@
-"""Bayesian GPLVM (Titsias & Lawrence 2010).
+"""GPLVM, the point-estimate latent variable model, and the Bayesian GPLVM (Titsias & Lawrence 2010).
+
+``GPLVM`` (gplvm.py:16-51) is a ``GPR`` whose inputs X [N, Q] are a trainable ``Parameter``: the likelihood is the exact-GP
+log-marginal likelihood of Y given the latent positions, and its gradient with respect to them,
+d LML / d X[i] = sum_j (A A^T - R K_y^-1)_ij d k(x_i, x_j) / d x_i, comes from the device with the rest of the gradient
+(gps_gpr_lml_grad_x, csrc/grad_x.hip): inside the single synchronisation of the one-launch path at the sizes the model is
+used at.  Any kernel with a likelihood gradient is accepted; at most 32 latent dimensions; no minibatching, no sharding over
+ranks, no random-feature kernels.
 
 Mirrors gpflowSlim/models/gplvm.py:54-220 (BayesianGPLVM, PCA_reduce).  The bound is the SGPR collapsed bound with
 sum Kdiag, Kuf and Kuf Kuf^T replaced by the kernel expectations psi0, Psi1, Psi2 under q(x_n) = N(X_mean_n, diag X_var_n);
@@ -7,7 +14,7 @@ The KL[q(x) || p(x)] term (gplvm.py:150-156) is elementwise over [N, Q] and is e
 
 Scope: one ``ekernels.RBF`` over all Q latent dimensions, or an ``ekernels.Sum`` of RBF kernels on pairwise disjoint latent
 dimensions (the kernel of the reference's examples/gplvm.py; gradients arrive per part in ``kern.kern_list[i]``), and diagonal
-``X_var`` [N, Q]; no minibatching, no sharding over ranks.  The point-estimate ``GPLVM`` is not implemented.
+``X_var`` [N, Q]; no minibatching, no sharding over ranks.
 """
 import numpy as np
 
@@ -19,6 +26,69 @@ from ..params import Parameter
 from ..mean_functions import Zero
 from .._settings import settings
 from .model import GPModel
+from .gpr import GPR
+
+
+class GPLVM(GPR):
+    """gplvm.py:16-51: standard GPLVM, the likelihood is optimised with respect to the latent X as well."""
+    MAX_LATENT = be.GPS_MAX_DIMS          # columns of X the device's input gradient takes
+
+    def __init__(self, Y, latent_dim, X_mean=None, kern=None, mean_function=None, obs_var=0.1, **kwargs):
+        """Y [N, D]; latent_dim Q; X_mean [N, Q] the initial latent positions (default: PCA_reduce(Y, Q)); kern (default: an
+        ARD RBF on the Q latent dimensions); mean_function (default: Zero)."""
+        from .. import kernels
+        Y = np.ascontiguousarray(Y, dtype=settings.float_type)
+        latent_dim = int(latent_dim)
+        if latent_dim > self.MAX_LATENT:
+            raise NotImplementedError("GPLVM takes at most %d latent dimensions (asked for %d)" % (self.MAX_LATENT, latent_dim))
+        if mean_function is None:
+            mean_function = Zero()
+        if kern is None:
+            kern = kernels.RBF(latent_dim, ARD=True)
+        if X_mean is None:
+            if Y.ndim == 2 and Y.shape[1] < latent_dim:
+                raise ValueError('More latent dimensions than observed.')
+            X_mean = PCA_reduce(Y, latent_dim)
+        X_mean = np.ascontiguousarray(X_mean, dtype=settings.float_type)
+        num_latent = X_mean.shape[1]
+        if num_latent != latent_dim:
+            raise ValueError('Passed in number of latent {0} does not match initial X {1}.'.format(latent_dim, num_latent))
+        if Y.shape[1] < num_latent:
+            raise ValueError('More latent dimensions than observed.')
+        self._X = None
+        GPR.__init__(self, X_mean, Y, kern, mean_function=mean_function, obs_var=obs_var, **kwargs)
+        self._X = Parameter(X_mean, name='X')
+        self._X_seen = None
+        self._parameters = self._parameters + [self._X]
+
+    @property
+    def X(self):
+        """The latent positions [N, Q].  GPR keys what is resident on the device on the IDENTITY of this array: the same
+        object comes back for as long as the parameter's bytes are unchanged (an optimiser that writes equal values back
+        causes no upload), a new one as soon as they differ."""
+        v = np.ascontiguousarray(self._X.value, dtype=settings.float_type)
+        if self._X_seen is None or self._X_seen.shape != v.shape or not np.array_equal(self._X_seen, v):
+            self._X_seen = v.copy()
+            self._X_seen.setflags(write=False)
+        return self._X_seen
+
+    @X.setter
+    def X(self, value):
+        if self._X is not None:
+            self._X.assign(np.ascontiguousarray(value, dtype=settings.float_type))
+        # (GPModel.__init__ stores the initial X before the Parameter exists: the Parameter made next holds it)
+
+    def compute_log_likelihood_and_gradients(self, with_inputs=False):
+        """(lml, [(Parameter, gradient), ...]): the list of GPR and, last, (the X parameter, d LML / d X) -- the device's input
+        gradient plus the mean function's chain term (X has the identity transform).  with_inputs: d LML / d X once more as a
+        third item, as GPR returns it."""
+        if self._has_features():
+            raise NotImplementedError("GPLVM needs d LML / d X, which the feature (random-feature) branch does not have")
+        lml, grads, gX = GPR.compute_log_likelihood_and_gradients(self, with_inputs=True)
+        last = grads[-1]
+        assert last[0] is self._X
+        grads[-1] = (self._X, gX * np.atleast_1d(self._X.transform.forward_grad(self._X.vf_val)))
+        return (lml, grads, gX) if with_inputs else (lml, grads)
 
 
 class BayesianGPLVM(GPModel):

@@ -130,22 +130,51 @@ class GPR(GPModel):
             lml = h.gpr_lml(prog, float(np.squeeze(self.likelihood.variance)), self._resid())
         return lml
 
-    def compute_log_likelihood_and_gradients(self):
+    def compute_log_likelihood_and_gradients(self, with_inputs=False):
         """LML and d LML / d(unconstrained parameter) for every parameter of the model -- what
         `tf.gradients(objective, variables)` yields in the reference (examples/gpr.py:53-54) up to the
         sign of `objective = -LML`.  Returns (lml, [(Parameter, gradient array shaped like
-        Parameter.unconstrained_tensor), ...]) in `self.parameters` order.  Priors are not included."""
+        Parameter.unconstrained_tensor), ...]) in `self.parameters` order.  Priors are not included.
+
+        with_inputs: (lml, grads, dLML_dX) with d LML / d X [N, D], the derivative of the evidence with respect to the input
+        locations: the kernel's part from the device (gps_gpr_lml_grad_x) plus the mean function's chain term."""
         if self._has_features():
+            if with_inputs:
+                raise NotImplementedError("d LML / d X is not available on the feature (random-feature) branch")
             return self._rff_likelihood_and_gradients()
+        if with_inputs:
+            self._input_chain(None)               # (refuse a mean function without a known chain before any device work)
         self.kern._check_inputs(self.X)
         h = self._handle()
         d_all = self.X.shape[1]
         prog = self.kern._program(d_all)
         layout = self.kern._grad_layout(d_all)
         resid = self._resid()
+        noise = float(np.squeeze(self.likelihood.variance))
         with h.factor_claim(self._state_key()):
-            lml, slots, gnoise, kinv_resid = h.gpr_lml_grad(prog, float(np.squeeze(self.likelihood.variance)), resid)
-        return lml, self._gradients_from_slots(layout, slots, gnoise, kinv_resid)
+            if with_inputs:
+                lml, slots, gnoise, kinv_resid, grad_X = h.gpr_lml_grad(prog, noise, resid, want_grad_X=True)
+            else:
+                lml, slots, gnoise, kinv_resid = h.gpr_lml_grad(prog, noise, resid)
+        grads = self._gradients_from_slots(layout, slots, gnoise, kinv_resid)
+        if with_inputs:
+            return lml, grads, grad_X + self._input_chain(kinv_resid)
+        return lml, grads
+
+    def _input_chain(self, kinv_resid):
+        """What the mean function adds to d LML / d X: d LML / d m(X) = K_y^-1 (Y - m) chained through d m / d X -- A^T rows for
+        Linear (m = X A + b), nothing for Zero and Constant.  kinv_resid None: only the check that the chain is known."""
+        from ..mean_functions import Zero as _MZero, Constant as _MConst, Linear as _MLin
+        mf = self.mean_function
+        if isinstance(mf, _MLin):
+            if kinv_resid is None:
+                return 0.0
+            A = np.atleast_2d(mf.A.value)                       # [D, R], or [D, 1] broadcast over the outputs
+            g = kinv_resid if A.shape[1] == kinv_resid.shape[1] else np.sum(kinv_resid, axis=1, keepdims=True)
+            return g @ A.T
+        if isinstance(mf, (_MZero, _MConst)):
+            return 0.0
+        raise NotImplementedError("d LML / d X through a %s mean function is not implemented" % type(mf).__name__)
 
     def _gradients_from_slots(self, layout, slots, gnoise, kinv_resid):
         """Map the kernel's gradient slots, d LML / d(noise variance) and K_y^-1 (Y - m) onto

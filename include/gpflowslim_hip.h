@@ -180,6 +180,19 @@ int gps_gpr_lml_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes,
                      double* grad_slots, int n_slots_cap, int* n_slots_out,
                      double* grad_noise, double* kinv_resid, int* info);
 
+/* The same, and the gradient with respect to the inputs with it -- what autodiff hands to a trainable X (models/gplvm.py:16-51:
+ * GPLVM is a GPR whose X is a Parameter):
+ *   grad_X host [n, d_all] (required):  grad_X[i][d] = sum_j W_ij d k(x_i, x_j) / d x_i[d],  W = A A^T - r K_y^-1
+ * (the derivative in the first argument; the 1/2 of d LML / d K cancels against the two arguments of a symmetric kernel; the
+ * diagonal term is included).  Columns of X that no primitive reads, and the label column of a Coregion node, receive exactly
+ * 0.0.  The chain through a mean function is the caller's (kinv_resid).  W never leaves the device: two launches behind the
+ * gradient's own on every route, inside the one synchronisation of the one-launch small path where the results fit its
+ * read-back.  Every other output is bytewise what gps_gpr_lml_grad returns.  d_all > GPS_MAX_DIMS: GPS_ERR_UNSUPPORTED.  */
+int gps_gpr_lml_grad_x(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes,
+                       double noise_var, const double* resid, int64_t r, double* lml,
+                       double* grad_slots, int n_slots_cap, int* n_slots_out,
+                       double* grad_noise, double* kinv_resid, double* grad_X, int* info);
+
 /* GPR._build_predict exact branch (models/gpr.py:119-131).
  * refactor != 0: rebuild K, L, V exactly like the reference does on every
  * predict_f call ("cold"); refactor == 0: reuse L / V left by the previous
