@@ -165,6 +165,7 @@ static int dg_streams(gps_handle_t h, int exchange_mode) {
 extern "C" int gps_dist_lml_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double noise_var, const double* resid,
                                  int64_t r, int64_t nb, int lookahead, int exchange_mode, double* lml, double* grad_slots,
                                  int n_slots_cap, int* n_slots_out, double* grad_noise, double* kinv_resid, int* info) {
+  if (int rf = gps_ms_refuse(h, "gps_dist_lml_grad")) return rf;
   if (!h || !prog || !lml || !grad_slots || !grad_noise || r <= 0) return gps_fail(h, GPS_ERR_ARG, "gps_dist_lml_grad: bad argument");
   if (!h->comm) return gps_fail(h, GPS_ERR_STATE, "gps_dist_lml_grad: the handle has no communicator (gps_comm_init)");
   if (!h->dist.partitioned) return gps_fail(h, GPS_ERR_STATE, "gps_dist_lml_grad: needs partitioned storage (option dist_partitioned = 1)");

@@ -320,12 +320,44 @@ struct gps_handle_s {
   // ---- GPMC (gps_gpmc.hip): L = chol(K + jitter I) in dK / dLinv, V^T in dAlpha, G^T in dS2, U^T in dS3 (planes [k][pad(n)]) ----
   // valid while factor_gen still is what it was when gps_gpmc_lik_grad left them (gps_diag_gpmc_front times its kernels on them)
   struct GpmcState { bool have = false; unsigned long long gen = 0; i64 n = 0, k = 0; } gpmc;
+  // ---- Multiscale inducing features (multiscale.hip): the one-shot "feature scales" state ----
+  // gps_inducing_scales arms it; the next inducing-point entry consumes it (MsConsume, gps_inducing.hpp: while `consuming` the
+  // seams build Kuu / Kuf and take their VJPs with per-feature widths) and clears it at its end on every return path.  An entry
+  // that does not consume it refuses while it is armed (gps_ms_refuse).
+  struct MsState {
+    bool armed = false, consuming = false;
+    i64 m = 0, d_all = 0;
+    std::vector<double> scales;             // host copy [m, d_all] (the VJPs' host tails need the widths)
+    std::vector<double> grad;               // d / d scales [m, d_all] of the last consuming gradient entry (gps_inducing_scales_grad)
+    bool grad_valid = false;
+  } ms;
+  DevBuf dScales{bufs};                     // [m, d_all]
+  DevBuf dMsPrep{bufs};                     // ms_prep's planes: z, 1 / L, L^2 [m][nd] each, then log prod_d l_d / L_md [m]
+  DevBuf dMsPart{bufs};                     // the VJPs' per-chunk partials and their fold
 };
 
 static inline int gps_fail(gps_handle_t h, int code, const std::string& msg) {
   if (h) h->err = msg;
   return code;
 }
+
+// An entry that takes no inducing feature, reached while feature scales are armed: refuse (and disarm) rather than ignore them.
+static inline int gps_ms_refuse(gps_handle_t h, const char* who) {
+  if (!h || !h->ms.armed || h->ms.consuming) return GPS_OK;
+  h->ms.armed = false;
+  return gps_fail(h, GPS_ERR_UNSUPPORTED, std::string(who) + ": Multiscale feature scales are armed, and this entry takes no inducing feature");
+}
+
+// The entries that take Multiscale feature scales (gps_inducing_scales) hold one of these from their first line to their last: the
+// armed state is theirs while it lives (the seams of gps_inducing.hpp branch on `consuming`) and is cleared when it goes, on every return path.
+// (A gradient entry calls its bound's entry for the forward pass: the inner scope finds the state taken and leaves it alone.)
+struct MsConsume {
+  gps_handle_t h; bool outer;
+  explicit MsConsume(gps_handle_t h_) : h(h_), outer(h_ && !h_->ms.consuming) { if (outer) h->ms.consuming = h->ms.armed; }
+  ~MsConsume() { if (outer) { h->ms.armed = false; h->ms.consuming = false; } }
+  MsConsume(const MsConsume&) = delete;
+  MsConsume& operator=(const MsConsume&) = delete;
+};
 
 // forward: raise a kernel's dynamic-LDS limit once per handle (= per device; the attribute is per device, so a
 // process-wide flag would leave a second GPU of the same process at the 64 KB default)
@@ -690,6 +722,23 @@ int gps_launch_psi1_vjp_dense(gps_handle_t h, const PsiIn& in, const double* Y, 
                               i64 r, i64 n0, i64 n1, const double* Bar, i64 ldb, const double* BarT, i64 ldbt, double* out_n,
                               double* part_z, i64 nz, i64 zchunk, i64 ldz);
 int gps_launch_psi_fold(gps_handle_t h, const double* part, int nchunks, i64 rows, i64 cols, i64 ldp, double* out, i64 ldo);
+// multiscale.hip : Kuu, Kuf and their VJPs for Multiscale inducing features (features.py:89-150) -- an RBF kernel whose inducing
+// variable m has the width L_md = l_d + s_md in dimension d.  prog must be ONE GPS_K_RBF node (GPS_ERR_UNSUPPORTED otherwise); the
+// widths are the armed state's (h->dScales [m, d_all], h->ms.scales).  All matrix pointers on the device.
+//   kuu      dK [mp, mp] (leading dimension ldk) = Kuu + jitter I, both triangles, identity padded
+//   kuf      dst [prow, ldd] = Kuf^T zero padded (prow, ldd multiples of 64 covering n, m)
+//   kuf_vjp  from W [m][ldw] = Kuf_bar (columns < n): grad_slots [1 + n_dims] += , grad_Z [m, d_all] += (or nullptr), h->ms.grad +=
+//   kuu_vjp  from the symmetric W [m][ldw]: the same of c * sum_ij W_ij Kuu_ij
+// points per workgroup of the two VJPs (a multiple of 64) and the number of chunks, for n points against m features
+void gps_ms_chunking(i64 n, i64 m, i64* chunk, int* nchunks);
+int gps_launch_ms_kuu(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dZ, i64 m, i64 d_all, double jitter,
+                      double* dK, i64 ldk, i64 mp);
+int gps_launch_ms_kuf(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dZ, i64 m, const double* dXp, i64 n,
+                      i64 d_all, double* dst, i64 ldd, i64 prow);
+int gps_launch_ms_kuf_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dZ, i64 m, const double* dXp, i64 n,
+                          i64 d_all, const double* W, i64 ldw, double* grad_slots_host, double* grad_Z_host);
+int gps_launch_ms_kuu_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dZ, i64 m, i64 d_all,
+                          const double* W, i64 ldw, double c, double* grad_slots_host, double* grad_Z_host);
 // out [b][ldo] <- sum_{m, m'} psi2n_n[m][m'] W_b[m][m'] point by point, psi2n never stored: see psi.hip
 int gps_launch_psi2_contract(gps_handle_t h, const PsiIn& in, const double* W, i64 ldw, i64 sw, int b, double* PKW, i64 ldpk,
                              double* out, i64 ldo);

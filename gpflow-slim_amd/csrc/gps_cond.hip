@@ -70,6 +70,7 @@ extern "C" int gps_conditional(gps_handle_t h, const gps_kern_node_t* prog, int 
                                int64_t n_new, const double* f, int64_t k, const double* q_sqrt,
                                int q_sqrt_ndim, int white, int full_cov, double* fmean_out,
                                double* fvar_out, int* info) {
+  MsConsume ms_scope(h);                                 // (Multiscale feature scales, if armed, are this call's)
   return with_la_retry(h, [&]() -> int {
   if (!h || !Z || !Xnew || !f || !fmean_out || !fvar_out || m <= 0 || n_new <= 0 || k <= 0 || d_all <= 0)
     return gps_fail(h, GPS_ERR_ARG, "gps_conditional: bad argument");
@@ -143,6 +144,27 @@ extern "C" int gps_base_conditional(gps_handle_t h, const double* Kmn, const dou
   });
 }
 
+// Multiscale features (the armed scales belong to X = Z [n, d_all]): both VJPs of W [n, m] against Kuf (X2 = the points) or of
+// W [n, n], as given, against Kuu (X2 == NULL) in one pass -- the slots, d / d Z (or nullptr) and, into the handle's vector, d / d scales.
+static int ms_kmat_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Z, i64 n, const double* X2, i64 m,
+                       i64 d_all, const double* W, double* grad_slots, double* grad_Z) {
+  GPS_HIP(h, h->dXnew.ensure((size_t)n * d_all * 8));
+  GPS_HIP(h, hipMemcpyAsync(h->dXnew.p, Z, (size_t)n * d_all * 8, hipMemcpyHostToDevice, h->stream));
+  GPS_HIP(h, h->dTmp.ensure((size_t)n * m * 8));
+  std::fill(h->ms.grad.begin(), h->ms.grad.end(), 0.0);
+  if (X2) {
+    GPS_HIP(h, h->dTmp3.ensure((size_t)m * d_all * 8));
+    GPS_HIP(h, hipMemcpyAsync(h->dTmp3.p, X2, (size_t)m * d_all * 8, hipMemcpyHostToDevice, h->stream));
+    GPS_HIP(h, hipMemcpyAsync(h->dTmp.p, W, (size_t)n * m * 8, hipMemcpyHostToDevice, h->stream));
+    return gps_launch_ms_kuf_vjp(h, prog, n_nodes, h->dXnew.d(), n, h->dTmp3.d(), m, d_all, h->dTmp.d(), m, grad_slots, grad_Z);
+  }
+  std::vector<double> Ws((size_t)n * n);                 // sum_ij W_ij K_ij = 1/2 sum_ij (W + W^T)_ij K_ij
+  for (i64 i = 0; i < n; ++i) for (i64 j = 0; j < n; ++j) Ws[(size_t)i * n + j] = W[(size_t)i * n + j] + W[(size_t)j * n + i];
+  GPS_HIP(h, hipMemcpyAsync(h->dTmp.p, Ws.data(), (size_t)n * n * 8, hipMemcpyHostToDevice, h->stream));
+  GPS_HIP(h, hipStreamSynchronize(h->stream));
+  return gps_launch_ms_kuu_vjp(h, prog, n_nodes, h->dXnew.d(), n, d_all, h->dTmp.d(), n, 0.5, grad_slots, grad_Z);
+}
+
 // ---- vector-Jacobian product of kernels.K: grad_slots = sum_ij W[i][j] d k(X_i, X2_j) / d theta ---------------------------
 // (reverse-mode autodiff through kern.K(X, X2), kernels.py:408-439 / 1071-1084 / neural_kernel_network.py:41-47, for a
 // caller-supplied cotangent W host [n, m]; X2 == NULL: K(X, X), W [n, n] taken as given -- no symmetrisation.)
@@ -150,11 +172,16 @@ extern "C" int gps_kmat_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_n
                             const double* X2, int64_t m, int64_t d_all, const double* W, double* grad_slots,
                             int n_slots_cap, int* n_slots_out) {
   if (!h || !X || !W || !grad_slots || n <= 0 || d_all <= 0) return gps_fail(h, GPS_ERR_ARG, "gps_kmat_vjp: bad argument");
+  MsConsume ms_scope(h);
   GPS_HIP(h, hipSetDevice(h->device));
   if (!X2) m = n;
   int ns = 0;
   int rc = grad_slot_count(h, "gps_kmat_vjp", prog, n_nodes, n_slots_cap, n_slots_out, &ns);
   if (rc) return rc;
+  if (h->ms.consuming) {
+    for (int s = 0; s < ns; ++s) grad_slots[s] = 0.0;
+    return ms_kmat_vjp(h, prog, n_nodes, X, n, X2, m, d_all, W, grad_slots, nullptr);
+  }
   GPS_HIP(h, h->dXnew.ensure((size_t)n * d_all * 8));
   GPS_HIP(h, hipMemcpyAsync(h->dXnew.p, X, (size_t)n * d_all * 8, hipMemcpyHostToDevice, h->stream));
   const double* dX2 = nullptr;
@@ -176,8 +203,14 @@ extern "C" int gps_kmat_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_n
 extern "C" int gps_kmat_input_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n,
                                   const double* X2, int64_t m, int64_t d_all, const double* W, double* grad_X) {
   if (!h || !X || !W || !grad_X || n <= 0 || d_all <= 0) return gps_fail(h, GPS_ERR_ARG, "gps_kmat_input_vjp: bad argument");
+  MsConsume ms_scope(h);
   GPS_HIP(h, hipSetDevice(h->device));
   if (!X2) m = n;
+  if (h->ms.consuming) {
+    std::vector<double> slots(1 + GPS_MAX_DIMS, 0.0);
+    for (int64_t i = 0; i < n * d_all; ++i) grad_X[i] = 0.0;
+    return ms_kmat_vjp(h, prog, n_nodes, X, n, X2, m, d_all, W, slots.data(), grad_X);
+  }
   GPS_HIP(h, h->dXnew.ensure((size_t)n * d_all * 8));
   GPS_HIP(h, hipMemcpyAsync(h->dXnew.p, X, (size_t)n * d_all * 8, hipMemcpyHostToDevice, h->stream));
   const double* dX2 = nullptr;

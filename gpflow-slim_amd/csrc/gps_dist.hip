@@ -27,6 +27,7 @@
 extern "C" int gps_dist_begin(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double noise_var,
                               const double* resid, int64_t r, int nparts, int part, int64_t nb,
                               int64_t* n_panels, int64_t* msg_doubles_max) {
+  if (int rf = gps_ms_refuse(h, "gps_dist_begin")) return rf;
   if (!h || nparts <= 0 || part < 0 || part >= nparts || nb <= 0 || nb % GPS_TILE || r < 0 || r > GPS_TILE || (r > 0 && !resid))
     return gps_fail(h, GPS_ERR_ARG, "gps_dist_begin: bad argument (at most 128 outputs)");
   if (h->n <= 0) return gps_fail(h, GPS_ERR_STATE, "gps_gpr_set_data has not been called");
@@ -303,6 +304,7 @@ static int dist_own_comm_bufs(gps_handle_t h, int count, const char* fail) {
 
 extern "C" int gps_dist_lml(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double noise_var, const double* resid,
                             int64_t r, int64_t nb, int lookahead, int exchange_mode, double* lml, int* info) {
+  if (int rf = gps_ms_refuse(h, "gps_dist_lml")) return rf;
   if (!h || !lml) return gps_fail(h, GPS_ERR_ARG, "gps_dist_lml: bad argument");
   if (!h->comm) return gps_fail(h, GPS_ERR_STATE, "gps_dist_lml: the handle has no communicator (gps_comm_init)");
   if (h->ext_stream) return gps_fail(h, GPS_ERR_STATE, "gps_dist_lml: an external stream is installed (gps_set_stream)");
@@ -346,6 +348,7 @@ extern "C" int gps_dist_lml(gps_handle_t h, const gps_kern_node_t* prog, int n_n
 //                     all:   gps_dist_solve_apply(j, buf)
 //   gps_dist_solve_finish(mean, var)     fmean = A^T alpha ; fvar = Kdiag - rowsum((A^T)^2)   (full_cov == 0)
 extern "C" int gps_dist_solve_begin(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Xnew, int64_t n_new) {
+  if (int rf = gps_ms_refuse(h, "gps_dist_solve_begin")) return rf;
   if (!h || !Xnew || n_new <= 0) return gps_fail(h, GPS_ERR_ARG, "gps_dist_solve_begin: bad argument");
   if (!h->dist.have_part_factor || h->dist.nb <= 0) return gps_fail(h, GPS_ERR_STATE, "gps_dist_solve_begin: no partitioned factor (run the distributed factorisation first)");
   GPS_HIP(h, hipSetDevice(h->device));
@@ -409,6 +412,7 @@ extern "C" int gps_dist_solve_finish(gps_handle_t h, const gps_kern_node_t* prog
 // still takes part in the exchanges).
 extern "C" int gps_dist_predict(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* Xnew, int64_t n_new,
                                 int exchange_mode, double* mean_out, double* var_out) {
+  if (int rf = gps_ms_refuse(h, "gps_dist_predict")) return rf;
   if (!h || n_new < 0 || (n_new > 0 && (!Xnew || !var_out))) return gps_fail(h, GPS_ERR_ARG, "gps_dist_predict: bad argument");
   if (!h->comm) return gps_fail(h, GPS_ERR_STATE, "gps_dist_predict: the handle has no communicator (gps_comm_init)");
   if (!h->dist.have_part_factor || h->dist.nb <= 0) return gps_fail(h, GPS_ERR_STATE, "gps_dist_predict: no partitioned factor (gps_dist_lml first)");

@@ -8,10 +8,36 @@ extern "C" int gps_kmat(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes
                         int64_t n, const double* X2, int64_t m, int64_t d_all, double diag_add,
                         double* K_out) {
   if (!h || !X || !K_out || n < 0 || d_all <= 0) return gps_fail(h, GPS_ERR_ARG, "gps_kmat: bad argument");
+  MsConsume ms_scope(h);
   GPS_HIP(h, hipSetDevice(h->device));
   const bool sym = (X2 == nullptr);
   if (sym) m = n;
   if (n == 0 || m == 0) return GPS_OK;
+  if (h->ms.consuming) {
+    // Multiscale features (the armed scales belong to X = Z): Kuu + diag_add I [n, n], or Kuf [n, m] against the points X2
+    const i64 zp = gps_pad(n), pp = gps_pad(m);
+    GPS_HIP(h, h->dXnew.ensure((size_t)n * d_all * 8));
+    GPS_HIP(h, hipMemcpyAsync(h->dXnew.p, X, (size_t)n * d_all * 8, hipMemcpyHostToDevice, h->stream));
+    GPS_HIP(h, h->dTmp2.ensure((size_t)n * m * 8));
+    int rm;
+    if (sym) {
+      GPS_HIP(h, h->dTmp.ensure((size_t)zp * zp * 8));
+      rm = gps_launch_ms_kuu(h, prog, n_nodes, h->dXnew.d(), n, d_all, diag_add, h->dTmp.d(), zp, zp);
+      if (rm) return rm;
+      rm = gps_launch_extract(h, h->dTmp.d(), zp, n, n, h->dTmp2.d(), n, 0);
+    } else {
+      GPS_HIP(h, h->dTmp3.ensure((size_t)m * d_all * 8));
+      GPS_HIP(h, hipMemcpyAsync(h->dTmp3.p, X2, (size_t)m * d_all * 8, hipMemcpyHostToDevice, h->stream));
+      GPS_HIP(h, h->dTmp.ensure((size_t)pp * zp * 8));
+      rm = gps_launch_ms_kuf(h, prog, n_nodes, h->dXnew.d(), n, h->dTmp3.d(), m, d_all, h->dTmp.d(), zp, pp);
+      if (rm) return rm;
+      rm = gps_launch_transpose(h, h->dTmp.d(), zp, m, n, h->dTmp2.d(), m);
+    }
+    if (rm) return rm;
+    GPS_HIP(h, hipMemcpyAsync(K_out, h->dTmp2.p, (size_t)n * m * 8, hipMemcpyDeviceToHost, h->stream));
+    GPS_HIP(h, hipStreamSynchronize(h->stream));
+    return GPS_OK;
+  }
   const i64 prow = ((n + 63) / 64) * 64;
   const i64 pcol = sym ? prow : ((m + 63) / 64) * 64;
   GPS_HIP(h, h->dXnew.ensure((size_t)n * d_all * 8));
@@ -117,6 +143,7 @@ extern "C" int gps_trsm_lower(gps_handle_t h, const double* L, int64_t n, double
 
 // ---- GPR ------------------------------------------------------------------------------------------------
 extern "C" int gps_gpr_set_data(gps_handle_t h, const double* X, int64_t n, int64_t d_all) {
+  if (int rf = gps_ms_refuse(h, "gps_gpr_set_data")) return rf;
   if (!h || !X || n <= 0 || d_all <= 0) return gps_fail(h, GPS_ERR_ARG, "gps_gpr_set_data: bad argument");
   GPS_HIP(h, hipSetDevice(h->device));
   drop_resident_factors(h);
@@ -344,6 +371,7 @@ static int gpr_factor(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, 
 
 extern "C" int gps_gpr_lml(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, double noise_var,
                            const double* resid, int64_t r, double* lml, int* info) {
+  if (int rf = gps_ms_refuse(h, "gps_gpr_lml")) return rf;
   return with_la_retry(h, [&]() -> int {
   if (!h || !lml) return gps_fail(h, GPS_ERR_ARG, "gps_gpr_lml: bad argument");
   GPS_HIP(h, hipSetDevice(h->device));
@@ -566,6 +594,7 @@ extern "C" int gps_gpr_lml_grad(gps_handle_t h, const gps_kern_node_t* prog, int
                                 const double* resid, int64_t r, double* lml, double* grad_slots,
                                 int n_slots_cap, int* n_slots_out, double* grad_noise, double* kinv_resid,
                                 int* info) {
+  if (int rf = gps_ms_refuse(h, "gps_gpr_lml_grad")) return rf;
   if (!h || !lml || !grad_slots || !grad_noise || r <= 0)
     return gps_fail(h, GPS_ERR_ARG, "gps_gpr_lml_grad: bad argument");
   return gpr_lml_grad_body(h, prog, n_nodes, noise_var, resid, r, lml, grad_slots, n_slots_cap, n_slots_out, grad_noise, kinv_resid,
@@ -577,6 +606,7 @@ extern "C" int gps_gpr_lml_grad_x(gps_handle_t h, const gps_kern_node_t* prog, i
                                   const double* resid, int64_t r, double* lml, double* grad_slots,
                                   int n_slots_cap, int* n_slots_out, double* grad_noise, double* kinv_resid,
                                   double* grad_X, int* info) {
+  if (int rf = gps_ms_refuse(h, "gps_gpr_lml_grad_x")) return rf;
   if (!h || !lml || !grad_slots || !grad_noise || !grad_X || r <= 0)
     return gps_fail(h, GPS_ERR_ARG, "gps_gpr_lml_grad_x: bad argument");
   if (h->d_all > GPS_MAX_DIMS)
@@ -617,6 +647,7 @@ extern "C" int gps_gpr_predict(gps_handle_t h, const gps_kern_node_t* prog, int 
                                double noise_var, const double* resid, int64_t r, const double* Xnew,
                                int64_t n_new, int full_cov, int refactor, double* mean_out,
                                double* var_out, int* info) {
+  if (int rf = gps_ms_refuse(h, "gps_gpr_predict")) return rf;
   return with_la_retry(h, [&]() -> int {
   if (!h || !Xnew || n_new <= 0 || !var_out || (r > 0 && !mean_out))
     return gps_fail(h, GPS_ERR_ARG, "gps_gpr_predict: bad argument");

@@ -9,6 +9,8 @@
 // ---- start of a call and set-up ---------------------------------------------------------------------------------------
 // Every entry that builds Kuu into the handle's dK / dLinv starts here: the resident GPR factor and data are gone after it.
 static int begin_inducing_call(gps_handle_t h, int* info) {
+  int rf = gps_ms_refuse(h, "this entry");                      // (armed feature scales and no MsConsume: not an entry that takes them)
+  if (rf) return rf;
   GPS_HIP(h, hipSetDevice(h->device));
   drop_resident_factors(h); h->n = 0;
   h->refine_now = (h->leaf_refine != 0);
@@ -38,11 +40,13 @@ static int inducing_upload(gps_handle_t h, const double* Z, i64 m, const double*
 // dK = K(Z) + jitter I, lower triangle, identity padded            (features.py:74-77 / conditionals.py:60)
 static int inducing_kuu(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 m, i64 d_all, double jitter) {
   const i64 mp = gps_pad(m);
+  if (h->ms.consuming) return gps_launch_ms_kuu(h, prog, n_nodes, h->dX.d(), m, d_all, jitter, h->dK.d(), mp, mp);
   return gps_launch_kmat(h, prog, n_nodes, h->dX.d(), m, nullptr, m, d_all, jitter, h->dK.d(), mp, mp, mp, 1, 1);
 }
 // dst [pad(n), mp] = K(dXnew, Z) = Kuf^T zero padded              (features.py:79-81)
 static int inducing_kuf(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 n, i64 m, i64 d_all, double* dst) {
   const i64 mp = gps_pad(m);
+  if (h->ms.consuming) return gps_launch_ms_kuf(h, prog, n_nodes, h->dX.d(), m, h->dXnew.d(), n, d_all, dst, mp, gps_pad(n));
   return gps_launch_kmat(h, prog, n_nodes, h->dXnew.d(), n, h->dX.d(), m, d_all, 0.0, dst, mp, gps_pad(n), mp, 0, 0);
 }
 // sizes dK / dLinv / dB for m inducing and n other points and k latents; Knn is left to the caller
@@ -102,6 +106,8 @@ static int upper_factor(gps_handle_t h, const double* L, i64 mp, double* U) {
 // (only a negative zero would come out as +0).
 static int kuu_side_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, i64 m, i64 d_all, const double* Kbar2, i64 mp, int ns,
                         double* grad_slots, double* grad_Z) {
+  if (h->ms.consuming)          // (the same convention: c = 1/2 on the full symmetric matrix, both arguments move)
+    return gps_launch_ms_kuu_vjp(h, prog, n_nodes, h->dX.d(), m, d_all, Kbar2, mp, 0.5, grad_slots, grad_Z);
   std::vector<double> uu((size_t)ns, 0.0);
   int rc = gps_launch_kmat_vjp(h, prog, n_nodes, h->dX.d(), m, nullptr, 0, d_all, Kbar2, mp, 0, uu.data());
   if (rc) return rc;
@@ -422,12 +428,19 @@ static int inducing_backward(gps_handle_t h, Blocked<HipOps>& bl, const Inducing
   if (rc) return rc;
   // contractions with the kernel derivatives: the Kuf side, the Kuu side, Kdiag -- each sum in that order
   for (int sI = 0; sI < ns; ++sI) g.grad_slots[sI] = 0.0;
-  rc = gps_launch_kmat_vjp(h, g.prog, g.n_nodes, h->dX.d(), m, h->dXnew.d(), n, d_all, KufBar, np, 0, g.grad_slots);
-  if (rc) return rc;
-  if (g.grad_Z) {
-    for (i64 i = 0; i < m * d_all; ++i) g.grad_Z[i] = 0.0;
-    rc = gps_launch_kmat_input_vjp(h, g.prog, g.n_nodes, h->dX.d(), m, h->dXnew.d(), n, d_all, KufBar, np, 1.0, g.grad_Z);
+  if (h->ms.consuming) {        // Multiscale features: one pass gives the slots, Z and the scales (into the handle's vector)
+    if (g.grad_Z) for (i64 i = 0; i < m * d_all; ++i) g.grad_Z[i] = 0.0;
+    std::fill(h->ms.grad.begin(), h->ms.grad.end(), 0.0);
+    rc = gps_launch_ms_kuf_vjp(h, g.prog, g.n_nodes, h->dX.d(), m, h->dXnew.d(), n, d_all, KufBar, np, g.grad_slots, g.grad_Z);
     if (rc) return rc;
+  } else {
+    rc = gps_launch_kmat_vjp(h, g.prog, g.n_nodes, h->dX.d(), m, h->dXnew.d(), n, d_all, KufBar, np, 0, g.grad_slots);
+    if (rc) return rc;
+    if (g.grad_Z) {
+      for (i64 i = 0; i < m * d_all; ++i) g.grad_Z[i] = 0.0;
+      rc = gps_launch_kmat_input_vjp(h, g.prog, g.n_nodes, h->dX.d(), m, h->dXnew.d(), n, d_all, KufBar, np, 1.0, g.grad_Z);
+      if (rc) return rc;
+    }
   }
   rc = kuu_side_vjp(h, g.prog, g.n_nodes, m, d_all, Kbar2, mp, ns, g.grad_slots, g.grad_Z);
   if (rc) return rc;

@@ -170,6 +170,7 @@ extern "C" int gps_sgpr(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes
                         const double* X, int64_t n, int64_t d_all, double jitter, double noise_var,
                         const double* resid, int64_t r, const double* Xnew, int64_t n_new, int full_cov,
                         double* bound_out, double* mean_out, double* var_out, int* info) {
+  MsConsume ms_scope(h);                                 // (Multiscale feature scales, if armed, are this call's)
   return with_la_retry(h, [&]() -> int {
   return sparse_gpr_impl(h, 0, prog, n_nodes, Z, m, X, n, d_all, jitter, noise_var, resid, r, Xnew, n_new, full_cov,
                          bound_out, mean_out, var_out, info);
@@ -180,6 +181,7 @@ extern "C" int gps_fitc(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes
                         const double* X, int64_t n, int64_t d_all, double jitter, double noise_var,
                         const double* resid, int64_t r, const double* Xnew, int64_t n_new, int full_cov,
                         double* bound_out, double* mean_out, double* var_out, int* info) {
+  MsConsume ms_scope(h);                                 // (Multiscale feature scales, if armed, are this call's)
   return with_la_retry(h, [&]() -> int {
   return sparse_gpr_impl(h, 1, prog, n_nodes, Z, m, X, n, d_all, jitter, noise_var, resid, r, Xnew, n_new, full_cov,
                          bound_out, mean_out, var_out, info);
@@ -282,6 +284,7 @@ extern "C" int gps_sgpr_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_
                              const double* X, int64_t n, int64_t d_all, double jitter, double noise_var,
                              const double* resid, int64_t r, double* bound, double* grad_slots, int n_slots_cap,
                              int* n_slots_out, double* grad_noise, double* grad_mean, double* grad_Z, int* info) {
+  MsConsume ms_scope(h);                                 // (Multiscale feature scales, if armed, are this call's)
   return with_la_retry(h, [&]() -> int { return sgpr_grad_body(h, prog, n_nodes, Z, m, X, n, d_all, jitter, noise_var, resid, r, bound, grad_slots, n_slots_cap, n_slots_out, grad_noise, grad_mean, grad_Z, info); });
 }
 
@@ -391,6 +394,7 @@ extern "C" int gps_fitc_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_
                              const double* X, int64_t n, int64_t d_all, double jitter, double noise_var,
                              const double* resid, int64_t r, double* bound, double* grad_slots, int n_slots_cap,
                              int* n_slots_out, double* grad_noise, double* grad_mean, double* grad_Z, int* info) {
+  MsConsume ms_scope(h);                                 // (Multiscale feature scales, if armed, are this call's)
   return with_la_retry(h, [&]() -> int { return fitc_grad_body(h, prog, n_nodes, Z, m, X, n, d_all, jitter, noise_var, resid, r, bound, grad_slots, n_slots_cap, n_slots_out, grad_noise, grad_mean, grad_Z, info); });
 }
 

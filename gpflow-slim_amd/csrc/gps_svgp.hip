@@ -131,6 +131,7 @@ extern "C" int gps_svgp_elbo(gps_handle_t h, const gps_kern_node_t* prog, int n_
                              const double* q_mu, int64_t k, const double* q_sqrt, int q_sqrt_ndim, int white,
                              double noise_var, double scale, double* elbo, double* kl_out, double* var_exp_sum,
                              int* info) {
+  MsConsume ms_scope(h);                                 // (Multiscale feature scales, if armed, are this call's)
   return with_la_retry(h, [&]() -> int {
   if (!h || !Z || !X || !yres || !q_mu || !q_sqrt || !elbo || m <= 0 || n <= 0 || k <= 0 || d_all <= 0 || !(noise_var > 0.0))
     return gps_fail(h, GPS_ERR_ARG, "gps_svgp_elbo: bad argument");
@@ -155,6 +156,7 @@ extern "C" int gps_svgp_elbo_lik(gps_handle_t h, const gps_kern_node_t* prog, in
                                  int64_t d_all, double jitter, const double* X, int64_t n, const double* Y, const double* mean,
                                  const double* q_mu, int64_t k, const double* q_sqrt, int q_sqrt_ndim, int white,
                                  const gps_lik_t* lik, double scale, double* elbo, double* kl_out, double* var_exp_sum, int* info) {
+  MsConsume ms_scope(h);                                 // (Multiscale feature scales, if armed, are this call's)
   return with_la_retry(h, [&]() -> int {
   if (!h || !Z || !X || !Y || !q_mu || !q_sqrt || !lik || !elbo || m <= 0 || n <= 0 || k <= 0 || d_all <= 0)
     return gps_fail(h, GPS_ERR_ARG, "gps_svgp_elbo_lik: bad argument");
@@ -497,6 +499,7 @@ extern "C" int gps_svgp_elbo_grad(gps_handle_t h, const gps_kern_node_t* prog, i
                                   double noise_var, double scale, double* elbo, double* grad_slots, int n_slots_cap,
                                   int* n_slots_out, double* grad_noise, double* grad_q_mu, double* grad_q_sqrt,
                                   double* grad_mean, double* grad_Z, int* info) {
+  MsConsume ms_scope(h);                                 // (Multiscale feature scales, if armed, are this call's)
   return with_la_retry(h, [&]() -> int { return svgp_elbo_grad_body(h, prog, n_nodes, Z, m, d_all, jitter, X, n, yres, q_mu, k, q_sqrt, q_sqrt_ndim, white, noise_var, scale, elbo, grad_slots, n_slots_cap, n_slots_out, grad_noise, grad_q_mu, grad_q_sqrt, grad_mean, grad_Z, info); });
 }
 
@@ -626,5 +629,6 @@ extern "C" int gps_svgp_elbo_lik_grad(gps_handle_t h, const gps_kern_node_t* pro
                                       const gps_lik_t* lik, double scale, double* elbo, double* grad_slots, int n_slots_cap,
                                       int* n_slots_out, double* grad_lik, double* grad_q_mu, double* grad_q_sqrt,
                                       double* grad_mean, double* grad_Z, int* info) {
+  MsConsume ms_scope(h);                                 // (Multiscale feature scales, if armed, are this call's)
   return with_la_retry(h, [&]() -> int { return svgp_elbo_lik_grad_body(h, prog, n_nodes, Z, m, d_all, jitter, X, n, Y, mean, q_mu, k, q_sqrt, q_sqrt_ndim, white, lik, scale, elbo, grad_slots, n_slots_cap, n_slots_out, grad_lik, grad_q_mu, grad_q_sqrt, grad_mean, grad_Z, info); });
 }

@@ -192,6 +192,15 @@ def psi_sum_chunking(n, m, opt=0):
     return ch, -(-n // ch)
 
 
+def ms_chunking(n, m):
+    """(points per chunk, chunks) of the Multiscale VJP kernels for n points against m inducing features
+    (csrc/multiscale.hip: gps_ms_chunking)."""
+    mt = -(-m // 64)
+    nc = max(min(-(-2048 // mt), -(-n // 64)), 1)
+    chunk = 64 * -(-n // (64 * nc))
+    return chunk, -(-n // chunk)
+
+
 def grad_x_slicing(n):
     """(32-row blocks, slices of the column tiles, column tiles per slice) of the walk that d LML / d X makes over the padded
     square of n points: workgroup (block, slice) owns 32 rows and `per` 32-column tiles  (csrc/grad_x.hip: gps_grad_x_slicing;
@@ -243,6 +252,8 @@ _SIGNATURES = {
     "gps_sgpmc_lik_grad": _SVGP + [_dp, _dp, _dp, _i64, _lik, _i64, _dp, _dp, _int, _ip, _dp, _dp, _dp, _dp, _ip],
     "gps_kmat_vjp": [_vp, _prog, _int, _dp, _i64, _dp, _i64, _i64, _dp, _dp, _int, _ip],
     "gps_kmat_input_vjp": [_vp, _prog, _int, _dp, _i64, _dp, _i64, _i64, _dp, _dp],
+    "gps_inducing_scales": [_vp, _dp, _i64, _i64],
+    "gps_inducing_scales_grad": [_vp, _dp, _i64, _i64],
     "gps_gauss_kl": [_vp, _dp, _i64, _dp, _i64, _dp, _int, _dp, _ip],
     "gps_sgpr": _SPARSE + [_dp, _i64, _int, _dp, _dp, _dp, _ip],
     "gps_sgpr_grad": _SPARSE + [_dp, _dp, _int, _ip, _dp, _dp, _dp, _ip],

@@ -16,7 +16,7 @@ from ._abi import (GPS_MAX_DIMS, GPS_MAX_NODES, GPS_MAX_STACK,                  
                    K_SQDIST, K_EUCLID, K_RATQUAD, K_LINEAR, K_POLYNOMIAL, K_COSINE, K_ARCCOSINE, K_ADD, K_MUL, K_COREGION,
                    K_NKN_LINROW, K_NKN_PRODUCT, K_NKN_ACT, KernNode, LikDesc, RffDesc,
                    RFF_RBF, RFF_LINEAR, RFF_CONSTANT, RFF_EXPLICIT, LIK_MAX_GH, LIK_MAX_EDGES, LIK_MULTICLASS, LIK_ORDINAL,
-                   make_rff, make_lik, make_program, primitive_node, coregion_node, op_node, psi2_chunking, psi_sum_chunking, grad_x_slicing,
+                   make_rff, make_lik, make_program, primitive_node, coregion_node, op_node, psi2_chunking, psi_sum_chunking, ms_chunking, grad_x_slicing,
                    _SIGNATURES, EXPORTED_SYMBOLS, ALLREDUCE_FN, _c_double_p, _c_int_p, _i64,
                    lib_path, load_library, comm_load, comm_unique_id, comm_version)
 
@@ -673,8 +673,9 @@ class Handle(object):
         return mean
 
     # ---- SGPR
-    def sgpr(self, prog, Z, X, resid, jitter, noise_var, Xnew=None, full_cov=False, want_bound=True, fitc=False):
-        """gps_sgpr (Titsias bound) or, with fitc=True, gps_fitc (Snelson & Ghahramani)."""
+    def sgpr(self, prog, Z, X, resid, jitter, noise_var, Xnew=None, full_cov=False, want_bound=True, fitc=False, scales=None):
+        """gps_sgpr (Titsias bound) or, with fitc=True, gps_fitc (Snelson & Ghahramani); scales [M, D]: Z are Multiscale
+        features of these widths."""
         Z, X, resid = _f64(Z), _f64(X), _f64(resid)
         m, d = Z.shape
         n, r = resid.shape
@@ -687,15 +688,17 @@ class Handle(object):
         if Xnew is not None and n_new == 0:
             return 0.0, mean, var
         self._drop_resident()
+        self._arm_scales(scales, Z)
         self._call("gps_fitc" if fitc else "gps_sgpr", prog, len(prog), _ptr(Z), m, _ptr(X), n, d, float(jitter),
                    float(noise_var), _ptr(resid), r, xp, n_new, 1 if full_cov else 0, _byref(bound) if want_bound else None,
                    mp_, vp, _byref(info))
         _raise_if_not_pd(info, _PD_ORDER)
         return bound.value, mean, var
 
-    def sgpr_grad(self, prog, Z, X, resid, jitter, noise_var, want_grad_Z=True, fitc=False):
+    def sgpr_grad(self, prog, Z, X, resid, jitter, noise_var, want_grad_Z=True, fitc=False, scales=None):
         """(bound, grad_slots, grad_noise, d/d mean(X) [N, R], grad_Z [M, D] or None) of the SGPR bound -- gps_sgpr_grad -- or,
-        with fitc=True, of the FITC log-likelihood -- gps_fitc_grad; gradients with respect to the constrained values."""
+        with fitc=True, of the FITC log-likelihood -- gps_fitc_grad; gradients with respect to the constrained values.  scales
+        (Multiscale features): one more item at the end, grad_scales [M, D]."""
         Z, X, resid = _f64(Z), _f64(X), _f64(resid)
         m, d = Z.shape
         n, r = resid.shape
@@ -705,11 +708,13 @@ class Handle(object):
         g_mean = np.zeros((n, r))
         g_Z = np.zeros((m, d))
         self._drop_resident()
+        armed = self._arm_scales(scales, Z)
         self._call("gps_fitc_grad" if fitc else "gps_sgpr_grad", prog, len(prog), _ptr(Z), m, _ptr(X), n, d, float(jitter),
                    float(noise_var), _ptr(resid), r, _byref(bound), _ptr(slots), SLOT_CAP, _byref(ns), _byref(gnoise),
                    _ptr(g_mean), _ptr(g_Z) if want_grad_Z else None, _byref(info))
         _raise_if_not_pd(info, _PD_ORDER)
-        return bound.value, slots[:ns.value].copy(), gnoise.value, g_mean, (g_Z if want_grad_Z else None)
+        out = (bound.value, slots[:ns.value].copy(), gnoise.value, g_mean, (g_Z if want_grad_Z else None))
+        return out + (self._scales_grad(m, d),) if armed else out
 
     def sparse_last_terms(self):
         """sum log diag LB, tr(A A^T), sum c^2, Kdiag constant, sum log nu of the last sgpr() call."""
@@ -854,6 +859,54 @@ class Handle(object):
         self._check(self._lib.gps_allreduce_doubles(int(m), int(r), _byref(out)), "gps_allreduce_doubles")   # (takes no handle)
         return out.value
 
+    # ---- Multiscale inducing features (features.Multiscale): the one-shot feature scales of the next inducing-point entry
+    def _arm_scales(self, scales, Z):
+        """gps_inducing_scales: the widths [M, D] of a Multiscale feature for the entry called next (the library clears them when
+        that entry returns, whatever it returns).  scales None: nothing happens."""
+        if scales is None:
+            return False
+        scales = _f64(scales)
+        _need(scales.shape == Z.shape, "the scales of a Multiscale feature must have the shape of Z")
+        self._call("gps_inducing_scales", _ptr(scales), Z.shape[0], Z.shape[1])
+        return True
+
+    def _scales_grad(self, m, d):
+        """gps_inducing_scales_grad: d / d scales [M, D] of the gradient entry that just consumed the armed scales."""
+        out = np.zeros((m, d))
+        self._call("gps_inducing_scales_grad", _ptr(out), m, d)
+        return out
+
+    def _ms_kmat(self, prog, Z, scales, X2=None, jitter=0.0):
+        """Kuu + jitter I [M, M] (X2 None) or Kuf [M, N] against the points X2 of a Multiscale feature (features.py:123-147)."""
+        Z = _f64(Z)
+        m, d = Z.shape
+        if X2 is not None:
+            X2 = _f64(X2)
+            _need(X2.ndim == 2 and X2.shape[1] == d, "X2 must be [N, %d]" % d)
+        out = np.empty((m, m if X2 is None else X2.shape[0]))
+        if out.size == 0:
+            return out
+        self._arm_scales(scales, Z)
+        self._call("gps_kmat", prog, len(prog), _ptr(Z), m, _opt(X2), 0 if X2 is None else X2.shape[0], d, float(jitter), _ptr(out))
+        return out
+
+    def _ms_kmat_vjp(self, prog, Z, scales, W, X2=None):
+        """(grad_slots, grad_Z [M, D], grad_scales [M, D]) of sum_ij W_ij K_ij for K = Kuf (W [M, N], X2 the points) or
+        K = Kuu (W [M, M] as given, X2 None) of a Multiscale feature."""
+        Z, W = _f64(Z), _f64(W)
+        m, d = Z.shape
+        if X2 is not None:
+            X2 = _f64(X2)
+        nc = m if X2 is None else X2.shape[0]
+        _need(W.shape == (m, nc), "W must be [M, N]")
+        slots, ns = self._slot_buffer()
+        g_Z = np.zeros((m, d))
+        self._arm_scales(scales, Z)
+        self._call("gps_kmat_vjp", prog, len(prog), _ptr(Z), m, _opt(X2), nc, d, _ptr(W), _ptr(slots), SLOT_CAP, _byref(ns))
+        self._arm_scales(scales, Z)
+        self._call("gps_kmat_input_vjp", prog, len(prog), _ptr(Z), m, _opt(X2), nc, d, _ptr(W), _ptr(g_Z))
+        return slots[:ns.value].copy(), g_Z, self._scales_grad(m, d)
+
     # ---- conditionals, SVGP
     @staticmethod
     def _prep_q_sqrt(q_sqrt):
@@ -882,7 +935,8 @@ class Handle(object):
         fvar = np.empty((k, n_new, n_new) if full_cov else (n_new, k))
         return fmean, fvar
 
-    def conditional(self, prog, Z, Xnew, f, jitter, q_sqrt=None, white=False, full_cov=False):
+    def conditional(self, prog, Z, Xnew, f, jitter, q_sqrt=None, white=False, full_cov=False, scales=None):
+        """gps_conditional; scales [M, D]: Z are Multiscale features of these widths (features.Multiscale)."""
         Z, Xnew, f = _f64(Z), _f64(Xnew), _f64(f)
         m, d = Z.shape
         _need(Xnew.ndim == 2 and Xnew.shape[1] == d, "Xnew must be [N*, %d]" % d)
@@ -895,6 +949,7 @@ class Handle(object):
             return fmean, (np.empty((0, 0, k)) if full_cov else fvar)
         info = ctypes.c_int(0)
         self._drop_resident()
+        self._arm_scales(scales, Z)
         self._call("gps_conditional", prog, len(prog), _ptr(Z), m, d, float(jitter), _ptr(Xnew), n_new, _ptr(f), k, _opt(q), qnd,
                    1 if white else 0, 1 if full_cov else 0, _ptr(fmean), _ptr(fvar), _byref(info))
         _raise_if_not_pd(info, _PD_ORDER)
@@ -939,23 +994,25 @@ class Handle(object):
         self._check_q_sqrt(q, qnd, m, k)
         return Z, X, q_mu, q, qnd, m, d, n, k
 
-    def svgp_elbo(self, prog, Z, X, yres, q_mu, q_sqrt, jitter, noise_var, white=True, scale=1.0):
+    def svgp_elbo(self, prog, Z, X, yres, q_mu, q_sqrt, jitter, noise_var, white=True, scale=1.0, scales=None):
         """(elbo, kl, sum of variational expectations) of models/svgp.py:108-125 for the Gaussian likelihood."""
         Z, X, q_mu, q, qnd, m, d, n, k = self._svgp_args(Z, X, q_mu, q_sqrt)
         yres = _f64(yres)
         _need(yres.shape == (n, k), "Y - mean must be [N, K] with K = number of latent functions")
         elbo, kl, ve, info = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0), ctypes.c_int(0)
         self._drop_resident()
+        self._arm_scales(scales, Z)
         self._call("gps_svgp_elbo", prog, len(prog), _ptr(Z), m, d, float(jitter), _ptr(X), n, _ptr(yres), _ptr(q_mu), k,
                    _ptr(q), qnd, 1 if white else 0, float(noise_var), float(scale), _byref(elbo), _byref(kl), _byref(ve),
                    _byref(info))
         _raise_if_not_pd(info, _PD_KUU)
         return elbo.value, kl.value, ve.value
 
-    def svgp_elbo_grad(self, prog, Z, X, yres, q_mu, q_sqrt, jitter, noise_var, white=True, scale=1.0, want_grad_Z=False):
+    def svgp_elbo_grad(self, prog, Z, X, yres, q_mu, q_sqrt, jitter, noise_var, white=True, scale=1.0, want_grad_Z=False,
+                       scales=None):
         """(elbo, grad_slots, grad_noise, grad_q_mu [M, K], grad_q_sqrt shaped like q_sqrt, d/d mean(X) [N, K]) -- gradients
         w.r.t. the constrained values, either parametrisation (gps_svgp_elbo_grad); want_grad_Z: a seventh item, the gradient
-        with respect to the inducing inputs [M, D]."""
+        with respect to the inducing inputs [M, D]; scales (Multiscale features): one more item at the end, grad_scales [M, D]."""
         Z, X, q_mu, q, qnd, m, d, n, k = self._svgp_args(Z, X, q_mu, q_sqrt)
         yres = _f64(yres)
         _need(yres.shape == (n, k), "Y - mean must be [N, K] with K = number of latent functions")
@@ -963,13 +1020,15 @@ class Handle(object):
         slots, ns = self._slot_buffer()
         g_qmu, g_q, g_mean, g_Z = np.zeros((m, k)), np.zeros_like(q), np.zeros((n, k)), np.zeros((m, d))
         self._drop_resident()
+        armed = self._arm_scales(scales, Z)
         self._call("gps_svgp_elbo_grad", prog, len(prog), _ptr(Z), m, d, float(jitter), _ptr(X), n, _ptr(yres), _ptr(q_mu), k,
                    _ptr(q), qnd, 1 if white else 0, float(noise_var), float(scale), _byref(elbo), _ptr(slots), SLOT_CAP,
                    _byref(ns), _byref(gnoise), _ptr(g_qmu), _ptr(g_q), _ptr(g_mean), _ptr(g_Z) if want_grad_Z else None,
                    _byref(info))
         _raise_if_not_pd(info, _PD_KUU)
         out = (elbo.value, slots[:ns.value].copy(), gnoise.value, g_qmu, self._q_sqrt_grad(g_q, qnd), g_mean)
-        return out + (g_Z,) if want_grad_Z else out
+        out = out + (g_Z,) if want_grad_Z else out
+        return out + (self._scales_grad(m, d),) if armed else out
 
     def lik_varexp(self, lik, Fmu, Fvar, Y, want_grad=False):
         """Sum over points and latents of the variational expectations of a device likelihood (``lik`` from make_lik) for
@@ -1006,33 +1065,37 @@ class Handle(object):
             mean = _f64(np.broadcast_to(mean, (n, k)))
         return desc, Z, X, Y, mean, q_mu, q, qnd, m, d, n, k
 
-    def svgp_elbo_lik(self, prog, Z, X, Y, q_mu, q_sqrt, jitter, lik, mean=None, white=True, scale=1.0):
+    def svgp_elbo_lik(self, prog, Z, X, Y, q_mu, q_sqrt, jitter, lik, mean=None, white=True, scale=1.0, scales=None):
         """(elbo, kl, sum of variational expectations) of models/svgp.py:108-125 for a device likelihood (make_lik); mean:
         mean_function(X) [N, K] or None."""
         desc, Z, X, Y, mean, q_mu, q, qnd, m, d, n, k = self._svgp_lik_args(lik, Z, X, Y, mean, q_mu, q_sqrt)
         elbo, kl, ve, info = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0), ctypes.c_int(0)
         self._drop_resident()
+        self._arm_scales(scales, Z)
         self._call("gps_svgp_elbo_lik", prog, len(prog), _ptr(Z), m, d, float(jitter), _ptr(X), n, _ptr(Y), _opt(mean),
                    _ptr(q_mu), k, _ptr(q), qnd, 1 if white else 0, _byref(desc), float(scale), _byref(elbo), _byref(kl),
                    _byref(ve), _byref(info))
         _raise_if_not_pd(info, _PD_KUU)
         return elbo.value, kl.value, ve.value
 
-    def svgp_elbo_lik_grad(self, prog, Z, X, Y, q_mu, q_sqrt, jitter, lik, mean=None, white=True, scale=1.0, want_grad_Z=False):
+    def svgp_elbo_lik_grad(self, prog, Z, X, Y, q_mu, q_sqrt, jitter, lik, mean=None, white=True, scale=1.0, want_grad_Z=False,
+                           scales=None):
         """svgp_elbo_grad for a device likelihood: (elbo, grad_slots, d/d likelihood parameter 0, grad_q_mu, grad_q_sqrt,
-        d/d mean(X) [N, K][, grad_Z])."""
+        d/d mean(X) [N, K][, grad_Z][, grad_scales])."""
         desc, Z, X, Y, mean, q_mu, q, qnd, m, d, n, k = self._svgp_lik_args(lik, Z, X, Y, mean, q_mu, q_sqrt)
         elbo, glik, info = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_int(0)
         slots, ns = self._slot_buffer()
         g_qmu, g_q, g_mean, g_Z = np.zeros((m, k)), np.zeros_like(q), np.zeros((n, k)), np.zeros((m, d))
         self._drop_resident()
+        armed = self._arm_scales(scales, Z)
         self._call("gps_svgp_elbo_lik_grad", prog, len(prog), _ptr(Z), m, d, float(jitter), _ptr(X), n, _ptr(Y), _opt(mean),
                    _ptr(q_mu), k, _ptr(q), qnd, 1 if white else 0, _byref(desc), float(scale), _byref(elbo), _ptr(slots),
                    SLOT_CAP, _byref(ns), _byref(glik), _ptr(g_qmu), _ptr(g_q), _ptr(g_mean),
                    _ptr(g_Z) if want_grad_Z else None, _byref(info))
         _raise_if_not_pd(info, _PD_KUU)
         out = (elbo.value, slots[:ns.value].copy(), glik.value, g_qmu, self._q_sqrt_grad(g_q, qnd), g_mean)
-        return out + (g_Z,) if want_grad_Z else out
+        out = out + (g_Z,) if want_grad_Z else out
+        return out + (self._scales_grad(m, d),) if armed else out
 
     # ---- GPMC: the whitened model for MCMC, and its kernels on their own
     def lik_logp(self, lik, F, Y, want_grad=False):

@@ -23,8 +23,17 @@ def conditional(Xnew, X, kern, f, *, full_cov=False, q_sqrt=None, white=False):
 
 
 def feature_conditional(Xnew, feat, kern, f, *, full_cov=False, q_sqrt=None, white=False):
-    """conditionals.py:69-77 with features.InducingPoints.Kuu/Kuf (features.py:74-81)"""
-    return conditional(Xnew, feat.Z, kern, f, full_cov=full_cov, q_sqrt=q_sqrt, white=white)
+    """conditionals.py:69-77 with the feature's Kuu / Kuf: features.InducingPoints (features.py:74-81) or, when the feature has
+    ``scales``, features.Multiscale (features.py:123-147) -- both built inside the one device call."""
+    scales = getattr(feat, "scales", None)
+    if scales is None:
+        return conditional(Xnew, feat.Z, kern, f, full_cov=full_cov, q_sqrt=q_sqrt, white=white)
+    feat._check_kern(kern)
+    Xnew = np.asarray(Xnew, dtype=settings.float_type)
+    Z = np.asarray(feat.Z, dtype=settings.float_type)
+    kern._check_inputs(Z, Xnew)
+    return be.get_handle().conditional(kern._program(Z.shape[1]), Z, Xnew, f, settings.numerics.jitter_level,
+                                       q_sqrt=q_sqrt, white=white, full_cov=full_cov, scales=scales)
 
 
 def uncertain_conditional(Xnew_mu, Xnew_var, feat, kern, q_mu, q_sqrt, *, full_cov_output=False, full_cov=False, white=False):
@@ -32,7 +41,8 @@ def uncertain_conditional(Xnew_mu, Xnew_var, feat, kern, q_mu, q_sqrt, *, full_c
     x_n ~ N(Xnew_mu_n, diag Xnew_var_n) under q(u) = N(q_mu, q_sqrt q_sqrt^T) at the inducing points.  ``kern`` is an
     ekernels.RBF or ekernels.Sum; ``Xnew_var`` holds the diagonals, [N, Din].  One device call (gps_uncertain_conditional): the
     [N, M, M] array eKufKfu of the reference is never formed."""
-    from .features import InducingPoints          # (features imports this module)
+    from .features import InducingPoints, refuse_multiscale          # (features imports this module)
+    refuse_multiscale(feat, "uncertain_conditional")
     if not isinstance(feat, InducingPoints):
         raise NotImplementedError("uncertain_conditional is implemented for InducingPoints only")
     if full_cov:

@@ -73,6 +73,8 @@ class _KLShare(object):
 
 
 def _shard(model, comm):
+    from .features import refuse_multiscale
+    refuse_multiscale(getattr(model, "feature", None), "distributed_sparse")
     b = shard_bounds(model.X.shape[0], comm.world)
     lo, hi = b[comm.rank], b[comm.rank + 1]
     if hi <= lo:

@@ -41,6 +41,7 @@ class SGPMC(GPModel):
         self.num_data = X.shape[0]
         self.num_latent = num_latent or Y.shape[1]
         self.feature = features.inducingpoint_wrapper(feat, Z)
+        features.refuse_multiscale(self.feature, "SGPMC")
         self._V = Parameter(np.zeros((len(self.feature), self.num_latent), dtype=settings.float_type), name='V')
         self._V.prior = priors.Gaussian(0., 1.)
         self._parameters = self._parameters + [self._V]

@@ -28,13 +28,14 @@ class SGPRUpperMixin(object):
         num_data = float(self.Y.shape[0])
         s2 = float(np.squeeze(self.likelihood.variance))
         jit = settings.numerics.jitter_level
-        h.sgpr(prog, self.feature.Z, self.X, Y, jit, s2)
+        scales = features.feature_scales(self.feature, self.kern)
+        h.sgpr(prog, self.feature.Z, self.X, Y, jit, s2, scales=scales)
         t = h.sparse_last_terms()
         c = num_data * t["kdiag"] - t["tr_AAT"]                       # trace bound, sgpr.py:67
         corrected_noise = s2 + c
         const = -0.5 * num_data * np.log(2 * np.pi * s2)
         logdet = -t["sum_log_diag_LB"]
-        h.sgpr(prog, self.feature.Z, self.X, Y, jit, corrected_noise)
+        h.sgpr(prog, self.feature.Z, self.X, Y, jit, corrected_noise, scales=scales)
         tc = h.sparse_last_terms()
         quad = -0.5 / corrected_noise * np.sum(Y ** 2.0) + 0.5 * tc["sum_c2"]
         return const + logdet + quad
@@ -51,6 +52,8 @@ class SGPR(GPModel, SGPRUpperMixin):
         self.num_data = X.shape[0] if num_data is None else num_data
         self.num_latent = Y.shape[1] if num_latent is None else num_latent
         self._parameters = self._parameters + [self.feature._Z]
+        if getattr(self.feature, "_scales", None) is not None:              # (features.Multiscale: the widths move with Z)
+            self._parameters = self._parameters + [self.feature._scales]
 
     def _call(self, Xnew=None, full_cov=False, want_bound=True, X=None, Y=None, handle=None):
         # (X, Y, handle: one rank's shard of the data points on its own handle -- gpflowSlim.distributed_sparse)
@@ -58,9 +61,10 @@ class SGPR(GPModel, SGPRUpperMixin):
         Y = self.Y if Y is None else Y
         err = np.ascontiguousarray(Y - self.mean_function(X))
         prog = self.kern._program(X.shape[1])
+        scales = features.feature_scales(self.feature, self.kern)
         return (handle or be.get_handle()).sgpr(prog, self.feature.Z, X, err, settings.numerics.jitter_level,
                                                 float(np.squeeze(self.likelihood.variance)), Xnew=Xnew, full_cov=full_cov,
-                                                want_bound=want_bound)
+                                                want_bound=want_bound, scales=scales)
 
     def _build_likelihood(self):
         """models/sgpr.py:121-153"""
@@ -79,9 +83,13 @@ class SGPR(GPModel, SGPRUpperMixin):
         err = np.ascontiguousarray(self.Y - self.mean_function(self.X))
         zparam = getattr(self.feature, "_Z", None)
         want_z = zparam is not None and any(p is zparam for p in self.parameters)
-        bound, slots, gnoise, g_mean, g_Z = be.get_handle().sgpr_grad(
+        scales = features.feature_scales(self.feature, self.kern)
+        sparam = getattr(self.feature, "_scales", None) if scales is not None else None
+        res = be.get_handle().sgpr_grad(
             prog, self.feature.Z, self.X, err, settings.numerics.jitter_level, float(np.squeeze(self.likelihood.variance)),
-            want_grad_Z=want_z, fitc=self._fitc_gradient)
+            want_grad_Z=want_z, fitc=self._fitc_gradient, scales=scales)
+        bound, slots, gnoise, g_mean, g_Z = res[:5]
+        g_scales = res[5] if scales is not None else None
         if len(layout) != len(slots):
             raise RuntimeError("gradient slot layout mismatch: %d vs %d" % (len(layout), len(slots)))
         grads = {id(p): np.zeros_like(np.atleast_1d(p.vf_val), dtype=settings.float_type) for p in self.parameters}
@@ -109,6 +117,8 @@ class SGPR(GPModel, SGPRUpperMixin):
         for p in self.parameters:
             if p is zparam:
                 out.append((p, (g_Z * np.atleast_1d(p.transform.forward_grad(p.vf_val))).reshape(p.vf_val.shape)))
+            elif sparam is not None and p is sparam:
+                out.append((p, (g_scales * np.atleast_1d(p.transform.forward_grad(p.vf_val))).reshape(p.vf_val.shape)))
             else:
                 g = grads[id(p)].reshape(np.atleast_1d(p.vf_val).shape) * np.atleast_1d(p.transform.forward_grad(p.vf_val))
                 out.append((p, g.reshape(p.vf_val.shape)))
@@ -139,15 +149,18 @@ class GPRFITC(GPModel, SGPRUpperMixin):
         self.num_data = X.shape[0] if num_data is None else num_data
         self.num_latent = Y.shape[1] if num_latent is None else num_latent
         self._parameters = self._parameters + [self.feature._Z]
+        if getattr(self.feature, "_scales", None) is not None:              # (features.Multiscale: the widths move with Z)
+            self._parameters = self._parameters + [self.feature._scales]
 
     def _call(self, Xnew=None, full_cov=False, want_bound=True, X=None, Y=None, handle=None):
         X = self.X if X is None else X
         Y = self.Y if Y is None else Y
         err = np.ascontiguousarray(Y - self.mean_function(X))
         prog = self.kern._program(X.shape[1])
+        scales = features.feature_scales(self.feature, self.kern)
         return (handle or be.get_handle()).sgpr(prog, self.feature.Z, X, err, settings.numerics.jitter_level,
                                                 float(np.squeeze(self.likelihood.variance)), Xnew=Xnew, full_cov=full_cov,
-                                                want_bound=want_bound, fitc=True)
+                                                want_bound=want_bound, fitc=True, scales=scales)
 
     def _build_likelihood(self):
         """models/sgpr.py:252-291"""

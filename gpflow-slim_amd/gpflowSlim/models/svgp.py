@@ -48,6 +48,8 @@ class SVGP(GPModel):
         self.train_inducing = bool(train_inducing)
         if self.train_inducing and getattr(self.feature, "_Z", None) is not None:
             self._parameters = self._parameters + [self.feature._Z]
+            if getattr(self.feature, "_scales", None) is not None:          # (features.Multiscale: the widths move with Z)
+                self._parameters = self._parameters + [self.feature._scales]
 
     @property
     def q_mu(self):
@@ -87,15 +89,17 @@ class SVGP(GPModel):
         """The bound on the data points (X, Y) with the given mini-batch scale: one device call.
         (The whole data set for _build_likelihood; one rank's shard for gpflowSlim.distributed_sparse.)"""
         dl = self._device_lik()
+        scales = features.feature_scales(self.feature, self.kern)
         if dl is not None:
             elbo, _, _ = (handle or be.get_handle()).svgp_elbo_lik(
                 self.kern._program(X.shape[1]), self.feature.Z, X, Y, self.q_mu, self.q_sqrt,
-                settings.numerics.jitter_level, dl[0], mean=self._mean_on(X), white=self.whiten, scale=scale)
+                settings.numerics.jitter_level, dl[0], mean=self._mean_on(X), white=self.whiten, scale=scale, scales=scales)
             return elbo
         yres = np.ascontiguousarray(np.broadcast_to(Y - self.mean_function(X), Y.shape))
         elbo, _, _ = (handle or be.get_handle()).svgp_elbo(
             self.kern._program(X.shape[1]), self.feature.Z, X, yres, self.q_mu, self.q_sqrt,
-            settings.numerics.jitter_level, float(np.squeeze(self.likelihood.variance)), white=self.whiten, scale=scale)
+            settings.numerics.jitter_level, float(np.squeeze(self.likelihood.variance)), white=self.whiten, scale=scale,
+            scales=scales)
         return elbo
 
     def _build_likelihood(self):
@@ -129,19 +133,22 @@ class SVGP(GPModel):
         layout = self.kern._grad_layout(d_all)
         zparam = getattr(self.feature, "_Z", None)
         want_z = zparam is not None and any(p is zparam for p in self.parameters)
+        scales = features.feature_scales(self.feature, self.kern)
+        sparam = getattr(self.feature, "_scales", None) if scales is not None else None
         if gaussian:
             yres = np.ascontiguousarray(np.broadcast_to(Y - self.mean_function(X), Y.shape))
             res = (handle or be.get_handle()).svgp_elbo_grad(
                 prog, self.feature.Z, X, yres, self.q_mu, self.q_sqrt, settings.numerics.jitter_level,
-                float(np.squeeze(self.likelihood.variance)), white=self.whiten, scale=scale, want_grad_Z=want_z)
+                float(np.squeeze(self.likelihood.variance)), white=self.whiten, scale=scale, want_grad_Z=want_z, scales=scales)
             lik_param = self.likelihood._variance
         else:
             res = (handle or be.get_handle()).svgp_elbo_lik_grad(
                 prog, self.feature.Z, X, Y, self.q_mu, self.q_sqrt, settings.numerics.jitter_level, dl[0],
-                mean=self._mean_on(X), white=self.whiten, scale=scale, want_grad_Z=want_z)
+                mean=self._mean_on(X), white=self.whiten, scale=scale, want_grad_Z=want_z, scales=scales)
             lik_param = dl[1]
         elbo, slots, gnoise, g_qmu, g_qsqrt, g_mean = res[:6]
         g_Z = res[6] if want_z else None
+        g_scales = res[-1] if scales is not None else None
         if len(layout) != len(slots):
             raise RuntimeError("gradient slot layout mismatch: %d vs %d" % (len(layout), len(slots)))
         grads = {id(p): np.zeros_like(np.atleast_1d(p.vf_val), dtype=settings.float_type) for p in self.parameters}
@@ -179,6 +186,8 @@ class SVGP(GPModel):
                     out.append((p, np.stack([g_qsqrt[rows, cols, q] for q in range(g_qsqrt.shape[2])]).reshape(p.vf_val.shape)))
             elif p is zparam:
                 out.append((p, (g_Z * np.atleast_1d(p.transform.forward_grad(p.vf_val))).reshape(p.vf_val.shape)))
+            elif sparam is not None and p is sparam:
+                out.append((p, (g_scales * np.atleast_1d(p.transform.forward_grad(p.vf_val))).reshape(p.vf_val.shape)))
             else:
                 g = grads[id(p)].reshape(np.atleast_1d(p.vf_val).shape) * np.atleast_1d(p.transform.forward_grad(p.vf_val))
                 out.append((p, g.reshape(p.vf_val.shape)))
@@ -196,6 +205,7 @@ class SVGP(GPModel):
         ekernels.Sum; a mean function other than Zero would need its own moments under q(x) and is refused."""
         from .. import conditionals
         from ..mean_functions import Zero
+        features.refuse_multiscale(self.feature, "predict_f_uncertain")
         if not isinstance(self.mean_function, Zero):
             raise NotImplementedError("predict_f_uncertain is implemented for the Zero mean function only")
         return conditionals.uncertain_conditional(Xnew_mu, Xnew_var, self.feature, self.kern, self.q_mu, self.q_sqrt,

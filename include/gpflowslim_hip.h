@@ -488,6 +488,23 @@ int gps_kmat_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const
 int gps_kmat_input_vjp(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n,
                        const double* X2, int64_t m, int64_t d_all, const double* W, double* grad_X);
 
+/* ---- Multiscale inducing features (features.py:89-150; Lazaro-Gredilla & Figueiras-Vidal 2009) -------------------------------
+ * Inducing variable m has its own width per dimension: with L_md = l_d + scales_md and c_mm'd^2 = L_md^2 + L_m'd^2 - l_d^2,
+ *   Kuf[m, n]  = v prod_d (l_d / L_md)   exp(-1/2 sum_d (x_nd - z_md)^2  / L_md^2)
+ *   Kuu[m, m'] = v prod_d (l_d / c_mm'd) exp(-1/2 sum_d (z_md - z_m'd)^2 / c_mm'd^2) + jitter [m == m']
+ * over the kernel's active dims (Z and scales sliced alike); Kdiag is the kernel's own.
+ * gps_inducing_scales arms a one-shot state with scales host [m, d_all] (> 0).  The NEXT call of one of
+ *   gps_conditional, gps_svgp_elbo(_grad), gps_svgp_elbo_lik(_grad), gps_sgpr(_grad), gps_fitc(_grad),
+ *   gps_kmat (X = Z: Kuu + diag_add I, or Kuf [m, n] against X2), gps_kmat_vjp / gps_kmat_input_vjp (X = Z likewise)
+ * with that Z [m, d_all] builds Kuu and Kuf by these formulas and takes their VJPs (grad_slots in the usual layout, grad_Z), and
+ * clears the state when it returns, whatever it returns.  The program must be ONE GPS_K_RBF node: anything else is
+ * GPS_ERR_UNSUPPORTED ("Multiscale ..."), as is every other entry that builds a kernel matrix while the state is armed (the GPR,
+ * MCMC, kernel-expectation and distributed entries) and a run with the data sharded over ranks.
+ * gps_inducing_scales_grad: d / d scales host [m, d_all] of the last such call that computed a gradient (columns outside the
+ * active dims are exact zeros); GPS_ERR_STATE when there is none.  With no scales armed every entry does what it always did.   */
+int gps_inducing_scales(gps_handle_t h, const double* scales, int64_t m, int64_t d_all);
+int gps_inducing_scales_grad(gps_handle_t h, double* out, int64_t m, int64_t d_all);
+
 /* gauss_kl(q_mu, q_sqrt, K) (kullback_leiblers.py:26-105): KL[N(q_mu, q_sqrt q_sqrt^T) || N(0, K)], summed over
  * the k independent columns; K host [m, m] or NULL (p = N(0, I)).  tf.cholesky(K) (:51), alpha = Lp^-1 q_mu (:52),
  * tr(K^-1 S_q) through Lp^-T (diagonal q_sqrt: row sums of squares of Lp^-T instead of forming K^-1, :84-90) or
