@@ -334,6 +334,9 @@ struct gps_handle_s {
   DevBuf dScales{bufs};                     // [m, d_all]
   DevBuf dMsPrep{bufs};                     // ms_prep's planes: z, 1 / L, L^2 [m][nd] each, then log prod_d l_d / L_md [m]
   DevBuf dMsPart{bufs};                     // the VJPs' per-chunk partials and their fold
+  // ---- matrix-free kernel product and the batched CG on it (kmvm.hip, gps_kmvm.hip) ----
+  int kmvm_split = 0;                       // gps_kmvm_set_split: chunks of the column walk (0: gps_kmvm_chunks decides)
+  DevBuf dKmvmPart{bufs};                   // the chunks' partial products [chunks][pad64(n)][<= 64]
 };
 
 static inline int gps_fail(gps_handle_t h, int code, const std::string& msg) {

@@ -1,0 +1,264 @@
+// C ABI of libgpflowslim_hip.so (include/gpflowslim_hip.h): exact GP regression without the N x N matrix -- the fused product
+// (K(X, X2) + c I) V of kmvm.hip, a batched conjugate-gradient solve on it, and the prediction built from the two.
+//
+//   gps_kmvm             out = K(X, X2) V, or (K(X, X) + diag_add I) V
+//   gps_kernel_cg        (K(X, X) + s I) x_t = b_t for T columns by plain CG from x = 0, per-column alpha / beta / stop
+//   gps_kernel_predict   alpha = (K + s I)^-1 resid ; mean = K(Xnew, X) alpha ; var_j = Kdiag - k_j^T (K + s I)^-1 k_j, sixteen test
+//                        points to a solve, the right-hand sides K(X, Xnew_block) from the kernel-matrix build and never on the host
+//
+// Stop rule of a column: |r_t| <= tol |b_t|, norm against norm (cgsolver of conjugate_gradient.py, gps_kron_cg, compares
+// tol |b| with the SQUARED residual norm; that rule is the reference's and stays there).  Reaching max_iter is not an error.
+// The loop's state stays on the device (KcgState, kmvm.hip); the host reads it every KCG_CHECK_EVERY = 8 iterations and stops
+// launching once every column has finished -- surplus launches return at once, so the result does not depend on the value.
+// No preconditioner.  The log-determinant, and with it training, is not on this path.
+//
+// Buffers (all the handle's own; np = n padded to 64, tp = the batch's columns padded to 16 or to 64, at most 64 a batch):
+//   dX      X [n, d_all]                dXnew   X2 / Xnew
+//   dFeatG  feature rows of X [*, np]   dGxTab  feature rows of X2 / Xnew / the block's test points
+//   dStage  V / B / resid as uploaded, then the result before it goes back
+//   dS1 x   dS2 r   dS3 p   dS4 Ap      [np, tp] each         dG1  V or B padded [np, tp]
+//   dB      KcgState | partial sums (two sets of gps_kcg_blocks rows of 64)
+//   predict:  dTmp  K(Xnew_block, X) [64, np] (the build's tile is 64 rows, 48 of them padding: 512 n bytes)     dG2  its transpose, the block's right-hand sides [np, 16]
+//             dG3   the mean's product [pad64(n_new), tp]      dMean  mean [n_new, r]
+// (gps_launch_kmat uses dFeat, dFeat2 and dProg; the chunked product dKmvmPart.)
+#include "gps_inducing.hpp"
+#include "kmat_common.hpp"
+
+#define KCG_CHECK_EVERY 8
+
+static inline i64 pad64(i64 n) { return (n + 63) / 64 * 64; }
+static inline i64 kmvm_tpad(i64 t) { return t <= 16 ? 16 : pad64(t); }      // columns of a padded V: one 16-block, or 64 a pass
+
+extern "C" int gps_kmvm_set_split(gps_handle_t h, int64_t chunks) {
+  if (!h || chunks < 0 || chunks > 65535) return gps_fail(h, GPS_ERR_ARG, "gps_kmvm_set_split: 0 .. 65535 chunks");
+  h->kmvm_split = (int)chunks;
+  return GPS_OK;
+}
+
+// what the three entries start with: the scope of the program (before anything touches the device), the refusals, the call's reset
+static int kmvm_begin(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes) {
+  if (!gps_kmvm_in_scope(prog, n_nodes))
+    return gps_fail(h, GPS_ERR_UNSUPPORTED, std::string(who) + ": the program must be one RBF, Matern12/32/52, Exponential or RatQuad primitive");
+  if (int rf = refuse_unsupported(h, who, true)) return rf;
+  return begin_inducing_call(h, nullptr);                  // (refuses armed Multiscale scales; dX, dS*, dG* are overwritten)
+}
+
+// host [rows, cols] (leading dimension ldh, columns c0 .. c0 + tc - 1) -> dst [prow, tp] zero padded; the upload itself is the caller's
+static int kmvm_pad_cols(gps_handle_t h, const double* stage, i64 ldh, i64 rows, i64 c0, i64 tc, double* dst, i64 prow, i64 tp) {
+  return gps_launch_pad_copy(h, stage + c0, ldh, rows, tc, dst, tp, prow, tp, 0, 0.0);
+}
+
+struct KcgBufs { double *x, *r, *p, *Ap; KcgState* st; double *part0, *part1; };
+
+static int kcg_buffers(gps_handle_t h, i64 np, i64 tp, KcgBufs& b) {
+  const size_t vb = (size_t)np * tp * 8;
+  GPS_HIP(h, h->dS1.ensure(vb)); GPS_HIP(h, h->dS2.ensure(vb)); GPS_HIP(h, h->dS3.ensure(vb)); GPS_HIP(h, h->dS4.ensure(vb));
+  const size_t sb = (sizeof(KcgState) + 63) / 64 * 64;
+  GPS_HIP(h, h->dB.ensure(sb + (size_t)2 * KCG_MAX_BLOCKS * 64 * 8));
+  b.x = h->dS1.d(); b.r = h->dS2.d(); b.p = h->dS3.d(); b.Ap = h->dS4.d();
+  b.st = (KcgState*)h->dB.p;
+  b.part0 = (double*)((char*)h->dB.p + sb); b.part1 = b.part0 + (size_t)KCG_MAX_BLOCKS * 64;
+  return GPS_OK;
+}
+
+// Plain CG on (K + noise I) x = B for the tp / 16 column blocks of B [np, tp] (device, zero padded); x in b.x.  iters / relres: the
+// first tc columns' iteration counts, |r| / |b| (0 for b = 0) and whether the column stopped by the tolerance -- the device's own
+// comparison r^T r <= tol^2 b^T b on the device's own numbers, not one recomputed from the quotient --, on the host.
+// The vector kernels of the loop walk the n real rows only: a padded row of K p is not 0 (a padded point has zero features, not a
+// zero kernel value), and left alone the padded rows of r and p keep the zeros they start from.
+static int kcg_solve(gps_handle_t h, const KmvmPlan& plan, i64 n, const KcgBufs& b, const double* B, i64 tp, double noise, int max_iter,
+                     double tol, i64 tc, int64_t* iters, double* relres, int* conv) {
+  const i64 np = plan.npr;
+  const int tb = (int)(tp / 16);
+  int rc = gps_launch_kcg_init(h, b.st, B, b.r, b.p, b.x, np, tb, tol, max_iter, b.part0);
+  if (rc) return rc;
+  KcgState hs;
+  int launched = 0;
+  bool fresh = false;
+  while (launched < max_iter) {
+    const int it = launched;
+    rc = gps_launch_kmvm(h, plan, b.p, tp, tp, noise, b.Ap, tp, &b.st->all_done[it & 1]);
+    if (rc) return rc;
+    rc = gps_launch_kcg_coldot(h, b.st, it, b.p, b.Ap, n, tb, b.part0);
+    if (rc) return rc;
+    rc = gps_launch_kcg_update(h, b.st, it, b.part0, b.p, b.Ap, b.x, b.r, n, tb, b.part1);
+    if (rc) return rc;
+    rc = gps_launch_kcg_dir(h, b.st, it, b.part1, b.r, b.p, n, tb);
+    if (rc) return rc;
+    ++launched;
+    fresh = false;
+    if (launched % KCG_CHECK_EVERY == 0) {
+      GPS_HIP(h, hipMemcpyAsync(&hs, b.st, sizeof(hs), hipMemcpyDeviceToHost, h->stream));
+      GPS_HIP(h, hipStreamSynchronize(h->stream));
+      fresh = true;
+      if (hs.all_done[launched & 1]) break;
+    }
+  }
+  if (!fresh) {
+    GPS_HIP(h, hipMemcpyAsync(&hs, b.st, sizeof(hs), hipMemcpyDeviceToHost, h->stream));
+    GPS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  const int slot = launched & 1;
+  for (i64 t = 0; t < tc; ++t) {
+    if (iters) iters[t] = hs.k[slot][t];
+    if (relres) relres[t] = hs.bb[t] > 0.0 ? sqrt(hs.rr[slot][t] / hs.bb[t]) : 0.0;
+    if (conv) conv[t] = hs.rr[slot][t] <= hs.tol2 * hs.bb[t] ? 1 : 0;
+  }
+  return GPS_OK;
+}
+
+// X -> dX and its features -> dFeatG: the plan of K(X, X)
+static int kmvm_sym_plan(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, i64 n, i64 d_all, KmvmPlan* plan) {
+  const i64 np = pad64(n);
+  GPS_HIP(h, h->dX.ensure((size_t)n * d_all * 8));
+  GPS_HIP(h, hipMemcpyAsync(h->dX.p, X, (size_t)n * d_all * 8, hipMemcpyHostToDevice, h->stream));
+  int rc = gps_kmvm_features(h, prog, n_nodes, h->dX.d(), n, d_all, np, h->dFeatG, &plan->node);
+  if (rc) return rc;
+  plan->Fr = h->dFeatG.d(); plan->Fc = plan->Fr; plan->npr = np; plan->npc = np; plan->sym = 1;
+  return GPS_OK;
+}
+
+extern "C" int gps_kmvm(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, const double* X2,
+                        int64_t n2, int64_t d_all, const double* V, int64_t T, double diag_add, double* out) {
+  if (!h || n < 0 || n2 < 0 || T < 0 || d_all <= 0) return gps_fail(h, GPS_ERR_ARG, "gps_kmvm: bad argument");
+  int rc = kmvm_begin(h, "gps_kmvm", prog, n_nodes);
+  if (rc) return rc;
+  const bool sym = (X2 == nullptr);
+  if (sym) n2 = n;
+  if (n == 0 || T == 0) return GPS_OK;
+  if (!X || !out || (n2 > 0 && !V)) return gps_fail(h, GPS_ERR_ARG, "gps_kmvm: bad argument");
+  if (n2 == 0) { memset(out, 0, (size_t)n * T * 8); return GPS_OK; }
+  KmvmPlan plan;
+  rc = kmvm_sym_plan(h, prog, n_nodes, X, n, d_all, &plan);
+  if (rc) return rc;
+  if (!sym) {
+    plan.npc = pad64(n2); plan.sym = 0;
+    GPS_HIP(h, h->dXnew.ensure((size_t)n2 * d_all * 8));
+    GPS_HIP(h, hipMemcpyAsync(h->dXnew.p, X2, (size_t)n2 * d_all * 8, hipMemcpyHostToDevice, h->stream));
+    rc = gps_kmvm_features(h, prog, n_nodes, h->dXnew.d(), n2, d_all, plan.npc, h->dGxTab, &plan.node);
+    if (rc) return rc;
+    plan.Fc = h->dGxTab.d();
+  }
+  const i64 tp = kmvm_tpad(T);
+  GPS_HIP(h, h->dStage.ensure((size_t)(n2 > n ? n2 : n) * T * 8));
+  GPS_HIP(h, h->dG1.ensure((size_t)plan.npc * tp * 8));
+  GPS_HIP(h, h->dS1.ensure((size_t)plan.npr * tp * 8));
+  GPS_HIP(h, hipMemcpyAsync(h->dStage.p, V, (size_t)n2 * T * 8, hipMemcpyHostToDevice, h->stream));
+  rc = kmvm_pad_cols(h, h->dStage.d(), T, n2, 0, T, h->dG1.d(), plan.npc, tp);
+  if (rc) return rc;
+  rc = gps_launch_kmvm(h, plan, h->dG1.d(), tp, tp, diag_add, h->dS1.d(), tp, nullptr);
+  if (rc) return rc;
+  rc = gps_launch_extract(h, h->dS1.d(), tp, n, T, h->dStage.d(), T, 0);
+  if (rc) return rc;
+  GPS_HIP(h, hipMemcpyAsync(out, h->dStage.p, (size_t)n * T * 8, hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipStreamSynchronize(h->stream));
+  return GPS_OK;
+}
+
+extern "C" int gps_kernel_cg(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                             double noise_var, const double* B, int64_t T, int max_iter, double tol, double* x_out,
+                             int64_t* iters_out, double* relres_out, int* converged_out) {
+  if (!h || n < 0 || T < 0 || d_all <= 0 || max_iter < 0 || !(tol >= 0.0) || !(noise_var >= 0.0))
+    return gps_fail(h, GPS_ERR_ARG, "gps_kernel_cg: bad argument");
+  int rc = kmvm_begin(h, "gps_kernel_cg", prog, n_nodes);
+  if (rc) return rc;
+  if (n == 0 || T == 0) return GPS_OK;
+  if (!X || !B || !x_out || !iters_out || !relres_out || !converged_out) return gps_fail(h, GPS_ERR_ARG, "gps_kernel_cg: bad argument");
+  KmvmPlan plan;
+  rc = kmvm_sym_plan(h, prog, n_nodes, X, n, d_all, &plan);
+  if (rc) return rc;
+  const i64 np = plan.npr;
+  GPS_HIP(h, h->dStage.ensure((size_t)n * T * 8));
+  GPS_HIP(h, hipMemcpyAsync(h->dStage.p, B, (size_t)n * T * 8, hipMemcpyHostToDevice, h->stream));
+  for (i64 c0 = 0; c0 < T; c0 += KCG_MAXT) {
+    const i64 tc = T - c0 < KCG_MAXT ? T - c0 : KCG_MAXT, tp = kmvm_tpad(tc);
+    KcgBufs b;
+    rc = kcg_buffers(h, np, tp, b);
+    if (rc) return rc;
+    GPS_HIP(h, h->dG1.ensure((size_t)np * tp * 8));
+    rc = kmvm_pad_cols(h, h->dStage.d(), T, n, c0, tc, h->dG1.d(), np, tp);
+    if (rc) return rc;
+    rc = kcg_solve(h, plan, n, b, h->dG1.d(), tp, noise_var, max_iter, tol, tc, iters_out + c0, relres_out + c0, converged_out + c0);
+    if (rc) return rc;
+    // (the batch's columns of B have been consumed: its solution takes their place in the staging area)
+    rc = gps_launch_extract(h, b.x, tp, n, tc, h->dStage.d() + c0, T, 0);
+    if (rc) return rc;
+  }
+  GPS_HIP(h, hipMemcpyAsync(x_out, h->dStage.p, (size_t)n * T * 8, hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipStreamSynchronize(h->stream));
+  return GPS_OK;
+}
+
+extern "C" int gps_kernel_predict(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                                  double noise_var, const double* resid, int64_t r, const double* Xnew, int64_t n_new, int max_iter,
+                                  double tol, double* mean_out, double* var_out, int64_t* iters_out, double* relres_out, int* converged_out) {
+  if (!h || n <= 0 || r <= 0 || n_new < 0 || d_all <= 0 || max_iter < 0 || !(tol >= 0.0) || !(noise_var >= 0.0))
+    return gps_fail(h, GPS_ERR_ARG, "gps_kernel_predict: bad argument");
+  int rc = kmvm_begin(h, "gps_kernel_predict", prog, n_nodes);
+  if (rc) return rc;
+  if (n_new == 0) return GPS_OK;
+  if (!X || !resid || !Xnew || !mean_out || !var_out || !iters_out || !relres_out || !converged_out)
+    return gps_fail(h, GPS_ERR_ARG, "gps_kernel_predict: bad argument");
+  double kdiag = 0.0;
+  rc = gps_launch_kdiag(h, prog, n_nodes, &kdiag);
+  if (rc) return rc;
+  KmvmPlan plan;
+  rc = kmvm_sym_plan(h, prog, n_nodes, X, n, d_all, &plan);
+  if (rc) return rc;
+  const i64 np = plan.npr, nsp = pad64(n_new);
+  GPS_HIP(h, h->dXnew.ensure((size_t)n_new * d_all * 8));
+  GPS_HIP(h, hipMemcpyAsync(h->dXnew.p, Xnew, (size_t)n_new * d_all * 8, hipMemcpyHostToDevice, h->stream));
+  // ---- the mean: alpha batch by batch, each pushed through K(Xnew, X) at once
+  KmvmPlan cross = plan;
+  rc = gps_kmvm_features(h, prog, n_nodes, h->dXnew.d(), n_new, d_all, nsp, h->dGxTab, &cross.node);
+  if (rc) return rc;
+  cross.Fr = h->dGxTab.d(); cross.npr = nsp; cross.sym = 0;
+  GPS_HIP(h, h->dStage.ensure((size_t)n * r * 8));
+  GPS_HIP(h, hipMemcpyAsync(h->dStage.p, resid, (size_t)n * r * 8, hipMemcpyHostToDevice, h->stream));
+  GPS_HIP(h, h->dMean.ensure((size_t)n_new * r * 8));
+  for (i64 c0 = 0; c0 < r; c0 += KCG_MAXT) {
+    const i64 tc = r - c0 < KCG_MAXT ? r - c0 : KCG_MAXT, tp = kmvm_tpad(tc);
+    KcgBufs b;
+    rc = kcg_buffers(h, np, tp, b);
+    if (rc) return rc;
+    GPS_HIP(h, h->dG1.ensure((size_t)np * tp * 8));
+    GPS_HIP(h, h->dG3.ensure((size_t)nsp * tp * 8));
+    rc = kmvm_pad_cols(h, h->dStage.d(), r, n, c0, tc, h->dG1.d(), np, tp);
+    if (rc) return rc;
+    rc = kcg_solve(h, plan, n, b, h->dG1.d(), tp, noise_var, max_iter, tol, tc, iters_out + c0, relres_out + c0, converged_out + c0);
+    if (rc) return rc;
+    rc = gps_launch_kmvm(h, cross, b.x, tp, tp, 0.0, h->dG3.d(), tp, nullptr);
+    if (rc) return rc;
+    rc = gps_launch_extract(h, h->dG3.d(), tp, n_new, tc, h->dMean.d() + c0, r, 0);
+    if (rc) return rc;
+  }
+  GPS_HIP(h, hipMemcpyAsync(mean_out, h->dMean.p, (size_t)n_new * r * 8, hipMemcpyDeviceToHost, h->stream));
+  // ---- the variance, sixteen test points to a solve
+  KcgBufs b;
+  rc = kcg_buffers(h, np, 16, b);
+  if (rc) return rc;
+  GPS_HIP(h, h->dTmp.ensure((size_t)64 * np * 8));
+  GPS_HIP(h, h->dG2.ensure((size_t)np * 16 * 8));
+  const int nblk = gps_kcg_blocks(np);
+  std::vector<double> hp((size_t)nblk * 64);
+  for (i64 j0 = 0; j0 < n_new; j0 += 16) {
+    const i64 nb = n_new - j0 < 16 ? n_new - j0 : 16;
+    rc = gps_launch_kmat(h, prog, n_nodes, h->dXnew.d() + j0 * d_all, nb, h->dX.d(), n, d_all, 0.0, h->dTmp.d(), np, 64, np, 0, 0);
+    if (rc) return rc;
+    rc = gps_launch_transpose(h, h->dTmp.d(), np, 16, np, h->dG2.d(), 16);        // rows nb .. 15 and columns n .. np - 1: zeros
+    if (rc) return rc;
+    rc = kcg_solve(h, plan, n, b, h->dG2.d(), 16, noise_var, max_iter, tol, nb, iters_out + r + j0, relres_out + r + j0, converged_out + r + j0);
+    if (rc) return rc;
+    rc = gps_launch_kcg_coldot(h, nullptr, 0, h->dG2.d(), b.x, np, 1, b.part0);
+    if (rc) return rc;
+    GPS_HIP(h, hipMemcpyAsync(hp.data(), b.part0, hp.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    GPS_HIP(h, hipStreamSynchronize(h->stream));
+    for (i64 c = 0; c < nb; ++c) {
+      double s = 0.0;
+      for (int q = 0; q < nblk; ++q) s += hp[(size_t)q * 64 + c];
+      var_out[j0 + c] = kdiag - s;
+    }
+  }
+  GPS_HIP(h, hipStreamSynchronize(h->stream));
+  return GPS_OK;
+}

@@ -26,30 +26,8 @@
 // slabs of one primitive at a time in LDS, accumulates a 4x4 patch of dot products per thread
 // and pushes k() onto a register-resident evaluation stack.  HBM traffic = one coalesced write
 // of K (512-byte row segments per wave) + O((n+m) F) feature reads.
-#include "gps_common.hpp"
-#include <cmath>
+#include "kmat_common.hpp"
 
-#define KT 64          // tile edge
-#define KLS 64         // LDS slab stride (doubles) per feature row
-#define KMAXF 64       // features per primitive (32 dims x {cos, sin})
-
-struct PrepFeat { int dim; int kind; double param; };   // kind 0: x/param ; 1: cos(2 pi x/param) ; 2: sin(...) ; 3: x*param
-// kind 4 / 5: cos / sin of a linear combination of columns, a = sum_q x[tab[dim + q].dim] * tab[dim + q].param over the
-// (int)param table entries from index `dim` on (Cosine: kind-3 entries x_d (w_d / l_d), which follow the pair in the table)
-// kind 6 / 7: looked up by the integer label a = (int)x[dim] (Coregion; gps_label, gps_common.hpp), from a table of doubles that
-// travels beside the feature table (PrepTabLut): 6: lut[off + a * stride] for a in [0, P), else 0 ; 7: lut[off] where a == p, else 0,
-// with (off, P or p, stride) packed into param (gps_lookup_code)
-struct PrepNorm { int f0; int nf; };
-
-struct KNodeDev {
-  int op; int f0; int nf; int norm_row;   // norm_row: row index in Ft holding |a|^2 (or -1)
-  double variance; double c0;             // c0: periodic lengthscale ; RatQuad: alpha ; Polynomial: degree (variance: its offset) ; ArcCosine: order
-  double c1;                              // periodic: -1 / (4 c0^2) ; RatQuad: 1 / alpha ; ArcCosine: bias variance
-};
-struct KProgDev {
-  int n_nodes;
-  KNodeDev nodes[GPS_MAX_NODES];
-};
 
 struct KmatArgs {
   const double* Fr; const double* Fc;     // feature-major [rows][ldf_r / ldf_c]
@@ -121,151 +99,6 @@ __global__ __launch_bounds__(256) void kmat_prep_kernel(const double* __restrict
   }
 }
 
-// ---- exp(x) for x <= 0 (every kernel-matrix formula of kernels.py:436-439, 560-610, 813-819 has a non-positive argument up
-// to rounding): rint reduction, degree-13 polynomial, v_ldexp_f64 -- no overflow branch, <= 1 ulp-class error.  One shared
-// path for all four tile kernels.
-// The coefficients live in constant memory: the loads are uniform, so they sit in SGPRs and every Horner step is ONE
-// v_fma_f64 with a scalar operand.  (As 64-bit literals the compiler materialised each of them with two v_mov_b32 in front of
-// a v_fmac -- 330 of the ~1000 VALU instructions a thread issued for its 16 entries; the kernels are VALU-issue-bound.)
-__constant__ double gps_exp_tab[16] = {
-    1.6059043836821613e-10,   // 1/13!
-    2.08767569878681e-09,     // 1/12!
-    2.505210838544172e-08,    // 1/11!
-    2.755731922398589e-07,    // 1/10!
-    2.7557319223985893e-06,   // 1/9!
-    2.48015873015873e-05,     // 1/8!
-    1.984126984126984e-04,    // 1/7!
-    1.3888888888888889e-03,   // 1/6!
-    8.333333333333333e-03,    // 1/5!
-    4.1666666666666664e-02,   // 1/4!
-    1.6666666666666666e-01,   // 1/3!
-    0.5, 1.0,
-    1.4426950408889634,            // [13] log2(e)
-    6.93147180369123816490e-01,    // [14] ln2 high
-    1.90821492927058770002e-10};   // [15] ln2 low
-// max(r2, 0) of kernels.py:421 the way tf.maximum does it: a NaN argument stays NaN (fmax would return the 0)
-__device__ __forceinline__ double gps_clamp0(double r2) { return (r2 < 0.0) ? 0.0 : r2; }
-struct ExpTab { double c[16]; };
-__device__ __forceinline__ ExpTab gps_exp_load() {
-  ExpTab t;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) t.c[i] = gps_exp_tab[i];
-  return t;
-}
-// The core both exponentials share: x = k ln2 + r and the polynomial's value p = exp(r)
-__device__ __forceinline__ double gps_exp_poly(double x, double k, const ExpTab& t) {
-  double r = fma(-k, t.c[14], x);
-  r = fma(-k, t.c[15], r);
-  // Taylor to degree 13 on |r| <= ln2 / 2 (remainder 4e-18), Horner
-  double p = t.c[0];
-#pragma unroll
-  for (int i = 1; i <= 10; ++i) p = fma(p, r, t.c[i]);
-  p = fma(p, r, 0.5);
-  p = fma(p, r, 1.0);
-  return fma(p, r, 1.0);
-}
-// k = round(x log2 e) by adding 1.5 * 2^52: the sum's low mantissa bits ARE the integer k (two's complement), and 2^k is
-// applied by adding k to the exponent field of the polynomial's value -- no v_rndne_f64 / v_cvt_i32_f64 / v_ldexp_f64 (each
-// a multi-cycle fp64 instruction; the kernel-matrix kernels are VALU-issue-bound).  Returns 2^ki exp(r), good for
-// ki >= -1021 (p in [0.70, 1.42]: the exponent field cannot wrap); what becomes of smaller ki and of a NaN argument (clamped
-// to -1100 here) is the callers' tail: both flush to 0 at ki < -1021, that is for x log2 e < -1021.5, x < -708.05, where the
-// result would be below 2^-1021.5 = 3.15e-308 (NOT at the smallest normal number 2.2e-308: the last binade of the normal
-// range and the denormals, through which exp() goes down to -745.13, are given up).  Pinned contract, tests/_kmat_tail.py: no
-// flush and full relative accuracy for x >= -708; below, a result in [0, 2^-1021] within 2^-1021 of exp(x).
-__device__ __forceinline__ double gps_exp_scaled(double x, const ExpTab& t, int& ki) {
-  const double magic = 6755399441055744.0;
-  const double kd = fma(fmax(x, -1100.0), t.c[13], magic);
-  ki = __double2loint(kd);
-  const double p = gps_exp_poly(x, kd - magic, t);
-  return __hiloint2double(__double2hiint(p) + (ki << 20), __double2loint(p));
-}
-__device__ __forceinline__ double gps_exp_nonpos(double x, const ExpTab& t) {        // exp(x) for x <= 0, <= 1 ulp-class error
-#ifndef GPS_EXP_LDEXP
-  int ki;
-  const double v = gps_exp_scaled(x, t, ki);
-  // (a NaN argument -- NaN in X or in a hyper-parameter: hand it through, as tf.exp and the small-N path's exp() do, instead
-  // of returning 0 and a finite kernel matrix)
-  return ki < -1021 ? (x == x ? 0.0 : x) : v;
-#else
-  const double k = rint(x * t.c[13]);
-  return ldexp(gps_exp_poly(x, k, t), (int)k);      // k >= -1075: gradual underflow to 0 like exp()
-#endif
-}
-// The same for the epilogue of kmat_mfma_kernel, where every VALU instruction counts (round 5).  A NaN argument is handed
-// through by a compare and a select on the result (round 6: the round-5 form, one FMA x * 0 + result, also turned an
-// argument of -infinity -- a squared distance that overflowed -- into NaN where tf.exp and the other kernel-matrix kernels
-// give 0: tests/test_gpu_parity.py::test_overflowed_distances_give_zero_not_nan).
-__device__ __forceinline__ double gps_exp_nonpos_lean(double x, const ExpTab& t) {
-  int ki;
-  const double v = gps_exp_scaled(x, t, ki);
-  const double z = ki < -1021 ? 0.0 : v;
-  return x != x ? x : z;
-}
-__device__ __forceinline__ double gps_exp_nonpos(double x) {        // (kernels that call it a few times only)
-  const ExpTab t = gps_exp_load();
-  return gps_exp_nonpos(x, t);
-}
-// sqrt(x) for x in [1e-12, huge): v_rsq_f64 and one coupled Newton step + a final correction (the library sqrt adds range
-// scaling and special cases around the same core)
-__device__ __forceinline__ double gps_sqrt_pos(double x) {
-#ifndef GPS_SQRT_LIB
-  const double y = __builtin_amdgcn_rsq(x);
-  double g = x * y, hh = 0.5 * y;
-  const double e = fma(-hh, g, 0.5);
-  g = fma(g, e, g); hh = fma(hh, e, hh);
-  const double d = fma(-g, g, x);
-  g = fma(d, hh, g);
-  const double d2 = fma(-g, g, x);
-  return fma(d2, hh, g);
-#else
-  return sqrt(x);
-#endif
-}
-// RatQuad (kernels.py:470-471): variance (1 + 0.5 r2 (1 / alpha))^(-alpha), the power as exp(-alpha log1p(.)): the argument of
-// the exponential is <= 0 like every other one here, and its rounding error alpha log1p(.) u stays far below that of pow() only
-// where the value itself has underflowed.  inv_alpha = 1 / alpha from the host.
-__device__ __forceinline__ double gps_ratquad(double variance, double alpha, double inv_alpha, double r2) {
-  return variance * gps_exp_nonpos(-alpha * log1p(0.5 * r2 * inv_alpha));
-}
-// Polynomial (kernels.py:550-551): (lin + offset)^degree for the integer degrees compile_prog lets through (1 .. 64)
-__device__ __forceinline__ double gps_polynomial(double lin, double offset, double degree) {
-  const double b = lin + offset;
-  double p = b;
-  for (int q = 1; q < (int)degree; ++q) p *= b;
-  return p;
-}
-
-// ArcCosine (kernels.py:727-758) from P = sum_d w_d x_d x'_d + b and n = P(x, x), n' = P(x', x'):
-//   c = 1e-15 + (1 - 2e-15) P / (sqrt(n) sqrt(n')),  theta = acos(c),  k = variance / pi J_order(theta) (sqrt(n) sqrt(n'))^order
-// sqrt(n) sqrt(n') is symmetric in the two points, so K(X, X) is symmetric to the bit.  same: one point against itself on the
-// diagonal of K(X, X) -- there P / (sqrt(n) sqrt(n)) is 1 and theta = acos(1 - 1e-15) = sqrt(2e-15) to 1e-16, and both are taken
-// as exactly that: the roundings of the quotient and of c, whose spacing next to 1 is 1.1e-16, move theta = 4.5e-8 by up to
-// 10 % and with it an order-0 entry by 2e-9 variance.  For two nearly parallel points c is clamped to 1 (where
-// tf.acos would return NaN).
-#define GPS_ARCCOS_THETA0 4.4721359549995794e-08
-#define GPS_ARCCOS_JITTER 1e-15
-// (cos(theta) = c and sin(theta) = sqrt((1 - c)(1 + c)) instead of tf.cos / tf.sin of the computed theta: the same numbers to
-// rounding, without two range reductions per entry)
-__device__ __forceinline__ double gps_arccos_J(int order, double theta, double c, bool same) {
-  const double pt = M_PI - theta;
-  if (order == 0) return pt;
-  const double s = same ? theta : sqrt((1.0 - c) * (1.0 + c));     // (same: sin(theta) = theta to 1e-23, not the sine of the rounded c)
-  if (order == 1) return s + pt * c;
-  return 3.0 * s * c + pt * (1.0 + 2.0 * (c * c));
-}
-__device__ __forceinline__ double gps_arccosine(double variance, int order, double P, double ni, double nj, bool same) {
-  const double sij = sqrt(ni) * sqrt(nj);
-  double c = GPS_ARCCOS_JITTER + (1.0 - 2.0 * GPS_ARCCOS_JITTER) * (same ? 1.0 : P / sij);
-  c = (c > 1.0) ? 1.0 : c;
-  const double theta = same ? GPS_ARCCOS_THETA0 : acos(c);
-  const double J = gps_arccos_J(order, theta, c, same);
-  const double scale = (order == 0) ? 1.0 : (order == 1 ? sij : sij * sij);
-  return variance * (1.0 / M_PI) * J * scale;
-}
-// ... and on the diagonal (theta = 0: J = pi, pi, 3 pi; kernels.py:760-766)
-__device__ __forceinline__ double gps_arccosine_diag(double variance, int order, double n) {
-  return order == 0 ? variance : (order == 1 ? variance * n : variance * 3.0 * (n * n));
-}
 
 // ---- the pieces the tile kernels share ---------------------------------------------------------------------------------------
 // Expression grouping in the formulas is part of the result: the compiler contracts multiply-adds by expression shape, so
@@ -316,40 +149,6 @@ __device__ __forceinline__ void kmat_dots(const KSlabs& s, int nf, int r0, int c
   }
 }
 
-// The value of a primitive with features from its dot product and the two squared norms, for the four VALU users.  same (read by
-// ArcCosine alone): the entry is one point against itself, on the diagonal of K(X, X).
-// OP >= 0: that op at compile time (kmat_single_kernel); OP < 0: `op` at run time.  EXT: RatQuad, Linear, Polynomial, Cosine,
-// ArcCosine and the distance ops too -- the interpreter, the network kernel and kmat_single_kernel<RATQUAD>; kmat_chain_kernel is routed none of
-// them (is_left_deep_chain) and does not pay registers for their formulas.
-// EXT: 0 none of them, 1 all but Cosine / ArcCosine (the instances that existed before those two keep their code), 2: Cosine
-// too (one multiplication), 3: ArcCosine too (acos, a division and three square roots per entry: one wave per SIMD less).
-template <int OP, int EXT>
-__device__ __forceinline__ double kmat_prim_value(const KNodeDev& node, int op, double dot, double ni, double nj, bool same = false) {
-  const int o = (OP >= 0) ? OP : op;
-  if (o == GPS_K_PERIODIC) {
-    // sum_d sin^2(pi (x - x')/p) / l^2 = (D - sum_d cos(a_d - b_d)) / (2 l^2): kernels.py:813-819 in cos / sin feature form
-    const double half_d = 0.5 * (double)(node.nf / 2);
-    const double l2 = node.c0 * node.c0;
-    const double rs = (half_d - 0.5 * dot) / l2;
-    return node.variance * gps_exp_nonpos(-0.5 * rs);
-  }
-  if (EXT && o == GPS_K_LINEAR) return dot;
-  if (EXT >= 2 && o == GPS_K_COSINE) return node.variance * dot;        // cos a cos a' + sin a sin a' (kernels.py:637-646)
-  if (EXT >= 3 && o == GPS_K_ARCCOSINE) return gps_arccosine(node.variance, (int)node.c0, dot + node.c1, ni + node.c1, nj + node.c1, same);
-  if (EXT && o == GPS_K_POLYNOMIAL) return gps_polynomial(dot, node.variance, node.c0);
-  const double sq3 = 1.7320508075688772, sq5 = 2.23606797749979;
-  double r2 = -2.0 * dot + (ni + nj);                                          // kernels.py:409-421
-  r2 = gps_clamp0(r2);
-  if (o == GPS_K_RBF) return node.variance * gps_exp_nonpos(-r2 / 2.0);
-  if (EXT && o == GPS_K_SQDIST) return node.variance * r2;                     // kernels.py:408-421 as a callable
-  if (EXT && o == GPS_K_RATQUAD) return gps_ratquad(node.variance, node.c0, node.c1, r2);
-  const double r = gps_sqrt_pos(r2 + 1e-12);
-  if (o == GPS_K_MATERN12) return node.variance * gps_exp_nonpos(-r);
-  if (EXT && o == GPS_K_EUCLID) return node.variance * r;                      // kernels.py:424-426
-  if (o == GPS_K_EXPONENTIAL) return node.variance * gps_exp_nonpos(-0.5 * r);
-  if (o == GPS_K_MATERN32) return node.variance * (1.0 + sq3 * r) * gps_exp_nonpos(-sq3 * r);
-  return node.variance * (1.0 + sq5 * r + 5.0 / 3.0 * (r * r)) * gps_exp_nonpos(-sq5 * r);
-}
 
 // One node of a program on the 4 x 4 patch (rows 4 ty .., columns 4 tx ..) of the interpreter and the chain kernel: Constant
 // and White without features, every other primitive through its staged slabs
@@ -1353,4 +1152,27 @@ int gps_launch_kmat_block(gps_handle_t h, const gps_kern_node_t* prog, int n_nod
   a.maxnf = 1;
   const double tiles = (double)(nrows / KT) * (double)(ncols / KT);
   return launch_tiles(h, kc, a, nrows, ncols, n_nodes, tiles);
+}
+
+// ---- the matrix-free product's way in (kmvm.hip) ---------------------------------------------------------------------------------
+// Its scope: a program of ONE stationary primitive (the ops kmat_single_kernel takes).  Host only.
+bool gps_kmvm_in_scope(const gps_kern_node_t* prog, int n_nodes) {
+  int rc = 0;
+  return prog && n_nodes == 1 && with_stationary_op<true>(prog[0].op, &rc, [](auto) { return 0; });
+}
+
+// ... and that primitive's feature rows and norm row of the n points dX [n, d_all], zero padded to npad points (a multiple of 64),
+// feature-major in `feat` with leading dimension npad: compile_prog's tables through kmat_prep_kernel, the build's own.
+int gps_kmvm_features(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n, i64 d_all, i64 npad,
+                      DevBuf& feat, KNodeDev* node) {
+  if (!gps_kmvm_in_scope(prog, n_nodes))
+    return gps_fail(h, GPS_ERR_UNSUPPORTED, "matrix-free product: the program must be one RBF, Matern12/32/52, Exponential or RatQuad primitive");
+  KCompiled kc;
+  int rc = compile_prog(h, prog, n_nodes, d_all, kc);
+  if (rc) return rc;
+  i64 ldf = npad;
+  rc = run_prep(h, kc, dX, n, d_all, npad, feat, h->dProg, &ldf);
+  if (rc) return rc;
+  *node = kc.prog.nodes[0];
+  return GPS_OK;
 }

@@ -201,6 +201,15 @@ def ms_chunking(n, m):
     return chunk, -(-n // chunk)
 
 
+def kmvm_chunking(n, n2, forced=0):
+    """The column-tile ranges [(first, end), ...] of the chunks of the matrix-free product for n row points against n2 column points;
+    forced is the value given to gps_kmvm_set_split (0: automatic)  (csrc/kmvm.hip: gps_kmvm_chunks and kmvm_kernel's t0, t1)."""
+    rt, ct = -(-n // 64), -(-n2 // 64)
+    ch = int(forced) if forced > 0 else min(-(-1024 // rt), 64)
+    ch = max(min(ch, ct), 1)
+    return [(c * ct // ch, (c + 1) * ct // ch) for c in range(ch)]
+
+
 def grad_x_slicing(n):
     """(32-row blocks, slices of the column tiles, column tiles per slice) of the walk that d LML / d X makes over the padded
     square of n points: workgroup (block, slice) owns 32 rows and `per` 32-column tiles  (csrc/grad_x.hip: gps_grad_x_slicing;
@@ -274,6 +283,10 @@ _SIGNATURES = {
     "gps_kgpr_lml": _KGPR,
     "gps_kgpr_lml_grad": _KGPR + [_dp, _dp, _dp, _int, _ip, _dp, _int, _ip, _dp],
     "gps_kgpr_predict": [_vp, _prog, _int, _dp, _i64, _i64, _dp, _i64, _prog, _int, _dp, _i64, _i64, _dp, _i64, _dp],
+    "gps_kmvm": [_vp, _prog, _int, _dp, _i64, _dp, _i64, _i64, _dp, _i64, _dbl, _dp],
+    "gps_kmvm_set_split": [_vp, _i64],
+    "gps_kernel_cg": [_vp, _prog, _int, _dp, _i64, _i64, _dbl, _dp, _i64, _int, _dbl, _dp, _i64p, _dp, _ip],
+    "gps_kernel_predict": [_vp, _prog, _int, _dp, _i64, _i64, _dbl, _dp, _i64, _dp, _i64, _int, _dbl, _dp, _dp, _i64p, _dp, _ip],
     "gps_sparse_last_terms": [_vp, _dp],
     "gps_profile_enable": [_vp, _int],
     "gps_profile_reset": [_vp],

@@ -16,7 +16,7 @@ from ._abi import (GPS_MAX_DIMS, GPS_MAX_NODES, GPS_MAX_STACK,                  
                    K_SQDIST, K_EUCLID, K_RATQUAD, K_LINEAR, K_POLYNOMIAL, K_COSINE, K_ARCCOSINE, K_ADD, K_MUL, K_COREGION,
                    K_NKN_LINROW, K_NKN_PRODUCT, K_NKN_ACT, KernNode, LikDesc, RffDesc,
                    RFF_RBF, RFF_LINEAR, RFF_CONSTANT, RFF_EXPLICIT, LIK_MAX_GH, LIK_MAX_EDGES, LIK_MULTICLASS, LIK_ORDINAL,
-                   make_rff, make_lik, make_program, primitive_node, coregion_node, op_node, psi2_chunking, psi_sum_chunking, ms_chunking, grad_x_slicing,
+                   make_rff, make_lik, make_program, primitive_node, coregion_node, op_node, psi2_chunking, psi_sum_chunking, ms_chunking, kmvm_chunking, grad_x_slicing,
                    _SIGNATURES, EXPORTED_SYMBOLS, ALLREDUCE_FN, _c_double_p, _c_int_p, _i64,
                    lib_path, load_library, comm_load, comm_unique_id, comm_version)
 
@@ -1262,3 +1262,58 @@ def set_handle(handle):
     global _default
     with _default_lock:
         _default = handle
+
+
+# ---- exact GP regression without the N x N matrix (csrc/gps_kmvm.hip) ------------------------------------------------------------------
+# Functions of a handle rather than methods of Handle: the three entries drop whatever X and factor were resident and leave nothing
+# resident themselves, so they have no place in the residency table of Handle's docstring; tests/test_gpu_kmvm.py covers them.
+def kmvm(h, prog, X, V, X2=None, diag_add=0.0):
+    """gps_kmvm: K(X, X2) V, or (K(X, X) + diag_add I) V without an X2, K never stored.  X [n, d], X2 [n2, d], V [n2, T]."""
+    X, V = _f64(X), _f64(V)
+    _need(X.ndim == 2 and V.ndim == 2, "X must be [N, D] and V [N2, T]")
+    n, d = X.shape
+    n2 = n
+    if X2 is not None:
+        X2 = _f64(X2)
+        _need(X2.ndim == 2 and X2.shape[1] == d, "X2 must be [N2, %d]" % d)
+        n2 = X2.shape[0]
+    _need(V.shape[0] == n2, "V must have %d rows" % n2)
+    out = np.zeros((n, V.shape[1]))
+    h._drop_resident()
+    h._call("gps_kmvm", prog, len(prog), _ptr(X), n, _opt(X2), 0 if X2 is None else n2, d, _ptr(V), V.shape[1], float(diag_add),
+            _ptr(out))
+    return out
+
+
+def kmvm_set_split(h, chunks):
+    """gps_kmvm_set_split: chunks of the product's column walk (0: automatic)."""
+    h._call("gps_kmvm_set_split", int(chunks))
+
+
+def kernel_cg(h, prog, X, B, noise_var, max_iter=1000, tol=1e-8):
+    """gps_kernel_cg: (x [n, T], iterations [T], |r| / |b| of the recurrence [T], stopped-by-the-tolerance flags [T] -- the loop's
+    own comparison, not one recomputed from the quotient) of (K(X, X) + noise_var I) x = B."""
+    X, B = _f64(X), _f64(B)
+    _need(X.ndim == 2 and B.ndim == 2 and B.shape[0] == X.shape[0], "X must be [N, D] and B [N, T]")
+    n, T = B.shape
+    x, iters, rel, conv = np.zeros((n, T)), np.zeros(T, dtype=np.int64), np.zeros(T), np.zeros(T, dtype=np.intc)
+    h._drop_resident()
+    h._call("gps_kernel_cg", prog, len(prog), _ptr(X), n, X.shape[1], float(noise_var), _ptr(B), T, int(max_iter), float(tol),
+            _ptr(x), iters.ctypes.data_as(ctypes.POINTER(_i64)), _ptr(rel), conv.ctypes.data_as(_c_int_p))
+    return x, iters, rel, conv != 0
+
+
+def kernel_predict(h, prog, X, noise_var, resid, Xnew, max_iter=1000, tol=1e-8):
+    """gps_kernel_predict: (mean [N*, R], var [N*], iterations [R + N*], |r| / |b| [R + N*], converged [R + N*])."""
+    X, resid, Xnew = _f64(X), _f64(resid), _f64(Xnew)
+    _need(X.ndim == 2 and resid.ndim == 2 and resid.shape[0] == X.shape[0] and X.shape[0] > 0 and resid.shape[1] > 0,
+          "X must be [N, D] and the residual [N, R]")
+    _need(Xnew.ndim == 2 and Xnew.shape[1] == X.shape[1], "Xnew must be [N*, %d]" % X.shape[1])
+    n, r, n_new = X.shape[0], resid.shape[1], Xnew.shape[0]
+    mean, var = np.zeros((n_new, r)), np.zeros(n_new)
+    iters, rel, conv = np.zeros(r + n_new, dtype=np.int64), np.zeros(r + n_new), np.zeros(r + n_new, dtype=np.intc)
+    h._drop_resident()
+    h._call("gps_kernel_predict", prog, len(prog), _ptr(X), n, X.shape[1], float(noise_var), _ptr(resid), r, _ptr(Xnew), n_new,
+            int(max_iter), float(tol), _ptr(mean), _ptr(var), iters.ctypes.data_as(ctypes.POINTER(_i64)), _ptr(rel),
+            conv.ctypes.data_as(_c_int_p))
+    return mean, var, iters, rel, conv != 0

@@ -232,3 +232,25 @@ class GPR(GPModel):
         else:
             fvar = np.tile(np.reshape(var, (-1, 1)), [1, R])       # models/gpr.py:131
         return fmean, fvar
+
+    def predict_f_iterative(self, Xnew, max_iter=1000, tol=1e-8):
+        """predict_f without the N x N matrix (not in the reference): alpha = (K + s I)^-1 (Y - m(X)) by batched conjugate
+        gradients on the fused kernel product, mean = K(Xnew, X) alpha + m(Xnew), var_j = Kdiag - k_j^T (K + s I)^-1 k_j sixteen
+        test points to a solve.  Returns (mean [N*, R], var [N*, R]) like predict_f; device memory O(N (D + R + 16)) for the solves
+        plus 512 N bytes for the variance's right-hand sides (the kernel-matrix build writes tiles of 64 rows for 16 test points).  Hyper-parameters
+        are not trained on this path (no log-determinant): fit them on a subset with the dense model.  A solve that did not reach
+        tol within max_iter is reported by a warning."""
+        import warnings
+        from ..conjugate_gradient import _matrix_free_program, MATRIX_FREE_SCOPE
+        if self._has_features():
+            raise NotImplementedError("predict_f_iterative is not available on the feature (random-feature) branch; it takes "
+                                      + MATRIX_FREE_SCOPE)
+        prog = _matrix_free_program(self.kern, self.X.shape[1])
+        Xnew = np.ascontiguousarray(Xnew, dtype=settings.float_type)
+        self.kern._check_inputs(self.X, Xnew)
+        mean, var, iters, rel, conv = be.kernel_predict(be.get_handle(), prog, self.X, float(np.squeeze(self.likelihood.variance)),
+                                                  self._resid(), Xnew, max_iter=max_iter, tol=tol)
+        if not np.all(conv):
+            warnings.warn("predict_f_iterative: %d of %d solves did not reach tol = %g in %d iterations (largest |r| / |b| = %.3g)"
+                          % (int(np.sum(~conv)), rel.size, tol, max_iter, float(np.max(rel))))
+        return mean + self.mean_function(Xnew), np.tile(np.reshape(var, (-1, 1)), [1, self.Y.shape[1]])

@@ -293,6 +293,40 @@ int gps_kgpr_predict(gps_handle_t h, const gps_kern_node_t* prog1, int n_nodes1,
                      const double* Xnew1, int64_t m_new, const gps_kern_node_t* prog2, int n_nodes2, const double* X2, int64_t n,
                      int64_t d2, const double* Xnew2, int64_t n_new, double* mean_out);
 
+/* ---- exact GP regression without the N x N matrix: fused kernel product and batched conjugate gradients ---------------
+ * The product (K(X, X2) + c I) V with K generated tile by tile on the device and never stored: O(n (d + T)) memory.  Scope of prog:
+ * ONE stationary primitive -- GPS_K_RBF, _MATERN12, _MATERN32, _MATERN52, _EXPONENTIAL or _RATQUAD, ARD or isotropic, any
+ * active_dims; any other program returns GPS_ERR_UNSUPPORTED before anything touches the device.  The entries of K are those of
+ * gps_kmat (same features, same formulas).  No floating-point atomics and a fixed summation order: equal bytes from call to
+ * call.  None of these entries takes Multiscale feature scales (refused while armed), and none leaves X or a factor resident.
+ *
+ * gps_kmvm: out host [n, T] = K(X, X2) V for X host [n, d_all], X2 host [n2, d_all], V host [n2, T]; X2 == NULL: n2 is ignored and
+ * out = (K(X, X) + diag_add I) V (diag_add is ignored with an X2).                                                          */
+int gps_kmvm(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, const double* X2, int64_t n2,
+             int64_t d_all, const double* V, int64_t T, double diag_add, double* out);
+/* Chunks of the column walk of the product (partials [chunk][n][T'] folded in chunk order): 0 (default) = enough for about 1024
+ * workgroups, at most 64; > 0: exactly this many (at most one per 64 column points), lengths differing by at most one tile.  The result depends on it only through the order
+ * of the sums.                                                                                                              */
+int gps_kmvm_set_split(gps_handle_t h, int64_t chunks);
+/* (K(X, X) + noise_var I) x_t = b_t for the T columns of B host [n, T] at once, by plain conjugate gradients from x = 0, no
+ * preconditioner.  The columns share each fused product and have their own step lengths; column t stops when
+ * |r_t| <= tol |b_t| -- the UNSQUARED norms (gps_kron_cg keeps the reference's rule, tol |b| against r^T r) -- or at max_iter,
+ * and takes steps of exactly zero from then on; b_t = 0 returns x_t = 0 after 0 iterations.  Reaching max_iter is not an
+ * error.  x_out host [n, T]; iters_out [T]; relres_out [T] = |r_t| / |b_t| of the recurrence (0 for b_t = 0); converged_out [T]:
+ * 1 where the column stopped by the tolerance (the loop's own comparison r^T r <= tol^2 b^T b), 0 where max_iter ended it.    */
+int gps_kernel_cg(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                  double noise_var, const double* B, int64_t T, int max_iter, double tol, double* x_out, int64_t* iters_out,
+                  double* relres_out, int* converged_out);
+/* GPR prediction by the two: alpha = (K + noise_var I)^-1 resid (resid host [n, r]), mean_out host [n_new, r] = K(Xnew, X) alpha,
+ * var_out host [n_new], var_j = Kdiag - k_j^T (K + noise_var I)^-1 k_j solved sixteen test points at a time (the right-hand
+ * sides K(X, Xnew_block) are built on the device and stay there, in tiles of 64 rows: 512 n bytes beside the five [n, 16] vectors
+ * of the solve).  iters_out / relres_out / converged_out [r + n_new]: as gps_kernel_cg, the r columns of alpha first, then one
+ * per test point.                                                                          */
+int gps_kernel_predict(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                       double noise_var, const double* resid, int64_t r, const double* Xnew, int64_t n_new, int max_iter,
+                       double tol, double* mean_out, double* var_out, int64_t* iters_out, double* relres_out,
+                       int* converged_out);
+
 /* ---- conditionals.conditional / base_conditional ------------------------
  * (conditionals.py:24-66, 80-121; features.py:74-81 for Kuu/Kuf).
  * Device-resident form: Kmm = kern.K(Z) + jitter*I, Kmn = kern.K(Z, Xnew) are

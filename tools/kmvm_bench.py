@@ -1,0 +1,55 @@
+"""The matrix-free kernel product (csrc/kmvm.hip) at RBF ARD, D = 8: device time per product for T = 1 and 16 as kernel
+evaluations per second, beside the entry rate of the kernel-matrix build that stores K, in the same process.  Device times come from the library's per-class kernel timers (class "kmat": the prep pass and
+the fused product), one warm-up call per shape, then `reps` repetitions: median, minimum and maximum.  Prints one JSON line.
+
+    python tools/kmvm_bench.py [reps] [n ...]          (default: 5 repetitions at n = 32768, 131072, 1000000)
+"""
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "gpflow-slim_amd"), ROOT]
+import gpflowSlim as gpf  # noqa: E402
+from gpflowSlim import _backend as be  # noqa: E402
+
+reps = int(sys.argv[1]) if len(sys.argv) > 1 else 5
+sizes = [int(a) for a in sys.argv[2:]] or [32768, 131072, 10 ** 6]
+d = 8
+kern = gpf.kernels.RBF(d, variance=1.0, lengthscales=np.sqrt(d) * np.ones(d), ARD=True)
+prog = kern._program(d)
+h = gpf.get_handle()
+
+
+def stats(v):
+    return {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))}
+
+
+def device_ms(call):
+    h.profile_reset(); h.profile_enable(True)
+    call()
+    h.profile_enable(False)
+    return h.profile_get("kmat")["ms"]
+
+
+out = {"d": d, "reps": reps, "device": str(h.device_info()), "sizes": {}}
+for n in sizes:
+    rng = np.random.default_rng(n)
+    X = rng.standard_normal((n, d))
+    row = {}
+    for T in (1, 16):
+        V = rng.standard_normal((n, T))
+        be.kmvm(h, prog, X, V, diag_add=0.1)                                     # warm-up: buffers, code objects
+        ms = [device_ms(lambda: be.kmvm(h, prog, X, V, diag_add=0.1)) for _ in range(reps)]
+        row["T%d" % T] = {"ms": stats(ms), "kernel_evals_per_s": float(n) * n / (1e-3 * float(np.median(ms)))}
+    if n == sizes[0]:
+        # the entry rate of the build that STORES K (kmat_single_kernel), same process, at 8192 points (the matrix comes back to
+        # the host: the timers see the kernels only)
+        h.kmat(prog, X[:8192])                                                   # warm-up
+        t = [device_ms(lambda: h.kmat(prog, X[:8192])) for _ in range(reps)]
+        row["kmat_store_8192"] = {"ms": stats(t), "kernel_evals_per_s": 8192.0 ** 2 / (1e-3 * float(np.median(t)))}
+    out["sizes"][str(n)] = row
+    print(n, row, flush=True)
+print(json.dumps(out))
