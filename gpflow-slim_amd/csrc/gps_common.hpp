@@ -337,6 +337,7 @@ struct gps_handle_s {
   // ---- matrix-free kernel product and the batched CG on it (kmvm.hip, gps_kmvm.hip) ----
   int kmvm_split = 0;                       // gps_kmvm_set_split: chunks of the column walk (0: gps_kmvm_chunks decides)
   DevBuf dKmvmPart{bufs};                   // the chunks' partial products [chunks][pad64(n)][<= 64]
+  DevBuf dLanczos{bufs};                    // gps_kernel_cg_lanczos: alpha_k, beta_k of a batch's columns [max_iter][2][64]
 };
 
 static inline int gps_fail(gps_handle_t h, int code, const std::string& msg) {

@@ -3,6 +3,8 @@
 //
 //   gps_kmvm             out = K(X, X2) V, or (K(X, X) + diag_add I) V
 //   gps_kernel_cg        (K(X, X) + s I) x_t = b_t for T columns by plain CG from x = 0, per-column alpha / beta / stop
+//   gps_kernel_cg_lanczos   the same, and the coefficients alpha_k, beta_k of every column
+//   gps_kmvm_grad        sum_ij (P Q^T)_ij dK_ij / d theta per gradient slot and tr(P Q^T), nothing n x n stored
 //   gps_kernel_predict   alpha = (K + s I)^-1 resid ; mean = K(Xnew, X) alpha ; var_j = Kdiag - k_j^T (K + s I)^-1 k_j, sixteen test
 //                        points to a solve, the right-hand sides K(X, Xnew_block) from the kernel-matrix build and never on the host
 //
@@ -10,7 +12,8 @@
 // tol |b| with the SQUARED residual norm; that rule is the reference's and stays there).  Reaching max_iter is not an error.
 // The loop's state stays on the device (KcgState, kmvm.hip); the host reads it every KCG_CHECK_EVERY = 8 iterations and stops
 // launching once every column has finished -- surplus launches return at once, so the result does not depend on the value.
-// No preconditioner.  The log-determinant, and with it training, is not on this path.
+// No preconditioner.  gps_kernel_cg_lanczos also returns every column's CG coefficients -- the Lanczos tridiagonal from which the
+// host takes the log-determinant by stochastic quadrature -- and gps_kmvm_grad the fused gradient form: with the two, training.
 //
 // Buffers (all the handle's own; np = n padded to 64, tp = the batch's columns padded to 16 or to 64, at most 64 a batch):
 //   dX      X [n, d_all]                dXnew   X2 / Xnew
@@ -67,7 +70,7 @@ static int kcg_buffers(gps_handle_t h, i64 np, i64 tp, KcgBufs& b) {
 // The vector kernels of the loop walk the n real rows only: a padded row of K p is not 0 (a padded point has zero features, not a
 // zero kernel value), and left alone the padded rows of r and p keep the zeros they start from.
 static int kcg_solve(gps_handle_t h, const KmvmPlan& plan, i64 n, const KcgBufs& b, const double* B, i64 tp, double noise, int max_iter,
-                     double tol, i64 tc, int64_t* iters, double* relres, int* conv) {
+                     double tol, i64 tc, int64_t* iters, double* relres, int* conv, double* lz = nullptr, int* launched_out = nullptr) {
   const i64 np = plan.npr;
   const int tb = (int)(tp / 16);
   int rc = gps_launch_kcg_init(h, b.st, B, b.r, b.p, b.x, np, tb, tol, max_iter, b.part0);
@@ -81,9 +84,9 @@ static int kcg_solve(gps_handle_t h, const KmvmPlan& plan, i64 n, const KcgBufs&
     if (rc) return rc;
     rc = gps_launch_kcg_coldot(h, b.st, it, b.p, b.Ap, n, tb, b.part0);
     if (rc) return rc;
-    rc = gps_launch_kcg_update(h, b.st, it, b.part0, b.p, b.Ap, b.x, b.r, n, tb, b.part1);
+    rc = gps_launch_kcg_update(h, b.st, it, b.part0, b.p, b.Ap, b.x, b.r, n, tb, b.part1, lz);
     if (rc) return rc;
-    rc = gps_launch_kcg_dir(h, b.st, it, b.part1, b.r, b.p, n, tb);
+    rc = gps_launch_kcg_dir(h, b.st, it, b.part1, b.r, b.p, n, tb, lz);
     if (rc) return rc;
     ++launched;
     fresh = false;
@@ -99,6 +102,7 @@ static int kcg_solve(gps_handle_t h, const KmvmPlan& plan, i64 n, const KcgBufs&
     GPS_HIP(h, hipStreamSynchronize(h->stream));
   }
   const int slot = launched & 1;
+  if (launched_out) *launched_out = launched;
   for (i64 t = 0; t < tc; ++t) {
     if (iters) iters[t] = hs.k[slot][t];
     if (relres) relres[t] = hs.bb[t] > 0.0 ? sqrt(hs.rr[slot][t] / hs.bb[t]) : 0.0;
@@ -155,15 +159,23 @@ extern "C" int gps_kmvm(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes
   return GPS_OK;
 }
 
-extern "C" int gps_kernel_cg(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
-                             double noise_var, const double* B, int64_t T, int max_iter, double tol, double* x_out,
-                             int64_t* iters_out, double* relres_out, int* converged_out) {
-  if (!h || n < 0 || T < 0 || d_all <= 0 || max_iter < 0 || !(tol >= 0.0) || !(noise_var >= 0.0))
-    return gps_fail(h, GPS_ERR_ARG, "gps_kernel_cg: bad argument");
-  int rc = kmvm_begin(h, "gps_kernel_cg", prog, n_nodes);
+// gps_kernel_cg, and with coef_out (host [max_iter][2][T]: alpha_k, beta_k of column t at [k][0][t], [k][1][t] for k below the
+// column's iteration count, zeros after) gps_kernel_cg_lanczos: the loop records its coefficients on the device (dLanczos) and they
+// are read once a batch, after the loop
+static int kernel_cg_impl(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n,
+                          int64_t d_all, double noise_var, const double* B, int64_t T, int max_iter, double tol, double* x_out,
+                          int64_t* iters_out, double* relres_out, int* converged_out, double* coef_out) {
+  const std::string bad = std::string(who) + ": bad argument";
+  if (!h || n < 0 || T < 0 || d_all <= 0 || max_iter < 0 || !(tol >= 0.0) || !(noise_var >= 0.0)) return gps_fail(h, GPS_ERR_ARG, bad);
+  int rc = kmvm_begin(h, who, prog, n_nodes);
   if (rc) return rc;
   if (n == 0 || T == 0) return GPS_OK;
-  if (!X || !B || !x_out || !iters_out || !relres_out || !converged_out) return gps_fail(h, GPS_ERR_ARG, "gps_kernel_cg: bad argument");
+  if (!X || !B || !x_out || !iters_out || !relres_out || !converged_out) return gps_fail(h, GPS_ERR_ARG, bad);
+  std::vector<double> hz;
+  if (coef_out) {
+    memset(coef_out, 0, (size_t)max_iter * 2 * T * 8);
+    GPS_HIP(h, h->dLanczos.ensure((size_t)(max_iter > 0 ? max_iter : 1) * 2 * KCG_MAXT * 8));
+  }
   KmvmPlan plan;
   rc = kmvm_sym_plan(h, prog, n_nodes, X, n, d_all, &plan);
   if (rc) return rc;
@@ -178,14 +190,92 @@ extern "C" int gps_kernel_cg(gps_handle_t h, const gps_kern_node_t* prog, int n_
     GPS_HIP(h, h->dG1.ensure((size_t)np * tp * 8));
     rc = kmvm_pad_cols(h, h->dStage.d(), T, n, c0, tc, h->dG1.d(), np, tp);
     if (rc) return rc;
-    rc = kcg_solve(h, plan, n, b, h->dG1.d(), tp, noise_var, max_iter, tol, tc, iters_out + c0, relres_out + c0, converged_out + c0);
+    int launched = 0;
+    rc = kcg_solve(h, plan, n, b, h->dG1.d(), tp, noise_var, max_iter, tol, tc, iters_out + c0, relres_out + c0, converged_out + c0,
+                   coef_out ? h->dLanczos.d() : nullptr, &launched);
     if (rc) return rc;
+    if (coef_out && launched > 0) {
+      hz.resize((size_t)launched * 2 * KCG_MAXT);
+      GPS_HIP(h, hipMemcpyAsync(hz.data(), h->dLanczos.p, hz.size() * 8, hipMemcpyDeviceToHost, h->stream));
+      GPS_HIP(h, hipStreamSynchronize(h->stream));
+      for (i64 t = 0; t < tc; ++t)
+        for (int64_t k = 0; k < iters_out[c0 + t]; ++k)
+          for (int ab = 0; ab < 2; ++ab) coef_out[((size_t)k * 2 + ab) * T + c0 + t] = hz[((size_t)k * 2 + ab) * KCG_MAXT + t];
+    }
     // (the batch's columns of B have been consumed: its solution takes their place in the staging area)
     rc = gps_launch_extract(h, b.x, tp, n, tc, h->dStage.d() + c0, T, 0);
     if (rc) return rc;
   }
   GPS_HIP(h, hipMemcpyAsync(x_out, h->dStage.p, (size_t)n * T * 8, hipMemcpyDeviceToHost, h->stream));
   GPS_HIP(h, hipStreamSynchronize(h->stream));
+  return GPS_OK;
+}
+
+extern "C" int gps_kernel_cg(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                             double noise_var, const double* B, int64_t T, int max_iter, double tol, double* x_out,
+                             int64_t* iters_out, double* relres_out, int* converged_out) {
+  return kernel_cg_impl(h, "gps_kernel_cg", prog, n_nodes, X, n, d_all, noise_var, B, T, max_iter, tol, x_out, iters_out, relres_out,
+                        converged_out, nullptr);
+}
+
+extern "C" int gps_kernel_cg_lanczos(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                                     double noise_var, const double* B, int64_t T, int max_iter, double tol, double* x_out,
+                                     int64_t* iters_out, double* relres_out, int* converged_out, double* coef_out) {
+  if (!coef_out && max_iter > 0 && T > 0) return gps_fail(h, GPS_ERR_ARG, "gps_kernel_cg_lanczos: bad argument");
+  return kernel_cg_impl(h, "gps_kernel_cg_lanczos", prog, n_nodes, X, n, d_all, noise_var, B, T, max_iter, tol, x_out, iters_out,
+                        relres_out, converged_out, coef_out);
+}
+
+// The fused gradient form (kmvm.hip): slots_out [1 + n_dims (+ 1: RatQuad's alpha)] = sum_ij (P Q^T)_ij dK_ij / d theta_slot in the
+// gradient kernels' slot order, trace_out = tr(P Q^T), the noise slot.  The device pass needs a symmetric weight: P == Q goes as it
+// is, 64 columns a pass; anything else as [P | Q], [Q | P] (P Q^T + Q P^T, 32 columns a pass) and is halved here.  The passes' sums are
+// added on the host in pass order.
+extern "C" int gps_kmvm_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                             const double* P, const double* Q, int64_t C, double* slots_out, double* trace_out) {
+  if (!h || n < 0 || C < 0 || d_all <= 0) return gps_fail(h, GPS_ERR_ARG, "gps_kmvm_grad: bad argument");
+  int rc = kmvm_begin(h, "gps_kmvm_grad", prog, n_nodes);
+  if (rc) return rc;
+  if (!slots_out || !trace_out) return gps_fail(h, GPS_ERR_ARG, "gps_kmvm_grad: bad argument");
+  const gps_kern_node_t& nd = prog[0];
+  const int nf = nd.n_dims, nslots = 1 + nf + (nd.op == GPS_K_RATQUAD ? 1 : 0), nv = nf + 3;
+  for (int s = 0; s < nslots; ++s) slots_out[s] = 0.0;
+  *trace_out = 0.0;
+  if (n == 0 || C == 0) return GPS_OK;
+  if (!X || !P || !Q || nf <= 0 || nf > GPS_MAX_DIMS) return gps_fail(h, GPS_ERR_ARG, "gps_kmvm_grad: bad argument");
+  KmvmPlan plan;
+  rc = kmvm_sym_plan(h, prog, n_nodes, X, n, d_all, &plan);
+  if (rc) return rc;
+  const i64 np = plan.npr;
+  const bool dbl = P != Q;
+  const size_t wb = (size_t)n * C * 8;
+  GPS_HIP(h, h->dStage.ensure(wb * (dbl ? 2 : 1)));
+  GPS_HIP(h, h->dG1.ensure((size_t)64 * np * 8));
+  GPS_HIP(h, h->dG2.ensure((size_t)64 * np * 8));
+  GPS_HIP(h, h->dB.ensure(64 * 8));
+  GPS_HIP(h, hipMemcpyAsync(h->dStage.p, P, wb, hipMemcpyHostToDevice, h->stream));
+  const double* dP = h->dStage.d();
+  const double* dQ = dP;
+  if (dbl) {
+    GPS_HIP(h, hipMemcpyAsync((char*)h->dStage.p + wb, Q, wb, hipMemcpyHostToDevice, h->stream));
+    dQ = dP + (size_t)n * C;
+  }
+  // d K / d variance = K / variance ; d q2 / d l_d = -2 (f_id - f_jd)^2 / l_d and the rows' sums carry half of sum_ij H_ij (f_id - f_jd)^2
+  double scale[GPS_MAX_DIMS + 3], vals[GPS_MAX_DIMS + 3];
+  scale[0] = 1.0 / nd.variance;
+  for (int d = 0; d < nf; ++d) scale[1 + d] = -4.0 / nd.lengthscales[d];
+  scale[nf + 1] = 1.0; scale[nf + 2] = 1.0;
+  const i64 group = dbl ? 32 : 64;
+  const double half = dbl ? 0.5 : 1.0;
+  for (i64 c0 = 0; c0 < C; c0 += group) {
+    const int tc = (int)(C - c0 < group ? C - c0 : group);
+    rc = gps_launch_kmvm_grad(h, plan, n, dP, dQ, C, c0, tc, h->dG1.d(), h->dG2.d(), scale, h->dB.d());
+    if (rc) return rc;
+    GPS_HIP(h, hipMemcpyAsync(vals, h->dB.p, (size_t)nv * 8, hipMemcpyDeviceToHost, h->stream));
+    GPS_HIP(h, hipStreamSynchronize(h->stream));
+    for (int s = 0; s <= nf; ++s) slots_out[s] += half * vals[s];
+    if (nd.op == GPS_K_RATQUAD) slots_out[nf + 1] += half * vals[nf + 1];
+    *trace_out += half * vals[nf + 2];
+  }
   return GPS_OK;
 }
 

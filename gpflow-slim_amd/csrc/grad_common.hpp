@@ -161,46 +161,12 @@ __device__ __forceinline__ void grad_lml_weight_tile(const Args& a, int ti, int 
   }
 }
 
-#define GRAD_SQRT3 1.7320508075688772
-#define GRAD_SQRT5 2.23606797749979
-
-// stationary primitive from the squared scaled distance q2 (alpha: RatQuad's).  EXT == false: a kernel instance that is never
-// handed RatQuad (grad.hip keeps one such instance, with the code it had before that primitive existed)
-template <bool EXT = true>
-__device__ __forceinline__ double grad_stationary_value(int op, double variance, double q2, double alpha) {
-  if (op == GPS_K_RBF) return variance * exp(-q2 / 2.0);
-  if (EXT && op == GPS_K_RATQUAD) return variance * exp(-alpha * log1p(0.5 * q2 * (1.0 / alpha)));    // (1 + q2 / (2 alpha))^-alpha
-  const double sq3 = GRAD_SQRT3, sq5 = GRAD_SQRT5;
-  const double rad = sqrt(q2 + 1e-12);
-  if (op == GPS_K_MATERN12) return variance * exp(-rad);
-  if (op == GPS_K_EXPONENTIAL) return variance * exp(-0.5 * rad);
-  if (op == GPS_K_MATERN32) return variance * (1.0 + sq3 * rad) * exp(-sq3 * rad);
-  return variance * (1.0 + sq5 * rad + 5.0 / 3.0 * (rad * rad)) * exp(-sq5 * rad);
-}
+#include "stationary_grad.hpp"      // grad_stationary_value, grad_dk_dq2, grad_ratquad_dalpha
 
 // Periodic primitive from dot = sum_d (cos_id cos_jd + sin_id sin_jd); *S = sum_d sin^2(pi D_d / p); l2 = lengthscale^2
 __device__ __forceinline__ double grad_periodic_value(double variance, int ndims, double dot, double l2, double* S) {
   *S = 0.5 * ((double)ndims - dot);
   return variance * exp(-0.5 * *S / l2);
-}
-
-// d k / d (q2) of a stationary primitive with value k at squared scaled distance q2
-template <bool EXT = true>
-__device__ __forceinline__ double grad_dk_dq2(int op, double variance, double k, double q2, double alpha) {
-  if (op == GPS_K_RBF) return -0.5 * k;
-  if (EXT && op == GPS_K_RATQUAD) return -0.5 * k / (1.0 + 0.5 * q2 / alpha);
-  const double sq3 = GRAD_SQRT3, sq5 = GRAD_SQRT5;
-  const double rad = sqrt(q2 + 1e-12);
-  if (op == GPS_K_MATERN12) return -k / (2.0 * rad);
-  if (op == GPS_K_EXPONENTIAL) return -k / (4.0 * rad);
-  if (op == GPS_K_MATERN32) return -1.5 * variance * exp(-sq3 * rad);
-  return -(5.0 / 6.0) * variance * (1.0 + sq5 * rad) * exp(-sq5 * rad);
-}
-
-// d k / d alpha of RatQuad with value k:  k (t / (1 + t) - log1p(t)),  t = q2 / (2 alpha)
-__device__ __forceinline__ double grad_ratquad_dalpha(double k, double q2, double alpha) {
-  const double t = 0.5 * q2 / alpha;
-  return k * (t / (1.0 + t) - log1p(t));
 }
 
 // Linear / Polynomial from lin = sum_d v_d x_d x'_d (the dot product of the features x_d sqrt(v_d)): the value, and d k / d lin

@@ -231,5 +231,13 @@ int gps_launch_kcg_init(gps_handle_t h, KcgState* st, const double* B, double* r
 // (rows: the rows the kernel walks -- the real points inside the loop, so that the padded rows of r and p stay 0)
 int gps_launch_kcg_coldot(gps_handle_t h, const KcgState* st, int it, const double* A, const double* Bm, i64 rows, int tb, double* part);
 int gps_launch_kcg_update(gps_handle_t h, const KcgState* st, int it, const double* part_pap, const double* p, const double* Ap,
-                          double* x, double* r, i64 rows, int tb, double* part_rr);
-int gps_launch_kcg_dir(gps_handle_t h, KcgState* st, int it, const double* part_rr, const double* r, double* p, i64 rows, int tb);
+                          double* x, double* r, i64 rows, int tb, double* part_rr, double* lz);
+int gps_launch_kcg_dir(gps_handle_t h, KcgState* st, int it, const double* part_rr, const double* r, double* p, i64 rows, int tb,
+                       double* lz);
+// lz of the two above: optional device [max_iter][2][KCG_MAXT], alpha_it and beta_it of every live column (NULL: none)
+// kmvm.hip : the fused gradient form  sum_ij G_ij dK_ij / d theta  for K(X, X) and G = P Q^T, one pass of at most 64 weight columns
+// (32 where P != Q: the pass runs [P | Q], [Q | P] and the caller halves).  P, Q device [n, ldc], columns c0 .. c0 + tc - 1; Pt, Qt:
+// room for [64][npr] doubles each; scale: host [nf + 3] factors; vals_out: device [nf + 3] = scale o [sum G K, one raw sum per
+// feature, sum G dk/dalpha, tr G].  Partials go through h->dKmvmPart.
+int gps_launch_kmvm_grad(gps_handle_t h, const KmvmPlan& p, i64 n, const double* P, const double* Q, i64 ldc, i64 c0, int tc,
+                         double* Pt, double* Qt, const double* scale, double* vals_out);

@@ -35,6 +35,7 @@
 //
 // Resources (gfx950, hipcc -O3): no scratch; VGPRs and occupancy are in DESIGN.md 8k.
 #include "kmat_common.hpp"
+#include "stationary_grad.hpp"
 
 #define KVT 64          // tile edge: rows per workgroup, column points per tile
 #define KVS 80          // LDS stride (doubles) of a staged feature row
@@ -214,6 +215,281 @@ int gps_launch_kmvm(gps_handle_t h, const KmvmPlan& p, const double* V, i64 ldv,
   return GPS_OK;
 }
 
+// ---- the fused gradient form ------------------------------------------------------------------------------------------------------
+// form[slot] = sum_ij G_ij dK_ij / d theta_slot for K(X, X) and the low-rank weight G = P Q^T (P, Q [n, C], G symmetric: the host
+// side sees to that), with K, its derivative and G regenerated tile by tile in registers and nothing n x n stored.  What training
+// on the matrix-free path needs: 1/2 tr(W dK / d theta) with W = alpha alpha^T - R/T sum_t u_t z_t^T (gps_kmvm.hip).
+//
+// The walk is kmvm_kernel's: four waves own 64 rows, column tiles of 64 points, feature rows and the norm row feature-major in LDS
+// at stride KVS, the wave's 16 row points in registers, the same chunks along grid.y.  P and Q travel the way the features do,
+// column-major [cp][np] (cp = C padded with zero columns to a multiple of 4, at most 64): the wave's rows of P sit in registers
+// (pv[], one double per four columns), the tile's rows of Q are staged in LDS beside the features.  Per 16 x 16 block:
+//   1. dot products on v_mfma_f64_16x16x4, exactly as kmvm_kernel;
+//   2. the weight block on the same instruction and operand map: A = the block's 16 column points of Q, B = the wave's 16 rows of
+//      P, cp / 4 steps, so register r of lane (i, k) holds G[i][4 r + k] where the first accumulator holds that entry's dot product;
+//   3. VALU: k = kmat_prim_value, k' = d k / d q2 (grad_dk_dq2) and RatQuad's d k / d alpha (stationary_grad.hpp: the dense gradient
+//      kernels' formulas); sum_j G_ij K_ij and sum_j G_ij dk/dalpha_ij are per-lane sums; H = G o k' in place;
+//   4. the H register is the A operand of the next product, as K is in kmvm_kernel: acc += H[i][4 r .. 4 r + 3] . [F | 1][p0 + 4 r ..],
+//      B = the tile's points with their scaled features f = x / l as columns, a column of ones after them and zeros up to 16 (KB = 2:
+//      one accumulator) or 48 (KB = 8: three).  B is a second, point-major copy of the staged tile (sB [64][16 NA]): read from the
+//      feature-major one, sixteen lanes would stride KVS doubles and meet in two banks.
+// That leaves (H F)_id and the row sums rs_i = sum_j H_ij, and the lengthscale slots follow from the expansion the build itself
+// uses for r2: for symmetric H,  sum_ij H_ij (f_id - f_jd)^2 = 2 sum_i f_id (f_id rs_i - (H F)_id);  d q2 / d l_d = -2 (f_id - f_jd)^2 / l_d.
+//
+// H is zeroed on the exact diagonal (the one block kmvm_kernel patches): its true share of every lengthscale slot is 0, and
+// Matern12 / Exponential have k' ~ 1 / sqrt(1e-12) there, which would turn the cancellation into a visible error.  G_ii K_ii stays
+// in the variance slot.  Edges by zeros: a padded point has zero features and zero rows in P and Q, so G and H vanish on it.
+//
+// Every chunk writes its partials ([chunk][np][16 NA] and the two per-lane sums [chunk][np][2]); kmvm_grad_rows_kernel folds them in
+// chunk order per row, forms the row's term of each value and leaves one partial per workgroup, over the n real rows only;
+// kmvm_grad_fold_kernel adds those in workgroup order and applies the factors (1 / variance, -4 / l_d).  No atomics, fixed order.
+struct KgradArgs {
+  const double* F; i64 np;                  // feature-major rows of the points [*, np] (rows and columns of K(X, X))
+  const double* Pt; const double* Qt; int cp;      // [cp][np], cp a multiple of 4, <= 64
+  double* part; double* ext;                // chunk c: part + c np W ([np][W], W = 16 NA), ext + c np 2
+  int tiles, chunks;
+};
+
+template <int OP, int KB>
+__global__ __launch_bounds__(256, 2) void kmvm_grad_kernel(KgradArgs a, KNodeDev node) {
+  constexpr int NA = KB == 2 ? 1 : 3, W = 16 * NA;
+  extern __shared__ double kg_smem[];
+  double* sF = kg_smem;                     // [4 KB][KVS]
+  double* sN = sF + 4 * KB * KVS;           // [KVT]
+  double* sB = sN + KVT;                    // [KVT][W]: the tile's points, columns [F | 1 | 0]
+  double* sQ = sB + KVT * W;                // [cp][KVS]
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int l15 = lane & 15, kq = lane >> 4;
+  const i64 gi0 = (i64)blockIdx.x * KVT;
+  const i64 row = gi0 + 16 * w + l15;
+  const int kbn = (node.nf + 3) >> 2;
+  double bv[KB];
+#pragma unroll
+  for (int kb = 0; kb < KB; ++kb) {
+    const int f = 4 * kb + kq;
+    bv[kb] = f < node.nf ? a.F[(i64)(node.f0 + f) * a.np + row] : 0.0;
+  }
+  // the wave's rows of P: B operand of the weight block, lane (i, k) holds column 4 s + k of row i
+  double pv[16];
+#pragma unroll
+  for (int s = 0; s < 16; ++s) pv[s] = 4 * s < a.cp ? a.Pt[(i64)(4 * s + kq) * a.np + row] : 0.0;
+  const double ni = a.F[(i64)node.norm_row * a.np + row];
+  const int c = blockIdx.y;
+  const int t0 = (int)((i64)c * a.tiles / a.chunks), t1 = (int)((i64)(c + 1) * a.tiles / a.chunks);
+  // register q of acc2[b] is row 16 w + 4 q + kq, column 16 b + l15 of [H F | rs | 0]
+  v4d_v acc2[NA];
+#pragma unroll
+  for (int b = 0; b < NA; ++b) acc2[b] = (v4d_v){0.0, 0.0, 0.0, 0.0};
+  double sv = 0.0, sa = 0.0;               // sum_j G_ij K_ij, sum_j G_ij dk/dalpha_ij over this lane's columns
+  for (int t = t0; t < t1; ++t) {
+    const i64 gj0 = (i64)t * KVT;
+    __syncthreads();
+    for (int idx = tid; idx < 4 * kbn * KVT; idx += 256) {
+      const int f = idx >> 6, p = idx & 63;
+      sF[f * KVS + p] = f < node.nf ? a.F[(i64)(node.f0 + f) * a.np + gj0 + p] : 0.0;
+    }
+    for (int idx = tid; idx < W * KVT; idx += 256) {
+      const int f = idx >> 6, p = idx & 63;
+      sB[p * W + f] = f < node.nf ? a.F[(i64)(node.f0 + f) * a.np + gj0 + p] : (f == node.nf ? 1.0 : 0.0);
+    }
+    for (int idx = tid; idx < a.cp * KVT; idx += 256) {
+      const int q = idx >> 6, p = idx & 63;
+      sQ[q * KVS + p] = a.Qt[(i64)q * a.np + gj0 + p];
+    }
+    if (tid < KVT) sN[tid] = a.F[(i64)node.norm_row * a.np + gj0 + tid];
+    __syncthreads();
+    const bool diag_tile = gj0 == gi0;
+#pragma unroll 1
+    for (int j = 0; j < 4; ++j) {
+      v4d_v acc = (v4d_v){0.0, 0.0, 0.0, 0.0}, g = (v4d_v){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int kb = 0; kb < KB; ++kb)
+        if (kb < kbn) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(sF[(4 * kb + kq) * KVS + 16 * j + l15], bv[kb], acc, 0, 0, 0);
+#pragma unroll
+      for (int s = 0; s < 16; ++s)
+        if (4 * s < a.cp) g = __builtin_amdgcn_mfma_f64_16x16x4f64(sQ[(4 * s + kq) * KVS + 16 * j + l15], pv[s], g, 0, 0, 0);
+      const bool diag_blk = diag_tile && j == w;
+      if (diag_blk) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (4 * r + kq == l15) acc[r] = fma(acc[r], 0.0, ni);
+      }
+      double hv[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const double nj = sN[16 * j + 4 * r + kq];
+        const double kv = kmat_prim_value<OP, 1>(node, OP, acc[r], ni, nj);
+        const double q2 = gps_clamp0(-2.0 * acc[r] + (ni + nj));       // (kmat_prim_value's own r2)
+        sv = fma(g[r], kv, sv);
+        if (OP == GPS_K_RATQUAD) sa = fma(g[r], grad_ratquad_dalpha(kv, q2, node.c0), sa);
+        hv[r] = g[r] * grad_dk_dq2<true>(OP, node.variance, kv, q2, node.c0);
+        if (diag_blk && 4 * r + kq == l15) hv[r] = 0.0;
+        __builtin_amdgcn_sched_barrier(0);                               // (one chain at a time: two exponentials and a division each)
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const double* bp = sB + (16 * j + 4 * r + kq) * W + l15;
+#pragma unroll
+        for (int b = 0; b < NA; ++b) acc2[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(hv[r], bp[16 * b], acc2[b], 0, 0, 0);
+      }
+    }
+  }
+  double* o = a.part + ((i64)c * a.np + gi0 + 16 * w + kq) * W + l15;
+#pragma unroll
+  for (int b = 0; b < NA; ++b)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) o[(i64)(4 * q) * W + 16 * b] = acc2[b][q];
+  sv += __shfl_xor(sv, 16, 64); sv += __shfl_xor(sv, 32, 64);
+  sa += __shfl_xor(sa, 16, 64); sa += __shfl_xor(sa, 32, 64);
+  if (kq == 0) {
+    double* e = a.ext + ((i64)c * a.np + row) * 2;
+    e[0] = sv; e[1] = sa;
+  }
+}
+
+// P, Q [n, ldc] (columns c0 .. c0 + tc - 1) -> Pt, Qt [cp][np], zero padded.  dbl: Pt = [P | Q], Qt = [Q | P] (P Q^T + Q P^T, the
+// symmetric double of a general P Q^T); else Pt = P alone (Qt is the same array: P Q^T with P == Q)
+__global__ __launch_bounds__(256) void kmvm_grad_pack_kernel(const double* __restrict__ P, const double* __restrict__ Q, i64 ldc, i64 n,
+                                                             i64 c0, int tc, int dbl, double* __restrict__ Pt, double* __restrict__ Qt, i64 np) {
+  const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+  const int q = blockIdx.y;
+  if (i >= np) return;
+  double pvv = 0.0, qvv = 0.0;
+  if (i < n) {
+    if (q < tc) { pvv = P[i * ldc + c0 + q]; if (dbl) qvv = Q[i * ldc + c0 + q]; }
+    else if (dbl && q < 2 * tc) { pvv = Q[i * ldc + c0 + q - tc]; qvv = P[i * ldc + c0 + q - tc]; }
+  }
+  Pt[(i64)q * np + i] = pvv;
+  if (dbl) Qt[(i64)q * np + i] = qvv;
+}
+
+// values of a pass, nv = nf + 3 of them: [0] sum_ij G_ij K_ij ; [1 + d] sum_i f_id (f_id rs_i - (H F)_id) ; [nf + 1] sum_ij G_ij
+// dk/dalpha_ij ; [nf + 2] tr(G) = sum_i sum_q P_iq Q_iq.  One partial per workgroup and value: out [gridDim.x][nv].
+struct KgradFin {
+  const double* F; i64 np, n; const double* Pt; const double* Qt; int cp;
+  const double* part; const double* ext; int chunks, W, nf, f0;
+};
+__global__ __launch_bounds__(256) void kmvm_grad_rows_kernel(KgradFin a, double* __restrict__ out) {
+  __shared__ double sh[4];
+  const int nv = a.nf + 3, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (int v = 0; v < nv; ++v) {
+    double s = 0.0;
+    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (i64)gridDim.x * 256) {
+      if (v == 0 || v == a.nf + 1) {
+        double e = 0.0;
+        for (int ch = 0; ch < a.chunks; ++ch) e += a.ext[((i64)ch * a.np + i) * 2 + (v ? 1 : 0)];
+        s += e;
+      } else if (v <= a.nf) {
+        double hf = 0.0, rs = 0.0;
+        for (int ch = 0; ch < a.chunks; ++ch) {
+          const double* pr = a.part + ((i64)ch * a.np + i) * a.W;
+          hf += pr[v - 1]; rs += pr[a.nf];
+        }
+        const double f = a.F[(i64)(a.f0 + v - 1) * a.np + i];
+        s += f * (f * rs - hf);
+      } else {
+        double e = 0.0;
+        for (int q = 0; q < a.cp; ++q) e = fma(a.Pt[(i64)q * a.np + i], a.Qt[(i64)q * a.np + i], e);
+        s += e;
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    if (lane == 0) sh[w] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) out[(i64)blockIdx.x * nv + v] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    __syncthreads();
+  }
+}
+
+struct KgradScale { double s[GPS_MAX_DIMS + 3]; };
+// out[v] = scale[v] * (the workgroups' partials of value v in workgroup order)
+__global__ __launch_bounds__(64) void kmvm_grad_fold_kernel(const double* __restrict__ part, int nblk, int nv, KgradScale sc,
+                                                            double* __restrict__ out) {
+  const int v = threadIdx.x;
+  if (v >= nv) return;
+  double s = 0.0;
+  for (int k = 0; k < nblk; ++k) s += part[(i64)k * nv + v];
+  out[v] = s * sc.s[v];
+}
+
+template <int OP>
+static int kmvm_grad_launch_op(gps_handle_t h, dim3 grid, const KgradArgs& a, const KNodeDev& node) {
+  const bool small = node.nf <= 8;
+  const int KBv = small ? 2 : 8, Wv = small ? 16 : 48;
+  const size_t lds = (size_t)(4 * KBv * KVS + KVT + KVT * Wv + a.cp * KVS) * 8;
+  if (small) {
+    GPS_HIP(h, hipFuncSetAttribute((const void*)kmvm_grad_kernel<OP, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((kmvm_grad_kernel<OP, 2>), grid, dim3(256), lds, h->stream, a, node);
+  } else {
+    GPS_HIP(h, hipFuncSetAttribute((const void*)kmvm_grad_kernel<OP, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((kmvm_grad_kernel<OP, 8>), grid, dim3(256), lds, h->stream, a, node);
+  }
+  return GPS_OK;
+}
+
+// One pass: columns c0 .. c0 + tc - 1 of P, Q (device [n, ldc]; Q == P: G = P P^T as it is, else doubled to P Q^T + Q P^T, which the
+// caller halves) -> vals_out (device, nf + 3 values in kmvm_grad_rows_kernel's order, times scale[]).  Pt, Qt: room for [64][npr] each.
+int gps_launch_kmvm_grad(gps_handle_t h, const KmvmPlan& p, i64 n, const double* P, const double* Q, i64 ldc, i64 c0, int tc,
+                         double* Pt, double* Qt, const double* scale, double* vals_out) {
+  const bool dbl = P != Q;
+  const int cp = ((dbl ? 2 * tc : tc) + 3) / 4 * 4;
+  if (tc <= 0 || cp > 64 || !p.sym || p.npr % KVT || p.npr != p.npc || n > p.npr)
+    return gps_fail(h, GPS_ERR_ARG, "kmvm_grad: at most 64 weight columns a pass (32 doubled), points padded to 64, K(X, X) only");
+  if (p.npr / KVT > 0x7fffffff / 2 || p.node.nf > 32 || p.node.norm_row < 0)
+    return gps_fail(h, GPS_ERR_UNSUPPORTED, "kmvm_grad: too many rows, or not a stationary primitive");
+  const i64 np = p.npr, tiles = np / KVT;
+  const int chunks = gps_kmvm_chunks(tiles, tiles, h->kmvm_split);
+  if (chunks > 65535) return gps_fail(h, GPS_ERR_UNSUPPORTED, "kmvm_grad: more than 65535 chunks");
+  const int W = p.node.nf <= 8 ? 16 : 48, nv = p.node.nf + 3;
+  const i64 nrow = (n + 255) / 256;
+  const int nblk = (int)(nrow < 1 ? 1 : (nrow > KCG_MAX_BLOCKS ? KCG_MAX_BLOCKS : nrow));
+  const size_t part_d = (size_t)chunks * np * W, ext_d = (size_t)chunks * np * 2;
+  GPS_HIP(h, h->dKmvmPart.ensure((part_d + ext_d + (size_t)nblk * nv) * 8));
+  double* part = h->dKmvmPart.d();
+  {
+    LaunchScope ls(h, KC_OTHER, 0.0, 16.0 * (double)np * cp);
+    hipLaunchKernelGGL(kmvm_grad_pack_kernel, dim3((unsigned)((np + 255) / 256), (unsigned)cp), dim3(256), 0, h->stream, P, Q, ldc, n, c0,
+                       tc, dbl ? 1 : 0, Pt, dbl ? Qt : Pt, np);
+    GPS_HIP(h, hipGetLastError());
+  }
+  KgradArgs a;
+  a.F = p.Fr; a.np = np; a.Pt = Pt; a.Qt = dbl ? Qt : Pt; a.cp = cp; a.part = part; a.ext = part + part_d;
+  a.tiles = (int)tiles; a.chunks = chunks;
+  {
+    const double entries = (double)np * (double)np;
+    LaunchScope ls(h, KC_KMAT, entries * (2.0 * p.node.nf + 2.0 * cp + 2.0 * W + 60.0), 8.0 * (double)np * chunks * (W + 2 + cp));
+    ls.tag[0] = np; ls.tag[1] = np; ls.tag[2] = cp; ls.tag[3] = chunks;
+    const dim3 grid((unsigned)tiles, (unsigned)chunks);
+    int rc = 0;
+    switch (p.node.op) {
+      case GPS_K_RBF: rc = kmvm_grad_launch_op<GPS_K_RBF>(h, grid, a, p.node); break;
+      case GPS_K_MATERN12: rc = kmvm_grad_launch_op<GPS_K_MATERN12>(h, grid, a, p.node); break;
+      case GPS_K_MATERN32: rc = kmvm_grad_launch_op<GPS_K_MATERN32>(h, grid, a, p.node); break;
+      case GPS_K_MATERN52: rc = kmvm_grad_launch_op<GPS_K_MATERN52>(h, grid, a, p.node); break;
+      case GPS_K_EXPONENTIAL: rc = kmvm_grad_launch_op<GPS_K_EXPONENTIAL>(h, grid, a, p.node); break;
+      case GPS_K_RATQUAD: rc = kmvm_grad_launch_op<GPS_K_RATQUAD>(h, grid, a, p.node); break;
+      default: rc = gps_fail(h, GPS_ERR_UNSUPPORTED, "kmvm_grad: not a stationary primitive");
+    }
+    if (rc) return rc;
+    GPS_HIP(h, hipGetLastError());
+  }
+  KgradFin f;
+  f.F = p.Fr; f.np = np; f.n = n; f.Pt = a.Pt; f.Qt = a.Qt; f.cp = cp; f.part = part; f.ext = a.ext; f.chunks = chunks; f.W = W;
+  f.nf = p.node.nf; f.f0 = p.node.f0;
+  double* part2 = a.ext + ext_d;
+  KgradScale sc;
+  for (int v = 0; v < nv; ++v) sc.s[v] = scale[v];
+  {
+    LaunchScope ls(h, KC_REDUCE, (double)n * nv * 4.0, 8.0 * (double)n * chunks * (W + 2));
+    hipLaunchKernelGGL(kmvm_grad_rows_kernel, dim3((unsigned)nblk), dim3(256), 0, h->stream, f, part2);
+    GPS_HIP(h, hipGetLastError());
+    hipLaunchKernelGGL(kmvm_grad_fold_kernel, dim3(1), dim3(64), 0, h->stream, (const double*)part2, nblk, nv, sc, vals_out);
+    GPS_HIP(h, hipGetLastError());
+  }
+  return GPS_OK;
+}
+
 // ---- batched conjugate gradients: the vector kernels ------------------------------------------------------------------------------
 // (K + s I) x_t = b_t for up to KCG_MAXT columns at once, every vector a row-major [npad][tpad] matrix (tpad = 16 tb, zero padded).
 // The columns share each fused product and nothing else: alpha, beta, the stop test and the iteration count are per column.
@@ -305,10 +581,13 @@ __global__ __launch_bounds__(256) void kcg_coldot_kernel(const KcgState* __restr
 }
 
 // a_t = r_t^T r_t / p_t^T Ap_t ; x += a p ; r -= a Ap ; partials of the new r_t^T r_t
+// lz (optional, [max_iter][2][KCG_MAXT]): the CG coefficients of every live column, alpha_it from workgroup 0 here (the one kernel
+// that knows p^T Ap) and beta_it from workgroup 0 of kcg_dir_kernel -- the Lanczos tridiagonal of the column's Krylov space
+// (gps_kernel_cg_lanczos).  A finished column stops writing; NULL: no stores, the same bytes as without the argument.
 __global__ __launch_bounds__(256) void kcg_update_kernel(const KcgState* __restrict__ st, int it, const double* __restrict__ part_pap,
                                                          int nblk, const double* __restrict__ p, const double* __restrict__ Ap,
                                                          double* __restrict__ x, double* __restrict__ r, i64 rows, int tb,
-                                                         double* __restrict__ part_rr) {
+                                                         double* __restrict__ part_rr, double* __restrict__ lz) {
   const int cur = it & 1;
   if (st->all_done[cur]) return;
   __shared__ double sh[256];
@@ -324,6 +603,7 @@ __global__ __launch_bounds__(256) void kcg_update_kernel(const KcgState* __restr
     live[b] = b < tb && !st->done[cur][t];
     const double pap = tot[t];
     al[b] = (live[b] && pap > 0.0) ? st->rr[cur][t] / pap : 0.0;
+    if (lz && blockIdx.x == 0 && rl == 0 && live[b]) lz[((i64)it * 2 + 0) * KCG_MAXT + t] = al[b];      // (Lanczos: alpha_it of a live column)
   }
   for (i64 row = (i64)blockIdx.x * 16 + rl; row < rows; row += (i64)gridDim.x * 16)
 #pragma unroll
@@ -340,7 +620,8 @@ __global__ __launch_bounds__(256) void kcg_update_kernel(const KcgState* __restr
 
 // beta_t = r_t^T r_t / (the previous one) ; p = r + beta p ; workgroup 0 writes the next state
 __global__ __launch_bounds__(256) void kcg_dir_kernel(KcgState* __restrict__ st, int it, const double* __restrict__ part_rr, int nblk,
-                                                      const double* __restrict__ r, double* __restrict__ p, i64 rows, int tb) {
+                                                      const double* __restrict__ r, double* __restrict__ p, i64 rows, int tb,
+                                                      double* __restrict__ lz) {
   const int cur = it & 1, nxt = cur ^ 1;
   if (st->all_done[cur]) {
     if (blockIdx.x == 0 && threadIdx.x < 64) {
@@ -363,6 +644,7 @@ __global__ __launch_bounds__(256) void kcg_dir_kernel(KcgState* __restrict__ st,
     const int t = 16 * b + c;
     live[b] = b < tb && !st->done[cur][t];
     be[b] = live[b] ? tot[t] / st->rr[cur][t] : 0.0;
+    if (lz && blockIdx.x == 0 && rl == 0 && live[b]) lz[((i64)it * 2 + 1) * KCG_MAXT + t] = be[b];      // (Lanczos: beta_it)
   }
   for (i64 row = (i64)blockIdx.x * 16 + rl; row < rows; row += (i64)gridDim.x * 16)
 #pragma unroll
@@ -416,16 +698,17 @@ int gps_launch_kcg_coldot(gps_handle_t h, const KcgState* st, int it, const doub
 }
 
 int gps_launch_kcg_update(gps_handle_t h, const KcgState* st, int it, const double* part_pap, const double* p, const double* Ap,
-                          double* x, double* r, i64 rows, int tb, double* part_rr) {
+                          double* x, double* r, i64 rows, int tb, double* part_rr, double* lz) {
   const int nblk = gps_kcg_blocks(rows);
   const double el = (double)rows * 16.0 * tb;
-  KCG_LAUNCH(kcg_update_kernel, nblk, 6.0 * el, 48.0 * el, st, it, part_pap, nblk, p, Ap, x, r, rows, tb, part_rr);
+  KCG_LAUNCH(kcg_update_kernel, nblk, 6.0 * el, 48.0 * el, st, it, part_pap, nblk, p, Ap, x, r, rows, tb, part_rr, lz);
   return GPS_OK;
 }
 
-int gps_launch_kcg_dir(gps_handle_t h, KcgState* st, int it, const double* part_rr, const double* r, double* p, i64 rows, int tb) {
+int gps_launch_kcg_dir(gps_handle_t h, KcgState* st, int it, const double* part_rr, const double* r, double* p, i64 rows, int tb,
+                       double* lz) {
   const int nblk = gps_kcg_blocks(rows);
   const double el = (double)rows * 16.0 * tb;
-  KCG_LAUNCH(kcg_dir_kernel, nblk, 2.0 * el, 24.0 * el, st, it, part_rr, nblk, r, p, rows, tb);
+  KCG_LAUNCH(kcg_dir_kernel, nblk, 2.0 * el, 24.0 * el, st, it, part_rr, nblk, r, p, rows, tb, lz);
   return GPS_OK;
 }

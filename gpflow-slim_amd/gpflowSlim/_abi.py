@@ -286,6 +286,8 @@ _SIGNATURES = {
     "gps_kmvm": [_vp, _prog, _int, _dp, _i64, _dp, _i64, _i64, _dp, _i64, _dbl, _dp],
     "gps_kmvm_set_split": [_vp, _i64],
     "gps_kernel_cg": [_vp, _prog, _int, _dp, _i64, _i64, _dbl, _dp, _i64, _int, _dbl, _dp, _i64p, _dp, _ip],
+    "gps_kernel_cg_lanczos": [_vp, _prog, _int, _dp, _i64, _i64, _dbl, _dp, _i64, _int, _dbl, _dp, _i64p, _dp, _ip, _dp],
+    "gps_kmvm_grad": [_vp, _prog, _int, _dp, _i64, _i64, _dp, _dp, _i64, _dp, _dp],
     "gps_kernel_predict": [_vp, _prog, _int, _dp, _i64, _i64, _dbl, _dp, _i64, _dp, _i64, _int, _dbl, _dp, _dp, _i64p, _dp, _ip],
     "gps_sparse_last_terms": [_vp, _dp],
     "gps_profile_enable": [_vp, _int],

@@ -1303,6 +1303,32 @@ def kernel_cg(h, prog, X, B, noise_var, max_iter=1000, tol=1e-8):
     return x, iters, rel, conv != 0
 
 
+def kernel_cg_lanczos(h, prog, X, B, noise_var, max_iter=1000, tol=1e-8):
+    """gps_kernel_cg_lanczos: kernel_cg's four results and the recurrence's coefficients alpha [max_iter, T], beta [max_iter, T]
+    (rows below a column's iteration count; zeros after)."""
+    X, B = _f64(X), _f64(B)
+    _need(X.ndim == 2 and B.ndim == 2 and B.shape[0] == X.shape[0], "X must be [N, D] and B [N, T]")
+    n, T = B.shape
+    x, iters, rel, conv = np.zeros((n, T)), np.zeros(T, dtype=np.int64), np.zeros(T), np.zeros(T, dtype=np.intc)
+    coef = np.zeros((max(int(max_iter), 1), 2, T))
+    h._drop_resident()
+    h._call("gps_kernel_cg_lanczos", prog, len(prog), _ptr(X), n, X.shape[1], float(noise_var), _ptr(B), T, int(max_iter), float(tol),
+            _ptr(x), iters.ctypes.data_as(ctypes.POINTER(_i64)), _ptr(rel), conv.ctypes.data_as(_c_int_p), _ptr(coef))
+    return x, iters, rel, conv != 0, coef[:, 0, :], coef[:, 1, :]
+
+
+def kmvm_grad(h, prog, X, P, Q, n_slots):
+    """gps_kmvm_grad: (sum_ij (P Q^T)_ij dK_ij / d theta per gradient slot [n_slots], tr(P Q^T)).  ``Q is P`` runs the symmetric
+    weight as it is; anything else is symmetrised by the entry."""
+    X, Pa = _f64(X), _f64(P)
+    Qa = Pa if Q is P else _f64(Q)
+    _need(X.ndim == 2 and Pa.ndim == 2 and Pa.shape == Qa.shape and Pa.shape[0] == X.shape[0], "X must be [N, D], P and Q [N, C]")
+    slots, trace = np.zeros(int(n_slots)), np.zeros(1)
+    h._drop_resident()
+    h._call("gps_kmvm_grad", prog, len(prog), _ptr(X), X.shape[0], X.shape[1], _ptr(Pa), _ptr(Qa), Pa.shape[1], _ptr(slots), _ptr(trace))
+    return slots, float(trace[0])
+
+
 def kernel_predict(h, prog, X, noise_var, resid, Xnew, max_iter=1000, tol=1e-8):
     """gps_kernel_predict: (mean [N*, R], var [N*], iterations [R + N*], |r| / |b| [R + N*], converged [R + N*])."""
     X, resid, Xnew = _f64(X), _f64(resid), _f64(Xnew)

@@ -43,7 +43,9 @@ def cgsolver(K1, K2, b, C, max_iter=100, tol=1e-6):
 
 # ---- exact GPs without the N x N matrix (not in the reference) -------------------------------------------------------------------
 # kernel_matmul is (K(X, X2) + c I) V with K generated tile by tile on the device and never stored; kernel_cgsolver solves
-# (K(X, X) + s I) x = B on it, all columns of B at once (gps_kmvm, gps_kernel_cg: csrc/kmvm.hip).
+# (K(X, X) + s I) x = B on it, all columns of B at once (gps_kmvm, gps_kernel_cg: csrc/kmvm.hip).  kernel_logdet (stochastic Lanczos
+# quadrature on the solve's own coefficients) and kernel_grad_form (sum_ij G_ij dK_ij / d theta for a low-rank G) are what training
+# needs on top: GPR.compute_log_likelihood_and_gradients_iterative.
 MATRIX_FREE_SCOPE = "one stationary kernel: RBF, Matern12, Matern32, Matern52, Exponential or RatQuad"
 
 
@@ -64,18 +66,80 @@ def kernel_matmul(kern, X, V, X2=None, diag_add=0.0):
     return be.kmvm(be.get_handle(), prog, X, V, X2=X2, diag_add=diag_add)
 
 
-def kernel_cgsolver(kern, X, B, noise_var, max_iter=1000, tol=1e-8):
+def kernel_cgsolver(kern, X, B, noise_var, max_iter=1000, tol=1e-8, lanczos=False):
     """(K(X, X) + noise_var I) x = B by plain conjugate gradients from x = 0, the T columns of B at once.  A column stops when
     |r| <= tol |b| -- the unsquared norms; ``cgsolver`` above keeps the reference's rule, tol |b| against r^T r.  Returns
     (x [n, T], info) with info['iterations'] [T], info['relative_residual'] [T] (of the recurrence) and info['converged'] [T];
-    a column that did not converge within max_iter is reported by a warning, not an error."""
+    a column that did not converge within max_iter is reported by a warning, not an error.  lanczos: info['alpha'] and
+    info['beta'] [iterations, T] as well, the recurrence's coefficients per column (rows below the column's iteration count)."""
     import warnings
     X = np.ascontiguousarray(X, dtype=settings.float_type)
     prog = _matrix_free_program(kern, X.shape[1])
     kern._check_inputs(X)
-    x, iters, rel, conv = be.kernel_cg(be.get_handle(), prog, X, B, noise_var, max_iter=max_iter, tol=tol)
-    info = {"iterations": iters, "relative_residual": rel, "converged": conv}
+    if lanczos:
+        x, iters, rel, conv, al, bt = be.kernel_cg_lanczos(be.get_handle(), prog, X, B, noise_var, max_iter=max_iter, tol=tol)
+        rows = int(np.max(iters)) if iters.size else 0
+        info = {"iterations": iters, "relative_residual": rel, "converged": conv, "alpha": al[:rows], "beta": bt[:rows]}
+    else:
+        x, iters, rel, conv = be.kernel_cg(be.get_handle(), prog, X, B, noise_var, max_iter=max_iter, tol=tol)
+        info = {"iterations": iters, "relative_residual": rel, "converged": conv}
     if not np.all(info["converged"]):
         warnings.warn("kernel_cgsolver: %d of %d columns did not reach tol = %g in %d iterations (largest |r| / |b| = %.3g)"
                       % (int(np.sum(~info["converged"])), rel.size, tol, max_iter, float(np.max(rel))))
+    return x, info
+
+
+def kernel_grad_form(kern, X, P, Q):
+    """(slots, trace): slots[s] = sum_ij (P Q^T)_ij dK(X, X)_ij / d theta_s for every gradient slot of the kernel, in the order
+    of ``kern._grad_layout`` ([variance], one per active dimension's lengthscale, RatQuad: [alpha]), and trace = tr(P Q^T), the
+    slot of a noise variance.  P, Q [n, C]; K, its derivative and the weight P Q^T are regenerated tile by tile on the device
+    (csrc/kmvm.hip: kmvm_grad_kernel), memory O(n (D + C)).  ``Q is P`` runs the symmetric weight as it is."""
+    X = np.ascontiguousarray(X, dtype=settings.float_type)
+    prog = _matrix_free_program(kern, X.shape[1])
+    kern._check_inputs(X)
+    return be.kmvm_grad(be.get_handle(), prog, X, P, Q, len(kern._grad_layout(X.shape[1])))
+
+
+def lanczos_quadrature(alpha, beta, iterations):
+    """e_1^T log(T_t) e_1 per column from the CG coefficients alpha, beta [iterations, T]: the tridiagonal of column t has
+    T_kk = 1 / alpha_k + beta_{k-1} / alpha_{k-1} and T_{k,k+1} = sqrt(beta_k) / alpha_k for k below iterations[t]; its
+    eigen-decomposition on the host gives sum_i (first component of v_i)^2 log(lambda_i).  A column of 0 iterations gives 0."""
+    out = np.zeros(len(iterations))
+    for t, m in enumerate(np.asarray(iterations, dtype=int)):
+        if m == 0:
+            continue
+        a, b = alpha[:m, t], beta[:m, t]
+        diag = 1.0 / a
+        diag[1:] += b[:-1] / a[:-1]
+        off = np.sqrt(b[:-1]) / a[:-1]
+        w, v = np.linalg.eigh(np.diag(diag) + np.diag(off, 1) + np.diag(off, -1))
+        out[t] = np.sum(np.square(v[0]) * np.log(w))
+    return out
+
+
+def kernel_logdet(kern, X, noise_var, probes=None, num_probes=16, seed=0, max_iter=1000, tol=1e-8):
+    """log det (K(X, X) + noise_var I) by stochastic Lanczos quadrature (Gardner et al. 2018): one batched CG solve of the probes,
+    whose coefficients are each probe's Lanczos tridiagonal.  probes [n, T]: Rademacher from ``np.random.default_rng(seed)``
+    unless given.  Returns (estimate = mean of per_probe, per_probe [T] = |z_t|^2 e_1^T log(T_t) e_1 -- an estimate of
+    z_t^T log(K_y) z_t --, info of the solve).  RuntimeError if a probe's solve did not converge: a cut-off recurrence is not an
+    estimate of anything."""
+    X = np.ascontiguousarray(X, dtype=settings.float_type)
+    if probes is None:
+        probes = np.random.default_rng(seed).integers(0, 2, size=(X.shape[0], int(num_probes))) * 2.0 - 1.0
+    Z = np.ascontiguousarray(probes, dtype=settings.float_type)
+    _, info = _solve_converged("kernel_logdet", kern, X, Z, noise_var, max_iter, tol)
+    per_probe = np.sum(np.square(Z), 0) * lanczos_quadrature(info["alpha"], info["beta"], info["iterations"])
+    return float(np.mean(per_probe)), per_probe, info
+
+
+def _solve_converged(who, kern, X, B, noise_var, max_iter, tol):
+    """kernel_cgsolver(lanczos=True) that raises where it would warn"""
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        x, info = kernel_cgsolver(kern, X, B, noise_var, max_iter=max_iter, tol=tol, lanczos=True)
+    if not np.all(info["converged"]):
+        raise RuntimeError("%s: %d of %d columns did not reach tol = %g in %d iterations (largest |r| / |b| = %.3g); raise max_iter"
+                           % (who, int(np.sum(~info["converged"])), info["converged"].size, tol, max_iter,
+                              float(np.max(info["relative_residual"]))))
     return x, info

@@ -41,6 +41,9 @@ class GPR(GPModel):
         self.reuse_factor = False
         # feature branch: rows of X per device chunk (0: the library chooses, about 1 GiB per chunk buffer)
         self.rff_chunk_rows = 0
+        # not in the reference: a dict of keyword arguments of compute_log_likelihood_and_gradients_iterative ({} for the
+        # defaults) sends the likelihood and its gradients -- and with them optimize() -- down the matrix-free route
+        self.iterative = None
 
     # ---- device plumbing -------------------------------------------------------------------
     @property
@@ -121,6 +124,8 @@ class GPR(GPModel):
     # ---- reference API ---------------------------------------------------------------------
     def _build_likelihood(self):
         """models/gpr.py:63-72 + densities.py:73-124, fused on the device."""
+        if self.iterative is not None:
+            return self.compute_log_likelihood_and_gradients_iterative(**self.iterative)[0]
         if self._has_features():
             return self._rff_likelihood()
         self.kern._check_inputs(self.X)
@@ -137,7 +142,13 @@ class GPR(GPModel):
         Parameter.unconstrained_tensor), ...]) in `self.parameters` order.  Priors are not included.
 
         with_inputs: (lml, grads, dLML_dX) with d LML / d X [N, D], the derivative of the evidence with respect to the input
-        locations: the kernel's part from the device (gps_gpr_lml_grad_x) plus the mean function's chain term."""
+        locations: the kernel's part from the device (gps_gpr_lml_grad_x) plus the mean function's chain term.
+
+        With ``self.iterative`` set this is compute_log_likelihood_and_gradients_iterative(**self.iterative)."""
+        if self.iterative is not None:
+            if with_inputs:
+                raise NotImplementedError("d LML / d X is not available on the matrix-free (iterative) route")
+            return self.compute_log_likelihood_and_gradients_iterative(**self.iterative)
         if self._has_features():
             if with_inputs:
                 raise NotImplementedError("d LML / d X is not available on the feature (random-feature) branch")
@@ -160,6 +171,40 @@ class GPR(GPModel):
         if with_inputs:
             return lml, grads, grad_X + self._input_chain(kinv_resid)
         return lml, grads
+
+    def compute_log_likelihood_and_gradients_iterative(self, num_probes=16, seed=0, probes=None, max_iter=1000, tol=1e-8):
+        """(lml, grads) shaped like compute_log_likelihood_and_gradients, without the N x N matrix (Gardner et al. 2018; not in
+        the reference).  One batched CG solve of [Y - m(X) | Z] gives alpha = K_y^-1 (Y - m), u_t = K_y^-1 z_t and each probe's
+        Lanczos tridiagonal; then
+            LML  = -1/2 sum y^T alpha - R/2 mean_t(|z_t|^2 e_1^T log(T_t) e_1) - N R / 2 log 2 pi,
+            d LML / d theta = 1/2 tr(W dK / d theta),  W = alpha alpha^T - R/T sum_t u_t z_t^T,
+        the trace as one fused pass over K's tiles (conjugate_gradient.kernel_grad_form) with P = [alpha, -(R/T) u], Q = [alpha, z].
+        Z [N, T]: ``probes``, or Rademacher from np.random.default_rng(seed) -- a fixed seed makes the objective deterministic, so
+        an optimiser sees one function.  R + T <= 64 (one batch).  The log-determinant and the trace are estimates: their error
+        falls as 1 / sqrt(T); the data-fit terms are exact to the solve's tolerance.  RuntimeError if a solve did not converge."""
+        from .. import conjugate_gradient as cg
+        if self._has_features():
+            raise NotImplementedError("the matrix-free (iterative) route is not available on the feature (random-feature) branch; "
+                                      "it takes " + cg.MATRIX_FREE_SCOPE)
+        cg._matrix_free_program(self.kern, self.X.shape[1])
+        N, R = self.Y.shape
+        if probes is None:
+            probes = np.random.default_rng(seed).integers(0, 2, size=(N, int(num_probes))) * 2.0 - 1.0
+        Z = np.ascontiguousarray(probes, dtype=settings.float_type)
+        T = Z.shape[1]
+        if Z.ndim != 2 or Z.shape[0] != N or T < 1 or R + T > 64:
+            raise ValueError("probes must be [N, T] with 1 <= T <= 64 - R")
+        resid = self._resid()
+        noise = float(np.squeeze(self.likelihood.variance))
+        x, info = cg._solve_converged("compute_log_likelihood_and_gradients_iterative", self.kern, self.X,
+                                      np.concatenate([resid, Z], 1), noise, max_iter, tol)
+        alpha, u = x[:, :R], x[:, R:]
+        quad = cg.lanczos_quadrature(info["alpha"][:, R:], info["beta"][:, R:], info["iterations"][R:])
+        logdet = float(np.mean(np.sum(np.square(Z), 0) * quad))
+        lml = -0.5 * float(np.sum(resid * alpha)) - 0.5 * R * logdet - 0.5 * N * R * np.log(2.0 * np.pi)
+        slots, trace = cg.kernel_grad_form(self.kern, self.X, np.concatenate([alpha, (-float(R) / T) * u], 1),
+                                           np.concatenate([alpha, Z], 1))
+        return lml, self._gradients_from_slots(self.kern._grad_layout(self.X.shape[1]), 0.5 * slots, 0.5 * trace, alpha)
 
     def _input_chain(self, kinv_resid):
         """What the mean function adds to d LML / d X: d LML / d m(X) = K_y^-1 (Y - m) chained through d m / d X -- A^T rows for
@@ -238,8 +283,8 @@ class GPR(GPModel):
         gradients on the fused kernel product, mean = K(Xnew, X) alpha + m(Xnew), var_j = Kdiag - k_j^T (K + s I)^-1 k_j sixteen
         test points to a solve.  Returns (mean [N*, R], var [N*, R]) like predict_f; device memory O(N (D + R + 16)) for the solves
         plus 512 N bytes for the variance's right-hand sides (the kernel-matrix build writes tiles of 64 rows for 16 test points).  Hyper-parameters
-        are not trained on this path (no log-determinant): fit them on a subset with the dense model.  A solve that did not reach
-        tol within max_iter is reported by a warning."""
+        are trained on this path by compute_log_likelihood_and_gradients_iterative (``self.iterative``).  A solve that did not
+        reach tol within max_iter is reported by a warning."""
         import warnings
         from ..conjugate_gradient import _matrix_free_program, MATRIX_FREE_SCOPE
         if self._has_features():

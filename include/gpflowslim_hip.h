@@ -317,6 +317,21 @@ int gps_kmvm_set_split(gps_handle_t h, int64_t chunks);
 int gps_kernel_cg(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
                   double noise_var, const double* B, int64_t T, int max_iter, double tol, double* x_out, int64_t* iters_out,
                   double* relres_out, int* converged_out);
+/* gps_kernel_cg, which also returns the coefficients of every column's recurrence: coef_out host [max_iter][2][T], alpha_k of
+ * column t at [k][0][t] and beta_k at [k][1][t] for k below iters_out[t], zeros from there on.  They are the Lanczos tridiagonal
+ * of the column's Krylov space (T_kk = 1 / alpha_k + beta_{k-1} / alpha_{k-1}, T_{k,k+1} = sqrt(beta_k) / alpha_k): what stochastic
+ * Lanczos quadrature takes log det (K + noise_var I) from.  Recorded on the device, read once per batch of 64 columns after the
+ * loop; x_out and the other outputs are bytewise gps_kernel_cg's.                                                              */
+int gps_kernel_cg_lanczos(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                          double noise_var, const double* B, int64_t T, int max_iter, double tol, double* x_out,
+                          int64_t* iters_out, double* relres_out, int* converged_out, double* coef_out);
+/* The fused gradient form: slots_out[s] = sum_ij (P Q^T)_ij dK(X, X)_ij / d theta_s for every gradient slot of the primitive, in the
+ * order of gps_gpr_lml_grad's slots ([variance], one per active dim's lengthscale, RatQuad: [alpha]), and *trace_out = tr(P Q^T)
+ * (the slot of a noise variance).  P, Q host [n, C]; K, its derivative and the weight tile are regenerated in registers, memory
+ * O(n (d + C)).  P == Q (the same pointer) runs as it is; otherwise the symmetric double [P | Q] [Q | P]^T runs and is halved.  No
+ * atomics, fixed summation order: equal bytes from call to call.                                                               */
+int gps_kmvm_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                  const double* P, const double* Q, int64_t C, double* slots_out, double* trace_out);
 /* GPR prediction by the two: alpha = (K + noise_var I)^-1 resid (resid host [n, r]), mean_out host [n_new, r] = K(Xnew, X) alpha,
  * var_out host [n_new], var_j = Kdiag - k_j^T (K + noise_var I)^-1 k_j solved sixteen test points at a time (the right-hand
  * sides K(X, Xnew_block) are built on the device and stay there, in tiles of 64 rows: 512 n bytes beside the five [n, 16] vectors

@@ -1,6 +1,9 @@
 """The matrix-free kernel product (csrc/kmvm.hip) at RBF ARD, D = 8: device time per product for T = 1 and 16 as kernel
 evaluations per second, beside the entry rate of the kernel-matrix build that stores K, in the same process.  Device times come from the library's per-class kernel timers (class "kmat": the prep pass and
 the fused product), one warm-up call per shape, then `reps` repetitions: median, minimum and maximum.  Prints one JSON line.
+Up to n = 131072 a row "grad_form_C17" follows: one launch of the fused gradient form (kmvm_grad_kernel and its two finishing
+kernels) for a general P Q^T of 17 columns -- one output and T = 16 probes, run doubled as 34 -> 36 weight columns --, beside the
+T = 16 product of the same process, and the ratio of the two medians.
 
     python tools/kmvm_bench.py [reps] [n ...]          (default: 5 repetitions at n = 32768, 131072, 1000000)
 """
@@ -27,11 +30,11 @@ def stats(v):
     return {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))}
 
 
-def device_ms(call):
+def device_ms(call, classes=("kmat",)):
     h.profile_reset(); h.profile_enable(True)
     call()
     h.profile_enable(False)
-    return h.profile_get("kmat")["ms"]
+    return sum(h.profile_get(c)["ms"] for c in classes)
 
 
 out = {"d": d, "reps": reps, "device": str(h.device_info()), "sizes": {}}
@@ -44,6 +47,11 @@ for n in sizes:
         be.kmvm(h, prog, X, V, diag_add=0.1)                                     # warm-up: buffers, code objects
         ms = [device_ms(lambda: be.kmvm(h, prog, X, V, diag_add=0.1)) for _ in range(reps)]
         row["T%d" % T] = {"ms": stats(ms), "kernel_evals_per_s": float(n) * n / (1e-3 * float(np.median(ms)))}
+    if n <= 131072:
+        P, Q = rng.standard_normal((n, 17)), rng.standard_normal((n, 17))
+        be.kmvm_grad(h, prog, X, P, Q, 1 + d)                                    # warm-up
+        ms = [device_ms(lambda: be.kmvm_grad(h, prog, X, P, Q, 1 + d), ("kmat", "reduce", "other")) for _ in range(reps)]
+        row["grad_form_C17"] = {"ms": stats(ms), "products_T16": float(np.median(ms)) / row["T16"]["ms"]["median"]}
     if n == sizes[0]:
         # the entry rate of the build that STORES K (kmat_single_kernel), same process, at 8192 points (the matrix comes back to
         # the host: the timers see the kernels only)
