@@ -4,7 +4,9 @@ ALL the points with predict_f_iterative -- conjugate gradients on the fused kern
 Then a short fit on ALL the points as well: GPR.iterative sends the likelihood and its gradients down the matrix-free route
 (Lanczos log-determinant, fused gradient form), so optimize() trains without the N x N matrix either.
 
-    python examples/gpr_matrix_free.py [N] [subset]
+    python examples/gpr_matrix_free.py [--precond-rank K] [N] [subset]
+
+--precond-rank K (1 .. 128): every solve preconditioned by the rank-K pivoted-Cholesky M = L L^T + noise I (csrc/pchol.hip).
 """
 import os
 import sys
@@ -15,8 +17,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "gpflow-slim_amd"), ROOT]
 import gpflowSlim as gpf  # noqa: E402
 
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 50000
-sub = int(sys.argv[2]) if len(sys.argv) > 2 else 2000
+argv, rank = sys.argv[1:], 0
+if "--precond-rank" in argv:
+    i = argv.index("--precond-rank")
+    rank = int(argv[i + 1])
+    del argv[i:i + 2]
+n = int(argv[0]) if argv else 50000
+sub = int(argv[1]) if len(argv) > 1 else 2000
 rng = np.random.default_rng(0)
 X = rng.uniform(-3, 3, (n, 2))
 f = lambda x: np.sin(2 * x[:, :1]) * np.cos(x[:, 1:2])  # noqa: E731
@@ -34,12 +41,12 @@ print("subset of %d: lml %.2f, lengthscales %s, noise %.4f" % (sub, lml, np.asar
 
 # 2. prediction from all n points with those hyper-parameters, matrix-free
 big = gpf.models.GPR(X, Y, small.kern, obs_var=float(np.squeeze(small.likelihood.variance)))
-mean, var = big.predict_f_iterative(Xs, max_iter=500, tol=1e-6)
+mean, var = big.predict_f_iterative(Xs, max_iter=500, tol=1e-6, precond_rank=rank)
 print("all %d points: rmse against the noise-free function %.4f, mean predictive sd %.4f"
       % (n, float(np.sqrt(np.mean((mean - f(Xs)) ** 2))), float(np.mean(np.sqrt(var)))))
 
-# 3. a short fit on all n points by Adam, matrix-free: 8 Rademacher probes from a fixed seed, so every step sees the same objective
-big.iterative = dict(num_probes=8, seed=0, max_iter=500, tol=1e-6)
+# 3. a short fit on all n points by Adam, matrix-free: 8 probes (Rademacher; with a rank: N(0, M)) from a fixed seed, so every step sees the same objective
+big.iterative = dict(num_probes=8, seed=0, max_iter=500, tol=1e-6, precond_rank=rank)
 before = -big.compute_log_likelihood()
 after = big.optimize(max_iter=10, method="adam", learning_rate=0.02)
 print("all %d points, 10 Adam steps: objective %.2f -> %.2f, lengthscales %s, noise %.4f"

@@ -338,6 +338,8 @@ struct gps_handle_s {
   int kmvm_split = 0;                       // gps_kmvm_set_split: chunks of the column walk (0: gps_kmvm_chunks decides)
   DevBuf dKmvmPart{bufs};                   // the chunks' partial products [chunks][pad64(n)][<= 64]
   DevBuf dLanczos{bufs};                    // gps_kernel_cg_lanczos: alpha_k, beta_k of a batch's columns [max_iter][2][64]
+  DevBuf dPcholL{bufs};                     // the preconditioner's factor L [pad64(n)][pad16(rank_max)] (pchol.hip), rebuilt by every call that uses it
+  DevBuf dPcholWs{bufs};                    // ... and its workspace (gps_pchol_workspace: d, partials, C, chol(C)^-1, S, z)
 };
 
 static inline int gps_fail(gps_handle_t h, int code, const std::string& msg) {

@@ -7,12 +7,15 @@
 //   gps_kmvm_grad        sum_ij (P Q^T)_ij dK_ij / d theta per gradient slot and tr(P Q^T), nothing n x n stored
 //   gps_kernel_predict   alpha = (K + s I)^-1 resid ; mean = K(Xnew, X) alpha ; var_j = Kdiag - k_j^T (K + s I)^-1 k_j, sixteen test
 //                        points to a solve, the right-hand sides K(X, Xnew_block) from the kernel-matrix build and never on the host
+//   gps_kernel_pchol / _precond_solve / _pcg / _predict_pcg   the pivoted-Cholesky preconditioner M = L L^T + s I (pchol.hip): its
+//                        factor, M^-1 V / log det M / samples, and the two solvers above with every solve preconditioned
 //
 // Stop rule of a column: |r_t| <= tol |b_t|, norm against norm (cgsolver of conjugate_gradient.py, gps_kron_cg, compares
 // tol |b| with the SQUARED residual norm; that rule is the reference's and stays there).  Reaching max_iter is not an error.
 // The loop's state stays on the device (KcgState, kmvm.hip); the host reads it every KCG_CHECK_EVERY = 8 iterations and stops
 // launching once every column has finished -- surplus launches return at once, so the result does not depend on the value.
-// No preconditioner.  gps_kernel_cg_lanczos also returns every column's CG coefficients -- the Lanczos tridiagonal from which the
+// Preconditioner: none unless an entry takes a rank (PcholPre, pchol_build below:z = M^-1 r after every update, three launches of pchol.hip, and
+// pcg_dir_kernel in place of kcg_dir_kernel; M is rebuilt by every such call into dPcholL / dPcholWs).  gps_kernel_cg_lanczos also returns every column's CG coefficients -- the Lanczos tridiagonal from which the
 // host takes the log-determinant by stochastic quadrature -- and gps_kmvm_grad the fused gradient form: with the two, training.
 //
 // Buffers (all the handle's own; np = n padded to 64, tp = the batch's columns padded to 16 or to 64, at most 64 a batch):
@@ -70,11 +73,22 @@ static int kcg_buffers(gps_handle_t h, i64 np, i64 tp, KcgBufs& b) {
 // The vector kernels of the loop walk the n real rows only: a padded row of K p is not 0 (a padded point has zero features, not a
 // zero kernel value), and left alone the padded rows of r and p keep the zeros they start from.
 static int kcg_solve(gps_handle_t h, const KmvmPlan& plan, i64 n, const KcgBufs& b, const double* B, i64 tp, double noise, int max_iter,
-                     double tol, i64 tc, int64_t* iters, double* relres, int* conv, double* lz = nullptr, int* launched_out = nullptr) {
+                     double tol, i64 tc, int64_t* iters, double* relres, int* conv, double* lz = nullptr, int* launched_out = nullptr,
+                     const PcholPre* pre = nullptr) {
   const i64 np = plan.npr;
   const int tb = (int)(tp / 16);
   int rc = gps_launch_kcg_init(h, b.st, B, b.r, b.p, b.x, np, tb, tol, max_iter, b.part0);
   if (rc) return rc;
+  // pre: the preconditioned loop -- z = M^-1 r after every update (three launches, which also leave the partials of r^T z), the
+  // step's numerator and beta from r^T z; without it the launches below are the plain loop's, argument for argument
+  double *pz = nullptr, *prz = nullptr, *rzs = nullptr;
+  if (pre) {
+    pz = pre->ws + pre->o_z; prz = pre->ws + pre->o_rzpart; rzs = pre->ws + pre->o_rzs;
+    rc = gps_launch_pchol_apply(h, *pre, b.r, tp, pz, prz, &b.st->all_done[0]);
+    if (rc) return rc;
+    rc = gps_launch_pcg_dir(h, b.st, -1, nullptr, prz, pre->lsg, pz, b.p, n, tb, nullptr, rzs);
+    if (rc) return rc;
+  }
   KcgState hs;
   int launched = 0;
   bool fresh = false;
@@ -84,9 +98,13 @@ static int kcg_solve(gps_handle_t h, const KmvmPlan& plan, i64 n, const KcgBufs&
     if (rc) return rc;
     rc = gps_launch_kcg_coldot(h, b.st, it, b.p, b.Ap, n, tb, b.part0);
     if (rc) return rc;
-    rc = gps_launch_kcg_update(h, b.st, it, b.part0, b.p, b.Ap, b.x, b.r, n, tb, b.part1, lz);
+    rc = gps_launch_kcg_update(h, b.st, it, b.part0, b.p, b.Ap, b.x, b.r, n, tb, b.part1, lz, rzs);
     if (rc) return rc;
-    rc = gps_launch_kcg_dir(h, b.st, it, b.part1, b.r, b.p, n, tb, lz);
+    if (pre) {
+      rc = gps_launch_pchol_apply(h, *pre, b.r, tp, pz, prz, &b.st->all_done[it & 1]);
+      if (rc) return rc;
+      rc = gps_launch_pcg_dir(h, b.st, it, b.part1, prz, pre->lsg, pz, b.p, n, tb, lz, rzs);
+    } else rc = gps_launch_kcg_dir(h, b.st, it, b.part1, b.r, b.p, n, tb, lz);
     if (rc) return rc;
     ++launched;
     fresh = false;
@@ -119,6 +137,137 @@ static int kmvm_sym_plan(gps_handle_t h, const gps_kern_node_t* prog, int n_node
   int rc = gps_kmvm_features(h, prog, n_nodes, h->dX.d(), n, d_all, np, h->dFeatG, &plan->node);
   if (rc) return rc;
   plan->Fr = h->dFeatG.d(); plan->Fc = plan->Fr; plan->npr = np; plan->npc = np; plan->sym = 1;
+  return GPS_OK;
+}
+
+// ---- the pivoted-Cholesky preconditioner (pchol.hip) ----------------------------------------------------------------------------
+// what every entry that takes a rank checks before anything touches the device
+static int pchol_check(gps_handle_t h, const char* who, int rank_max, double rel_tol, double noise_var) {
+  if (rank_max < 0 || rank_max > 128) return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": the preconditioner's rank must be 0 .. 128");
+  if (!(rel_tol >= 0.0)) return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": rel_tol must be >= 0");
+  if (rank_max > 0 && !(noise_var > 0.0))
+    return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": a preconditioner needs a noise variance > 0 (M = L L^T + noise I)");
+  return GPS_OK;
+}
+
+// L (dPcholL) and, with gram, chol(noise I + L^T L)^-1, log det M and the rank on the host (dPcholWs).  Rebuilt by every call:
+// O(n k^2) beside the O(n^2) of one product, and no state that outlives the call.
+static int pchol_build(gps_handle_t h, const char* who, const KmvmPlan& plan, i64 n, double noise_var, int rank_max, double rel_tol,
+                       bool gram, PcholPre* pre) {
+  const int kp = (rank_max + 15) / 16 * 16;
+  const size_t wsb = gps_pchol_workspace(plan.npr, kp, pre);
+  GPS_HIP(h, h->dPcholL.ensure((size_t)plan.npr * kp * 8));
+  GPS_HIP(h, h->dPcholWs.ensure(wsb));
+  pre->L = h->dPcholL.d(); pre->ws = h->dPcholWs.d(); pre->noise = noise_var; pre->rank = 0; pre->logdet = 0.0;
+  int rc = gps_launch_pchol_factor(h, plan, n, rank_max, rel_tol, *pre);
+  if (rc) return rc;
+  PcholState hs;
+  if (!gram) {
+    GPS_HIP(h, hipMemcpyAsync(&hs, pre->ws + pre->o_st, sizeof(hs), hipMemcpyDeviceToHost, h->stream));
+    GPS_HIP(h, hipStreamSynchronize(h->stream));
+    pre->rank = hs.rank; pre->logdet = hs.trace;             // (no M without a noise: the residual trace travels here)
+    return GPS_OK;
+  }
+  rc = gps_launch_pchol_gram(h, *pre, noise_var);
+  if (rc) return rc;
+  int* d_info = (int*)h->dInfo.p;
+  rc = gps_launch_fill_info(h, d_info, INT_MAX);
+  if (rc) return rc;
+  double* C = pre->ws + pre->o_C;
+  rc = gps_launch_potrf_base(h, C, 128, pre->ws + pre->o_W, nullptr, d_info, 0, 1);
+  if (rc) return rc;
+  std::vector<double> hc((size_t)128 * 128);
+  GPS_HIP(h, hipMemcpyAsync(&hs, pre->ws + pre->o_st, sizeof(hs), hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipMemcpyAsync(hc.data(), C, hc.size() * 8, hipMemcpyDeviceToHost, h->stream));
+  int info = 0;
+  rc = read_info(h, d_info, &info);
+  if (rc) return rc;
+  if (info != 0) {
+    char msg[160];
+    snprintf(msg, sizeof msg, ": noise I + L^T L is not positive definite in fp64 at noise / variance = %.3g (rank %d); lower the rank or raise the noise",
+             noise_var / plan.node.variance, hs.rank);
+    return gps_fail(h, GPS_ERR_STATE, std::string(who) + msg);
+  }
+  // log det M = log det C_k + (n - k) log noise, and C is block diagonal [C_k, noise I] over its 128 rows
+  double ld = 0.0;
+  for (int j = 0; j < 128; ++j) ld += 2.0 * log(hc[(size_t)j * 128 + j]);
+  pre->rank = hs.rank;
+  pre->logdet = ld + ((double)n - 128.0) * log(noise_var);
+  return GPS_OK;
+}
+
+extern "C" int gps_kernel_pchol(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                                int rank_max, double rel_tol, double* L_out, int64_t* piv_out, int64_t* rank_out, double* trace_out) {
+  if (!h || n < 0 || d_all <= 0 || rank_max < 1) return gps_fail(h, GPS_ERR_ARG, "gps_kernel_pchol: bad argument");
+  if (int rf = pchol_check(h, "gps_kernel_pchol", rank_max, rel_tol, 1.0)) return rf;
+  int rc = kmvm_begin(h, "gps_kernel_pchol", prog, n_nodes);
+  if (rc) return rc;
+  if (!rank_out || !trace_out) return gps_fail(h, GPS_ERR_ARG, "gps_kernel_pchol: bad argument");
+  *rank_out = 0; *trace_out = 0.0;
+  if (n == 0) return GPS_OK;
+  if (!X || !L_out || !piv_out) return gps_fail(h, GPS_ERR_ARG, "gps_kernel_pchol: bad argument");
+  KmvmPlan plan;
+  rc = kmvm_sym_plan(h, prog, n_nodes, X, n, d_all, &plan);
+  if (rc) return rc;
+  PcholPre pre;
+  rc = pchol_build(h, "gps_kernel_pchol", plan, n, 0.0, rank_max, rel_tol, false, &pre);
+  if (rc) return rc;
+  GPS_HIP(h, h->dStage.ensure((size_t)n * rank_max * 8));
+  rc = gps_launch_extract(h, pre.L, pre.kp, n, rank_max, h->dStage.d(), rank_max, 0);
+  if (rc) return rc;
+  int hpiv[128];
+  GPS_HIP(h, hipMemcpyAsync(L_out, h->dStage.p, (size_t)n * rank_max * 8, hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipMemcpyAsync(hpiv, pre.ws + pre.o_piv, sizeof hpiv, hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipStreamSynchronize(h->stream));
+  for (int m = 0; m < rank_max; ++m) piv_out[m] = m < pre.rank ? hpiv[m] : -1;
+  *rank_out = pre.rank; *trace_out = pre.logdet;
+  return GPS_OK;
+}
+
+extern "C" int gps_kernel_precond_solve(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                                        double noise_var, int rank_max, double rel_tol, const double* V, int64_t T, const double* G1,
+                                        double* out, double* logdet_out, int64_t* rank_out) {
+  const char* who = "gps_kernel_precond_solve";
+  if (!h || n < 0 || T < 0 || d_all <= 0 || rank_max < 1) return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": bad argument");
+  if (int rf = pchol_check(h, who, rank_max, rel_tol, noise_var)) return rf;
+  int rc = kmvm_begin(h, who, prog, n_nodes);
+  if (rc) return rc;
+  if (!logdet_out || !rank_out) return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": bad argument");
+  *logdet_out = 0.0; *rank_out = 0;
+  if (n == 0) return GPS_OK;
+  if (!X || (T > 0 && (!V || !out))) return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": bad argument");
+  KmvmPlan plan;
+  rc = kmvm_sym_plan(h, prog, n_nodes, X, n, d_all, &plan);
+  if (rc) return rc;
+  PcholPre pre;
+  rc = pchol_build(h, who, plan, n, noise_var, rank_max, rel_tol, true, &pre);
+  if (rc) return rc;
+  *logdet_out = pre.logdet; *rank_out = pre.rank;
+  if (T == 0) return GPS_OK;
+  const i64 np = plan.npr;
+  GPS_HIP(h, h->dStage.ensure((size_t)n * T * 8));
+  GPS_HIP(h, hipMemcpyAsync(h->dStage.p, V, (size_t)n * T * 8, hipMemcpyHostToDevice, h->stream));
+  if (G1) {
+    GPS_HIP(h, h->dTmp.ensure((size_t)rank_max * T * 8));
+    GPS_HIP(h, hipMemcpyAsync(h->dTmp.p, G1, (size_t)rank_max * T * 8, hipMemcpyHostToDevice, h->stream));
+  }
+  for (i64 c0 = 0; c0 < T; c0 += KCG_MAXT) {
+    const i64 tc = T - c0 < KCG_MAXT ? T - c0 : KCG_MAXT, tp = kmvm_tpad(tc);
+    GPS_HIP(h, h->dG1.ensure((size_t)np * tp * 8));
+    rc = kmvm_pad_cols(h, h->dStage.d(), T, n, c0, tc, h->dG1.d(), np, tp);
+    if (rc) return rc;
+    double* o = pre.ws + pre.o_z;
+    if (G1) {                                                // the sample L G1 + sqrt(noise) V
+      rc = gps_launch_pad_copy(h, h->dTmp.d() + c0, T, rank_max, tc, pre.ws + pre.o_S, 64, pre.kp, 64, 0, 0.0);
+      if (rc) return rc;
+      rc = gps_launch_pchol_ls(h, pre, h->dG1.d(), tp, sqrt(noise_var), 1.0, 0, -1.0, o, nullptr, nullptr);
+    } else rc = gps_launch_pchol_apply(h, pre, h->dG1.d(), tp, o, nullptr, nullptr);
+    if (rc) return rc;
+    rc = gps_launch_extract(h, o, tp, n, tc, h->dStage.d() + c0, T, 0);
+    if (rc) return rc;
+  }
+  GPS_HIP(h, hipMemcpyAsync(out, h->dStage.p, (size_t)n * T * 8, hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipStreamSynchronize(h->stream));
   return GPS_OK;
 }
 
@@ -162,13 +311,28 @@ extern "C" int gps_kmvm(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes
 // gps_kernel_cg, and with coef_out (host [max_iter][2][T]: alpha_k, beta_k of column t at [k][0][t], [k][1][t] for k below the
 // column's iteration count, zeros after) gps_kernel_cg_lanczos: the loop records its coefficients on the device (dLanczos) and they
 // are read once a batch, after the loop
+// pc (gps_kernel_pcg): the loop preconditioned by the rank-pc->rank_max pivoted-Cholesky M, built here; the last n_probe columns of B
+// are probes -- with G1 they arrive as Gaussian G2 and become Z = L G1 + sqrt(noise) G2 on the device first -- whose Z, M^-1 Z and
+// z^T M^-1 z go back beside the solve's outputs
+struct PcgOpts {
+  int rank_max; double rel_tol; const double* G1; int64_t n_probe;
+  double* Z_out; double* MinvZ_out; double* zmz_out; double* logdet_out; int64_t* rank_out;
+};
 static int kernel_cg_impl(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n,
                           int64_t d_all, double noise_var, const double* B, int64_t T, int max_iter, double tol, double* x_out,
-                          int64_t* iters_out, double* relres_out, int* converged_out, double* coef_out) {
+                          int64_t* iters_out, double* relres_out, int* converged_out, double* coef_out, const PcgOpts* pc = nullptr) {
   const std::string bad = std::string(who) + ": bad argument";
   if (!h || n < 0 || T < 0 || d_all <= 0 || max_iter < 0 || !(tol >= 0.0) || !(noise_var >= 0.0)) return gps_fail(h, GPS_ERR_ARG, bad);
+  if (pc) {
+    if (int rf = pchol_check(h, who, pc->rank_max, pc->rel_tol, noise_var)) return rf;
+    if (pc->n_probe < 0 || pc->n_probe > T || (pc->n_probe > 0 && (pc->rank_max == 0 || !pc->Z_out || !pc->MinvZ_out || !pc->zmz_out)))
+      return gps_fail(h, GPS_ERR_ARG, bad);
+    if (pc->rank_max == 0) pc = nullptr;
+  }
   int rc = kmvm_begin(h, who, prog, n_nodes);
   if (rc) return rc;
+  if (pc && pc->logdet_out) *pc->logdet_out = 0.0;
+  if (pc && pc->rank_out) *pc->rank_out = 0;
   if (n == 0 || T == 0) return GPS_OK;
   if (!X || !B || !x_out || !iters_out || !relres_out || !converged_out) return gps_fail(h, GPS_ERR_ARG, bad);
   std::vector<double> hz;
@@ -182,6 +346,22 @@ static int kernel_cg_impl(gps_handle_t h, const char* who, const gps_kern_node_t
   const i64 np = plan.npr;
   GPS_HIP(h, h->dStage.ensure((size_t)n * T * 8));
   GPS_HIP(h, hipMemcpyAsync(h->dStage.p, B, (size_t)n * T * 8, hipMemcpyHostToDevice, h->stream));
+  PcholPre pre;
+  const i64 np0 = pc ? T - pc->n_probe : T;                  // first probe column
+  if (pc) {
+    rc = pchol_build(h, who, plan, n, noise_var, pc->rank_max, pc->rel_tol, true, &pre);
+    if (rc) return rc;
+    if (pc->logdet_out) *pc->logdet_out = pre.logdet;
+    if (pc->rank_out) *pc->rank_out = pre.rank;
+    if (pc->n_probe > 0) {
+      // dTmp: G1 as uploaded [rank_max, n_probe] ; dTmp2: Z | M^-1 Z [n, n_probe] each, on their way back
+      GPS_HIP(h, h->dTmp2.ensure((size_t)2 * n * pc->n_probe * 8));
+      if (pc->G1) {
+        GPS_HIP(h, h->dTmp.ensure((size_t)pc->rank_max * pc->n_probe * 8));
+        GPS_HIP(h, hipMemcpyAsync(h->dTmp.p, pc->G1, (size_t)pc->rank_max * pc->n_probe * 8, hipMemcpyHostToDevice, h->stream));
+      }
+    }
+  }
   for (i64 c0 = 0; c0 < T; c0 += KCG_MAXT) {
     const i64 tc = T - c0 < KCG_MAXT ? T - c0 : KCG_MAXT, tp = kmvm_tpad(tc);
     KcgBufs b;
@@ -190,9 +370,42 @@ static int kernel_cg_impl(gps_handle_t h, const char* who, const gps_kern_node_t
     GPS_HIP(h, h->dG1.ensure((size_t)np * tp * 8));
     rc = kmvm_pad_cols(h, h->dStage.d(), T, n, c0, tc, h->dG1.d(), np, tp);
     if (rc) return rc;
+    if (pc && c0 + tc > np0) {
+      // the batch's probe columns: local columns l0 .. tc - 1 are the probes q0 .. of the call
+      const i64 l0 = np0 > c0 ? np0 - c0 : 0, q0 = c0 + l0 - np0, nq = tc - l0;
+      double* dZ = h->dTmp2.d();
+      double* dMz = dZ + (size_t)n * pc->n_probe;
+      if (pc->G1) {
+        double* S = pre.ws + pre.o_S;
+        rc = gps_launch_pad_copy(h, h->dTmp.d() + q0, pc->n_probe, pc->rank_max, nq, S + l0, 64, pre.kp, 64 - l0, 0, 0.0);
+        if (rc) return rc;
+        if (l0 > 0) {
+          rc = gps_launch_pad_copy(h, S, 64, 0, 0, S, 64, pre.kp, l0, 0, 0.0);      // (no probes there: zero columns of S)
+          if (rc) return rc;
+        }
+        rc = gps_launch_pchol_ls(h, pre, h->dG1.d(), tp, sqrt(noise_var), 1.0, (int)l0, -1.0, h->dG1.d(), nullptr, nullptr);
+        if (rc) return rc;
+      }
+      rc = gps_launch_extract(h, h->dG1.d() + l0, tp, n, nq, dZ + q0, pc->n_probe, 0);
+      if (rc) return rc;
+      double* pz = pre.ws + pre.o_z;
+      double* prz = pre.ws + pre.o_rzpart;
+      rc = gps_launch_pchol_apply(h, pre, h->dG1.d(), tp, pz, prz, nullptr);
+      if (rc) return rc;
+      rc = gps_launch_extract(h, pz + l0, tp, n, nq, dMz + q0, pc->n_probe, 0);
+      if (rc) return rc;
+      std::vector<double> hp((size_t)pre.lsg * 64);
+      GPS_HIP(h, hipMemcpyAsync(hp.data(), prz, hp.size() * 8, hipMemcpyDeviceToHost, h->stream));
+      GPS_HIP(h, hipStreamSynchronize(h->stream));
+      for (i64 c = 0; c < nq; ++c) {
+        double s = 0.0;
+        for (int g = 0; g < pre.lsg; ++g) s += hp[(size_t)g * 64 + l0 + c];
+        pc->zmz_out[q0 + c] = s;
+      }
+    }
     int launched = 0;
     rc = kcg_solve(h, plan, n, b, h->dG1.d(), tp, noise_var, max_iter, tol, tc, iters_out + c0, relres_out + c0, converged_out + c0,
-                   coef_out ? h->dLanczos.d() : nullptr, &launched);
+                   coef_out ? h->dLanczos.d() : nullptr, &launched, pc ? &pre : nullptr);
     if (rc) return rc;
     if (coef_out && launched > 0) {
       hz.resize((size_t)launched * 2 * KCG_MAXT);
@@ -207,6 +420,11 @@ static int kernel_cg_impl(gps_handle_t h, const char* who, const gps_kern_node_t
     if (rc) return rc;
   }
   GPS_HIP(h, hipMemcpyAsync(x_out, h->dStage.p, (size_t)n * T * 8, hipMemcpyDeviceToHost, h->stream));
+  if (pc && pc->n_probe > 0) {
+    const size_t zb = (size_t)n * pc->n_probe * 8;
+    GPS_HIP(h, hipMemcpyAsync(pc->Z_out, h->dTmp2.p, zb, hipMemcpyDeviceToHost, h->stream));
+    GPS_HIP(h, hipMemcpyAsync(pc->MinvZ_out, (char*)h->dTmp2.p + zb, zb, hipMemcpyDeviceToHost, h->stream));
+  }
   GPS_HIP(h, hipStreamSynchronize(h->stream));
   return GPS_OK;
 }
@@ -224,6 +442,16 @@ extern "C" int gps_kernel_cg_lanczos(gps_handle_t h, const gps_kern_node_t* prog
   if (!coef_out && max_iter > 0 && T > 0) return gps_fail(h, GPS_ERR_ARG, "gps_kernel_cg_lanczos: bad argument");
   return kernel_cg_impl(h, "gps_kernel_cg_lanczos", prog, n_nodes, X, n, d_all, noise_var, B, T, max_iter, tol, x_out, iters_out,
                         relres_out, converged_out, coef_out);
+}
+
+extern "C" int gps_kernel_pcg(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                              double noise_var, const double* B, int64_t T, int max_iter, double tol, int rank_max, double rel_tol,
+                              const double* G1, int64_t n_probe, double* x_out, int64_t* iters_out, double* relres_out,
+                              int* converged_out, double* coef_out, double* Z_out, double* MinvZ_out, double* zmz_out,
+                              double* logdet_out, int64_t* rank_out) {
+  const PcgOpts pc = {rank_max, rel_tol, G1, n_probe, Z_out, MinvZ_out, zmz_out, logdet_out, rank_out};
+  return kernel_cg_impl(h, "gps_kernel_pcg", prog, n_nodes, X, n, d_all, noise_var, B, T, max_iter, tol, x_out, iters_out, relres_out,
+                        converged_out, coef_out, &pc);
 }
 
 // The fused gradient form (kmvm.hip): slots_out [1 + n_dims (+ 1: RatQuad's alpha)] = sum_ij (P Q^T)_ij dK_ij / d theta_slot in the
@@ -279,16 +507,20 @@ extern "C" int gps_kmvm_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_
   return GPS_OK;
 }
 
-extern "C" int gps_kernel_predict(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
-                                  double noise_var, const double* resid, int64_t r, const double* Xnew, int64_t n_new, int max_iter,
-                                  double tol, double* mean_out, double* var_out, int64_t* iters_out, double* relres_out, int* converged_out) {
+// gps_kernel_predict, and with rank_max > 0 gps_kernel_predict_pcg: every solve below preconditioned by one M, built once a call
+static int kernel_predict_impl(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n,
+                               int64_t d_all, double noise_var, const double* resid, int64_t r, const double* Xnew, int64_t n_new,
+                               int max_iter, double tol, int rank_max, double rel_tol, double* mean_out, double* var_out,
+                               int64_t* iters_out, double* relres_out, int* converged_out) {
+  const std::string bad = std::string(who) + ": bad argument";
   if (!h || n <= 0 || r <= 0 || n_new < 0 || d_all <= 0 || max_iter < 0 || !(tol >= 0.0) || !(noise_var >= 0.0))
-    return gps_fail(h, GPS_ERR_ARG, "gps_kernel_predict: bad argument");
-  int rc = kmvm_begin(h, "gps_kernel_predict", prog, n_nodes);
+    return gps_fail(h, GPS_ERR_ARG, bad);
+  if (int rf = pchol_check(h, who, rank_max, rel_tol, noise_var)) return rf;
+  int rc = kmvm_begin(h, who, prog, n_nodes);
   if (rc) return rc;
   if (n_new == 0) return GPS_OK;
   if (!X || !resid || !Xnew || !mean_out || !var_out || !iters_out || !relres_out || !converged_out)
-    return gps_fail(h, GPS_ERR_ARG, "gps_kernel_predict: bad argument");
+    return gps_fail(h, GPS_ERR_ARG, bad);
   double kdiag = 0.0;
   rc = gps_launch_kdiag(h, prog, n_nodes, &kdiag);
   if (rc) return rc;
@@ -296,6 +528,13 @@ extern "C" int gps_kernel_predict(gps_handle_t h, const gps_kern_node_t* prog, i
   rc = kmvm_sym_plan(h, prog, n_nodes, X, n, d_all, &plan);
   if (rc) return rc;
   const i64 np = plan.npr, nsp = pad64(n_new);
+  PcholPre pre;
+  const PcholPre* pp = nullptr;
+  if (rank_max > 0) {
+    rc = pchol_build(h, who, plan, n, noise_var, rank_max, rel_tol, true, &pre);
+    if (rc) return rc;
+    pp = &pre;
+  }
   GPS_HIP(h, h->dXnew.ensure((size_t)n_new * d_all * 8));
   GPS_HIP(h, hipMemcpyAsync(h->dXnew.p, Xnew, (size_t)n_new * d_all * 8, hipMemcpyHostToDevice, h->stream));
   // ---- the mean: alpha batch by batch, each pushed through K(Xnew, X) at once
@@ -315,7 +554,8 @@ extern "C" int gps_kernel_predict(gps_handle_t h, const gps_kern_node_t* prog, i
     GPS_HIP(h, h->dG3.ensure((size_t)nsp * tp * 8));
     rc = kmvm_pad_cols(h, h->dStage.d(), r, n, c0, tc, h->dG1.d(), np, tp);
     if (rc) return rc;
-    rc = kcg_solve(h, plan, n, b, h->dG1.d(), tp, noise_var, max_iter, tol, tc, iters_out + c0, relres_out + c0, converged_out + c0);
+    rc = kcg_solve(h, plan, n, b, h->dG1.d(), tp, noise_var, max_iter, tol, tc, iters_out + c0, relres_out + c0, converged_out + c0,
+                   nullptr, nullptr, pp);
     if (rc) return rc;
     rc = gps_launch_kmvm(h, cross, b.x, tp, tp, 0.0, h->dG3.d(), tp, nullptr);
     if (rc) return rc;
@@ -337,7 +577,8 @@ extern "C" int gps_kernel_predict(gps_handle_t h, const gps_kern_node_t* prog, i
     if (rc) return rc;
     rc = gps_launch_transpose(h, h->dTmp.d(), np, 16, np, h->dG2.d(), 16);        // rows nb .. 15 and columns n .. np - 1: zeros
     if (rc) return rc;
-    rc = kcg_solve(h, plan, n, b, h->dG2.d(), 16, noise_var, max_iter, tol, nb, iters_out + r + j0, relres_out + r + j0, converged_out + r + j0);
+    rc = kcg_solve(h, plan, n, b, h->dG2.d(), 16, noise_var, max_iter, tol, nb, iters_out + r + j0, relres_out + r + j0, converged_out + r + j0,
+                   nullptr, nullptr, pp);
     if (rc) return rc;
     rc = gps_launch_kcg_coldot(h, nullptr, 0, h->dG2.d(), b.x, np, 1, b.part0);
     if (rc) return rc;
@@ -351,4 +592,19 @@ extern "C" int gps_kernel_predict(gps_handle_t h, const gps_kern_node_t* prog, i
   }
   GPS_HIP(h, hipStreamSynchronize(h->stream));
   return GPS_OK;
+}
+
+extern "C" int gps_kernel_predict(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                                  double noise_var, const double* resid, int64_t r, const double* Xnew, int64_t n_new, int max_iter,
+                                  double tol, double* mean_out, double* var_out, int64_t* iters_out, double* relres_out, int* converged_out) {
+  return kernel_predict_impl(h, "gps_kernel_predict", prog, n_nodes, X, n, d_all, noise_var, resid, r, Xnew, n_new, max_iter, tol, 0, 0.0,
+                             mean_out, var_out, iters_out, relres_out, converged_out);
+}
+
+extern "C" int gps_kernel_predict_pcg(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                                      double noise_var, const double* resid, int64_t r, const double* Xnew, int64_t n_new, int max_iter,
+                                      double tol, int rank_max, double rel_tol, double* mean_out, double* var_out, int64_t* iters_out,
+                                      double* relres_out, int* converged_out) {
+  return kernel_predict_impl(h, "gps_kernel_predict_pcg", prog, n_nodes, X, n, d_all, noise_var, resid, r, Xnew, n_new, max_iter, tol,
+                             rank_max, rel_tol, mean_out, var_out, iters_out, relres_out, converged_out);
 }

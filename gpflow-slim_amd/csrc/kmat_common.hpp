@@ -231,10 +231,32 @@ int gps_launch_kcg_init(gps_handle_t h, KcgState* st, const double* B, double* r
 // (rows: the rows the kernel walks -- the real points inside the loop, so that the padded rows of r and p stay 0)
 int gps_launch_kcg_coldot(gps_handle_t h, const KcgState* st, int it, const double* A, const double* Bm, i64 rows, int tb, double* part);
 int gps_launch_kcg_update(gps_handle_t h, const KcgState* st, int it, const double* part_pap, const double* p, const double* Ap,
-                          double* x, double* r, i64 rows, int tb, double* part_rr, double* lz);
+                          double* x, double* r, i64 rows, int tb, double* part_rr, double* lz, const double* rzs = nullptr);
 int gps_launch_kcg_dir(gps_handle_t h, KcgState* st, int it, const double* part_rr, const double* r, double* p, i64 rows, int tb,
                        double* lz);
 // lz of the two above: optional device [max_iter][2][KCG_MAXT], alpha_it and beta_it of every live column (NULL: none)
+// rzs of gps_launch_kcg_update: NULL, or the preconditioned loop's r^T z per column, device [2][KCG_MAXT] by iteration parity: the
+// step's numerator in place of r^T r.  gps_launch_pcg_dir is that loop's direction kernel: beta = (r^T z)_new / (r^T z)_old from
+// the nblk_rz partial rows part_rz, p = z + beta p, the next state (the stop rule stays on r^T r); it < 0: the start, p = z and
+// rzs[0] alone.
+int gps_launch_pcg_dir(gps_handle_t h, KcgState* st, int it, const double* part_rr, const double* part_rz, int nblk_rz, const double* z,
+                       double* p, i64 rows, int tb, double* lz, double* rzs);
+
+// pchol.hip : the pivoted-Cholesky preconditioner M = L L^T + noise I of the loop above (see there).  One workspace `ws` (doubles,
+// gps_pchol_workspace fills the offsets) beside L [np][kp].
+struct PcholState { int rank; int done; int pad[2]; double trace; };
+struct PcholPre {
+  i64 np; int kp, nblk, gb, tg, lsg;
+  double* L; double* ws; double noise;
+  size_t o_d, o_pv, o_pi, o_piv, o_st, o_C, o_W, o_part, o_S, o_rzpart, o_rzs, o_z;
+  int rank; double logdet;                 // (host copies, after the build)
+};
+size_t gps_pchol_workspace(i64 np, int kp, PcholPre* pre);      // bytes of ws
+int gps_launch_pchol_factor(gps_handle_t h, const KmvmPlan& plan, i64 n, int cap, double rel_tol, const PcholPre& pre);
+int gps_launch_pchol_gram(gps_handle_t h, const PcholPre& pre, double noise);
+int gps_launch_pchol_ls(gps_handle_t h, const PcholPre& pre, const double* V, i64 tp, double c1, double c1lo, int col0, double c2,
+                        double* out, double* part, const int* skip);
+int gps_launch_pchol_apply(gps_handle_t h, const PcholPre& pre, const double* V, i64 tp, double* out, double* part, const int* skip);
 // kmvm.hip : the fused gradient form  sum_ij G_ij dK_ij / d theta  for K(X, X) and G = P Q^T, one pass of at most 64 weight columns
 // (32 where P != Q: the pass runs [P | Q], [Q | P] and the caller halves).  P, Q device [n, ldc], columns c0 .. c0 + tc - 1; Pt, Qt:
 // room for [64][npr] doubles each; scale: host [nf + 3] factors; vals_out: device [nf + 3] = scale o [sum G K, one raw sum per

@@ -587,7 +587,8 @@ __global__ __launch_bounds__(256) void kcg_coldot_kernel(const KcgState* __restr
 __global__ __launch_bounds__(256) void kcg_update_kernel(const KcgState* __restrict__ st, int it, const double* __restrict__ part_pap,
                                                          int nblk, const double* __restrict__ p, const double* __restrict__ Ap,
                                                          double* __restrict__ x, double* __restrict__ r, i64 rows, int tb,
-                                                         double* __restrict__ part_rr, double* __restrict__ lz) {
+                                                         double* __restrict__ part_rr, double* __restrict__ lz,
+                                                         const double* __restrict__ rzs) {
   const int cur = it & 1;
   if (st->all_done[cur]) return;
   __shared__ double sh[256];
@@ -602,7 +603,7 @@ __global__ __launch_bounds__(256) void kcg_update_kernel(const KcgState* __restr
     const int t = 16 * b + c;
     live[b] = b < tb && !st->done[cur][t];
     const double pap = tot[t];
-    al[b] = (live[b] && pap > 0.0) ? st->rr[cur][t] / pap : 0.0;
+    al[b] = (live[b] && pap > 0.0) ? (rzs ? rzs[cur * KCG_MAXT + t] : st->rr[cur][t]) / pap : 0.0;      // (rzs: the preconditioned loop's r^T z)
     if (lz && blockIdx.x == 0 && rl == 0 && live[b]) lz[((i64)it * 2 + 0) * KCG_MAXT + t] = al[b];      // (Lanczos: alpha_it of a live column)
   }
   for (i64 row = (i64)blockIdx.x * 16 + rl; row < rows; row += (i64)gridDim.x * 16)
@@ -669,6 +670,73 @@ __global__ __launch_bounds__(256) void kcg_dir_kernel(KcgState* __restrict__ st,
   }
 }
 
+// The preconditioned loop's direction kernel (z = M^-1 r from pchol.hip, which also left the partials of r^T z):
+// beta_t = (r^T z)_new / (r^T z)_old ; p = z + beta p ; workgroup 0 writes the next state and rzs[next].  The stop rule is
+// kcg_dir_kernel's, on the unpreconditioned r^T r.  it < 0: the start -- p = z, rzs[0] = r^T z, the state as kcg_start_kernel left it.
+__global__ __launch_bounds__(256) void pcg_dir_kernel(KcgState* __restrict__ st, int it, const double* __restrict__ part_rr, int nblk,
+                                                      const double* __restrict__ part_rz, int nblk_rz, const double* __restrict__ z,
+                                                      double* __restrict__ p, i64 rows, int tb, double* __restrict__ lz,
+                                                      double* __restrict__ rzs) {
+  const bool start = it < 0;
+  const int cur = start ? 0 : (it & 1), nxt = cur ^ 1;
+  if (st->all_done[cur]) {
+    if (!start && blockIdx.x == 0 && threadIdx.x < 64) {
+      const int t = threadIdx.x;
+      st->rr[nxt][t] = st->rr[cur][t]; st->k[nxt][t] = st->k[cur][t]; st->done[nxt][t] = 1;
+      rzs[nxt * KCG_MAXT + t] = rzs[cur * KCG_MAXT + t];
+      if (t == 0) st->all_done[nxt] = 1;
+    }
+    return;
+  }
+  __shared__ double sh[256];
+  __shared__ double tot[64];
+  __shared__ double totz[64];
+  __shared__ int nd[64];
+  kcg_fold(part_rz, nblk_rz, sh, totz);
+  const int c = threadIdx.x & 15, rl = threadIdx.x >> 4;
+  const i64 ld = 16 * tb;
+  if (start) {
+    for (i64 row = (i64)blockIdx.x * 16 + rl; row < rows; row += (i64)gridDim.x * 16)
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+        if (b < tb) { const i64 e = row * ld + 16 * b + c; p[e] = z[e]; }
+    if (blockIdx.x == 0 && threadIdx.x < 64) { rzs[threadIdx.x] = totz[threadIdx.x]; rzs[KCG_MAXT + threadIdx.x] = totz[threadIdx.x]; }
+    return;
+  }
+  kcg_fold(part_rr, nblk, sh, tot);
+  double be[4];
+  bool live[4];
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const int t = 16 * b + c;
+    live[b] = b < tb && !st->done[cur][t];
+    be[b] = live[b] ? totz[t] / rzs[cur * KCG_MAXT + t] : 0.0;
+    if (lz && blockIdx.x == 0 && rl == 0 && live[b]) lz[((i64)it * 2 + 1) * KCG_MAXT + t] = be[b];
+  }
+  for (i64 row = (i64)blockIdx.x * 16 + rl; row < rows; row += (i64)gridDim.x * 16)
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+      if (live[b]) { const i64 e = row * ld + 16 * b + c; p[e] = fma(be[b], p[e], z[e]); }
+  if (blockIdx.x != 0) return;
+  if (threadIdx.x < 64) {
+    const int t = threadIdx.x;
+    int done = st->done[cur][t], k = st->k[cur][t];
+    double rr = st->rr[cur][t], rz = rzs[cur * KCG_MAXT + t];
+    if (!done) {
+      rr = tot[t]; rz = totz[t]; k += 1;
+      done = (rr <= st->tol2 * st->bb[t]) || k >= st->max_iter || !(rr == rr) || !(rz == rz);
+    }
+    st->rr[nxt][t] = rr; st->k[nxt][t] = k; st->done[nxt][t] = done; nd[t] = done;
+    rzs[nxt * KCG_MAXT + t] = rz;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int all = 1;
+    for (int t = 0; t < 64; ++t) all &= nd[t];
+    st->all_done[nxt] = all;
+  }
+}
+
 // ---- launchers -------------------------------------------------------------------------------------------------------------------
 int gps_kcg_blocks(i64 npad) {
   const i64 b = (npad + 15) / 16;
@@ -698,10 +766,18 @@ int gps_launch_kcg_coldot(gps_handle_t h, const KcgState* st, int it, const doub
 }
 
 int gps_launch_kcg_update(gps_handle_t h, const KcgState* st, int it, const double* part_pap, const double* p, const double* Ap,
-                          double* x, double* r, i64 rows, int tb, double* part_rr, double* lz) {
+                          double* x, double* r, i64 rows, int tb, double* part_rr, double* lz, const double* rzs) {
   const int nblk = gps_kcg_blocks(rows);
   const double el = (double)rows * 16.0 * tb;
-  KCG_LAUNCH(kcg_update_kernel, nblk, 6.0 * el, 48.0 * el, st, it, part_pap, nblk, p, Ap, x, r, rows, tb, part_rr, lz);
+  KCG_LAUNCH(kcg_update_kernel, nblk, 6.0 * el, 48.0 * el, st, it, part_pap, nblk, p, Ap, x, r, rows, tb, part_rr, lz, rzs);
+  return GPS_OK;
+}
+
+int gps_launch_pcg_dir(gps_handle_t h, KcgState* st, int it, const double* part_rr, const double* part_rz, int nblk_rz, const double* z,
+                       double* p, i64 rows, int tb, double* lz, double* rzs) {
+  const int nblk = gps_kcg_blocks(rows);
+  const double el = (double)rows * 16.0 * tb;
+  KCG_LAUNCH(pcg_dir_kernel, nblk, 2.0 * el, 24.0 * el, st, it, part_rr, nblk, part_rz, nblk_rz, z, p, rows, tb, lz, rzs);
   return GPS_OK;
 }
 

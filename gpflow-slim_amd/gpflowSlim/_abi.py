@@ -289,6 +289,12 @@ _SIGNATURES = {
     "gps_kernel_cg_lanczos": [_vp, _prog, _int, _dp, _i64, _i64, _dbl, _dp, _i64, _int, _dbl, _dp, _i64p, _dp, _ip, _dp],
     "gps_kmvm_grad": [_vp, _prog, _int, _dp, _i64, _i64, _dp, _dp, _i64, _dp, _dp],
     "gps_kernel_predict": [_vp, _prog, _int, _dp, _i64, _i64, _dbl, _dp, _i64, _dp, _i64, _int, _dbl, _dp, _dp, _i64p, _dp, _ip],
+    "gps_kernel_pchol": [_vp, _prog, _int, _dp, _i64, _i64, _int, _dbl, _dp, _i64p, _i64p, _dp],
+    "gps_kernel_precond_solve": [_vp, _prog, _int, _dp, _i64, _i64, _dbl, _int, _dbl, _dp, _i64, _dp, _dp, _dp, _i64p],
+    "gps_kernel_pcg": [_vp, _prog, _int, _dp, _i64, _i64, _dbl, _dp, _i64, _int, _dbl, _int, _dbl, _dp, _i64, _dp, _i64p, _dp, _ip, _dp,
+                       _dp, _dp, _dp, _dp, _i64p],
+    "gps_kernel_predict_pcg": [_vp, _prog, _int, _dp, _i64, _i64, _dbl, _dp, _i64, _dp, _i64, _int, _dbl, _int, _dbl, _dp, _dp, _i64p,
+                               _dp, _ip],
     "gps_sparse_last_terms": [_vp, _dp],
     "gps_profile_enable": [_vp, _int],
     "gps_profile_reset": [_vp],

@@ -1343,3 +1343,85 @@ def kernel_predict(h, prog, X, noise_var, resid, Xnew, max_iter=1000, tol=1e-8):
             int(max_iter), float(tol), _ptr(mean), _ptr(var), iters.ctypes.data_as(ctypes.POINTER(_i64)), _ptr(rel),
             conv.ctypes.data_as(_c_int_p))
     return mean, var, iters, rel, conv != 0
+
+
+# ---- the pivoted-Cholesky preconditioner of the matrix-free path (csrc/pchol.hip) -------------------------------------------------------
+# Module functions like the ones above: the preconditioner is rebuilt inside every call and nothing stays resident.
+def _check_precond(rank, rel_tol, noise_var=None):
+    """The refusals of every entry that takes a rank, before anything touches the device."""
+    _need(isinstance(rank, (int, np.integer)) and 0 <= rank <= 128, "the preconditioner's rank must be an integer in 0 .. 128")
+    _need(rel_tol >= 0.0, "rel_tol must be >= 0")
+    _need(rank == 0 or noise_var is None or noise_var > 0.0, "a preconditioner needs a noise variance > 0 (M = L L^T + noise I)")
+
+
+def kernel_pchol(h, prog, X, rank_max, rel_tol=1e-10):
+    """gps_kernel_pchol: (L [n, rank], pivots [rank], residual trace) of the rank-capped pivoted partial Cholesky of K(X, X)."""
+    X = _f64(X)
+    _need(X.ndim == 2, "X must be [N, D]")
+    _check_precond(rank_max, rel_tol)
+    _need(rank_max >= 1, "the factor's rank cap must be 1 .. 128")
+    n = X.shape[0]
+    L, piv = np.zeros((n, int(rank_max))), np.zeros(int(rank_max), dtype=np.int64)
+    rank, trace = np.zeros(1, dtype=np.int64), np.zeros(1)
+    h._drop_resident()
+    h._call("gps_kernel_pchol", prog, len(prog), _ptr(X), n, X.shape[1], int(rank_max), float(rel_tol), _ptr(L),
+            piv.ctypes.data_as(ctypes.POINTER(_i64)), rank.ctypes.data_as(ctypes.POINTER(_i64)), _ptr(trace))
+    k = int(rank[0])
+    return np.ascontiguousarray(L[:, :k]), piv[:k], float(trace[0])
+
+
+def kernel_precond_solve(h, prog, X, V, noise_var, rank_max, rel_tol=1e-10, G1=None):
+    """gps_kernel_precond_solve: (M^-1 V [n, T] -- or the sample L G1 + sqrt(noise) V with G1 [rank_max, T] --, log det M, rank)."""
+    X, V = _f64(X), _f64(V)
+    _need(X.ndim == 2 and V.ndim == 2 and V.shape[0] == X.shape[0], "X must be [N, D] and V [N, T]")
+    _check_precond(rank_max, rel_tol, noise_var)
+    _need(rank_max >= 1, "the preconditioner's rank cap must be 1 .. 128 here")
+    if G1 is not None:
+        G1 = _f64(G1)
+        _need(G1.shape == (int(rank_max), V.shape[1]), "G1 must be [rank_max, T]")
+    n, T = V.shape
+    out, logdet, rank = np.zeros((n, T)), np.zeros(1), np.zeros(1, dtype=np.int64)
+    h._drop_resident()
+    h._call("gps_kernel_precond_solve", prog, len(prog), _ptr(X), n, X.shape[1], float(noise_var), int(rank_max), float(rel_tol),
+            _ptr(V), T, _opt(G1), _ptr(out), _ptr(logdet), rank.ctypes.data_as(ctypes.POINTER(_i64)))
+    return out, float(logdet[0]), int(rank[0])
+
+
+def kernel_pcg(h, prog, X, B, noise_var, rank_max, rel_tol=1e-10, max_iter=1000, tol=1e-8, n_probe=0, G1=None):
+    """gps_kernel_pcg: kernel_cg_lanczos's six results, then (Z [n, n_probe], M^-1 Z, z^T M^-1 z [n_probe], log det M, rank)."""
+    X, B = _f64(X), _f64(B)
+    _need(X.ndim == 2 and B.ndim == 2 and B.shape[0] == X.shape[0], "X must be [N, D] and B [N, T]")
+    _check_precond(rank_max, rel_tol, noise_var)
+    n, T = B.shape
+    n_probe = int(n_probe)
+    _need(0 <= n_probe <= T and (n_probe == 0 or rank_max > 0), "n_probe must be 0 .. T, and probes need a rank")
+    if G1 is not None:
+        G1 = _f64(G1)
+        _need(G1.shape == (int(rank_max), n_probe), "G1 must be [rank_max, n_probe]")
+    x, iters, rel, conv = np.zeros((n, T)), np.zeros(T, dtype=np.int64), np.zeros(T), np.zeros(T, dtype=np.intc)
+    coef = np.zeros((max(int(max_iter), 1), 2, T))
+    Z, MiZ, zmz = np.zeros((n, n_probe)), np.zeros((n, n_probe)), np.zeros(n_probe)
+    logdet, rank = np.zeros(1), np.zeros(1, dtype=np.int64)
+    h._drop_resident()
+    h._call("gps_kernel_pcg", prog, len(prog), _ptr(X), n, X.shape[1], float(noise_var), _ptr(B), T, int(max_iter), float(tol),
+            int(rank_max), float(rel_tol), _opt(G1), n_probe, _ptr(x), iters.ctypes.data_as(ctypes.POINTER(_i64)), _ptr(rel),
+            conv.ctypes.data_as(_c_int_p), _ptr(coef), _ptr(Z), _ptr(MiZ), _ptr(zmz), _ptr(logdet),
+            rank.ctypes.data_as(ctypes.POINTER(_i64)))
+    return x, iters, rel, conv != 0, coef[:, 0, :], coef[:, 1, :], Z, MiZ, zmz, float(logdet[0]), int(rank[0])
+
+
+def kernel_predict_pcg(h, prog, X, noise_var, resid, Xnew, rank_max, rel_tol=1e-10, max_iter=1000, tol=1e-8):
+    """gps_kernel_predict_pcg: kernel_predict's results with every solve preconditioned."""
+    X, resid, Xnew = _f64(X), _f64(resid), _f64(Xnew)
+    _need(X.ndim == 2 and resid.ndim == 2 and resid.shape[0] == X.shape[0] and X.shape[0] > 0 and resid.shape[1] > 0,
+          "X must be [N, D] and the residual [N, R]")
+    _need(Xnew.ndim == 2 and Xnew.shape[1] == X.shape[1], "Xnew must be [N*, %d]" % X.shape[1])
+    _check_precond(rank_max, rel_tol, noise_var)
+    n, r, n_new = X.shape[0], resid.shape[1], Xnew.shape[0]
+    mean, var = np.zeros((n_new, r)), np.zeros(n_new)
+    iters, rel, conv = np.zeros(r + n_new, dtype=np.int64), np.zeros(r + n_new), np.zeros(r + n_new, dtype=np.intc)
+    h._drop_resident()
+    h._call("gps_kernel_predict_pcg", prog, len(prog), _ptr(X), n, X.shape[1], float(noise_var), _ptr(resid), r, _ptr(Xnew), n_new,
+            int(max_iter), float(tol), int(rank_max), float(rel_tol), _ptr(mean), _ptr(var),
+            iters.ctypes.data_as(ctypes.POINTER(_i64)), _ptr(rel), conv.ctypes.data_as(_c_int_p))
+    return mean, var, iters, rel, conv != 0

@@ -66,17 +66,68 @@ def kernel_matmul(kern, X, V, X2=None, diag_add=0.0):
     return be.kmvm(be.get_handle(), prog, X, V, X2=X2, diag_add=diag_add)
 
 
-def kernel_cgsolver(kern, X, B, noise_var, max_iter=1000, tol=1e-8, lanczos=False):
+def _precond_program(kern, X, rank, rel_tol, noise_var=None):
+    """(X as the device takes it, the program) after the refusals of every call that takes a preconditioner's rank -- the kernel's
+    scope, the rank in 0 .. 128, a noise above 0 with a rank --, all before anything touches the device."""
+    X = np.ascontiguousarray(X, dtype=settings.float_type)
+    prog = _matrix_free_program(kern, X.shape[1])
+    be._check_precond(rank, rel_tol, None if noise_var is None else float(noise_var))
+    kern._check_inputs(X)
+    return X, prog
+
+
+def kernel_pivoted_cholesky(kern, X, rank, rel_tol=1e-10):
+    """(L [n, k], pivots [k], residual trace): the pivoted partial Cholesky factor of K(X, X) -- no noise -- built on the device
+    (csrc/pchol.hip), K ~ L L^T, with the largest residual diagonal entry as each step's pivot, ties to the lowest index.  k <= rank <= 128: the factor stops early once that entry is <= rel_tol * variance.  residual trace = tr(K - L L^T)."""
+    X, prog = _precond_program(kern, X, rank, rel_tol)
+    return be.kernel_pchol(be.get_handle(), prog, X, rank, rel_tol)
+
+
+def kernel_precond_solve(kern, X, V, noise_var, rank, rel_tol=1e-10, G1=None):
+    """(M^-1 V [n, T], log det M) for the preconditioner M = L L^T + noise_var I of kernel_cgsolver(precond_rank=rank), by Woodbury
+    on the device.  G1 [rank, T]: the sample L G1 + sqrt(noise_var) V of N(0, M) (G1, V standard normal) in place of M^-1 V."""
+    X, prog = _precond_program(kern, X, rank, rel_tol, noise_var)
+    out, logdet, _ = be.kernel_precond_solve(be.get_handle(), prog, X, V, noise_var, rank, rel_tol, G1=G1)
+    return out, logdet
+
+
+def _pcg(kern, X, B, noise_var, rank, rel_tol, max_iter, tol, n_probe=0, G1=None):
+    """be.kernel_pcg as (x, info): kernel_cgsolver(lanczos=True)'s info and 'logdet_M', 'rank', 'Z', 'MinvZ', 'zMz'"""
+    X, prog = _precond_program(kern, X, rank, rel_tol, noise_var)
+    x, iters, rel, conv, al, bt, Z, MiZ, zmz, logdet, k = be.kernel_pcg(be.get_handle(), prog, X, B, noise_var, rank, rel_tol,
+                                                                     max_iter=max_iter, tol=tol, n_probe=n_probe, G1=G1)
+    rows = int(np.max(iters)) if iters.size else 0
+    return x, {"iterations": iters, "relative_residual": rel, "converged": conv, "alpha": al[:rows], "beta": bt[:rows],
+               "logdet_M": logdet, "rank": k, "Z": Z, "MinvZ": MiZ, "zMz": zmz}
+
+
+def _probe_normals(seed, rank, n, num_probes):
+    """(G1 [rank, T], G2 [n, T]) standard normal from default_rng(seed): Z = L G1 + sqrt(noise) G2 ~ N(0, M)"""
+    rng = np.random.default_rng(seed)
+    return rng.standard_normal((int(rank), int(num_probes))), rng.standard_normal((n, int(num_probes)))
+
+
+def kernel_cgsolver(kern, X, B, noise_var, max_iter=1000, tol=1e-8, lanczos=False, precond_rank=0, precond_rel_tol=1e-10):
     """(K(X, X) + noise_var I) x = B by plain conjugate gradients from x = 0, the T columns of B at once.  A column stops when
     |r| <= tol |b| -- the unsquared norms; ``cgsolver`` above keeps the reference's rule, tol |b| against r^T r.  Returns
     (x [n, T], info) with info['iterations'] [T], info['relative_residual'] [T] (of the recurrence) and info['converged'] [T];
     a column that did not converge within max_iter is reported by a warning, not an error.  lanczos: info['alpha'] and
-    info['beta'] [iterations, T] as well, the recurrence's coefficients per column (rows below the column's iteration count)."""
+    info['beta'] [iterations, T] as well, the recurrence's coefficients per column (rows below the column's iteration count).
+    precond_rank (0 .. 128; 0: the plain loop, byte for byte): the loop preconditioned by M = L L^T + noise_var I, L the pivoted
+    partial Cholesky factor of that rank at most (kernel_pivoted_cholesky; rebuilt inside the call).  The stop rule stays on the
+    unpreconditioned residual; the coefficients are then those of M^-1/2 (K + noise_var I) M^-1/2, and info gains 'logdet_M'
+    and 'rank'."""
     import warnings
     X = np.ascontiguousarray(X, dtype=settings.float_type)
     prog = _matrix_free_program(kern, X.shape[1])
+    be._check_precond(precond_rank, precond_rel_tol, float(noise_var))
     kern._check_inputs(X)
-    if lanczos:
+    if precond_rank:
+        x, info = _pcg(kern, X, B, noise_var, precond_rank, precond_rel_tol, max_iter, tol)
+        rel = info["relative_residual"]
+        if not lanczos:
+            info = {k: info[k] for k in ("iterations", "relative_residual", "converged", "logdet_M", "rank")}
+    elif lanczos:
         x, iters, rel, conv, al, bt = be.kernel_cg_lanczos(be.get_handle(), prog, X, B, noise_var, max_iter=max_iter, tol=tol)
         rows = int(np.max(iters)) if iters.size else 0
         info = {"iterations": iters, "relative_residual": rel, "converged": conv, "alpha": al[:rows], "beta": bt[:rows]}
@@ -117,13 +168,28 @@ def lanczos_quadrature(alpha, beta, iterations):
     return out
 
 
-def kernel_logdet(kern, X, noise_var, probes=None, num_probes=16, seed=0, max_iter=1000, tol=1e-8):
+def kernel_logdet(kern, X, noise_var, probes=None, num_probes=16, seed=0, max_iter=1000, tol=1e-8, precond_rank=0,
+                  precond_rel_tol=1e-10):
     """log det (K(X, X) + noise_var I) by stochastic Lanczos quadrature (Gardner et al. 2018): one batched CG solve of the probes,
     whose coefficients are each probe's Lanczos tridiagonal.  probes [n, T]: Rademacher from ``np.random.default_rng(seed)``
     unless given.  Returns (estimate = mean of per_probe, per_probe [T] = |z_t|^2 e_1^T log(T_t) e_1 -- an estimate of
     z_t^T log(K_y) z_t --, info of the solve).  RuntimeError if a probe's solve did not converge: a cut-off recurrence is not an
-    estimate of anything."""
+    estimate of anything.
+    precond_rank > 0 (Gardner et al. 2018, section 4): with M = L L^T + noise_var I the estimate is log det M + mean of per_probe,
+    per_probe [T] = (z_t^T M^-1 z_t) e_1^T log(T_t) e_1 from the preconditioned solve of probes z_t ~ N(0, M): Z = L G1 +
+    sqrt(noise_var) G2 formed on the device from standard normals of ``default_rng(seed)`` unless ``probes`` are given, which are
+    used as Z as they are.  Only log det (M^-1 K_y) is estimated, so the spread falls with the rank."""
     X = np.ascontiguousarray(X, dtype=settings.float_type)
+    if precond_rank:
+        _precond_program(kern, X, precond_rank, precond_rel_tol, noise_var)
+        if probes is None:
+            G1, B = _probe_normals(seed, precond_rank, X.shape[0], num_probes)
+        else:
+            G1, B = None, np.ascontiguousarray(probes, dtype=settings.float_type)
+        _, info = _pcg(kern, X, B, noise_var, precond_rank, precond_rel_tol, max_iter, tol, n_probe=B.shape[1], G1=G1)
+        _raise_unconverged("kernel_logdet", info, tol, max_iter)
+        per_probe = info["zMz"] * lanczos_quadrature(info["alpha"], info["beta"], info["iterations"])
+        return float(info["logdet_M"] + np.mean(per_probe)), per_probe, info
     if probes is None:
         probes = np.random.default_rng(seed).integers(0, 2, size=(X.shape[0], int(num_probes))) * 2.0 - 1.0
     Z = np.ascontiguousarray(probes, dtype=settings.float_type)
@@ -138,8 +204,12 @@ def _solve_converged(who, kern, X, B, noise_var, max_iter, tol):
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         x, info = kernel_cgsolver(kern, X, B, noise_var, max_iter=max_iter, tol=tol, lanczos=True)
+    _raise_unconverged(who, info, tol, max_iter)
+    return x, info
+
+
+def _raise_unconverged(who, info, tol, max_iter):
     if not np.all(info["converged"]):
         raise RuntimeError("%s: %d of %d columns did not reach tol = %g in %d iterations (largest |r| / |b| = %.3g); raise max_iter"
                            % (who, int(np.sum(~info["converged"])), info["converged"].size, tol, max_iter,
                               float(np.max(info["relative_residual"]))))
-    return x, info

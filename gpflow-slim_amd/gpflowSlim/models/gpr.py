@@ -172,7 +172,8 @@ class GPR(GPModel):
             return lml, grads, grad_X + self._input_chain(kinv_resid)
         return lml, grads
 
-    def compute_log_likelihood_and_gradients_iterative(self, num_probes=16, seed=0, probes=None, max_iter=1000, tol=1e-8):
+    def compute_log_likelihood_and_gradients_iterative(self, num_probes=16, seed=0, probes=None, max_iter=1000, tol=1e-8,
+                                                       precond_rank=0):
         """(lml, grads) shaped like compute_log_likelihood_and_gradients, without the N x N matrix (Gardner et al. 2018; not in
         the reference).  One batched CG solve of [Y - m(X) | Z] gives alpha = K_y^-1 (Y - m), u_t = K_y^-1 z_t and each probe's
         Lanczos tridiagonal; then
@@ -181,12 +182,17 @@ class GPR(GPModel):
         the trace as one fused pass over K's tiles (conjugate_gradient.kernel_grad_form) with P = [alpha, -(R/T) u], Q = [alpha, z].
         Z [N, T]: ``probes``, or Rademacher from np.random.default_rng(seed) -- a fixed seed makes the objective deterministic, so
         an optimiser sees one function.  R + T <= 64 (one batch).  The log-determinant and the trace are estimates: their error
-        falls as 1 / sqrt(T); the data-fit terms are exact to the solve's tolerance.  RuntimeError if a solve did not converge."""
+        falls as 1 / sqrt(T); the data-fit terms are exact to the solve's tolerance.  RuntimeError if a solve did not converge.
+        precond_rank (1 .. 128): the solve preconditioned by the pivoted-Cholesky M = L L^T + noise I (csrc/pchol.hip), the probes
+        z_t ~ N(0, M) formed on the device from standard normals of default_rng(seed) (``probes`` are taken as Z as they are);
+            log det K_y ~ log det M + mean_t (z_t^T M^-1 z_t) e_1^T log(T_t) e_1,   W = alpha alpha^T - R/T sum_t u_t (M^-1 z_t)^T."""
         from .. import conjugate_gradient as cg
         if self._has_features():
             raise NotImplementedError("the matrix-free (iterative) route is not available on the feature (random-feature) branch; "
                                       "it takes " + cg.MATRIX_FREE_SCOPE)
         cg._matrix_free_program(self.kern, self.X.shape[1])
+        if precond_rank:
+            return self._lml_grad_preconditioned(cg, precond_rank, num_probes, seed, probes, max_iter, tol)
         N, R = self.Y.shape
         if probes is None:
             probes = np.random.default_rng(seed).integers(0, 2, size=(N, int(num_probes))) * 2.0 - 1.0
@@ -204,6 +210,29 @@ class GPR(GPModel):
         lml = -0.5 * float(np.sum(resid * alpha)) - 0.5 * R * logdet - 0.5 * N * R * np.log(2.0 * np.pi)
         slots, trace = cg.kernel_grad_form(self.kern, self.X, np.concatenate([alpha, (-float(R) / T) * u], 1),
                                            np.concatenate([alpha, Z], 1))
+        return lml, self._gradients_from_slots(self.kern._grad_layout(self.X.shape[1]), 0.5 * slots, 0.5 * trace, alpha)
+
+    def _lml_grad_preconditioned(self, cg, rank, num_probes, seed, probes, max_iter, tol):
+        """compute_log_likelihood_and_gradients_iterative with precond_rank: one preconditioned solve of [Y - m(X) | Z]"""
+        N, R = self.Y.shape
+        noise = float(np.squeeze(self.likelihood.variance))
+        cg._precond_program(self.kern, self.X, rank, 1e-10, noise)
+        if probes is None:
+            G1, Zin = cg._probe_normals(seed, rank, N, num_probes)
+        else:
+            G1, Zin = None, np.ascontiguousarray(probes, dtype=settings.float_type)
+        T = Zin.shape[1] if Zin.ndim == 2 else 0
+        if Zin.ndim != 2 or Zin.shape[0] != N or T < 1 or R + T > 64:
+            raise ValueError("probes must be [N, T] with 1 <= T <= 64 - R")
+        resid = self._resid()
+        x, info = cg._pcg(self.kern, self.X, np.concatenate([resid, Zin], 1), noise, rank, 1e-10, max_iter, tol, n_probe=T, G1=G1)
+        cg._raise_unconverged("compute_log_likelihood_and_gradients_iterative", info, tol, max_iter)
+        alpha, u = x[:, :R], x[:, R:]
+        quad = cg.lanczos_quadrature(info["alpha"][:, R:], info["beta"][:, R:], info["iterations"][R:])
+        logdet = info["logdet_M"] + float(np.mean(info["zMz"] * quad))
+        lml = -0.5 * float(np.sum(resid * alpha)) - 0.5 * R * logdet - 0.5 * N * R * np.log(2.0 * np.pi)
+        slots, trace = cg.kernel_grad_form(self.kern, self.X, np.concatenate([alpha, (-float(R) / T) * u], 1),
+                                           np.concatenate([alpha, info["MinvZ"]], 1))
         return lml, self._gradients_from_slots(self.kern._grad_layout(self.X.shape[1]), 0.5 * slots, 0.5 * trace, alpha)
 
     def _input_chain(self, kinv_resid):
@@ -278,13 +307,14 @@ class GPR(GPModel):
             fvar = np.tile(np.reshape(var, (-1, 1)), [1, R])       # models/gpr.py:131
         return fmean, fvar
 
-    def predict_f_iterative(self, Xnew, max_iter=1000, tol=1e-8):
+    def predict_f_iterative(self, Xnew, max_iter=1000, tol=1e-8, precond_rank=0):
         """predict_f without the N x N matrix (not in the reference): alpha = (K + s I)^-1 (Y - m(X)) by batched conjugate
         gradients on the fused kernel product, mean = K(Xnew, X) alpha + m(Xnew), var_j = Kdiag - k_j^T (K + s I)^-1 k_j sixteen
         test points to a solve.  Returns (mean [N*, R], var [N*, R]) like predict_f; device memory O(N (D + R + 16)) for the solves
         plus 512 N bytes for the variance's right-hand sides (the kernel-matrix build writes tiles of 64 rows for 16 test points).  Hyper-parameters
         are trained on this path by compute_log_likelihood_and_gradients_iterative (``self.iterative``).  A solve that did not
-        reach tol within max_iter is reported by a warning."""
+        reach tol within max_iter is reported by a warning.  precond_rank (0 .. 128; 0: the plain loop): every solve
+        preconditioned by the pivoted-Cholesky M = L L^T + s I of that rank at most, built once a call (csrc/pchol.hip)."""
         import warnings
         from ..conjugate_gradient import _matrix_free_program, MATRIX_FREE_SCOPE
         if self._has_features():
@@ -293,8 +323,14 @@ class GPR(GPModel):
         prog = _matrix_free_program(self.kern, self.X.shape[1])
         Xnew = np.ascontiguousarray(Xnew, dtype=settings.float_type)
         self.kern._check_inputs(self.X, Xnew)
-        mean, var, iters, rel, conv = be.kernel_predict(be.get_handle(), prog, self.X, float(np.squeeze(self.likelihood.variance)),
-                                                  self._resid(), Xnew, max_iter=max_iter, tol=tol)
+        noise = float(np.squeeze(self.likelihood.variance))
+        be._check_precond(precond_rank, 1e-10, noise)
+        if precond_rank:
+            mean, var, iters, rel, conv = be.kernel_predict_pcg(be.get_handle(), prog, self.X, noise, self._resid(), Xnew, precond_rank,
+                                                                max_iter=max_iter, tol=tol)
+        else:
+            mean, var, iters, rel, conv = be.kernel_predict(be.get_handle(), prog, self.X, noise, self._resid(), Xnew,
+                                                            max_iter=max_iter, tol=tol)
         if not np.all(conv):
             warnings.warn("predict_f_iterative: %d of %d solves did not reach tol = %g in %d iterations (largest |r| / |b| = %.3g)"
                           % (int(np.sum(~conv)), rel.size, tol, max_iter, float(np.max(rel))))

@@ -341,6 +341,36 @@ int gps_kernel_predict(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes,
                        double noise_var, const double* resid, int64_t r, const double* Xnew, int64_t n_new, int max_iter,
                        double tol, double* mean_out, double* var_out, int64_t* iters_out, double* relres_out,
                        int* converged_out);
+/* ---- the pivoted-Cholesky preconditioner of the loop above (Gardner et al. 2018) ----
+ * M = L L^T + noise_var I with L [n, k] the rank-k pivoted partial Cholesky factor of K(X, X) (no noise): the pivot of a step is the
+ * largest residual diagonal entry, ties to the lowest index, and the factor stops before rank_max (1 .. 128) when that entry is
+ * <= rel_tol * variance.  Built on the device inside every call that takes a rank, nothing n x n stored, no atomics: equal bytes from
+ * call to call.  Same scope of prog as above; a rank needs noise_var > 0 (GPS_ERR_ARG otherwise, before any device work).
+ *
+ * gps_kernel_pchol (inspection): L_out host [n, rank_max] (zero columns from *rank_out on), piv_out [rank_max] (-1 from *rank_out on),
+ * *trace_out = sum_i of the residual diagonal.                                                                               */
+int gps_kernel_pchol(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                     int rank_max, double rel_tol, double* L_out, int64_t* piv_out, int64_t* rank_out, double* trace_out);
+/* out host [n, T] = M^-1 V by Woodbury, (V - L C^-1 L^T V) / noise_var with C = noise_var I + L^T L factored by the 128-block
+ * Cholesky; or, with G1 host [rank_max, T], the sample L G1 + sqrt(noise_var) V of N(0, M) for Gaussian G1, V.  *logdet_out =
+ * log det M = 2 sum log diag chol(C) + (n - k) log noise_var.  GPS_ERR_STATE if C is not positive definite in fp64.            */
+int gps_kernel_precond_solve(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                             double noise_var, int rank_max, double rel_tol, const double* V, int64_t T, const double* G1,
+                             double* out, double* logdet_out, int64_t* rank_out);
+/* gps_kernel_cg_lanczos preconditioned by M (rank_max 0: the plain loop, launch for launch): z = M^-1 r every iteration,
+ * alpha = r^T z / p^T A p, beta = (r^T z)_new / (r^T z)_old, the stop rule still |r_t| <= tol |b_t|.  coef_out (optional) then
+ * holds the tridiagonal of M^-1/2 (K + noise_var I) M^-1/2.  The last n_probe columns of B are probes (needs rank_max > 0): with
+ * G1 host [rank_max, n_probe] they arrive as Gaussian G2 and are turned into Z = L G1 + sqrt(noise_var) G2 on the device before
+ * the solve, with G1 == NULL they are Z as given.  Z_out, MinvZ_out host [n, n_probe], zmz_out [n_probe] = z_t^T M^-1 z_t.       */
+int gps_kernel_pcg(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                   double noise_var, const double* B, int64_t T, int max_iter, double tol, int rank_max, double rel_tol,
+                   const double* G1, int64_t n_probe, double* x_out, int64_t* iters_out, double* relres_out, int* converged_out,
+                   double* coef_out, double* Z_out, double* MinvZ_out, double* zmz_out, double* logdet_out, int64_t* rank_out);
+/* gps_kernel_predict with every solve preconditioned by one M, built once a call (rank_max 0: gps_kernel_predict).           */
+int gps_kernel_predict_pcg(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                           double noise_var, const double* resid, int64_t r, const double* Xnew, int64_t n_new, int max_iter,
+                           double tol, int rank_max, double rel_tol, double* mean_out, double* var_out, int64_t* iters_out,
+                           double* relres_out, int* converged_out);
 
 /* ---- conditionals.conditional / base_conditional ------------------------
  * (conditionals.py:24-66, 80-121; features.py:74-81 for Kuu/Kuf).

@@ -5,7 +5,11 @@ Up to n = 131072 a row "grad_form_C17" follows: one launch of the fused gradient
 kernels) for a general P Q^T of 17 columns -- one output and T = 16 probes, run doubled as 34 -> 36 weight columns --, beside the
 T = 16 product of the same process, and the ratio of the two medians.
 
-    python tools/kmvm_bench.py [reps] [n ...]          (default: 5 repetitions at n = 32768, 131072, 1000000)
+    python tools/kmvm_bench.py [--rank K] [--noise S] [reps] [n ...]    (default: 5 repetitions at n = 32768, 131072, 1000000)
+
+--rank K (1 .. 128; with --noise, default 1e-2): a row "pcg_rankK" per size as well -- a 16-column solve (tol 1e-8, at most 2000
+iterations) plain and preconditioned by the rank-K pivoted-Cholesky M (csrc/pchol.hip): iteration counts and wall time of each, and
+the wall time of one call that builds M and applies M^-1 once (build + one application), beside the T = 16 product.
 """
 import json
 import os
@@ -18,8 +22,17 @@ sys.path[:0] = [os.path.join(ROOT, "gpflow-slim_amd"), ROOT]
 import gpflowSlim as gpf  # noqa: E402
 from gpflowSlim import _backend as be  # noqa: E402
 
-reps = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-sizes = [int(a) for a in sys.argv[2:]] or [32768, 131072, 10 ** 6]
+import time  # noqa: E402
+
+argv, opts = sys.argv[1:], {"--rank": 0, "--noise": 1e-2}
+for flag in opts:
+    if flag in argv:
+        i = argv.index(flag)
+        opts[flag] = float(argv[i + 1])
+        del argv[i:i + 2]
+rank, noise = int(opts["--rank"]), opts["--noise"]
+reps = int(argv[0]) if argv else 5
+sizes = [int(a) for a in argv[1:]] or [32768, 131072, 10 ** 6]
 d = 8
 kern = gpf.kernels.RBF(d, variance=1.0, lengthscales=np.sqrt(d) * np.ones(d), ARD=True)
 prog = kern._program(d)
@@ -52,6 +65,20 @@ for n in sizes:
         be.kmvm_grad(h, prog, X, P, Q, 1 + d)                                    # warm-up
         ms = [device_ms(lambda: be.kmvm_grad(h, prog, X, P, Q, 1 + d), ("kmat", "reduce", "other")) for _ in range(reps)]
         row["grad_form_C17"] = {"ms": stats(ms), "products_T16": float(np.median(ms)) / row["T16"]["ms"]["median"]}
+    if rank:
+        B = rng.standard_normal((n, 16))
+
+        def wall(call):
+            t0 = time.perf_counter()
+            res = call()
+            return res, time.perf_counter() - t0
+        be.kernel_precond_solve(h, prog, X, B, noise, rank)                      # warm-up
+        _, t_build = wall(lambda: be.kernel_precond_solve(h, prog, X, B, noise, rank))
+        plain, t_plain = wall(lambda: be.kernel_cg(h, prog, X, B, noise, max_iter=2000))
+        pre, t_pre = wall(lambda: be.kernel_pcg(h, prog, X, B, noise, rank, max_iter=2000))
+        row["pcg_rank%d" % rank] = {"noise": noise, "rank_reached": pre[-1], "build_and_one_apply_s": t_build,
+                                    "plain": {"iterations": int(np.max(plain[1])), "wall_s": t_plain, "converged": bool(np.all(plain[3]))},
+                                    "preconditioned": {"iterations": int(np.max(pre[1])), "wall_s": t_pre, "converged": bool(np.all(pre[3]))}}
     if n == sizes[0]:
         # the entry rate of the build that STORES K (kmat_single_kernel), same process, at 8192 points (the matrix comes back to
         # the host: the timers see the kernels only)
