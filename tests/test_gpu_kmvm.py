@@ -57,7 +57,18 @@ PRODUCTS = {
     "near_duplicates": ("rbf", 65, None, 3, 3, None, 0.37, 0, "dup"),
     "matern_epsilon": ("matern12", 65, 130, 3, 3, None, 0.0, 0, "origin"),
     "two_passes_two_chunks": ("rbf", 130, None, 65, 3, None, 0.37, 2, False),     # T = 65: passes of 64 + 1 columns; 3 tiles in chunks of 1, 2
+    # the dimension edges of the two instances (KB = 2: up to 8 feature rows, kbn 1 -> 2 from D = 5; KB = 8: D = 16 and 32 fill four
+    # and all eight feature groups)
+    "four_dims": ("rbf", 65, None, 17, 4, None, 0.37, 0, False),
+    "five_dims": ("matern52", 65, None, 17, 5, None, 0.37, 0, False),
+    "eight_dims": ("ratquad", 65, None, 17, 8, None, 0.37, 0, False),
+    "sixteen_dims": ("matern32", 65, None, 17, 16, None, 0.37, 0, False),
+    "thirty_two_dims": ("rbf", 65, None, 17, 32, None, 0.37, 0, False),
+    "rect_exponential_twelve_dims": ("exponential", 65, 130, 17, 12, None, 0.0, 0, False),
 }
+# These cases multiply the leaf's lengthscales by sqrt(D / 3): r2 stays near 6 and the off-diagonal entries O(1e-2 .. 1).  With
+# lengthscales near 1 at D = 32 the matrix is numerically diagonal and the comparison checks nothing.
+WIDE = ("four_dims", "five_dims", "eight_dims", "sixteen_dims", "thirty_two_dims", "rect_exponential_twelve_dims")
 _REF = {}
 
 
@@ -74,6 +85,8 @@ def _product_case(name):
             X[0], X2[0] = 0.0, 1e-9
         V = rng.normal(size=(n if n2 is None else n2, T))
         lf = mr.leaf(kind, range(d_all) if dims is None else dims, n + T)
+        if name in WIDE:
+            lf["lengthscales"] = lf["lengthscales"] * np.sqrt(d_all / 3.0)
         _REF[name] = (lf, X, X2, V) + mr.product(lf, X, V, X2, diag_add)
     return _REF[name]
 
@@ -186,6 +199,22 @@ def test_predict_f_iterative(gpf, kind, n_new):
                                                                      np.max(np.abs(var[:, 0] - ref_var)), np.min(bound_var)))
     assert np.all(nrm(mean - ref_mean) <= bound_mean)
     assert np.all(np.abs(var[:, 0] - ref_var) <= bound_var)
+
+
+def test_refuses_33_dims(gpf, monkeypatch):
+    """33 active dims (the instances hold 32 feature rows): refused on the host, before the product or the gradient form reaches
+    the backend's entry"""
+    be, cg = gpf._backend, gpf.conjugate_gradient
+
+    def launched(*a, **k):
+        raise AssertionError("the backend was entered")
+    monkeypatch.setattr(be, "kmvm", launched)
+    monkeypatch.setattr(be, "kmvm_grad", launched)
+    X, V = np.ones((4, 33)), np.ones((4, 1))
+    with pytest.raises(ValueError, match="at most 32 active dims"):
+        cg.kernel_matmul(gpf.kernels.RBF(33, lengthscales=np.ones(33), ARD=True), X, V)
+    with pytest.raises(ValueError, match="at most 32 active dims"):
+        cg.kernel_grad_form(gpf.kernels.Matern52(33), X, V, V)
 
 
 def test_refusals(gpf):

@@ -19,7 +19,8 @@ import _kmvm_ref as mr  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 EPS = np.finfo(np.float64).eps
-NAMES = {"rbf": "RBF", "matern12": "Matern12", "matern52": "Matern52", "ratquad": "RatQuad"}
+NAMES = {"rbf": "RBF", "matern12": "Matern12", "matern32": "Matern32", "matern52": "Matern52", "exponential": "Exponential",
+         "ratquad": "RatQuad"}
 
 
 @pytest.fixture(scope="module")
@@ -58,7 +59,12 @@ def dense_form(lf, X, P, Q, dtype, absolute=False):
 # name -> (kernel, n, D, C, P is Q, forced chunks, isotropic)
 FORMS = {"rbf_one_column": ("rbf", 65, 3, 1, True, 0, False), "ratquad_split3": ("ratquad", 130, 3, 5, False, 3, False),
          "ratquad_split2": ("ratquad", 130, 3, 5, False, 2, False), "matern12_nine_dims": ("matern12", 200, 9, 17, False, 0, False),
-         "matern52_isotropic": ("matern52", 64, 3, 3, True, 0, True)}
+         "matern52_isotropic": ("matern52", 64, 3, 3, True, 0, True),
+         # the two kernels the cases above leave out, and the dimension edges of the two instances (ones column of [F | 1 | 0] at
+         # index 8, 16 and 32; ratquad_32_dims: cp = 64, all eight feature groups, W = 48, the largest LDS request)
+         "matern32": ("matern32", 130, 3, 5, False, 0, False), "exponential_four_dims": ("exponential", 130, 4, 3, True, 0, False),
+         "rbf_eight_dims": ("rbf", 65, 8, 5, False, 0, False), "matern52_sixteen_dims": ("matern52", 130, 16, 17, False, 0, False),
+         "ratquad_32_dims": ("ratquad", 130, 32, 32, False, 0, False)}
 
 
 @pytest.mark.parametrize("name", list(FORMS))
@@ -68,6 +74,8 @@ def test_form_slot_by_slot(gpf, name):
     X, P = rng.standard_normal((n, D)), rng.standard_normal((n, C))
     Q = P if same else rng.standard_normal((n, C))
     lf = mr.leaf(kind, range(D), n + C)
+    if D > 3 and name != "matern12_nine_dims":          # (the newer wide cases: r2 stays near 6, as test_gpu_kmvm.py's WIDE)
+        lf["lengthscales"] = lf["lengthscales"] * np.sqrt(D / 3.0)
     if iso:
         lf["lengthscales"] = 0.9
     ref, scale = dense_form(lf, X, P, Q, mr.LD), dense_form(lf, X, P, Q, mr.LD, absolute=True)
