@@ -7,6 +7,8 @@
 //   gps_kmvm_grad        sum_ij (P Q^T)_ij dK_ij / d theta per gradient slot and tr(P Q^T), nothing n x n stored
 //   gps_kernel_predict   alpha = (K + s I)^-1 resid ; mean = K(Xnew, X) alpha ; var_j = Kdiag - k_j^T (K + s I)^-1 k_j, sixteen test
 //                        points to a solve, the right-hand sides K(X, Xnew_block) from the kernel-matrix build and never on the host
+//   gps_kmvm_sop / gps_kernel_cg_sop / gps_kernel_predict_sop   the first, second + third and fifth of these on a sum of products of
+//                        primitives (kmvm_sop.hip): the same bodies with KmvmPlan::sop set; no preconditioner, no gradient form
 //   gps_kernel_pchol / _precond_solve / _pcg / _predict_pcg   the pivoted-Cholesky preconditioner M = L L^T + s I (pchol.hip): its
 //                        factor, M^-1 V / log det M / samples, and the two solvers above with every solve preconditioned
 //
@@ -42,8 +44,11 @@ extern "C" int gps_kmvm_set_split(gps_handle_t h, int64_t chunks) {
 }
 
 // what the three entries start with: the scope of the program (before anything touches the device), the refusals, the call's reset
-static int kmvm_begin(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes) {
-  if (!gps_kmvm_in_scope(prog, n_nodes))
+// (sop: an entry of the sum-of-products path, whose scope gps_kmvm_sop_check states)
+static int kmvm_begin(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes, bool sop = false) {
+  if (sop) {
+    if (int rs = gps_kmvm_sop_check(h, who, prog, n_nodes)) return rs;
+  } else if (!gps_kmvm_in_scope(prog, n_nodes))
     return gps_fail(h, GPS_ERR_UNSUPPORTED, std::string(who) + ": the program must be one RBF, Matern12/32/52, Exponential or RatQuad primitive");
   if (int rf = refuse_unsupported(h, who, true)) return rf;
   return begin_inducing_call(h, nullptr);                  // (refuses armed Multiscale scales; dX, dS*, dG* are overwritten)
@@ -129,14 +134,22 @@ static int kcg_solve(gps_handle_t h, const KmvmPlan& plan, i64 n, const KcgBufs&
   return GPS_OK;
 }
 
+// the feature rows of a plan's points: the one primitive's (node), or with sop the whole program's table and the program itself
+static int kmvm_features(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n, i64 d_all, i64 npad,
+                         DevBuf& feat, KNodeDev* node, KmvmSop* sop) {
+  if (sop) return gps_kmvm_sop_features(h, prog, n_nodes, dX, n, d_all, npad, feat, sop);
+  return gps_kmvm_features(h, prog, n_nodes, dX, n, d_all, npad, feat, node);
+}
+
 // X -> dX and its features -> dFeatG: the plan of K(X, X)
-static int kmvm_sym_plan(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, i64 n, i64 d_all, KmvmPlan* plan) {
+static int kmvm_sym_plan(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, i64 n, i64 d_all, KmvmPlan* plan,
+                         KmvmSop* sop = nullptr) {
   const i64 np = pad64(n);
   GPS_HIP(h, h->dX.ensure((size_t)n * d_all * 8));
   GPS_HIP(h, hipMemcpyAsync(h->dX.p, X, (size_t)n * d_all * 8, hipMemcpyHostToDevice, h->stream));
-  int rc = gps_kmvm_features(h, prog, n_nodes, h->dX.d(), n, d_all, np, h->dFeatG, &plan->node);
+  int rc = kmvm_features(h, prog, n_nodes, h->dX.d(), n, d_all, np, h->dFeatG, &plan->node, sop);
   if (rc) return rc;
-  plan->Fr = h->dFeatG.d(); plan->Fc = plan->Fr; plan->npr = np; plan->npc = np; plan->sym = 1;
+  plan->Fr = h->dFeatG.d(); plan->Fc = plan->Fr; plan->npr = np; plan->npc = np; plan->sym = 1; plan->sop = sop;
   return GPS_OK;
 }
 
@@ -271,24 +284,26 @@ extern "C" int gps_kernel_precond_solve(gps_handle_t h, const gps_kern_node_t* p
   return GPS_OK;
 }
 
-extern "C" int gps_kmvm(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, const double* X2,
-                        int64_t n2, int64_t d_all, const double* V, int64_t T, double diag_add, double* out) {
-  if (!h || n < 0 || n2 < 0 || T < 0 || d_all <= 0) return gps_fail(h, GPS_ERR_ARG, "gps_kmvm: bad argument");
-  int rc = kmvm_begin(h, "gps_kmvm", prog, n_nodes);
+// gps_kmvm, and with sop gps_kmvm_sop: the same buffers, the whole program's features in place of the one primitive's
+static int kmvm_impl(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, const double* X2,
+                     int64_t n2, int64_t d_all, const double* V, int64_t T, double diag_add, double* out, KmvmSop* sop) {
+  const std::string bad = std::string(who) + ": bad argument";
+  if (!h || n < 0 || n2 < 0 || T < 0 || d_all <= 0) return gps_fail(h, GPS_ERR_ARG, bad);
+  int rc = kmvm_begin(h, who, prog, n_nodes, sop != nullptr);
   if (rc) return rc;
   const bool sym = (X2 == nullptr);
   if (sym) n2 = n;
   if (n == 0 || T == 0) return GPS_OK;
-  if (!X || !out || (n2 > 0 && !V)) return gps_fail(h, GPS_ERR_ARG, "gps_kmvm: bad argument");
+  if (!X || !out || (n2 > 0 && !V)) return gps_fail(h, GPS_ERR_ARG, bad);
   if (n2 == 0) { memset(out, 0, (size_t)n * T * 8); return GPS_OK; }
   KmvmPlan plan;
-  rc = kmvm_sym_plan(h, prog, n_nodes, X, n, d_all, &plan);
+  rc = kmvm_sym_plan(h, prog, n_nodes, X, n, d_all, &plan, sop);
   if (rc) return rc;
   if (!sym) {
     plan.npc = pad64(n2); plan.sym = 0;
     GPS_HIP(h, h->dXnew.ensure((size_t)n2 * d_all * 8));
     GPS_HIP(h, hipMemcpyAsync(h->dXnew.p, X2, (size_t)n2 * d_all * 8, hipMemcpyHostToDevice, h->stream));
-    rc = gps_kmvm_features(h, prog, n_nodes, h->dXnew.d(), n2, d_all, plan.npc, h->dGxTab, &plan.node);
+    rc = kmvm_features(h, prog, n_nodes, h->dXnew.d(), n2, d_all, plan.npc, h->dGxTab, &plan.node, sop);
     if (rc) return rc;
     plan.Fc = h->dGxTab.d();
   }
@@ -308,6 +323,17 @@ extern "C" int gps_kmvm(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes
   return GPS_OK;
 }
 
+extern "C" int gps_kmvm(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, const double* X2,
+                        int64_t n2, int64_t d_all, const double* V, int64_t T, double diag_add, double* out) {
+  return kmvm_impl(h, "gps_kmvm", prog, n_nodes, X, n, X2, n2, d_all, V, T, diag_add, out, nullptr);
+}
+
+extern "C" int gps_kmvm_sop(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, const double* X2,
+                            int64_t n2, int64_t d_all, const double* V, int64_t T, double diag_add, double* out) {
+  KmvmSop sop;
+  return kmvm_impl(h, "gps_kmvm_sop", prog, n_nodes, X, n, X2, n2, d_all, V, T, diag_add, out, &sop);
+}
+
 // gps_kernel_cg, and with coef_out (host [max_iter][2][T]: alpha_k, beta_k of column t at [k][0][t], [k][1][t] for k below the
 // column's iteration count, zeros after) gps_kernel_cg_lanczos: the loop records its coefficients on the device (dLanczos) and they
 // are read once a batch, after the loop
@@ -320,7 +346,8 @@ struct PcgOpts {
 };
 static int kernel_cg_impl(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n,
                           int64_t d_all, double noise_var, const double* B, int64_t T, int max_iter, double tol, double* x_out,
-                          int64_t* iters_out, double* relres_out, int* converged_out, double* coef_out, const PcgOpts* pc = nullptr) {
+                          int64_t* iters_out, double* relres_out, int* converged_out, double* coef_out, const PcgOpts* pc = nullptr,
+                          KmvmSop* sop = nullptr) {
   const std::string bad = std::string(who) + ": bad argument";
   if (!h || n < 0 || T < 0 || d_all <= 0 || max_iter < 0 || !(tol >= 0.0) || !(noise_var >= 0.0)) return gps_fail(h, GPS_ERR_ARG, bad);
   if (pc) {
@@ -329,7 +356,7 @@ static int kernel_cg_impl(gps_handle_t h, const char* who, const gps_kern_node_t
       return gps_fail(h, GPS_ERR_ARG, bad);
     if (pc->rank_max == 0) pc = nullptr;
   }
-  int rc = kmvm_begin(h, who, prog, n_nodes);
+  int rc = kmvm_begin(h, who, prog, n_nodes, sop != nullptr);
   if (rc) return rc;
   if (pc && pc->logdet_out) *pc->logdet_out = 0.0;
   if (pc && pc->rank_out) *pc->rank_out = 0;
@@ -341,7 +368,7 @@ static int kernel_cg_impl(gps_handle_t h, const char* who, const gps_kern_node_t
     GPS_HIP(h, h->dLanczos.ensure((size_t)(max_iter > 0 ? max_iter : 1) * 2 * KCG_MAXT * 8));
   }
   KmvmPlan plan;
-  rc = kmvm_sym_plan(h, prog, n_nodes, X, n, d_all, &plan);
+  rc = kmvm_sym_plan(h, prog, n_nodes, X, n, d_all, &plan, sop);
   if (rc) return rc;
   const i64 np = plan.npr;
   GPS_HIP(h, h->dStage.ensure((size_t)n * T * 8));
@@ -444,6 +471,15 @@ extern "C" int gps_kernel_cg_lanczos(gps_handle_t h, const gps_kern_node_t* prog
                         relres_out, converged_out, coef_out);
 }
 
+// the plain loop on a sum-of-products program; coef_out: NULL, or gps_kernel_cg_lanczos' coefficients -- one entry for both calls
+extern "C" int gps_kernel_cg_sop(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                                 double noise_var, const double* B, int64_t T, int max_iter, double tol, double* x_out,
+                                 int64_t* iters_out, double* relres_out, int* converged_out, double* coef_out) {
+  KmvmSop sop;
+  return kernel_cg_impl(h, "gps_kernel_cg_sop", prog, n_nodes, X, n, d_all, noise_var, B, T, max_iter, tol, x_out, iters_out, relres_out,
+                        converged_out, coef_out, nullptr, &sop);
+}
+
 extern "C" int gps_kernel_pcg(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
                               double noise_var, const double* B, int64_t T, int max_iter, double tol, int rank_max, double rel_tol,
                               const double* G1, int64_t n_probe, double* x_out, int64_t* iters_out, double* relres_out,
@@ -511,21 +547,21 @@ extern "C" int gps_kmvm_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_
 static int kernel_predict_impl(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n,
                                int64_t d_all, double noise_var, const double* resid, int64_t r, const double* Xnew, int64_t n_new,
                                int max_iter, double tol, int rank_max, double rel_tol, double* mean_out, double* var_out,
-                               int64_t* iters_out, double* relres_out, int* converged_out) {
+                               int64_t* iters_out, double* relres_out, int* converged_out, KmvmSop* sop = nullptr) {
   const std::string bad = std::string(who) + ": bad argument";
   if (!h || n <= 0 || r <= 0 || n_new < 0 || d_all <= 0 || max_iter < 0 || !(tol >= 0.0) || !(noise_var >= 0.0))
     return gps_fail(h, GPS_ERR_ARG, bad);
   if (int rf = pchol_check(h, who, rank_max, rel_tol, noise_var)) return rf;
-  int rc = kmvm_begin(h, who, prog, n_nodes);
+  int rc = kmvm_begin(h, who, prog, n_nodes, sop != nullptr);
   if (rc) return rc;
   if (n_new == 0) return GPS_OK;
   if (!X || !resid || !Xnew || !mean_out || !var_out || !iters_out || !relres_out || !converged_out)
     return gps_fail(h, GPS_ERR_ARG, bad);
   double kdiag = 0.0;
-  rc = gps_launch_kdiag(h, prog, n_nodes, &kdiag);
+  rc = gps_launch_kdiag(h, prog, n_nodes, &kdiag);      // (a sum of products: sum_terms prod variances, White's included)
   if (rc) return rc;
   KmvmPlan plan;
-  rc = kmvm_sym_plan(h, prog, n_nodes, X, n, d_all, &plan);
+  rc = kmvm_sym_plan(h, prog, n_nodes, X, n, d_all, &plan, sop);
   if (rc) return rc;
   const i64 np = plan.npr, nsp = pad64(n_new);
   PcholPre pre;
@@ -539,7 +575,7 @@ static int kernel_predict_impl(gps_handle_t h, const char* who, const gps_kern_n
   GPS_HIP(h, hipMemcpyAsync(h->dXnew.p, Xnew, (size_t)n_new * d_all * 8, hipMemcpyHostToDevice, h->stream));
   // ---- the mean: alpha batch by batch, each pushed through K(Xnew, X) at once
   KmvmPlan cross = plan;
-  rc = gps_kmvm_features(h, prog, n_nodes, h->dXnew.d(), n_new, d_all, nsp, h->dGxTab, &cross.node);
+  rc = kmvm_features(h, prog, n_nodes, h->dXnew.d(), n_new, d_all, nsp, h->dGxTab, &cross.node, sop);
   if (rc) return rc;
   cross.Fr = h->dGxTab.d(); cross.npr = nsp; cross.sym = 0;
   GPS_HIP(h, h->dStage.ensure((size_t)n * r * 8));
@@ -607,4 +643,13 @@ extern "C" int gps_kernel_predict_pcg(gps_handle_t h, const gps_kern_node_t* pro
                                       double* relres_out, int* converged_out) {
   return kernel_predict_impl(h, "gps_kernel_predict_pcg", prog, n_nodes, X, n, d_all, noise_var, resid, r, Xnew, n_new, max_iter, tol,
                              rank_max, rel_tol, mean_out, var_out, iters_out, relres_out, converged_out);
+}
+
+extern "C" int gps_kernel_predict_sop(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                                      double noise_var, const double* resid, int64_t r, const double* Xnew, int64_t n_new, int max_iter,
+                                      double tol, double* mean_out, double* var_out, int64_t* iters_out, double* relres_out,
+                                      int* converged_out) {
+  KmvmSop sop;
+  return kernel_predict_impl(h, "gps_kernel_predict_sop", prog, n_nodes, X, n, d_all, noise_var, resid, r, Xnew, n_new, max_iter, tol, 0, 0.0,
+                             mean_out, var_out, iters_out, relres_out, converged_out, &sop);
 }

@@ -1176,3 +1176,83 @@ int gps_kmvm_features(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, 
   *node = kc.prog.nodes[0];
   return GPS_OK;
 }
+
+// ---- ... and the sum-of-products product's (kmvm_sop.hip) --------------------------------------------------------------------------
+// A postfix program is a sum of products exactly when no MUL takes a sum as an operand.  A product's primitives are then contiguous
+// in program order, so the terms are runs of primitives: flags[i] (per NODE; 0 on ADD / MUL) = 1 on the first primitive of a term
+// | 2 on its last.  Returns what is outside the scope, or NULL; rows: the staged feature rows, each primitive's padded to 4.
+static const char* sop_walk(const gps_kern_node_t* prog, int n_nodes, int* flags, int* n_prims, int* rows) {
+  if (!prog || n_nodes <= 0 || n_nodes > GPS_MAX_NODES) return "1 .. GPS_MAX_NODES nodes expected";
+  struct Item { bool sum; int first, last; };
+  Item st[GPS_MAX_NODES];
+  int sp = 0;
+  *n_prims = 0; *rows = 0;
+  auto close_term = [&](const Item& it) { if (!it.sum) { flags[it.first] |= 1; flags[it.last] |= 2; } };
+  for (int i = 0; i < n_nodes; ++i) {
+    flags[i] = 0;
+    const int op = prog[i].op;
+    if (op == GPS_K_ADD || op == GPS_K_MUL) {
+      if (sp < 2) return "stack underflow";
+      const Item b = st[--sp], a = st[--sp];
+      if (op == GPS_K_MUL) {
+        if (a.sum || b.sum) return "a Sum under a Product is not a sum of products: expand (a + b) * c into a * c + b * c";
+        st[sp++] = {false, a.first, b.last};
+      } else {
+        close_term(a); close_term(b);
+        st[sp++] = {true, a.first, b.last};
+      }
+      continue;
+    }
+    int nf = 0;
+    switch (op) {
+      case GPS_K_RBF: case GPS_K_MATERN12: case GPS_K_MATERN32: case GPS_K_MATERN52: case GPS_K_EXPONENTIAL: case GPS_K_RATQUAD:
+        nf = prog[i].n_dims; break;
+      case GPS_K_PERIODIC: nf = 2 * prog[i].n_dims; break;
+      case GPS_K_COSINE: nf = 2; break;
+      case GPS_K_CONSTANT: case GPS_K_WHITE: break;
+      default:
+        return "the primitives of a sum of products are RBF, Matern12/32/52, Exponential, RatQuad, Periodic, Cosine, Constant and White";
+    }
+    if (prog[i].n_dims < 0 || prog[i].n_dims > GPS_MAX_DIMS) return "n_dims out of range";
+    *n_prims += 1; *rows += (nf + 3) & ~3;
+    st[sp++] = {false, i, i};
+  }
+  if (sp != 1) return "the program must leave exactly one value";
+  close_term(st[0]);
+  if (*n_prims > GPS_SOP_MAX_PRIMS) return "more than 16 primitives";
+  if (*rows > GPS_SOP_MAX_ROWS) return "more than 64 feature rows (every primitive's rounded up to 4; Periodic takes two per dim)";
+  return nullptr;
+}
+
+int gps_kmvm_sop_check(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes) {
+  int flags[GPS_MAX_NODES], np = 0, rows = 0;
+  if (const char* why = sop_walk(prog, n_nodes, flags, &np, &rows)) return gps_fail(h, GPS_ERR_UNSUPPORTED, std::string(who) + ": " + why);
+  return GPS_OK;
+}
+
+int gps_kmvm_sop_features(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n, i64 d_all, i64 npad,
+                          DevBuf& feat, KmvmSop* sop) {
+  int flags[GPS_MAX_NODES], np = 0, rows = 0;
+  if (const char* why = sop_walk(prog, n_nodes, flags, &np, &rows))
+    return gps_fail(h, GPS_ERR_UNSUPPORTED, std::string("matrix-free product: ") + why);
+  KCompiled kc;
+  int rc = compile_prog(h, prog, n_nodes, d_all, kc);
+  if (rc) return rc;
+  i64 ldf = npad;
+  rc = run_prep(h, kc, dX, n, d_all, npad, feat, h->dProg, &ldf);
+  if (rc) return rc;
+  memset(sop, 0, sizeof(*sop));
+  KSopLayout& L = sop->lay;
+  int q = 0;
+  for (int i = 0; i < n_nodes; ++i) {
+    if (prog[i].op == GPS_K_ADD || prog[i].op == GPS_K_MUL) continue;
+    const KNodeDev& nd = kc.prog.nodes[i];
+    sop->prog.nodes[q] = nd;
+    L.s0[q] = L.f4; L.f4 += (nd.nf + 3) & ~3;
+    L.sn[q] = nd.norm_row >= 0 ? L.nn++ : -1;
+    L.flags[q] = flags[i];
+    ++q;
+  }
+  sop->prog.n_nodes = q; L.n_prims = q;
+  return GPS_OK;
+}

@@ -216,8 +216,28 @@ int gps_kmvm_features(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, 
 // kmvm.hip : the matrix-free product  out = K(X, X2) V (+ diag_add V for K(X, X))  and the vector kernels of the batched CG on it
 // One product's operands: the primitive, the feature-major rows of the row points [*, npr] and of the column points [*, npc]
 // (the same array for K(X, X)); npr, npc multiples of 64.
-struct KmvmPlan { KNodeDev node; const double* Fr; const double* Fc; i64 npr, npc; int sym; };
+// sop: NULL, or the sum-of-products program of kmvm_sop.hip -- the product then evaluates the whole program per block and `node` is
+// not read; Fr / Fc are run_prep's table of the whole program.
+struct KmvmSop;
+struct KmvmPlan { KNodeDev node; const double* Fr; const double* Fc; i64 npr, npc; int sym; const KmvmSop* sop = nullptr; };
 int gps_kmvm_chunks(i64 row_tiles, i64 col_tiles, int forced);
+// kmvm_sop.hip : K = sum_terms prod_factors p.  prog holds the primitives alone, in program order (n_nodes = n_prims; f0, nf and
+// norm_row index run_prep's table of the whole program); lay how they are staged: primitive q's feature rows from row s0[q] of the
+// staged tile on, padded to a multiple of 4 (f4 rows in all), its norm row at sn[q] of the nn staged norm rows (-1: none), and
+// flags[q] = 1 (first primitive of its term) | 2 (last of its term).
+#define GPS_SOP_MAX_PRIMS 16
+#define GPS_SOP_MAX_ROWS 64
+struct KSopLayout { int n_prims, f4, nn; int s0[GPS_SOP_MAX_PRIMS]; int sn[GPS_SOP_MAX_PRIMS]; int flags[GPS_SOP_MAX_PRIMS]; };
+struct KmvmSop { KProgDev prog; KSopLayout lay; };
+// kmat.hip, host only: the scope of that path -- a postfix program that is a sum of products of RBF, Matern12/32/52, Exponential,
+// RatQuad, Periodic, Cosine, Constant and White within the two limits above (GPS_ERR_UNSUPPORTED names what is outside) --, and the
+// whole program's feature table of the n points dX, as gps_kmvm_features', with *sop filled
+int gps_kmvm_sop_check(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes);
+int gps_kmvm_sop_features(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* dX, i64 n, i64 d_all, i64 npad,
+                          DevBuf& feat, KmvmSop* sop);
+// one pass of gps_launch_kmvm on a plan with sop: tb blocks of V, chunk c of `chunks` writes out + c part_stride
+int gps_launch_kmvm_sop_pass(gps_handle_t h, const KmvmPlan& p, const double* V, i64 ldv, int tb, double* out, i64 ldo, i64 part_stride,
+                             int tiles, int chunks, double diag_add, const int* skip);
 // V [npc][ldv], out [npr][ldo], tpad columns (16, or a multiple of 64: passes of 64); skip: optional device flag, non-zero =
 // the kernel returns at once.  Partials of a chunked walk go through h->dKmvmPart.
 int gps_launch_kmvm(gps_handle_t h, const KmvmPlan& p, const double* V, i64 ldv, i64 tpad, double diag_add, double* out, i64 ldo,

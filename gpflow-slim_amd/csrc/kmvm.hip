@@ -163,7 +163,7 @@ int gps_launch_kmvm(gps_handle_t h, const KmvmPlan& p, const double* V, i64 ldv,
                     const int* skip) {
   if (tpad <= 0 || (tpad != 16 && tpad % 64) || ldv < tpad || ldo < tpad || p.npr % KVT || p.npc % KVT || (p.sym && p.npr != p.npc))
     return gps_fail(h, GPS_ERR_ARG, "kmvm: columns must be padded to 16 or a multiple of 64, points to 64");
-  if (p.npr / KVT > 0x7fffffff / 2 || p.node.nf > 32 || p.node.norm_row < 0)
+  if (p.npr / KVT > 0x7fffffff / 2 || (!p.sop && (p.node.nf > 32 || p.node.norm_row < 0)))
     return gps_fail(h, GPS_ERR_UNSUPPORTED, "kmvm: too many rows, or not a stationary primitive");
   const i64 row_tiles = p.npr / KVT, col_tiles = p.npc / KVT;
   const int chunks = gps_kmvm_chunks(row_tiles, col_tiles, h->kmvm_split);
@@ -185,10 +185,15 @@ int gps_launch_kmvm(gps_handle_t h, const KmvmPlan& p, const double* V, i64 ldv,
     }
     {
       const double entries = (double)p.npr * (double)p.npc;
-      LaunchScope ls(h, KC_KMAT, entries * (2.0 * p.node.nf + 30.0 + 2.0 * cols), 8.0 * ((double)p.npr * cols * nch + (double)p.npc * cols));
+      // (a sum-of-products plan: every staged feature row and one epilogue per primitive)
+      const double per_entry = p.sop ? 2.0 * p.sop->lay.f4 + 30.0 * p.sop->lay.n_prims : 2.0 * p.node.nf + 30.0;
+      LaunchScope ls(h, KC_KMAT, entries * (per_entry + 2.0 * cols), 8.0 * ((double)p.npr * cols * nch + (double)p.npc * cols));
       ls.tag[0] = p.npr; ls.tag[1] = p.npc; ls.tag[2] = cols; ls.tag[3] = nch;
       const dim3 grid((unsigned)row_tiles, (unsigned)nch);
       int rc = 0;
+      // p.sop: the whole program per block (kmvm_sop.hip) on the same geometry; NULL: the one primitive, as ever
+      if (p.sop) rc = gps_launch_kmvm_sop_pass(h, p, a.V, a.ldv, a.tb, a.out, a.ldo, a.part_stride, a.tiles, a.chunks, a.diag_add, a.skip);
+      else
       // (the ops of gps_kmvm_in_scope; the switch is kmat.hip's with_stationary_op<true>, spelt out: that one is static there)
       switch (p.node.op) {
         case GPS_K_RBF: kmvm_launch_op<GPS_K_RBF>(h, grid, a, p.node); break;
@@ -436,7 +441,7 @@ int gps_launch_kmvm_grad(gps_handle_t h, const KmvmPlan& p, i64 n, const double*
   const int cp = ((dbl ? 2 * tc : tc) + 3) / 4 * 4;
   if (tc <= 0 || cp > 64 || !p.sym || p.npr % KVT || p.npr != p.npc || n > p.npr)
     return gps_fail(h, GPS_ERR_ARG, "kmvm_grad: at most 64 weight columns a pass (32 doubled), points padded to 64, K(X, X) only");
-  if (p.npr / KVT > 0x7fffffff / 2 || p.node.nf > 32 || p.node.norm_row < 0)
+  if (p.npr / KVT > 0x7fffffff / 2 || p.sop || p.node.nf > 32 || p.node.norm_row < 0)
     return gps_fail(h, GPS_ERR_UNSUPPORTED, "kmvm_grad: too many rows, or not a stationary primitive");
   const i64 np = p.npr, tiles = np / KVT;
   const int chunks = gps_kmvm_chunks(tiles, tiles, h->kmvm_split);

@@ -330,7 +330,7 @@ size_t gps_pchol_workspace(i64 np, int kp, PcholPre* pre) {
 }
 
 int gps_launch_pchol_factor(gps_handle_t h, const KmvmPlan& plan, i64 n, int cap, double rel_tol, const PcholPre& pre) {
-  if (cap < 1 || cap > 128 || cap > pre.kp || pre.kp % 16 || pre.np % 64 || plan.node.nf > 32 || plan.node.norm_row < 0)
+  if (cap < 1 || cap > 128 || cap > pre.kp || pre.kp % 16 || pre.np % 64 || plan.sop || plan.node.nf > 32 || plan.node.norm_row < 0)
     return gps_fail(h, GPS_ERR_ARG, "pchol: rank cap 1 .. 128 inside kp, points padded to 64, a stationary primitive");
   double* ws = pre.ws;
   PcholArgs a;

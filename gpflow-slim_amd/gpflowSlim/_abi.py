@@ -295,6 +295,9 @@ _SIGNATURES = {
                        _dp, _dp, _dp, _dp, _i64p],
     "gps_kernel_predict_pcg": [_vp, _prog, _int, _dp, _i64, _i64, _dbl, _dp, _i64, _dp, _i64, _int, _dbl, _int, _dbl, _dp, _dp, _i64p,
                                _dp, _ip],
+    "gps_kmvm_sop": [_vp, _prog, _int, _dp, _i64, _dp, _i64, _i64, _dp, _i64, _dbl, _dp],
+    "gps_kernel_cg_sop": [_vp, _prog, _int, _dp, _i64, _i64, _dbl, _dp, _i64, _int, _dbl, _dp, _i64p, _dp, _ip, _dp],
+    "gps_kernel_predict_sop": [_vp, _prog, _int, _dp, _i64, _i64, _dbl, _dp, _i64, _dp, _i64, _int, _dbl, _dp, _dp, _i64p, _dp, _ip],
     "gps_sparse_last_terms": [_vp, _dp],
     "gps_profile_enable": [_vp, _int],
     "gps_profile_reset": [_vp],

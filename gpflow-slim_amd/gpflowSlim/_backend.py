@@ -1267,7 +1267,7 @@ def set_handle(handle):
 # ---- exact GP regression without the N x N matrix (csrc/gps_kmvm.hip) ------------------------------------------------------------------
 # Functions of a handle rather than methods of Handle: the three entries drop whatever X and factor were resident and leave nothing
 # resident themselves, so they have no place in the residency table of Handle's docstring; tests/test_gpu_kmvm.py covers them.
-def kmvm(h, prog, X, V, X2=None, diag_add=0.0):
+def kmvm(h, prog, X, V, X2=None, diag_add=0.0, entry="gps_kmvm"):
     """gps_kmvm: K(X, X2) V, or (K(X, X) + diag_add I) V without an X2, K never stored.  X [n, d], X2 [n2, d], V [n2, T]."""
     X, V = _f64(X), _f64(V)
     _need(X.ndim == 2 and V.ndim == 2, "X must be [N, D] and V [N2, T]")
@@ -1280,9 +1280,30 @@ def kmvm(h, prog, X, V, X2=None, diag_add=0.0):
     _need(V.shape[0] == n2, "V must have %d rows" % n2)
     out = np.zeros((n, V.shape[1]))
     h._drop_resident()
-    h._call("gps_kmvm", prog, len(prog), _ptr(X), n, _opt(X2), 0 if X2 is None else n2, d, _ptr(V), V.shape[1], float(diag_add),
+    h._call(entry, prog, len(prog), _ptr(X), n, _opt(X2), 0 if X2 is None else n2, d, _ptr(V), V.shape[1], float(diag_add),
             _ptr(out))
     return out
+
+
+# ---- ... on a sum of products of primitives (csrc/kmvm_sop.hip): the same arguments, buffers and claims as their siblings above
+def kmvm_sop(h, prog, X, V, X2=None, diag_add=0.0):
+    """gps_kmvm_sop: ``kmvm`` for a postfix program K = sum_terms prod_factors p."""
+    return kmvm(h, prog, X, V, X2=X2, diag_add=diag_add, entry="gps_kmvm_sop")
+
+
+def kernel_cg_sop(h, prog, X, B, noise_var, max_iter=1000, tol=1e-8, lanczos=False):
+    """gps_kernel_cg_sop: ``kernel_cg``'s four results, and with lanczos ``kernel_cg_lanczos``'s two more."""
+    X, B = _f64(X), _f64(B)
+    _need(X.ndim == 2 and B.ndim == 2 and B.shape[0] == X.shape[0], "X must be [N, D] and B [N, T]")
+    n, T = B.shape
+    x, iters, rel, conv = np.zeros((n, T)), np.zeros(T, dtype=np.int64), np.zeros(T), np.zeros(T, dtype=np.intc)
+    coef = np.zeros((max(int(max_iter), 1), 2, T)) if lanczos else None
+    h._drop_resident()
+    h._call("gps_kernel_cg_sop", prog, len(prog), _ptr(X), n, X.shape[1], float(noise_var), _ptr(B), T, int(max_iter), float(tol),
+            _ptr(x), iters.ctypes.data_as(ctypes.POINTER(_i64)), _ptr(rel), conv.ctypes.data_as(_c_int_p), _opt(coef))
+    if lanczos:
+        return x, iters, rel, conv != 0, coef[:, 0, :], coef[:, 1, :]
+    return x, iters, rel, conv != 0
 
 
 def kmvm_set_split(h, chunks):
@@ -1329,7 +1350,12 @@ def kmvm_grad(h, prog, X, P, Q, n_slots):
     return slots, float(trace[0])
 
 
-def kernel_predict(h, prog, X, noise_var, resid, Xnew, max_iter=1000, tol=1e-8):
+def kernel_predict_sop(h, prog, X, noise_var, resid, Xnew, max_iter=1000, tol=1e-8):
+    """gps_kernel_predict_sop: ``kernel_predict`` for a sum-of-products program."""
+    return kernel_predict(h, prog, X, noise_var, resid, Xnew, max_iter=max_iter, tol=tol, entry="gps_kernel_predict_sop")
+
+
+def kernel_predict(h, prog, X, noise_var, resid, Xnew, max_iter=1000, tol=1e-8, entry="gps_kernel_predict"):
     """gps_kernel_predict: (mean [N*, R], var [N*], iterations [R + N*], |r| / |b| [R + N*], converged [R + N*])."""
     X, resid, Xnew = _f64(X), _f64(resid), _f64(Xnew)
     _need(X.ndim == 2 and resid.ndim == 2 and resid.shape[0] == X.shape[0] and X.shape[0] > 0 and resid.shape[1] > 0,
@@ -1339,7 +1365,7 @@ def kernel_predict(h, prog, X, noise_var, resid, Xnew, max_iter=1000, tol=1e-8):
     mean, var = np.zeros((n_new, r)), np.zeros(n_new)
     iters, rel, conv = np.zeros(r + n_new, dtype=np.int64), np.zeros(r + n_new), np.zeros(r + n_new, dtype=np.intc)
     h._drop_resident()
-    h._call("gps_kernel_predict", prog, len(prog), _ptr(X), n, X.shape[1], float(noise_var), _ptr(resid), r, _ptr(Xnew), n_new,
+    h._call(entry, prog, len(prog), _ptr(X), n, X.shape[1], float(noise_var), _ptr(resid), r, _ptr(Xnew), n_new,
             int(max_iter), float(tol), _ptr(mean), _ptr(var), iters.ctypes.data_as(ctypes.POINTER(_i64)), _ptr(rel),
             conv.ctypes.data_as(_c_int_p))
     return mean, var, iters, rel, conv != 0

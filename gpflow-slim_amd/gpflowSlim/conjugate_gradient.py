@@ -46,16 +46,64 @@ def cgsolver(K1, K2, b, C, max_iter=100, tol=1e-6):
 # (K(X, X) + s I) x = B on it, all columns of B at once (gps_kmvm, gps_kernel_cg: csrc/kmvm.hip).  kernel_logdet (stochastic Lanczos
 # quadrature on the solve's own coefficients) and kernel_grad_form (sum_ij G_ij dK_ij / d theta for a low-rank G) are what training
 # needs on top: GPR.compute_log_likelihood_and_gradients_iterative.
-MATRIX_FREE_SCOPE = "one stationary kernel: RBF, Matern12, Matern32, Matern52, Exponential or RatQuad"
+MATRIX_FREE_SCOPE = ("one stationary kernel: RBF, Matern12, Matern32, Matern52, Exponential or RatQuad; or, for products, solves "
+                     "without a preconditioner and prediction, a Sum of Products of those, Periodic, Cosine, Constant and White "
+                     "(at most 16 primitives and 64 feature rows)")
+SOP_MAX_PRIMS, SOP_MAX_ROWS = 16, 64          # csrc/kmat_common.hpp: GPS_SOP_MAX_PRIMS, GPS_SOP_MAX_ROWS
 
 
-def _matrix_free_program(kern, d_all):
-    """The kernel's program if the matrix-free path takes it, else NotImplementedError -- before anything touches the device."""
+def _sop_rows(k, d_all):
+    """Feature rows of one primitive of a sum of products, rounded up to 4 (csrc/kmvm_sop.hip), or NotImplementedError"""
     from . import kernels
+    if isinstance(k, (kernels.Constant, kernels.White)) or isinstance(k, kernels._SCALARS):
+        return 0
+    if isinstance(k, kernels.Cosine):
+        nf = 2
+    elif isinstance(k, kernels.Periodic):
+        nf = 2 * len(k._dims(False, d_all))
+    elif isinstance(k, (kernels.RBF, kernels.Matern12, kernels.Matern32, kernels.Matern52, kernels.Exponential, kernels.RatQuad)):
+        nf = len(k._dims(False, d_all))
+    elif isinstance(k, kernels.Sum):
+        raise NotImplementedError("the matrix-free path takes a sum of products, not a Sum under a Product: expand (a + b) * c "
+                                  "into a * c + b * c")
+    else:
+        raise NotImplementedError("the matrix-free path takes %s; got a %s factor" % (MATRIX_FREE_SCOPE, type(k).__name__))
+    if len(k._dims(False, d_all)) > 32:
+        raise ValueError("the matrix-free path takes at most 32 active dims per primitive")
+    return -(-nf // 4) * 4
+
+
+def _matrix_free_program(kern, d_all, composite=None):
+    """The kernel's program if the matrix-free path takes it, else NotImplementedError -- before anything touches the device.  The
+    one place where the scope is decided: a lone stationary primitive (one node: kmvm_kernel's route), or a Combination that is a
+    Sum of Products of primitives (more nodes: kmvm_sop_kernel's, the postfix program whose term flags the library compiles).
+    composite: None, or why the caller cannot take a Combination -- then the NotImplementedError names that limit."""
+    from . import kernels
+    if isinstance(kern, kernels.Combination):
+        if composite is not None:
+            raise NotImplementedError("%s takes %s; a %s kernel is %s" % (composite[0], MATRIX_FREE_SCOPE.split(";")[0],
+                                                                          type(kern).__name__, composite[1]))
+        terms = (kern.kern_list + kern.const_list) if isinstance(kern, kernels.Sum) else [kern]
+        prims = []
+        for t in terms:
+            prims.extend(t.kern_list + t.const_list if isinstance(t, kernels.Product) else [t])
+        if len(prims) == 1 and isinstance(prims[0], kernels.Kernel):      # (a Combination of one kernel is that kernel)
+            return _matrix_free_program(prims[0], d_all)
+        rows = sum(_sop_rows(k, d_all) for k in prims)
+        if len(prims) > SOP_MAX_PRIMS or rows > SOP_MAX_ROWS:
+            raise ValueError("the matrix-free path takes at most %d primitives and %d feature rows (active dims per primitive "
+                             "rounded up to 4, twice the dims for Periodic); got %d and %d"
+                             % (SOP_MAX_PRIMS, SOP_MAX_ROWS, len(prims), rows))
+        return kern._program(d_all)
     if not isinstance(kern, (kernels.RBF, kernels.Matern12, kernels.Matern32, kernels.Matern52, kernels.Exponential,
                              kernels.RatQuad)):
         raise NotImplementedError("the matrix-free path takes %s; got %s" % (MATRIX_FREE_SCOPE, type(kern).__name__))
     return kern._program(d_all)
+
+
+def _is_sop(prog):
+    """more than one node: the sum-of-products entries (gps_*_sop)"""
+    return len(prog) > 1
 
 
 def kernel_matmul(kern, X, V, X2=None, diag_add=0.0):
@@ -63,14 +111,15 @@ def kernel_matmul(kern, X, V, X2=None, diag_add=0.0):
     X = np.ascontiguousarray(X, dtype=settings.float_type)
     prog = _matrix_free_program(kern, X.shape[1])
     kern._check_inputs(*([X] if X2 is None else [X, X2]))
-    return be.kmvm(be.get_handle(), prog, X, V, X2=X2, diag_add=diag_add)
+    return (be.kmvm_sop if _is_sop(prog) else be.kmvm)(be.get_handle(), prog, X, V, X2=X2, diag_add=diag_add)
 
 
 def _precond_program(kern, X, rank, rel_tol, noise_var=None):
     """(X as the device takes it, the program) after the refusals of every call that takes a preconditioner's rank -- the kernel's
     scope, the rank in 0 .. 128, a noise above 0 with a rank --, all before anything touches the device."""
     X = np.ascontiguousarray(X, dtype=settings.float_type)
-    prog = _matrix_free_program(kern, X.shape[1])
+    prog = _matrix_free_program(kern, X.shape[1], composite=("the pivoted-Cholesky preconditioner (precond_rank > 0)",
+                                                             "not preconditioned: its step kernel knows one primitive"))
     be._check_precond(rank, rel_tol, None if noise_var is None else float(noise_var))
     kern._check_inputs(X)
     return X, prog
@@ -122,7 +171,16 @@ def kernel_cgsolver(kern, X, B, noise_var, max_iter=1000, tol=1e-8, lanczos=Fals
     prog = _matrix_free_program(kern, X.shape[1])
     be._check_precond(precond_rank, precond_rel_tol, float(noise_var))
     kern._check_inputs(X)
-    if precond_rank:
+    if _is_sop(prog):
+        if precond_rank:
+            _precond_program(kern, X, precond_rank, precond_rel_tol, noise_var)      # (raises: no preconditioner for a composite kernel)
+        res = be.kernel_cg_sop(be.get_handle(), prog, X, B, noise_var, max_iter=max_iter, tol=tol, lanczos=lanczos)
+        x, iters, rel, conv = res[:4]
+        info = {"iterations": iters, "relative_residual": rel, "converged": conv}
+        if lanczos:
+            rows = int(np.max(iters)) if iters.size else 0
+            info.update(alpha=res[4][:rows], beta=res[5][:rows])
+    elif precond_rank:
         x, info = _pcg(kern, X, B, noise_var, precond_rank, precond_rel_tol, max_iter, tol)
         rel = info["relative_residual"]
         if not lanczos:
@@ -146,7 +204,8 @@ def kernel_grad_form(kern, X, P, Q):
     slot of a noise variance.  P, Q [n, C]; K, its derivative and the weight P Q^T are regenerated tile by tile on the device
     (csrc/kmvm.hip: kmvm_grad_kernel), memory O(n (D + C)).  ``Q is P`` runs the symmetric weight as it is."""
     X = np.ascontiguousarray(X, dtype=settings.float_type)
-    prog = _matrix_free_program(kern, X.shape[1])
+    prog = _matrix_free_program(kern, X.shape[1], composite=("kernel_grad_form", "products, solves and prediction only: the fused "
+                                                             "gradient form knows one primitive"))
     kern._check_inputs(X)
     return be.kmvm_grad(be.get_handle(), prog, X, P, Q, len(kern._grad_layout(X.shape[1])))
 

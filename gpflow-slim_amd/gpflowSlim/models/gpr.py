@@ -190,7 +190,8 @@ class GPR(GPModel):
         if self._has_features():
             raise NotImplementedError("the matrix-free (iterative) route is not available on the feature (random-feature) branch; "
                                       "it takes " + cg.MATRIX_FREE_SCOPE)
-        cg._matrix_free_program(self.kern, self.X.shape[1])
+        cg._matrix_free_program(self.kern, self.X.shape[1], composite=("matrix-free training (the iterative route)", "predicted, "
+                                                                      "not trained, on this path: the fused gradient form knows one primitive"))
         if precond_rank:
             return self._lml_grad_preconditioned(cg, precond_rank, num_probes, seed, probes, max_iter, tol)
         N, R = self.Y.shape
@@ -325,7 +326,13 @@ class GPR(GPModel):
         self.kern._check_inputs(self.X, Xnew)
         noise = float(np.squeeze(self.likelihood.variance))
         be._check_precond(precond_rank, 1e-10, noise)
-        if precond_rank:
+        if len(prog) > 1:                  # a Sum of Products: gps_kernel_predict_sop, and no preconditioner
+            if precond_rank:
+                from ..conjugate_gradient import _precond_program
+                _precond_program(self.kern, self.X, precond_rank, 1e-10, noise)
+            mean, var, iters, rel, conv = be.kernel_predict_sop(be.get_handle(), prog, self.X, noise, self._resid(), Xnew,
+                                                                max_iter=max_iter, tol=tol)
+        elif precond_rank:
             mean, var, iters, rel, conv = be.kernel_predict_pcg(be.get_handle(), prog, self.X, noise, self._resid(), Xnew, precond_rank,
                                                                 max_iter=max_iter, tol=tol)
         else:

@@ -371,6 +371,22 @@ int gps_kernel_predict_pcg(gps_handle_t h, const gps_kern_node_t* prog, int n_no
                            double noise_var, const double* resid, int64_t r, const double* Xnew, int64_t n_new, int max_iter,
                            double tol, int rank_max, double rel_tol, double* mean_out, double* var_out, int64_t* iters_out,
                            double* relres_out, int* converged_out);
+/* ---- the same on a sum of products of primitives (csrc/kmvm_sop.hip) ----
+ * prog: a postfix program K = sum_terms prod_factors p -- no GPS_K_MUL takes a sum as an operand -- of GPS_K_RBF, _MATERN12, _MATERN32,
+ * _MATERN52, _EXPONENTIAL, _RATQUAD, _PERIODIC, _COSINE, _CONSTANT and _WHITE, at most 16 primitives and 64 feature rows (n_dims of a
+ * stationary primitive, 2 n_dims of a Periodic, 2 of a Cosine, each rounded up to 4).  Anything else: GPS_ERR_UNSUPPORTED before anything
+ * touches the device.  White is its variance where the row index equals the column index of K(X, X) and 0 against an X2.  The entries above keep
+ * refusing every program of more than one node.  Arguments, buffers and outputs are those of gps_kmvm, gps_kernel_cg_lanczos (coef_out
+ * may be NULL: gps_kernel_cg) and gps_kernel_predict; no preconditioner and no gradient form on this path.                        */
+int gps_kmvm_sop(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, const double* X2, int64_t n2,
+                 int64_t d_all, const double* V, int64_t T, double diag_add, double* out);
+int gps_kernel_cg_sop(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                      double noise_var, const double* B, int64_t T, int max_iter, double tol, double* x_out, int64_t* iters_out,
+                      double* relres_out, int* converged_out, double* coef_out);
+int gps_kernel_predict_sop(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                           double noise_var, const double* resid, int64_t r, const double* Xnew, int64_t n_new, int max_iter,
+                           double tol, double* mean_out, double* var_out, int64_t* iters_out, double* relres_out,
+                           int* converged_out);
 
 /* ---- conditionals.conditional / base_conditional ------------------------
  * (conditionals.py:24-66, 80-121; features.py:74-81 for Kuu/Kuf).

@@ -5,7 +5,11 @@ Up to n = 131072 a row "grad_form_C17" follows: one launch of the fused gradient
 kernels) for a general P Q^T of 17 columns -- one output and T = 16 probes, run doubled as 34 -> 36 weight columns --, beside the
 T = 16 product of the same process, and the ratio of the two medians.
 
-    python tools/kmvm_bench.py [--rank K] [--noise S] [reps] [n ...]    (default: 5 repetitions at n = 32768, 131072, 1000000)
+    python tools/kmvm_bench.py [--rank K] [--noise S] [--composite] [reps] [n ...]    (default: 5 repetitions at n = 32768, 131072, 1000000)
+
+--composite: rows "sop_mauna_T*" and "sop_rbf_periodic_T*" per size up to n = 131072 as well -- one product of the sum-of-products
+kernel (csrc/kmvm_sop.hip) on the five-term Mauna-Loa form RBF + RBF.Periodic + RatQuad + RBF + White over the first column and on
+RBF.Periodic at D = 8, in kernel-matrix entries per second, and the ratio to the single RBF's product of the same T and process.
 
 --rank K (1 .. 128; with --noise, default 1e-2): a row "pcg_rankK" per size as well -- a 16-column solve (tol 1e-8, at most 2000
 iterations) plain and preconditioned by the rank-K pivoted-Cholesky M (csrc/pchol.hip): iteration counts and wall time of each, and
@@ -25,6 +29,9 @@ from gpflowSlim import _backend as be  # noqa: E402
 import time  # noqa: E402
 
 argv, opts = sys.argv[1:], {"--rank": 0, "--noise": 1e-2}
+composite = "--composite" in argv
+if composite:
+    argv.remove("--composite")
 for flag in opts:
     if flag in argv:
         i = argv.index(flag)
@@ -65,6 +72,19 @@ for n in sizes:
         be.kmvm_grad(h, prog, X, P, Q, 1 + d)                                    # warm-up
         ms = [device_ms(lambda: be.kmvm_grad(h, prog, X, P, Q, 1 + d), ("kmat", "reduce", "other")) for _ in range(reps)]
         row["grad_form_C17"] = {"ms": stats(ms), "products_T16": float(np.median(ms)) / row["T16"]["ms"]["median"]}
+    if composite and n <= 131072:
+        k, one = gpf.kernels, [0]
+        forms = {"sop_mauna": k.RBF(1, lengthscales=3.0, active_dims=one) + k.RBF(1, active_dims=one) * k.Periodic(1, active_dims=one)
+                 + k.RatQuad(1, alpha=1.7, active_dims=one) + k.RBF(1, lengthscales=0.3, active_dims=one) + k.White(1, variance=0.1),
+                 "sop_rbf_periodic": kern * k.Periodic(d, period=1.7, lengthscales=np.sqrt(d))}
+        for name, comp in forms.items():
+            cprog = comp._program(d)
+            for T in (1, 16):
+                V = rng.standard_normal((n, T))
+                be.kmvm_sop(h, cprog, X, V, diag_add=0.1)                        # warm-up
+                ms = [device_ms(lambda: be.kmvm_sop(h, cprog, X, V, diag_add=0.1)) for _ in range(reps)]
+                row["%s_T%d" % (name, T)] = {"ms": stats(ms), "kernel_evals_per_s": float(n) * n / (1e-3 * float(np.median(ms))),
+                                             "single_rbf_products": float(np.median(ms)) / row["T%d" % T]["ms"]["median"]}
     if rank:
         B = rng.standard_normal((n, 16))
 
