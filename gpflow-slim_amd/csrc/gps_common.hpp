@@ -340,6 +340,8 @@ struct gps_handle_s {
   DevBuf dLanczos{bufs};                    // gps_kernel_cg_lanczos: alpha_k, beta_k of a batch's columns [max_iter][2][64]
   DevBuf dPcholL{bufs};                     // the preconditioner's factor L [pad64(n)][pad16(rank_max)] (pchol.hip), rebuilt by every call that uses it
   DevBuf dPcholWs{bufs};                    // ... and its workspace (gps_pchol_workspace: d, partials, C, chol(C)^-1, S, z)
+  DevBuf dLzQ{bufs};                        // the Lanczos vectors Q [pad64(n)][pad16(rank_max)] (lanczos.hip), rebuilt by every call that uses them
+  DevBuf dLzWs{bufs};                       // ... and the run's workspace (gps_lanczos_workspace: state, v, w, w1, w2, partials)
 };
 
 static inline int gps_fail(gps_handle_t h, int code, const std::string& msg) {

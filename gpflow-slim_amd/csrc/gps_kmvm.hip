@@ -11,6 +11,8 @@
 //                        primitives (kmvm_sop.hip): the same bodies with KmvmPlan::sop set; no preconditioner, no gradient form
 //   gps_kernel_pchol / _precond_solve / _pcg / _predict_pcg   the pivoted-Cholesky preconditioner M = L L^T + s I (pchol.hip): its
 //                        factor, M^-1 V / log det M / samples, and the two solvers above with every solve preconditioned
+//   gps_kernel_lanczos / gps_kernel_predict_lanczos   Lanczos with full reorthogonalisation on K(X, X) + s I (lanczos.hip): Q, alpha,
+//                        beta; and the prediction whose variances all come from one such run (dLzQ, dLzWs; A = K(Xnew, X) Q in dTmp)
 //
 // Stop rule of a column: |r_t| <= tol |b_t|, norm against norm (cgsolver of conjugate_gradient.py, gps_kron_cg, compares
 // tol |b| with the SQUARED residual norm; that rule is the reference's and stays there).  Reaching max_iter is not an error.
@@ -543,29 +545,35 @@ extern "C" int gps_kmvm_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_
   return GPS_OK;
 }
 
-// gps_kernel_predict, and with rank_max > 0 gps_kernel_predict_pcg: every solve below preconditioned by one M, built once a call
-static int kernel_predict_impl(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n,
+// What gps_kernel_predict and its kin share: the refusals, Kdiag, the plans of K(X, X) and K(Xnew, X), the preconditioner where
+// there is a rank, and the mean -- alpha = (K + s I)^-1 resid batch by batch, each pushed through K(Xnew, X) at once -- on its way
+// to mean_out.  done: n_new == 0, nothing left to do.
+struct PredictCtx { double kdiag; KmvmPlan plan, cross; i64 np, nsp; PcholPre pre; const PcholPre* pp; bool done; };
+static int kernel_predict_mean(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n,
                                int64_t d_all, double noise_var, const double* resid, int64_t r, const double* Xnew, int64_t n_new,
                                int max_iter, double tol, int rank_max, double rel_tol, double* mean_out, double* var_out,
-                               int64_t* iters_out, double* relres_out, int* converged_out, KmvmSop* sop = nullptr) {
+                               int64_t* iters_out, double* relres_out, int* converged_out, KmvmSop* sop, PredictCtx* c) {
   const std::string bad = std::string(who) + ": bad argument";
   if (!h || n <= 0 || r <= 0 || n_new < 0 || d_all <= 0 || max_iter < 0 || !(tol >= 0.0) || !(noise_var >= 0.0))
     return gps_fail(h, GPS_ERR_ARG, bad);
   if (int rf = pchol_check(h, who, rank_max, rel_tol, noise_var)) return rf;
   int rc = kmvm_begin(h, who, prog, n_nodes, sop != nullptr);
   if (rc) return rc;
+  c->done = n_new == 0;
   if (n_new == 0) return GPS_OK;
   if (!X || !resid || !Xnew || !mean_out || !var_out || !iters_out || !relres_out || !converged_out)
     return gps_fail(h, GPS_ERR_ARG, bad);
-  double kdiag = 0.0;
-  rc = gps_launch_kdiag(h, prog, n_nodes, &kdiag);      // (a sum of products: sum_terms prod variances, White's included)
+  c->kdiag = 0.0;
+  rc = gps_launch_kdiag(h, prog, n_nodes, &c->kdiag);   // (a sum of products: sum_terms prod variances, White's included)
   if (rc) return rc;
-  KmvmPlan plan;
+  KmvmPlan& plan = c->plan;
   rc = kmvm_sym_plan(h, prog, n_nodes, X, n, d_all, &plan, sop);
   if (rc) return rc;
   const i64 np = plan.npr, nsp = pad64(n_new);
-  PcholPre pre;
-  const PcholPre* pp = nullptr;
+  c->np = np; c->nsp = nsp;
+  PcholPre& pre = c->pre;
+  const PcholPre*& pp = c->pp;
+  pp = nullptr;
   if (rank_max > 0) {
     rc = pchol_build(h, who, plan, n, noise_var, rank_max, rel_tol, true, &pre);
     if (rc) return rc;
@@ -574,7 +582,8 @@ static int kernel_predict_impl(gps_handle_t h, const char* who, const gps_kern_n
   GPS_HIP(h, h->dXnew.ensure((size_t)n_new * d_all * 8));
   GPS_HIP(h, hipMemcpyAsync(h->dXnew.p, Xnew, (size_t)n_new * d_all * 8, hipMemcpyHostToDevice, h->stream));
   // ---- the mean: alpha batch by batch, each pushed through K(Xnew, X) at once
-  KmvmPlan cross = plan;
+  KmvmPlan& cross = c->cross;
+  cross = plan;
   rc = kmvm_features(h, prog, n_nodes, h->dXnew.d(), n_new, d_all, nsp, h->dGxTab, &cross.node, sop);
   if (rc) return rc;
   cross.Fr = h->dGxTab.d(); cross.npr = nsp; cross.sym = 0;
@@ -599,6 +608,22 @@ static int kernel_predict_impl(gps_handle_t h, const char* who, const gps_kern_n
     if (rc) return rc;
   }
   GPS_HIP(h, hipMemcpyAsync(mean_out, h->dMean.p, (size_t)n_new * r * 8, hipMemcpyDeviceToHost, h->stream));
+  return GPS_OK;
+}
+
+// gps_kernel_predict, and with rank_max > 0 gps_kernel_predict_pcg: every solve below preconditioned by one M, built once a call
+static int kernel_predict_impl(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n,
+                               int64_t d_all, double noise_var, const double* resid, int64_t r, const double* Xnew, int64_t n_new,
+                               int max_iter, double tol, int rank_max, double rel_tol, double* mean_out, double* var_out,
+                               int64_t* iters_out, double* relres_out, int* converged_out, KmvmSop* sop = nullptr) {
+  PredictCtx ctx;
+  int rc = kernel_predict_mean(h, who, prog, n_nodes, X, n, d_all, noise_var, resid, r, Xnew, n_new, max_iter, tol, rank_max, rel_tol,
+                               mean_out, var_out, iters_out, relres_out, converged_out, sop, &ctx);
+  if (rc || ctx.done) return rc;
+  const KmvmPlan& plan = ctx.plan;
+  const i64 np = ctx.np;
+  const PcholPre* pp = ctx.pp;
+  const double kdiag = ctx.kdiag;
   // ---- the variance, sixteen test points to a solve
   KcgBufs b;
   rc = kcg_buffers(h, np, 16, b);
@@ -652,4 +677,146 @@ extern "C" int gps_kernel_predict_sop(gps_handle_t h, const gps_kern_node_t* pro
   KmvmSop sop;
   return kernel_predict_impl(h, "gps_kernel_predict_sop", prog, n_nodes, X, n, d_all, noise_var, resid, r, Xnew, n_new, max_iter, tol, 0, 0.0,
                              mean_out, var_out, iters_out, relres_out, converged_out, &sop);
+}
+
+// ---- Lanczos with full reorthogonalisation (lanczos.hip) and the variance estimate built on it ------------------------------------
+// One entry each for a lone primitive and for a sum of products: more than one node is the sum-of-products plan, as on the host side.
+#define LZ_CHECK_EVERY 8
+#define LZ_PREDICT_BREAKDOWN_TOL 1e-12
+
+static int lanczos_check(gps_handle_t h, const char* who, int64_t n, int rank_max) {
+  if (rank_max < 1 || rank_max > 128 || rank_max > n)
+    return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": the Lanczos rank must be 1 .. 128 and at most n");
+  return GPS_OK;
+}
+
+// Q (dLzQ) and the workspace (dLzWs) of a run of rank_max steps at most; nvp: rows of the operand v
+static int lanczos_buffers(gps_handle_t h, i64 np, i64 nvp, int rank_max, LzPlan* lz) {
+  const int kp = (rank_max + 15) / 16 * 16;
+  const size_t wsb = gps_lanczos_workspace(np, nvp, kp, lz);
+  GPS_HIP(h, h->dLzQ.ensure((size_t)np * kp * 8));
+  GPS_HIP(h, h->dLzWs.ensure(wsb));
+  lz->Q = h->dLzQ.d(); lz->ws = h->dLzWs.d();
+  return GPS_OK;
+}
+
+// The run from the start vector in column 0 of lz.w(): q_0, then product and step until rank_max or a breakdown.  The host reads
+// the state every LZ_CHECK_EVERY steps only to stop launching (surplus launches return at once), and once at the end into *hs.
+// A zero or non-finite start vector is GPS_ERR_ARG.
+static int lanczos_run(gps_handle_t h, const char* who, const KmvmPlan& plan, const LzPlan& lz, i64 n, double noise_var, int rank_max,
+                       double tol, LzState* hs) {
+  int rc = gps_launch_lanczos_init(h, lz);
+  if (rc) return rc;
+  rc = gps_launch_lanczos_start(h, lz, n);
+  if (rc) return rc;
+  bool fresh = false;
+  for (int j = 0; j < rank_max; ++j) {
+    rc = gps_launch_kmvm(h, plan, lz.v(), 16, 16, noise_var, lz.w(), 16, &lz.st()->stop);
+    if (rc) return rc;
+    rc = gps_launch_lanczos_step(h, lz, n, j, rank_max, tol);
+    if (rc) return rc;
+    fresh = false;
+    if ((j + 1) % LZ_CHECK_EVERY == 0) {
+      GPS_HIP(h, hipMemcpyAsync(hs, lz.st(), sizeof(*hs), hipMemcpyDeviceToHost, h->stream));
+      GPS_HIP(h, hipStreamSynchronize(h->stream));
+      fresh = true;
+      if (hs->stop) break;
+    }
+  }
+  if (!fresh) {
+    GPS_HIP(h, hipMemcpyAsync(hs, lz.st(), sizeof(*hs), hipMemcpyDeviceToHost, h->stream));
+    GPS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  if (hs->stop == 2) return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": the start vector is zero or not finite");
+  return GPS_OK;
+}
+
+extern "C" int gps_kernel_lanczos(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                                  double noise_var, const double* start, int rank_max, double breakdown_tol, double* Q_out,
+                                  double* alpha_out, double* beta_out, int64_t* rank_out) {
+  const char* who = "gps_kernel_lanczos";
+  if (!h || n <= 0 || d_all <= 0 || !(noise_var >= 0.0) || !(breakdown_tol >= 0.0)) return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": bad argument");
+  if (int rf = lanczos_check(h, who, n, rank_max)) return rf;
+  KmvmSop sopbuf;
+  KmvmSop* sop = n_nodes > 1 ? &sopbuf : nullptr;
+  int rc = kmvm_begin(h, who, prog, n_nodes, sop != nullptr);
+  if (rc) return rc;
+  if (!X || !start || !Q_out || !alpha_out || !beta_out || !rank_out) return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": bad argument");
+  *rank_out = 0;
+  KmvmPlan plan;
+  rc = kmvm_sym_plan(h, prog, n_nodes, X, n, d_all, &plan, sop);
+  if (rc) return rc;
+  const i64 np = plan.npr;
+  LzPlan lz;
+  rc = lanczos_buffers(h, np, np, rank_max, &lz);
+  if (rc) return rc;
+  GPS_HIP(h, h->dStage.ensure((size_t)n * rank_max * 8));
+  GPS_HIP(h, hipMemcpyAsync(h->dStage.p, start, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+  rc = kmvm_pad_cols(h, h->dStage.d(), 1, n, 0, 1, lz.w(), np, 16);
+  if (rc) return rc;
+  LzState hs;
+  rc = lanczos_run(h, who, plan, lz, n, noise_var, rank_max, breakdown_tol, &hs);
+  if (rc) return rc;
+  rc = gps_launch_extract(h, lz.Q, lz.kp, n, rank_max, h->dStage.d(), rank_max, 0);
+  if (rc) return rc;
+  GPS_HIP(h, hipMemcpyAsync(Q_out, h->dStage.p, (size_t)n * rank_max * 8, hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipStreamSynchronize(h->stream));
+  for (int i = 0; i < rank_max; ++i) {
+    alpha_out[i] = i < hs.steps ? hs.alpha[i] : 0.0;
+    beta_out[i] = i < hs.steps ? hs.beta[i] : 0.0;
+  }
+  *rank_out = hs.steps;
+  return GPS_OK;
+}
+
+// The mean as gps_kernel_predict (one CG solve); the variance from one Lanczos run started at K(X, Xnew) 1 / N* (Pleiss et al.):
+// var_j = Kdiag - |L_T^-1 Q^T k_j|^2 with A = K(Xnew, X) Q from the fused product, 64 columns a pass and 16 for what is left.
+extern "C" int gps_kernel_predict_lanczos(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n,
+                                          int64_t d_all, double noise_var, const double* resid, int64_t r, const double* Xnew,
+                                          int64_t n_new, int rank_max, int max_iter, double tol, double* mean_out, double* var_out,
+                                          int64_t* iters_out, double* relres_out, int* converged_out, int64_t* rank_out) {
+  const char* who = "gps_kernel_predict_lanczos";
+  if (!h || !rank_out) return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": bad argument");
+  if (int rf = lanczos_check(h, who, n, rank_max)) return rf;
+  *rank_out = 0;
+  KmvmSop sopbuf;
+  PredictCtx ctx;
+  int rc = kernel_predict_mean(h, who, prog, n_nodes, X, n, d_all, noise_var, resid, r, Xnew, n_new, max_iter, tol, 0, 0.0, mean_out,
+                               var_out, iters_out, relres_out, converged_out, n_nodes > 1 ? &sopbuf : nullptr, &ctx);
+  if (rc || ctx.done) return rc;
+  const i64 np = ctx.np, nsp = ctx.nsp;
+  LzPlan lz;
+  rc = lanczos_buffers(h, np, np > nsp ? np : nsp, rank_max, &lz);
+  if (rc) return rc;
+  // the start vector: w = K(X, Xnew) (1 / N*), one product with the test points as the column points
+  KmvmPlan kxn = ctx.plan;
+  kxn.Fc = ctx.cross.Fr; kxn.npc = nsp; kxn.sym = 0;
+  rc = gps_launch_lanczos_fill(h, lz, n_new, nsp, 1.0 / (double)n_new);
+  if (rc) return rc;
+  rc = gps_launch_kmvm(h, kxn, lz.v(), 16, 16, 0.0, lz.w(), 16, nullptr);
+  if (rc) return rc;
+  LzState hs;
+  rc = lanczos_run(h, who, ctx.plan, lz, n, noise_var, rank_max, LZ_PREDICT_BREAKDOWN_TOL, &hs);
+  if (rc) return rc;
+  rc = gps_launch_lanczos_tchol(h, lz);
+  if (rc) return rc;
+  // A = K(Xnew, X) Q over the columns in use (the run's rank padded to 16; the rest of Q is zero and is not read)
+  const i64 ku = ((i64)hs.steps + 15) / 16 * 16;
+  GPS_HIP(h, h->dTmp.ensure((size_t)nsp * lz.kp * 8));
+  GPS_HIP(h, h->dVar.ensure((size_t)nsp * 8));
+  for (i64 c0 = 0; c0 < ku;) {
+    const i64 cols = ku - c0 >= 64 ? 64 : 16;
+    rc = gps_launch_kmvm(h, ctx.cross, lz.Q + c0, lz.kp, cols, 0.0, h->dTmp.d() + c0, lz.kp, nullptr);
+    if (rc) return rc;
+    c0 += cols;
+  }
+  rc = gps_launch_lanczos_var(h, lz, h->dTmp.d(), n_new, ctx.kdiag, h->dVar.d());
+  if (rc) return rc;
+  GPS_HIP(h, hipMemcpyAsync(var_out, h->dVar.p, (size_t)n_new * 8, hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipMemcpyAsync(&hs, lz.st(), sizeof(hs), hipMemcpyDeviceToHost, h->stream));
+  GPS_HIP(h, hipStreamSynchronize(h->stream));
+  if (hs.stop == 3)
+    return gps_fail(h, GPS_ERR_STATE, std::string(who) + ": the Lanczos tridiagonal is not positive definite in fp64; lower the rank or raise the noise");
+  *rank_out = hs.steps;
+  return GPS_OK;
 }

@@ -277,6 +277,31 @@ int gps_launch_pchol_gram(gps_handle_t h, const PcholPre& pre, double noise);
 int gps_launch_pchol_ls(gps_handle_t h, const PcholPre& pre, const double* V, i64 tp, double c1, double c1lo, int col0, double c2,
                         double* out, double* part, const int* skip);
 int gps_launch_pchol_apply(gps_handle_t h, const PcholPre& pre, const double* V, i64 tp, double* out, double* part, const int* skip);
+// lanczos.hip : Lanczos with full reorthogonalisation on (K(X, X) + s I) through gps_launch_kmvm, and the variance epilogue (see
+// there).  Q [np][kp] and one workspace `ws` (doubles, gps_lanczos_workspace fills the offsets; nvp: rows of the product's operand
+// v, np or more where the start vector is formed from more column points).
+#define LZ_MAX_BLOCKS 256
+struct LzState { double alpha[128]; double beta[128]; double ld[128]; double le[128]; double scale; int steps; int stop; };
+struct LzPlan {
+  i64 np, nv; int kp, nblk;
+  double* Q; double* ws;
+  size_t o_st, o_v, o_w, o_w1, o_w2, o_part1, o_part2, o_partn;
+  LzState* st() const { return (LzState*)(ws + o_st); }
+  double* v() const { return ws + o_v; }
+  double* w() const { return ws + o_w; }
+  double* w1() const { return ws + o_w1; }
+  double* w2() const { return ws + o_w2; }
+  double* part1() const { return ws + o_part1; }
+  double* part2() const { return ws + o_part2; }
+  double* partn() const { return ws + o_partn; }
+};
+size_t gps_lanczos_workspace(i64 np, i64 nvp, int kp, LzPlan* lz);      // bytes of ws
+int gps_launch_lanczos_init(gps_handle_t h, const LzPlan& lz);                                   // Q, v and the state to zero
+int gps_launch_lanczos_fill(gps_handle_t h, const LzPlan& lz, i64 rows, i64 rows_pad, double val);   // v[:, 0] = val on `rows` rows
+int gps_launch_lanczos_start(gps_handle_t h, const LzPlan& lz, i64 n);                           // q_0 = w[:, 0] / |w[:, 0]|
+int gps_launch_lanczos_step(gps_handle_t h, const LzPlan& lz, i64 n, int j, int rank_max, double tol);   // after w = K_y q_j
+int gps_launch_lanczos_tchol(gps_handle_t h, const LzPlan& lz);
+int gps_launch_lanczos_var(gps_handle_t h, const LzPlan& lz, const double* A, i64 n_new, double kdiag, double* var);
 // kmvm.hip : the fused gradient form  sum_ij G_ij dK_ij / d theta  for K(X, X) and G = P Q^T, one pass of at most 64 weight columns
 // (32 where P != Q: the pass runs [P | Q], [Q | P] and the caller halves).  P, Q device [n, ldc], columns c0 .. c0 + tc - 1; Pt, Qt:
 // room for [64][npr] doubles each; scale: host [nf + 3] factors; vals_out: device [nf + 3] = scale o [sum G K, one raw sum per

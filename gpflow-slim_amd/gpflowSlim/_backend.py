@@ -1451,3 +1451,48 @@ def kernel_predict_pcg(h, prog, X, noise_var, resid, Xnew, rank_max, rel_tol=1e-
             int(max_iter), float(tol), int(rank_max), float(rel_tol), _ptr(mean), _ptr(var),
             iters.ctypes.data_as(ctypes.POINTER(_i64)), _ptr(rel), conv.ctypes.data_as(_c_int_p))
     return mean, var, iters, rel, conv != 0
+
+
+# ---- Lanczos variance estimates of the matrix-free path (csrc/lanczos.hip) ---------------------------------------------------------------
+# Module functions like the ones above: Q and T are rebuilt inside every call and nothing stays resident.
+def _check_lanczos_rank(rank, n):
+    """The refusal of every entry that takes a Lanczos rank, before anything touches the device."""
+    _need(isinstance(rank, (int, np.integer)) and 1 <= rank <= 128 and rank <= n,
+          "the Lanczos rank must be an integer in 1 .. 128 and at most N = %d" % n)
+
+
+def kernel_lanczos(h, prog, X, noise_var, start, rank_max, breakdown_tol=1e-12):
+    """gps_kernel_lanczos: (Q [n, k], alpha [k], beta [k - 1]) of k <= rank_max Lanczos steps with full reorthogonalisation on
+    K(X, X) + noise_var I from ``start`` [n]: Q^T Q = I, Q^T (K + noise_var I) Q = tridiag(alpha, beta).  More than one node in
+    ``prog``: the sum-of-products plan."""
+    X, start = _f64(X), _f64(start).reshape(-1)
+    _need(X.ndim == 2 and start.shape[0] == X.shape[0] and X.shape[0] > 0, "X must be [N, D] and the start vector [N]")
+    n = X.shape[0]
+    _check_lanczos_rank(rank_max, n)
+    _need(breakdown_tol >= 0.0, "breakdown_tol must be >= 0")
+    Q, alpha, beta = np.zeros((n, int(rank_max))), np.zeros(int(rank_max)), np.zeros(int(rank_max))
+    rank = np.zeros(1, dtype=np.int64)
+    h._drop_resident()
+    h._call("gps_kernel_lanczos", prog, len(prog), _ptr(X), n, X.shape[1], float(noise_var), _ptr(start), int(rank_max),
+            float(breakdown_tol), _ptr(Q), _ptr(alpha), _ptr(beta), rank.ctypes.data_as(ctypes.POINTER(_i64)))
+    k = int(rank[0])
+    return np.ascontiguousarray(Q[:, :k]), alpha[:k].copy(), beta[:max(k - 1, 0)].copy()
+
+
+def kernel_predict_lanczos(h, prog, X, noise_var, resid, Xnew, rank_max, max_iter=1000, tol=1e-8):
+    """gps_kernel_predict_lanczos: (mean [N*, R], var [N*], iterations [R], |r| / |b| [R], converged [R], Lanczos rank found): the
+    mean by the solve of ``kernel_predict``, the variance of every test point from one Lanczos run of rank_max steps at most."""
+    X, resid, Xnew = _f64(X), _f64(resid), _f64(Xnew)
+    _need(X.ndim == 2 and resid.ndim == 2 and resid.shape[0] == X.shape[0] and X.shape[0] > 0 and resid.shape[1] > 0,
+          "X must be [N, D] and the residual [N, R]")
+    _need(Xnew.ndim == 2 and Xnew.shape[1] == X.shape[1], "Xnew must be [N*, %d]" % X.shape[1])
+    n, r, n_new = X.shape[0], resid.shape[1], Xnew.shape[0]
+    _check_lanczos_rank(rank_max, n)
+    mean, var = np.zeros((n_new, r)), np.zeros(n_new)
+    iters, rel, conv = np.zeros(r, dtype=np.int64), np.zeros(r), np.zeros(r, dtype=np.intc)
+    rank = np.zeros(1, dtype=np.int64)
+    h._drop_resident()
+    h._call("gps_kernel_predict_lanczos", prog, len(prog), _ptr(X), n, X.shape[1], float(noise_var), _ptr(resid), r, _ptr(Xnew), n_new,
+            int(rank_max), int(max_iter), float(tol), _ptr(mean), _ptr(var), iters.ctypes.data_as(ctypes.POINTER(_i64)), _ptr(rel),
+            conv.ctypes.data_as(_c_int_p), rank.ctypes.data_as(ctypes.POINTER(_i64)))
+    return mean, var, iters, rel, conv != 0, int(rank[0])

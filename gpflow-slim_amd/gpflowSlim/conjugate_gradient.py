@@ -132,6 +132,18 @@ def kernel_pivoted_cholesky(kern, X, rank, rel_tol=1e-10):
     return be.kernel_pchol(be.get_handle(), prog, X, rank, rel_tol)
 
 
+def kernel_lanczos(kern, X, noise_var, start, rank, breakdown_tol=1e-12):
+    """(Q [n, k], alpha [k], beta [k - 1]): k <= rank <= min(128, n) steps of Lanczos with full reorthogonalisation on
+    K_y = K(X, X) + noise_var I from q_0 = start / |start|, K never stored (csrc/lanczos.hip).  Q^T Q = I and
+    Q^T K_y Q = tridiag(alpha, beta); the run stops early, with the columns it has, once beta_j <= breakdown_tol |K_y q_0| (the
+    Krylov space of ``start`` is exhausted).  What GPR.predict_f_iterative(variance="lanczos") builds its variances on."""
+    X = np.ascontiguousarray(X, dtype=settings.float_type)
+    prog = _matrix_free_program(kern, X.shape[1])
+    be._check_lanczos_rank(rank, X.shape[0])
+    kern._check_inputs(X)
+    return be.kernel_lanczos(be.get_handle(), prog, X, noise_var, start, rank, breakdown_tol)
+
+
 def kernel_precond_solve(kern, X, V, noise_var, rank, rel_tol=1e-10, G1=None):
     """(M^-1 V [n, T], log det M) for the preconditioner M = L L^T + noise_var I of kernel_cgsolver(precond_rank=rank), by Woodbury
     on the device.  G1 [rank, T]: the sample L G1 + sqrt(noise_var) V of N(0, M) (G1, V standard normal) in place of M^-1 V."""

@@ -308,14 +308,18 @@ class GPR(GPModel):
             fvar = np.tile(np.reshape(var, (-1, 1)), [1, R])       # models/gpr.py:131
         return fmean, fvar
 
-    def predict_f_iterative(self, Xnew, max_iter=1000, tol=1e-8, precond_rank=0):
+    def predict_f_iterative(self, Xnew, max_iter=1000, tol=1e-8, precond_rank=0, variance="solve", variance_rank=64):
         """predict_f without the N x N matrix (not in the reference): alpha = (K + s I)^-1 (Y - m(X)) by batched conjugate
         gradients on the fused kernel product, mean = K(Xnew, X) alpha + m(Xnew), var_j = Kdiag - k_j^T (K + s I)^-1 k_j sixteen
         test points to a solve.  Returns (mean [N*, R], var [N*, R]) like predict_f; device memory O(N (D + R + 16)) for the solves
         plus 512 N bytes for the variance's right-hand sides (the kernel-matrix build writes tiles of 64 rows for 16 test points).  Hyper-parameters
         are trained on this path by compute_log_likelihood_and_gradients_iterative (``self.iterative``).  A solve that did not
         reach tol within max_iter is reported by a warning.  precond_rank (0 .. 128; 0: the plain loop): every solve
-        preconditioned by the pivoted-Cholesky M = L L^T + s I of that rank at most, built once a call (csrc/pchol.hip)."""
+        preconditioned by the pivoted-Cholesky M = L L^T + s I of that rank at most, built once a call (csrc/pchol.hip).
+        variance="lanczos": the variances of all test points from one Lanczos run of variance_rank (1 .. 128, at most N) steps on
+        K + s I (Pleiss et al. 2018; csrc/lanczos.hip) in place of N* / 16 solves: var_j = Kdiag - (Q^T k_j)^T T^-1 (Q^T k_j), which
+        never falls below the exact variance and reaches it as the rank grows; variance_rank kernel products and one rectangular
+        product, device memory O(N (D + variance_rank)).  The mean is the same solve either way; no preconditioner with it."""
         import warnings
         from ..conjugate_gradient import _matrix_free_program, MATRIX_FREE_SCOPE
         if self._has_features():
@@ -326,7 +330,16 @@ class GPR(GPModel):
         self.kern._check_inputs(self.X, Xnew)
         noise = float(np.squeeze(self.likelihood.variance))
         be._check_precond(precond_rank, 1e-10, noise)
-        if len(prog) > 1:                  # a Sum of Products: gps_kernel_predict_sop, and no preconditioner
+        if variance not in ("solve", "lanczos"):
+            raise ValueError("predict_f_iterative: variance must be 'solve' or 'lanczos', got %r" % (variance,))
+        if variance == "lanczos":
+            if precond_rank:
+                raise ValueError("predict_f_iterative: variance='lanczos' takes no preconditioner; got precond_rank = %d"
+                                 % precond_rank)
+            be._check_lanczos_rank(variance_rank, self.X.shape[0])
+            mean, var, iters, rel, conv, _ = be.kernel_predict_lanczos(be.get_handle(), prog, self.X, noise, self._resid(), Xnew,
+                                                                       variance_rank, max_iter=max_iter, tol=tol)
+        elif len(prog) > 1:                # a Sum of Products: gps_kernel_predict_sop, and no preconditioner
             if precond_rank:
                 from ..conjugate_gradient import _precond_program
                 _precond_program(self.kern, self.X, precond_rank, 1e-10, noise)

@@ -387,6 +387,26 @@ int gps_kernel_predict_sop(gps_handle_t h, const gps_kern_node_t* prog, int n_no
                            double noise_var, const double* resid, int64_t r, const double* Xnew, int64_t n_new, int max_iter,
                            double tol, double* mean_out, double* var_out, int64_t* iters_out, double* relres_out,
                            int* converged_out);
+/* ---- Lanczos variance estimates on the same product (Pleiss et al. 2018; csrc/lanczos.hip) ----
+ * prog: one primitive of the scope of gps_kmvm, or (n_nodes > 1) a sum of products of the scope of gps_kmvm_sop.  rank_max is 1 .. 128
+ * and at most n (GPS_ERR_ARG otherwise, before any device work).  Full reorthogonalisation (classical Gram-Schmidt, twice), all state
+ * on the device, no floating-point atomics: equal bytes from call to call.
+ *
+ * gps_kernel_lanczos: rank_max steps at most on K(X, X) + noise_var I from q_0 = start / |start| (start host [n]; zero or not finite:
+ * GPS_ERR_ARG).  The run stops early at step j when beta_j <= breakdown_tol |(K + noise_var I) q_0|.  Q_out host [n, rank_max]
+ * (zero columns from *rank_out on), alpha_out [rank_max] the diagonal and beta_out [rank_max] the off-diagonal (beta_j couples q_j and
+ * q_j+1) of T = Q^T (K + noise_var I) Q, zeros from *rank_out on.                                                                    */
+int gps_kernel_lanczos(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                       double noise_var, const double* start, int rank_max, double breakdown_tol, double* Q_out, double* alpha_out,
+                       double* beta_out, int64_t* rank_out);
+/* gps_kernel_predict with the variance of all test points from one Lanczos run: the mean is the same solve (iters_out / relres_out /
+ * converged_out [r]); var_j = Kdiag - |L^-1 Q^T k_j|^2 with T = L L^T, Q and T from rank_max steps at most started at
+ * K(X, Xnew) 1 / n_new (breakdown at 1e-12), and Q^T k_j from one rectangular product K(Xnew, X) Q.  *rank_out: the steps taken.
+ * GPS_ERR_STATE if T is not positive definite in fp64.  Memory O(n (d_all + rank_max)).                                              */
+int gps_kernel_predict_lanczos(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                               double noise_var, const double* resid, int64_t r, const double* Xnew, int64_t n_new, int rank_max,
+                               int max_iter, double tol, double* mean_out, double* var_out, int64_t* iters_out, double* relres_out,
+                               int* converged_out, int64_t* rank_out);
 
 /* ---- conditionals.conditional / base_conditional ------------------------
  * (conditionals.py:24-66, 80-121; features.py:74-81 for Kuu/Kuf).
