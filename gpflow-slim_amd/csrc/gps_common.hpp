@@ -342,6 +342,8 @@ struct gps_handle_s {
   DevBuf dPcholWs{bufs};                    // ... and its workspace (gps_pchol_workspace: d, partials, C, chol(C)^-1, S, z)
   DevBuf dLzQ{bufs};                        // the Lanczos vectors Q [pad64(n)][pad16(rank_max)] (lanczos.hip), rebuilt by every call that uses them
   DevBuf dLzWs{bufs};                       // ... and the run's workspace (gps_lanczos_workspace: state, v, w, w1, w2, partials)
+  DevBuf dKmvmF32{bufs};                    // the fp32 product's tables (kmvm_f32.hip): 64 doubles of column sums | rows' floats | columns' floats
+  DevBuf dKmxVec{bufs};                     // the mixed-precision solve's outer vectors x | r [pad64(n)][<= 64] each, then |r_t|^2 [64]
 };
 
 static inline int gps_fail(gps_handle_t h, int code, const std::string& msg) {

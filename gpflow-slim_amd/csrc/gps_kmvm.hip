@@ -13,6 +13,9 @@
 //                        factor, M^-1 V / log det M / samples, and the two solvers above with every solve preconditioned
 //   gps_kernel_lanczos / gps_kernel_predict_lanczos   Lanczos with full reorthogonalisation on K(X, X) + s I (lanczos.hip): Q, alpha,
 //                        beta; and the prediction whose variances all come from one such run (dLzQ, dLzWs; A = K(Xnew, X) Q in dTmp)
+//   gps_kmvm_f32 / gps_kernel_cg_mixed / gps_kernel_predict_mixed   the first with K and the product in fp32 (kmvm_f32.hip), and the
+//                        second and fifth by iterative refinement on it under an fp64 residual (kcg_solve_mixed below; dKmvmF32: the
+//                        centred fp32 feature tables, dKmxVec: the outer x and r); one primitive, no preconditioner
 //
 // Stop rule of a column: |r_t| <= tol |b_t|, norm against norm (cgsolver of conjugate_gradient.py, gps_kron_cg, compares
 // tol |b| with the SQUARED residual norm; that rule is the reference's and stays there).  Reaching max_iter is not an error.
@@ -79,24 +82,15 @@ static int kcg_buffers(gps_handle_t h, i64 np, i64 tp, KcgBufs& b) {
 // comparison r^T r <= tol^2 b^T b on the device's own numbers, not one recomputed from the quotient --, on the host.
 // The vector kernels of the loop walk the n real rows only: a padded row of K p is not 0 (a padded point has zero features, not a
 // zero kernel value), and left alone the padded rows of r and p keep the zeros they start from.
-static int kcg_solve(gps_handle_t h, const KmvmPlan& plan, i64 n, const KcgBufs& b, const double* B, i64 tp, double noise, int max_iter,
-                     double tol, i64 tc, int64_t* iters, double* relres, int* conv, double* lz = nullptr, int* launched_out = nullptr,
-                     const PcholPre* pre = nullptr) {
-  const i64 np = plan.npr;
+// The loop proper, after gps_launch_kcg_init (and the preconditioned start): launches until max_iter, or until a read of the state
+// -- every KCG_CHECK_EVERY iterations -- shows every column finished.  *fresh: *hs is the state after the last launch.
+static int kcg_loop(gps_handle_t h, const KmvmPlan& plan, i64 n, const KcgBufs& b, i64 tp, double noise, int max_iter, double* lz,
+                    const PcholPre* pre, KcgState* hsp, int* launched_out, bool* fresh_out) {
   const int tb = (int)(tp / 16);
-  int rc = gps_launch_kcg_init(h, b.st, B, b.r, b.p, b.x, np, tb, tol, max_iter, b.part0);
-  if (rc) return rc;
-  // pre: the preconditioned loop -- z = M^-1 r after every update (three launches, which also leave the partials of r^T z), the
-  // step's numerator and beta from r^T z; without it the launches below are the plain loop's, argument for argument
+  int rc = GPS_OK;
   double *pz = nullptr, *prz = nullptr, *rzs = nullptr;
-  if (pre) {
-    pz = pre->ws + pre->o_z; prz = pre->ws + pre->o_rzpart; rzs = pre->ws + pre->o_rzs;
-    rc = gps_launch_pchol_apply(h, *pre, b.r, tp, pz, prz, &b.st->all_done[0]);
-    if (rc) return rc;
-    rc = gps_launch_pcg_dir(h, b.st, -1, nullptr, prz, pre->lsg, pz, b.p, n, tb, nullptr, rzs);
-    if (rc) return rc;
-  }
-  KcgState hs;
+  if (pre) { pz = pre->ws + pre->o_z; prz = pre->ws + pre->o_rzpart; rzs = pre->ws + pre->o_rzs; }
+  KcgState& hs = *hsp;
   int launched = 0;
   bool fresh = false;
   while (launched < max_iter) {
@@ -122,6 +116,31 @@ static int kcg_solve(gps_handle_t h, const KmvmPlan& plan, i64 n, const KcgBufs&
       if (hs.all_done[launched & 1]) break;
     }
   }
+  *launched_out = launched; *fresh_out = fresh;
+  return GPS_OK;
+}
+
+static int kcg_solve(gps_handle_t h, const KmvmPlan& plan, i64 n, const KcgBufs& b, const double* B, i64 tp, double noise, int max_iter,
+                     double tol, i64 tc, int64_t* iters, double* relres, int* conv, double* lz = nullptr, int* launched_out = nullptr,
+                     const PcholPre* pre = nullptr) {
+  const i64 np = plan.npr;
+  const int tb = (int)(tp / 16);
+  int rc = gps_launch_kcg_init(h, b.st, B, b.r, b.p, b.x, np, tb, tol, max_iter, b.part0);
+  if (rc) return rc;
+  // pre: the preconditioned loop -- z = M^-1 r after every update (three launches, which also leave the partials of r^T z), the
+  // step's numerator and beta from r^T z; without it the launches of kcg_loop are the plain loop's, argument for argument
+  if (pre) {
+    double *pz = pre->ws + pre->o_z, *prz = pre->ws + pre->o_rzpart, *rzs = pre->ws + pre->o_rzs;
+    rc = gps_launch_pchol_apply(h, *pre, b.r, tp, pz, prz, &b.st->all_done[0]);
+    if (rc) return rc;
+    rc = gps_launch_pcg_dir(h, b.st, -1, nullptr, prz, pre->lsg, pz, b.p, n, tb, nullptr, rzs);
+    if (rc) return rc;
+  }
+  KcgState hs;
+  int launched = 0;
+  bool fresh = false;
+  rc = kcg_loop(h, plan, n, b, tp, noise, max_iter, lz, pre, &hs, &launched, &fresh);
+  if (rc) return rc;
   if (!fresh) {
     GPS_HIP(h, hipMemcpyAsync(&hs, b.st, sizeof(hs), hipMemcpyDeviceToHost, h->stream));
     GPS_HIP(h, hipStreamSynchronize(h->stream));
@@ -133,6 +152,117 @@ static int kcg_solve(gps_handle_t h, const KmvmPlan& plan, i64 n, const KcgBufs&
     if (relres) relres[t] = hs.bb[t] > 0.0 ? sqrt(hs.rr[slot][t] / hs.bb[t]) : 0.0;
     if (conv) conv[t] = hs.rr[slot][t] <= hs.tol2 * hs.bb[t] ? 1 : 0;
   }
+  return GPS_OK;
+}
+
+// ---- the mixed-precision solve ---------------------------------------------------------------------------------------------------
+// Iterative refinement around the loop above: x = 0, r = b; an outer step solves A d = r by that loop on the fp32 product
+// (plan.Fr32, kmvm_f32.hip) until |r_inner| <= inner_tol |r| per column, then x += d and r = b - A x with the fp64 product.  Column
+// t is finished when |r_t| <= tol |b_t| on that fp64 residual -- the fp64 solver's rule, on a true residual -- and its column of r
+// is zeroed, so that the next correction solve skips it (b = 0: finished after 0 iterations, as there).  If an outer step fails to
+// halve a live column's fp64 residual (condition number x fp32 product error of order 1) or max_outer is reached, the columns still
+// live are finished by the fp64 loop on A d = r, its stop rule measured against |b| (kmx_setbb): its recurrence residual r - A d IS
+// b - A (x + d), so the contract is then gps_kernel_cg's (converged_out: the loop's own comparison).  Its x is checked the same way
+// -- x += d, r = b - A x -- and where the recurrence has drifted from that residual the fp64 loop runs again on it, while it
+// halves.  A step that made a column's fp64 residual larger is not taken for that column (kmx_commit: x and r stay).  max_iter counts inner iterations summed over the outer steps (per step: the live columns' largest count); a correction
+// solve on the fp32 product may spend half of what is left, so that one which does not converge -- K in fp32 need not be positive
+// definite where K in fp64 barely is -- cannot starve the fp64 loop.  State stays on the device: the loop's reads every
+// KCG_CHECK_EVERY iterations, and one read an outer step (the loop's state together with the |r_t|^2 of the new residual).
+struct MixedOpts { double inner_tol; int max_outer; int64_t* outer_out; int64_t* products_out; int* fell_back_out; };
+
+static int mixed_check(gps_handle_t h, const char* who, const MixedOpts& mx) {
+  if (!(mx.inner_tol > 0.0 && mx.inner_tol < 1.0) || mx.max_outer < 0)
+    return gps_fail(h, GPS_ERR_ARG, std::string(who) + ": inner_tol must be in (0, 1) and max_outer >= 0");
+  return GPS_OK;
+}
+
+// the centred fp32 tables of a plan's points (dKmvmF32: sums | rows | the columns of a rectangular plan) -> plan->Fr32, Fc32
+static int kmvm_f32_tables(gps_handle_t h, KmvmPlan* plan, i64 n, i64 n2) {
+  const i64 rows = gps_kmvm_f32_rows(plan->node);
+  const bool two = plan->Fc != plan->Fr;
+  const size_t fr = (size_t)rows * plan->npr, fc = two ? (size_t)rows * plan->npc : 0;
+  GPS_HIP(h, h->dKmvmF32.ensure(64 * 8 + (fr + fc) * 4));
+  double* sums = h->dKmvmF32.d();
+  float* o1 = (float*)(sums + 64);
+  float* o2 = two ? o1 + fr : nullptr;
+  int rc = gps_launch_kmvm_f32_features(h, plan->node, plan->Fr, n, plan->npr, two ? plan->Fc : nullptr, n2, plan->npc, sums, o1, o2);
+  if (rc) return rc;
+  plan->Fr32 = o1; plan->Fc32 = two ? o2 : o1;
+  return GPS_OK;
+}
+
+// x in *x_dev (dKmxVec).  products (may be NULL): [0] += fp32 products launched, [1] += fp64 ones.  outer / fell_back: per column.
+static int kcg_solve_mixed(gps_handle_t h, const KmvmPlan& plan, i64 n, const KcgBufs& b, const double* B, i64 tp, double noise,
+                           int max_iter, double tol, const MixedOpts& mx, i64 tc, int64_t* iters, double* relres, int* conv,
+                           int64_t* outer_out, int64_t* products, int* fell_back, double** x_dev) {
+  const i64 np = plan.npr;
+  const int tb = (int)(tp / 16);
+  const size_t ve = (size_t)np * tp;
+  GPS_HIP(h, h->dKmxVec.ensure((2 * ve + KCG_MAXT) * 8));
+  double* X = h->dKmxVec.d();
+  double* R = X + ve;
+  double* drr = R + ve;
+  *x_dev = X;
+  KmvmPlan p32 = plan;
+  p32.f32 = 1;
+  KcgState hs;
+  KmxBb bb;
+  double rr[KCG_MAXT], prev[KCG_MAXT];
+  int64_t it_sum[KCG_MAXT] = {0}, outer_n[KCG_MAXT] = {0};
+  unsigned long long done = 0;
+  const unsigned long long all = tc >= 64 ? ~0ull : ((1ull << tc) - 1);
+  int used = 0, outer = 0;
+  bool fallback = mx.max_outer == 0;
+  for (i64 t = 0; t < tc; ++t) { iters[t] = 0; relres[t] = 0.0; conv[t] = 0; if (fell_back) fell_back[t] = 0; }
+  for (;;) {
+    const int budget = fallback ? max_iter - used : (max_iter - used + 1) / 2;      // (half: a stalled correction leaves the fp64 loop its share)
+    int rc = gps_launch_kcg_init(h, b.st, outer == 0 ? B : R, b.r, b.p, b.x, np, tb, fallback ? tol : mx.inner_tol, budget, b.part0);
+    if (rc) return rc;
+    if (fallback && outer > 0) { rc = gps_launch_kmx_setbb(h, b.st, bb); if (rc) return rc; }
+    int launched = 0;
+    bool fresh = false;
+    rc = kcg_loop(h, fallback ? plan : p32, n, b, tp, noise, budget, nullptr, nullptr, &hs, &launched, &fresh);
+    if (rc) return rc;
+    if (products) products[fallback ? 1 : 0] += launched;
+    // the trial x + d in b.p and its fp64 residual in b.r (the loop is over: both are free)
+    rc = gps_launch_kmx_axpy(h, b.p, X, b.x, np, tb, outer == 0);
+    if (rc) return rc;
+    rc = gps_launch_kmvm(h, plan, b.p, tp, tp, noise, b.Ap, tp, nullptr);
+    if (rc) return rc;
+    if (products) products[1] += 1;
+    rc = gps_launch_kmx_resid(h, B, b.Ap, b.r, n, tb, b.part0, drr);
+    if (rc) return rc;
+    GPS_HIP(h, hipMemcpyAsync(rr, drr, sizeof rr, hipMemcpyDeviceToHost, h->stream));
+    if (!fresh) GPS_HIP(h, hipMemcpyAsync(&hs, b.st, sizeof(hs), hipMemcpyDeviceToHost, h->stream));
+    GPS_HIP(h, hipStreamSynchronize(h->stream));
+    const int slot = launched & 1;
+    if (outer == 0)
+      for (int t = 0; t < KCG_MAXT; ++t) { bb.v[t] = hs.bb[t]; prev[t] = hs.bb[t]; }
+    int step_max = 0;
+    bool stall = false;
+    unsigned long long accept = ~all;                          // (the padding columns: zeros either way)
+    for (i64 t = 0; t < tc; ++t)
+      if (!((done >> t) & 1ull)) {
+        it_sum[t] += hs.k[slot][t];
+        if (hs.k[slot][t] > step_max) step_max = hs.k[slot][t];
+        if (bb.v[t] > 0.0) outer_n[t] += 1;
+        if (fallback) {
+          if (fell_back) fell_back[t] = 1;
+          if (hs.rr[slot][t] <= hs.tol2 * bb.v[t]) conv[t] = 1;          // (the fp64 loop's own comparison)
+        }
+        if (!(rr[t] <= 0.25 * prev[t])) stall = true;                    // (not halved, or NaN)
+        if (rr[t] <= prev[t]) { accept |= 1ull << t; prev[t] = rr[t]; }   // (a step that made the column worse is not taken)
+        relres[t] = bb.v[t] > 0.0 ? sqrt(prev[t] / bb.v[t]) : 0.0;
+        if (prev[t] <= tol * tol * bb.v[t]) { done |= 1ull << t; conv[t] = 1; }
+      }
+    used += step_max;
+    outer += 1;
+    rc = gps_launch_kmx_commit(h, X, R, b.p, b.r, B, np, tb, accept, done, outer == 1);
+    if (rc) return rc;
+    if ((done & all) == all || used >= max_iter || (fallback && stall)) break;
+    if (stall || outer >= mx.max_outer) fallback = true;
+  }
+  for (i64 t = 0; t < tc; ++t) { iters[t] = it_sum[t]; if (outer_out) outer_out[t] = outer_n[t]; }
   return GPS_OK;
 }
 
@@ -288,7 +418,7 @@ extern "C" int gps_kernel_precond_solve(gps_handle_t h, const gps_kern_node_t* p
 
 // gps_kmvm, and with sop gps_kmvm_sop: the same buffers, the whole program's features in place of the one primitive's
 static int kmvm_impl(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, const double* X2,
-                     int64_t n2, int64_t d_all, const double* V, int64_t T, double diag_add, double* out, KmvmSop* sop) {
+                     int64_t n2, int64_t d_all, const double* V, int64_t T, double diag_add, double* out, KmvmSop* sop, bool f32 = false) {
   const std::string bad = std::string(who) + ": bad argument";
   if (!h || n < 0 || n2 < 0 || T < 0 || d_all <= 0) return gps_fail(h, GPS_ERR_ARG, bad);
   int rc = kmvm_begin(h, who, prog, n_nodes, sop != nullptr);
@@ -308,6 +438,11 @@ static int kmvm_impl(gps_handle_t h, const char* who, const gps_kern_node_t* pro
     rc = kmvm_features(h, prog, n_nodes, h->dXnew.d(), n2, d_all, plan.npc, h->dGxTab, &plan.node, sop);
     if (rc) return rc;
     plan.Fc = h->dGxTab.d();
+  }
+  if (f32) {                                                 // gps_kmvm_f32: both point sets centred by their common mean
+    rc = kmvm_f32_tables(h, &plan, n, n2);
+    if (rc) return rc;
+    plan.f32 = 1;
   }
   const i64 tp = kmvm_tpad(T);
   GPS_HIP(h, h->dStage.ensure((size_t)(n2 > n ? n2 : n) * T * 8));
@@ -330,6 +465,11 @@ extern "C" int gps_kmvm(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes
   return kmvm_impl(h, "gps_kmvm", prog, n_nodes, X, n, X2, n2, d_all, V, T, diag_add, out, nullptr);
 }
 
+extern "C" int gps_kmvm_f32(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, const double* X2,
+                            int64_t n2, int64_t d_all, const double* V, int64_t T, double diag_add, double* out) {
+  return kmvm_impl(h, "gps_kmvm_f32", prog, n_nodes, X, n, X2, n2, d_all, V, T, diag_add, out, nullptr, true);
+}
+
 extern "C" int gps_kmvm_sop(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, const double* X2,
                             int64_t n2, int64_t d_all, const double* V, int64_t T, double diag_add, double* out) {
   KmvmSop sop;
@@ -349,9 +489,12 @@ struct PcgOpts {
 static int kernel_cg_impl(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n,
                           int64_t d_all, double noise_var, const double* B, int64_t T, int max_iter, double tol, double* x_out,
                           int64_t* iters_out, double* relres_out, int* converged_out, double* coef_out, const PcgOpts* pc = nullptr,
-                          KmvmSop* sop = nullptr) {
+                          KmvmSop* sop = nullptr, const MixedOpts* mx = nullptr) {
   const std::string bad = std::string(who) + ": bad argument";
   if (!h || n < 0 || T < 0 || d_all <= 0 || max_iter < 0 || !(tol >= 0.0) || !(noise_var >= 0.0)) return gps_fail(h, GPS_ERR_ARG, bad);
+  if (mx) {
+    if (int rf = mixed_check(h, who, *mx)) return rf;
+  }
   if (pc) {
     if (int rf = pchol_check(h, who, pc->rank_max, pc->rel_tol, noise_var)) return rf;
     if (pc->n_probe < 0 || pc->n_probe > T || (pc->n_probe > 0 && (pc->rank_max == 0 || !pc->Z_out || !pc->MinvZ_out || !pc->zmz_out)))
@@ -362,8 +505,10 @@ static int kernel_cg_impl(gps_handle_t h, const char* who, const gps_kern_node_t
   if (rc) return rc;
   if (pc && pc->logdet_out) *pc->logdet_out = 0.0;
   if (pc && pc->rank_out) *pc->rank_out = 0;
+  if (mx && mx->products_out) { mx->products_out[0] = 0; mx->products_out[1] = 0; }
   if (n == 0 || T == 0) return GPS_OK;
   if (!X || !B || !x_out || !iters_out || !relres_out || !converged_out) return gps_fail(h, GPS_ERR_ARG, bad);
+  if (mx && (!mx->outer_out || !mx->products_out || !mx->fell_back_out)) return gps_fail(h, GPS_ERR_ARG, bad);
   std::vector<double> hz;
   if (coef_out) {
     memset(coef_out, 0, (size_t)max_iter * 2 * T * 8);
@@ -373,6 +518,10 @@ static int kernel_cg_impl(gps_handle_t h, const char* who, const gps_kern_node_t
   rc = kmvm_sym_plan(h, prog, n_nodes, X, n, d_all, &plan, sop);
   if (rc) return rc;
   const i64 np = plan.npr;
+  if (mx) {
+    rc = kmvm_f32_tables(h, &plan, n, 0);
+    if (rc) return rc;
+  }
   GPS_HIP(h, h->dStage.ensure((size_t)n * T * 8));
   GPS_HIP(h, hipMemcpyAsync(h->dStage.p, B, (size_t)n * T * 8, hipMemcpyHostToDevice, h->stream));
   PcholPre pre;
@@ -433,6 +582,11 @@ static int kernel_cg_impl(gps_handle_t h, const char* who, const gps_kern_node_t
       }
     }
     int launched = 0;
+    double* xd = b.x;
+    if (mx)
+      rc = kcg_solve_mixed(h, plan, n, b, h->dG1.d(), tp, noise_var, max_iter, tol, *mx, tc, iters_out + c0, relres_out + c0,
+                           converged_out + c0, mx->outer_out + c0, mx->products_out, mx->fell_back_out + c0, &xd);
+    else
     rc = kcg_solve(h, plan, n, b, h->dG1.d(), tp, noise_var, max_iter, tol, tc, iters_out + c0, relres_out + c0, converged_out + c0,
                    coef_out ? h->dLanczos.d() : nullptr, &launched, pc ? &pre : nullptr);
     if (rc) return rc;
@@ -445,7 +599,7 @@ static int kernel_cg_impl(gps_handle_t h, const char* who, const gps_kern_node_t
           for (int ab = 0; ab < 2; ++ab) coef_out[((size_t)k * 2 + ab) * T + c0 + t] = hz[((size_t)k * 2 + ab) * KCG_MAXT + t];
     }
     // (the batch's columns of B have been consumed: its solution takes their place in the staging area)
-    rc = gps_launch_extract(h, b.x, tp, n, tc, h->dStage.d() + c0, T, 0);
+    rc = gps_launch_extract(h, xd, tp, n, tc, h->dStage.d() + c0, T, 0);
     if (rc) return rc;
   }
   GPS_HIP(h, hipMemcpyAsync(x_out, h->dStage.p, (size_t)n * T * 8, hipMemcpyDeviceToHost, h->stream));
@@ -471,6 +625,18 @@ extern "C" int gps_kernel_cg_lanczos(gps_handle_t h, const gps_kern_node_t* prog
   if (!coef_out && max_iter > 0 && T > 0) return gps_fail(h, GPS_ERR_ARG, "gps_kernel_cg_lanczos: bad argument");
   return kernel_cg_impl(h, "gps_kernel_cg_lanczos", prog, n_nodes, X, n, d_all, noise_var, B, T, max_iter, tol, x_out, iters_out,
                         relres_out, converged_out, coef_out);
+}
+
+// the mixed-precision solve (kcg_solve_mixed): gps_kernel_cg's arguments and outputs, iters_out the inner iterations summed over the
+// outer steps; outer_out [T] the outer steps a column was live in, products_out [2] the fp32 and fp64 products launched,
+// fell_back_out [T] 1 where the fp64 loop finished the column
+extern "C" int gps_kernel_cg_mixed(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                                   double noise_var, const double* B, int64_t T, int max_iter, double tol, double* x_out,
+                                   int64_t* iters_out, double* relres_out, int* converged_out, double inner_tol, int max_outer,
+                                   int64_t* outer_out, int64_t* products_out, int* fell_back_out) {
+  const MixedOpts mx = {inner_tol, max_outer, outer_out, products_out, fell_back_out};
+  return kernel_cg_impl(h, "gps_kernel_cg_mixed", prog, n_nodes, X, n, d_all, noise_var, B, T, max_iter, tol, x_out, iters_out,
+                        relres_out, converged_out, nullptr, nullptr, nullptr, &mx);
 }
 
 // the plain loop on a sum-of-products program; coef_out: NULL, or gps_kernel_cg_lanczos' coefficients -- one entry for both calls
@@ -549,13 +715,24 @@ extern "C" int gps_kmvm_grad(gps_handle_t h, const gps_kern_node_t* prog, int n_
 // there is a rank, and the mean -- alpha = (K + s I)^-1 resid batch by batch, each pushed through K(Xnew, X) at once -- on its way
 // to mean_out.  done: n_new == 0, nothing left to do.
 struct PredictCtx { double kdiag; KmvmPlan plan, cross; i64 np, nsp; PcholPre pre; const PcholPre* pp; bool done; };
+// one solve of the prediction: the plain or preconditioned loop, or with mx the mixed-precision one; x in *xd
+static int predict_solve(gps_handle_t h, const KmvmPlan& plan, i64 n, const KcgBufs& b, const double* B, i64 tp, double noise, int max_iter,
+                         double tol, i64 tc, int64_t* iters, double* relres, int* conv, const PcholPre* pp, const MixedOpts* mx, double** xd) {
+  *xd = b.x;
+  if (mx) return kcg_solve_mixed(h, plan, n, b, B, tp, noise, max_iter, tol, *mx, tc, iters, relres, conv, nullptr, nullptr, nullptr, xd);
+  return kcg_solve(h, plan, n, b, B, tp, noise, max_iter, tol, tc, iters, relres, conv, nullptr, nullptr, pp);
+}
 static int kernel_predict_mean(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n,
                                int64_t d_all, double noise_var, const double* resid, int64_t r, const double* Xnew, int64_t n_new,
                                int max_iter, double tol, int rank_max, double rel_tol, double* mean_out, double* var_out,
-                               int64_t* iters_out, double* relres_out, int* converged_out, KmvmSop* sop, PredictCtx* c) {
+                               int64_t* iters_out, double* relres_out, int* converged_out, KmvmSop* sop, PredictCtx* c,
+                               const MixedOpts* mx = nullptr) {
   const std::string bad = std::string(who) + ": bad argument";
   if (!h || n <= 0 || r <= 0 || n_new < 0 || d_all <= 0 || max_iter < 0 || !(tol >= 0.0) || !(noise_var >= 0.0))
     return gps_fail(h, GPS_ERR_ARG, bad);
+  if (mx) {
+    if (int rf = mixed_check(h, who, *mx)) return rf;
+  }
   if (int rf = pchol_check(h, who, rank_max, rel_tol, noise_var)) return rf;
   int rc = kmvm_begin(h, who, prog, n_nodes, sop != nullptr);
   if (rc) return rc;
@@ -571,6 +748,10 @@ static int kernel_predict_mean(gps_handle_t h, const char* who, const gps_kern_n
   if (rc) return rc;
   const i64 np = plan.npr, nsp = pad64(n_new);
   c->np = np; c->nsp = nsp;
+  if (mx) {                                                  // (the cross product of the mean below stays fp64: cross.f32 = 0)
+    rc = kmvm_f32_tables(h, &plan, n, 0);
+    if (rc) return rc;
+  }
   PcholPre& pre = c->pre;
   const PcholPre*& pp = c->pp;
   pp = nullptr;
@@ -599,10 +780,11 @@ static int kernel_predict_mean(gps_handle_t h, const char* who, const gps_kern_n
     GPS_HIP(h, h->dG3.ensure((size_t)nsp * tp * 8));
     rc = kmvm_pad_cols(h, h->dStage.d(), r, n, c0, tc, h->dG1.d(), np, tp);
     if (rc) return rc;
-    rc = kcg_solve(h, plan, n, b, h->dG1.d(), tp, noise_var, max_iter, tol, tc, iters_out + c0, relres_out + c0, converged_out + c0,
-                   nullptr, nullptr, pp);
+    double* xd = nullptr;
+    rc = predict_solve(h, plan, n, b, h->dG1.d(), tp, noise_var, max_iter, tol, tc, iters_out + c0, relres_out + c0, converged_out + c0,
+                       pp, mx, &xd);
     if (rc) return rc;
-    rc = gps_launch_kmvm(h, cross, b.x, tp, tp, 0.0, h->dG3.d(), tp, nullptr);
+    rc = gps_launch_kmvm(h, cross, xd, tp, tp, 0.0, h->dG3.d(), tp, nullptr);
     if (rc) return rc;
     rc = gps_launch_extract(h, h->dG3.d(), tp, n_new, tc, h->dMean.d() + c0, r, 0);
     if (rc) return rc;
@@ -615,10 +797,11 @@ static int kernel_predict_mean(gps_handle_t h, const char* who, const gps_kern_n
 static int kernel_predict_impl(gps_handle_t h, const char* who, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n,
                                int64_t d_all, double noise_var, const double* resid, int64_t r, const double* Xnew, int64_t n_new,
                                int max_iter, double tol, int rank_max, double rel_tol, double* mean_out, double* var_out,
-                               int64_t* iters_out, double* relres_out, int* converged_out, KmvmSop* sop = nullptr) {
+                               int64_t* iters_out, double* relres_out, int* converged_out, KmvmSop* sop = nullptr,
+                               const MixedOpts* mx = nullptr) {
   PredictCtx ctx;
   int rc = kernel_predict_mean(h, who, prog, n_nodes, X, n, d_all, noise_var, resid, r, Xnew, n_new, max_iter, tol, rank_max, rel_tol,
-                               mean_out, var_out, iters_out, relres_out, converged_out, sop, &ctx);
+                               mean_out, var_out, iters_out, relres_out, converged_out, sop, &ctx, mx);
   if (rc || ctx.done) return rc;
   const KmvmPlan& plan = ctx.plan;
   const i64 np = ctx.np;
@@ -638,10 +821,11 @@ static int kernel_predict_impl(gps_handle_t h, const char* who, const gps_kern_n
     if (rc) return rc;
     rc = gps_launch_transpose(h, h->dTmp.d(), np, 16, np, h->dG2.d(), 16);        // rows nb .. 15 and columns n .. np - 1: zeros
     if (rc) return rc;
-    rc = kcg_solve(h, plan, n, b, h->dG2.d(), 16, noise_var, max_iter, tol, nb, iters_out + r + j0, relres_out + r + j0, converged_out + r + j0,
-                   nullptr, nullptr, pp);
+    double* xd = nullptr;
+    rc = predict_solve(h, plan, n, b, h->dG2.d(), 16, noise_var, max_iter, tol, nb, iters_out + r + j0, relres_out + r + j0,
+                       converged_out + r + j0, pp, mx, &xd);
     if (rc) return rc;
-    rc = gps_launch_kcg_coldot(h, nullptr, 0, h->dG2.d(), b.x, np, 1, b.part0);
+    rc = gps_launch_kcg_coldot(h, nullptr, 0, h->dG2.d(), xd, np, 1, b.part0);
     if (rc) return rc;
     GPS_HIP(h, hipMemcpyAsync(hp.data(), b.part0, hp.size() * 8, hipMemcpyDeviceToHost, h->stream));
     GPS_HIP(h, hipStreamSynchronize(h->stream));
@@ -660,6 +844,16 @@ extern "C" int gps_kernel_predict(gps_handle_t h, const gps_kern_node_t* prog, i
                                   double tol, double* mean_out, double* var_out, int64_t* iters_out, double* relres_out, int* converged_out) {
   return kernel_predict_impl(h, "gps_kernel_predict", prog, n_nodes, X, n, d_all, noise_var, resid, r, Xnew, n_new, max_iter, tol, 0, 0.0,
                              mean_out, var_out, iters_out, relres_out, converged_out);
+}
+
+// gps_kernel_predict with the mean's solve and the variance's solves through the mixed-precision loop
+extern "C" int gps_kernel_predict_mixed(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                                        double noise_var, const double* resid, int64_t r, const double* Xnew, int64_t n_new, int max_iter,
+                                        double tol, double* mean_out, double* var_out, int64_t* iters_out, double* relres_out,
+                                        int* converged_out, double inner_tol, int max_outer) {
+  const MixedOpts mx = {inner_tol, max_outer, nullptr, nullptr, nullptr};
+  return kernel_predict_impl(h, "gps_kernel_predict_mixed", prog, n_nodes, X, n, d_all, noise_var, resid, r, Xnew, n_new, max_iter, tol, 0,
+                             0.0, mean_out, var_out, iters_out, relres_out, converged_out, nullptr, &mx);
 }
 
 extern "C" int gps_kernel_predict_pcg(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,

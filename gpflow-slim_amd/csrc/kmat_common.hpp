@@ -219,7 +219,10 @@ int gps_kmvm_features(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, 
 // sop: NULL, or the sum-of-products program of kmvm_sop.hip -- the product then evaluates the whole program per block and `node` is
 // not read; Fr / Fc are run_prep's table of the whole program.
 struct KmvmSop;
-struct KmvmPlan { KNodeDev node; const double* Fr; const double* Fc; i64 npr, npc; int sym; const KmvmSop* sop = nullptr; };
+// f32: the product runs kmvm_f32.hip's kernel on Fr32 / Fc32, the centred fp32 tables of the same points (gps_launch_kmvm_f32_features;
+// a lone primitive only); V, out, the chunks and the folds are the fp64 product's.
+struct KmvmPlan { KNodeDev node; const double* Fr; const double* Fc; i64 npr, npc; int sym; const KmvmSop* sop = nullptr;
+                  int f32 = 0; const float* Fr32 = nullptr; const float* Fc32 = nullptr; };
 int gps_kmvm_chunks(i64 row_tiles, i64 col_tiles, int forced);
 // kmvm_sop.hip : K = sum_terms prod_factors p.  prog holds the primitives alone, in program order (n_nodes = n_prims; f0, nf and
 // norm_row index run_prep's table of the whole program); lay how they are staged: primitive q's feature rows from row s0[q] of the
@@ -237,6 +240,12 @@ int gps_kmvm_sop_features(gps_handle_t h, const gps_kern_node_t* prog, int n_nod
                           DevBuf& feat, KmvmSop* sop);
 // one pass of gps_launch_kmvm on a plan with sop: tb blocks of V, chunk c of `chunks` writes out + c part_stride
 int gps_launch_kmvm_sop_pass(gps_handle_t h, const KmvmPlan& p, const double* V, i64 ldv, int tb, double* out, i64 ldo, i64 part_stride,
+                             int tiles, int chunks, double diag_add, const int* skip);
+// kmvm_f32.hip : the fp32 tables (rows x npad floats each; sums: device [64] doubles) and one pass of gps_launch_kmvm on a plan with f32
+i64 gps_kmvm_f32_rows(const KNodeDev& node);
+int gps_launch_kmvm_f32_features(gps_handle_t h, const KNodeDev& node, const double* F, i64 n, i64 npad, const double* F2, i64 n2,
+                                 i64 npad2, double* sums, float* out, float* out2);
+int gps_launch_kmvm_f32_pass(gps_handle_t h, const KmvmPlan& p, const double* V, i64 ldv, int tb, double* out, i64 ldo, i64 part_stride,
                              int tiles, int chunks, double diag_add, const int* skip);
 // V [npc][ldv], out [npr][ldo], tpad columns (16, or a multiple of 64: passes of 64); skip: optional device flag, non-zero =
 // the kernel returns at once.  Partials of a chunked walk go through h->dKmvmPart.
@@ -261,6 +270,18 @@ int gps_launch_kcg_dir(gps_handle_t h, KcgState* st, int it, const double* part_
 // rzs[0] alone.
 int gps_launch_pcg_dir(gps_handle_t h, KcgState* st, int it, const double* part_rr, const double* part_rz, int nblk_rz, const double* z,
                        double* p, i64 rows, int tb, double* lz, double* rzs);
+// The outer step of the mixed-precision solve (kmvm.hip: kmx_* kernels), all fp64, vectors [*, 16 tb] as above:
+//   _axpy   the trial solution out = d (first) or X + d
+//   _resid  R = B - AX over the real rows, and rr[t] = |R_t|^2 (device [KCG_MAXT]; part: gps_kcg_blocks rows of 64)
+//   _commit per column t: bit t of `accept` -- X = Xt, R = Rt ; else they stay (first: X = 0, R = B) ; bit t of `done` -- R = 0 (a
+//           finished column: the next correction solve skips it)
+//   _setbb  st->bb[t] = bb.v[t]: the stop rule of a correction solve A d = r measured against |b|, not |r|
+struct KmxBb { double v[KCG_MAXT]; };
+int gps_launch_kmx_axpy(gps_handle_t h, double* out, const double* X, const double* d, i64 rows, int tb, int first);
+int gps_launch_kmx_resid(gps_handle_t h, const double* B, const double* AX, double* R, i64 rows, int tb, double* part, double* rr);
+int gps_launch_kmx_commit(gps_handle_t h, double* X, double* R, const double* Xt, const double* Rt, const double* B, i64 rows, int tb,
+                          unsigned long long accept, unsigned long long done, int first);
+int gps_launch_kmx_setbb(gps_handle_t h, KcgState* st, const KmxBb& bb);
 
 // pchol.hip : the pivoted-Cholesky preconditioner M = L L^T + noise I of the loop above (see there).  One workspace `ws` (doubles,
 // gps_pchol_workspace fills the offsets) beside L [np][kp].

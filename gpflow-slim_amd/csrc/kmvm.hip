@@ -193,6 +193,8 @@ int gps_launch_kmvm(gps_handle_t h, const KmvmPlan& p, const double* V, i64 ldv,
       int rc = 0;
       // p.sop: the whole program per block (kmvm_sop.hip) on the same geometry; NULL: the one primitive, as ever
       if (p.sop) rc = gps_launch_kmvm_sop_pass(h, p, a.V, a.ldv, a.tb, a.out, a.ldo, a.part_stride, a.tiles, a.chunks, a.diag_add, a.skip);
+      // p.f32: the fp32 kernel (kmvm_f32.hip) on the centred fp32 tables, the same geometry, partials and folds
+      else if (p.f32) rc = gps_launch_kmvm_f32_pass(h, p, a.V, a.ldv, a.tb, a.out, a.ldo, a.part_stride, a.tiles, a.chunks, a.diag_add, a.skip);
       else
       // (the ops of gps_kmvm_in_scope; the switch is kmat.hip's with_stationary_op<true>, spelt out: that one is static there)
       switch (p.node.op) {
@@ -742,6 +744,69 @@ __global__ __launch_bounds__(256) void pcg_dir_kernel(KcgState* __restrict__ st,
   }
 }
 
+// ---- the outer step of the mixed-precision solve (gps_kmvm.hip: kcg_solve_mixed) -------------------------------------------------
+// x is refined by corrections: A d = r solved by the loop above on the fp32 product, then the trial x + d, its residual b - A (x + d)
+// with the fp64 product, and the host's verdict per column.  These are the vector kernels between the two, in the layout and with
+// the reductions of the kcg_* kernels.
+// the trial solution: out = d (first) or X + d
+__global__ __launch_bounds__(256) void kmx_axpy_kernel(double* __restrict__ out, const double* __restrict__ X, const double* __restrict__ d,
+                                                       i64 rows, int tb, int first) {
+  const int c = threadIdx.x & 15, rl = threadIdx.x >> 4;
+  const i64 ld = 16 * tb;
+  for (i64 row = (i64)blockIdx.x * 16 + rl; row < rows; row += (i64)gridDim.x * 16)
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+      if (b < tb) { const i64 e = row * ld + 16 * b + c; out[e] = first ? d[e] : X[e] + d[e]; }
+}
+
+// R = B - AX ; partials of r_t^T r_t
+__global__ __launch_bounds__(256) void kmx_resid_kernel(const double* __restrict__ B, const double* __restrict__ AX, double* __restrict__ R,
+                                                        i64 rows, int tb, double* __restrict__ part) {
+  __shared__ double sh[256];
+  const int c = threadIdx.x & 15, rl = threadIdx.x >> 4;
+  const i64 ld = 16 * tb;
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  for (i64 row = (i64)blockIdx.x * 16 + rl; row < rows; row += (i64)gridDim.x * 16)
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+      if (b < tb) {
+        const i64 e = row * ld + 16 * b + c;
+        const double v = B[e] - AX[e];
+        R[e] = v;
+        s[b] = fma(v, v, s[b]);
+      }
+  kcg_block_colsum(s, sh, part + (i64)blockIdx.x * 64);
+}
+
+// one workgroup: rr[t] = the partials' sum in kcg_fold's order
+__global__ __launch_bounds__(256) void kmx_fold_kernel(const double* __restrict__ part, int nblk, double* __restrict__ rr) {
+  __shared__ double sh[256];
+  __shared__ double tot[64];
+  kcg_fold(part, nblk, sh, tot);
+  if (threadIdx.x < 64) rr[threadIdx.x] = tot[threadIdx.x];
+}
+
+// the step's verdict, column by column: accepted -- x = the trial, r = its residual ; not accepted -- x and r stay (first: x = 0,
+// r = b) ; done -- r = 0, so that the next correction solve skips the column (x as accepted)
+__global__ __launch_bounds__(256) void kmx_commit_kernel(double* __restrict__ X, double* __restrict__ R, const double* __restrict__ Xt,
+                                                         const double* __restrict__ Rt, const double* __restrict__ B, i64 rows, int tb,
+                                                         unsigned long long accept, unsigned long long done, int first) {
+  const int c = threadIdx.x & 15, rl = threadIdx.x >> 4;
+  const i64 ld = 16 * tb;
+  for (i64 row = (i64)blockIdx.x * 16 + rl; row < rows; row += (i64)gridDim.x * 16)
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+      if (b < tb) {
+        const i64 e = row * ld + 16 * b + c;
+        const int t = 16 * b + c;
+        if ((accept >> t) & 1ull) { X[e] = Xt[e]; R[e] = Rt[e]; }
+        else if (first) { X[e] = 0.0; R[e] = B[e]; }
+        if ((done >> t) & 1ull) R[e] = 0.0;
+      }
+}
+
+__global__ __launch_bounds__(64) void kmx_setbb_kernel(KcgState* __restrict__ st, KmxBb bb) { st->bb[threadIdx.x] = bb.v[threadIdx.x]; }
+
 // ---- launchers -------------------------------------------------------------------------------------------------------------------
 int gps_kcg_blocks(i64 npad) {
   const i64 b = (npad + 15) / 16;
@@ -791,5 +856,32 @@ int gps_launch_kcg_dir(gps_handle_t h, KcgState* st, int it, const double* part_
   const int nblk = gps_kcg_blocks(rows);
   const double el = (double)rows * 16.0 * tb;
   KCG_LAUNCH(kcg_dir_kernel, nblk, 2.0 * el, 24.0 * el, st, it, part_rr, nblk, r, p, rows, tb, lz);
+  return GPS_OK;
+}
+
+int gps_launch_kmx_axpy(gps_handle_t h, double* out, const double* X, const double* d, i64 rows, int tb, int first) {
+  const double el = (double)rows * 16.0 * tb;
+  KCG_LAUNCH(kmx_axpy_kernel, gps_kcg_blocks(rows), el, 24.0 * el, out, X, d, rows, tb, first);
+  return GPS_OK;
+}
+
+int gps_launch_kmx_resid(gps_handle_t h, const double* B, const double* AX, double* R, i64 rows, int tb, double* part, double* rr) {
+  const int nblk = gps_kcg_blocks(rows);
+  const double el = (double)rows * 16.0 * tb;
+  KCG_LAUNCH(kmx_resid_kernel, nblk, 3.0 * el, 24.0 * el, B, AX, R, rows, tb, part);
+  KCG_LAUNCH(kmx_fold_kernel, 1, 64.0 * nblk, 512.0 * nblk, (const double*)part, nblk, rr);
+  return GPS_OK;
+}
+
+int gps_launch_kmx_commit(gps_handle_t h, double* X, double* R, const double* Xt, const double* Rt, const double* B, i64 rows, int tb,
+                          unsigned long long accept, unsigned long long done, int first) {
+  KCG_LAUNCH(kmx_commit_kernel, gps_kcg_blocks(rows), 0.0, 40.0 * (double)rows * 16.0 * tb, X, R, Xt, Rt, B, rows, tb, accept, done, first);
+  return GPS_OK;
+}
+
+int gps_launch_kmx_setbb(gps_handle_t h, KcgState* st, const KmxBb& bb) {
+  LaunchScope ls(h, KC_OTHER, 0.0, 512.0);
+  hipLaunchKernelGGL(kmx_setbb_kernel, dim3(1), dim3(64), 0, h->stream, st, bb);
+  GPS_HIP(h, hipGetLastError());
   return GPS_OK;
 }

@@ -298,6 +298,11 @@ _SIGNATURES = {
     "gps_kmvm_sop": [_vp, _prog, _int, _dp, _i64, _dp, _i64, _i64, _dp, _i64, _dbl, _dp],
     "gps_kernel_cg_sop": [_vp, _prog, _int, _dp, _i64, _i64, _dbl, _dp, _i64, _int, _dbl, _dp, _i64p, _dp, _ip, _dp],
     "gps_kernel_predict_sop": [_vp, _prog, _int, _dp, _i64, _i64, _dbl, _dp, _i64, _dp, _i64, _int, _dbl, _dp, _dp, _i64p, _dp, _ip],
+    "gps_kmvm_f32": [_vp, _prog, _int, _dp, _i64, _dp, _i64, _i64, _dp, _i64, _dbl, _dp],
+    "gps_kernel_cg_mixed": [_vp, _prog, _int, _dp, _i64, _i64, _dbl, _dp, _i64, _int, _dbl, _dp, _i64p, _dp, _ip, _dbl, _int, _i64p,
+                            _i64p, _ip],
+    "gps_kernel_predict_mixed": [_vp, _prog, _int, _dp, _i64, _i64, _dbl, _dp, _i64, _dp, _i64, _int, _dbl, _dp, _dp, _i64p, _dp, _ip,
+                                 _dbl, _int],
     "gps_kernel_lanczos": [_vp, _prog, _int, _dp, _i64, _i64, _dbl, _dp, _int, _dbl, _dp, _dp, _dp, _i64p],
     "gps_kernel_predict_lanczos": [_vp, _prog, _int, _dp, _i64, _i64, _dbl, _dp, _i64, _dp, _i64, _int, _int, _dbl, _dp, _dp, _i64p, _dp,
                                    _ip, _i64p],

@@ -1371,6 +1371,61 @@ def kernel_predict(h, prog, X, noise_var, resid, Xnew, max_iter=1000, tol=1e-8, 
     return mean, var, iters, rel, conv != 0
 
 
+# ---- mixed precision on the same path (csrc/kmvm_f32.hip): one primitive only; module functions like the ones above
+PRECISIONS = {"kernel_matmul": ("fp64", "fp32"), "solve": ("fp64", "mixed")}
+
+
+def _check_precision(who, precision, kind, **off):
+    """The refusals of every call that takes a precision, before anything touches the device: a string outside the call's two, and
+    any other precision than 'fp64' together with an option (name = value of ``off``) that is set."""
+    if precision not in PRECISIONS[kind]:
+        raise ValueError("%s: precision must be %s, got %r" % (who, " or ".join(repr(p) for p in PRECISIONS[kind]), precision))
+    if precision != "fp64":
+        for name, val in off.items():
+            if val:
+                raise ValueError("%s: precision=%r is not available together with %s (= %r); the mixed-precision path has no "
+                                 "Lanczos coefficients, no preconditioner and no training" % (who, precision, name, val))
+
+
+def kmvm_f32(h, prog, X, V, X2=None, diag_add=0.0):
+    """gps_kmvm_f32: ``kmvm`` with K and the product in fp32, each 64-column tile's share added in fp64."""
+    return kmvm(h, prog, X, V, X2=X2, diag_add=diag_add, entry="gps_kmvm_f32")
+
+
+def kernel_cg_mixed(h, prog, X, B, noise_var, max_iter=1000, tol=1e-8, inner_tol=1e-4, max_outer=20):
+    """gps_kernel_cg_mixed: kernel_cg's four results -- iterations summed over the outer steps, |r| / |b| of the fp64 residual --,
+    then (outer steps [T], fp32 products, fp64 products, fell-back flags [T])."""
+    X, B = _f64(X), _f64(B)
+    _need(X.ndim == 2 and B.ndim == 2 and B.shape[0] == X.shape[0], "X must be [N, D] and B [N, T]")
+    _need(0.0 < inner_tol < 1.0 and int(max_outer) >= 0, "inner_tol must be in (0, 1) and max_outer >= 0")
+    n, T = B.shape
+    x, iters, rel, conv = np.zeros((n, T)), np.zeros(T, dtype=np.int64), np.zeros(T), np.zeros(T, dtype=np.intc)
+    outer, prods, fell = np.zeros(T, dtype=np.int64), np.zeros(2, dtype=np.int64), np.zeros(T, dtype=np.intc)
+    i64p = ctypes.POINTER(_i64)
+    h._drop_resident()
+    h._call("gps_kernel_cg_mixed", prog, len(prog), _ptr(X), n, X.shape[1], float(noise_var), _ptr(B), T, int(max_iter), float(tol),
+            _ptr(x), iters.ctypes.data_as(i64p), _ptr(rel), conv.ctypes.data_as(_c_int_p), float(inner_tol), int(max_outer),
+            outer.ctypes.data_as(i64p), prods.ctypes.data_as(i64p), fell.ctypes.data_as(_c_int_p))
+    return x, iters, rel, conv != 0, outer, int(prods[0]), int(prods[1]), fell != 0
+
+
+def kernel_predict_mixed(h, prog, X, noise_var, resid, Xnew, max_iter=1000, tol=1e-8, inner_tol=1e-4, max_outer=20):
+    """gps_kernel_predict_mixed: ``kernel_predict``'s results, every solve through the mixed-precision loop."""
+    X, resid, Xnew = _f64(X), _f64(resid), _f64(Xnew)
+    _need(X.ndim == 2 and resid.ndim == 2 and resid.shape[0] == X.shape[0] and X.shape[0] > 0 and resid.shape[1] > 0,
+          "X must be [N, D] and the residual [N, R]")
+    _need(Xnew.ndim == 2 and Xnew.shape[1] == X.shape[1], "Xnew must be [N*, %d]" % X.shape[1])
+    _need(0.0 < inner_tol < 1.0 and int(max_outer) >= 0, "inner_tol must be in (0, 1) and max_outer >= 0")
+    n, r, n_new = X.shape[0], resid.shape[1], Xnew.shape[0]
+    mean, var = np.zeros((n_new, r)), np.zeros(n_new)
+    iters, rel, conv = np.zeros(r + n_new, dtype=np.int64), np.zeros(r + n_new), np.zeros(r + n_new, dtype=np.intc)
+    h._drop_resident()
+    h._call("gps_kernel_predict_mixed", prog, len(prog), _ptr(X), n, X.shape[1], float(noise_var), _ptr(resid), r, _ptr(Xnew), n_new,
+            int(max_iter), float(tol), _ptr(mean), _ptr(var), iters.ctypes.data_as(ctypes.POINTER(_i64)), _ptr(rel),
+            conv.ctypes.data_as(_c_int_p), float(inner_tol), int(max_outer))
+    return mean, var, iters, rel, conv != 0
+
+
 # ---- the pivoted-Cholesky preconditioner of the matrix-free path (csrc/pchol.hip) -------------------------------------------------------
 # Module functions like the ones above: the preconditioner is rebuilt inside every call and nothing stays resident.
 def _check_precond(rank, rel_tol, noise_var=None):

@@ -106,11 +106,24 @@ def _is_sop(prog):
     return len(prog) > 1
 
 
-def kernel_matmul(kern, X, V, X2=None, diag_add=0.0):
-    """K(X, X2) V [n, T], or (K(X, X) + diag_add I) V without an X2; memory O(n (D + T))."""
+def _precision_program(who, kern, d_all, precision):
+    """_matrix_free_program for a call that takes a precision: anything but 'fp64' knows one primitive (csrc/kmvm_f32.hip)"""
+    composite = None if precision == "fp64" else ("%s(precision=%r)" % (who, precision), "served in fp64 only: the fp32 product "
+                                                  "knows one primitive")
+    return _matrix_free_program(kern, d_all, composite=composite)
+
+
+def kernel_matmul(kern, X, V, X2=None, diag_add=0.0, precision="fp64"):
+    """K(X, X2) V [n, T], or (K(X, X) + diag_add I) V without an X2; memory O(n (D + T)).  precision="fp32" (one stationary kernel
+    only): dot products, the kernel's formula and the product with V on the fp32 pipes, the feature rows centred in fp64 first and
+    every 64-column tile's share added in fp64 -- fp32-grade entries, about 1e-7 of sum_p |K_ip| |V_pt| whatever n; what the inner
+    loop of kernel_cgsolver(precision="mixed") runs."""
+    be._check_precision("kernel_matmul", precision, "kernel_matmul")
     X = np.ascontiguousarray(X, dtype=settings.float_type)
-    prog = _matrix_free_program(kern, X.shape[1])
+    prog = _precision_program("kernel_matmul", kern, X.shape[1], precision)
     kern._check_inputs(*([X] if X2 is None else [X, X2]))
+    if precision == "fp32":
+        return be.kmvm_f32(be.get_handle(), prog, X, V, X2=X2, diag_add=diag_add)
     return (be.kmvm_sop if _is_sop(prog) else be.kmvm)(be.get_handle(), prog, X, V, X2=X2, diag_add=diag_add)
 
 
@@ -168,7 +181,8 @@ def _probe_normals(seed, rank, n, num_probes):
     return rng.standard_normal((int(rank), int(num_probes))), rng.standard_normal((n, int(num_probes)))
 
 
-def kernel_cgsolver(kern, X, B, noise_var, max_iter=1000, tol=1e-8, lanczos=False, precond_rank=0, precond_rel_tol=1e-10):
+def kernel_cgsolver(kern, X, B, noise_var, max_iter=1000, tol=1e-8, lanczos=False, precond_rank=0, precond_rel_tol=1e-10,
+                    precision="fp64", inner_tol=1e-4, max_outer=20):
     """(K(X, X) + noise_var I) x = B by plain conjugate gradients from x = 0, the T columns of B at once.  A column stops when
     |r| <= tol |b| -- the unsquared norms; ``cgsolver`` above keeps the reference's rule, tol |b| against r^T r.  Returns
     (x [n, T], info) with info['iterations'] [T], info['relative_residual'] [T] (of the recurrence) and info['converged'] [T];
@@ -177,13 +191,25 @@ def kernel_cgsolver(kern, X, B, noise_var, max_iter=1000, tol=1e-8, lanczos=Fals
     precond_rank (0 .. 128; 0: the plain loop, byte for byte): the loop preconditioned by M = L L^T + noise_var I, L the pivoted
     partial Cholesky factor of that rank at most (kernel_pivoted_cholesky; rebuilt inside the call).  The stop rule stays on the
     unpreconditioned residual; the coefficients are then those of M^-1/2 (K + noise_var I) M^-1/2, and info gains 'logdet_M'
-    and 'rank'."""
+    and 'rank'.
+    precision="mixed" (one stationary kernel, no lanczos, no preconditioner): iterative refinement -- an outer step solves
+    A d = r by the same loop on the fp32 product (kernel_matmul(precision="fp32")) until |r_inner| <= inner_tol |r|, then x += d
+    and r = b - A x with the fp64 product; a column stops by the same rule, on that fp64 residual.  If an outer step fails to halve
+    a column's residual, or after max_outer steps, the fp64 loop finishes the columns that are left.  max_iter and
+    info['iterations'] count inner iterations summed over the outer steps; info gains 'outer_iterations' [T], 'fp32_products',
+    'fp64_products' and 'fell_back' [T]."""
     import warnings
+    be._check_precision("kernel_cgsolver", precision, "solve", lanczos=lanczos, precond_rank=precond_rank)
     X = np.ascontiguousarray(X, dtype=settings.float_type)
-    prog = _matrix_free_program(kern, X.shape[1])
+    prog = _precision_program("kernel_cgsolver", kern, X.shape[1], precision)
     be._check_precond(precond_rank, precond_rel_tol, float(noise_var))
     kern._check_inputs(X)
-    if _is_sop(prog):
+    if precision == "mixed":
+        x, iters, rel, conv, outer, p32, p64, fell = be.kernel_cg_mixed(be.get_handle(), prog, X, B, noise_var, max_iter=max_iter,
+                                                                        tol=tol, inner_tol=inner_tol, max_outer=max_outer)
+        info = {"iterations": iters, "relative_residual": rel, "converged": conv, "outer_iterations": outer, "fp32_products": p32,
+                "fp64_products": p64, "fell_back": fell}
+    elif _is_sop(prog):
         if precond_rank:
             _precond_program(kern, X, precond_rank, precond_rel_tol, noise_var)      # (raises: no preconditioner for a composite kernel)
         res = be.kernel_cg_sop(be.get_handle(), prog, X, B, noise_var, max_iter=max_iter, tol=tol, lanczos=lanczos)

@@ -173,7 +173,7 @@ class GPR(GPModel):
         return lml, grads
 
     def compute_log_likelihood_and_gradients_iterative(self, num_probes=16, seed=0, probes=None, max_iter=1000, tol=1e-8,
-                                                       precond_rank=0):
+                                                       precond_rank=0, precision="fp64"):
         """(lml, grads) shaped like compute_log_likelihood_and_gradients, without the N x N matrix (Gardner et al. 2018; not in
         the reference).  One batched CG solve of [Y - m(X) | Z] gives alpha = K_y^-1 (Y - m), u_t = K_y^-1 z_t and each probe's
         Lanczos tridiagonal; then
@@ -185,8 +185,11 @@ class GPR(GPModel):
         falls as 1 / sqrt(T); the data-fit terms are exact to the solve's tolerance.  RuntimeError if a solve did not converge.
         precond_rank (1 .. 128): the solve preconditioned by the pivoted-Cholesky M = L L^T + noise I (csrc/pchol.hip), the probes
         z_t ~ N(0, M) formed on the device from standard normals of default_rng(seed) (``probes`` are taken as Z as they are);
-            log det K_y ~ log det M + mean_t (z_t^T M^-1 z_t) e_1^T log(T_t) e_1,   W = alpha alpha^T - R/T sum_t u_t (M^-1 z_t)^T."""
+            log det K_y ~ log det M + mean_t (z_t^T M^-1 z_t) e_1^T log(T_t) e_1,   W = alpha alpha^T - R/T sum_t u_t (M^-1 z_t)^T.
+        precision: "fp64" only -- the log-determinant needs the solve's Lanczos coefficients, which the mixed-precision loop does
+        not have; "mixed" is refused."""
         from .. import conjugate_gradient as cg
+        be._check_precision("compute_log_likelihood_and_gradients_iterative", precision, "solve", training=True)
         if self._has_features():
             raise NotImplementedError("the matrix-free (iterative) route is not available on the feature (random-feature) branch; "
                                       "it takes " + cg.MATRIX_FREE_SCOPE)
@@ -308,7 +311,8 @@ class GPR(GPModel):
             fvar = np.tile(np.reshape(var, (-1, 1)), [1, R])       # models/gpr.py:131
         return fmean, fvar
 
-    def predict_f_iterative(self, Xnew, max_iter=1000, tol=1e-8, precond_rank=0, variance="solve", variance_rank=64):
+    def predict_f_iterative(self, Xnew, max_iter=1000, tol=1e-8, precond_rank=0, variance="solve", variance_rank=64,
+                            precision="fp64", inner_tol=1e-4, max_outer=20):
         """predict_f without the N x N matrix (not in the reference): alpha = (K + s I)^-1 (Y - m(X)) by batched conjugate
         gradients on the fused kernel product, mean = K(Xnew, X) alpha + m(Xnew), var_j = Kdiag - k_j^T (K + s I)^-1 k_j sixteen
         test points to a solve.  Returns (mean [N*, R], var [N*, R]) like predict_f; device memory O(N (D + R + 16)) for the solves
@@ -319,13 +323,17 @@ class GPR(GPModel):
         variance="lanczos": the variances of all test points from one Lanczos run of variance_rank (1 .. 128, at most N) steps on
         K + s I (Pleiss et al. 2018; csrc/lanczos.hip) in place of N* / 16 solves: var_j = Kdiag - (Q^T k_j)^T T^-1 (Q^T k_j), which
         never falls below the exact variance and reaches it as the rank grows; variance_rank kernel products and one rectangular
-        product, device memory O(N (D + variance_rank)).  The mean is the same solve either way; no preconditioner with it."""
+        product, device memory O(N (D + variance_rank)).  The mean is the same solve either way; no preconditioner with it.
+        precision="mixed" (one stationary kernel, variance="solve", no preconditioner): the mean's solve and the variance's solves
+        by the mixed-precision loop of conjugate_gradient.kernel_cgsolver, with its inner_tol and max_outer."""
         import warnings
-        from ..conjugate_gradient import _matrix_free_program, MATRIX_FREE_SCOPE
+        from ..conjugate_gradient import _precision_program, MATRIX_FREE_SCOPE
+        be._check_precision("predict_f_iterative", precision, "solve", precond_rank=precond_rank,
+                            variance=variance if variance == "lanczos" else None)
         if self._has_features():
             raise NotImplementedError("predict_f_iterative is not available on the feature (random-feature) branch; it takes "
                                       + MATRIX_FREE_SCOPE)
-        prog = _matrix_free_program(self.kern, self.X.shape[1])
+        prog = _precision_program("predict_f_iterative", self.kern, self.X.shape[1], precision)
         Xnew = np.ascontiguousarray(Xnew, dtype=settings.float_type)
         self.kern._check_inputs(self.X, Xnew)
         noise = float(np.squeeze(self.likelihood.variance))
@@ -339,6 +347,9 @@ class GPR(GPModel):
             be._check_lanczos_rank(variance_rank, self.X.shape[0])
             mean, var, iters, rel, conv, _ = be.kernel_predict_lanczos(be.get_handle(), prog, self.X, noise, self._resid(), Xnew,
                                                                        variance_rank, max_iter=max_iter, tol=tol)
+        elif precision == "mixed":
+            mean, var, iters, rel, conv = be.kernel_predict_mixed(be.get_handle(), prog, self.X, noise, self._resid(), Xnew,
+                                                                  max_iter=max_iter, tol=tol, inner_tol=inner_tol, max_outer=max_outer)
         elif len(prog) > 1:                # a Sum of Products: gps_kernel_predict_sop, and no preconditioner
             if precond_rank:
                 from ..conjugate_gradient import _precond_program

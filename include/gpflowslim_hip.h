@@ -387,6 +387,33 @@ int gps_kernel_predict_sop(gps_handle_t h, const gps_kern_node_t* prog, int n_no
                            double noise_var, const double* resid, int64_t r, const double* Xnew, int64_t n_new, int max_iter,
                            double tol, double* mean_out, double* var_out, int64_t* iters_out, double* relres_out,
                            int* converged_out);
+/* ---- mixed precision on the same path (csrc/kmvm_f32.hip) ----
+ * prog: one primitive of the scope of gps_kmvm; anything else returns GPS_ERR_UNSUPPORTED before anything touches the device.
+ *
+ * gps_kmvm_f32: gps_kmvm with the dot products, the kernel's formula and the product with V in fp32 (the feature rows centred by
+ * the point sets' common mean in fp64 before they are rounded; each 64-column tile's share added into fp64 accumulators, so the
+ * error does not grow with n).  fp32-grade entries: about 1e-7 of sum_p |K_ip| |V_pt|.  Same arguments, equal bytes from call to call.
+ *
+ * gps_kernel_cg_mixed: gps_kernel_cg by iterative refinement -- x = 0, r = b; an outer step solves A d = r by the batched loop on the
+ * fp32 product until |r_inner| <= inner_tol |r| per column (0 < inner_tol < 1), then x += d and r = b - A x with the fp64 product.
+ * Column t is finished when |r_t| <= tol |b_t| on that fp64 residual.  If an outer step fails to halve a live column's fp64 residual,
+ * or after max_outer (>= 0) outer steps, the columns still live are finished by the fp64 loop on A d = r under gps_kernel_cg's own
+ * rule.  max_iter and iters_out [T] count inner iterations summed over the outer steps (one fp32 correction solve may spend half of
+ * what is left of max_iter); relres_out [T] = |r_t| / |b_t| of the fp64
+ * residual (of the recurrence for a column that fell back).  outer_out [T]: the outer steps the column was live in (0 for b_t = 0;
+ * the fp64 loop counts as one); products_out [2]: fp32 and fp64 products launched; fell_back_out [T]: 1 where the fp64 loop finished
+ * the column.                                                                                                                  */
+int gps_kmvm_f32(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, const double* X2, int64_t n2,
+                 int64_t d_all, const double* V, int64_t T, double diag_add, double* out);
+int gps_kernel_cg_mixed(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                        double noise_var, const double* B, int64_t T, int max_iter, double tol, double* x_out, int64_t* iters_out,
+                        double* relres_out, int* converged_out, double inner_tol, int max_outer, int64_t* outer_out,
+                        int64_t* products_out, int* fell_back_out);
+/* gps_kernel_predict with the mean's solve and the sixteen-at-a-time variance solves through the mixed loop.                     */
+int gps_kernel_predict_mixed(gps_handle_t h, const gps_kern_node_t* prog, int n_nodes, const double* X, int64_t n, int64_t d_all,
+                             double noise_var, const double* resid, int64_t r, const double* Xnew, int64_t n_new, int max_iter,
+                             double tol, double* mean_out, double* var_out, int64_t* iters_out, double* relres_out,
+                             int* converged_out, double inner_tol, int max_outer);
 /* ---- Lanczos variance estimates on the same product (Pleiss et al. 2018; csrc/lanczos.hip) ----
  * prog: one primitive of the scope of gps_kmvm, or (n_nodes > 1) a sum of products of the scope of gps_kmvm_sop.  rank_max is 1 .. 128
  * and at most n (GPS_ERR_ARG otherwise, before any device work).  Full reorthogonalisation (classical Gram-Schmidt, twice), all state

@@ -5,11 +5,16 @@ Up to n = 131072 a row "grad_form_C17" follows: one launch of the fused gradient
 kernels) for a general P Q^T of 17 columns -- one output and T = 16 probes, run doubled as 34 -> 36 weight columns --, beside the
 T = 16 product of the same process, and the ratio of the two medians.
 
-    python tools/kmvm_bench.py [--rank K] [--noise S] [--composite] [reps] [n ...]    (default: 5 repetitions at n = 32768, 131072, 1000000)
+    python tools/kmvm_bench.py [--rank K] [--noise S] [--composite] [--mixed] [reps] [n ...]    (default: 5 repetitions at n = 32768, 131072, 1000000)
 
 --composite: rows "sop_mauna_T*" and "sop_rbf_periodic_T*" per size up to n = 131072 as well -- one product of the sum-of-products
 kernel (csrc/kmvm_sop.hip) on the five-term Mauna-Loa form RBF + RBF.Periodic + RatQuad + RBF + White over the first column and on
 RBF.Periodic at D = 8, in kernel-matrix entries per second, and the ratio to the single RBF's product of the same T and process.
+
+--mixed: rows "f32_T1" / "f32_T16" per size -- the fp32 product (csrc/kmvm_f32.hip) timed in turn with the fp64 one, same process and
+operands, its kernel evaluations per second and the ratio of the medians -- and "solve_fp64_T16" / "solve_mixed_T16": one 16-column solve at
+--noise (tol 1e-8, at most 2000 iterations) by the fp64 loop and by the mixed-precision one, `reps` times each in turn: wall time, inner
+and outer iteration counts, the two product counts.
 
 --rank K (1 .. 128; with --noise, default 1e-2): a row "pcg_rankK" per size as well -- a 16-column solve (tol 1e-8, at most 2000
 iterations) plain and preconditioned by the rank-K pivoted-Cholesky M (csrc/pchol.hip): iteration counts and wall time of each, and
@@ -32,6 +37,9 @@ argv, opts = sys.argv[1:], {"--rank": 0, "--noise": 1e-2}
 composite = "--composite" in argv
 if composite:
     argv.remove("--composite")
+mixed = "--mixed" in argv
+if mixed:
+    argv.remove("--mixed")
 for flag in opts:
     if flag in argv:
         i = argv.index(flag)
@@ -67,6 +75,32 @@ for n in sizes:
         be.kmvm(h, prog, X, V, diag_add=0.1)                                     # warm-up: buffers, code objects
         ms = [device_ms(lambda: be.kmvm(h, prog, X, V, diag_add=0.1)) for _ in range(reps)]
         row["T%d" % T] = {"ms": stats(ms), "kernel_evals_per_s": float(n) * n / (1e-3 * float(np.median(ms)))}
+    if mixed:
+        for T in (1, 16):
+            V = rng.standard_normal((n, T))
+            be.kmvm_f32(h, prog, X, V, diag_add=0.1)                                 # warm-up
+            ms64, ms32 = [], []
+            for _ in range(reps):                                                    # the two versions alternate
+                ms64.append(device_ms(lambda: be.kmvm(h, prog, X, V, diag_add=0.1)))
+                ms32.append(device_ms(lambda: be.kmvm_f32(h, prog, X, V, diag_add=0.1)))
+            row["f32_T%d" % T] = {"ms": stats(ms32), "kernel_evals_per_s": float(n) * n / (1e-3 * float(np.median(ms32))),
+                                  "fp64_ms": stats(ms64), "fp64_over_fp32": float(np.median(ms64) / np.median(ms32))}
+        B = rng.standard_normal((n, 16))
+        solves = {"fp64": lambda: be.kernel_cg(h, prog, X, B, noise, max_iter=2000),
+                  "mixed": lambda: be.kernel_cg_mixed(h, prog, X, B, noise, max_iter=2000)}
+        walls = {name: [] for name in solves}
+        for name, call in solves.items():
+            call()                                                                   # warm-up
+        for _ in range(reps):
+            for name, call in solves.items():
+                t0 = time.perf_counter()
+                res = call()
+                walls[name].append(time.perf_counter() - t0)
+                row["solve_%s_T16" % name] = {"noise": noise, "tol": 1e-8, "wall_s": stats(walls[name]), "inner_iterations": int(np.max(res[1])),
+                                              "converged": bool(np.all(res[3]))}
+                if name == "mixed":
+                    row["solve_mixed_T16"].update(outer_iterations=int(np.max(res[4])), fp32_products=res[5], fp64_products=res[6],
+                                                  fell_back=bool(np.any(res[7])))
     if n <= 131072:
         P, Q = rng.standard_normal((n, 17)), rng.standard_normal((n, 17))
         be.kmvm_grad(h, prog, X, P, Q, 1 + d)                                    # warm-up
